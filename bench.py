@@ -4,7 +4,8 @@
 global-norm clip + Adam, + RCCL gradient all-reduce when N > 1), synthetic 16 kHz
 10 s utterances, random-init weights of the named topology.
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg3|cfg2]
+    python bench.py --gpus N --steps K --warmup W [--config cfg3|cfg2] [--full]
+                    [--dump-outputs DIR]
 
 Default workload: cfg3 (BASELINE.json configs[2], the configuration the north-star targets
 and the 1/2/4/8 scaling curve are quoted on: 5 x BiLSTM(512), 80 log-mel features, batch 64
@@ -15,11 +16,20 @@ and the explicit torchrun form run 8 ranks); rank 0 prints ONE JSON line.  A "st
 pass of the hot path over one mini-batch whose samples are already resident in HBM when
 the timed region starts.
 
+A plain run sets up, warms up, times the K steps and prints the line: the contract fields,
+`config`, `fallbacks` and the rooflines taken from the timed steps' own HIP events.  Every
+measurement that takes runs of its own -- the companion configurations, the gate-GEMM and
+CTC rooflines, predict latency, beam search, dataset build, the all-reduce bus bandwidth and
+the CPU baseline -- runs only with ``--full``.  ``--dump-outputs DIR`` writes what the last
+timed step computed (per-utterance CTC loss, greedy decode and its lengths, and a fixed,
+seeded sample of the updated parameters and of their gradients) as DIR/<name>.npy; the inputs
+depend on the arguments only, so two builds can be compared output for output.
+
 The ONE stdout line is small (< LINE_LIMIT bytes, tests/test_bench_launch.py): the contract
 fields, `config`, ONE `roofline` (the family with the largest share of GPU time, over ALL of
 its launches; the launches that own the chip are its `chip_owning` sub-object), `cpu_baseline`
 (the NumPy oracle port on this host's cores, bounded sample, N = 1 only), and compact
-{value, ms_per_step, frac} objects / scalars for the companion measurements:
+{value, ms_per_step, frac} objects / scalars for the companion measurements (``--full``):
   as_written        BASELINE.json configs[2] WITH its 2-conv front-end (own process),
   cfg2 / cfg2_n128  configs[1], and its topology at a chip-filling batch (own processes),
   exact_fp32        cfg3 again with every product on the exact-fp32 MFMA instructions,
@@ -351,7 +361,7 @@ def _sub_bench(config, env_extra, steps, warmup, dropout):
         env.pop(k, None)
     cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(steps),
            '--warmup', str(warmup), '--config', config, '--dropout', str(dropout),
-           '--no-cpu-baseline', '--no-extras', '--emit', 'detail']
+           '--full', '--no-cpu-baseline', '--no-extras', '--emit', 'detail']
     try:
         r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                            timeout=600, stdin=subprocess.DEVNULL)
@@ -531,9 +541,16 @@ def main():
     ap.add_argument('--config', default=os.environ.get('ASR_BENCH_CONFIG', 'cfg3'),
                     choices=sorted(CONFIGS))
     ap.add_argument('--dropout', type=float, default=0.2)      # brsmv1 default
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every measurement beyond the headline: companion '
+                         'configurations, gate-GEMM / CTC rooflines, predict latency, beam search, '
+                         'dataset build, all-reduce bandwidth, CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='with --full: skip the CPU baseline')
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip the cfg2 / exact-fp32 companion runs')
+                    help='with --full: skip the cfg2 / exact-fp32 companion runs')
     ap.add_argument('--emit', default='compact', choices=('compact', 'detail'),
                     help='stdout line: the compact line (default) or the full detail object '
                          '(what the companion runs hand to their parent)')
@@ -702,6 +719,8 @@ def main():
         ops.lstm_status(ops.WS.get(name, 0, dev))
     ctc = out[0].cpu().numpy()
     assert np.all(np.isfinite(ctc)), 'non-finite CTC loss in the benchmark step'
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model)
 
     extra = {'fallbacks': timeouts, 'ranks_seen_by_rccl': ranks_seen}
     # modelled cost of the step's ONE gradient all-reduce over xGMI at 8 ranks (7 links x ~153
@@ -713,7 +732,7 @@ def main():
         'recurrence fills the chip (ASR_AR_OVERLAP=auto), per-layer async beside BPTT otherwise',
         'ring_8gpu_ms': round(2.0 * 7 / 8 * gbytes / 77e9 * 1e3, 3),
         'direct_8gpu_ms': round(2.0 * 7 / 8 * gbytes / (7 * 77e9) * 1e3, 3)}
-    if world > 1:
+    if world > 1 and args.full:
         # ---- bus bandwidth of the gradient all-reduce (outside the timed region): the flat
         # fp32 gradient buffer, as one collective; bus = 2 (n-1)/n * bytes / time
         g = model._gbuf
@@ -739,7 +758,7 @@ def main():
             'bus_GBps': round(2.0 * (world - 1) / world * nbytes / (float(ar_ms.item()) * 1e-3) / 1e9, 2),
             'backend': 'rccl through the C ABI (asr_comm_allreduce_sum)', 'note': 'one fp32 all-reduce of the flat '
             'gradient buffer (+ the timeout-flag slots), exactly as the step issues it'}
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- secondary roofline figures (outside the timed region): the gate GEMM of
         # a middle layer and the CTC loss+gradient, each timed with HIP events
         T0 = 999
@@ -1004,7 +1023,7 @@ def main():
                         'time tap is kf / F_in dense (layer 1: 41 of 80 -> ~2x), cut by the '
                         'frequency blocks where the channel count allows (layer 2: ~1.3x), '
                         'so the pipes are busier than `frac` says'}
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             if args.config == 'cfg3':
                 line['cfg3_conv'] = _sub_bench('cfg3_conv', {}, args.steps, args.warmup, args.dropout)
                 # BASELINE.json configs[2] AS WRITTEN ("5xBiLSTM(512) + 2 conv front-end"): the
@@ -1034,7 +1053,7 @@ def main():
                 line['dataset_build'] = dataset_build(dev, feat)
             except Exception as e:
                 line['dataset_build'] = {'error': repr(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(cfg)
         if args.emit == 'detail':
             print(json.dumps(line))
@@ -1044,6 +1063,31 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+DUMP_SAMPLE = 1 << 20             # parameters / gradients sampled into the dump (4 MB each)
+
+
+def dump_outputs(path, out, model):
+    """What the last timed step handed its caller, as float32 .npy files: the per-utterance CTC
+    loss, the greedy decode (-1 padded) and its lengths, and the same DUMP_SAMPLE entries
+    (RandomState(0), sorted, distinct) of the updated flat parameters and of the step's
+    gradients; `sample_index` names those entries."""
+    os.makedirs(path, exist_ok=True)
+    ctc, dec, dlen = out
+    arrays = {'ctc_loss': ctc, 'greedy_decode': dec, 'greedy_decode_len': dlen}
+    n = model.n_params
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.unique(
+        np.random.RandomState(0).randint(0, n, size=DUMP_SAMPLE))
+    import torch
+    idx_d = torch.from_numpy(idx).to(model.params.device)
+    arrays['params_sample'] = model.params.index_select(0, idx_d)
+    arrays['grads_sample'] = model.grads.index_select(0, idx_d)
+    arrays['sample_index'] = torch.from_numpy(idx.astype(np.float64))
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy()
+        np.save(os.path.join(path, name + '.npy'),
+                a.astype(np.float64 if a.dtype == np.float64 else np.float32))
 
 
 def _cpu_stub(args, rank, world):

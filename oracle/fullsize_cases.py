@@ -18,6 +18,8 @@ compares the HIP path with those fixtures).  Everything here is a seeded recipe:
   ``RandomState(4242)`` (core/models.py:265-266 semantics: one mask per batch, shared over
   time, inverted scaling).
 """
+import os
+
 import numpy as np
 
 from . import frontend as OF
@@ -86,6 +88,42 @@ def grad_sample_index(i, size):
     if size <= GRAD_SAMPLES:
         return np.arange(size)
     return np.sort(rs.choice(size, GRAD_SAMPLES, replace=False))
+
+
+FIXTURE_PARTS = ('grads', 'states')   # side files of a fixture: each committed file < 1 MiB
+
+
+def _fixture_part(key):
+    if key[:2] in ('h_', 'c_'):
+        return 'states'
+    if key[0] == 'g' and key[1:3].isdigit():
+        return 'grads'
+    return None
+
+
+def save_fixture(golden_dir, name, fix):
+    """Writes fixture `name` as model_<name>.npz plus model_<name>_<part>.npz side files
+    (gradient probes, recurrent states): one file of a full-size case exceeds 1 MiB."""
+    parts = {None: {}}
+    parts.update((p, {}) for p in FIXTURE_PARTS)
+    for k, v in fix.items():
+        parts[_fixture_part(k)][k] = v
+    paths = []
+    for p, arrays in parts.items():
+        path = os.path.join(golden_dir, 'model_%s%s.npz' % (name, '' if p is None else '_' + p))
+        np.savez_compressed(path, **arrays)
+        paths.append(path)
+    return paths
+
+
+def load_fixture(golden_dir, name):
+    """The arrays save_fixture wrote for `name`, merged into one dict."""
+    fix = {}
+    for p in (None,) + FIXTURE_PARTS:
+        path = os.path.join(golden_dir, 'model_%s%s.npz' % (name, '' if p is None else '_' + p))
+        with np.load(path) as z:
+            fix.update((k, z[k]) for k in z.files)
+    return fix
 
 
 def build(name):

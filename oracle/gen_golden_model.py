@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Generate tests/golden/model_<case>.npz: the float64 oracle run ONCE at the benchmarked
+"""Generate tests/golden/model_<case>{,_grads,_states}.npz: the float64 oracle run ONCE at the benchmarked
 sizes (T = 999; cfg2 = 5 x BiLSTM(256), N = 32; cfg3 slice = 5 x BiLSTM(512), N = 16; the
 same slice behind the 2-conv front-end of configs[2], T' = 500), kept
 as compact fixtures so that the -m gpu suite can compare the HIP path element-wise at full
@@ -123,12 +123,12 @@ def run(name):
     idx, vals = FC.feature_probe(case['x'])
     fix['feat_probe'] = vals.astype(np.float32)
     fix['lens'] = case['lens']
-    path = os.path.join(OUT, 'model_%s.npz' % name)
-    np.savez_compressed(path, **fix)
+    paths = FC.save_fixture(OUT, name, fix)
     print('[%s] loss mean %.6f, min margin %.3e, frames with margin < 2e-4: %d, wrote %s '
           '(%.0f KB) in %.0f s' % (name, float(np.mean(out['ctc'])), float(fix['margin'].min()),
-                                    int((fix['margin'] < 2e-4).sum()), path,
-                                    os.path.getsize(path) / 1024.0, time.time() - t0), flush=True)
+                                    int((fix['margin'] < 2e-4).sum()), ' + '.join(paths),
+                                    sum(os.path.getsize(p) for p in paths) / 1024.0,
+                                    time.time() - t0), flush=True)
 
 
 if __name__ == '__main__':

@@ -190,3 +190,36 @@ def test_line_survives_failed_companions():
     assert len(json.dumps(line)) < bench.LINE_LIMIT
     assert line['cfg2'] == {'error': 'Traceback ' + 'x' * 107 + '...'}
     assert line['value'] == 15081.2 and line['roofline']['frac'] == 0.346
+
+
+# ---- --dump-outputs: what the last timed step computed, as float .npy files
+
+def test_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    import numpy as np
+    import torch
+    bench = _bench_module()
+
+    class Model:
+        n_params = 3 * bench.DUMP_SAMPLE
+        params = torch.arange(n_params, dtype=torch.float32)
+        grads = -params
+
+    ctc = torch.tensor([1.5, 2.5], dtype=torch.float32)
+    dec = torch.tensor([[3, 4, -1], [5, -1, -1]], dtype=torch.int32)
+    dlen = torch.tensor([2, 1], dtype=torch.int32)
+    files = {}
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), (ctc, dec, dlen), Model)
+        files[run] = {f[:-4]: np.load(str(tmp_path / run / f)) for f in os.listdir(str(tmp_path / run))}
+    got = files['a']
+    assert set(got) == {'ctc_loss', 'greedy_decode', 'greedy_decode_len', 'params_sample',
+                        'grads_sample', 'sample_index'}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert np.array_equal(got['ctc_loss'], [1.5, 2.5])
+    assert np.array_equal(got['greedy_decode'], dec.numpy()) and np.array_equal(got['greedy_decode_len'], [2, 1])
+    idx = got['sample_index'].astype(np.int64)
+    assert 0.8 * bench.DUMP_SAMPLE < idx.size <= bench.DUMP_SAMPLE and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got['params_sample'], idx) and np.array_equal(got['grads_sample'], -idx)
+    for k in got:                                 # a fixed sample: the same entries every run
+        assert np.array_equal(got[k], files['b'][k]), k

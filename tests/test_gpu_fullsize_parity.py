@@ -3,7 +3,7 @@ sizes (T = 999 frames; cfg2 = 5 x BiLSTM(256), N = 32, with and without dropout 
 ragged lengths; cfg3's topology 5 x BiLSTM(512) on a 16-utterance slice of its batch).
 
 The oracle ran once in the build container (oracle/gen_golden_model.py, minutes per case)
-and left compact fixtures in tests/golden/model_<case>.npz; the inputs are seeded recipes
+and left compact fixtures in tests/golden/model_<case>{,_grads,_states}.npz; the inputs are seeded recipes
 (oracle/fullsize_cases.py) rebuilt here.  Compared, under the DEFAULT arithmetic (split-fp16
 products) and under ASR_LSTM_PREC=0 ASR_GEMM_PREC=0 (exact fp32 MFMA):
 
@@ -65,7 +65,7 @@ def _engine_masks(case, model):
 def _check(name):
     from asr_study_amd import ops
     from asr_study_amd.core import ctc_utils, models
-    fix = np.load(os.path.join(GOLDEN, 'model_%s.npz' % name))
+    fix = FC.load_fixture(GOLDEN, name)
     case = FC.build(name)
     cfg, T = case['cfg'], case['T']
     N, F, H, L, C = cfg['N'], cfg['F'], cfg['H'], cfg['L'], cfg['C']

@@ -64,7 +64,7 @@ def test_two_rank_gradients_equal_the_single_rank_gradient_of_the_whole_batch():
 def test_bench_at_two_gpus_reports_both_ranks_and_a_measured_allreduce():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2',
-           '--warmup', '1', '--no-extras', '--no-cpu-baseline']
+           '--warmup', '1', '--full', '--no-extras', '--no-cpu-baseline']
     out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          timeout=560, stdin=subprocess.DEVNULL)
     assert out.returncode == 0, out.stderr.decode()[-3000:]

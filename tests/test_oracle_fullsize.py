@@ -15,7 +15,7 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 @pytest.mark.parametrize('name', sorted(FC.CASES))
 def test_fixture_matches_its_recipe(name):
-    fix = np.load(os.path.join(GOLDEN, 'model_%s.npz' % name))
+    fix = FC.load_fixture(GOLDEN, name)
     case = FC.build(name)
     cfg, T = case['cfg'], case['T']
     N, H, C, L = cfg['N'], cfg['H'], cfg['C'], cfg['L']

@@ -7,7 +7,7 @@ from oracle import lstm as OL
 from asr_study_amd import ops
 from asr_study_amd.core import models
 name = 'cfg2'
-fix = np.load('tests/golden/model_%s.npz' % name)
+fix = FC.load_fixture('tests/golden', name)
 case = FC.build(name)
 cfg, T = case['cfg'], case['T']
 N, F, H, L, C = cfg['N'], cfg['F'], cfg['H'], cfg['L'], cfg['C']

@@ -29,7 +29,7 @@ def worker(name):
     from asr_study_amd.core import models
     from oracle import fullsize_cases as FC
     from oracle import lstm as OL
-    fix = np.load(os.path.join(ROOT, 'tests', 'golden', 'model_%s.npz' % name))
+    fix = FC.load_fixture(os.path.join(ROOT, 'tests', 'golden'), name)
     case = FC.build(name)
     cfg, T = case['cfg'], case['T']
     N, F, H, L, C = cfg['N'], cfg['F'], cfg['H'], cfg['L'], cfg['C']
