@@ -106,12 +106,21 @@ class GateGemmArgs(C.Structure):
                 ('split_k', C.c_int), ('precision', C.c_int)]
 
 
+class RnnArgs(C.Structure):
+    _fields_ = [('T', C.c_int), ('n_pad', C.c_int), ('H', C.c_int), ('mode', C.c_int),
+                ('activation', C.c_int), ('clip', C.c_float),
+                ('U', void_p), ('mask_u', void_p), ('zx', void_p), ('h', void_p),
+                ('y_sum', void_p), ('dy', void_p), ('dy_ld', C.c_int),
+                ('dy_dir_stride', C.c_int), ('dz', void_p), ('db_part', void_p),
+                ('dz_absmax', void_p)]
+
+
 class Segment(C.Structure):
     _fields_ = [('offset', C.c_int64), ('len', C.c_int64), ('l2', C.c_float),
                 ('reserved', C.c_float)]
 
 
-ABI_VERSION = 106      # include/asr_hip.h ASR_HIP_ABI_VERSION: the struct layouts bound above
+ABI_VERSION = 107      # include/asr_hip.h ASR_HIP_ABI_VERSION: the struct layouts bound above
 
 # name -> (restype, argtypes); also the list the "exports every symbol" test walks
 SIGNATURES = {
@@ -197,6 +206,13 @@ SIGNATURES = {
     'asr_lstm_ln_workspace_bytes': (C.c_size_t, [C.POINTER(LstmLnArgs)]),
     'asr_lstm_ln_seq_fwd': (C.c_int, [C.POINTER(LstmLnArgs), void_p]),
     'asr_lstm_ln_seq_bwd': (C.c_int, [C.POINTER(LstmLnArgs), void_p, C.c_size_t, void_p]),
+    'asr_rnn_workspace_bytes': (C.c_size_t, [C.POINTER(RnnArgs), C.c_int]),
+    'asr_rnn_seq_fwd': (C.c_int, [C.POINTER(RnnArgs), void_p, C.c_size_t, void_p]),
+    'asr_rnn_seq_bwd': (C.c_int, [C.POINTER(RnnArgs), void_p, C.c_size_t, void_p]),
+    'asr_rnn_plan': (C.c_int, [C.POINTER(RnnArgs), C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
+    'asr_activation_fwd': (C.c_int, [void_p, void_p, C.c_int64, C.c_int, C.c_float, void_p]),
+    'asr_activation_bwd': (C.c_int, [void_p, void_p, void_p, C.c_int64, C.c_int, C.c_float,
+                                     void_p]),
     # operation-level entry points (csrc/roles.cpp)
     'asr_frontend_mfcc_batch': (C.c_int, [C.POINTER(FrontendCfg), void_p, void_p, void_p,
                                           c_int_p, C.c_int, C.c_int, void_p, void_p, void_p,

@@ -60,8 +60,12 @@ def keras_layers(model, weights):
     """[(layer name, [(weight name, array), ...])] in Keras-1.2.2 naming for the model's
     weight-bearing stages (get_weights() order); every array of ``weights`` is consumed."""
     it = iter(weights)
-    out, nb, nd, nc = [], 0, 0, 0
+    out, nb, nd, nc, ntd = [], 0, 0, 0, 0
     for s in model.stages:
+        # (Keras names a TimeDistributed layer by its own counter; the weight group of a Dense
+        # is named after the TimeDistributed around it)
+        if s.kind in ('act', 'dropout') and getattr(s, 'wrapped', False):
+            ntd += 1
         if s.kind == 'conv':        # keras.layers.Convolution2D: '<name>_W', '<name>_b'
             nc += 1
             out.append(('convolution2d_%d' % nc, [('convolution2d_%d_W:0' % nc, next(it)),
@@ -73,9 +77,17 @@ def keras_layers(model, weights):
                 for part in lstm_weight_parts(s):
                     ws.append(('%s_lstm_%d_%s:0' % (d, nb, part), next(it)))
             out.append(('bidirectional_%d' % nb, ws))
+        elif s.kind == 'birnn':     # Bidirectional(SimpleRNN): forward W, U, b, then backward
+            nb += 1
+            ws = []
+            for d in ('forward', 'backward'):
+                for part in LSTM_PARTS:
+                    ws.append(('%s_simplernn_%d_%s:0' % (d, nb, part), next(it)))
+            out.append(('bidirectional_%d' % nb, ws))
         elif s.kind == 'dense':
             nd += 1
-            out.append(('timedistributed_%d' % nd, [('dense_%d_W:0' % nd, next(it)),
+            ntd += 1
+            out.append(('timedistributed_%d' % ntd, [('dense_%d_W:0' % nd, next(it)),
                                                     ('dense_%d_b:0' % nd, next(it))]))
     rest = sum(1 for _ in it)
     if rest:

@@ -210,6 +210,7 @@ class Model(object):
             s.f_in, s.f_in_pad = f_real, f_pad
             if s.kind in ('noise', 'dropout'):
                 s.value = st['value']
+                s.wrapped = bool(st.get('wrapped', False))      # TimeDistributed(Dropout)
             elif s.kind == 'reshape':
                 s.target = [int(v) for v in st['target']]
             elif s.kind == 'conv':
@@ -231,7 +232,8 @@ class Model(object):
                                      '(asr_conv2d_* keeps one plane shift per time tap)' % s.kt)
                 if s.st < 1 or s.sf < 1:
                     raise ValueError('conv stage: strides must be >= 1')
-                if s.st > 1 and any(p.kind in ('dense', 'bilstm', 'conv') for p in self.stages):
+                if s.st > 1 and any(p.kind in ('dense', 'bilstm', 'conv', 'birnn')
+                                    for p in self.stages):
                     raise ValueError(
                         'conv stage with time stride %d behind a trainable stage: asr_conv2d_dgrad '
                         'exists for time stride 1 only, so a time-strided convolution must be the '
@@ -302,6 +304,35 @@ class Model(object):
                                    np.full(width, float(s.ln[1]), np.float32)]
                 init.append((s, 'bilstm', ws))
                 f_real, f_pad = 2 * s.H, 2 * s.Hp
+            elif s.kind == 'act':
+                s.act = st['activation']        # 'tanh' / 'relu' / 'linear' / clipped_relu()
+                s.wrapped = bool(st.get('wrapped', False))      # TimeDistributed(Activation)
+            elif s.kind == 'birnn':
+                # Bidirectional(SimpleRNN) (csrc/rnn.hip): W (in, 2, Hp), U (2, Hp, Hp), b (2, Hp)
+                s.H = st['H']
+                s.Hp = _pad4(s.H)
+                s.merge = st.get('merge_mode', 'concat')
+                s.act = st.get('activation') or 'tanh'
+                s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
+                s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
+                s.init = st.get('init', 'glorot_uniform')
+                s.oW = take(f_pad * 2 * s.Hp)
+                s.oU = take(2 * s.Hp * s.Hp)
+                s.ob = take(2 * s.Hp)
+                segs += [(s.oW, _pad4(f_pad * 2 * s.Hp), s.l2_W),
+                         (s.oU, _pad4(2 * s.Hp * s.Hp), s.l2_U), (s.ob, _pad4(2 * s.Hp), 0.0)]
+                ws = []
+                for _ in range(2):      # Keras 1.2.2 SimpleRNN.build: init, inner_init, zeros
+                    if s.init == 'he_normal':       # normal(0, sqrt(2 / fan_in)), not truncated
+                        W = rs.normal(0.0, math.sqrt(2.0 / f_real), size=(f_real, s.H))
+                    else:
+                        lim = math.sqrt(6.0 / (f_real + s.H))
+                        W = rs.uniform(-lim, lim, size=(f_real, s.H))
+                    u, _, v = np.linalg.svd(rs.normal(0.0, 1.0, (s.H, s.H)), full_matrices=False)
+                    ws += [W.astype(np.float32), (1.1 * u).astype(np.float32),
+                           np.zeros(s.H, np.float32)]
+                init.append((s, 'birnn', ws))
+                f_real, f_pad = (2 * s.H, 2 * s.Hp) if s.merge == 'concat' else (s.H, s.Hp)
             elif s.kind == 'merge':
                 s.mode, s.skip = st['mode'], int(st['skip'])
                 src = self.stages[s.skip]
@@ -318,6 +349,7 @@ class Model(object):
         self.packed = (_os.environ.get('ASR_GEMM_PREC', '1') != '0' and
                        (self._packed_mode == '1' or (self._packed_mode == 'auto' and widest >= 512)))
         self.num_classes = f_real
+        self._has_rnn = any(st.kind == 'birnn' for st in self.stages)
         self.time_strides = [st.st for st in self.stages if st.kind == 'conv' and st.st > 1]
         self._convs = {}
         self.n_params = off
@@ -341,9 +373,10 @@ class Model(object):
         for st in self.stages:
             if st is s:
                 break
-            if st.kind in ('dense', 'bilstm', 'conv'):
+            if st.kind in ('dense', 'bilstm', 'conv', 'birnn'):
                 prev = st
-        if prev is not None and prev.kind == 'bilstm' and prev.Hp != prev.H:
+        if (prev is not None and prev.kind in ('bilstm', 'birnn') and prev.Hp != prev.H
+                and getattr(prev, 'merge', 'concat') == 'concat'):
             idx = np.concatenate([np.arange(prev.H), prev.Hp + np.arange(prev.H)])
         else:
             idx = np.arange(s.f_in)
@@ -401,6 +434,20 @@ class Model(object):
                     host[s.ob:s.ob + bp.size] = bp.ravel()
                 else:
                     host[s.omi:s.omi + mip.size] = mip.ravel()
+            elif s.kind == 'birnn':
+                rows = self._real_rows(s)
+                Wp = np.zeros((s.f_in_pad, 2, s.Hp), np.float32)
+                Up = np.zeros((2, s.Hp, s.Hp), np.float32)
+                bp = np.zeros((2, s.Hp), np.float32)
+                for d in range(2):          # Keras order: forward W, U, b, then backward
+                    W, U, b = [np.asarray(next(it), np.float32) for _ in range(3)]
+                    assert W.shape == (len(rows), s.H) and U.shape == (s.H, s.H), (W.shape, U.shape)
+                    Wp[rows, d, :s.H] = W
+                    Up[d, :s.H, :s.H] = U
+                    bp[d, :s.H] = b
+                host[s.oW:s.oW + Wp.size] = Wp.ravel()
+                host[s.oU:s.oU + Up.size] = Up.ravel()
+                host[s.ob:s.ob + bp.size] = bp.ravel()
         self.params.copy_(torch.from_numpy(host))
         self._weights_epoch += 1        # (bounds measured under the old weights are dropped)
 
@@ -438,6 +485,14 @@ class Model(object):
                         out += [_um2gm(cp[d, (16 + 4 * k) * H:(20 + 4 * k) * H], H, H)
                                 for k in range(4)]
                         out += [cp[d, 32 * H:33 * H].copy(), cp[d, 33 * H:34 * H].copy()]
+            elif s.kind == 'birnn':
+                rows = self._real_rows(s)
+                Wp = flat[s.oW:s.oW + s.f_in_pad * 2 * s.Hp].reshape(s.f_in_pad, 2, s.Hp)
+                Up = flat[s.oU:s.oU + 2 * s.Hp * s.Hp].reshape(2, s.Hp, s.Hp)
+                bp = flat[s.ob:s.ob + 2 * s.Hp].reshape(2, s.Hp)
+                for d in range(2):
+                    out += [Wp[rows, d, :s.H].copy(), Up[d, :s.H, :s.H].copy(),
+                            bp[d, :s.H].copy()]
         return out
 
     def get_weights(self):
@@ -772,9 +827,84 @@ class Model(object):
                         n_valid=n_valid if not need_grad else 0, **var)
                 rec.update(y=y, cell=cell, gates=gates)
                 a = y
+            elif s.kind == 'act':
+                out = self._buf('act%d' % si, a.shape)
+                a = ops.activation_fwd(a.contiguous(), out, s.act)
+            elif s.kind == 'birnn':
+                Hp = s.Hp
+                BW, BU = stage_masks(si)[:2]
+                rec['BW'], rec['BU'] = BW, BU
+                zx = self._buf('rzx%d' % si, (T, n_pad, 2, Hp))
+                self._rnn_input_gemm(a.contiguous(), s, zx, BW, rows, n_pad)
+                h = self._buf('rh%d' % si, (T, n_pad, 2, Hp))
+                ysum = self._buf('rsum%d' % si, (T, n_pad, Hp)) if s.merge == 'sum' else None
+                rec['ws'] = ops.rnn_seq_fwd(zx, self._view(s.oU, 2 * Hp * Hp), h, T, n_pad, Hp,
+                                            act=s.act, mask_u=BU, y_sum=ysum, mode=self.lstm_mode)
+                rec['h'] = h
+                a = ysum if ysum is not None else h.view(T, n_pad, 2 * Hp)
             rec['out'] = a
             self._acts.append(rec)
         return a
+
+    def _rnn_input_gemm(self, a, s, zx, BW, rows, n_pad):
+        """zx = (a (.) B_W[d]) @ W_d + b_d of a SimpleRNN stage, both directions."""
+        Hp = s.Hp
+        bias = self._view(s.ob, 2 * Hp)
+        if BW is None:
+            ops.gemm(a, self.params, zx, rows, 2 * Hp, s.f_in_pad, b_off=s.oW, bias=bias)
+            return
+        for d in range(2):
+            ops.gemm(a, self.params, zx, rows, Hp, s.f_in_pad, ldb=2 * Hp, ldc=2 * Hp,
+                     b_off=s.oW + d * Hp, c_off=d * Hp, bias=bias[d * Hp:(d + 1) * Hp],
+                     a_scale=BW[d], a_scale_period=n_pad)
+
+    def _rnn_backward(self, s, si, rec, da, first, split):
+        """BPTT of a SimpleRNN stage (csrc/rnn.hip), then its weight gradients and dx from the
+        GEMMs: dU[d] = (h_prev (.) B_U)^T dz_d, dW[d] = (x (.) B_W)^T dz_d, db from BPTT's
+        per-batch-tile sums, dx = sum_d B_W[d] (.) (dz_d @ W_d^T).  Returns dx (or None)."""
+        T, n_pad = da.shape[0], da.shape[1]
+        rows, Hp = T * n_pad, s.Hp
+        BW, BU, h, a_in = rec['BW'], rec['BU'], rec['h'], rec['in']
+        dz = self._buf('rdz%d' % si, (T, n_pad, 2, Hp))
+        dbp = self._buf('rdbp%d' % si, (n_pad // 16, 2, Hp))
+        zmx = self._buf('rdzmax%d' % si, (1,))
+        rec['ws_b'] = ops.rnn_seq_bwd(da.contiguous(), self._view(s.oU, 2 * Hp * Hp), h, dz, T,
+                                      n_pad, Hp, act=s.act, mask_u=BU,
+                                      shared_dy=s.merge == 'sum', mode=self.lstm_mode,
+                                      db_part=dbp, dz_absmax=zmx)
+        ops.colsum(dbp, n_pad // 16, 2 * Hp, 2 * Hp, self._gview(s.ob, 2 * Hp))
+        kk = (T - 1) * n_pad
+        for d in range(2):
+            # h_prev is h one frame earlier in the direction's processing order
+            if kk > 0:
+                ops.gemm(h, dz, self.grads, Hp, Hp, kk, trans_a=True, lda=2 * Hp, ldb=2 * Hp,
+                         ldc=Hp, a_off=d * Hp + (0 if d == 0 else n_pad * 2 * Hp),
+                         b_off=d * Hp + (n_pad * 2 * Hp if d == 0 else 0),
+                         c_off=s.oU + d * Hp * Hp, split_k=split,
+                         a_scale=None if BU is None else BU[d], a_scale_period=n_pad,
+                         b_absmax=zmx)
+            else:
+                self._gview(s.oU + d * Hp * Hp, Hp * Hp).zero_()
+        if BW is None:
+            ops.gemm(a_in, dz, self.grads, s.f_in_pad, 2 * Hp, rows, trans_a=True, c_off=s.oW,
+                     split_k=split, b_absmax=zmx)
+        else:
+            for d in range(2):
+                ops.gemm(a_in, dz, self.grads, s.f_in_pad, Hp, rows, trans_a=True, ldb=2 * Hp,
+                         ldc=2 * Hp, b_off=d * Hp, c_off=s.oW + d * Hp, split_k=split,
+                         a_scale=BW[d], a_scale_period=n_pad, b_absmax=zmx)
+        if first:
+            return None
+        dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
+        if BW is None:
+            ops.gemm(dz, self.params, dx, rows, s.f_in_pad, 2 * Hp, trans_b=True, b_off=s.oW,
+                     a_absmax=zmx)
+        else:
+            for d in range(2):
+                ops.gemm(dz, self.params, dx, rows, s.f_in_pad, Hp, trans_b=True, lda=2 * Hp,
+                         ldb=2 * Hp, a_off=d * Hp, b_off=s.oW + d * Hp, c_scale=BW[d],
+                         c_scale_period=n_pad, beta=0.0 if d == 0 else 1.0, a_absmax=zmx)
+        return dx
 
     def _clip_bound(self, si):
         """1-element device tensor >= max|input of stage si| when that input is a clipped-ReLU
@@ -953,7 +1083,7 @@ class Model(object):
         stream id 4 * stage (B_W) / 4 * stage + 1 (B_U) at step self._step."""
         out = {}
         for si, s in enumerate(self.stages):
-            if s.kind != 'bilstm' or not (s.dropout_W > 0 or s.dropout_U > 0):
+            if s.kind not in ('bilstm', 'birnn') or not (s.dropout_W > 0 or s.dropout_U > 0):
                 continue
             BW = self._buf('BW%d' % si, (2, n_pad, s.f_in_pad))
             BU = self._buf('BU%d' % si, (2, n_pad, s.Hp))
@@ -1046,7 +1176,8 @@ class Model(object):
                     da = ops.axpby(s.coef, da, 0.0, da, self._buf('dmerge%d' % si, da.shape))
                 skip_grads[s.skip] = da
                 continue
-            first = not any(st.kind in ('dense', 'bilstm', 'conv') for st in self.stages[:si])
+            first = not any(st.kind in ('dense', 'bilstm', 'conv', 'birnn')
+                            for st in self.stages[:si])
             if s.kind in ('noise', 'reshape'):
                 continue
             if s.kind == 'conv':
@@ -1063,6 +1194,16 @@ class Model(object):
                 op.wgrad(a_in, da, z, self._gview(s.oW, nw), self._gview(s.ob, s.C_out),
                          reuse_x=True, reuse_dz=dz_ready)
                 if not first:
+                    da = dx
+                continue
+            if s.kind == 'act':
+                if not first:
+                    da = ops.activation_bwd(da.contiguous(), rec['out'],
+                                            self._buf('dact%d' % si, da.shape), s.act)
+                continue
+            if s.kind == 'birnn':
+                dx = self._rnn_backward(s, si, rec, da, first, split)
+                if dx is not None:
                     da = dx
                 continue
             if s.kind == 'dropout':
@@ -1456,7 +1597,9 @@ class Model(object):
         """What the optimiser's guard looks at: data parallel, the all-reduced flag slots
         (non-zero on EVERY rank when any rank timed out, so all ranks skip the same update);
         single process, None = the workspaces' own sticky words."""
-        return self._gbuf[self.n_params:self.n_params + 2] if self._dist_active() else None
+        # (slots 2, 3: the SimpleRNN workspaces' flags, ops.collect_timeout_flags)
+        n = 4 if getattr(self, '_has_rnn', False) else 2
+        return self._gbuf[self.n_params:self.n_params + n] if self._dist_active() else None
 
     def _flag_snapshot(self):
         v = self.veto_flags()

@@ -9,6 +9,8 @@ HIP engine (core/engine.py) executes.  ``LSTM`` keeps the reference override's
 signature (core/layers.py:366-386: zoneout_h/zoneout_c/layer_norm/mi on top of the
 Keras LSTM arguments); of the optional variants the residual ``merge``, multiplicative
 integration, zoneout and layer normalisation are implemented.
+``SimpleRNN`` (Bidirectional, 'concat' or 'sum'), ``Activation`` and ``recurrent()`` serve the
+maas / deep_speech factories (core/models.py).
 """
 
 
@@ -79,14 +81,19 @@ class Dense(object):
 
 
 class TimeDistributed(Layer):
-    """TimeDistributed(Dense(n)): a row-wise affine map (core/models.py:278-279)."""
+    """TimeDistributed(Dense(n)): a row-wise affine map (core/models.py:278-279);
+    TimeDistributed(Activation(...)) and TimeDistributed(Dropout(p)) act per element, exactly as
+    the bare layers do (the Deep Speech factories wrap both)."""
 
     def __init__(self, layer):
-        assert isinstance(layer, Dense)
-        self.dense = layer
+        if not isinstance(layer, (Dense, Activation, Dropout)):
+            raise NotImplementedError('TimeDistributed(%s): Dense, Activation or Dropout only'
+                                      % type(layer).__name__)
+        self.dense = layer if isinstance(layer, Dense) else None
+        self.layer = layer
 
     def out_features(self, f):
-        return self.dense.output_dim
+        return self.dense.output_dim if self.dense is not None else f
 
 
 class LSTM(object):
@@ -129,17 +136,79 @@ class LSTM(object):
         self.l2_U = U_regularizer.l2 if U_regularizer is not None else 0.0
 
 
+class SimpleRNN(object):
+    """keras.layers.SimpleRNN (Keras 1.2.2): h_t = act(x_t W + b + h_{t-1} U), h_0 = 0.
+
+    init: 'glorot_uniform' (default) or 'he_normal' (normal(0, sqrt(2 / fan_in)), not
+    truncated); inner_init: 'orthogonal' (x 1.1, as the LSTM's U); b = 0.  activation: 'tanh',
+    'relu', 'linear' or ``clipped_relu(max_value)``.  dropout_W / dropout_U: variational
+    inverted-dropout masks per (sample, feature), drawn once per sequence and direction.
+    Runs on csrc/rnn.hip; only return_sequences=True."""
+
+    def __init__(self, output_dim, init='glorot_uniform', inner_init='orthogonal',
+                 activation='tanh', W_regularizer=None, U_regularizer=None, b_regularizer=None,
+                 dropout_W=0., dropout_U=0., return_sequences=True, **kwargs):
+        if init not in ('glorot_uniform', 'he_normal'):
+            raise NotImplementedError('SimpleRNN init %r (implemented: glorot_uniform, he_normal)'
+                                      % (init,))
+        if inner_init != 'orthogonal':
+            raise NotImplementedError('SimpleRNN inner_init %r (implemented: orthogonal)'
+                                      % (inner_init,))
+        if b_regularizer is not None:
+            raise NotImplementedError('SimpleRNN b_regularizer')
+        if not return_sequences:
+            raise NotImplementedError('return_sequences=False')
+        from .. import ops
+        ops.rnn_activation_id(activation)           # NotImplementedError for anything else
+        self.activation = activation
+        self.init, self.inner_init = init, inner_init
+        self.output_dim = int(output_dim)
+        self.dropout_W = float(dropout_W or 0.0)
+        self.dropout_U = float(dropout_U or 0.0)
+        self.l2_W = W_regularizer.l2 if W_regularizer is not None else 0.0
+        self.l2_U = U_regularizer.l2 if U_regularizer is not None else 0.0
+
+
+class Activation(Layer):
+    """keras.layers.Activation: 'tanh', 'relu', 'linear' or ``clipped_relu(max_value)``,
+    element-wise (bare or inside TimeDistributed)."""
+
+    def __init__(self, activation):
+        from .. import ops
+        ops.rnn_activation_id(activation)           # NotImplementedError for anything else
+        self.activation = activation
+
+
+def recurrent(output_dim, model='keras_lstm', activation='tanh', regularizer=None, dropout=0.,
+              **kwargs):
+    """The reference's recurrent-layer factory (core/layers.py:482-516): 'rnn' -> SimpleRNN,
+    'lstm' / 'keras_lstm' -> LSTM, with W and U regularised by ``regularizer`` and dropout_W =
+    dropout_U = ``dropout``; 'gru' and 'rhn' are not implemented."""
+    if model in ('gru', 'rhn'):
+        raise NotImplementedError('recurrent(model=%r): only rnn, lstm, keras_lstm' % (model,))
+    common = dict(W_regularizer=regularizer, U_regularizer=regularizer, dropout_W=dropout,
+                  dropout_U=dropout, activation=activation, return_sequences=True)
+    if model == 'rnn':
+        return SimpleRNN(output_dim, **dict(common, **kwargs))
+    if model in ('lstm', 'keras_lstm'):
+        return LSTM(output_dim, **dict(common, **kwargs))
+    raise ValueError('recurrent(model=%r): unknown model' % (model,))
+
+
 class Bidirectional(Layer):
-    """keras.layers.Bidirectional(merge_mode='concat')."""
+    """keras.layers.Bidirectional: LSTM with merge_mode='concat'; SimpleRNN with 'concat'
+    ([h_f | h_b]) or 'sum' (h_f + h_b)."""
 
     def __init__(self, layer, merge_mode='concat'):
-        assert isinstance(layer, LSTM)
-        if merge_mode != 'concat':
+        assert isinstance(layer, (LSTM, SimpleRNN))
+        allowed = ('concat', 'sum') if isinstance(layer, SimpleRNN) else ('concat',)
+        if merge_mode not in allowed:
             raise NotImplementedError('merge_mode=%r' % merge_mode)
         self.lstm = layer
+        self.merge_mode = merge_mode
 
     def out_features(self, f):
-        return 2 * self.lstm.output_dim
+        return (2 if self.merge_mode == 'concat' else 1) * self.lstm.output_dim
 
 
 class Merge(Layer):

@@ -1,17 +1,20 @@
 """Model factories with the reference's names and hyper-parameters
-(core/models.py): ``ctc_model``, ``graves2006``, ``eyben``, ``brsmv1``.
+(core/models.py): ``ctc_model``, ``graves2006``, ``eyben``, ``maas``, ``deep_speech``,
+``brsmv1``, plus this build's ``deep_speech2``.
 
 ``train.py`` resolves them by name -- ``get_from_module('core.models', 'brsmv1')
 (**hparams)`` (train.py:127-129) -- and gets back an object with the Keras
 ``compile / fit_generator / evaluate_generator / metrics_names / optimizer.lr``
 surface; here that object is core.engine.Model, which runs on the HIP kernels.
-``maas`` and ``deep_speech`` reference un-imported Keras names in the reference
-(NameError at call time) and are not provided.
+``maas`` and ``deep_speech`` are dead code in the reference (they use ``Activation`` and
+``SimpleRNN`` without importing them); here they run on the SimpleRNN kernels of csrc/rnn.hip
+with the reference's signatures, defaults and layer sequence.
 """
 from . import ctc_utils
 from .engine import Model
 from .layers import (Input, GaussianNoise, TimeDistributed, Dense, LSTM, Bidirectional,
-                     Dropout, Merge, merge, l2, Reshape, Convolution2D, clipped_relu)
+                     Dropout, Merge, merge, l2, Reshape, Convolution2D, clipped_relu, SimpleRNN,
+                     Activation)
 
 
 def ctc_model(inputs, output, **kwargs):
@@ -48,10 +51,17 @@ def ctc_model(inputs, output, **kwargs):
                          'st': layer.st, 'sf': layer.sf, 'clip': layer.clip, 'l2': layer.l2})
         elif isinstance(layer, GaussianNoise):
             spec.append({'type': 'noise', 'value': layer.sigma})
-        elif isinstance(layer, Dropout):
-            spec.append({'type': 'dropout', 'value': layer.p})
+        elif isinstance(layer, TimeDistributed) and layer.dense is None:
+            spec.append(_elementwise_spec(layer.layer, wrapped=True))
+        elif isinstance(layer, (Dropout, Activation)):
+            spec.append(_elementwise_spec(layer))
         elif isinstance(layer, TimeDistributed):
             spec.append({'type': 'dense', 'n_out': layer.dense.output_dim, 'l2': layer.dense.l2})
+        elif isinstance(layer, Bidirectional) and isinstance(layer.lstm, SimpleRNN):
+            r = layer.lstm
+            spec.append({'type': 'birnn', 'H': r.output_dim, 'merge_mode': layer.merge_mode,
+                         'activation': r.activation, 'init': r.init, 'dropout_W': r.dropout_W,
+                         'dropout_U': r.dropout_U, 'l2_W': r.l2_W, 'l2_U': r.l2_U})
         elif isinstance(layer, Bidirectional):
             r = layer.lstm
             spec.append({'type': 'bilstm', 'H': r.output_dim, 'dropout_W': r.dropout_W,
@@ -66,6 +76,14 @@ def ctc_model(inputs, output, **kwargs):
                                                 if k in ('is_greedy', 'beam_width',
                                                          'merge_repeated', 'top_paths')})
     return model
+
+
+def _elementwise_spec(layer, wrapped=False):
+    """Dropout / Activation, bare or inside TimeDistributed (``wrapped``: kept for the Keras
+    config writer; the arithmetic is the same)."""
+    if isinstance(layer, Dropout):
+        return {'type': 'dropout', 'value': layer.p, 'wrapped': wrapped}
+    return {'type': 'act', 'activation': layer.activation, 'wrapped': wrapped}
 
 
 def graves2006(num_features=26, num_hiddens=100, num_classes=28, std=.6, **kw):
@@ -96,6 +114,56 @@ def eyben(num_features=39, num_hiddens=[78, 120, 27], num_classes=28, **kw):
     model = ctc_model(x, o, **kw)
     model.config = {'name': 'eyben', 'kwargs': dict(
         num_features=num_features, num_hiddens=list(num_hiddens), num_classes=num_classes)}
+    return model
+
+
+def maas(num_features=81, num_classes=29, num_hiddens=1824, dropout=0.1, max_value=20, **kw):
+    """Maas et al. 2015, "Lexicon-free conversational speech recognition with neural networks"
+    (core/models.py:106-145): two clipped-ReLU Dense layers, a summed Bidirectional SimpleRNN
+    with input dropout, two more clipped-ReLU Dense layers, the output Dense."""
+    x = Input(name='inputs', shape=(None, num_features))
+    act = clipped_relu(max_value)
+    o = x
+    for _ in range(2):
+        o = TimeDistributed(Dense(num_hiddens))(o)
+        o = TimeDistributed(Activation(act))(o)
+    o = Bidirectional(SimpleRNN(num_hiddens, return_sequences=True, dropout_W=dropout,
+                                activation=act, init='he_normal'), merge_mode='sum')(o)
+    for _ in range(2):
+        o = TimeDistributed(Dense(num_hiddens))(o)
+        o = TimeDistributed(Activation(act))(o)
+    o = TimeDistributed(Dense(num_classes))(o)
+    model = ctc_model(x, o, **kw)
+    model.config = {'name': 'maas', 'kwargs': dict(
+        num_features=num_features, num_classes=num_classes, num_hiddens=num_hiddens,
+        dropout=dropout, max_value=max_value)}
+    return model
+
+
+def deep_speech(num_features=81, num_classes=29, num_hiddens=2048, dropout=0.1, max_value=20,
+                **kw):
+    """Hannun et al. 2014, "Deep Speech: scaling up end-to-end speech recognition"
+    (core/models.py:148-214): three clipped-ReLU Dense layers with dropout, a summed
+    Bidirectional SimpleRNN with input dropout and dropout behind it, one more clipped-ReLU
+    Dense layer with dropout, the output Dense."""
+    x = Input(name='inputs', shape=(None, num_features))
+    act = clipped_relu(max_value)
+    o = x
+    for _ in range(3):
+        o = TimeDistributed(Dense(num_hiddens))(o)
+        o = TimeDistributed(Activation(act))(o)
+        o = TimeDistributed(Dropout(dropout))(o)
+    o = Bidirectional(SimpleRNN(num_hiddens, return_sequences=True, dropout_W=dropout,
+                                activation=act, init='he_normal'), merge_mode='sum')(o)
+    o = TimeDistributed(Dropout(dropout))(o)
+    o = TimeDistributed(Dense(num_hiddens))(o)
+    o = TimeDistributed(Activation(act))(o)
+    o = TimeDistributed(Dropout(dropout))(o)
+    o = TimeDistributed(Dense(num_classes))(o)
+    model = ctc_model(x, o, **kw)
+    model.config = {'name': 'deep_speech', 'kwargs': dict(
+        num_features=num_features, num_classes=num_classes, num_hiddens=num_hiddens,
+        dropout=dropout, max_value=max_value)}
     return model
 
 

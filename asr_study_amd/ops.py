@@ -278,6 +278,108 @@ def lstm_seq_bwd(dy, U, cell, gates, dz, T, n_pad, H, mask_u=None, mode=0, check
     return ws
 
 
+# --------------------------------------------------------------------------- SimpleRNN (K14)
+# asr_rnn_args.activation: the SimpleRNN / Activation names this build runs
+RNN_ACTIVATIONS = {'tanh': 0, 'relu': 1, 'linear': 4, 'clipped_relu': 7}
+RNN_WS = ('rnn_fwd', 'rnn_bwd')     # workspaces: sticky timeout word in their first bytes
+
+
+def _rnn_ran(device):
+    return (RNN_WS[0], str(device)) in WS.bufs or (RNN_WS[1], str(device)) in WS.bufs
+
+
+def rnn_activation_id(act):
+    """'tanh' / 'relu' / 'linear' / ('clipped_relu', max_value) -> (id, clip)."""
+    if isinstance(act, (tuple, list)) and act and act[0] == 'clipped_relu':
+        return RNN_ACTIVATIONS['clipped_relu'], float(act[1])
+    try:
+        return RNN_ACTIVATIONS[act or 'tanh'], 0.0
+    except (KeyError, TypeError):
+        raise NotImplementedError('activation %r (implemented: tanh, relu, linear, clipped_relu)'
+                                  % (act,))
+
+
+def _rnn_args(T, n_pad, H, U, act, mode, mask_u=None):
+    a = L.RnnArgs()
+    a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
+    a.activation, a.clip = rnn_activation_id(act)
+    a.U = U.data_ptr()
+    a.mask_u = mask_u.data_ptr() if mask_u is not None else None
+    return a
+
+
+def rnn_seq_fwd(zx, U, h, T, n_pad, H, act='tanh', mask_u=None, y_sum=None, mode=0, check=False):
+    """Both directions of a SimpleRNN layer: h (T, n_pad, 2, H) from zx = x@W + b (same shape),
+    U (2, H, H), optional B_U (2, n_pad, H); y_sum (T, n_pad, H) <- h_f + h_b when given.
+    mode: 0 = the library's form, 1 = stepwise, 2 = persistent."""
+    lib = L.load()
+    _check_f32(zx, U, h, mask_u, y_sum)
+    a = _rnn_args(T, n_pad, H, U, act, mode, mask_u)
+    a.zx, a.h = zx.data_ptr(), h.data_ptr()
+    a.y_sum = y_sum.data_ptr() if y_sum is not None else None
+    nbytes = lib.asr_rnn_workspace_bytes(C.byref(a), 0)
+    if nbytes == 0:
+        L.check(-1, 'asr_rnn_workspace_bytes')
+    ws = WS.get(RNN_WS[0], nbytes, zx.device)
+    L.check(lib.asr_rnn_seq_fwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_rnn_seq_fwd')
+    if check:
+        L.check(lib.asr_lstm_status(_ptr(ws), _stream()), 'asr_rnn status (fwd)')
+    return ws
+
+
+def rnn_seq_bwd(dy, U, h, dz, T, n_pad, H, act='tanh', mask_u=None, shared_dy=False, mode=0,
+                db_part=None, dz_absmax=None, check=False):
+    """BPTT of both directions: dz (T, n_pad, 2, H) = d loss / d pre-activation.  dy is the
+    gradient of the layer output: (T, n_pad, 2H) for 'concat', (T, n_pad, H) shared by both
+    directions for 'sum' (shared_dy).  db_part (n_pad/16, 2, H): per-batch-tile sums of dz;
+    dz_absmax (1,): max |dz|."""
+    lib = L.load()
+    _check_f32(dy, U, h, dz, mask_u, db_part, dz_absmax)
+    a = _rnn_args(T, n_pad, H, U, act, mode, mask_u)
+    a.h, a.dy, a.dz = h.data_ptr(), dy.data_ptr(), dz.data_ptr()
+    a.dy_ld, a.dy_dir_stride = (int(H), 0) if shared_dy else (2 * int(H), int(H))
+    a.db_part = db_part.data_ptr() if db_part is not None else None
+    a.dz_absmax = dz_absmax.data_ptr() if dz_absmax is not None else None
+    nbytes = lib.asr_rnn_workspace_bytes(C.byref(a), 1)
+    if nbytes == 0:
+        L.check(-1, 'asr_rnn_workspace_bytes')
+    ws = WS.get(RNN_WS[1], nbytes, dy.device)
+    L.check(lib.asr_rnn_seq_bwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_rnn_seq_bwd')
+    if check:
+        L.check(lib.asr_lstm_status(_ptr(ws), _stream()), 'asr_rnn status (bwd)')
+    return ws
+
+
+def rnn_plan(T, n_pad, H, backward=False, mode=0):
+    """{'persistent': bool, 'rows': batch rows, 'units': units per workgroup, 'blocks':
+    workgroups per launch} of the form the library would run (asr_rnn_plan)."""
+    a = L.RnnArgs()
+    a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
+    per, rows, units, blocks = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    L.check(L.load().asr_rnn_plan(C.byref(a), int(bool(backward)), C.byref(per), C.byref(rows),
+                                  C.byref(units), C.byref(blocks)), 'asr_rnn_plan')
+    return {'persistent': bool(per.value), 'rows': rows.value, 'units': units.value,
+            'blocks': blocks.value}
+
+
+def activation_fwd(x, y, act):
+    """y = act(x), element-wise (the Activation layer)."""
+    _check_f32(x, y)
+    aid, clip = rnn_activation_id(act)
+    L.check(L.load().asr_activation_fwd(_ptr(x), _ptr(y), x.numel(), aid, clip, _stream()),
+            'asr_activation_fwd')
+    return y
+
+
+def activation_bwd(dy, y, dx, act):
+    """dx = dy (.) act'(y), the derivative read from the output."""
+    _check_f32(dy, y, dx)
+    aid, clip = rnn_activation_id(act)
+    L.check(L.load().asr_activation_bwd(_ptr(dy), _ptr(y), _ptr(dx), dy.numel(), aid, clip,
+                                        _stream()), 'asr_activation_bwd')
+    return dx
+
+
 def lstm_dz_hl_supported(T, n_pad, H, mode=0, compact=False, act=0):
     """Whether lstm_seq_bwd would write packed planes for this geometry (asr_lstm_dz_hl_supported:
     the plain cell on the two-dimensional-split BPTT kernels, persistent mode, split-fp16)."""
@@ -306,9 +408,14 @@ def lstm_status(ws):
 def lstm_timeout_flags(device):
     """The sticky timeout flags of the forward / BPTT workspaces as one int32 tensor of two
     elements on the device (a snapshot enqueued on the current stream, no synchronisation);
-    non-zero = a persistent kernel abandoned a bounded spin since the flag was cleared."""
-    return torch.stack([WS.get(name, 0, device)[:4].view(torch.int32)[0]
-                        for name in ('lstm_fwd', 'lstm_bwd')])
+    non-zero = a persistent kernel abandoned a bounded spin since the flag was cleared.
+    Once a SimpleRNN recurrence has run in this process its workspaces' words are OR-ed in."""
+    words = torch.stack([WS.get(name, 0, device)[:4].view(torch.int32)[0]
+                         for name in ('lstm_fwd', 'lstm_bwd')])
+    if _rnn_ran(device):
+        words = torch.bitwise_or(words, torch.stack(
+            [WS.get(name, 0, device)[:4].view(torch.int32)[0] for name in RNN_WS]))
+    return words
 
 
 def lstm_fast_chains(ws):
@@ -528,6 +635,14 @@ def optim_guard(norm, device, flags=None):
         assert flags.numel() >= 2 and flags.element_size() == 4 and flags.is_contiguous()
         pa, pb = C.c_void_p(flags.data_ptr()), C.c_void_p(flags.data_ptr() + 4)
     L.check(L.load().asr_optim_guard(_ptr(norm), pa, pb, _stream()), 'asr_optim_guard')
+    # the SimpleRNN workspaces' words (own process) / slots 2, 3 (all-reduced), where present
+    if flags is None and _rnn_ran(device):
+        pa, pb = [_ptr(WS.get(name, 0, device)) for name in RNN_WS]
+    elif flags is not None and flags.numel() >= 4:
+        pa, pb = C.c_void_p(flags.data_ptr() + 8), C.c_void_p(flags.data_ptr() + 12)
+    else:
+        return
+    L.check(L.load().asr_optim_guard(_ptr(norm), pa, pb, _stream()), 'asr_optim_guard')
 
 
 def collect_timeout_flags(out, device):
@@ -537,6 +652,11 @@ def collect_timeout_flags(out, device):
     L.check(L.load().asr_timeout_flags(_ptr(WS.get('lstm_fwd', 0, device)),
                                        _ptr(WS.get('lstm_bwd', 0, device)), _ptr(out), _stream()),
             'asr_timeout_flags')
+    if _rnn_ran(device) and out.numel() >= 4:      # SimpleRNN words -> out[2:4]
+        L.check(L.load().asr_timeout_flags(_ptr(WS.get(RNN_WS[0], 0, device)),
+                                           _ptr(WS.get(RNN_WS[1], 0, device)),
+                                           C.c_void_p(out.data_ptr() + 8), _stream()),
+                'asr_timeout_flags')
 
 
 def debug_occupy(blocks, lds_bytes, seconds):
@@ -547,7 +667,7 @@ def debug_occupy(blocks, lds_bytes, seconds):
 
 
 def clear_timeout_flags(device):
-    for name in ('lstm_fwd', 'lstm_bwd'):
+    for name in ('lstm_fwd', 'lstm_bwd') + (RNN_WS if _rnn_ran(device) else ()):
         WS.get(name, 0, device)[:4].zero_()
 
 

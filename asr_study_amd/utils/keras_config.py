@@ -9,7 +9,8 @@ reads back:
   the functional graph ``ctc_model`` builds (core/models.py:31-52): the three ``Input``s
   (``inputs``, sparse int32 ``labels``, int32 ``inputs_length``), the chain of
   ``GaussianNoise`` / ``TimeDistributed(Dense)`` / ``Dropout`` / ``Bidirectional(LSTM)`` /
-  ``Merge`` layers and the two ``Lambda``s ``decoder`` and ``ctc``;
+  ``Bidirectional(SimpleRNN)`` ('concat' or 'sum') / ``TimeDistributed(Activation)`` /
+  ``TimeDistributed(Dropout)`` / ``Merge`` layers and the two ``Lambda``s ``decoder`` and ``ctc``;
 * root attribute ``training_config``: JSON with the optimizer's class and config, the loss /
   metric names and ``loss_weights`` of ``train.py:140-143``;
 * group ``optimizer_weights`` (attribute ``weight_names``): ``[iterations, m..., v...]`` for
@@ -55,6 +56,36 @@ def _lstm_config(name, s, go_backwards=False):
         'zoneout_c': float(s.zoneout_c)}
 
 
+def _act_name(act):
+    """An activation as Keras config text: the clipped ReLU is named (a closure in the
+    reference, not serialisable) and its max_value kept beside it."""
+    if isinstance(act, (tuple, list)) and act and act[0] == 'clipped_relu':
+        return 'clipped_relu', float(act[1])
+    return str(act or 'tanh'), None
+
+
+def _act_from(c):
+    from ..core import layers as L
+    if c.get('activation') == 'clipped_relu':
+        return L.clipped_relu(c.get('max_value', 20.0))
+    return c.get('activation', 'tanh')
+
+
+def _simplernn_config(name, s):
+    """keras.layers.SimpleRNN.get_config() (Recurrent + SimpleRNN)."""
+    act, mv = _act_name(s.act)
+    cfg = {'name': name, 'trainable': True, 'return_sequences': True, 'go_backwards': False,
+           'stateful': False, 'unroll': False, 'consume_less': 'cpu', 'input_dim': int(s.f_in),
+           'input_length': None, 'output_dim': int(s.H), 'init': s.init,
+           'inner_init': 'orthogonal', 'activation': act,
+           'W_regularizer': _regularizer(s.l2_W), 'U_regularizer': _regularizer(s.l2_U),
+           'b_regularizer': None, 'dropout_W': float(s.dropout_W),
+           'dropout_U': float(s.dropout_U)}
+    if mv is not None:
+        cfg['max_value'] = mv
+    return cfg
+
+
 def _lambda_config(name, function, output_shape, arguments):
     return {'name': name, 'trainable': True, 'function': function, 'function_type': 'function',
             'output_shape': output_shape[0], 'output_shape_type': output_shape[1],
@@ -82,12 +113,18 @@ def model_config(model):
             name = nm('gaussiannoise')
             add('GaussianNoise', name, {'name': name, 'trainable': True, 'sigma': float(s.value)},
                 [prev])
+        elif s.kind == 'dropout' and getattr(s, 'wrapped', False):
+            name = nm('timedistributed')
+            inner = nm('dropout')
+            add('TimeDistributed', name, {'name': name, 'trainable': True, 'layer': {
+                'class_name': 'Dropout', 'config': {'name': inner, 'trainable': True,
+                                                   'p': float(s.value)}}}, [prev])
         elif s.kind == 'dropout':
             name = nm('dropout')
             add('Dropout', name, {'name': name, 'trainable': True, 'p': float(s.value)}, [prev])
         elif s.kind == 'dense':
             name = nm('timedistributed')
-            dname = 'dense_%d' % counts['timedistributed']
+            dname = nm('dense')
             add('TimeDistributed', name, {
                 'name': name, 'trainable': True,
                 'layer': {'class_name': 'Dense', 'config': {
@@ -102,6 +139,25 @@ def model_config(model):
                 'name': name, 'trainable': True, 'merge_mode': 'concat',
                 'layer': {'class_name': 'LSTM',
                           'config': _lstm_config('lstm_%d' % counts['bidirectional'], s)}}, [prev])
+        elif s.kind == 'act':
+            wrapped = getattr(s, 'wrapped', False)
+            name = nm('timedistributed') if wrapped else None
+            act, mv = _act_name(s.act)
+            inner = {'name': nm('activation'), 'trainable': True, 'activation': act}
+            if mv is not None:
+                inner['max_value'] = mv
+            if wrapped:
+                add('TimeDistributed', name, {'name': name, 'trainable': True, 'layer': {
+                    'class_name': 'Activation', 'config': inner}}, [prev])
+            else:
+                name = inner['name']
+                add('Activation', name, inner, [prev])
+        elif s.kind == 'birnn':
+            name = nm('bidirectional')
+            add('Bidirectional', name, {
+                'name': name, 'trainable': True, 'merge_mode': s.merge,
+                'layer': {'class_name': 'SimpleRNN', 'config': _simplernn_config(
+                    'simplernn_%d' % counts['bidirectional'], s)}}, [prev])
         elif s.kind == 'reshape':
             name = nm('reshape')
             add('Reshape', name, {'name': name, 'trainable': True,
@@ -222,6 +278,20 @@ def topology_from_config(text):
                                 dim_ordering=c.get('dim_ordering', 'tf'))(o)
         elif kind == 'Dropout':
             o = L.Dropout(c['p'])(o)
+        elif kind == 'Activation':
+            o = L.Activation(_act_from(c))(o)
+        elif kind == 'TimeDistributed' and c['layer']['class_name'] == 'Activation':
+            o = L.TimeDistributed(L.Activation(_act_from(c['layer']['config'])))(o)
+        elif kind == 'TimeDistributed' and c['layer']['class_name'] == 'Dropout':
+            o = L.TimeDistributed(L.Dropout(c['layer']['config']['p']))(o)
+        elif kind == 'Bidirectional' and c['layer']['class_name'] == 'SimpleRNN':
+            r = c['layer']['config']
+            o = L.Bidirectional(L.SimpleRNN(
+                r['output_dim'], init=r.get('init', 'glorot_uniform'),
+                inner_init=r.get('inner_init', 'orthogonal'), activation=_act_from(r),
+                W_regularizer=reg(r.get('W_regularizer')), U_regularizer=reg(r.get('U_regularizer')),
+                dropout_W=r.get('dropout_W', 0.), dropout_U=r.get('dropout_U', 0.)),
+                merge_mode=c.get('merge_mode', 'concat'))(o)
         elif kind == 'TimeDistributed':
             d = c['layer']['config']
             o = L.TimeDistributed(L.Dense(d['output_dim'], W_regularizer=reg(d.get('W_regularizer')),

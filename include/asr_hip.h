@@ -50,8 +50,9 @@ const char* asr_last_error(void);
  * struct carries a size field).  A caller checks asr_version() == ASR_HIP_ABI_VERSION right
  * after loading the library (asr_study_amd/_lib.py does) and refuses a mismatch.
  * 100: rounds 1-4.  105: asr_lstm_args +compact +activation +fwd_units, asr_pack_args +mask2
- * +r2_hl, asr_lstm_ln_args +activation.  106: asr_lstm_args +dz_hl +dz_bound +dz_scale_out. */
-#define ASR_HIP_ABI_VERSION 106
+ * +r2_hl, asr_lstm_ln_args +activation.  106: asr_lstm_args +dz_hl +dz_bound +dz_scale_out.
+ * 107: asr_rnn_args and the asr_rnn_* / asr_activation_* entry points (K14). */
+#define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
 int asr_device_info(int* num_cus, int* lds_bytes_per_cu, char* arch, int arch_len);
@@ -435,6 +436,51 @@ int asr_lstm_trace(long long* out, size_t n_words, asr_stream_t stream);
  * before the gather, waiting for it, arithmetic behind it, barrier, products +
  * publish, issuing the next gather}.                                           */
 int asr_lstm_profile(const void* workspace, asr_stream_t stream, long long* out24);
+
+/* ------------------------------------------------------------------------ */
+/* K14 SimpleRNN recurrence of a Bidirectional layer (Keras 1.2.2            */
+/* SimpleRNN.step: h_t = act(x_t W + b + h_{t-1} U); csrc/rnn.hip).          */
+/* Forward: h = act(zx + (h_prev (.) mask_u) @ U) with zx = x @ W + b from   */
+/* the GEMMs; direction 1 walks the padded slab from T-1 down to 0 and its   */
+/* h stays in frame order.  BPTT: dz = (dy + (dz_next @ U^T) (.) mask_u)     */
+/* (.) act'(h), act' from h alone (clipped relu: 1 on 0 < h < clip).  dW,    */
+/* dU, db, dx come from asr_gemm / asr_colsum.  Exact fp32 products.         */
+/* ------------------------------------------------------------------------ */
+#define ASR_ACT_CLIPPED_RELU 7
+typedef struct asr_rnn_args {
+  int T, n_pad, H;       /* H: padded width, a multiple of 4; n_pad a multiple of 16    */
+  int mode;              /* 0 = the plan's form, 1 = stepwise (one launch per step),    */
+                         /* 2 = persistent (ASR_ERR_INVALID if it would not be resident) */
+  int activation;        /* 0 tanh, 1 relu, 4 linear, ASR_ACT_CLIPPED_RELU              */
+  float clip;            /* max_value of the clipped relu                               */
+  const float* U;        /* (2, H, H) per direction, Keras [in][out]                    */
+  const float* mask_u;   /* optional (2, n_pad, H) B_U, constant over time               */
+  const float* zx;       /* forward: (T, n_pad, 2, H) = x @ W + b                        */
+  float* h;              /* (T, n_pad, 2, H): forward writes it, BPTT reads it           */
+  float* y_sum;          /* forward, optional: (T, n_pad, H) = h_f + h_b ('sum' merge)   */
+  const float* dy;       /* BPTT: gradient of the layer output, row (t, n) at dy_ld      */
+  int dy_ld;             /*   floats per (t, n) row: 2H (concat) or H (sum)              */
+  int dy_dir_stride;     /*   floats between the two directions' dy: H (concat), 0 (sum) */
+  float* dz;             /* BPTT: (T, n_pad, 2, H) gradient of the pre-activation        */
+  float* db_part;        /* BPTT, optional: (n_pad/16, 2, H) per-batch-tile sums of dz   */
+  float* dz_absmax;      /* BPTT, optional: max |dz| (written, not accumulated)          */
+} asr_rnn_args;
+/* Workspace: the first 256 bytes hold a sticky timeout word with the contract of            */
+/* asr_lstm_status (which may be called on it); zero them before the first use.              */
+size_t asr_rnn_workspace_bytes(const asr_rnn_args* a, int backward);
+int asr_rnn_seq_fwd(const asr_rnn_args* a, void* workspace, size_t ws_bytes,
+                    asr_stream_t stream);
+int asr_rnn_seq_bwd(const asr_rnn_args* a, void* workspace, size_t ws_bytes,
+                    asr_stream_t stream);
+/* The form the library would run (persistent 1 / stepwise 0) and its geometry: batch rows    */
+/* and units per workgroup, workgroups per launch (both directions).                          */
+int asr_rnn_plan(const asr_rnn_args* a, int backward, int* persistent, int* rows, int* units,
+                 int* blocks);
+/* Element-wise Activation layer: y = act(x); dx = dy (.) act'(y) (ids as asr_rnn_args).      */
+int asr_activation_fwd(const float* x, float* y, int64_t n, int activation, float clip,
+                       asr_stream_t stream);
+int asr_activation_bwd(const float* dy, const float* y, float* dx, int64_t n, int activation,
+                       float clip, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* K7  CTC loss + gradient.  Replaces core/ctc_utils.py:60-70 ->             */
