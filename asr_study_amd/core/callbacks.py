@@ -60,7 +60,7 @@ def keras_layers(model, weights):
     """[(layer name, [(weight name, array), ...])] in Keras-1.2.2 naming for the model's
     weight-bearing stages (get_weights() order); every array of ``weights`` is consumed."""
     it = iter(weights)
-    out, nb, nd, nc, ntd = [], 0, 0, 0, 0
+    out, nb, nd, nc, ntd, nbn = [], 0, 0, 0, 0, 0
     for s in model.stages:
         # (Keras names a TimeDistributed layer by its own counter; the weight group of a Dense
         # is named after the TimeDistributed around it)
@@ -84,6 +84,11 @@ def keras_layers(model, weights):
                 for part in LSTM_PARTS:
                     ws.append(('%s_simplernn_%d_%s:0' % (d, nb, part), next(it)))
             out.append(('bidirectional_%d' % nb, ws))
+        elif s.kind == 'bn':        # keras.layers.BatchNormalization: gamma, beta, running moments
+            nbn += 1
+            out.append(('batchnormalization_%d' % nbn,
+                        [('batchnormalization_%d_%s:0' % (nbn, part), next(it))
+                         for part in ('gamma', 'beta', 'running_mean', 'running_std')]))
         elif s.kind == 'dense':
             nd += 1
             ntd += 1

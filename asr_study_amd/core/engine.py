@@ -196,6 +196,8 @@ class Model(object):
         f_real, f_pad = self.num_features, _pad4(self.num_features)
         self.f_in_pad0 = f_pad
         init = []
+        run_off = 0                     # BatchNormalization running moments (self.bn_running)
+        tail = 4                        # ... and their moments blocks behind the flag slots
 
         def take(n):
             nonlocal off
@@ -232,7 +234,7 @@ class Model(object):
                                      '(asr_conv2d_* keeps one plane shift per time tap)' % s.kt)
                 if s.st < 1 or s.sf < 1:
                     raise ValueError('conv stage: strides must be >= 1')
-                if s.st > 1 and any(p.kind in ('dense', 'bilstm', 'conv', 'birnn')
+                if s.st > 1 and any(p.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn')
                                     for p in self.stages):
                     raise ValueError(
                         'conv stage with time stride %d behind a trainable stage: asr_conv2d_dgrad '
@@ -333,6 +335,38 @@ class Model(object):
                            np.zeros(s.H, np.float32)]
                 init.append((s, 'birnn', ws))
                 f_real, f_pad = (2 * s.H, 2 * s.Hp) if s.merge == 'concat' else (s.H, s.Hp)
+            elif s.kind == 'bn':
+                # BatchNormalization (csrc/batchnorm.hip): gamma, beta (C each) in the flat
+                # parameters (l2 0); running mean / variance in self.bn_running (not trainable);
+                # the moments block of the running update behind the gradients' flag slots, so
+                # that data parallel the gradient all-reduce pools it over the ranks
+                s.eps, s.momentum = float(st.get('epsilon', 1e-3)), float(st.get('momentum', 0.99))
+                fc = st.get('fc')
+                s.grouped = fc is not None and int(fc[1]) < f_pad
+                if s.grouped:
+                    s.C = int(fc[1])            # per channel of the (N, T, F, C) conv image
+                    if f_pad != f_real or f_pad != int(fc[0]) * s.C or s.C % 4 or s.C > 256:
+                        raise NotImplementedError(
+                            'BatchNormalization on an (N, T, %d, %d) image: the channel count '
+                            'must be a multiple of 4, at most 256' % (int(fc[0]), s.C))
+                else:
+                    s.C = f_pad                 # per column, pad columns get gamma = beta = 0
+                    if f_pad % 4:
+                        raise NotImplementedError('BatchNormalization over %d features: the '
+                                                  'width must be a multiple of 4' % f_real)
+                s.n_real = s.C if s.grouped else f_real
+                s.clip = 0.0                    # > 0: a following clipped ReLU fused (below)
+                s.og = take(s.C)
+                s.obeta = take(s.C)
+                segs += [(s.og, _pad4(s.C), 0.0), (s.obeta, _pad4(s.C), 0.0)]
+                s.orun = run_off
+                run_off += 2 * _pad4(s.C)
+                s.omom = tail
+                tail += _pad4(ops.bn_moments_len(s.C))
+                init.append((s, 'bn', [np.ones(s.n_real, np.float32),
+                                       np.zeros(s.n_real, np.float32),
+                                       np.zeros(s.n_real, np.float32),
+                                       np.ones(s.n_real, np.float32)]))
             elif s.kind == 'merge':
                 s.mode, s.skip = st['mode'], int(st['skip'])
                 src = self.stages[s.skip]
@@ -350,15 +384,28 @@ class Model(object):
                        (self._packed_mode == '1' or (self._packed_mode == 'auto' and widest >= 512)))
         self.num_classes = f_real
         self._has_rnn = any(st.kind == 'birnn' for st in self.stages)
+        self._bn = [(i, st) for i, st in enumerate(self.stages) if st.kind == 'bn']
+        skips = set(st.skip for st in self.stages if st.kind == 'merge')
+        for i, st in self._bn:
+            # BN followed by a clipped ReLU: one pass (asr_bn_* clip), the Activation stage is
+            # then a pass-through (unless a residual branch reads the BN output itself)
+            nxt = self.stages[i + 1] if i + 1 < len(self.stages) else None
+            if (nxt is not None and nxt.kind == 'act' and isinstance(nxt.act, (tuple, list))
+                    and nxt.act[0] == 'clipped_relu' and float(nxt.act[1]) > 0
+                    and i not in skips and os.environ.get('ASR_BN_FUSE', '1') != '0'):
+                st.clip = float(nxt.act[1])
+                nxt.fused = True
         self.time_strides = [st.st for st in self.stages if st.kind == 'conv' and st.st > 1]
         self._convs = {}
         self.n_params = off
         self.params = torch.zeros(off, dtype=torch.float32, device=self.device)
         # gradients + 4 trailing floats: [0:2] carry this rank's recurrent-kernel timeout flags
         # through the gradient all-reduce (sum > 0 on every rank if ANY rank timed out), so a
-        # veto of the update is collective and costs no collective of its own
-        self._gbuf = torch.zeros(off + 4, dtype=torch.float32, device=self.device)
+        # veto of the update is collective and costs no collective of its own; behind them the
+        # BatchNormalization stages' moments blocks (none without such a stage)
+        self._gbuf = torch.zeros(off + tail, dtype=torch.float32, device=self.device)
         self.grads = self._gbuf[:off]
+        self.bn_running = torch.zeros(max(run_off, 4), dtype=torch.float32, device=self.device)
         self._segments = sorted(segs)
         self._segs_dev, self._nseg = ops.make_segments(self._segments, self.device)
         self._norm = torch.zeros(2, dtype=torch.float64, device=self.device)
@@ -385,6 +432,7 @@ class Model(object):
     def set_weights(self, weights):
         """weights: flat list in the reference's Keras order (see module doc)."""
         host = self.params.detach().cpu().numpy().copy()
+        run = self.bn_running.detach().cpu().numpy().copy()
         it = iter(weights)
         for s in self.stages:
             if s.kind == 'conv':
@@ -448,10 +496,32 @@ class Model(object):
                 host[s.oW:s.oW + Wp.size] = Wp.ravel()
                 host[s.oU:s.oU + Up.size] = Up.ravel()
                 host[s.ob:s.ob + bp.size] = bp.ravel()
+            elif s.kind == 'bn':            # Keras order: gamma, beta, running_mean, running_std
+                idx = self._bn_cols(s)
+                g, b, rm, rv = [np.asarray(next(it), np.float32).reshape(-1) for _ in range(4)]
+                assert g.shape == (len(idx),) and rv.shape == (len(idx),), (g.shape, rv.shape)
+                for o, v, pad in ((s.og, g, 0.0), (s.obeta, b, 0.0)):
+                    vp = np.full(s.C, pad, np.float32)
+                    vp[idx] = v
+                    host[o:o + s.C] = vp
+                Cp = _pad4(s.C)
+                run[s.orun:s.orun + s.C] = 0.0
+                run[s.orun + Cp:s.orun + Cp + s.C] = 1.0
+                run[s.orun + idx] = rm
+                run[s.orun + Cp + idx] = rv
         self.params.copy_(torch.from_numpy(host))
+        if self._bn:
+            self.bn_running.copy_(torch.from_numpy(run))
         self._weights_epoch += 1        # (bounds measured under the old weights are dropped)
 
-    def _unpack(self, flat):
+    def _bn_cols(self, s):
+        """Physical channels of a BatchNormalization stage that carry real features."""
+        return np.arange(s.C) if s.grouped else self._real_rows(s)
+
+    def _unpack(self, flat, running=None):
+        """flat (params / grads / optimiser slots) -> Keras-order arrays.  running: the host copy
+        of bn_running (get_weights), 'zeros' (get_gradients: the running moments have none) or
+        None (optimiser slots: trainable weights only)."""
         out = []
         for s in self.stages:
             if s.kind == 'conv':
@@ -493,15 +563,24 @@ class Model(object):
                 for d in range(2):
                     out += [Wp[rows, d, :s.H].copy(), Up[d, :s.H, :s.H].copy(),
                             bp[d, :s.H].copy()]
+            elif s.kind == 'bn':
+                idx = self._bn_cols(s)
+                out += [flat[s.og:s.og + s.C][idx].copy(), flat[s.obeta:s.obeta + s.C][idx].copy()]
+                if isinstance(running, str):
+                    out += [np.zeros(len(idx), np.float32), np.zeros(len(idx), np.float32)]
+                elif running is not None:
+                    Cp = _pad4(s.C)
+                    out += [running[s.orun + idx].copy(), running[s.orun + Cp + idx].copy()]
         return out
 
     def get_weights(self):
-        return self._unpack(self.params.detach().cpu().numpy())
+        return self._unpack(self.params.detach().cpu().numpy(),
+                            running=self.bn_running.detach().cpu().numpy())
 
     def get_gradients(self):
         """Last computed gradients (before clipping, without the l2 term), in the
         same order/layout as get_weights()."""
-        return self._unpack(self.grads.detach().cpu().numpy())
+        return self._unpack(self.grads.detach().cpu().numpy(), running='zeros')
 
     def count_params(self):
         return int(sum(w.size for w in self.get_weights()))
@@ -637,10 +716,14 @@ class Model(object):
                         c_off=d * 4 * Hp, ldc=8 * Hp, bias=bias[d * 4 * Hp:(d + 1) * 4 * Hp])
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x, training=False, masks=None, need_grad=True, n_valid=0):
+    def forward(self, x, training=False, masks=None, need_grad=True, n_valid=0, n_real=None,
+                bn_weight=None):
         """x: (T, n_pad, F) float32 CUDA slab -> logits (T, n_pad, C).
         need_grad=False (evaluation / prediction) skips what only BPTT would read; n_valid=1
         with it (one utterance, predict.py) selects the tile-free recurrent kernel.
+        n_real: the real samples of the slab (rows n < n_real of every frame; default n_valid, else
+        n_pad), over which BatchNormalization takes its training statistics; bn_weight: samples
+        this rank contributes to the running moments (default n_real; 0 = a zero-weight dummy).
 
         masks: optional explicit variational-dropout masks (parity tests):
         {stage_index: (BW (2, n_pad, f_in_pad), BU (2, n_pad, Hp))}.
@@ -675,6 +758,8 @@ class Model(object):
         pre = {}
         if any(self._stage_packed(st) for st in self.stages):
             self._pack_weights()
+        n_real = int(n_real or n_valid or n_pad)
+        bn_weight = n_real if bn_weight is None else int(bn_weight)
 
         def stage_masks(i):
             st = self.stages[i]
@@ -828,8 +913,11 @@ class Model(object):
                 rec.update(y=y, cell=cell, gates=gates)
                 a = y
             elif s.kind == 'act':
-                out = self._buf('act%d' % si, a.shape)
-                a = ops.activation_fwd(a.contiguous(), out, s.act)
+                if not getattr(s, 'fused', False):     # (else applied by the BN stage before)
+                    out = self._buf('act%d' % si, a.shape)
+                    a = ops.activation_fwd(a.contiguous(), out, s.act)
+            elif s.kind == 'bn':
+                a = self._bn_forward(s, si, a.contiguous(), rec, training, n_real, bn_weight)
             elif s.kind == 'birnn':
                 Hp = s.Hp
                 BW, BU = stage_masks(si)[:2]
@@ -845,6 +933,48 @@ class Model(object):
             rec['out'] = a
             self._acts.append(rec)
         return a
+
+    def _bn_forward(self, s, si, a, rec, training, n_real, bn_weight):
+        """BatchNormalization stage: batch statistics of the n_real real rows in training (saved
+        for the backward pass; the moments block of the running update written behind the flag
+        slots), the running moments otherwise."""
+        T, n_pad, ld = a.shape
+        y = self._buf('bn%d' % si, a.shape)
+        gamma, beta = self._view(s.og, s.C), self._view(s.obeta, s.C)
+        Cp = _pad4(s.C)
+        rm = self.bn_running[s.orun:s.orun + s.C]
+        rv = self.bn_running[s.orun + Cp:s.orun + Cp + s.C]
+        if not training:
+            return ops.bn_fwd_infer(a, y, gamma, beta, rm, rv, min(n_real, n_pad), ld, s.C,
+                                    s.eps, s.clip)
+        stats = self._buf('bnstats%d' % si, (ops.bn_stats_len(s.C),))
+        mom = self._gbuf[self.n_params + s.omom:self.n_params + s.omom + ops.bn_moments_len(s.C)]
+        # data parallel the moments are taken about the running mean (the same on every rank),
+        # weighted by the rank's real frames, and pooled by the gradient all-reduce
+        dist = self._dist_active()
+        ops.bn_fwd_train(a, y, gamma, beta, stats, min(n_real, n_pad), ld, s.C, s.eps, s.clip,
+                         moments=mom, shift=rm if dist else None,
+                         weight=float(bn_weight * T))
+        rec.update(stats=stats, N=min(n_real, n_pad), shift=None if dist else stats[:s.C])
+        return y
+
+    def _bn_update(self):
+        """Running-moment update of every BatchNormalization stage, once per optimisation step,
+        behind the optimiser: skipped on the device with the update (the same flag words as the
+        optimiser's guard), so a vetoed step leaves the statistics alone; no host sync."""
+        if not self._bn or not getattr(self, '_acts', None):
+            return
+        flags = self.veto_flags()
+        for si, s in self._bn:
+            rec = self._acts[si]
+            if 'stats' not in rec:
+                continue
+            Cp = _pad4(s.C)
+            mom = self._gbuf[self.n_params + s.omom:self.n_params + s.omom +
+                             ops.bn_moments_len(s.C)]
+            ops.bn_update_running(self.bn_running[s.orun:s.orun + s.C],
+                                  self.bn_running[s.orun + Cp:s.orun + Cp + s.C], mom, s.C,
+                                  s.momentum, shift=rec['shift'], flags=flags)
 
     def _rnn_input_gemm(self, a, s, zx, BW, rows, n_pad):
         """zx = (a (.) B_W[d]) @ W_d + b_d of a SimpleRNN stage, both directions."""
@@ -1176,7 +1306,7 @@ class Model(object):
                     da = ops.axpby(s.coef, da, 0.0, da, self._buf('dmerge%d' % si, da.shape))
                 skip_grads[s.skip] = da
                 continue
-            first = not any(st.kind in ('dense', 'bilstm', 'conv', 'birnn')
+            first = not any(st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn')
                             for st in self.stages[:si])
             if s.kind in ('noise', 'reshape'):
                 continue
@@ -1197,9 +1327,18 @@ class Model(object):
                     da = dx
                 continue
             if s.kind == 'act':
-                if not first:
+                if not first and not getattr(s, 'fused', False):
                     da = ops.activation_bwd(da.contiguous(), rec['out'],
                                             self._buf('dact%d' % si, da.shape), s.act)
+                continue
+            if s.kind == 'bn':
+                # dgamma / dbeta into the gradients, dx from the saved statistics (x re-read)
+                dx = None if first else self._buf('dbn%d' % si, a_in.shape)
+                ops.bn_bwd(a_in.contiguous(), da.contiguous(), self._view(s.og, s.C),
+                           self._view(s.obeta, s.C), rec['stats'], dx, self._gview(s.og, s.C),
+                           self._gview(s.obeta, s.C), rec['N'], a_in.shape[2], s.C, s.clip)
+                if dx is not None:
+                    da = dx
                 continue
             if s.kind == 'birnn':
                 dx = self._rnn_backward(s, si, rec, da, first, split)
@@ -1560,7 +1699,8 @@ class Model(object):
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         ng = int(n_ref or n_global or N * world)
         self._ar_ref_pad = ops.pad16((ng + world - 1) // world)
-        logits = self.forward(slab, training=training, masks=masks)
+        logits = self.forward(slab, training=training, masks=masks, n_real=N,
+                              bn_weight=0 if n_global == 0 else N)
         dlog = self._buf('dlogits', logits.shape)
         # n_global = 0: a zero-weight dummy shard (parallel.ShardedBatch.n_local == 0)
         ctc = ops.ctc_loss_grad(logits, lab, lab_len, sl, N, grad=dlog,
@@ -1579,6 +1719,7 @@ class Model(object):
         self._allreduce()
         self._step += 1
         self.optimizer.step(self)
+        self._bn_update()
         dec, dlen = ops.ctc_greedy(logits, sl, N)
         return ctc, dec, dlen
 
@@ -1673,7 +1814,7 @@ class Model(object):
         from ..parallel import grad_comm, world_size
         comm = grad_comm(self._gbuf.device)
         self._collect_flags()
-        total = self.n_params + 4
+        total = self._gbuf.numel()      # (the flag slots and any BN moments blocks behind them)
         covered = sorted(getattr(self, '_ar_covered', []))
         pos = 0
         for lo, hi in covered + [(total, total)]:
@@ -1707,6 +1848,7 @@ class Model(object):
         self._step += 1
         self._enqueued += 1
         self.optimizer.step(self)
+        self._bn_update()
         dec, dlen = ops.ctc_greedy(logits, sl, N)
         if not sync:
             # snapshots of this step's small result tensors (the buffers behind them are

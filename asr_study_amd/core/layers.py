@@ -10,7 +10,8 @@ signature (core/layers.py:366-386: zoneout_h/zoneout_c/layer_norm/mi on top of t
 Keras LSTM arguments); of the optional variants the residual ``merge``, multiplicative
 integration, zoneout and layer normalisation are implemented.
 ``SimpleRNN`` (Bidirectional, 'concat' or 'sum'), ``Activation`` and ``recurrent()`` serve the
-maas / deep_speech factories (core/models.py).
+maas / deep_speech factories (core/models.py).  ``BatchNormalization`` (mode 0, axis -1) runs
+bare or on the (N, T, F, C) image of the convolution front-end (csrc/batchnorm.hip).
 """
 
 
@@ -234,6 +235,38 @@ def clipped_relu(max_value=20.0):
     """The reference's activation of its (dead) Deep Speech factories: ``relu(x,
     max_value=max_value)`` = min(max(x, 0), max_value) (core/models.py:116-117)."""
     return ('clipped_relu', float(max_value))
+
+
+class BatchNormalization(Layer):
+    """keras.layers.BatchNormalization (Keras 1.2.2), mode 0, axis -1: per feature (per channel on
+    the (N, T, F, C) image between the convolution front-end's Reshapes) over every other axis.
+    Training: the batch mean and biased variance of the real samples (all frames, time padding
+    included); inference: the running moments, updated once per optimisation step as r <-
+    momentum r + (1 - momentum) batch (no debias).  Weights: gamma, beta, running_mean,
+    running_std (which holds the variance, as Keras names it)."""
+
+    def __init__(self, epsilon=1e-3, mode=0, axis=-1, momentum=0.99, weights=None,
+                 beta_init='zero', gamma_init='one', gamma_regularizer=None,
+                 beta_regularizer=None, **kwargs):
+        if mode != 0:
+            raise NotImplementedError('BatchNormalization(mode=%r): mode 0 only' % (mode,))
+        if axis != -1:
+            raise NotImplementedError('BatchNormalization(axis=%r): axis -1 only' % (axis,))
+        if gamma_regularizer is not None or beta_regularizer is not None:
+            raise NotImplementedError('BatchNormalization regularizers')
+        if beta_init != 'zero' or gamma_init != 'one':
+            raise NotImplementedError("BatchNormalization: beta_init='zero', gamma_init='one' only")
+        if weights is not None:
+            raise NotImplementedError('BatchNormalization(weights=...): use set_weights')
+        if not float(epsilon) > 0:
+            raise ValueError('BatchNormalization: epsilon must be > 0')
+        self.epsilon, self.momentum = float(epsilon), float(momentum)
+        self.mode, self.axis = 0, -1
+        self.in_fc = None
+
+    def __call__(self, x):
+        self.in_fc = x.fc
+        return Layer.__call__(self, x)
 
 
 class Reshape(Layer):

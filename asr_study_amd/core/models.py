@@ -14,7 +14,7 @@ from . import ctc_utils
 from .engine import Model
 from .layers import (Input, GaussianNoise, TimeDistributed, Dense, LSTM, Bidirectional,
                      Dropout, Merge, merge, l2, Reshape, Convolution2D, clipped_relu, SimpleRNN,
-                     Activation)
+                     Activation, BatchNormalization)
 
 
 def ctc_model(inputs, output, **kwargs):
@@ -51,6 +51,9 @@ def ctc_model(inputs, output, **kwargs):
                          'st': layer.st, 'sf': layer.sf, 'clip': layer.clip, 'l2': layer.l2})
         elif isinstance(layer, GaussianNoise):
             spec.append({'type': 'noise', 'value': layer.sigma})
+        elif isinstance(layer, BatchNormalization):
+            spec.append({'type': 'bn', 'epsilon': layer.epsilon, 'momentum': layer.momentum,
+                         'fc': None if layer.in_fc is None else list(layer.in_fc)})
         elif isinstance(layer, TimeDistributed) and layer.dense is None:
             spec.append(_elementwise_spec(layer.layer, wrapped=True))
         elif isinstance(layer, (Dropout, Activation)):
@@ -208,7 +211,8 @@ def brsmv1(num_features=39, num_classes=28, num_hiddens=256, num_layers=5,
 
 def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
                  conv_filters=32, conv_kernels=((11, 41), (11, 21)), conv_strides=((2, 2), (1, 2)),
-                 max_value=20, dropout=0.2, weight_decay=1e-4, input_std_noise=.0, **kw):
+                 max_value=20, dropout=0.2, weight_decay=1e-4, input_std_noise=.0,
+                 batch_norm=False, **kw):
     """BASELINE.json configs[2]: "DeepSpeech2-style 5xBiLSTM(512) + 2 conv front-end, 80-dim
     log-mel".  NO REFERENCE COUNTERPART: the reference lists Deep Speech 2 as TODO
     (README.md:118) and its ``deep_speech`` factory (core/models.py:148-214) is dead code
@@ -217,7 +221,13 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
     of its Deep Speech factories (:116-117), and two Keras Convolution2D layers over (time,
     frequency) with DeepSpeech2's filter shapes -- 32 x (11 x 41) stride (2, 2) and
     32 x (11 x 21) stride (1, 2), 'same' padding -- so the recurrent stack sees T/2 frames of
-    F/4 * 32 features.  ``inputs_length`` is mapped to ceil(len / 2) inside the model."""
+    F/4 * 32 features.  ``inputs_length`` is mapped to ceil(len / 2) inside the model.
+
+    batch_norm=True: each Convolution2D becomes linear and is followed by BatchNormalization
+    (per channel) and Activation(clipped_relu(max_value)); a BatchNormalization also goes in
+    front of every Bidirectional(LSTM).  That normalises the layer INPUT x, not the input
+    projection W x of the published Deep Speech 2 (sequence-wise BN inside the recurrent layer),
+    and its statistics include the time-padding frames, as Keras sees the zero-padded batch."""
     x = Input(name='inputs', shape=(None, num_features))
     o = x
     if input_std_noise is not None:
@@ -225,10 +235,15 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
     o = Reshape((-1, num_features, 1))(o)
     for (kt, kf), (st, sf) in zip(conv_kernels, conv_strides):
         o = Convolution2D(conv_filters, kt, kf, subsample=(st, sf), border_mode='same',
-                          activation=clipped_relu(max_value),
+                          activation=None if batch_norm else clipped_relu(max_value),
                           W_regularizer=l2(weight_decay))(o)
+        if batch_norm:
+            o = BatchNormalization()(o)
+            o = Activation(clipped_relu(max_value))(o)
     o = Reshape((-1, o.features))(o)
     for _ in range(num_layers):
+        if batch_norm:
+            o = BatchNormalization()(o)
         o = Bidirectional(LSTM(num_hiddens, return_sequences=True,
                                W_regularizer=l2(weight_decay), U_regularizer=l2(weight_decay),
                                dropout_W=dropout, dropout_U=dropout))(o)
@@ -240,5 +255,7 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
         conv_kernels=[list(k) for k in conv_kernels], conv_strides=[list(k) for k in conv_strides],
         max_value=max_value, dropout=dropout, weight_decay=weight_decay,
         input_std_noise=input_std_noise)}
+    if batch_norm:          # (only then: default checkpoints keep their config byte for byte)
+        model.config['kwargs']['batch_norm'] = True
     return model
 

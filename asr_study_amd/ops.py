@@ -380,6 +380,87 @@ def activation_bwd(dy, y, dx, act):
     return dx
 
 
+# --------------------------------------------------------------------------- BatchNormalization
+def bn_stats_len(C):
+    """Floats of a stage's stats block: [mean_hi | mean_lo | invstd | var] (C each)."""
+    return 4 * int(C)
+
+
+def bn_moments_len(C):
+    """Floats of a stage's moments block for the running update: [w, 0, 0, 0 | w d | w (var +
+    d^2)] (asr_bn_fwd_train)."""
+    return 4 + 2 * int(C)
+
+
+def _bn_ws(T, N, n_pad, ld, W, C, device):
+    nbytes = L.load().asr_bn_workspace_bytes(int(T), int(N), int(n_pad), int(ld), int(W), int(C))
+    if nbytes == 0:
+        L.check(-1, 'asr_bn_workspace_bytes (T %d N %d n_pad %d ld %d W %d C %d)'
+                % (T, N, n_pad, ld, W, C))
+    return WS.get('bn', nbytes, device), nbytes
+
+
+def bn_fwd_train(x, y, gamma, beta, stats, N, W, C, eps=1e-3, clip=0.0, moments=None,
+                 shift=None, weight=0.0):
+    """Training-phase BatchNormalization of x (T, n_pad, ld): y (same shape), stats (4C) from
+    the batch moments of the N real rows of every frame; moments (4 + 2C, optional) for
+    bn_update_running with weight w and shift (None: the batch mean)."""
+    _check_f32(x, y, gamma, beta, stats, moments, shift)
+    T, n_pad, ld = x.shape
+    ws, nbytes = _bn_ws(T, N, n_pad, ld, W, C, x.device)
+    L.check(L.load().asr_bn_fwd_train(_ptr(x), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(stats),
+                                      _ptr(moments), _ptr(shift), float(weight), int(T), int(N),
+                                      int(n_pad), int(ld), int(W), int(C), float(eps), float(clip),
+                                      _ptr(ws), nbytes, _stream()), 'asr_bn_fwd_train')
+    return y
+
+
+def bn_fwd_infer(x, y, gamma, beta, running_mean, running_var, N, W, C, eps=1e-3, clip=0.0):
+    """Inference-phase BatchNormalization on the running moments (one pass)."""
+    _check_f32(x, y, gamma, beta, running_mean, running_var)
+    T, n_pad, ld = x.shape
+    L.check(L.load().asr_bn_fwd_infer(_ptr(x), _ptr(y), _ptr(gamma), _ptr(beta),
+                                      _ptr(running_mean), _ptr(running_var), int(T), int(N),
+                                      int(n_pad), int(ld), int(W), int(C), float(eps), float(clip),
+                                      _stream()), 'asr_bn_fwd_infer')
+    return y
+
+
+def bn_bwd(x, dy, gamma, beta, stats, dx, dgamma, dbeta, N, W, C, clip=0.0):
+    """dgamma, dbeta (C, written) and dx (same shape as x, or None) from the saved stats."""
+    _check_f32(x, dy, gamma, beta, stats, dx, dgamma, dbeta)
+    T, n_pad, ld = x.shape
+    ws, nbytes = _bn_ws(T, N, n_pad, ld, W, C, x.device)
+    L.check(L.load().asr_bn_bwd(_ptr(x), _ptr(dy), _ptr(gamma), _ptr(beta), _ptr(stats),
+                                _ptr(dx), _ptr(dgamma), _ptr(dbeta), int(T), int(N), int(n_pad),
+                                int(ld), int(W), int(C), float(clip), _ptr(ws), nbytes, _stream()),
+            'asr_bn_bwd')
+    return dx
+
+
+def bn_flag_words(device, flags=None):
+    """The four flag words the running update's guard reads, as raw device pointers: the
+    all-reduced flag slots (data parallel, ``flags`` = Model.veto_flags()) or this process'
+    sticky timeout words -- the same words ops.optim_guard reads."""
+    if flags is not None:
+        base = flags.data_ptr()
+        return [C.c_void_p(base + 4 * k) if k < flags.numel() else None for k in range(4)]
+    out = [_ptr(WS.get('lstm_fwd', 0, device)), _ptr(WS.get('lstm_bwd', 0, device))]
+    out += [_ptr(WS.get(name, 0, device)) for name in RNN_WS] if _rnn_ran(device) else [None,
+                                                                                         None]
+    return out
+
+
+def bn_update_running(running_mean, running_var, moments, C, momentum, shift=None, flags=None):
+    """EMA of the running moments from a moments block (skipped on the device when a flag word
+    is set: bn_flag_words)."""
+    _check_f32(running_mean, running_var, moments, shift)
+    fw = bn_flag_words(running_mean.device, flags)
+    L.check(L.load().asr_bn_update_running(_ptr(running_mean), _ptr(running_var), _ptr(moments),
+                                           _ptr(shift), int(C), float(momentum), *fw, _stream()),
+            'asr_bn_update_running')
+
+
 def lstm_dz_hl_supported(T, n_pad, H, mode=0, compact=False, act=0):
     """Whether lstm_seq_bwd would write packed planes for this geometry (asr_lstm_dz_hl_supported:
     the plain cell on the two-dimensional-split BPTT kernels, persistent mode, split-fp16)."""

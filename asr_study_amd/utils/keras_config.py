@@ -10,7 +10,8 @@ reads back:
   (``inputs``, sparse int32 ``labels``, int32 ``inputs_length``), the chain of
   ``GaussianNoise`` / ``TimeDistributed(Dense)`` / ``Dropout`` / ``Bidirectional(LSTM)`` /
   ``Bidirectional(SimpleRNN)`` ('concat' or 'sum') / ``TimeDistributed(Activation)`` /
-  ``TimeDistributed(Dropout)`` / ``Merge`` layers and the two ``Lambda``s ``decoder`` and ``ctc``;
+  ``TimeDistributed(Dropout)`` / ``BatchNormalization`` / ``Merge`` layers and the two ``Lambda``s
+  ``decoder`` and ``ctc``;
 * root attribute ``training_config``: JSON with the optimizer's class and config, the loss /
   metric names and ``loss_weights`` of ``train.py:140-143``;
 * group ``optimizer_weights`` (attribute ``weight_names``): ``[iterations, m..., v...]`` for
@@ -158,6 +159,12 @@ def model_config(model):
                 'name': name, 'trainable': True, 'merge_mode': s.merge,
                 'layer': {'class_name': 'SimpleRNN', 'config': _simplernn_config(
                     'simplernn_%d' % counts['bidirectional'], s)}}, [prev])
+        elif s.kind == 'bn':
+            name = nm('batchnormalization')
+            add('BatchNormalization', name, {
+                'name': name, 'trainable': True, 'epsilon': float(s.eps), 'mode': 0, 'axis': -1,
+                'momentum': float(s.momentum), 'gamma_regularizer': None,
+                'beta_regularizer': None}, [prev])
         elif s.kind == 'reshape':
             name = nm('reshape')
             add('Reshape', name, {'name': name, 'trainable': True,
@@ -280,6 +287,9 @@ def topology_from_config(text):
             o = L.Dropout(c['p'])(o)
         elif kind == 'Activation':
             o = L.Activation(_act_from(c))(o)
+        elif kind == 'BatchNormalization':
+            o = L.BatchNormalization(epsilon=c.get('epsilon', 1e-3), mode=c.get('mode', 0),
+                                     axis=c.get('axis', -1), momentum=c.get('momentum', 0.99))(o)
         elif kind == 'TimeDistributed' and c['layer']['class_name'] == 'Activation':
             o = L.TimeDistributed(L.Activation(_act_from(c['layer']['config'])))(o)
         elif kind == 'TimeDistributed' and c['layer']['class_name'] == 'Dropout':

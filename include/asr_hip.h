@@ -51,7 +51,8 @@ const char* asr_last_error(void);
  * after loading the library (asr_study_amd/_lib.py does) and refuses a mismatch.
  * 100: rounds 1-4.  105: asr_lstm_args +compact +activation +fwd_units, asr_pack_args +mask2
  * +r2_hl, asr_lstm_ln_args +activation.  106: asr_lstm_args +dz_hl +dz_bound +dz_scale_out.
- * 107: asr_rnn_args and the asr_rnn_* / asr_activation_* entry points (K14). */
+ * 107: asr_rnn_args and the asr_rnn_* / asr_activation_* entry points (K14); the asr_bn_*
+ * entry points (K15: plain scalar arguments, no struct, so the version stays). */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -481,6 +482,48 @@ int asr_activation_fwd(const float* x, float* y, int64_t n, int activation, floa
                        asr_stream_t stream);
 int asr_activation_bwd(const float* dy, const float* y, float* dx, int64_t n, int activation,
                        float clip, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K15 BatchNormalization (Keras 1.2.2, mode 0, axis -1; csrc/batchnorm.hip) */
+/* over a time-major slab x (T, n_pad, ld), ld a multiple of 4, 16-byte     */
+/* aligned.  Columns [0, W) are normalised, [W, ld) and the padding rows     */
+/* n >= N of y / dx are written as zeros.  channel = column % C: C == W is a */
+/* plain (N, T, W) tensor, C < W the (N, T, F, C) conv image (W = F * C, no  */
+/* pad columns, C a multiple of 4, at most 256).  Statistics over every real */
+/* row of all T frames, biased variance, fp64 partials added in a fixed      */
+/* order (no float atomics: bit-identical repeats).                          */
+/*  stats (4C floats): [mean_hi | mean_lo | 1/sqrt(var + eps) | var], the    */
+/*    mean split into two floats (x - mean stays exact for large means).     */
+/*  moments (4 + 2C floats, optional): [w, 0, 0, 0 | w d | w (var + d^2)],   */
+/*    d = mean - shift[c] (shift NULL: the batch mean itself).  Sums of such */
+/*    blocks over data-parallel ranks (w = real frames of the rank, shift =  */
+/*    the rank-invariant running mean) are the moments of the union batch.  */
+/*  clip > 0 fuses a following clipped ReLU: y = min(max(y, 0), clip); the   */
+/*    backward masks dy with 0 < y < clip (y recomputed from x).             */
+/* ------------------------------------------------------------------------ */
+size_t asr_bn_workspace_bytes(int T, int N, int n_pad, int ld, int W, int C);
+int asr_bn_fwd_train(const float* x, float* y, const float* gamma, const float* beta,
+                     float* stats, float* moments, const float* shift, float weight, int T, int N,
+                     int n_pad, int ld, int W, int C, float eps, float clip, void* workspace,
+                     size_t ws_bytes, asr_stream_t stream);
+/* y = gamma (x - running_mean) / sqrt(running_var + eps) + beta (no workspace).              */
+int asr_bn_fwd_infer(const float* x, float* y, const float* gamma, const float* beta,
+                     const float* running_mean, const float* running_var, int T, int N, int n_pad,
+                     int ld, int W, int C, float eps, float clip, asr_stream_t stream);
+/* dgamma / dbeta (C floats) are written, not accumulated; dx may be NULL (no input gradient). */
+int asr_bn_bwd(const float* x, const float* dy, const float* gamma, const float* beta,
+               const float* stats, float* dx, float* dgamma, float* dbeta, int T, int N,
+               int n_pad, int ld, int W, int C, float clip, void* workspace, size_t ws_bytes,
+               asr_stream_t stream);
+/* r <- momentum r + (1 - momentum) batch for the running mean and variance (no debias), the   */
+/* batch moments taken from `moments` (shift as given to asr_bn_fwd_train; NULL: the running   */
+/* mean).  Skipped on the device when moments[0] <= 0 or when any of the four flag words (device */
+/* ints, NULL allowed; the sticky timeout words / all-reduced flag slots asr_optim_guard reads) */
+/* holds a non-zero bit pattern: a vetoed step leaves the statistics alone.                     */
+int asr_bn_update_running(float* running_mean, float* running_var, const float* moments,
+                          const float* shift, int C, float momentum, const int* flag_a,
+                          const int* flag_b, const int* flag_c, const int* flag_d,
+                          asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* K7  CTC loss + gradient.  Replaces core/ctc_utils.py:60-70 ->             */
