@@ -115,6 +115,16 @@ class RnnArgs(C.Structure):
                 ('dz_absmax', void_p)]
 
 
+class GruArgs(C.Structure):
+    _fields_ = [('T', C.c_int), ('n_pad', C.c_int), ('H', C.c_int), ('mode', C.c_int),
+                ('activation', C.c_int), ('clip', C.c_float),
+                ('U', void_p), ('mask_u', void_p), ('zx', void_p), ('h', void_p),
+                ('gates', void_p), ('rm', void_p),
+                ('y_sum', void_p), ('dy', void_p), ('dy_ld', C.c_int),
+                ('dy_dir_stride', C.c_int), ('da', void_p), ('db_part', void_p),
+                ('dz_absmax', void_p)]
+
+
 class Segment(C.Structure):
     _fields_ = [('offset', C.c_int64), ('len', C.c_int64), ('l2', C.c_float),
                 ('reserved', C.c_float)]
@@ -210,6 +220,10 @@ SIGNATURES = {
     'asr_rnn_seq_fwd': (C.c_int, [C.POINTER(RnnArgs), void_p, C.c_size_t, void_p]),
     'asr_rnn_seq_bwd': (C.c_int, [C.POINTER(RnnArgs), void_p, C.c_size_t, void_p]),
     'asr_rnn_plan': (C.c_int, [C.POINTER(RnnArgs), C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
+    'asr_gru_workspace_bytes': (C.c_size_t, [C.POINTER(GruArgs), C.c_int]),
+    'asr_gru_seq_fwd': (C.c_int, [C.POINTER(GruArgs), void_p, C.c_size_t, void_p]),
+    'asr_gru_seq_bwd': (C.c_int, [C.POINTER(GruArgs), void_p, C.c_size_t, void_p]),
+    'asr_gru_plan': (C.c_int, [C.POINTER(GruArgs), C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
     'asr_activation_fwd': (C.c_int, [void_p, void_p, C.c_int64, C.c_int, C.c_float, void_p]),
     'asr_activation_bwd': (C.c_int, [void_p, void_p, void_p, C.c_int64, C.c_int, C.c_float,
                                      void_p]),

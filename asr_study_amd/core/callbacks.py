@@ -84,6 +84,13 @@ def keras_layers(model, weights):
                 for part in LSTM_PARTS:
                     ws.append(('%s_simplernn_%d_%s:0' % (d, nb, part), next(it)))
             out.append(('bidirectional_%d' % nb, ws))
+        elif s.kind == 'bigru':     # Bidirectional(GRU), fused 'gpu' layout: W, U, b per direction
+            nb += 1
+            ws = []
+            for d in ('forward', 'backward'):
+                for part in LSTM_PARTS:
+                    ws.append(('%s_gru_%d_%s:0' % (d, nb, part), next(it)))
+            out.append(('bidirectional_%d' % nb, ws))
         elif s.kind == 'bn':        # keras.layers.BatchNormalization: gamma, beta, running moments
             nbn += 1
             out.append(('batchnormalization_%d' % nbn,

@@ -46,6 +46,19 @@ def _um2gm(a, H, Hp):
     return np.ascontiguousarray(np.swapaxes(u, -1, -2)).reshape(sh + (4 * H,))
 
 
+def _blocks_pad(a, H, Hp):
+    """(..., 3H) GRU column blocks z | r | h -> (..., 3Hp): each block zero padded to Hp."""
+    sh = a.shape[:-1]
+    out = np.zeros(sh + (3, Hp), a.dtype)
+    out[..., :H] = a.reshape(sh + (3, H))
+    return out.reshape(sh + (3 * Hp,))
+
+
+def _blocks_unpad(a, H, Hp):
+    sh = a.shape[:-1]
+    return np.ascontiguousarray(a.reshape(sh + (3, Hp))[..., :H]).reshape(sh + (3 * H,))
+
+
 # where a Model lives when the factory is given no ``device`` (host-only tests build on 'cpu':
 # weights I/O works there, every compute call still needs the HIP library and a GPU)
 DEFAULT_DEVICE = os.environ.get('ASR_DEVICE', 'cuda:0')
@@ -234,7 +247,7 @@ class Model(object):
                                      '(asr_conv2d_* keeps one plane shift per time tap)' % s.kt)
                 if s.st < 1 or s.sf < 1:
                     raise ValueError('conv stage: strides must be >= 1')
-                if s.st > 1 and any(p.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn')
+                if s.st > 1 and any(p.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn', 'bigru')
                                     for p in self.stages):
                     raise ValueError(
                         'conv stage with time stride %d behind a trainable stage: asr_conv2d_dgrad '
@@ -335,6 +348,31 @@ class Model(object):
                            np.zeros(s.H, np.float32)]
                 init.append((s, 'birnn', ws))
                 f_real, f_pad = (2 * s.H, 2 * s.Hp) if s.merge == 'concat' else (s.H, s.Hp)
+            elif s.kind == 'bigru':
+                # Bidirectional(GRU) (csrc/gru.hip): W (in, 2, 3Hp), U (2, Hp, 3Hp), b (2, 3Hp),
+                # column blocks z, r, h of Hp each
+                s.H = st['H']
+                s.Hp = _pad4(s.H)
+                s.merge = st.get('merge_mode', 'concat')
+                s.act = st.get('activation') or 'tanh'
+                s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
+                s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
+                s.oW = take(f_pad * 6 * s.Hp)
+                s.oU = take(2 * s.Hp * 3 * s.Hp)
+                s.ob = take(6 * s.Hp)
+                segs += [(s.oW, _pad4(f_pad * 6 * s.Hp), s.l2_W),
+                         (s.oU, _pad4(2 * s.Hp * 3 * s.Hp), s.l2_U), (s.ob, _pad4(6 * s.Hp), 0.0)]
+                ws = []
+                for _ in range(2):      # Keras-1.2.2 consume_less='gpu' init, as the BiLSTM stage
+                    lim = math.sqrt(6.0 / (f_real + 3 * s.H))
+                    W = rs.uniform(-lim, lim, size=(f_real, 3 * s.H))
+                    a = rs.normal(0.0, 1.0, (s.H, 3 * s.H))
+                    u, _, v = np.linalg.svd(a, full_matrices=False)
+                    U = 1.1 * (u if u.shape == (s.H, 3 * s.H) else v)
+                    ws += [W.astype(np.float32), U.astype(np.float32),
+                           np.zeros(3 * s.H, np.float32)]
+                init.append((s, 'bigru', ws))
+                f_real, f_pad = (2 * s.H, 2 * s.Hp) if s.merge == 'concat' else (s.H, s.Hp)
             elif s.kind == 'bn':
                 # BatchNormalization (csrc/batchnorm.hip): gamma, beta (C each) in the flat
                 # parameters (l2 0); running mean / variance in self.bn_running (not trainable);
@@ -420,9 +458,9 @@ class Model(object):
         for st in self.stages:
             if st is s:
                 break
-            if st.kind in ('dense', 'bilstm', 'conv', 'birnn'):
+            if st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bigru'):
                 prev = st
-        if (prev is not None and prev.kind in ('bilstm', 'birnn') and prev.Hp != prev.H
+        if (prev is not None and prev.kind in ('bilstm', 'birnn', 'bigru') and prev.Hp != prev.H
                 and getattr(prev, 'merge', 'concat') == 'concat'):
             idx = np.concatenate([np.arange(prev.H), prev.Hp + np.arange(prev.H)])
         else:
@@ -496,6 +534,21 @@ class Model(object):
                 host[s.oW:s.oW + Wp.size] = Wp.ravel()
                 host[s.oU:s.oU + Up.size] = Up.ravel()
                 host[s.ob:s.ob + bp.size] = bp.ravel()
+            elif s.kind == 'bigru':
+                rows = self._real_rows(s)
+                Wp = np.zeros((s.f_in_pad, 2, 3 * s.Hp), np.float32)
+                Up = np.zeros((2, s.Hp, 3 * s.Hp), np.float32)
+                bp = np.zeros((2, 3 * s.Hp), np.float32)
+                for d in range(2):          # Keras order: forward W, U, b, then backward
+                    W, U, b = [np.asarray(next(it), np.float32) for _ in range(3)]
+                    assert W.shape == (len(rows), 3 * s.H) and U.shape == (s.H, 3 * s.H), \
+                        (W.shape, U.shape)
+                    Wp[rows, d] = _blocks_pad(W, s.H, s.Hp)
+                    Up[d, :s.H] = _blocks_pad(U, s.H, s.Hp)
+                    bp[d] = _blocks_pad(b, s.H, s.Hp)
+                host[s.oW:s.oW + Wp.size] = Wp.ravel()
+                host[s.oU:s.oU + Up.size] = Up.ravel()
+                host[s.ob:s.ob + bp.size] = bp.ravel()
             elif s.kind == 'bn':            # Keras order: gamma, beta, running_mean, running_std
                 idx = self._bn_cols(s)
                 g, b, rm, rv = [np.asarray(next(it), np.float32).reshape(-1) for _ in range(4)]
@@ -563,6 +616,14 @@ class Model(object):
                 for d in range(2):
                     out += [Wp[rows, d, :s.H].copy(), Up[d, :s.H, :s.H].copy(),
                             bp[d, :s.H].copy()]
+            elif s.kind == 'bigru':
+                rows = self._real_rows(s)
+                Wp = flat[s.oW:s.oW + s.f_in_pad * 6 * s.Hp].reshape(s.f_in_pad, 2, 3 * s.Hp)
+                Up = flat[s.oU:s.oU + 2 * s.Hp * 3 * s.Hp].reshape(2, s.Hp, 3 * s.Hp)
+                bp = flat[s.ob:s.ob + 6 * s.Hp].reshape(2, 3 * s.Hp)
+                for d in range(2):
+                    out += [_blocks_unpad(Wp[rows, d], s.H, s.Hp),
+                            _blocks_unpad(Up[d, :s.H], s.H, s.Hp), _blocks_unpad(bp[d], s.H, s.Hp)]
             elif s.kind == 'bn':
                 idx = self._bn_cols(s)
                 out += [flat[s.og:s.og + s.C][idx].copy(), flat[s.obeta:s.obeta + s.C][idx].copy()]
@@ -930,9 +991,90 @@ class Model(object):
                                             act=s.act, mask_u=BU, y_sum=ysum, mode=self.lstm_mode)
                 rec['h'] = h
                 a = ysum if ysum is not None else h.view(T, n_pad, 2 * Hp)
+            elif s.kind == 'bigru':
+                a = self._gru_forward(s, si, a.contiguous(), rec, stage_masks(si)[:2], n_pad)
             rec['out'] = a
             self._acts.append(rec)
         return a
+
+    def _gru_forward(self, s, si, a, rec, masks, n_pad):
+        """Bidirectional(GRU) stage (csrc/gru.hip): zx = (a (.) B_W[d]) @ W_d + b_d from the
+        GEMMs, then the recurrence; h, the gates z | r | hh and r (.) m are kept for BPTT."""
+        T, Hp = a.shape[0], s.Hp
+        rows = T * n_pad
+        BW, BU = masks
+        rec['BW'], rec['BU'] = BW, BU
+        zx = self._buf('gzx%d' % si, (T, n_pad, 2, 3 * Hp))
+        bias = self._view(s.ob, 6 * Hp)
+        if BW is None:
+            ops.gemm(a, self.params, zx, rows, 6 * Hp, s.f_in_pad, b_off=s.oW, bias=bias)
+        else:
+            for d in range(2):
+                ops.gemm(a, self.params, zx, rows, 3 * Hp, s.f_in_pad, ldb=6 * Hp, ldc=6 * Hp,
+                         b_off=s.oW + d * 3 * Hp, c_off=d * 3 * Hp,
+                         bias=bias[d * 3 * Hp:(d + 1) * 3 * Hp], a_scale=BW[d],
+                         a_scale_period=n_pad)
+        h = self._buf('gh%d' % si, (T, n_pad, 2, Hp))
+        gates = self._buf('ggates%d' % si, (T, n_pad, 2, 3 * Hp))
+        rm = self._buf('grm%d' % si, (T, n_pad, 2, Hp))
+        ysum = self._buf('gsum%d' % si, (T, n_pad, Hp)) if s.merge == 'sum' else None
+        ops.gru_seq_fwd(zx, self._view(s.oU, 2 * Hp * 3 * Hp), h, gates, rm, T, n_pad, Hp,
+                        act=s.act, mask_u=BU, y_sum=ysum)
+        rec.update(h=h, gates=gates, rm=rm)
+        return ysum if ysum is not None else h.view(T, n_pad, 2 * Hp)
+
+    def _gru_backward(self, s, si, rec, da, first, split):
+        """BPTT of a GRU stage (csrc/gru.hip), then its weight gradients and dx from the GEMMs:
+        dU_z, dU_r [d] = (h_prev (.) B_U)^T [da_z | da_r], dU_h[d] = (r (.) m)^T da_h (r (.) m
+        kept by the forward pass), dW[d] = (x (.) B_W)^T da_d, db from the per-batch-tile sums,
+        dx = sum_d B_W[d] (.) (da_d @ W_d^T).  Returns dx (or None)."""
+        T, n_pad = da.shape[0], da.shape[1]
+        rows, Hp = T * n_pad, s.Hp
+        BW, BU, h, a_in = rec['BW'], rec['BU'], rec['h'], rec['in']
+        dg = self._buf('gda%d' % si, (T, n_pad, 2, 3 * Hp))
+        dbp = self._buf('gdbp%d' % si, (n_pad // 16, 2, 3 * Hp))
+        zmx = self._buf('gdamax%d' % si, (1,))
+        ops.gru_seq_bwd(da.contiguous(), self._view(s.oU, 2 * Hp * 3 * Hp), h, rec['gates'],
+                        dg, T, n_pad, Hp, act=s.act, mask_u=BU,
+                        shared_dy=s.merge == 'sum', db_part=dbp, dz_absmax=zmx)
+        ops.colsum(dbp, n_pad // 16, 6 * Hp, 6 * Hp, self._gview(s.ob, 6 * Hp))
+        kk = (T - 1) * n_pad
+        for d in range(2):
+            oU = s.oU + d * Hp * 3 * Hp
+            # h_prev is h one frame earlier in the direction's processing order
+            if kk > 0:
+                ops.gemm(h, dg, self.grads, Hp, 2 * Hp, kk, trans_a=True, lda=2 * Hp, ldb=6 * Hp,
+                         ldc=3 * Hp, a_off=d * Hp + (0 if d == 0 else n_pad * 2 * Hp),
+                         b_off=d * 3 * Hp + (n_pad * 6 * Hp if d == 0 else 0), c_off=oU,
+                         split_k=split, a_scale=None if BU is None else BU[d],
+                         a_scale_period=n_pad, b_absmax=zmx)
+            else:
+                self._gview(oU, Hp * 3 * Hp).view(Hp, 3 * Hp)[:, :2 * Hp].zero_()
+            ops.gemm(rec['rm'], dg, self.grads, Hp, Hp, rows, trans_a=True, lda=2 * Hp,
+                     ldb=6 * Hp, ldc=3 * Hp, a_off=d * Hp, b_off=d * 3 * Hp + 2 * Hp,
+                     c_off=oU + 2 * Hp, split_k=split, b_absmax=zmx)
+        a_in = a_in.contiguous()
+        if BW is None:
+            ops.gemm(a_in, dg, self.grads, s.f_in_pad, 6 * Hp, rows, trans_a=True, c_off=s.oW,
+                     split_k=split, b_absmax=zmx)
+        else:
+            for d in range(2):
+                ops.gemm(a_in, dg, self.grads, s.f_in_pad, 3 * Hp, rows, trans_a=True,
+                         ldb=6 * Hp, ldc=6 * Hp, b_off=d * 3 * Hp, c_off=s.oW + d * 3 * Hp,
+                         split_k=split, a_scale=BW[d], a_scale_period=n_pad, b_absmax=zmx)
+        if first:
+            return None
+        dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
+        if BW is None:
+            ops.gemm(dg, self.params, dx, rows, s.f_in_pad, 6 * Hp, trans_b=True, b_off=s.oW,
+                     a_absmax=zmx)
+        else:
+            for d in range(2):
+                ops.gemm(dg, self.params, dx, rows, s.f_in_pad, 3 * Hp, trans_b=True,
+                         lda=6 * Hp, ldb=6 * Hp, a_off=d * 3 * Hp, b_off=s.oW + d * 3 * Hp,
+                         c_scale=BW[d], c_scale_period=n_pad, beta=0.0 if d == 0 else 1.0,
+                         a_absmax=zmx)
+        return dx
 
     def _bn_forward(self, s, si, a, rec, training, n_real, bn_weight):
         """BatchNormalization stage: batch statistics of the n_real real rows in training (saved
@@ -1213,7 +1355,7 @@ class Model(object):
         stream id 4 * stage (B_W) / 4 * stage + 1 (B_U) at step self._step."""
         out = {}
         for si, s in enumerate(self.stages):
-            if s.kind not in ('bilstm', 'birnn') or not (s.dropout_W > 0 or s.dropout_U > 0):
+            if s.kind not in ('bilstm', 'birnn', 'bigru') or not (s.dropout_W > 0 or s.dropout_U > 0):
                 continue
             BW = self._buf('BW%d' % si, (2, n_pad, s.f_in_pad))
             BU = self._buf('BU%d' % si, (2, n_pad, s.Hp))
@@ -1306,7 +1448,7 @@ class Model(object):
                     da = ops.axpby(s.coef, da, 0.0, da, self._buf('dmerge%d' % si, da.shape))
                 skip_grads[s.skip] = da
                 continue
-            first = not any(st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn')
+            first = not any(st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn', 'bigru')
                             for st in self.stages[:si])
             if s.kind in ('noise', 'reshape'):
                 continue
@@ -1342,6 +1484,11 @@ class Model(object):
                 continue
             if s.kind == 'birnn':
                 dx = self._rnn_backward(s, si, rec, da, first, split)
+                if dx is not None:
+                    da = dx
+                continue
+            if s.kind == 'bigru':
+                dx = self._gru_backward(s, si, rec, da, first, split)
                 if dx is not None:
                     da = dx
                 continue

@@ -10,7 +10,9 @@ signature (core/layers.py:366-386: zoneout_h/zoneout_c/layer_norm/mi on top of t
 Keras LSTM arguments); of the optional variants the residual ``merge``, multiplicative
 integration, zoneout and layer normalisation are implemented.
 ``SimpleRNN`` (Bidirectional, 'concat' or 'sum'), ``Activation`` and ``recurrent()`` serve the
-maas / deep_speech factories (core/models.py).  ``BatchNormalization`` (mode 0, axis -1) runs
+maas / deep_speech factories (core/models.py).  ``GRU`` (Keras 1.2.2, consume_less='gpu' layout,
+hard_sigmoid gates, Bidirectional 'concat' or 'sum') runs on csrc/gru.hip and is deep_speech2's
+``rnn_type='gru'`` cell.  ``BatchNormalization`` (mode 0, axis -1) runs
 bare or on the (N, T, F, C) image of the convolution front-end (csrc/batchnorm.hip).
 """
 
@@ -170,6 +172,57 @@ class SimpleRNN(object):
         self.l2_U = U_regularizer.l2 if U_regularizer is not None else 0.0
 
 
+class GRU(object):
+    """keras.layers.GRU (Keras 1.2.2) in the fused consume_less='gpu' layout: W (F, 3H), U (H, 3H),
+    b (3H) with the column blocks z, r, h; with m = h_prev (.) B_U,
+    z = hs(x_z + m U_z), r = hs(x_r + m U_r), hh = act(x_h + (r (.) m) U_h),
+    h = z h_prev + (1 - z) hh, h_0 = 0 (the reset gate is applied before the product).
+
+    Implemented: init='glorot_uniform' over the fused shape, inner_init='orthogonal' (x 1.1, as the
+    LSTM's U), b = 0; activation 'tanh', 'relu', 'linear' or ``clipped_relu(max_value)``;
+    inner_activation='hard_sigmoid'; W_regularizer / U_regularizer l2; variational dropout_W /
+    dropout_U (one mask per sample, feature and direction, as Keras' 'gpu' mode uses mask 0 of its
+    three); return_sequences=True.  Runs on csrc/gru.hip."""
+
+    IMPLEMENTED = ("output_dim, init='glorot_uniform', inner_init='orthogonal', activation in "
+                   "(tanh, relu, linear, clipped_relu(v)), inner_activation='hard_sigmoid', "
+                   "W_regularizer / U_regularizer l2, dropout_W, dropout_U, return_sequences=True, "
+                   "consume_less='gpu'")
+
+    def __init__(self, output_dim, init='glorot_uniform', inner_init='orthogonal',
+                 activation='tanh', inner_activation='hard_sigmoid', W_regularizer=None,
+                 U_regularizer=None, b_regularizer=None, dropout_W=0., dropout_U=0.,
+                 return_sequences=True, consume_less='gpu', **kwargs):
+        def refuse(what):
+            raise NotImplementedError('GRU %s (implemented: %s)' % (what, self.IMPLEMENTED))
+        if init != 'glorot_uniform':
+            refuse('init %r' % (init,))
+        if inner_init != 'orthogonal':
+            refuse('inner_init %r' % (inner_init,))
+        if inner_activation != 'hard_sigmoid':
+            refuse('inner_activation %r' % (inner_activation,))
+        if b_regularizer is not None:
+            refuse('b_regularizer')
+        if not return_sequences:
+            refuse('return_sequences=False')
+        if consume_less != 'gpu':
+            refuse('consume_less %r' % (consume_less,))
+        if kwargs:
+            refuse('argument(s) %s' % ', '.join(sorted(kwargs)))
+        from .. import ops
+        try:
+            ops.rnn_activation_id(activation)
+        except NotImplementedError:
+            refuse('activation %r' % (activation,))
+        self.activation = activation
+        self.init, self.inner_init, self.inner_activation = init, inner_init, inner_activation
+        self.output_dim = int(output_dim)
+        self.dropout_W = float(dropout_W or 0.0)
+        self.dropout_U = float(dropout_U or 0.0)
+        self.l2_W = W_regularizer.l2 if W_regularizer is not None else 0.0
+        self.l2_U = U_regularizer.l2 if U_regularizer is not None else 0.0
+
+
 class Activation(Layer):
     """keras.layers.Activation: 'tanh', 'relu', 'linear' or ``clipped_relu(max_value)``,
     element-wise (bare or inside TimeDistributed)."""
@@ -184,8 +237,12 @@ def recurrent(output_dim, model='keras_lstm', activation='tanh', regularizer=Non
               **kwargs):
     """The reference's recurrent-layer factory (core/layers.py:482-516): 'rnn' -> SimpleRNN,
     'lstm' / 'keras_lstm' -> LSTM, with W and U regularised by ``regularizer`` and dropout_W =
-    dropout_U = ``dropout``; 'gru' and 'rhn' are not implemented."""
-    if model in ('gru', 'rhn'):
+    dropout_U = ``dropout``.  'gru' is not routed here yet: build the layer with ``GRU(...)``
+    (this module) directly; 'rhn' is not implemented."""
+    if model == 'gru':
+        raise NotImplementedError("recurrent(model='gru') is not routed yet: use "
+                                  'layers.GRU(output_dim, ...) directly')
+    if model == 'rhn':
         raise NotImplementedError('recurrent(model=%r): only rnn, lstm, keras_lstm' % (model,))
     common = dict(W_regularizer=regularizer, U_regularizer=regularizer, dropout_W=dropout,
                   dropout_U=dropout, activation=activation, return_sequences=True)
@@ -197,12 +254,12 @@ def recurrent(output_dim, model='keras_lstm', activation='tanh', regularizer=Non
 
 
 class Bidirectional(Layer):
-    """keras.layers.Bidirectional: LSTM with merge_mode='concat'; SimpleRNN with 'concat'
+    """keras.layers.Bidirectional: LSTM with merge_mode='concat'; SimpleRNN and GRU with 'concat'
     ([h_f | h_b]) or 'sum' (h_f + h_b)."""
 
     def __init__(self, layer, merge_mode='concat'):
-        assert isinstance(layer, (LSTM, SimpleRNN))
-        allowed = ('concat', 'sum') if isinstance(layer, SimpleRNN) else ('concat',)
+        assert isinstance(layer, (LSTM, SimpleRNN, GRU))
+        allowed = ('concat', 'sum') if isinstance(layer, (SimpleRNN, GRU)) else ('concat',)
         if merge_mode not in allowed:
             raise NotImplementedError('merge_mode=%r' % merge_mode)
         self.lstm = layer

@@ -1,6 +1,6 @@
 """Model factories with the reference's names and hyper-parameters
 (core/models.py): ``ctc_model``, ``graves2006``, ``eyben``, ``maas``, ``deep_speech``,
-``brsmv1``, plus this build's ``deep_speech2``.
+``brsmv1``, plus this build's ``deep_speech2`` (BiLSTM or, with ``rnn_type='gru'``, BiGRU).
 
 ``train.py`` resolves them by name -- ``get_from_module('core.models', 'brsmv1')
 (**hparams)`` (train.py:127-129) -- and gets back an object with the Keras
@@ -14,7 +14,7 @@ from . import ctc_utils
 from .engine import Model
 from .layers import (Input, GaussianNoise, TimeDistributed, Dense, LSTM, Bidirectional,
                      Dropout, Merge, merge, l2, Reshape, Convolution2D, clipped_relu, SimpleRNN,
-                     Activation, BatchNormalization)
+                     Activation, BatchNormalization, GRU)
 
 
 def ctc_model(inputs, output, **kwargs):
@@ -64,6 +64,11 @@ def ctc_model(inputs, output, **kwargs):
             r = layer.lstm
             spec.append({'type': 'birnn', 'H': r.output_dim, 'merge_mode': layer.merge_mode,
                          'activation': r.activation, 'init': r.init, 'dropout_W': r.dropout_W,
+                         'dropout_U': r.dropout_U, 'l2_W': r.l2_W, 'l2_U': r.l2_U})
+        elif isinstance(layer, Bidirectional) and isinstance(layer.lstm, GRU):
+            r = layer.lstm
+            spec.append({'type': 'bigru', 'H': r.output_dim, 'merge_mode': layer.merge_mode,
+                         'activation': r.activation, 'dropout_W': r.dropout_W,
                          'dropout_U': r.dropout_U, 'l2_W': r.l2_W, 'l2_U': r.l2_U})
         elif isinstance(layer, Bidirectional):
             r = layer.lstm
@@ -212,7 +217,7 @@ def brsmv1(num_features=39, num_classes=28, num_hiddens=256, num_layers=5,
 def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
                  conv_filters=32, conv_kernels=((11, 41), (11, 21)), conv_strides=((2, 2), (1, 2)),
                  max_value=20, dropout=0.2, weight_decay=1e-4, input_std_noise=.0,
-                 batch_norm=False, **kw):
+                 batch_norm=False, rnn_type='lstm', **kw):
     """BASELINE.json configs[2]: "DeepSpeech2-style 5xBiLSTM(512) + 2 conv front-end, 80-dim
     log-mel".  NO REFERENCE COUNTERPART: the reference lists Deep Speech 2 as TODO
     (README.md:118) and its ``deep_speech`` factory (core/models.py:148-214) is dead code
@@ -227,7 +232,14 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
     (per channel) and Activation(clipped_relu(max_value)); a BatchNormalization also goes in
     front of every Bidirectional(LSTM).  That normalises the layer INPUT x, not the input
     projection W x of the published Deep Speech 2 (sequence-wise BN inside the recurrent layer),
-    and its statistics include the time-padding frames, as Keras sees the zero-padded batch."""
+    and its statistics include the time-padding frames, as Keras sees the zero-padded batch.
+
+    rnn_type='gru': every Bidirectional(LSTM) becomes a Bidirectional(GRU) (the cell of the
+    published Deep Speech 2; Keras-1.2.2 GRU on csrc/gru.hip) with the same regularisers and
+    dropouts; it composes with batch_norm."""
+    if rnn_type not in ('lstm', 'gru'):
+        raise ValueError("deep_speech2: rnn_type %r ('lstm' or 'gru')" % (rnn_type,))
+    cell = GRU if rnn_type == 'gru' else LSTM
     x = Input(name='inputs', shape=(None, num_features))
     o = x
     if input_std_noise is not None:
@@ -244,7 +256,7 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
     for _ in range(num_layers):
         if batch_norm:
             o = BatchNormalization()(o)
-        o = Bidirectional(LSTM(num_hiddens, return_sequences=True,
+        o = Bidirectional(cell(num_hiddens, return_sequences=True,
                                W_regularizer=l2(weight_decay), U_regularizer=l2(weight_decay),
                                dropout_W=dropout, dropout_U=dropout))(o)
     o = TimeDistributed(Dense(num_classes, W_regularizer=l2(weight_decay)))(o)
@@ -257,5 +269,7 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
         input_std_noise=input_std_noise)}
     if batch_norm:          # (only then: default checkpoints keep their config byte for byte)
         model.config['kwargs']['batch_norm'] = True
+    if rnn_type != 'lstm':  # (likewise)
+        model.config['kwargs']['rnn_type'] = rnn_type
     return model
 

@@ -380,6 +380,70 @@ def activation_bwd(dy, y, dx, act):
     return dx
 
 
+# --------------------------------------------------------------------------- GRU (K16)
+GRU_WS = ('gru_fwd', 'gru_bwd')     # scratch only: the stepwise form has no status words
+
+
+def _gru_args(T, n_pad, H, U, h, gates, act, mode, mask_u=None):
+    a = L.GruArgs()
+    a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
+    a.activation, a.clip = rnn_activation_id(act)
+    a.U, a.h, a.gates = U.data_ptr(), h.data_ptr(), gates.data_ptr()
+    a.mask_u = mask_u.data_ptr() if mask_u is not None else None
+    return a
+
+
+def gru_seq_fwd(zx, U, h, gates, rm, T, n_pad, H, act='tanh', mask_u=None, y_sum=None, mode=0):
+    """Both directions of a GRU layer: h (T, n_pad, 2, H), gates (T, n_pad, 2, 3H) = z | r | hh and
+    rm (T, n_pad, 2, H) = r (.) h_prev (.) B_U from zx = x@W + b (T, n_pad, 2, 3H), U (2, H, 3H),
+    optional B_U (2, n_pad, H); y_sum (T, n_pad, H) <- h_f + h_b when given.
+    mode: 0 = the library's form, 1 = stepwise (the only form there is)."""
+    lib = L.load()
+    _check_f32(zx, U, h, gates, rm, mask_u, y_sum)
+    a = _gru_args(T, n_pad, H, U, h, gates, act, mode, mask_u)
+    a.zx, a.rm = zx.data_ptr(), rm.data_ptr()
+    a.y_sum = y_sum.data_ptr() if y_sum is not None else None
+    nbytes = lib.asr_gru_workspace_bytes(C.byref(a), 0)
+    if nbytes == 0:
+        L.check(-1, 'asr_gru_workspace_bytes')
+    ws = WS.get(GRU_WS[0], nbytes, zx.device)
+    L.check(lib.asr_gru_seq_fwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_gru_seq_fwd')
+    return ws
+
+
+def gru_seq_bwd(dy, U, h, gates, da, T, n_pad, H, act='tanh', mask_u=None, shared_dy=False,
+                mode=0, db_part=None, dz_absmax=None):
+    """BPTT of both directions: da (T, n_pad, 2, 3H) = da_z | da_r | da_h, the gradient of the
+    gate pre-activations.  dy is the gradient of the layer output: (T, n_pad, 2H) for 'concat',
+    (T, n_pad, H) shared by both directions for 'sum' (shared_dy).  db_part (n_pad/16, 2, 3H):
+    per-batch-tile sums of da; dz_absmax (1,): max |da|."""
+    lib = L.load()
+    _check_f32(dy, U, h, gates, da, mask_u, db_part, dz_absmax)
+    a = _gru_args(T, n_pad, H, U, h, gates, act, mode, mask_u)
+    a.dy, a.da = dy.data_ptr(), da.data_ptr()
+    a.dy_ld, a.dy_dir_stride = (int(H), 0) if shared_dy else (2 * int(H), int(H))
+    a.db_part = db_part.data_ptr() if db_part is not None else None
+    a.dz_absmax = dz_absmax.data_ptr() if dz_absmax is not None else None
+    nbytes = lib.asr_gru_workspace_bytes(C.byref(a), 1)
+    if nbytes == 0:
+        L.check(-1, 'asr_gru_workspace_bytes')
+    ws = WS.get(GRU_WS[1], nbytes, dy.device)
+    L.check(lib.asr_gru_seq_bwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_gru_seq_bwd')
+    return ws
+
+
+def gru_plan(T, n_pad, H, backward=False, mode=0):
+    """{'persistent': False, 'rows': batch rows, 'units': output columns per workgroup, 'blocks':
+    workgroups of the widest launch of a step} (asr_gru_plan)."""
+    a = L.GruArgs()
+    a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
+    per, rows, units, blocks = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    L.check(L.load().asr_gru_plan(C.byref(a), int(bool(backward)), C.byref(per), C.byref(rows),
+                                  C.byref(units), C.byref(blocks)), 'asr_gru_plan')
+    return {'persistent': bool(per.value), 'rows': rows.value, 'units': units.value,
+            'blocks': blocks.value}
+
+
 # --------------------------------------------------------------------------- BatchNormalization
 def bn_stats_len(C):
     """Floats of a stage's stats block: [mean_hi | mean_lo | invstd | var] (C each)."""

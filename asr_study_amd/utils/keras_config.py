@@ -87,6 +87,21 @@ def _simplernn_config(name, s):
     return cfg
 
 
+def _gru_config(name, s):
+    """keras.layers.GRU.get_config() (Recurrent + GRU), consume_less='gpu'."""
+    act, mv = _act_name(s.act)
+    cfg = {'name': name, 'trainable': True, 'return_sequences': True, 'go_backwards': False,
+           'stateful': False, 'unroll': False, 'consume_less': 'gpu', 'input_dim': int(s.f_in),
+           'input_length': None, 'output_dim': int(s.H), 'init': 'glorot_uniform',
+           'inner_init': 'orthogonal', 'activation': act, 'inner_activation': 'hard_sigmoid',
+           'W_regularizer': _regularizer(s.l2_W), 'U_regularizer': _regularizer(s.l2_U),
+           'b_regularizer': None, 'dropout_W': float(s.dropout_W),
+           'dropout_U': float(s.dropout_U)}
+    if mv is not None:
+        cfg['max_value'] = mv
+    return cfg
+
+
 def _lambda_config(name, function, output_shape, arguments):
     return {'name': name, 'trainable': True, 'function': function, 'function_type': 'function',
             'output_shape': output_shape[0], 'output_shape_type': output_shape[1],
@@ -159,6 +174,12 @@ def model_config(model):
                 'name': name, 'trainable': True, 'merge_mode': s.merge,
                 'layer': {'class_name': 'SimpleRNN', 'config': _simplernn_config(
                     'simplernn_%d' % counts['bidirectional'], s)}}, [prev])
+        elif s.kind == 'bigru':
+            name = nm('bidirectional')
+            add('Bidirectional', name, {
+                'name': name, 'trainable': True, 'merge_mode': s.merge,
+                'layer': {'class_name': 'GRU', 'config': _gru_config(
+                    'gru_%d' % counts['bidirectional'], s)}}, [prev])
         elif s.kind == 'bn':
             name = nm('batchnormalization')
             add('BatchNormalization', name, {
@@ -301,6 +322,16 @@ def topology_from_config(text):
                 inner_init=r.get('inner_init', 'orthogonal'), activation=_act_from(r),
                 W_regularizer=reg(r.get('W_regularizer')), U_regularizer=reg(r.get('U_regularizer')),
                 dropout_W=r.get('dropout_W', 0.), dropout_U=r.get('dropout_U', 0.)),
+                merge_mode=c.get('merge_mode', 'concat'))(o)
+        elif kind == 'Bidirectional' and c['layer']['class_name'] == 'GRU':
+            r = c['layer']['config']
+            o = L.Bidirectional(L.GRU(
+                r['output_dim'], init=r.get('init', 'glorot_uniform'),
+                inner_init=r.get('inner_init', 'orthogonal'), activation=_act_from(r),
+                inner_activation=r.get('inner_activation', 'hard_sigmoid'),
+                W_regularizer=reg(r.get('W_regularizer')), U_regularizer=reg(r.get('U_regularizer')),
+                dropout_W=r.get('dropout_W', 0.), dropout_U=r.get('dropout_U', 0.),
+                consume_less=r.get('consume_less', 'gpu')),
                 merge_mode=c.get('merge_mode', 'concat'))(o)
         elif kind == 'TimeDistributed':
             d = c['layer']['config']

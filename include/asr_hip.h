@@ -52,7 +52,8 @@ const char* asr_last_error(void);
  * 100: rounds 1-4.  105: asr_lstm_args +compact +activation +fwd_units, asr_pack_args +mask2
  * +r2_hl, asr_lstm_ln_args +activation.  106: asr_lstm_args +dz_hl +dz_bound +dz_scale_out.
  * 107: asr_rnn_args and the asr_rnn_* / asr_activation_* entry points (K14); the asr_bn_*
- * entry points (K15: plain scalar arguments, no struct, so the version stays). */
+ * entry points (K15: plain scalar arguments, no struct, so the version stays); asr_gru_args
+ * and the asr_gru_* entry points (K16: additions only, no existing layout changes). */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -482,6 +483,55 @@ int asr_activation_fwd(const float* x, float* y, int64_t n, int activation, floa
                        asr_stream_t stream);
 int asr_activation_bwd(const float* dy, const float* y, float* dx, int64_t n, int activation,
                        float clip, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K16 GRU recurrence of a Bidirectional layer (Keras 1.2.2 GRU.step,        */
+/* consume_less='gpu', inner_activation='hard_sigmoid'; csrc/gru.hip).       */
+/* U = [U_z | U_r | U_h] (H, 3H) per direction, zx = x @ W + b in the same   */
+/* column order, m = h_prev (.) mask_u, hs(a) = clip(0.2 a + 0.5, 0, 1):     */
+/*   z = hs(zx_z + m U_z), r = hs(zx_r + m U_r), hh = act(zx_h + (r (.) m)   */
+/*   U_h), h = z (.) h_prev + (1 - z) (.) hh   (reset gate BEFORE the        */
+/* product).  Direction 1 walks the padded slab from T-1 down to 0; all      */
+/* slabs stay in frame order.  BPTT, g = dy + carry:                         */
+/*   da_h = g (1 - z) act'(hh), da_z = g (h_prev - hh) hs'(z),               */
+/*   q = da_h U_h^T, da_r = q m hs'(r),                                      */
+/*   carry = g z + (q r + [da_z | da_r] [U_z | U_r]^T) (.) mask_u            */
+/* with hs' = 0.2 where 0 < gate < 1 else 0, read from the SAVED gates, and  */
+/* act' from hh alone.  dW, dU (dU_z, dU_r from m, dU_h from rm), db, dx     */
+/* come from asr_gemm / asr_colsum.  Exact fp32 products, no float atomics   */
+/* (repeats are bit-identical).  Stepwise only: two launches per step.       */
+/* ------------------------------------------------------------------------ */
+typedef struct asr_gru_args {
+  int T, n_pad, H;       /* H: padded width, a multiple of 4; n_pad a multiple of 16    */
+  int mode;              /* 0 = the plan's form, 1 = stepwise; 2 (persistent) does not   */
+                         /* exist for this cell: ASR_ERR_INVALID                         */
+  int activation;        /* 0 tanh, 1 relu, 4 linear, ASR_ACT_CLIPPED_RELU              */
+  float clip;            /* max_value of the clipped relu                               */
+  const float* U;        /* (2, H, 3H) per direction, Keras [in][out], blocks z, r, h   */
+  const float* mask_u;   /* optional (2, n_pad, H) B_U, constant over time               */
+  const float* zx;       /* forward: (T, n_pad, 2, 3H) = x @ W + b                       */
+  float* h;              /* (T, n_pad, 2, H): forward writes it, BPTT reads it           */
+  float* gates;          /* (T, n_pad, 2, 3H) z | r | hh: forward writes, BPTT reads     */
+  float* rm;             /* forward: (T, n_pad, 2, H) r (.) m, written (left operand of  */
+                         /*   dU_h; 0 at each direction's first processed frame)         */
+  float* y_sum;          /* forward, optional: (T, n_pad, H) = h_f + h_b ('sum' merge)   */
+  const float* dy;       /* BPTT: gradient of the layer output, row (t, n) at dy_ld      */
+  int dy_ld;             /*   floats per (t, n) row: 2H (concat) or H (sum)              */
+  int dy_dir_stride;     /*   floats between the two directions' dy: H (concat), 0 (sum) */
+  float* da;             /* BPTT: (T, n_pad, 2, 3H) da_z | da_r | da_h                   */
+  float* db_part;        /* BPTT, optional: (n_pad/16, 2, 3H) per-batch-tile sums of da  */
+  float* dz_absmax;      /* BPTT, optional: max |da| (written, not accumulated)          */
+} asr_gru_args;
+/* Workspace: scratch only (BPTT: U^T and two (n_pad, 2, H) vectors); no status words.       */
+size_t asr_gru_workspace_bytes(const asr_gru_args* a, int backward);
+int asr_gru_seq_fwd(const asr_gru_args* a, void* workspace, size_t ws_bytes,
+                    asr_stream_t stream);
+int asr_gru_seq_bwd(const asr_gru_args* a, void* workspace, size_t ws_bytes,
+                    asr_stream_t stream);
+/* The form the library runs (persistent: always 0) and its geometry: batch rows and output   */
+/* columns per workgroup, workgroups of the widest launch of a step (both directions).        */
+int asr_gru_plan(const asr_gru_args* a, int backward, int* persistent, int* rows, int* units,
+                 int* blocks);
 
 /* ------------------------------------------------------------------------ */
 /* K15 BatchNormalization (Keras 1.2.2, mode 0, axis -1; csrc/batchnorm.hip) */
