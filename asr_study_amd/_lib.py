@@ -125,6 +125,17 @@ class GruArgs(C.Structure):
                 ('dz_absmax', void_p)]
 
 
+class RhnArgs(C.Structure):
+    _fields_ = [('T', C.c_int), ('n_pad', C.c_int), ('H', C.c_int), ('depth', C.c_int),
+                ('coupling', C.c_int), ('mode', C.c_int),
+                ('activation', C.c_int), ('clip', C.c_float),
+                ('U', void_p), ('b', void_p), ('mask_u', void_p), ('zx', void_p), ('h', void_p),
+                ('gates', void_p),
+                ('y_sum', void_p), ('dy', void_p), ('dy_ld', C.c_int),
+                ('dy_dir_stride', C.c_int), ('da', void_p), ('db_part', void_p),
+                ('dz_absmax', void_p)]
+
+
 class Segment(C.Structure):
     _fields_ = [('offset', C.c_int64), ('len', C.c_int64), ('l2', C.c_float),
                 ('reserved', C.c_float)]
@@ -224,6 +235,10 @@ SIGNATURES = {
     'asr_gru_seq_fwd': (C.c_int, [C.POINTER(GruArgs), void_p, C.c_size_t, void_p]),
     'asr_gru_seq_bwd': (C.c_int, [C.POINTER(GruArgs), void_p, C.c_size_t, void_p]),
     'asr_gru_plan': (C.c_int, [C.POINTER(GruArgs), C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
+    'asr_rhn_workspace_bytes': (C.c_size_t, [C.POINTER(RhnArgs), C.c_int]),
+    'asr_rhn_seq_fwd': (C.c_int, [C.POINTER(RhnArgs), void_p, C.c_size_t, void_p]),
+    'asr_rhn_seq_bwd': (C.c_int, [C.POINTER(RhnArgs), void_p, C.c_size_t, void_p]),
+    'asr_rhn_plan': (C.c_int, [C.POINTER(RhnArgs), C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
     'asr_activation_fwd': (C.c_int, [void_p, void_p, C.c_int64, C.c_int, C.c_float, void_p]),
     'asr_activation_bwd': (C.c_int, [void_p, void_p, void_p, C.c_int64, C.c_int, C.c_float,
                                      void_p]),

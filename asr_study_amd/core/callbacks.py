@@ -91,6 +91,15 @@ def keras_layers(model, weights):
                 for part in LSTM_PARTS:
                     ws.append(('%s_gru_%d_%s:0' % (d, nb, part), next(it)))
             out.append(('bidirectional_%d' % nb, ws))
+        elif s.kind == 'birhn':     # Bidirectional(RHN): '<name>_W', '<name>_<l>_U', '<name>_<l>_b'
+            nb += 1
+            ws = []
+            for d in ('forward', 'backward'):
+                ws.append(('%s_rhn_%d_W:0' % (d, nb), next(it)))
+                for part in ('U', 'b'):
+                    for l in range(s.depth):
+                        ws.append(('%s_rhn_%d_%d_%s:0' % (d, nb, l, part), next(it)))
+            out.append(('bidirectional_%d' % nb, ws))
         elif s.kind == 'bn':        # keras.layers.BatchNormalization: gamma, beta, running moments
             nbn += 1
             out.append(('batchnormalization_%d' % nbn,

@@ -59,6 +59,19 @@ def _blocks_unpad(a, H, Hp):
     return np.ascontiguousarray(a.reshape(sh + (3, Hp))[..., :H]).reshape(sh + (3 * H,))
 
 
+def _cblocks_pad(a, H, Hp, C):
+    """(..., C H) RHN column blocks h | t | [c] -> (..., C Hp): each block zero padded to Hp."""
+    sh = a.shape[:-1]
+    out = np.zeros(sh + (C, Hp), a.dtype)
+    out[..., :H] = a.reshape(sh + (C, H))
+    return out.reshape(sh + (C * Hp,))
+
+
+def _cblocks_unpad(a, H, Hp, C):
+    sh = a.shape[:-1]
+    return np.ascontiguousarray(a.reshape(sh + (C, Hp))[..., :H]).reshape(sh + (C * H,))
+
+
 # where a Model lives when the factory is given no ``device`` (host-only tests build on 'cpu':
 # weights I/O works there, every compute call still needs the HIP library and a GPU)
 DEFAULT_DEVICE = os.environ.get('ASR_DEVICE', 'cuda:0')
@@ -247,8 +260,8 @@ class Model(object):
                                      '(asr_conv2d_* keeps one plane shift per time tap)' % s.kt)
                 if s.st < 1 or s.sf < 1:
                     raise ValueError('conv stage: strides must be >= 1')
-                if s.st > 1 and any(p.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn', 'bigru')
-                                    for p in self.stages):
+                if s.st > 1 and any(p.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn', 'bigru',
+                                                   'birhn') for p in self.stages):
                     raise ValueError(
                         'conv stage with time stride %d behind a trainable stage: asr_conv2d_dgrad '
                         'exists for time stride 1 only, so a time-strided convolution must be the '
@@ -373,6 +386,38 @@ class Model(object):
                            np.zeros(3 * s.H, np.float32)]
                 init.append((s, 'bigru', ws))
                 f_real, f_pad = (2 * s.H, 2 * s.Hp) if s.merge == 'concat' else (s.H, s.Hp)
+            elif s.kind == 'birhn':
+                # Bidirectional(RHN) (csrc/rhn.hip): W (in, 2, C Hp), U (2, L, Hp, C Hp),
+                # b (2, L, C Hp), column blocks h, t [, c] of Hp each (C = 2 when coupled)
+                s.H = st['H']
+                s.Hp = _pad4(s.H)
+                s.depth = int(st.get('depth', 1))
+                s.coupling = bool(st.get('coupling', True))
+                s.nblk = 2 if s.coupling else 3
+                s.merge = st.get('merge_mode', 'concat')
+                s.act = st.get('activation') or 'tanh'
+                s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
+                s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
+                Wd = s.nblk * s.Hp
+                s.oW = take(f_pad * 2 * Wd)
+                s.oU = take(2 * s.depth * s.Hp * Wd)
+                s.ob = take(2 * s.depth * Wd)
+                segs += [(s.oW, _pad4(f_pad * 2 * Wd), s.l2_W),
+                         (s.oU, _pad4(2 * s.depth * s.Hp * Wd), s.l2_U),
+                         (s.ob, _pad4(2 * s.depth * Wd), 0.0)]
+                ws = []
+                for _ in range(2):      # the reference's RHN.build: init, inner_init, highway bias
+                    lim = math.sqrt(6.0 / (f_real + s.nblk * s.H))
+                    ws.append(rs.uniform(-lim, lim, size=(f_real, s.nblk * s.H)).astype(np.float32))
+                    for _l in range(s.depth):
+                        a = rs.normal(0.0, 1.0, (s.H, s.nblk * s.H))
+                        u, _, v = np.linalg.svd(a, full_matrices=False)
+                        ws.append((1.1 * (u if u.shape == a.shape else v)).astype(np.float32))
+                    b = np.zeros(s.nblk * s.H, np.float32)
+                    b[s.H:] = -2.0              # highway_bias_initializer on t (and c)
+                    ws += [b.copy() for _l in range(s.depth)]
+                init.append((s, 'birhn', ws))
+                f_real, f_pad = (2 * s.H, 2 * s.Hp) if s.merge == 'concat' else (s.H, s.Hp)
             elif s.kind == 'bn':
                 # BatchNormalization (csrc/batchnorm.hip): gamma, beta (C each) in the flat
                 # parameters (l2 0); running mean / variance in self.bn_running (not trainable);
@@ -458,9 +503,10 @@ class Model(object):
         for st in self.stages:
             if st is s:
                 break
-            if st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bigru'):
+            if st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bigru', 'birhn'):
                 prev = st
-        if (prev is not None and prev.kind in ('bilstm', 'birnn', 'bigru') and prev.Hp != prev.H
+        if (prev is not None and prev.kind in ('bilstm', 'birnn', 'bigru', 'birhn')
+                and prev.Hp != prev.H
                 and getattr(prev, 'merge', 'concat') == 'concat'):
             idx = np.concatenate([np.arange(prev.H), prev.Hp + np.arange(prev.H)])
         else:
@@ -549,6 +595,25 @@ class Model(object):
                 host[s.oW:s.oW + Wp.size] = Wp.ravel()
                 host[s.oU:s.oU + Up.size] = Up.ravel()
                 host[s.ob:s.ob + bp.size] = bp.ravel()
+            elif s.kind == 'birhn':
+                rows = self._real_rows(s)
+                Ld, Cb, Wd = s.depth, s.nblk, s.nblk * s.Hp
+                Wp = np.zeros((s.f_in_pad, 2, Wd), np.float32)
+                Up = np.zeros((2, Ld, s.Hp, Wd), np.float32)
+                bp = np.zeros((2, Ld, Wd), np.float32)     # (pad entries stay 0, not -2)
+                for d in range(2):          # per direction: W, U_0 .. U_{L-1}, b_0 .. b_{L-1}
+                    W = np.asarray(next(it), np.float32)
+                    assert W.shape == (len(rows), Cb * s.H), W.shape
+                    Wp[rows, d] = _cblocks_pad(W, s.H, s.Hp, Cb)
+                    for l in range(Ld):
+                        U = np.asarray(next(it), np.float32)
+                        assert U.shape == (s.H, Cb * s.H), U.shape
+                        Up[d, l, :s.H] = _cblocks_pad(U, s.H, s.Hp, Cb)
+                    for l in range(Ld):
+                        bp[d, l] = _cblocks_pad(np.asarray(next(it), np.float32), s.H, s.Hp, Cb)
+                host[s.oW:s.oW + Wp.size] = Wp.ravel()
+                host[s.oU:s.oU + Up.size] = Up.ravel()
+                host[s.ob:s.ob + bp.size] = bp.ravel()
             elif s.kind == 'bn':            # Keras order: gamma, beta, running_mean, running_std
                 idx = self._bn_cols(s)
                 g, b, rm, rv = [np.asarray(next(it), np.float32).reshape(-1) for _ in range(4)]
@@ -624,6 +689,16 @@ class Model(object):
                 for d in range(2):
                     out += [_blocks_unpad(Wp[rows, d], s.H, s.Hp),
                             _blocks_unpad(Up[d, :s.H], s.H, s.Hp), _blocks_unpad(bp[d], s.H, s.Hp)]
+            elif s.kind == 'birhn':
+                rows = self._real_rows(s)
+                Ld, Cb, Wd = s.depth, s.nblk, s.nblk * s.Hp
+                Wp = flat[s.oW:s.oW + s.f_in_pad * 2 * Wd].reshape(s.f_in_pad, 2, Wd)
+                Up = flat[s.oU:s.oU + 2 * Ld * s.Hp * Wd].reshape(2, Ld, s.Hp, Wd)
+                bp = flat[s.ob:s.ob + 2 * Ld * Wd].reshape(2, Ld, Wd)
+                for d in range(2):
+                    out.append(_cblocks_unpad(Wp[rows, d], s.H, s.Hp, Cb))
+                    out += [_cblocks_unpad(Up[d, l, :s.H], s.H, s.Hp, Cb) for l in range(Ld)]
+                    out += [_cblocks_unpad(bp[d, l], s.H, s.Hp, Cb) for l in range(Ld)]
             elif s.kind == 'bn':
                 idx = self._bn_cols(s)
                 out += [flat[s.og:s.og + s.C][idx].copy(), flat[s.obeta:s.obeta + s.C][idx].copy()]
@@ -993,6 +1068,8 @@ class Model(object):
                 a = ysum if ysum is not None else h.view(T, n_pad, 2 * Hp)
             elif s.kind == 'bigru':
                 a = self._gru_forward(s, si, a.contiguous(), rec, stage_masks(si)[:2], n_pad)
+            elif s.kind == 'birhn':
+                a = self._rhn_forward(s, si, a.contiguous(), rec, stage_masks(si)[:2], n_pad)
             rec['out'] = a
             self._acts.append(rec)
         return a
@@ -1072,6 +1149,88 @@ class Model(object):
             for d in range(2):
                 ops.gemm(dg, self.params, dx, rows, s.f_in_pad, 3 * Hp, trans_b=True,
                          lda=6 * Hp, ldb=6 * Hp, a_off=d * 3 * Hp, b_off=s.oW + d * 3 * Hp,
+                         c_scale=BW[d], c_scale_period=n_pad, beta=0.0 if d == 0 else 1.0,
+                         a_absmax=zmx)
+        return dx
+
+    def _rhn_forward(self, s, si, a, rec, masks, n_pad):
+        """Bidirectional(RHN) stage (csrc/rhn.hip): zx = (a (.) B_W[d]) @ W_d from the GEMMs (the
+        kernel adds every level's bias), then the recurrence; the states and gates of all levels
+        are kept for BPTT, level-major.  B_U is (2, L, n_pad, Hp): one mask per level."""
+        T, Hp, Ld, Wd = a.shape[0], s.Hp, s.depth, s.nblk * s.Hp
+        rows = T * n_pad
+        BW, BU = masks
+        rec['BW'], rec['BU'] = BW, BU
+        zx = self._buf('hzx%d' % si, (T, n_pad, 2, Wd))
+        if BW is None:
+            ops.gemm(a, self.params, zx, rows, 2 * Wd, s.f_in_pad, b_off=s.oW)
+        else:
+            for d in range(2):
+                ops.gemm(a, self.params, zx, rows, Wd, s.f_in_pad, ldb=2 * Wd, ldc=2 * Wd,
+                         b_off=s.oW + d * Wd, c_off=d * Wd, a_scale=BW[d], a_scale_period=n_pad)
+        h = self._buf('hh%d' % si, (Ld, T, n_pad, 2, Hp))
+        gates = self._buf('hgates%d' % si, (Ld, T, n_pad, 2, Wd))
+        ysum = self._buf('hsum%d' % si, (T, n_pad, Hp)) if s.merge == 'sum' else None
+        ops.rhn_seq_fwd(zx, self._view(s.oU, 2 * Ld * Hp * Wd), self._view(s.ob, 2 * Ld * Wd), h,
+                        gates, T, n_pad, Hp, Ld, coupling=s.coupling, act=s.act, mask_u=BU,
+                        y_sum=ysum)
+        rec.update(h=h, gates=gates)
+        return ysum if ysum is not None else h[Ld - 1].view(T, n_pad, 2 * Hp)
+
+    def _rhn_backward(self, s, si, rec, da, first, split):
+        """BPTT of an RHN stage (csrc/rhn.hip), then its weight gradients and dx from the GEMMs:
+        dU_l[d] = (s_prev^l (.) B_U[d, l])^T da^l, where s_prev^l is the states slab of level
+        l - 1 or, for l = 0, slab L - 1 one frame earlier in the direction's processing order;
+        dW[d] = (x (.) B_W)^T da^0_d, db from the per-batch-tile sums,
+        dx = sum_d B_W[d] (.) (da^0_d @ W_d^T).  Returns dx (or None)."""
+        T, n_pad = da.shape[0], da.shape[1]
+        rows, Hp, Ld, Wd = T * n_pad, s.Hp, s.depth, s.nblk * s.Hp
+        BW, BU, h, a_in = rec['BW'], rec['BU'], rec['h'], rec['in']
+        dg = self._buf('hda%d' % si, (Ld, T, n_pad, 2, Wd))
+        dbp = self._buf('hdbp%d' % si, (n_pad // 16, 2, Ld, Wd))
+        zmx = self._buf('hdamax%d' % si, (1,))
+        ops.rhn_seq_bwd(da.contiguous(), self._view(s.oU, 2 * Ld * Hp * Wd), h, rec['gates'], dg,
+                        T, n_pad, Hp, Ld, coupling=s.coupling, act=s.act, mask_u=BU,
+                        shared_dy=s.merge == 'sum', db_part=dbp, dz_absmax=zmx)
+        ops.colsum(dbp, n_pad // 16, 2 * Ld * Wd, 2 * Ld * Wd, self._gview(s.ob, 2 * Ld * Wd))
+        kk = (T - 1) * n_pad
+        for d in range(2):
+            for l in range(Ld):
+                oU = s.oU + (d * Ld + l) * Hp * Wd
+                scale = None if BU is None else BU[d, l]
+                if l > 0:
+                    ops.gemm(h, dg, self.grads, Hp, Wd, rows, trans_a=True, lda=2 * Hp,
+                             ldb=2 * Wd, ldc=Wd, a_off=(l - 1) * rows * 2 * Hp + d * Hp,
+                             b_off=l * rows * 2 * Wd + d * Wd, c_off=oU, split_k=split,
+                             a_scale=scale, a_scale_period=n_pad, b_absmax=zmx)
+                elif kk > 0:
+                    ops.gemm(h, dg, self.grads, Hp, Wd, kk, trans_a=True, lda=2 * Hp,
+                             ldb=2 * Wd, ldc=Wd,
+                             a_off=(Ld - 1) * rows * 2 * Hp + d * Hp
+                             + (0 if d == 0 else n_pad * 2 * Hp),
+                             b_off=d * Wd + (n_pad * 2 * Wd if d == 0 else 0), c_off=oU,
+                             split_k=split, a_scale=scale, a_scale_period=n_pad, b_absmax=zmx)
+                else:
+                    self._gview(oU, Hp * Wd).zero_()
+        a_in = a_in.contiguous()
+        if BW is None:
+            ops.gemm(a_in, dg, self.grads, s.f_in_pad, 2 * Wd, rows, trans_a=True, c_off=s.oW,
+                     split_k=split, b_absmax=zmx)
+        else:
+            for d in range(2):
+                ops.gemm(a_in, dg, self.grads, s.f_in_pad, Wd, rows, trans_a=True,
+                         ldb=2 * Wd, ldc=2 * Wd, b_off=d * Wd, c_off=s.oW + d * Wd,
+                         split_k=split, a_scale=BW[d], a_scale_period=n_pad, b_absmax=zmx)
+        if first:
+            return None
+        dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
+        if BW is None:
+            ops.gemm(dg, self.params, dx, rows, s.f_in_pad, 2 * Wd, trans_b=True, b_off=s.oW,
+                     a_absmax=zmx)
+        else:
+            for d in range(2):
+                ops.gemm(dg, self.params, dx, rows, s.f_in_pad, Wd, trans_b=True,
+                         lda=2 * Wd, ldb=2 * Wd, a_off=d * Wd, b_off=s.oW + d * Wd,
                          c_scale=BW[d], c_scale_period=n_pad, beta=0.0 if d == 0 else 1.0,
                          a_absmax=zmx)
         return dx
@@ -1352,13 +1511,17 @@ class Model(object):
         """Variational-dropout masks of every BiLSTM stage for one batch (core/models.py:265-266:
         one mask per batch and direction, constant over time, inverted scaling), from the
         library's counter-based streams: {stage: (B_W (2, n_pad, in), B_U (2, n_pad, H))} with
-        stream id 4 * stage (B_W) / 4 * stage + 1 (B_U) at step self._step."""
+        stream id 4 * stage (B_W) / 4 * stage + 1 (B_U) at step self._step.  An RHN stage has one
+        B_U per level: (2, L, n_pad, H), all from that one stream."""
         out = {}
         for si, s in enumerate(self.stages):
-            if s.kind not in ('bilstm', 'birnn', 'bigru') or not (s.dropout_W > 0 or s.dropout_U > 0):
+            if s.kind not in ('bilstm', 'birnn', 'bigru', 'birhn') \
+                    or not (s.dropout_W > 0 or s.dropout_U > 0):
                 continue
             BW = self._buf('BW%d' % si, (2, n_pad, s.f_in_pad))
-            BU = self._buf('BU%d' % si, (2, n_pad, s.Hp))
+            # (an RHN stage: one B_U per level, all from the one stream 4 * stage + 1)
+            BU = self._buf('BU%d' % si, (2, s.depth, n_pad, s.Hp) if s.kind == 'birhn'
+                           else (2, n_pad, s.Hp))
             for k, (t, p) in enumerate(((BW, s.dropout_W), (BU, s.dropout_U))):
                 if p > 0:
                     ops.dropout_masks(t, p, 1.0 / (1.0 - p), self.rng_seed, 4 * si + k, self._step)
@@ -1448,7 +1611,7 @@ class Model(object):
                     da = ops.axpby(s.coef, da, 0.0, da, self._buf('dmerge%d' % si, da.shape))
                 skip_grads[s.skip] = da
                 continue
-            first = not any(st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn', 'bigru')
+            first = not any(st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn', 'bigru', 'birhn')
                             for st in self.stages[:si])
             if s.kind in ('noise', 'reshape'):
                 continue
@@ -1489,6 +1652,11 @@ class Model(object):
                 continue
             if s.kind == 'bigru':
                 dx = self._gru_backward(s, si, rec, da, first, split)
+                if dx is not None:
+                    da = dx
+                continue
+            if s.kind == 'birhn':
+                dx = self._rhn_backward(s, si, rec, da, first, split)
                 if dx is not None:
                     da = dx
                 continue

@@ -12,7 +12,8 @@ integration, zoneout and layer normalisation are implemented.
 ``SimpleRNN`` (Bidirectional, 'concat' or 'sum'), ``Activation`` and ``recurrent()`` serve the
 maas / deep_speech factories (core/models.py).  ``GRU`` (Keras 1.2.2, consume_less='gpu' layout,
 hard_sigmoid gates, Bidirectional 'concat' or 'sum') runs on csrc/gru.hip and is deep_speech2's
-``rnn_type='gru'`` cell.  ``BatchNormalization`` (mode 0, axis -1) runs
+``rnn_type='gru'`` cell.  ``RHN`` (the reference's Recurrent Highway Network layer) runs on
+csrc/rhn.hip and is the cell of the ``rhn`` factory.  ``BatchNormalization`` (mode 0, axis -1) runs
 bare or on the (N, T, F, C) image of the convolution front-end (csrc/batchnorm.hip).
 """
 
@@ -223,6 +224,91 @@ class GRU(object):
         self.l2_U = U_regularizer.l2 if U_regularizer is not None else 0.0
 
 
+def highway_bias_initializer(shape, name=None):
+    """The reference's bias initialiser of the RHN gates (core/initializers.py): constant -2."""
+    import numpy as np
+    return np.full(shape, -2.0, np.float32)
+
+
+class RHN(object):
+    """The reference's Recurrent Highway Network layer (core/layers.py:92-353; Zilly et al. 2016):
+    one time step is ``depth`` highway micro-layers in sequence, only the first of which sees the
+    input.  W (F, C H), U_l (H, C H), b_l (C H), column blocks h | t | [c]; C = 2 with
+    ``coupling`` (c = 1 - t), else 3.  With s the state carried in (0 at the first frame):
+
+        for l in 0 .. depth-1:
+            a = (l == 0 ? (x B_W) W : 0) + (s B_U[l]) U_l + b_l
+            h = act(a_h), t = hs(a_t), c = coupling ? 1 - t : hs(a_c)
+            s = h t + s c
+        y = s
+
+    Implemented: init='glorot_uniform' over (F, C H), inner_init='orthogonal' (x 1.1, per U_l),
+    bias_init=highway_bias_initializer (b_l = [0 | -2 | -2]); activation 'tanh', 'relu', 'linear'
+    or ``clipped_relu(max_value)``; inner_activation='hard_sigmoid'; W_regularizer l2; variational
+    dropout_W (one mask) / dropout_U (one mask per level); return_sequences=True.  Runs on
+    csrc/rhn.hip.
+
+    Three arguments cannot be taken from the reference, which crashes on them:
+    * U_regularizer: the reference registers it on ``self.U``, an attribute that does not exist
+      (core/layers.py:230-232).  Here it is l2 on every U_l, the evident intent (W_regularizer is
+      l2 on W).
+    * layer_norm=True: the reference calls an un-imported ``LN`` (:282).  NotImplementedError.
+    * mi=True: the reference unpacks one tensor into three for every level above 0 (:200-203,
+      :270).  NotImplementedError."""
+
+    IMPLEMENTED = ("output_dim, depth >= 1, init='glorot_uniform', inner_init='orthogonal', "
+                   "bias_init=highway_bias_initializer, activation in (tanh, relu, linear, "
+                   "clipped_relu(v)), inner_activation='hard_sigmoid', coupling, "
+                   "W_regularizer / U_regularizer l2, dropout_W, dropout_U, "
+                   "return_sequences=True, consume_less")
+
+    def __init__(self, output_dim, depth=1, init='glorot_uniform', inner_init='orthogonal',
+                 bias_init=highway_bias_initializer, activation='tanh',
+                 inner_activation='hard_sigmoid', coupling=True, layer_norm=False,
+                 ln_gain_init='one', ln_bias_init='zero', mi=False, W_regularizer=None,
+                 U_regularizer=None, b_regularizer=None, dropout_W=0., dropout_U=0.,
+                 return_sequences=True, stateful=False, consume_less='gpu', **kwargs):
+        def refuse(what):
+            raise NotImplementedError('RHN %s (implemented: %s)' % (what, self.IMPLEMENTED))
+        if int(depth) < 1:
+            refuse('depth %r' % (depth,))
+        if init != 'glorot_uniform':
+            refuse('init %r' % (init,))
+        if inner_init != 'orthogonal':
+            refuse('inner_init %r' % (inner_init,))
+        if bias_init not in (highway_bias_initializer, 'highway_bias_initializer'):
+            refuse('bias_init %r' % (bias_init,))
+        if inner_activation != 'hard_sigmoid':
+            refuse('inner_activation %r' % (inner_activation,))
+        if layer_norm:
+            refuse('layer_norm=True (the reference calls an un-imported LN there)')
+        if mi:
+            refuse('mi=True (the reference cannot build it for depth > 1)')
+        if b_regularizer is not None:
+            refuse('b_regularizer')
+        if not return_sequences:
+            refuse('return_sequences=False')
+        if stateful:
+            refuse('stateful=True')
+        if kwargs:
+            refuse('argument(s) %s' % ', '.join(sorted(kwargs)))
+        from .. import ops
+        try:
+            ops.rnn_activation_id(activation)
+        except NotImplementedError:
+            refuse('activation %r' % (activation,))
+        self.activation = activation
+        self.init, self.inner_init, self.inner_activation = init, inner_init, inner_activation
+        self.bias_init = 'highway_bias_initializer'
+        self.output_dim = int(output_dim)
+        self.depth = int(depth)
+        self.coupling = bool(coupling)
+        self.dropout_W = float(dropout_W or 0.0)
+        self.dropout_U = float(dropout_U or 0.0)
+        self.l2_W = W_regularizer.l2 if W_regularizer is not None else 0.0
+        self.l2_U = U_regularizer.l2 if U_regularizer is not None else 0.0
+
+
 class Activation(Layer):
     """keras.layers.Activation: 'tanh', 'relu', 'linear' or ``clipped_relu(max_value)``,
     element-wise (bare or inside TimeDistributed)."""
@@ -238,12 +324,13 @@ def recurrent(output_dim, model='keras_lstm', activation='tanh', regularizer=Non
     """The reference's recurrent-layer factory (core/layers.py:482-516): 'rnn' -> SimpleRNN,
     'lstm' / 'keras_lstm' -> LSTM, with W and U regularised by ``regularizer`` and dropout_W =
     dropout_U = ``dropout``.  'gru' is not routed here yet: build the layer with ``GRU(...)``
-    (this module) directly; 'rhn' is not implemented."""
+    (this module) directly, and likewise 'rhn' with ``RHN(...)``."""
     if model == 'gru':
         raise NotImplementedError("recurrent(model='gru') is not routed yet: use "
                                   'layers.GRU(output_dim, ...) directly')
     if model == 'rhn':
-        raise NotImplementedError('recurrent(model=%r): only rnn, lstm, keras_lstm' % (model,))
+        raise NotImplementedError("recurrent(model='rhn') is not routed yet: use "
+                                  'layers.RHN(output_dim, depth, ...) directly')
     common = dict(W_regularizer=regularizer, U_regularizer=regularizer, dropout_W=dropout,
                   dropout_U=dropout, activation=activation, return_sequences=True)
     if model == 'rnn':
@@ -254,12 +341,12 @@ def recurrent(output_dim, model='keras_lstm', activation='tanh', regularizer=Non
 
 
 class Bidirectional(Layer):
-    """keras.layers.Bidirectional: LSTM with merge_mode='concat'; SimpleRNN and GRU with 'concat'
-    ([h_f | h_b]) or 'sum' (h_f + h_b)."""
+    """keras.layers.Bidirectional: LSTM with merge_mode='concat'; SimpleRNN, GRU and RHN with
+    'concat' ([h_f | h_b]) or 'sum' (h_f + h_b)."""
 
     def __init__(self, layer, merge_mode='concat'):
-        assert isinstance(layer, (LSTM, SimpleRNN, GRU))
-        allowed = ('concat', 'sum') if isinstance(layer, (SimpleRNN, GRU)) else ('concat',)
+        assert isinstance(layer, (LSTM, SimpleRNN, GRU, RHN))
+        allowed = ('concat', 'sum') if isinstance(layer, (SimpleRNN, GRU, RHN)) else ('concat',)
         if merge_mode not in allowed:
             raise NotImplementedError('merge_mode=%r' % merge_mode)
         self.lstm = layer

@@ -1,6 +1,7 @@
 """Model factories with the reference's names and hyper-parameters
 (core/models.py): ``ctc_model``, ``graves2006``, ``eyben``, ``maas``, ``deep_speech``,
-``brsmv1``, plus this build's ``deep_speech2`` (BiLSTM or, with ``rnn_type='gru'``, BiGRU).
+``brsmv1``, plus this build's ``deep_speech2`` (BiLSTM or, with ``rnn_type='gru'``, BiGRU) and
+``rhn`` (brsmv1's topology on the reference's own RHN cell).
 
 ``train.py`` resolves them by name -- ``get_from_module('core.models', 'brsmv1')
 (**hparams)`` (train.py:127-129) -- and gets back an object with the Keras
@@ -14,7 +15,7 @@ from . import ctc_utils
 from .engine import Model
 from .layers import (Input, GaussianNoise, TimeDistributed, Dense, LSTM, Bidirectional,
                      Dropout, Merge, merge, l2, Reshape, Convolution2D, clipped_relu, SimpleRNN,
-                     Activation, BatchNormalization, GRU)
+                     Activation, BatchNormalization, GRU, RHN)
 
 
 def ctc_model(inputs, output, **kwargs):
@@ -68,6 +69,12 @@ def ctc_model(inputs, output, **kwargs):
         elif isinstance(layer, Bidirectional) and isinstance(layer.lstm, GRU):
             r = layer.lstm
             spec.append({'type': 'bigru', 'H': r.output_dim, 'merge_mode': layer.merge_mode,
+                         'activation': r.activation, 'dropout_W': r.dropout_W,
+                         'dropout_U': r.dropout_U, 'l2_W': r.l2_W, 'l2_U': r.l2_U})
+        elif isinstance(layer, Bidirectional) and isinstance(layer.lstm, RHN):
+            r = layer.lstm
+            spec.append({'type': 'birhn', 'H': r.output_dim, 'depth': r.depth,
+                         'coupling': r.coupling, 'merge_mode': layer.merge_mode,
                          'activation': r.activation, 'dropout_W': r.dropout_W,
                          'dropout_U': r.dropout_U, 'l2_W': r.l2_W, 'l2_U': r.l2_U})
         elif isinstance(layer, Bidirectional):
@@ -273,3 +280,35 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
         model.config['kwargs']['rnn_type'] = rnn_type
     return model
 
+
+
+def rhn(num_features=39, num_classes=28, num_hiddens=256, num_layers=5, depth=2, coupling=True,
+        dropout=0.2, input_dropout=False, input_std_noise=.0, weight_decay=1e-4,
+        merge_mode='concat', activation='tanh', **kw):
+    """brsmv1's topology on the reference's Recurrent Highway Network cell.  NO REFERENCE
+    COUNTERPART: the reference defines the ``RHN`` layer (core/layers.py:92-353) and routes it
+    through ``recurrent(model='rhn')``, but none of its factories uses it.  Built from the
+    reference's own pieces: brsmv1's noise / dropout / regularisers / output Dense
+    (core/models.py:217-281) with every Bidirectional(LSTM) replaced by
+    Bidirectional(RHN(num_hiddens, depth, coupling), merge_mode) -- W and every U_l l2
+    ``weight_decay``, dropout_W = dropout_U = ``dropout``.  Runs on csrc/rhn.hip."""
+    x = Input(name='inputs', shape=(None, num_features))
+    o = x
+    if input_std_noise is not None:
+        o = GaussianNoise(input_std_noise)(o)
+    if input_dropout:
+        o = Dropout(dropout)(o)
+    for _ in range(num_layers):
+        o = Bidirectional(RHN(num_hiddens, depth=depth, coupling=coupling,
+                              return_sequences=True, W_regularizer=l2(weight_decay),
+                              U_regularizer=l2(weight_decay), dropout_W=dropout,
+                              dropout_U=dropout, activation=activation),
+                          merge_mode=merge_mode)(o)
+    o = TimeDistributed(Dense(num_classes, W_regularizer=l2(weight_decay)))(o)
+    model = ctc_model(x, o, **kw)
+    model.config = {'name': 'rhn', 'kwargs': dict(
+        num_features=num_features, num_classes=num_classes, num_hiddens=num_hiddens,
+        num_layers=num_layers, depth=depth, coupling=coupling, dropout=dropout,
+        input_dropout=input_dropout, input_std_noise=input_std_noise,
+        weight_decay=weight_decay, merge_mode=merge_mode, activation=activation)}
+    return model

@@ -444,6 +444,75 @@ def gru_plan(T, n_pad, H, backward=False, mode=0):
             'blocks': blocks.value}
 
 
+# --------------------------------------------------------------------------- RHN (K17)
+RHN_WS = ('rhn_fwd', 'rhn_bwd')     # scratch only: the stepwise form has no status words
+
+
+def _rhn_args(T, n_pad, H, depth, coupling, U, h, gates, act, mode, mask_u=None):
+    a = L.RhnArgs()
+    a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
+    a.depth, a.coupling = int(depth), int(bool(coupling))
+    a.activation, a.clip = rnn_activation_id(act)
+    a.U, a.h, a.gates = U.data_ptr(), h.data_ptr(), gates.data_ptr()
+    a.mask_u = mask_u.data_ptr() if mask_u is not None else None
+    return a
+
+
+def rhn_seq_fwd(zx, U, b, h, gates, T, n_pad, H, depth, coupling=True, act='tanh', mask_u=None,
+                y_sum=None, mode=0):
+    """Both directions of an RHN layer (C = 2 column blocks h | t when coupling, else 3 with c):
+    states h (L, T, n_pad, 2, H) of every level (slab L-1 is the layer output) and gates
+    (L, T, n_pad, 2, C H) = hh | tg | [cg] from zx = x@W (T, n_pad, 2, C H, no bias),
+    U (2, L, H, C H), b (2, L, C H), optional B_U (2, L, n_pad, H); y_sum (T, n_pad, H) <- the sum
+    of the two directions' outputs when given.
+    mode: 0 = the library's form, 1 = stepwise (the only form there is)."""
+    lib = L.load()
+    _check_f32(zx, U, b, h, gates, mask_u, y_sum)
+    a = _rhn_args(T, n_pad, H, depth, coupling, U, h, gates, act, mode, mask_u)
+    a.zx, a.b = zx.data_ptr(), b.data_ptr()
+    a.y_sum = y_sum.data_ptr() if y_sum is not None else None
+    nbytes = lib.asr_rhn_workspace_bytes(C.byref(a), 0)
+    if nbytes == 0:
+        L.check(-1, 'asr_rhn_workspace_bytes')
+    ws = WS.get(RHN_WS[0], nbytes, zx.device)
+    L.check(lib.asr_rhn_seq_fwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_rhn_seq_fwd')
+    return ws
+
+
+def rhn_seq_bwd(dy, U, h, gates, da, T, n_pad, H, depth, coupling=True, act='tanh', mask_u=None,
+                shared_dy=False, mode=0, db_part=None, dz_absmax=None):
+    """BPTT of both directions: da (L, T, n_pad, 2, C H) = da_h | da_t | [da_c], the gradient of
+    every level's pre-activations.  dy is the gradient of the layer output: (T, n_pad, 2H) for
+    'concat', (T, n_pad, H) shared by both directions for 'sum' (shared_dy).  db_part
+    (n_pad/16, 2, L, C H): per-batch-tile sums of da; dz_absmax (1,): max |da|."""
+    lib = L.load()
+    _check_f32(dy, U, h, gates, da, mask_u, db_part, dz_absmax)
+    a = _rhn_args(T, n_pad, H, depth, coupling, U, h, gates, act, mode, mask_u)
+    a.dy, a.da = dy.data_ptr(), da.data_ptr()
+    a.dy_ld, a.dy_dir_stride = (int(H), 0) if shared_dy else (2 * int(H), int(H))
+    a.db_part = db_part.data_ptr() if db_part is not None else None
+    a.dz_absmax = dz_absmax.data_ptr() if dz_absmax is not None else None
+    nbytes = lib.asr_rhn_workspace_bytes(C.byref(a), 1)
+    if nbytes == 0:
+        L.check(-1, 'asr_rhn_workspace_bytes')
+    ws = WS.get(RHN_WS[1], nbytes, dy.device)
+    L.check(lib.asr_rhn_seq_bwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_rhn_seq_bwd')
+    return ws
+
+
+def rhn_plan(T, n_pad, H, depth=1, coupling=True, backward=False, mode=0):
+    """{'persistent': False, 'rows': batch rows, 'units': state columns per workgroup, 'blocks':
+    workgroups of a launch} (asr_rhn_plan)."""
+    a = L.RhnArgs()
+    a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
+    a.depth, a.coupling = int(depth), int(bool(coupling))
+    per, rows, units, blocks = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    L.check(L.load().asr_rhn_plan(C.byref(a), int(bool(backward)), C.byref(per), C.byref(rows),
+                                  C.byref(units), C.byref(blocks)), 'asr_rhn_plan')
+    return {'persistent': bool(per.value), 'rows': rows.value, 'units': units.value,
+            'blocks': blocks.value}
+
+
 # --------------------------------------------------------------------------- BatchNormalization
 def bn_stats_len(C):
     """Floats of a stage's stats block: [mean_hi | mean_lo | invstd | var] (C each)."""

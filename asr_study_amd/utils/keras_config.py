@@ -102,6 +102,24 @@ def _gru_config(name, s):
     return cfg
 
 
+def _rhn_config(name, s):
+    """The reference's RHN.get_config() (core/layers.py:331-353) on top of Recurrent's keys."""
+    act, mv = _act_name(s.act)
+    cfg = {'name': name, 'trainable': True, 'return_sequences': True, 'go_backwards': False,
+           'stateful': False, 'unroll': False, 'consume_less': 'gpu', 'input_dim': int(s.f_in),
+           'input_length': None, 'output_dim': int(s.H), 'depth': int(s.depth),
+           'init': 'glorot_uniform', 'inner_init': 'orthogonal',
+           'bias_init': 'highway_bias_initializer', 'activation': act,
+           'inner_activation': 'hard_sigmoid', 'coupling': bool(s.coupling), 'layer_norm': False,
+           'ln_gain_init': 'one', 'ln_bias_init': 'zero', 'mi': False,
+           'W_regularizer': _regularizer(s.l2_W), 'U_regularizer': _regularizer(s.l2_U),
+           'b_regularizer': None, 'dropout_W': float(s.dropout_W),
+           'dropout_U': float(s.dropout_U)}
+    if mv is not None:
+        cfg['max_value'] = mv
+    return cfg
+
+
 def _lambda_config(name, function, output_shape, arguments):
     return {'name': name, 'trainable': True, 'function': function, 'function_type': 'function',
             'output_shape': output_shape[0], 'output_shape_type': output_shape[1],
@@ -180,6 +198,12 @@ def model_config(model):
                 'name': name, 'trainable': True, 'merge_mode': s.merge,
                 'layer': {'class_name': 'GRU', 'config': _gru_config(
                     'gru_%d' % counts['bidirectional'], s)}}, [prev])
+        elif s.kind == 'birhn':
+            name = nm('bidirectional')
+            add('Bidirectional', name, {
+                'name': name, 'trainable': True, 'merge_mode': s.merge,
+                'layer': {'class_name': 'RHN', 'config': _rhn_config(
+                    'rhn_%d' % counts['bidirectional'], s)}}, [prev])
         elif s.kind == 'bn':
             name = nm('batchnormalization')
             add('BatchNormalization', name, {
@@ -332,6 +356,19 @@ def topology_from_config(text):
                 W_regularizer=reg(r.get('W_regularizer')), U_regularizer=reg(r.get('U_regularizer')),
                 dropout_W=r.get('dropout_W', 0.), dropout_U=r.get('dropout_U', 0.),
                 consume_less=r.get('consume_less', 'gpu')),
+                merge_mode=c.get('merge_mode', 'concat'))(o)
+        elif kind == 'Bidirectional' and c['layer']['class_name'] == 'RHN':
+            r = c['layer']['config']
+            o = L.Bidirectional(L.RHN(
+                r['output_dim'], depth=r.get('depth', 1), init=r.get('init', 'glorot_uniform'),
+                inner_init=r.get('inner_init', 'orthogonal'),
+                bias_init=r.get('bias_init', 'highway_bias_initializer'),
+                activation=_act_from(r),
+                inner_activation=r.get('inner_activation', 'hard_sigmoid'),
+                coupling=r.get('coupling', True), layer_norm=r.get('layer_norm', False),
+                mi=r.get('mi', False),
+                W_regularizer=reg(r.get('W_regularizer')), U_regularizer=reg(r.get('U_regularizer')),
+                dropout_W=r.get('dropout_W', 0.), dropout_U=r.get('dropout_U', 0.)),
                 merge_mode=c.get('merge_mode', 'concat'))(o)
         elif kind == 'TimeDistributed':
             d = c['layer']['config']

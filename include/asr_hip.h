@@ -53,7 +53,8 @@ const char* asr_last_error(void);
  * +r2_hl, asr_lstm_ln_args +activation.  106: asr_lstm_args +dz_hl +dz_bound +dz_scale_out.
  * 107: asr_rnn_args and the asr_rnn_* / asr_activation_* entry points (K14); the asr_bn_*
  * entry points (K15: plain scalar arguments, no struct, so the version stays); asr_gru_args
- * and the asr_gru_* entry points (K16: additions only, no existing layout changes). */
+ * and the asr_gru_* entry points (K16: additions only, no existing layout changes); asr_rhn_args
+ * and the asr_rhn_* entry points (K17: additions only as well). */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -531,6 +532,69 @@ int asr_gru_seq_bwd(const asr_gru_args* a, void* workspace, size_t ws_bytes,
 /* The form the library runs (persistent: always 0) and its geometry: batch rows and output   */
 /* columns per workgroup, workgroups of the widest launch of a step (both directions).        */
 int asr_gru_plan(const asr_gru_args* a, int backward, int* persistent, int* rows, int* units,
+                 int* blocks);
+
+/* ------------------------------------------------------------------------ */
+/* K17 Recurrent Highway Network recurrence of a Bidirectional layer (Zilly  */
+/* et al. 2016; the reference's RHN layer, core/layers.py:92-353;            */
+/* csrc/rhn.hip).  depth L >= 1, C = 2 column blocks h | t when coupling,    */
+/* C = 3 (h | t | c) otherwise.  Per direction U_l (H, C H) and b_l (C H),   */
+/* l = 0 .. L-1; zx = x @ W (NO bias) in the same column order;              */
+/* hs(a) = clip(0.2 a + 0.5, 0, 1); s the state carried in (0 at the         */
+/* direction's first processed frame):                                       */
+/*   for l in 0 .. L-1:                                                      */
+/*     a  = (l == 0 ? zx_t : 0) + (s (.) mask_u[l]) U_l + b_l                */
+/*     hh = act(a_h), tg = hs(a_t), cg = coupling ? 1 - tg : hs(a_c)         */
+/*     s  = hh tg + s cg          (the carry uses the UNMASKED s)            */
+/*   y_t = s                      (the state after level L-1)                */
+/* Direction 1 walks the padded slab from T-1 down to 0; all slabs stay in   */
+/* frame order.  BPTT, g = gradient of the state a level wrote (dy_t is      */
+/* added at level L-1 of every frame), s_prev the state that level read:     */
+/*   da_h = g tg act'(hh)                                                    */
+/*   da_t = g (hh - s_prev) hs'(tg)   (coupling; else g hh hs'(tg))          */
+/*   da_c = g s_prev hs'(cg)          (no coupling only)                     */
+/*   g_prev = g cg + (da U_l^T) (.) mask_u[l]                                */
+/* with hs' = 0.2 where 0 < gate < 1 else 0, read from the SAVED gates, and  */
+/* act' from hh alone.  dW, dU_l, db_l, dx come from asr_gemm / asr_colsum.  */
+/* Exact fp32 products, no float atomics (repeats are bit-identical).        */
+/* Stepwise only: one launch per level and frame.  The saved tensors are     */
+/* level-major, so every level is an ordinary time-major slab.               */
+/* ------------------------------------------------------------------------ */
+typedef struct asr_rhn_args {
+  int T, n_pad, H;       /* H: padded width, a multiple of 4; n_pad a multiple of 16    */
+  int depth;             /* L >= 1 highway levels per frame                             */
+  int coupling;          /* 1: cg = 1 - tg, C = 2 blocks; 0: own carry gate, C = 3      */
+  int mode;              /* 0 = the plan's form, 1 = stepwise; 2 (persistent) does not   */
+                         /* exist for this cell: ASR_ERR_INVALID                         */
+  int activation;        /* 0 tanh, 1 relu, 4 linear, ASR_ACT_CLIPPED_RELU              */
+  float clip;            /* max_value of the clipped relu                               */
+  const float* U;        /* (2, L, H, C H): per direction and level, [in][out]          */
+  const float* b;        /* (2, L, C H); forward only                                   */
+  const float* mask_u;   /* optional (2, L, n_pad, H) B_U: one mask per level, constant  */
+                         /*   over time                                                  */
+  const float* zx;       /* forward: (T, n_pad, 2, C H) = x @ W                          */
+  float* h;              /* (L, T, n_pad, 2, H) states of every level: forward writes,   */
+                         /*   BPTT reads; slab L-1 is the layer output                   */
+  float* gates;          /* (L, T, n_pad, 2, C H) hh | tg | [cg]: forward writes, BPTT   */
+                         /*   reads                                                      */
+  float* y_sum;          /* forward, optional: (T, n_pad, H) = y_f + y_b ('sum' merge)   */
+  const float* dy;       /* BPTT: gradient of the layer output, row (t, n) at dy_ld      */
+  int dy_ld;             /*   floats per (t, n) row: 2H (concat) or H (sum)              */
+  int dy_dir_stride;     /*   floats between the two directions' dy: H (concat), 0 (sum) */
+  float* da;             /* BPTT: (L, T, n_pad, 2, C H) da_h | da_t | [da_c]             */
+  float* db_part;        /* BPTT, optional: (n_pad/16, 2, L, C H) per-batch-tile sums    */
+  float* dz_absmax;      /* BPTT, optional: max |da| (written, not accumulated)          */
+} asr_rhn_args;
+/* Workspace: scratch only (forward: a tile-interleaved copy of every U_l; BPTT: every U_l^T  */
+/* and one (n_pad, 2, H) vector).                                                             */
+size_t asr_rhn_workspace_bytes(const asr_rhn_args* a, int backward);
+int asr_rhn_seq_fwd(const asr_rhn_args* a, void* workspace, size_t ws_bytes,
+                    asr_stream_t stream);
+int asr_rhn_seq_bwd(const asr_rhn_args* a, void* workspace, size_t ws_bytes,
+                    asr_stream_t stream);
+/* The form the library runs (persistent: always 0) and its geometry: batch rows and state    */
+/* columns per workgroup, workgroups of a launch (both directions).                           */
+int asr_rhn_plan(const asr_rhn_args* a, int backward, int* persistent, int* rows, int* units,
                  int* blocks);
 
 /* ------------------------------------------------------------------------ */
