@@ -251,6 +251,11 @@ SIGNATURES = {
                                                              void_p]),
     'asr_bn_update_running': (C.c_int, [void_p, void_p, void_p, void_p, C.c_int, C.c_float,
                                         void_p, void_p, void_p, void_p, void_p]),
+    'asr_seqbn_workspace_bytes': (C.c_size_t, [C.c_int] * 5),
+    'asr_seqbn_fwd_train': (C.c_int, [void_p] * 8 + [C.c_float] + [C.c_int] * 5 +
+                            [C.c_float, void_p, C.c_size_t, void_p]),
+    'asr_seqbn_fwd_infer': (C.c_int, [void_p] * 6 + [C.c_int] * 5 + [C.c_float, void_p]),
+    'asr_seqbn_bwd': (C.c_int, [void_p] * 9 + [C.c_int] * 5 + [void_p, C.c_size_t, void_p]),
     # operation-level entry points (csrc/roles.cpp)
     'asr_frontend_mfcc_batch': (C.c_int, [C.POINTER(FrontendCfg), void_p, void_p, void_p,
                                           c_int_p, C.c_int, C.c_int, void_p, void_p, void_p,

@@ -38,6 +38,9 @@ class Callback(object):
 
 
 LSTM_PARTS = ('W', 'U', 'b')
+# GRU(batch_norm=True): beta takes the place of b; the running moments follow (running_std holds
+# the variance, as in keras.layers.BatchNormalization)
+GRU_BN_PARTS = ('W', 'U', 'gamma', 'beta', 'running_mean', 'running_std')
 MI_PARTS = ('mi_alpha', 'mi_beta1', 'mi_beta2')
 # the reference iterates a dict literal {'Uh', 'Wx', 'new_c'} (core/layers.py:409): its
 # Python-2 order is unspecified, so files are written in this order and READ BY NAME
@@ -87,8 +90,9 @@ def keras_layers(model, weights):
         elif s.kind == 'bigru':     # Bidirectional(GRU), fused 'gpu' layout: W, U, b per direction
             nb += 1
             ws = []
+            parts = GRU_BN_PARTS if getattr(s, 'bn', False) else LSTM_PARTS
             for d in ('forward', 'backward'):
-                for part in LSTM_PARTS:
+                for part in parts:
                     ws.append(('%s_gru_%d_%s:0' % (d, nb, part), next(it)))
             out.append(('bidirectional_%d' % nb, ws))
         elif s.kind == 'birhn':     # Bidirectional(RHN): '<name>_W', '<name>_<l>_U', '<name>_<l>_b'

@@ -370,11 +370,28 @@ class Model(object):
                 s.act = st.get('activation') or 'tanh'
                 s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
                 s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
+                # batch_norm (K18, csrc/batchnorm.hip): sequence-wise BN of the input projection;
+                # no b segment -- gamma, beta (2, 3Hp) each (l2 0) instead, the running moments
+                # and the moments block kept where the bn stage keeps its own
+                s.bn = bool(st.get('batch_norm', False))
                 s.oW = take(f_pad * 6 * s.Hp)
                 s.oU = take(2 * s.Hp * 3 * s.Hp)
-                s.ob = take(6 * s.Hp)
                 segs += [(s.oW, _pad4(f_pad * 6 * s.Hp), s.l2_W),
-                         (s.oU, _pad4(2 * s.Hp * 3 * s.Hp), s.l2_U), (s.ob, _pad4(6 * s.Hp), 0.0)]
+                         (s.oU, _pad4(2 * s.Hp * 3 * s.Hp), s.l2_U)]
+                if s.bn:
+                    s.bn_eps = float(st.get('bn_epsilon', 1e-3))
+                    s.bn_momentum = float(st.get('bn_momentum', 0.99))
+                    s.ob = None
+                    s.og = take(6 * s.Hp)
+                    s.obeta = take(6 * s.Hp)
+                    segs += [(s.og, _pad4(6 * s.Hp), 0.0), (s.obeta, _pad4(6 * s.Hp), 0.0)]
+                    s.orun = run_off
+                    run_off += 2 * 6 * s.Hp
+                    s.omom = tail
+                    tail += _pad4(ops.bn_moments_len(6 * s.Hp))
+                else:
+                    s.ob = take(6 * s.Hp)
+                    segs.append((s.ob, _pad4(6 * s.Hp), 0.0))
                 ws = []
                 for _ in range(2):      # Keras-1.2.2 consume_less='gpu' init, as the BiLSTM stage
                     lim = math.sqrt(6.0 / (f_real + 3 * s.H))
@@ -382,8 +399,12 @@ class Model(object):
                     a = rs.normal(0.0, 1.0, (s.H, 3 * s.H))
                     u, _, v = np.linalg.svd(a, full_matrices=False)
                     U = 1.1 * (u if u.shape == (s.H, 3 * s.H) else v)
-                    ws += [W.astype(np.float32), U.astype(np.float32),
-                           np.zeros(3 * s.H, np.float32)]
+                    ws += [W.astype(np.float32), U.astype(np.float32)]
+                    if s.bn:            # gamma, beta, running mean, running variance
+                        ws += [np.ones(3 * s.H, np.float32), np.zeros(3 * s.H, np.float32),
+                               np.zeros(3 * s.H, np.float32), np.ones(3 * s.H, np.float32)]
+                    else:
+                        ws.append(np.zeros(3 * s.H, np.float32))
                 init.append((s, 'bigru', ws))
                 f_real, f_pad = (2 * s.H, 2 * s.Hp) if s.merge == 'concat' else (s.H, s.Hp)
             elif s.kind == 'birhn':
@@ -468,6 +489,8 @@ class Model(object):
         self.num_classes = f_real
         self._has_rnn = any(st.kind == 'birnn' for st in self.stages)
         self._bn = [(i, st) for i, st in enumerate(self.stages) if st.kind == 'bn']
+        self._seqbn = [(i, st) for i, st in enumerate(self.stages)
+                       if st.kind == 'bigru' and st.bn]
         skips = set(st.skip for st in self.stages if st.kind == 'merge')
         for i, st in self._bn:
             # BN followed by a clipped ReLU: one pass (asr_bn_* clip), the Activation stage is
@@ -585,16 +608,33 @@ class Model(object):
                 Wp = np.zeros((s.f_in_pad, 2, 3 * s.Hp), np.float32)
                 Up = np.zeros((2, s.Hp, 3 * s.Hp), np.float32)
                 bp = np.zeros((2, 3 * s.Hp), np.float32)
+                gp = np.zeros((2, 3 * s.Hp), np.float32)
                 for d in range(2):          # Keras order: forward W, U, b, then backward
-                    W, U, b = [np.asarray(next(it), np.float32) for _ in range(3)]
+                    W, U = [np.asarray(next(it), np.float32) for _ in range(2)]
                     assert W.shape == (len(rows), 3 * s.H) and U.shape == (s.H, 3 * s.H), \
                         (W.shape, U.shape)
                     Wp[rows, d] = _blocks_pad(W, s.H, s.Hp)
                     Up[d, :s.H] = _blocks_pad(U, s.H, s.Hp)
+                    if s.bn:                # ... W, U, gamma, beta, running_mean, running_std
+                        g, b, rm, rv = [np.asarray(next(it), np.float32).reshape(-1)
+                                        for _ in range(4)]
+                        assert g.shape == (3 * s.H,) and rv.shape == (3 * s.H,), (g.shape, rv.shape)
+                        gp[d] = _blocks_pad(g, s.H, s.Hp)
+                        o = s.orun + d * 3 * s.Hp
+                        run[o:o + 3 * s.Hp] = _blocks_pad(rm, s.H, s.Hp)
+                        o += 6 * s.Hp       # (pad columns: variance 1, like the bn stage's)
+                        real = _blocks_pad(np.ones_like(rv), s.H, s.Hp) > 0
+                        run[o:o + 3 * s.Hp] = np.where(real, _blocks_pad(rv, s.H, s.Hp), 1.0)
+                    else:
+                        b = np.asarray(next(it), np.float32)
                     bp[d] = _blocks_pad(b, s.H, s.Hp)
                 host[s.oW:s.oW + Wp.size] = Wp.ravel()
                 host[s.oU:s.oU + Up.size] = Up.ravel()
-                host[s.ob:s.ob + bp.size] = bp.ravel()
+                if s.bn:
+                    host[s.og:s.og + gp.size] = gp.ravel()
+                    host[s.obeta:s.obeta + bp.size] = bp.ravel()
+                else:
+                    host[s.ob:s.ob + bp.size] = bp.ravel()
             elif s.kind == 'birhn':
                 rows = self._real_rows(s)
                 Ld, Cb, Wd = s.depth, s.nblk, s.nblk * s.Hp
@@ -628,7 +668,7 @@ class Model(object):
                 run[s.orun + idx] = rm
                 run[s.orun + Cp + idx] = rv
         self.params.copy_(torch.from_numpy(host))
-        if self._bn:
+        if self._bn or self._seqbn:
             self.bn_running.copy_(torch.from_numpy(run))
         self._weights_epoch += 1        # (bounds measured under the old weights are dropped)
 
@@ -685,10 +725,22 @@ class Model(object):
                 rows = self._real_rows(s)
                 Wp = flat[s.oW:s.oW + s.f_in_pad * 6 * s.Hp].reshape(s.f_in_pad, 2, 3 * s.Hp)
                 Up = flat[s.oU:s.oU + 2 * s.Hp * 3 * s.Hp].reshape(2, s.Hp, 3 * s.Hp)
-                bp = flat[s.ob:s.ob + 6 * s.Hp].reshape(2, 3 * s.Hp)
+                ob = s.obeta if s.bn else s.ob
+                bp = flat[ob:ob + 6 * s.Hp].reshape(2, 3 * s.Hp)
                 for d in range(2):
                     out += [_blocks_unpad(Wp[rows, d], s.H, s.Hp),
-                            _blocks_unpad(Up[d, :s.H], s.H, s.Hp), _blocks_unpad(bp[d], s.H, s.Hp)]
+                            _blocks_unpad(Up[d, :s.H], s.H, s.Hp)]
+                    if not s.bn:
+                        out.append(_blocks_unpad(bp[d], s.H, s.Hp))
+                        continue
+                    gp = flat[s.og:s.og + 6 * s.Hp].reshape(2, 3 * s.Hp)
+                    out += [_blocks_unpad(gp[d], s.H, s.Hp), _blocks_unpad(bp[d], s.H, s.Hp)]
+                    if isinstance(running, str):
+                        out += [np.zeros(3 * s.H, np.float32), np.zeros(3 * s.H, np.float32)]
+                    elif running is not None:
+                        o = s.orun + d * 3 * s.Hp
+                        out += [_blocks_unpad(running[o + k * 6 * s.Hp:o + k * 6 * s.Hp + 3 * s.Hp],
+                                              s.H, s.Hp) for k in range(2)]
             elif s.kind == 'birhn':
                 rows = self._real_rows(s)
                 Ld, Cb, Wd = s.depth, s.nblk, s.nblk * s.Hp
@@ -853,13 +905,16 @@ class Model(object):
 
     # ------------------------------------------------------------------ forward
     def forward(self, x, training=False, masks=None, need_grad=True, n_valid=0, n_real=None,
-                bn_weight=None):
+                bn_weight=None, seq_len=None):
         """x: (T, n_pad, F) float32 CUDA slab -> logits (T, n_pad, C).
         need_grad=False (evaluation / prediction) skips what only BPTT would read; n_valid=1
         with it (one utterance, predict.py) selects the tile-free recurrent kernel.
         n_real: the real samples of the slab (rows n < n_real of every frame; default n_valid, else
         n_pad), over which BatchNormalization takes its training statistics; bn_weight: samples
         this rank contributes to the running moments (default n_real; 0 = a zero-weight dummy).
+        seq_len: device int32 lengths of the real samples on the recurrent stack's time axis (what
+        CTC gets): the valid frames of a GRU(batch_norm=True) stage's training statistics (None:
+        every frame).
 
         masks: optional explicit variational-dropout masks (parity tests):
         {stage_index: (BW (2, n_pad, f_in_pad), BU (2, n_pad, Hp))}.
@@ -1067,30 +1122,37 @@ class Model(object):
                 rec['h'] = h
                 a = ysum if ysum is not None else h.view(T, n_pad, 2 * Hp)
             elif s.kind == 'bigru':
-                a = self._gru_forward(s, si, a.contiguous(), rec, stage_masks(si)[:2], n_pad)
+                a = self._gru_forward(s, si, a.contiguous(), rec, stage_masks(si)[:2], n_pad,
+                                      training, n_real, bn_weight, seq_len)
             elif s.kind == 'birhn':
                 a = self._rhn_forward(s, si, a.contiguous(), rec, stage_masks(si)[:2], n_pad)
             rec['out'] = a
             self._acts.append(rec)
         return a
 
-    def _gru_forward(self, s, si, a, rec, masks, n_pad):
+    def _gru_forward(self, s, si, a, rec, masks, n_pad, training=False, n_real=None,
+                     bn_weight=None, seq_len=None):
         """Bidirectional(GRU) stage (csrc/gru.hip): zx = (a (.) B_W[d]) @ W_d + b_d from the
-        GEMMs, then the recurrence; h, the gates z | r | hh and r (.) m are kept for BPTT."""
+        GEMMs, then the recurrence; h, the gates z | r | hh and r (.) m are kept for BPTT.
+        batch_norm: the GEMMs write the bias-free projection p into a buffer of the layer (the
+        backward pass reads it again), and zx = BN(p) goes to a scratch all layers share (BPTT
+        never reads zx)."""
         T, Hp = a.shape[0], s.Hp
         rows = T * n_pad
         BW, BU = masks
         rec['BW'], rec['BU'] = BW, BU
         zx = self._buf('gzx%d' % si, (T, n_pad, 2, 3 * Hp))
-        bias = self._view(s.ob, 6 * Hp)
+        bias = None if s.bn else self._view(s.ob, 6 * Hp)
         if BW is None:
             ops.gemm(a, self.params, zx, rows, 6 * Hp, s.f_in_pad, b_off=s.oW, bias=bias)
         else:
             for d in range(2):
                 ops.gemm(a, self.params, zx, rows, 3 * Hp, s.f_in_pad, ldb=6 * Hp, ldc=6 * Hp,
                          b_off=s.oW + d * 3 * Hp, c_off=d * 3 * Hp,
-                         bias=bias[d * 3 * Hp:(d + 1) * 3 * Hp], a_scale=BW[d],
-                         a_scale_period=n_pad)
+                         bias=None if s.bn else bias[d * 3 * Hp:(d + 1) * 3 * Hp],
+                         a_scale=BW[d], a_scale_period=n_pad)
+        if s.bn:
+            zx = self._seqbn_forward(s, si, zx, rec, training, n_real, bn_weight, seq_len)
         h = self._buf('gh%d' % si, (T, n_pad, 2, Hp))
         gates = self._buf('ggates%d' % si, (T, n_pad, 2, 3 * Hp))
         rm = self._buf('grm%d' % si, (T, n_pad, 2, Hp))
@@ -1099,6 +1161,32 @@ class Model(object):
                         act=s.act, mask_u=BU, y_sum=ysum)
         rec.update(h=h, gates=gates, rm=rm)
         return ysum if ysum is not None else h.view(T, n_pad, 2 * Hp)
+
+    def _seqbn_forward(self, s, si, p, rec, training, n_real, bn_weight, seq_len):
+        """zx = BN(p) of a GRU(batch_norm=True) stage (K18): batch statistics over the valid frames
+        in training (saved, with p, for the backward pass; the moments block of the running
+        update written behind the flag slots), the running moments otherwise."""
+        T, n_pad = p.shape[0], p.shape[1]
+        Wd = 6 * s.Hp
+        N = min(int(n_real or n_pad), n_pad)
+        p3 = p.view(T, n_pad, Wd)
+        y = self._buf('gzxbn_%d' % Wd, (T, n_pad, Wd))
+        gamma, beta = self._view(s.og, Wd), self._view(s.obeta, Wd)
+        rm = self.bn_running[s.orun:s.orun + Wd]
+        rv = self.bn_running[s.orun + Wd:s.orun + 2 * Wd]
+        if not training:
+            ops.seqbn_fwd_infer(p3, y, gamma, beta, rm, rv, N, Wd, s.bn_eps)
+            return y.view(T, n_pad, 2, 3 * s.Hp)
+        stats = self._buf('gbnstats%d' % si, (ops.seqbn_stats_len(Wd),))
+        mom = self._gbuf[self.n_params + s.omom:self.n_params + s.omom + ops.bn_moments_len(Wd)]
+        # (data parallel: moments about the running mean, pooled by the gradient all-reduce, as
+        # in _bn_forward; the weight |V| is counted on the device, 0 for a zero-weight dummy)
+        dist = self._dist_active()
+        ops.seqbn_fwd_train(p3, y, gamma, beta, stats, N, Wd, lens=seq_len, eps=s.bn_eps,
+                            moments=mom, shift=rm if dist else None,
+                            weight=0.0 if bn_weight == 0 else 1.0)
+        rec.update(p=p3, stats=stats, N=N, lens=seq_len, shift=None if dist else stats[:Wd])
+        return y.view(T, n_pad, 2, 3 * s.Hp)
 
     def _gru_backward(self, s, si, rec, da, first, split):
         """BPTT of a GRU stage (csrc/gru.hip), then its weight gradients and dx from the GEMMs:
@@ -1114,7 +1202,8 @@ class Model(object):
         ops.gru_seq_bwd(da.contiguous(), self._view(s.oU, 2 * Hp * 3 * Hp), h, rec['gates'],
                         dg, T, n_pad, Hp, act=s.act, mask_u=BU,
                         shared_dy=s.merge == 'sum', db_part=dbp, dz_absmax=zmx)
-        ops.colsum(dbp, n_pad // 16, 6 * Hp, 6 * Hp, self._gview(s.ob, 6 * Hp))
+        if not s.bn:
+            ops.colsum(dbp, n_pad // 16, 6 * Hp, 6 * Hp, self._gview(s.ob, 6 * Hp))
         kk = (T - 1) * n_pad
         for d in range(2):
             oU = s.oU + d * Hp * 3 * Hp
@@ -1130,6 +1219,15 @@ class Model(object):
             ops.gemm(rec['rm'], dg, self.grads, Hp, Hp, rows, trans_a=True, lda=2 * Hp,
                      ldb=6 * Hp, ldc=3 * Hp, a_off=d * Hp, b_off=d * 3 * Hp + 2 * Hp,
                      c_off=oU + 2 * Hp, split_k=split, b_absmax=zmx)
+        if s.bn:
+            # dU above came from da; dW and dx come from dp = BN'(da), which has its own absmax
+            # (dbeta is what colsum(db_part) would give: the one reduction pass writes both)
+            dp = self._buf('gdp_%d' % (6 * Hp), (T, n_pad, 6 * Hp))
+            zmx = self._buf('gdpmax%d' % si, (1,))
+            ops.seqbn_bwd(rec['p'], dg.view(T, n_pad, 6 * Hp), self._view(s.og, 6 * Hp),
+                          rec['stats'], dp, self._gview(s.og, 6 * Hp), rec['N'], 6 * Hp,
+                          lens=rec['lens'], dbeta=self._gview(s.obeta, 6 * Hp), dp_absmax=zmx)
+            dg = dp
         a_in = a_in.contiguous()
         if BW is None:
             ops.gemm(a_in, dg, self.grads, s.f_in_pad, 6 * Hp, rows, trans_a=True, c_off=s.oW,
@@ -1263,9 +1361,19 @@ class Model(object):
         """Running-moment update of every BatchNormalization stage, once per optimisation step,
         behind the optimiser: skipped on the device with the update (the same flag words as the
         optimiser's guard), so a vetoed step leaves the statistics alone; no host sync."""
-        if not self._bn or not getattr(self, '_acts', None):
+        if not (self._bn or self._seqbn) or not getattr(self, '_acts', None):
             return
         flags = self.veto_flags()
+        for si, s in self._seqbn:       # GRU(batch_norm=True): one channel per column of zx
+            rec = self._acts[si]
+            if 'stats' not in rec:
+                continue
+            Wd = 6 * s.Hp
+            mom = self._gbuf[self.n_params + s.omom:self.n_params + s.omom +
+                             ops.bn_moments_len(Wd)]
+            ops.bn_update_running(self.bn_running[s.orun:s.orun + Wd],
+                                  self.bn_running[s.orun + Wd:s.orun + 2 * Wd], mom, Wd,
+                                  s.bn_momentum, shift=rec['shift'], flags=flags)
         for si, s in self._bn:
             rec = self._acts[si]
             if 'stats' not in rec:
@@ -2015,7 +2123,7 @@ class Model(object):
         ng = int(n_ref or n_global or N * world)
         self._ar_ref_pad = ops.pad16((ng + world - 1) // world)
         logits = self.forward(slab, training=training, masks=masks, n_real=N,
-                              bn_weight=0 if n_global == 0 else N)
+                              bn_weight=0 if n_global == 0 else N, seq_len=sl)
         dlog = self._buf('dlogits', logits.shape)
         # n_global = 0: a zero-weight dummy shard (parallel.ShardedBatch.n_local == 0)
         ctc = ops.ctc_loss_grad(logits, lab, lab_len, sl, N, grad=dlog,

@@ -183,17 +183,26 @@ class GRU(object):
     LSTM's U), b = 0; activation 'tanh', 'relu', 'linear' or ``clipped_relu(max_value)``;
     inner_activation='hard_sigmoid'; W_regularizer / U_regularizer l2; variational dropout_W /
     dropout_U (one mask per sample, feature and direction, as Keras' 'gpu' mode uses mask 0 of its
-    three); return_sequences=True.  Runs on csrc/gru.hip."""
+    three); return_sequences=True.  Runs on csrc/gru.hip.
+
+    batch_norm=True (not a Keras argument): sequence-wise batch normalisation of the input
+    projection (arXiv 1510.01378), zx = gamma (.) (p - mu) / sqrt(var + bn_epsilon) + beta with
+    p = (x (.) B_W) W and mu, var the per-column moments of the batch's VALID frames (t < length);
+    padded frames are normalised with them and count for nothing.  beta replaces b: the weights per
+    direction are W, U, gamma, beta and the running mean / variance (momentum bn_momentum), which
+    inference uses.  Runs on the K18 kernels of csrc/batchnorm.hip."""
 
     IMPLEMENTED = ("output_dim, init='glorot_uniform', inner_init='orthogonal', activation in "
                    "(tanh, relu, linear, clipped_relu(v)), inner_activation='hard_sigmoid', "
                    "W_regularizer / U_regularizer l2, dropout_W, dropout_U, return_sequences=True, "
-                   "consume_less='gpu'")
+                   "consume_less='gpu', batch_norm in (False, True), bn_epsilon > 0, "
+                   "0 <= bn_momentum <= 1")
 
     def __init__(self, output_dim, init='glorot_uniform', inner_init='orthogonal',
                  activation='tanh', inner_activation='hard_sigmoid', W_regularizer=None,
                  U_regularizer=None, b_regularizer=None, dropout_W=0., dropout_U=0.,
-                 return_sequences=True, consume_less='gpu', **kwargs):
+                 return_sequences=True, consume_less='gpu', batch_norm=False, bn_epsilon=1e-3,
+                 bn_momentum=0.99, **kwargs):
         def refuse(what):
             raise NotImplementedError('GRU %s (implemented: %s)' % (what, self.IMPLEMENTED))
         if init != 'glorot_uniform':
@@ -210,12 +219,20 @@ class GRU(object):
             refuse('consume_less %r' % (consume_less,))
         if kwargs:
             refuse('argument(s) %s' % ', '.join(sorted(kwargs)))
+        if not isinstance(batch_norm, bool):
+            refuse('batch_norm %r' % (batch_norm,))
+        if not float(bn_epsilon) > 0.0:
+            refuse('bn_epsilon %r' % (bn_epsilon,))
+        if not 0.0 <= float(bn_momentum) <= 1.0:
+            refuse('bn_momentum %r' % (bn_momentum,))
         from .. import ops
         try:
             ops.rnn_activation_id(activation)
         except NotImplementedError:
             refuse('activation %r' % (activation,))
         self.activation = activation
+        self.batch_norm = batch_norm
+        self.bn_epsilon, self.bn_momentum = float(bn_epsilon), float(bn_momentum)
         self.init, self.inner_init, self.inner_activation = init, inner_init, inner_activation
         self.output_dim = int(output_dim)
         self.dropout_W = float(dropout_W or 0.0)

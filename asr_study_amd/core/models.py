@@ -71,6 +71,9 @@ def ctc_model(inputs, output, **kwargs):
             spec.append({'type': 'bigru', 'H': r.output_dim, 'merge_mode': layer.merge_mode,
                          'activation': r.activation, 'dropout_W': r.dropout_W,
                          'dropout_U': r.dropout_U, 'l2_W': r.l2_W, 'l2_U': r.l2_U})
+            if r.batch_norm:        # (only then: the spec of every other model is unchanged)
+                spec[-1].update(batch_norm=True, bn_epsilon=r.bn_epsilon,
+                                bn_momentum=r.bn_momentum)
         elif isinstance(layer, Bidirectional) and isinstance(layer.lstm, RHN):
             r = layer.lstm
             spec.append({'type': 'birhn', 'H': r.output_dim, 'depth': r.depth,
@@ -241,12 +244,25 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
     projection W x of the published Deep Speech 2 (sequence-wise BN inside the recurrent layer),
     and its statistics include the time-padding frames, as Keras sees the zero-padded batch.
 
+    batch_norm='recurrent' (with rnn_type='gru' only): the convolution blocks as with
+    batch_norm=True, no BatchNormalization in front of the recurrent layers, and every
+    GRU(batch_norm=True): the published form, sequence-wise batch normalisation of the input
+    projection W x inside the layer, its statistics taken over the valid frames of every utterance
+    (the time-padding frames count for nothing; arXiv 1510.01378).
+
     rnn_type='gru': every Bidirectional(LSTM) becomes a Bidirectional(GRU) (the cell of the
     published Deep Speech 2; Keras-1.2.2 GRU on csrc/gru.hip) with the same regularisers and
     dropouts; it composes with batch_norm."""
     if rnn_type not in ('lstm', 'gru'):
         raise ValueError("deep_speech2: rnn_type %r ('lstm' or 'gru')" % (rnn_type,))
+    if batch_norm not in (False, True, 'recurrent'):
+        raise ValueError("deep_speech2: batch_norm %r (False, True or 'recurrent')" % (batch_norm,))
+    recurrent_bn = batch_norm == 'recurrent'
+    if recurrent_bn and rnn_type != 'gru':
+        raise ValueError("deep_speech2: batch_norm='recurrent' needs rnn_type='gru': only the GRU "
+                         "layer normalises its input projection (LSTM has no batch_norm argument)")
     cell = GRU if rnn_type == 'gru' else LSTM
+    cell_kw = dict(batch_norm=True) if recurrent_bn else {}
     x = Input(name='inputs', shape=(None, num_features))
     o = x
     if input_std_noise is not None:
@@ -261,11 +277,11 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
             o = Activation(clipped_relu(max_value))(o)
     o = Reshape((-1, o.features))(o)
     for _ in range(num_layers):
-        if batch_norm:
+        if batch_norm and not recurrent_bn:
             o = BatchNormalization()(o)
         o = Bidirectional(cell(num_hiddens, return_sequences=True,
                                W_regularizer=l2(weight_decay), U_regularizer=l2(weight_decay),
-                               dropout_W=dropout, dropout_U=dropout))(o)
+                               dropout_W=dropout, dropout_U=dropout, **cell_kw))(o)
     o = TimeDistributed(Dense(num_classes, W_regularizer=l2(weight_decay)))(o)
     model = ctc_model(x, o, **kw)
     model.config = {'name': 'deep_speech2', 'kwargs': dict(
@@ -275,7 +291,7 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
         max_value=max_value, dropout=dropout, weight_decay=weight_decay,
         input_std_noise=input_std_noise)}
     if batch_norm:          # (only then: default checkpoints keep their config byte for byte)
-        model.config['kwargs']['batch_norm'] = True
+        model.config['kwargs']['batch_norm'] = 'recurrent' if recurrent_bn else True
     if rnn_type != 'lstm':  # (likewise)
         model.config['kwargs']['rnn_type'] = rnn_type
     return model

@@ -324,6 +324,234 @@ __global__ void bn_update_kernel(float* __restrict__ rmean, float* __restrict__ 
   rvar[c] = mom * rvar[c] + one_m * bv;
 }
 
+// ---------------------------------------------------------------------------------------------
+// K18 sequence-wise BatchNormalization of a recurrent layer's input projection p (T, n_pad, ld),
+// W real columns, one channel per column (cell-agnostic: only the slab width is known here).
+// The statistics are taken over the VALID rows (n < N, t < min(len_n, T)); every real row (n < N,
+// all T frames) is normalised with them, so time-padding frames contribute nothing to mu / var
+// but still get a value.  Backward: dbeta = sum_R da, dgamma = sum_R da * xhat, dp = gamma *
+// invstd * (da - [valid] (dbeta / |V| + xhat * dgamma / |V|)).  Same workgroup geometry, fp64
+// partials and fixed-order folds as K15 above (the plain 2-D case, C == W).
+// stats (4W + 4 floats): [mean_hi | mean_lo | invstd | var | |V|, 0, 0, 0].
+
+__device__ __forceinline__ int seqbn_len(const int* __restrict__ lens, int n, int T) {
+  if (lens == nullptr) return T;
+  const int l = lens[n];
+  return l < 0 ? 0 : (l > T ? T : l);
+}
+
+// mode 0: statistics over V (p - shift, (p - shift)^2), shift = row (0, 0) of the column;
+// mode 1: backward sums over R (da, da * xhat).
+template <int MODE>
+__global__ void __launch_bounds__(BN_THREADS)
+seqbn_reduce_kernel(const float* __restrict__ p, const float* __restrict__ da,
+                    const float* __restrict__ stats, const int* __restrict__ lens, int T, int N,
+                    int n_pad, int ld, int W, int cw, int rw, int tw, int ntiles,
+                    long long nreal, long long rpp, double2* __restrict__ part) {
+  __shared__ double red[2][BN_THREADS * 4];
+  const int tid = threadIdx.x, tile = blockIdx.x, pt = blockIdx.y;
+  const int cl = tid % cw, rl = tid / cw;
+  const int col = tile * tw + cl * 4;
+  const bool act = rl < rw && col < ld;
+  double s1[4] = {0., 0., 0., 0.}, s2[4] = {0., 0., 0., 0.};
+  if (act) {
+    const long long i0 = (long long)pt * rpp;
+    long long i1 = i0 + rpp;
+    if (i1 > nreal) i1 = nreal;
+    if (MODE == 0) {
+      const float4 k = ld4(p + col);
+      for (long long i = i0 + rl; i < i1; i += rw) {
+        const long long t = i / N;
+        const int n = (int)(i - t * N);
+        if (t >= seqbn_len(lens, n, T)) continue;
+        const float4 v = ld4(p + (size_t)(t * n_pad + n) * ld + col);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const double d = (double)f4get(v, q) - (double)f4get(k, q);
+          s1[q] += d;
+          s2[q] = fma(d, d, s2[q]);
+        }
+      }
+    } else {
+      float mh[4], ml[4], is[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c = col + q < W ? col + q : 0;
+        mh[q] = stats[c];
+        ml[q] = stats[W + c];
+        is[q] = stats[2 * W + c];
+      }
+      for (long long i = i0 + rl; i < i1; i += rw) {
+        const long long t = i / N, n = i - t * N;
+        const size_t o = (size_t)(t * n_pad + n) * ld + col;
+        const float4 v = ld4(p + o), g = ld4(da + o);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float xh = ((f4get(v, q) - mh[q]) - ml[q]) * is[q];
+          const float d = f4get(g, q);
+          s1[q] += (double)d;
+          s2[q] = fma((double)d, (double)xh, s2[q]);
+        }
+      }
+    }
+  }
+  if (rl < rw) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      red[0][rl * tw + cl * 4 + q] = act ? s1[q] : 0.;
+      red[1][rl * tw + cl * 4 + q] = act ? s2[q] : 0.;
+    }
+  }
+  __syncthreads();
+  // fold the row lanes: thread j owns column j of the tile (fixed order)
+  if (tid < tw) {
+    double a = 0., b = 0.;
+    for (int r = 0; r < rw; ++r) {
+      a += red[0][r * tw + tid];
+      b += red[1][r * tw + tid];
+    }
+    part[((size_t)pt * ntiles + tile) * tw + tid] = make_double2(a, b);
+  }
+}
+
+// One wave per column: adds the partials in a fixed order.
+// mode 0 -> stats and the optional moments block [w, 0, 0, 0 | w d (W) | w (var + d^2) (W)],
+// w = weight * |V| (|V| counted here from the lengths), d = mean - shift.
+// mode 1 -> dgamma, dbeta (optional) and coef [sum da / |V| | sum da * xhat / |V|] (2W floats).
+template <int MODE>
+__global__ void seqbn_finalize_kernel(const double2* __restrict__ part,
+                                      const float* __restrict__ p, const int* __restrict__ lens,
+                                      int T, int N, int W, int ntiles, int tw, int P, float eps,
+                                      float* __restrict__ stats, float* __restrict__ moments,
+                                      const float* __restrict__ shift, float weight,
+                                      float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                      float* __restrict__ coef) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  const int t = c / tw, s = c % tw;
+  double a = 0., b = 0.;
+  for (int q = lane; q < P; q += ASR_WAVE) {
+    const double2 v = part[((size_t)q * ntiles + t) * tw + s];
+    a += v.x;
+    b += v.y;
+  }
+  a = asr_wave_sum_d(a);
+  b = asr_wave_sum_d(b);
+  if (MODE == 0) {
+    double nv = 0.;                 // |V| (integers: exact in any order)
+    for (int n = lane; n < N; n += ASR_WAVE) nv += (double)seqbn_len(lens, n, T);
+    nv = asr_wave_sum_d(nv);
+    if (lane != 0) return;
+    const double cnt = nv > 0. ? nv : 1.;
+    const double dm = a / cnt;
+    const double mean = (double)p[c] + dm;
+    double var = b / cnt - dm * dm;
+    var = var > 0. ? var : 0.;
+    const float mh = (float)mean;
+    stats[c] = mh;
+    stats[W + c] = (float)(mean - (double)mh);
+    stats[2 * W + c] = (float)(1.0 / sqrt(var + (double)eps));
+    stats[3 * W + c] = (float)var;
+    if (c == 0) {
+      stats[4 * W] = (float)nv;
+      stats[4 * W + 1] = stats[4 * W + 2] = stats[4 * W + 3] = 0.f;
+    }
+    if (moments != nullptr) {
+      const double w = (double)weight * nv;
+      const double d = mean - (double)(shift != nullptr ? shift[c] : mh);
+      moments[4 + c] = (float)(w * d);
+      moments[4 + W + c] = (float)(w * (var + d * d));
+      if (c == 0) {
+        moments[0] = (float)w;
+        moments[1] = moments[2] = moments[3] = 0.f;
+      }
+    }
+  } else {
+    if (lane != 0) return;
+    const double nv = (double)stats[4 * W];
+    const double cnt = nv > 0. ? nv : 1.;
+    dgamma[c] = (float)b;
+    if (dbeta != nullptr) dbeta[c] = (float)a;
+    coef[c] = (float)(a / cnt);
+    coef[W + c] = (float)(b / cnt);
+  }
+}
+
+// Element-wise passes over all T * n_pad rows.  MODE 0: training apply (stats), 1: inference
+// apply (running mean / variance), 2: backward dp (stats + coef; the valid / padded split) and
+// max |dp| (bits of a non-negative float: an integer atomicMax, order-independent).
+template <int MODE>
+__global__ void __launch_bounds__(BN_THREADS)
+seqbn_apply_kernel(const float* __restrict__ p, const float* __restrict__ da,
+                   const float* __restrict__ gamma, const float* __restrict__ beta,
+                   const float* __restrict__ stats, const float* __restrict__ rmean,
+                   const float* __restrict__ rvar, const float* __restrict__ coef,
+                   const int* __restrict__ lens, float* __restrict__ out,
+                   unsigned* __restrict__ absmax, int T, int N, int n_pad, int ld, int W, int cw,
+                   int rw, int tw, long long rows, float eps) {
+  const int tid = threadIdx.x, tile = blockIdx.x;
+  const int cl = tid % cw, rl = tid / cw;
+  const int col = tile * tw + cl * 4;
+  float mx = 0.f;
+  if (rl < rw && col < ld) {
+    // the thread's four columns: coefficients (pad columns W <= col < ld: written as zeros)
+    float mh[4], ml[4], sc[4], is[4], be[4], cb[4], cc[4];
+    bool ok[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      ok[q] = col + q < W;
+      const int c = ok[q] ? col + q : 0;
+      be[q] = MODE == 2 ? 0.f : beta[c];
+      if (MODE == 1) {
+        mh[q] = rmean[c];
+        ml[q] = 0.f;
+        is[q] = 1.f / sqrtf(rvar[c] + eps);
+      } else {
+        mh[q] = stats[c];
+        ml[q] = stats[W + c];
+        is[q] = stats[2 * W + c];
+      }
+      sc[q] = is[q] * gamma[c];
+      if (MODE == 2) {
+        cb[q] = coef[c];
+        cc[q] = coef[W + c];
+      }
+    }
+    const long long step = (long long)rw * gridDim.y;
+    for (long long r = (long long)blockIdx.y * rw + rl; r < rows; r += step) {
+      const size_t o = (size_t)r * ld + col;
+      const long long t = r / n_pad;
+      const int n = (int)(r - t * n_pad);
+      float res[4] = {0.f, 0.f, 0.f, 0.f};
+      if (n < N) {
+        const float4 v = ld4(p + o);
+        if (MODE == 2) {
+          const float4 g = ld4(da + o);
+          const bool valid = t < seqbn_len(lens, n, T);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float xh = ((f4get(v, q) - mh[q]) - ml[q]) * is[q];
+            const float d = f4get(g, q);
+            const float e = valid ? (d - cb[q]) - xh * cc[q] : d;
+            res[q] = ok[q] ? sc[q] * e : 0.f;
+            mx = fmaxf(mx, fabsf(res[q]));
+          }
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float xc = (f4get(v, q) - mh[q]) - ml[q];
+            res[q] = ok[q] ? fmaf(xc, sc[q], be[q]) : 0.f;
+          }
+        }
+      }
+      st4(out + o, make_float4(res[0], res[1], res[2], res[3]));
+    }
+  }
+  if (MODE == 2 && absmax != nullptr) {
+    mx = asr_wave_max(mx);
+    if ((tid & (ASR_WAVE - 1)) == 0 && mx > 0.f) atomicMax(absmax, __float_as_uint(mx));
+  }
+}
+
 }  // namespace
 
 extern "C" size_t asr_bn_workspace_bytes(int T, int N, int n_pad, int ld, int W, int C) {
@@ -423,6 +651,92 @@ extern "C" int asr_bn_update_running(float* running_mean, float* running_var,
   hipLaunchKernelGGL(bn_update_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      running_mean, running_var, moments, shift, C, momentum, flag_a, flag_b,
                      flag_c, flag_d);
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
+}
+
+// ------------------------------------------------------------------------------- K18 entry points
+extern "C" size_t asr_seqbn_workspace_bytes(int T, int N, int n_pad, int ld, int W) {
+  BnGeo g;
+  if (!bn_geo(T, N, n_pad, ld, W, W, &g)) return 0;
+  return bn_partial_bytes(g) + asr_align_up((size_t)2 * W * sizeof(float), 256);
+}
+
+#define SEQBN_GEO_OR_FAIL(what)                                                                \
+  BnGeo g;                                                                                     \
+  ASR_CHECK_ARG(bn_geo(T, N, n_pad, ld, W, W, &g),                                             \
+                what ": bad geometry (T %d N %d n_pad %d ld %d W %d)", T, N, n_pad, ld, W);    \
+  ASR_CHECK_ARG(ws_bytes >= asr_seqbn_workspace_bytes(T, N, n_pad, ld, W) && workspace,        \
+                what ": workspace too small")
+
+extern "C" int asr_seqbn_fwd_train(const float* p, float* y, const float* gamma,
+                                   const float* beta, const int* lens, float* stats,
+                                   float* moments, const float* shift, float weight, int T, int N,
+                                   int n_pad, int ld, int W, float eps, void* workspace,
+                                   size_t ws_bytes, asr_stream_t stream) {
+  ASR_CHECK_ARG(p && y && gamma && beta && stats && eps > 0.f && weight >= 0.f,
+                "seqbn_fwd_train: bad arguments");
+  SEQBN_GEO_OR_FAIL("seqbn_fwd_train");
+  hipStream_t s = (hipStream_t)stream;
+  double2* part = (double2*)workspace;
+  hipLaunchKernelGGL(seqbn_reduce_kernel<0>, dim3(g.ntiles, g.P), dim3(BN_THREADS), 0, s, p,
+                     nullptr, nullptr, lens, T, N, n_pad, ld, W, g.cw, g.rw, g.tw, g.ntiles,
+                     g.nreal, g.rpp, part);
+  ASR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(seqbn_finalize_kernel<0>, dim3(W), dim3(ASR_WAVE), 0, s, part, p, lens, T,
+                     N, W, g.ntiles, g.tw, g.P, eps, stats, moments, shift, weight, nullptr,
+                     nullptr, nullptr);
+  ASR_CHECK_LAUNCH();
+  const long long rows = (long long)T * n_pad;
+  hipLaunchKernelGGL(seqbn_apply_kernel<0>, dim3(g.ntiles, bn_apply_py(g, rows)),
+                     dim3(BN_THREADS), 0, s, p, nullptr, gamma, beta, stats, nullptr, nullptr,
+                     nullptr, nullptr, y, nullptr, T, N, n_pad, ld, W, g.cw, g.rw, g.tw, rows,
+                     eps);
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
+}
+
+extern "C" int asr_seqbn_fwd_infer(const float* p, float* y, const float* gamma,
+                                   const float* beta, const float* running_mean,
+                                   const float* running_var, int T, int N, int n_pad, int ld,
+                                   int W, float eps, asr_stream_t stream) {
+  ASR_CHECK_ARG(p && y && gamma && beta && running_mean && running_var && eps > 0.f,
+                "seqbn_fwd_infer: bad arguments");
+  BnGeo g;
+  ASR_CHECK_ARG(bn_geo(T, N, n_pad, ld, W, W, &g), "seqbn_fwd_infer: bad geometry");
+  const long long rows = (long long)T * n_pad;
+  hipLaunchKernelGGL(seqbn_apply_kernel<1>, dim3(g.ntiles, bn_apply_py(g, rows)),
+                     dim3(BN_THREADS), 0, (hipStream_t)stream, p, nullptr, gamma, beta, nullptr,
+                     running_mean, running_var, nullptr, nullptr, y, nullptr, T, N, n_pad, ld, W,
+                     g.cw, g.rw, g.tw, rows, eps);
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
+}
+
+extern "C" int asr_seqbn_bwd(const float* p, const float* da, const float* gamma,
+                             const int* lens, const float* stats, float* dp, float* dgamma,
+                             float* dbeta, float* dp_absmax, int T, int N, int n_pad, int ld,
+                             int W, void* workspace, size_t ws_bytes, asr_stream_t stream) {
+  ASR_CHECK_ARG(p && da && gamma && stats && dp && dgamma, "seqbn_bwd: bad arguments");
+  ASR_CHECK_ARG(dp != da && dp != p, "seqbn_bwd: dp must not alias p or da");
+  SEQBN_GEO_OR_FAIL("seqbn_bwd");
+  hipStream_t s = (hipStream_t)stream;
+  double2* part = (double2*)workspace;
+  float* coef = (float*)((char*)workspace + bn_partial_bytes(g));
+  hipLaunchKernelGGL(seqbn_reduce_kernel<1>, dim3(g.ntiles, g.P), dim3(BN_THREADS), 0, s, p, da,
+                     stats, nullptr, T, N, n_pad, ld, W, g.cw, g.rw, g.tw, g.ntiles, g.nreal,
+                     g.rpp, part);
+  ASR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(seqbn_finalize_kernel<1>, dim3(W), dim3(ASR_WAVE), 0, s, part, p, nullptr,
+                     T, N, W, g.ntiles, g.tw, g.P, 0.f, const_cast<float*>(stats), nullptr,
+                     nullptr, 0.f, dgamma, dbeta, coef);
+  ASR_CHECK_LAUNCH();
+  if (dp_absmax) ASR_CHECK_HIP(hipMemsetAsync(dp_absmax, 0, sizeof(float), s));
+  const long long rows = (long long)T * n_pad;
+  hipLaunchKernelGGL(seqbn_apply_kernel<2>, dim3(g.ntiles, bn_apply_py(g, rows)),
+                     dim3(BN_THREADS), 0, s, p, da, gamma, nullptr, stats, nullptr, nullptr, coef,
+                     lens, dp, reinterpret_cast<unsigned*>(dp_absmax), T, N, n_pad, ld, W, g.cw,
+                     g.rw, g.tw, rows, 0.f);
   ASR_CHECK_LAUNCH();
   return ASR_OK;
 }

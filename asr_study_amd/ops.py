@@ -594,6 +594,67 @@ def bn_update_running(running_mean, running_var, moments, C, momentum, shift=Non
             'asr_bn_update_running')
 
 
+# --------------------------------------------------------------------------- sequence-wise BN (K18)
+def seqbn_stats_len(W):
+    """Floats of a stats block: [mean_hi | mean_lo | invstd | var] (W each) + [|V|, 0, 0, 0]."""
+    return 4 * int(W) + 4
+
+
+def _seqbn_ws(T, N, n_pad, ld, W, device):
+    nbytes = L.load().asr_seqbn_workspace_bytes(int(T), int(N), int(n_pad), int(ld), int(W))
+    if nbytes == 0:
+        L.check(-1, 'asr_seqbn_workspace_bytes (T %d N %d n_pad %d ld %d W %d)'
+                % (T, N, n_pad, ld, W))
+    return WS.get('bn', nbytes, device), nbytes
+
+
+def _check_lens(lens, N):
+    if lens is not None and (lens.dtype != torch.int32 or not lens.is_contiguous()
+                             or lens.numel() < N or not lens.is_cuda):
+        raise ValueError('lens: a contiguous CUDA int32 tensor of at least N = %d entries' % N)
+
+
+def seqbn_fwd_train(p, y, gamma, beta, stats, N, W, lens=None, eps=1e-3, moments=None,
+                    shift=None, weight=1.0):
+    """Training-phase sequence-wise BatchNormalization of p (T, n_pad, ld): statistics over the
+    valid rows (n < N, t < lens[n]; lens None: all frames), y for every real row; stats
+    (seqbn_stats_len(W)); moments (bn_moments_len(W), optional) with w = weight * |V|."""
+    _check_f32(p, y, gamma, beta, stats, moments, shift)
+    _check_lens(lens, N)
+    T, n_pad, ld = p.shape
+    ws, nbytes = _seqbn_ws(T, N, n_pad, ld, W, p.device)
+    L.check(L.load().asr_seqbn_fwd_train(_ptr(p), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(lens),
+                                         _ptr(stats), _ptr(moments), _ptr(shift), float(weight),
+                                         int(T), int(N), int(n_pad), int(ld), int(W), float(eps),
+                                         _ptr(ws), nbytes, _stream()), 'asr_seqbn_fwd_train')
+    return y
+
+
+def seqbn_fwd_infer(p, y, gamma, beta, running_mean, running_var, N, W, eps=1e-3):
+    """Inference-phase affine map on the running moments (one pass, no lengths)."""
+    _check_f32(p, y, gamma, beta, running_mean, running_var)
+    T, n_pad, ld = p.shape
+    L.check(L.load().asr_seqbn_fwd_infer(_ptr(p), _ptr(y), _ptr(gamma), _ptr(beta),
+                                         _ptr(running_mean), _ptr(running_var), int(T), int(N),
+                                         int(n_pad), int(ld), int(W), float(eps), _stream()),
+            'asr_seqbn_fwd_infer')
+    return y
+
+
+def seqbn_bwd(p, da, gamma, stats, dp, dgamma, N, W, lens=None, dbeta=None, dp_absmax=None):
+    """dgamma (W), optional dbeta (W) -- both over every real row -- dp (same shape as p) with
+    the valid / padded split, and max |dp| (1,), from the saved p and stats."""
+    _check_f32(p, da, gamma, stats, dp, dgamma, dbeta, dp_absmax)
+    _check_lens(lens, N)
+    T, n_pad, ld = p.shape
+    ws, nbytes = _seqbn_ws(T, N, n_pad, ld, W, p.device)
+    L.check(L.load().asr_seqbn_bwd(_ptr(p), _ptr(da), _ptr(gamma), _ptr(lens), _ptr(stats),
+                                   _ptr(dp), _ptr(dgamma), _ptr(dbeta), _ptr(dp_absmax), int(T),
+                                   int(N), int(n_pad), int(ld), int(W), _ptr(ws), nbytes,
+                                   _stream()), 'asr_seqbn_bwd')
+    return dp
+
+
 def lstm_dz_hl_supported(T, n_pad, H, mode=0, compact=False, act=0):
     """Whether lstm_seq_bwd would write packed planes for this geometry (asr_lstm_dz_hl_supported:
     the plain cell on the two-dimensional-split BPTT kernels, persistent mode, split-fp16)."""

@@ -99,6 +99,8 @@ def _gru_config(name, s):
            'dropout_U': float(s.dropout_U)}
     if mv is not None:
         cfg['max_value'] = mv
+    if getattr(s, 'bn', False):     # (only then: files of every other model keep their bytes)
+        cfg.update(batch_norm=True, bn_epsilon=float(s.bn_eps), bn_momentum=float(s.bn_momentum))
     return cfg
 
 
@@ -355,7 +357,9 @@ def topology_from_config(text):
                 inner_activation=r.get('inner_activation', 'hard_sigmoid'),
                 W_regularizer=reg(r.get('W_regularizer')), U_regularizer=reg(r.get('U_regularizer')),
                 dropout_W=r.get('dropout_W', 0.), dropout_U=r.get('dropout_U', 0.),
-                consume_less=r.get('consume_less', 'gpu')),
+                consume_less=r.get('consume_less', 'gpu'),
+                batch_norm=bool(r.get('batch_norm', False)), bn_epsilon=r.get('bn_epsilon', 1e-3),
+                bn_momentum=r.get('bn_momentum', 0.99)),
                 merge_mode=c.get('merge_mode', 'concat'))(o)
         elif kind == 'Bidirectional' and c['layer']['class_name'] == 'RHN':
             r = c['layer']['config']

@@ -54,7 +54,8 @@ const char* asr_last_error(void);
  * 107: asr_rnn_args and the asr_rnn_* / asr_activation_* entry points (K14); the asr_bn_*
  * entry points (K15: plain scalar arguments, no struct, so the version stays); asr_gru_args
  * and the asr_gru_* entry points (K16: additions only, no existing layout changes); asr_rhn_args
- * and the asr_rhn_* entry points (K17: additions only as well). */
+ * and the asr_rhn_* entry points (K17: additions only as well); the asr_seqbn_* entry points
+ * (K18: plain scalar arguments again). */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -638,6 +639,37 @@ int asr_bn_update_running(float* running_mean, float* running_var, const float* 
                           const float* shift, int C, float momentum, const int* flag_a,
                           const int* flag_b, const int* flag_c, const int* flag_d,
                           asr_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K18 sequence-wise BatchNormalization of a recurrent layer's input         */
+/* projection (arXiv 1510.01378), csrc/batchnorm.hip.  p, y, da, dp are      */
+/* time-major slabs (T, n_pad, ld) with W <= ld real columns, one channel    */
+/* per column; lens (N device ints, NULL: every frame) holds each sample's   */
+/* length on this time axis, clamped to [0, T] inside.  The statistics are   */
+/* taken over the VALID rows (n < N, t < len_n) only; every real row (n < N, */
+/* all T frames) is normalised with them.  Rows n >= N and pad columns of y  */
+/* and dp are written as zeros.  No float atomics: bit-identical repeats.    */
+/*  stats (4W + 4 floats): [mean_hi | mean_lo | 1/sqrt(var + eps) | var |    */
+/*    |V|, 0, 0, 0], |V| the number of valid rows.                           */
+/*  moments (4 + 2W floats, optional): the block of asr_bn_fwd_train with    */
+/*    w = weight * |V|, for asr_bn_update_running (C = W).                   */
+/*  asr_seqbn_bwd: dgamma = sum da * xhat and dbeta = sum da (optional) over */
+/*    every real row, written, not accumulated; dp = gamma invstd (da -      */
+/*    [row valid] (dbeta + xhat dgamma) / |V|); dp_absmax (optional) <- max  */
+/*    |dp|.  xhat is recomputed from p and stats, never from y.              */
+/* ------------------------------------------------------------------------ */
+size_t asr_seqbn_workspace_bytes(int T, int N, int n_pad, int ld, int W);
+int asr_seqbn_fwd_train(const float* p, float* y, const float* gamma, const float* beta,
+                        const int* lens, float* stats, float* moments, const float* shift,
+                        float weight, int T, int N, int n_pad, int ld, int W, float eps,
+                        void* workspace, size_t ws_bytes, asr_stream_t stream);
+int asr_seqbn_fwd_infer(const float* p, float* y, const float* gamma, const float* beta,
+                        const float* running_mean, const float* running_var, int T, int N,
+                        int n_pad, int ld, int W, float eps, asr_stream_t stream);
+int asr_seqbn_bwd(const float* p, const float* da, const float* gamma, const int* lens,
+                  const float* stats, float* dp, float* dgamma, float* dbeta, float* dp_absmax,
+                  int T, int N, int n_pad, int ld, int W, void* workspace, size_t ws_bytes,
+                  asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* K7  CTC loss + gradient.  Replaces core/ctc_utils.py:60-70 ->             */
