@@ -23,6 +23,7 @@ def _deps():
     return [os.path.join(CSRC, s) for s in SOURCES] + [
         os.path.join(CSRC, 'common.h'),
         os.path.join(CSRC, 'lstm_common.h'),
+        os.path.join(CSRC, 'rec_tile.h'),
         os.path.join(os.path.dirname(HERE), 'include', 'asr_hip.h')]
 
 

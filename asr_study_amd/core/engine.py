@@ -1114,7 +1114,8 @@ class Model(object):
                 BW, BU = stage_masks(si)[:2]
                 rec['BW'], rec['BU'] = BW, BU
                 zx = self._buf('rzx%d' % si, (T, n_pad, 2, Hp))
-                self._rnn_input_gemm(a.contiguous(), s, zx, BW, rows, n_pad)
+                self._rec_proj(a.contiguous(), s, zx, Hp, BW, rows, n_pad,
+                               bias=self._view(s.ob, 2 * Hp))
                 h = self._buf('rh%d' % si, (T, n_pad, 2, Hp))
                 ysum = self._buf('rsum%d' % si, (T, n_pad, Hp)) if s.merge == 'sum' else None
                 rec['ws'] = ops.rnn_seq_fwd(zx, self._view(s.oU, 2 * Hp * Hp), h, T, n_pad, Hp,
@@ -1142,15 +1143,8 @@ class Model(object):
         BW, BU = masks
         rec['BW'], rec['BU'] = BW, BU
         zx = self._buf('gzx%d' % si, (T, n_pad, 2, 3 * Hp))
-        bias = None if s.bn else self._view(s.ob, 6 * Hp)
-        if BW is None:
-            ops.gemm(a, self.params, zx, rows, 6 * Hp, s.f_in_pad, b_off=s.oW, bias=bias)
-        else:
-            for d in range(2):
-                ops.gemm(a, self.params, zx, rows, 3 * Hp, s.f_in_pad, ldb=6 * Hp, ldc=6 * Hp,
-                         b_off=s.oW + d * 3 * Hp, c_off=d * 3 * Hp,
-                         bias=None if s.bn else bias[d * 3 * Hp:(d + 1) * 3 * Hp],
-                         a_scale=BW[d], a_scale_period=n_pad)
+        self._rec_proj(a, s, zx, 3 * Hp, BW, rows, n_pad,
+                       bias=None if s.bn else self._view(s.ob, 6 * Hp))
         if s.bn:
             zx = self._seqbn_forward(s, si, zx, rec, training, n_real, bn_weight, seq_len)
         h = self._buf('gh%d' % si, (T, n_pad, 2, Hp))
@@ -1204,18 +1198,10 @@ class Model(object):
                         shared_dy=s.merge == 'sum', db_part=dbp, dz_absmax=zmx)
         if not s.bn:
             ops.colsum(dbp, n_pad // 16, 6 * Hp, 6 * Hp, self._gview(s.ob, 6 * Hp))
-        kk = (T - 1) * n_pad
         for d in range(2):
             oU = s.oU + d * Hp * 3 * Hp
-            # h_prev is h one frame earlier in the direction's processing order
-            if kk > 0:
-                ops.gemm(h, dg, self.grads, Hp, 2 * Hp, kk, trans_a=True, lda=2 * Hp, ldb=6 * Hp,
-                         ldc=3 * Hp, a_off=d * Hp + (0 if d == 0 else n_pad * 2 * Hp),
-                         b_off=d * 3 * Hp + (n_pad * 6 * Hp if d == 0 else 0), c_off=oU,
-                         split_k=split, a_scale=None if BU is None else BU[d],
-                         a_scale_period=n_pad, b_absmax=zmx)
-            else:
-                self._gview(oU, Hp * 3 * Hp).view(Hp, 3 * Hp)[:, :2 * Hp].zero_()
+            self._rec_du_prev(h, dg, oU, d, 3 * Hp, 2 * Hp, T, n_pad, Hp,
+                              None if BU is None else BU[d], split, zmx)
             ops.gemm(rec['rm'], dg, self.grads, Hp, Hp, rows, trans_a=True, lda=2 * Hp,
                      ldb=6 * Hp, ldc=3 * Hp, a_off=d * Hp, b_off=d * 3 * Hp + 2 * Hp,
                      c_off=oU + 2 * Hp, split_k=split, b_absmax=zmx)
@@ -1228,28 +1214,8 @@ class Model(object):
                           rec['stats'], dp, self._gview(s.og, 6 * Hp), rec['N'], 6 * Hp,
                           lens=rec['lens'], dbeta=self._gview(s.obeta, 6 * Hp), dp_absmax=zmx)
             dg = dp
-        a_in = a_in.contiguous()
-        if BW is None:
-            ops.gemm(a_in, dg, self.grads, s.f_in_pad, 6 * Hp, rows, trans_a=True, c_off=s.oW,
-                     split_k=split, b_absmax=zmx)
-        else:
-            for d in range(2):
-                ops.gemm(a_in, dg, self.grads, s.f_in_pad, 3 * Hp, rows, trans_a=True,
-                         ldb=6 * Hp, ldc=6 * Hp, b_off=d * 3 * Hp, c_off=s.oW + d * 3 * Hp,
-                         split_k=split, a_scale=BW[d], a_scale_period=n_pad, b_absmax=zmx)
-        if first:
-            return None
-        dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-        if BW is None:
-            ops.gemm(dg, self.params, dx, rows, s.f_in_pad, 6 * Hp, trans_b=True, b_off=s.oW,
-                     a_absmax=zmx)
-        else:
-            for d in range(2):
-                ops.gemm(dg, self.params, dx, rows, s.f_in_pad, 3 * Hp, trans_b=True,
-                         lda=6 * Hp, ldb=6 * Hp, a_off=d * 3 * Hp, b_off=s.oW + d * 3 * Hp,
-                         c_scale=BW[d], c_scale_period=n_pad, beta=0.0 if d == 0 else 1.0,
-                         a_absmax=zmx)
-        return dx
+        self._rec_dw(a_in.contiguous(), dg, s, 3 * Hp, BW, rows, n_pad, split, zmx)
+        return self._rec_dx(dg, s, si, 3 * Hp, BW, T, n_pad, zmx, first)
 
     def _rhn_forward(self, s, si, a, rec, masks, n_pad):
         """Bidirectional(RHN) stage (csrc/rhn.hip): zx = (a (.) B_W[d]) @ W_d from the GEMMs (the
@@ -1260,12 +1226,7 @@ class Model(object):
         BW, BU = masks
         rec['BW'], rec['BU'] = BW, BU
         zx = self._buf('hzx%d' % si, (T, n_pad, 2, Wd))
-        if BW is None:
-            ops.gemm(a, self.params, zx, rows, 2 * Wd, s.f_in_pad, b_off=s.oW)
-        else:
-            for d in range(2):
-                ops.gemm(a, self.params, zx, rows, Wd, s.f_in_pad, ldb=2 * Wd, ldc=2 * Wd,
-                         b_off=s.oW + d * Wd, c_off=d * Wd, a_scale=BW[d], a_scale_period=n_pad)
+        self._rec_proj(a, s, zx, Wd, BW, rows, n_pad)
         h = self._buf('hh%d' % si, (Ld, T, n_pad, 2, Hp))
         gates = self._buf('hgates%d' % si, (Ld, T, n_pad, 2, Wd))
         ysum = self._buf('hsum%d' % si, (T, n_pad, Hp)) if s.merge == 'sum' else None
@@ -1291,7 +1252,6 @@ class Model(object):
                         T, n_pad, Hp, Ld, coupling=s.coupling, act=s.act, mask_u=BU,
                         shared_dy=s.merge == 'sum', db_part=dbp, dz_absmax=zmx)
         ops.colsum(dbp, n_pad // 16, 2 * Ld * Wd, 2 * Ld * Wd, self._gview(s.ob, 2 * Ld * Wd))
-        kk = (T - 1) * n_pad
         for d in range(2):
             for l in range(Ld):
                 oU = s.oU + (d * Ld + l) * Hp * Wd
@@ -1301,37 +1261,11 @@ class Model(object):
                              ldb=2 * Wd, ldc=Wd, a_off=(l - 1) * rows * 2 * Hp + d * Hp,
                              b_off=l * rows * 2 * Wd + d * Wd, c_off=oU, split_k=split,
                              a_scale=scale, a_scale_period=n_pad, b_absmax=zmx)
-                elif kk > 0:
-                    ops.gemm(h, dg, self.grads, Hp, Wd, kk, trans_a=True, lda=2 * Hp,
-                             ldb=2 * Wd, ldc=Wd,
-                             a_off=(Ld - 1) * rows * 2 * Hp + d * Hp
-                             + (0 if d == 0 else n_pad * 2 * Hp),
-                             b_off=d * Wd + (n_pad * 2 * Wd if d == 0 else 0), c_off=oU,
-                             split_k=split, a_scale=scale, a_scale_period=n_pad, b_absmax=zmx)
                 else:
-                    self._gview(oU, Hp * Wd).zero_()
-        a_in = a_in.contiguous()
-        if BW is None:
-            ops.gemm(a_in, dg, self.grads, s.f_in_pad, 2 * Wd, rows, trans_a=True, c_off=s.oW,
-                     split_k=split, b_absmax=zmx)
-        else:
-            for d in range(2):
-                ops.gemm(a_in, dg, self.grads, s.f_in_pad, Wd, rows, trans_a=True,
-                         ldb=2 * Wd, ldc=2 * Wd, b_off=d * Wd, c_off=s.oW + d * Wd,
-                         split_k=split, a_scale=BW[d], a_scale_period=n_pad, b_absmax=zmx)
-        if first:
-            return None
-        dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-        if BW is None:
-            ops.gemm(dg, self.params, dx, rows, s.f_in_pad, 2 * Wd, trans_b=True, b_off=s.oW,
-                     a_absmax=zmx)
-        else:
-            for d in range(2):
-                ops.gemm(dg, self.params, dx, rows, s.f_in_pad, Wd, trans_b=True,
-                         lda=2 * Wd, ldb=2 * Wd, a_off=d * Wd, b_off=s.oW + d * Wd,
-                         c_scale=BW[d], c_scale_period=n_pad, beta=0.0 if d == 0 else 1.0,
-                         a_absmax=zmx)
-        return dx
+                    self._rec_du_prev(h, dg, oU, d, Wd, Wd, T, n_pad, Hp, scale, split, zmx,
+                                      h_off=(Ld - 1) * rows * 2 * Hp)
+        self._rec_dw(a_in.contiguous(), dg, s, Wd, BW, rows, n_pad, split, zmx)
+        return self._rec_dx(dg, s, si, Wd, BW, T, n_pad, zmx, first)
 
     def _bn_forward(self, s, si, a, rec, training, n_real, bn_weight):
         """BatchNormalization stage: batch statistics of the n_real real rows in training (saved
@@ -1385,17 +1319,58 @@ class Model(object):
                                   self.bn_running[s.orun + Cp:s.orun + Cp + s.C], mom, s.C,
                                   s.momentum, shift=rec['shift'], flags=flags)
 
-    def _rnn_input_gemm(self, a, s, zx, BW, rows, n_pad):
-        """zx = (a (.) B_W[d]) @ W_d + b_d of a SimpleRNN stage, both directions."""
-        Hp = s.Hp
-        bias = self._view(s.ob, 2 * Hp)
+    # The GEMMs around a recurrence (SimpleRNN, GRU, RHN).  G is the gate width of one direction:
+    # the rows of zx and of the gate gradient dg hold both directions, 2 G wide, and so do W's.
+    def _rec_proj(self, a, s, zx, G, BW, rows, n_pad, bias=None):
+        """zx = (a (.) B_W[d]) @ W_d (+ b_d), both directions; bias (2 G) or None."""
         if BW is None:
-            ops.gemm(a, self.params, zx, rows, 2 * Hp, s.f_in_pad, b_off=s.oW, bias=bias)
+            ops.gemm(a, self.params, zx, rows, 2 * G, s.f_in_pad, b_off=s.oW, bias=bias)
             return
         for d in range(2):
-            ops.gemm(a, self.params, zx, rows, Hp, s.f_in_pad, ldb=2 * Hp, ldc=2 * Hp,
-                     b_off=s.oW + d * Hp, c_off=d * Hp, bias=bias[d * Hp:(d + 1) * Hp],
+            ops.gemm(a, self.params, zx, rows, G, s.f_in_pad, ldb=2 * G, ldc=2 * G,
+                     b_off=s.oW + d * G, c_off=d * G,
+                     bias=None if bias is None else bias[d * G:(d + 1) * G],
                      a_scale=BW[d], a_scale_period=n_pad)
+
+    def _rec_dw(self, a_in, dg, s, G, BW, rows, n_pad, split, zmx):
+        """dW[d] = (x (.) B_W[d])^T dg_d."""
+        if BW is None:
+            ops.gemm(a_in, dg, self.grads, s.f_in_pad, 2 * G, rows, trans_a=True, c_off=s.oW,
+                     split_k=split, b_absmax=zmx)
+            return
+        for d in range(2):
+            ops.gemm(a_in, dg, self.grads, s.f_in_pad, G, rows, trans_a=True, ldb=2 * G,
+                     ldc=2 * G, b_off=d * G, c_off=s.oW + d * G, split_k=split,
+                     a_scale=BW[d], a_scale_period=n_pad, b_absmax=zmx)
+
+    def _rec_dx(self, dg, s, si, G, BW, T, n_pad, zmx, first):
+        """dx = sum_d B_W[d] (.) (dg_d @ W_d^T); None for the first stage."""
+        if first:
+            return None
+        rows = T * n_pad
+        dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
+        if BW is None:
+            ops.gemm(dg, self.params, dx, rows, s.f_in_pad, 2 * G, trans_b=True, b_off=s.oW,
+                     a_absmax=zmx)
+            return dx
+        for d in range(2):
+            ops.gemm(dg, self.params, dx, rows, s.f_in_pad, G, trans_b=True, lda=2 * G,
+                     ldb=2 * G, a_off=d * G, b_off=s.oW + d * G, c_scale=BW[d],
+                     c_scale_period=n_pad, beta=0.0 if d == 0 else 1.0, a_absmax=zmx)
+        return dx
+
+    def _rec_du_prev(self, h, dg, c_off, d, G, N, T, n_pad, Hp, scale, split, zmx, h_off=0):
+        """grads[c_off:] (Hp, G), columns [0, N) = (h_prev (.) scale)^T dg_d[:, :N], where h_prev is
+        the slab h (T, n_pad, 2, Hp) at h_off one frame earlier in direction d's processing
+        order: 0 before the first frame, so T == 1 leaves zeros."""
+        kk = (T - 1) * n_pad
+        if kk > 0:
+            ops.gemm(h, dg, self.grads, Hp, N, kk, trans_a=True, lda=2 * Hp, ldb=2 * G, ldc=G,
+                     a_off=h_off + d * Hp + (0 if d == 0 else n_pad * 2 * Hp),
+                     b_off=d * G + (n_pad * 2 * G if d == 0 else 0), c_off=c_off,
+                     split_k=split, a_scale=scale, a_scale_period=n_pad, b_absmax=zmx)
+        else:
+            self._gview(c_off, Hp * G).view(Hp, G)[:, :N].zero_()
 
     def _rnn_backward(self, s, si, rec, da, first, split):
         """BPTT of a SimpleRNN stage (csrc/rnn.hip), then its weight gradients and dx from the
@@ -1412,38 +1387,11 @@ class Model(object):
                                       shared_dy=s.merge == 'sum', mode=self.lstm_mode,
                                       db_part=dbp, dz_absmax=zmx)
         ops.colsum(dbp, n_pad // 16, 2 * Hp, 2 * Hp, self._gview(s.ob, 2 * Hp))
-        kk = (T - 1) * n_pad
         for d in range(2):
-            # h_prev is h one frame earlier in the direction's processing order
-            if kk > 0:
-                ops.gemm(h, dz, self.grads, Hp, Hp, kk, trans_a=True, lda=2 * Hp, ldb=2 * Hp,
-                         ldc=Hp, a_off=d * Hp + (0 if d == 0 else n_pad * 2 * Hp),
-                         b_off=d * Hp + (n_pad * 2 * Hp if d == 0 else 0),
-                         c_off=s.oU + d * Hp * Hp, split_k=split,
-                         a_scale=None if BU is None else BU[d], a_scale_period=n_pad,
-                         b_absmax=zmx)
-            else:
-                self._gview(s.oU + d * Hp * Hp, Hp * Hp).zero_()
-        if BW is None:
-            ops.gemm(a_in, dz, self.grads, s.f_in_pad, 2 * Hp, rows, trans_a=True, c_off=s.oW,
-                     split_k=split, b_absmax=zmx)
-        else:
-            for d in range(2):
-                ops.gemm(a_in, dz, self.grads, s.f_in_pad, Hp, rows, trans_a=True, ldb=2 * Hp,
-                         ldc=2 * Hp, b_off=d * Hp, c_off=s.oW + d * Hp, split_k=split,
-                         a_scale=BW[d], a_scale_period=n_pad, b_absmax=zmx)
-        if first:
-            return None
-        dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-        if BW is None:
-            ops.gemm(dz, self.params, dx, rows, s.f_in_pad, 2 * Hp, trans_b=True, b_off=s.oW,
-                     a_absmax=zmx)
-        else:
-            for d in range(2):
-                ops.gemm(dz, self.params, dx, rows, s.f_in_pad, Hp, trans_b=True, lda=2 * Hp,
-                         ldb=2 * Hp, a_off=d * Hp, b_off=s.oW + d * Hp, c_scale=BW[d],
-                         c_scale_period=n_pad, beta=0.0 if d == 0 else 1.0, a_absmax=zmx)
-        return dx
+            self._rec_du_prev(h, dz, s.oU + d * Hp * Hp, d, Hp, Hp, T, n_pad, Hp,
+                              None if BU is None else BU[d], split, zmx)
+        self._rec_dw(a_in, dz, s, Hp, BW, rows, n_pad, split, zmx)
+        return self._rec_dx(dz, s, si, Hp, BW, T, n_pad, zmx, first)
 
     def _clip_bound(self, si):
         """1-element device tensor >= max|input of stage si| when that input is a clipped-ReLU

@@ -15,21 +15,15 @@
 //               the element-wise head of a step rides in the tail of the one before it.
 // There is no persistent form (asr_gru_args.mode 2 is an argument error): DESIGN.md 15.
 //
-// Geometry, as rnn.hip: a workgroup (256 threads) owns NR batch rows x J output columns of one
-// direction, NR * J = 1024, NR = 64 / 32 / 16 (the largest that divides n_pad).  The reduction
-// runs in chunks of 256: the chunk's operand is staged in LDS row by row (coalesced 1 KB reads, rows
-// padded by 4 floats so that the 16 lanes of a quarter-wave hit distinct banks), the four waves
-// split the chunk, every lane keeps a 4 x 4 register tile and consumes four reduction indices
-// per pass, the next chunk is in flight meanwhile.
-// Products are exact fp32 FMAs.  The activation slopes of BPTT are read from the SAVED gates
-// (hs' = 0.2 on 0 < gate < 1, else 0; act' from hh alone).  No float atomics: repeats are
-// bit-identical.
-#include "lstm_common.h"
+// Geometry and reduction: RecTile of rec_tile.h (NR batch rows x J output columns per workgroup,
+// chunked operand in LDS, 4 x 4 register tiles, fixed-order cross-wave sum).  This file keeps
+// what is the GRU's own: the address set-up of the four phases and their epilogues.
+// The activation slopes of BPTT are read from the SAVED gates (hs' = 0.2 on 0 < gate < 1, else 0;
+// act' from hh alone).
+#include "rec_tile.h"
 
 namespace {
 
-constexpr int kKc = 256;                   // reduction chunk
-constexpr int kActClipped = 7;
 enum { kFwdA = 0, kFwdB = 1, kBwdA = 2, kBwdB = 3 };
 
 struct GruParams {
@@ -51,38 +45,14 @@ struct GruParams {
   float* qr;               // BPTT workspace (n_pad, 2, Hp): q (.) r
 };
 
-__device__ __forceinline__ float gru_act(int id, float clip, float z) {
-  if (id == kActClipped) return fminf(fmaxf(z, 0.f), clip);
-  return asr_act_apply(id, z);
-}
-__device__ __forceinline__ float gru_slope(int id, float clip, float h) {
-  if (id == kActClipped) return (h > 0.f && h < clip) ? 1.f : 0.f;
-  return asr_act_slope(id, h);
-}
-__device__ __forceinline__ float hs(float a) { return fminf(fmaxf(0.2f * a + 0.5f, 0.f), 1.f); }
-__device__ __forceinline__ float hs_slope(float g) { return (g > 0.f && g < 1.f) ? 0.2f : 0.f; }
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 mul4(float4 a, float4 b) {
-  return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
-}
-
 template <int NR, int PH>
 __global__ void __launch_bounds__(kThreads)
 gru_step_kernel(GruParams p) {
-  constexpr int J = 1024 / NR;
-  constexpr int KP = kKc + 4;              // padded LDS row of the operand (bank spread)
-  constexpr int NQ = NR / 4;
-  constexpr int OPV = NR * kKc / 4 / kThreads;
-  constexpr int UV = kKc * J / 4 / kThreads;
-  __shared__ __attribute__((aligned(16))) float lds[NR * KP + kKc * J];
-  float* opS = lds;                        // [NR][KP]: row n, reduction index minor
-  float* Us = lds + NR * KP;               // [kKc][J]
-  float* red = lds;                        // [4][NR][J] after the last chunk (aliases opS)
+  using Tile = RecTile<NR>;
+  constexpr int J = Tile::J;
+  __shared__ __attribute__((aligned(16))) float lds[Tile::kLdsFloats];
 
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const int jb = blockIdx.x, nt = blockIdx.y, d = blockIdx.z;
   const int Hp = p.Hp, n_pad = p.n_pad, T = p.T, s = p.s;
   const int j0 = jb * J, n0 = nt * NR;
@@ -115,95 +85,20 @@ gru_step_kernel(GruParams p) {
     mat = p.U + (size_t)d * 3 * Hp * Hp; K = 2 * Hp;
     skip = s >= T;
   }
-  const int nchunks = (K + kKc - 1) / kKc;
 
   // epilogue ownership: row en, columns ej .. ej + 3 of the tile
   const int en = (4 * tid) / J, ej = (4 * tid) % J;
   const int jg = j0 + ej;
   const bool eown = jg < nout;
-  // compute ownership: rows nq + NQ i (i < 4: neighbouring lanes read neighbouring LDS rows,
-  // whose padded stride spreads them over the banks), columns 4 jq .. +3, reduction quarter w
-  const int nq = lane % NQ, jq = lane / NQ;
 
-  float acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-
-  if (!skip) {
-    float4 cop[OPV], cu[UV];
-    auto load = [&](int c) {
-      const int kc = c * kKc;
-#pragma unroll
-      for (int i = 0; i < OPV; ++i) {
-        // a wave reads one row's whole chunk (1 KB, contiguous)
-        const int idx = tid + i * kThreads;
-        const int n = idx / (kKc / 4), k = kc + 4 * (idx % (kKc / 4));
-        cop[i] = k < K ? ld4(op + (size_t)n * op_ld + k) : zero4();
-      }
-#pragma unroll
-      for (int i = 0; i < UV; ++i) {
-        const int idx = tid + i * kThreads;
-        const int jj = 4 * (idx % (J / 4)), k = kc + idx / (J / 4);
-        cu[i] = (k < K && j0 + jj < nout) ? ld4(mat + (size_t)k * ldm + j0 + jj) : zero4();
-      }
-    };
-    load(0);
-    for (int c = 0; c < nchunks; ++c) {
-      __syncthreads();                                 // previous chunk fully consumed
-      const int kc = c * kKc;
-#pragma unroll
-      for (int i = 0; i < OPV; ++i) {
-        const int idx = tid + i * kThreads;
-        const int n = idx / (kKc / 4), kl = 4 * (idx % (kKc / 4));
-        float4 v = cop[i];
-        if (PH == kFwdA && mu != nullptr && kc + kl < K)      // m = h_prev (.) B_U
-          v = mul4(v, ld4(mu + (size_t)n * Hp + kc + kl));
-        st4(opS + n * KP + kl, v);
-      }
-#pragma unroll
-      for (int i = 0; i < UV; ++i) {
-        const int idx = tid + i * kThreads;
-        const int jj = 4 * (idx % (J / 4)), kl = idx / (J / 4);
-        st4(Us + kl * J + jj, cu[i]);
-      }
-      __syncthreads();
-      if (c + 1 < nchunks) load(c + 1);                // in flight while this chunk reduces
-      const int kw = w * (kKc / 4);
-#pragma unroll 2
-      for (int kk = 0; kk < kKc / 4; kk += 4) {
-        float av[4][4], bv[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float4 a = ld4(opS + (nq + NQ * i) * KP + kw + kk);
-          av[i][0] = a.x; av[i][1] = a.y; av[i][2] = a.z; av[i][3] = a.w;
-          const float4 b = ld4(Us + (kw + kk + i) * J + 4 * jq);
-          bv[i][0] = b.x; bv[i][1] = b.y; bv[i][2] = b.z; bv[i][3] = b.w;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(av[i][q], bv[q][j], acc[i][j]);
-      }
-    }
-  }
   float4 r = zero4();
   if (!skip) {
-    // cross-wave sum of the four reduction quarters (fixed order)
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      st4(red + (w * NR + nq + NQ * i) * J + 4 * jq,
-          make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]));
-    __syncthreads();
-#pragma unroll
-    for (int ww = 0; ww < 4; ++ww) {
-      const float4 v = ld4(red + (ww * NR + en) * J + ej);
-      r.x += v.x; r.y += v.y; r.z += v.z; r.w += v.w;
-    }
+    float acc[4][4];
+    Tile::template reduce<PH == kFwdA>(                  // kFwdA: m = h_prev (.) B_U
+        lds, op, op_ld, K, mat, ldm, mu, Hp,
+        [&](int jj) { return j0 + jj < nout ? j0 + jj : -1; }, acc);
+    Tile::spill(lds, acc);
+    r = Tile::total(lds, en, ej);
   }
   if (!eown) return;
 
@@ -212,7 +107,8 @@ gru_step_kernel(GruParams p) {
     // columns [0, Hp): z; [Hp, 2Hp): r (a float4 never straddles the two: Hp % 4 == 0)
     const size_t o = (row * 2 + d) * 3 * Hp + jg;
     const float4 zx = ld4(p.zx + o);
-    const float4 g = make_float4(hs(zx.x + r.x), hs(zx.y + r.y), hs(zx.z + r.z), hs(zx.w + r.w));
+    const float4 g = make_float4(hard_sigmoid(zx.x + r.x), hard_sigmoid(zx.y + r.y),
+                                 hard_sigmoid(zx.z + r.z), hard_sigmoid(zx.w + r.w));
     st4(p.gates + o, g);
     if (jg >= Hp) {
       const int j = jg - Hp;
@@ -228,8 +124,8 @@ gru_step_kernel(GruParams p) {
     const float4 zx = ld4(p.zx + og + 2 * Hp + jg);
     const float4 z = ld4(p.gates + og + jg);
     const float4 hp = s > 0 ? ld4(p.h + (rowp * 2 + d) * Hp + jg) : zero4();
-    const float4 hh = make_float4(gru_act(p.act, p.clip, zx.x + r.x), gru_act(p.act, p.clip, zx.y + r.y),
-                                  gru_act(p.act, p.clip, zx.z + r.z), gru_act(p.act, p.clip, zx.w + r.w));
+    const float4 hh = make_float4(rec_act(p.act, p.clip, zx.x + r.x), rec_act(p.act, p.clip, zx.y + r.y),
+                                  rec_act(p.act, p.clip, zx.z + r.z), rec_act(p.act, p.clip, zx.w + r.w));
     st4(p.gates + og + 2 * Hp + jg, hh);
     st4(p.h + oh, make_float4(z.x * hp.x + (1.f - z.x) * hh.x, z.y * hp.y + (1.f - z.y) * hh.y,
                               z.z * hp.z + (1.f - z.z) * hh.z, z.w * hp.w + (1.f - z.w) * hh.w));
@@ -263,76 +159,14 @@ gru_step_kernel(GruParams p) {
     const float4 hp = s - 1 > 0 ? ld4(p.h + (((size_t)tpp * n_pad + n0 + en) * 2 + d) * Hp + jg)
                                 : zero4();
     st4(p.da + og + 2 * Hp + jg,
-        make_float4(g.x * (1.f - z.x) * gru_slope(p.act, p.clip, hh.x),
-                    g.y * (1.f - z.y) * gru_slope(p.act, p.clip, hh.y),
-                    g.z * (1.f - z.z) * gru_slope(p.act, p.clip, hh.z),
-                    g.w * (1.f - z.w) * gru_slope(p.act, p.clip, hh.w)));
+        make_float4(g.x * (1.f - z.x) * rec_slope(p.act, p.clip, hh.x),
+                    g.y * (1.f - z.y) * rec_slope(p.act, p.clip, hh.y),
+                    g.z * (1.f - z.z) * rec_slope(p.act, p.clip, hh.z),
+                    g.w * (1.f - z.w) * rec_slope(p.act, p.clip, hh.w)));
     st4(p.da + og + jg,
         make_float4(g.x * (hp.x - hh.x) * hs_slope(z.x), g.y * (hp.y - hh.y) * hs_slope(z.y),
                     g.z * (hp.z - hh.z) * hs_slope(z.z), g.w * (hp.w - hh.w) * hs_slope(z.w)));
     st4(p.gbuf + ow, g);
-  }
-}
-
-// U (2, Hp, 3Hp) -> U^T (2, 3Hp, Hp)
-__global__ void gru_transpose_kernel(const float* __restrict__ U, float* __restrict__ Ut, int Hp) {
-  __shared__ float tile[32][33];
-  const int d = blockIdx.z, R = Hp, Cc = 3 * Hp;
-  const float* src = U + (size_t)d * R * Cc;
-  float* dst = Ut + (size_t)d * R * Cc;
-  const int bx = blockIdx.x * 32, by = blockIdx.y * 32;
-  for (int i = threadIdx.y; i < 32; i += 8) {
-    const int r = by + i, c = bx + threadIdx.x;
-    if (r < R && c < Cc) tile[i][threadIdx.x] = src[(size_t)r * Cc + c];
-  }
-  __syncthreads();
-  for (int i = threadIdx.y; i < 32; i += 8) {
-    const int r = bx + i, c = by + threadIdx.x;
-    if (r < Cc && c < R) dst[(size_t)r * R + c] = tile[threadIdx.x][i];
-  }
-}
-
-// y_sum (T, n_pad, Hp) = h[:, :, 0] + h[:, :, 1] (merge_mode='sum')
-__global__ void gru_sum_kernel(const float4* __restrict__ h, float4* __restrict__ y, long long rows,
-                               int hq) {
-  const long long n = rows * hq;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x) {
-    const long long r = i / hq, q = i % hq;
-    const float4 a = h[(r * 2) * hq + q], b = h[(r * 2 + 1) * hq + q];
-    y[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-  }
-}
-
-// db_part (n_pad / 16, 2, 3Hp): sums of da over the 16 rows of a batch tile and all frames, in a
-// fixed order (16 columns x 16 interleaved slices per workgroup, the slices added in sequence);
-// max |da| beside it.
-__global__ void __launch_bounds__(kThreads)
-gru_dbias_kernel(const float* __restrict__ da, float* __restrict__ db_part, unsigned* dz_absmax,
-                 int T, int n_pad, int Hp) {
-  __shared__ float part[16][17];
-  const int cl = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const int c = blockIdx.x * 16 + cl;
-  const int tile = blockIdx.y, d = blockIdx.z, W = 3 * Hp;
-  float sum = 0.f, mx = 0.f;
-  if (c < W) {
-    for (int i = sl; i < T * 16; i += 16) {
-      const int t = i >> 4, n = tile * 16 + (i & 15);
-      const float v = da[(((size_t)t * n_pad + n) * 2 + d) * W + c];
-      sum += v;
-      mx = fmaxf(mx, fabsf(v));
-    }
-  }
-  part[sl][cl] = sum;
-  __syncthreads();
-  if (sl == 0 && c < W && db_part != nullptr) {
-    float tot = 0.f;
-    for (int k = 0; k < 16; ++k) tot += part[k][cl];
-    db_part[((size_t)tile * 2 + d) * W + c] = tot;
-  }
-  if (dz_absmax != nullptr) {
-    mx = asr_wave_max(mx);
-    if ((threadIdx.x & 63) == 0) atomicMax(dz_absmax, __float_as_uint(mx));
   }
 }
 
@@ -342,19 +176,10 @@ struct GruPlan {
   size_t ut_bytes, vec_bytes;
 };
 
-bool act_ok(int id) { return id == 0 || id == 1 || id == 4 || id == kActClipped; }
-
 int make_gru_plan(const asr_gru_args* a, bool bwd, GruPlan* pl) {
-  ASR_CHECK_ARG(a != nullptr, "gru: null arguments");
-  ASR_CHECK_ARG(a->T >= 1 && a->n_pad >= 16 && a->n_pad % 16 == 0 && a->H >= 4 && a->H % 4 == 0,
-                "gru: T >= 1, n_pad a multiple of 16, H a positive multiple of 4 (T=%d n_pad=%d H=%d)",
-                a->T, a->n_pad, a->H);
-  ASR_CHECK_ARG(a->mode == 0 || a->mode == 1, "gru: mode %d: only the stepwise form exists "
-                "(0 = the plan's form, 1 = stepwise)", a->mode);
-  ASR_CHECK_ARG(act_ok(a->activation), "gru: activation id %d (tanh 0, relu 1, linear 4, "
-                "clipped relu 7)", a->activation);
-  ASR_CHECK_ARG(a->activation != kActClipped || a->clip > 0.f, "gru: clipped relu needs clip > 0");
-  pl->NR = a->n_pad % 64 == 0 ? 64 : (a->n_pad % 32 == 0 ? 32 : 16);
+  const int rc = rec_check_args("gru", a, false);
+  if (rc != ASR_OK) return rc;
+  pl->NR = rec_rows(a->n_pad);
   pl->J = 1024 / pl->NR;
   pl->NBT = a->n_pad / pl->NR;
   // the widest launch: forward phase A has 2H output columns, every other phase H
@@ -368,7 +193,7 @@ size_t gru_ws_bytes(const GruPlan& pl) { return 256 + pl.ut_bytes + 2 * pl.vec_b
 
 template <int NR>
 int gru_launch(int ph, const GruParams& p, int ncols, int nbt, hipStream_t stream) {
-  constexpr int J = 1024 / NR;
+  constexpr int J = RecTile<NR>::J;
   const dim3 grid((ncols + J - 1) / J, nbt, 2);
   switch (ph) {
     case kFwdA: hipLaunchKernelGGL((gru_step_kernel<NR, kFwdA>), grid, dim3(kThreads), 0, stream, p); break;
@@ -381,9 +206,9 @@ int gru_launch(int ph, const GruParams& p, int ncols, int nbt, hipStream_t strea
 }
 
 int gru_phase(const GruPlan& pl, int ph, const GruParams& p, int ncols, hipStream_t stream) {
-  return pl.NR == 64 ? gru_launch<64>(ph, p, ncols, pl.NBT, stream)
-       : pl.NR == 32 ? gru_launch<32>(ph, p, ncols, pl.NBT, stream)
-                     : gru_launch<16>(ph, p, ncols, pl.NBT, stream);
+  return rec_with_rows(pl.NR, [&](auto nr) {
+    return gru_launch<decltype(nr)::value>(ph, p, ncols, pl.NBT, stream);
+  });
 }
 
 int gru_run(const asr_gru_args* a, bool bwd, void* workspace, size_t ws_bytes, hipStream_t stream) {
@@ -415,21 +240,11 @@ int gru_run(const asr_gru_args* a, bool bwd, void* workspace, size_t ws_bytes, h
       if ((rc = gru_phase(pl, kFwdA, p, 2 * H, stream)) != ASR_OK) return rc;
       if ((rc = gru_phase(pl, kFwdB, p, H, stream)) != ASR_OK) return rc;
     }
-    if (a->y_sum) {
-      const long long rows = (long long)T * a->n_pad;
-      const long long n4 = rows * (H / 4);
-      const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-      hipLaunchKernelGGL(gru_sum_kernel, dim3(blocks), dim3(256), 0, stream,
-                         reinterpret_cast<const float4*>(a->h), reinterpret_cast<float4*>(a->y_sum),
-                         rows, H / 4);
-      ASR_CHECK_LAUNCH();
-    }
+    if (a->y_sum) return rec_sum(a->h, a->y_sum, (long long)T * a->n_pad, H, stream);
     return ASR_OK;
   }
   float* Ut = reinterpret_cast<float*>(ws + 256);
-  hipLaunchKernelGGL(gru_transpose_kernel, dim3((3 * H + 31) / 32, (H + 31) / 32, 2), dim3(32, 8),
-                     0, stream, a->U, Ut, H);
-  ASR_CHECK_LAUNCH();
+  if ((rc = rec_transpose(a->U, Ut, 2, H, 3 * H, stream)) != ASR_OK) return rc;
   p.U = Ut;
   // phase B of step s also prepares da_h, da_z of step s - 1: s = T is the prologue (carry 0)
   p.s = T;
@@ -439,13 +254,8 @@ int gru_run(const asr_gru_args* a, bool bwd, void* workspace, size_t ws_bytes, h
     if ((rc = gru_phase(pl, kBwdA, p, H, stream)) != ASR_OK) return rc;
     if (s > 0 && (rc = gru_phase(pl, kBwdB, p, H, stream)) != ASR_OK) return rc;
   }
-  if (a->db_part || a->dz_absmax) {
-    if (a->dz_absmax) ASR_CHECK_HIP(hipMemsetAsync(a->dz_absmax, 0, sizeof(float), stream));
-    hipLaunchKernelGGL(gru_dbias_kernel, dim3((3 * H + 15) / 16, a->n_pad / 16, 2), dim3(kThreads),
-                       0, stream, a->da, a->db_part, reinterpret_cast<unsigned*>(a->dz_absmax), T,
-                       a->n_pad, H);
-    ASR_CHECK_LAUNCH();
-  }
+  if (a->db_part || a->dz_absmax)
+    return rec_dbias(a->da, a->db_part, a->dz_absmax, T, a->n_pad, 1, 3 * H, stream);
   return ASR_OK;
 }
 

@@ -15,25 +15,21 @@
 // and from it the da of the level below (the previous frame's level L-1 when l = 0: that is where
 // dy enters).  There is no persistent form (asr_rhn_args.mode 2 is an argument error).
 //
-// Geometry, as gru.hip: a workgroup (256 threads) owns NR batch rows x J tile columns of one
-// direction, NR * J = 1024, NR = 64 / 32 / 16 (the largest that divides n_pad); 256-deep chunks,
-// the operand staged row-wise in LDS (rows padded by 4 floats), a 4 x 4 register tile per lane,
-// four reduction indices per pass, the next chunk in flight, a fixed-order cross-wave sum.
-// New here: the forward epilogue needs a_h, a_t (and a_c) of the SAME column, so the J tile
+// Geometry and reduction: RecTile of rec_tile.h (NR batch rows x J tile columns per workgroup,
+// chunked operand in LDS, 4 x 4 register tiles, fixed-order cross-wave sum).
+// Its own: the forward epilogue needs a_h, a_t (and a_c) of the SAME column, so the J tile
 // columns are G groups of JB = J / G neighbouring columns, group g taken from block g of U_l:
 // G = 2 when coupled; G = 4 with the fourth group idle when not (J is no multiple of 3).  The
 // forward pass reads a copy of U made once per call in the workspace, in which the C JB columns
 // of a tile lie side by side (a row of a tile is then one 48 / 64-byte piece instead of C pieces
 // Hp floats apart; measured faster than index arithmetic into U itself).  BPTT
 // reduces da^l (C H long) against U_l^T (copied once per call as well) with J plain columns.
-// Products are exact fp32 FMAs.  The slopes of BPTT are read from the SAVED gates (hs' = 0.2 on
-// 0 < gate < 1, else 0; act' from hh alone).  No float atomics: repeats are bit-identical.
-#include "lstm_common.h"
+// The slopes of BPTT are read from the SAVED gates (hs' = 0.2 on 0 < gate < 1, else 0; act' from
+// hh alone).
+#include "rec_tile.h"
 
 namespace {
 
-constexpr int kKc = 256;                   // reduction chunk
-constexpr int kActClipped = 7;
 enum { kFwd = 0, kBwd = 1 };
 
 struct RhnParams {
@@ -56,37 +52,16 @@ struct RhnParams {
   float* gbuf;             // BPTT workspace (n_pad, 2, Hp): gradient of the state last formed
 };
 
-__device__ __forceinline__ float rhn_act(int id, float clip, float z) {
-  if (id == kActClipped) return fminf(fmaxf(z, 0.f), clip);
-  return asr_act_apply(id, z);
-}
-__device__ __forceinline__ float rhn_slope(int id, float clip, float h) {
-  if (id == kActClipped) return (h > 0.f && h < clip) ? 1.f : 0.f;
-  return asr_act_slope(id, h);
-}
-__device__ __forceinline__ float hs(float a) { return fminf(fmaxf(0.2f * a + 0.5f, 0.f), 1.f); }
-__device__ __forceinline__ float hs_slope(float g) { return (g > 0.f && g < 1.f) ? 0.2f : 0.f; }
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 mul4(float4 a, float4 b) {
-  return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) {
-  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-}
-
 // da of one level from the gradient g of the state it wrote, its saved gates and the state sp it
 // read; written to the C blocks at `o` (block stride Hp)
 template <int C>
 __device__ __forceinline__ void rhn_da(const RhnParams& p, float* o, float4 g, float4 sp) {
   const int Hp = p.Hp;
   const float4 hh = ld4(p.gates + (o - p.da)), tg = ld4(p.gates + (o - p.da) + Hp);
-  st4(o, make_float4(g.x * tg.x * rhn_slope(p.act, p.clip, hh.x),
-                     g.y * tg.y * rhn_slope(p.act, p.clip, hh.y),
-                     g.z * tg.z * rhn_slope(p.act, p.clip, hh.z),
-                     g.w * tg.w * rhn_slope(p.act, p.clip, hh.w)));
+  st4(o, make_float4(g.x * tg.x * rec_slope(p.act, p.clip, hh.x),
+                     g.y * tg.y * rec_slope(p.act, p.clip, hh.y),
+                     g.z * tg.z * rec_slope(p.act, p.clip, hh.z),
+                     g.w * tg.w * rec_slope(p.act, p.clip, hh.w)));
   if (C == 2) {
     st4(o + Hp, make_float4(g.x * (hh.x - sp.x) * hs_slope(tg.x), g.y * (hh.y - sp.y) * hs_slope(tg.y),
                             g.z * (hh.z - sp.z) * hs_slope(tg.z), g.w * (hh.w - sp.w) * hs_slope(tg.w)));
@@ -102,19 +77,13 @@ __device__ __forceinline__ void rhn_da(const RhnParams& p, float* o, float4 g, f
 template <int NR, int PH, int C>
 __global__ void __launch_bounds__(kThreads)
 rhn_step_kernel(RhnParams p) {
-  constexpr int J = 1024 / NR;
+  using Tile = RecTile<NR>;
+  constexpr int J = Tile::J;
   constexpr int G = PH == kFwd ? (C == 2 ? 2 : 4) : 1;     // column groups of the tile
   constexpr int JB = J / G;                                // neighbouring columns per group
-  constexpr int KP = kKc + 4;              // padded LDS row of the operand (bank spread)
-  constexpr int NQ = NR / 4;
-  constexpr int OPV = NR * kKc / 4 / kThreads;
-  constexpr int UV = kKc * J / 4 / kThreads;
-  __shared__ __attribute__((aligned(16))) float lds[NR * KP + kKc * J];
-  float* opS = lds;                        // [NR][KP]: row n, reduction index minor
-  float* Us = lds + NR * KP;               // [kKc][J]
-  float* red = lds;                        // [4][NR][J] after the last chunk (aliases opS)
+  __shared__ __attribute__((aligned(16))) float lds[Tile::kLdsFloats];
 
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const int jb = blockIdx.x, nt = blockIdx.y, d = blockIdx.z;
   const int Hp = p.Hp, n_pad = p.n_pad, T = p.T, L = p.L, s = p.s, l = p.l;
   const int j0 = jb * JB, n0 = nt * NR;
@@ -145,100 +114,30 @@ rhn_step_kernel(RhnParams p) {
     op = p.da + (row0 * 2 + d) * W; op_ld = 2 * (size_t)W;
     mat = p.U + ((size_t)d * L + l) * W * Hp; K = W;
   }
-  const int nchunks = (K + kKc - 1) / kKc;
 
   // epilogue ownership: row en, columns ej .. ej + 3 of a group (forward: NR * JB / 4 threads)
   const int en = (4 * tid) / JB, ej = (4 * tid) % JB;
   const int jg = j0 + ej;
   const bool eown = en < NR && jg < Hp;
-  // compute ownership: rows nq + NQ i, tile columns 4 jq .. +3, reduction quarter w
-  const int nq = lane % NQ, jq = lane / NQ;
 
-  float acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-
-  if (!skip) {
-    float4 cop[OPV], cu[UV];
-    auto load = [&](int c) {
-      const int kc = c * kKc;
-#pragma unroll
-      for (int i = 0; i < OPV; ++i) {
-        // a wave reads one row's whole chunk (1 KB, contiguous)
-        const int idx = tid + i * kThreads;
-        const int n = idx / (kKc / 4), k = kc + 4 * (idx % (kKc / 4));
-        cop[i] = k < K ? ld4(op + (size_t)n * op_ld + k) : zero4();
-      }
-#pragma unroll
-      for (int i = 0; i < UV; ++i) {
-        const int idx = tid + i * kThreads;
-        const int jj = 4 * (idx % (J / 4)), k = kc + idx / (J / 4);
-        // tile column jj = group g, column jc of it: block g of U_l, column j0 + jc (forward:
-        // at jb C JB + g JB + jc of the interleaved copy)
-        const int g = jj / JB, jc = jj % JB;
-        const int col = PH == kFwd ? jb * (C * JB) + g * JB + jc : j0 + jc;
-        cu[i] = (k < K && g < C && j0 + jc < Hp) ? ld4(mat + (size_t)k * ldm + col) : zero4();
-      }
-    };
-    load(0);
-    for (int c = 0; c < nchunks; ++c) {
-      __syncthreads();                                 // previous chunk fully consumed
-      const int kc = c * kKc;
-#pragma unroll
-      for (int i = 0; i < OPV; ++i) {
-        const int idx = tid + i * kThreads;
-        const int n = idx / (kKc / 4), kl = 4 * (idx % (kKc / 4));
-        float4 v = cop[i];
-        if (PH == kFwd && mu != nullptr && kc + kl < K)       // m = s (.) B_U[l]
-          v = mul4(v, ld4(mu + (size_t)n * Hp + kc + kl));
-        st4(opS + n * KP + kl, v);
-      }
-#pragma unroll
-      for (int i = 0; i < UV; ++i) {
-        const int idx = tid + i * kThreads;
-        const int jj = 4 * (idx % (J / 4)), kl = idx / (J / 4);
-        st4(Us + kl * J + jj, cu[i]);
-      }
-      __syncthreads();
-      if (c + 1 < nchunks) load(c + 1);                // in flight while this chunk reduces
-      const int kw = w * (kKc / 4);
-#pragma unroll 2
-      for (int kk = 0; kk < kKc / 4; kk += 4) {
-        float av[4][4], bv[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float4 a = ld4(opS + (nq + NQ * i) * KP + kw + kk);
-          av[i][0] = a.x; av[i][1] = a.y; av[i][2] = a.z; av[i][3] = a.w;
-          const float4 b = ld4(Us + (kw + kk + i) * J + 4 * jq);
-          bv[i][0] = b.x; bv[i][1] = b.y; bv[i][2] = b.z; bv[i][3] = b.w;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(av[i][q], bv[q][j], acc[i][j]);
-      }
-    }
-  }
   float4 r[PH == kFwd ? C : 1];
 #pragma unroll
   for (int g = 0; g < (PH == kFwd ? C : 1); ++g) r[g] = zero4();
   if (!skip) {
-    // cross-wave sum of the four reduction quarters (fixed order)
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      st4(red + (w * NR + nq + NQ * i) * J + 4 * jq,
-          make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]));
-    __syncthreads();
+    float acc[4][4];
+    // tile column jj = group g, column jc of it: block g of U_l, column j0 + jc (forward: at
+    // jb C JB + g JB + jc of the interleaved copy)
+    auto ucol = [&](int jj) {
+      const int g = jj / JB, jc = jj % JB;
+      if (g >= C || j0 + jc >= Hp) return -1;
+      return PH == kFwd ? jb * (C * JB) + g * JB + jc : j0 + jc;
+    };
+    // forward: m = s (.) B_U[l]
+    Tile::template reduce<PH == kFwd>(lds, op, op_ld, K, mat, ldm, mu, Hp, ucol, acc);
+    Tile::spill(lds, acc);
     if (en < NR) {
 #pragma unroll
-      for (int g = 0; g < (PH == kFwd ? C : 1); ++g)
-#pragma unroll
-        for (int ww = 0; ww < 4; ++ww) r[g] = add4(r[g], ld4(red + (ww * NR + en) * J + g * JB + ej));
+      for (int g = 0; g < (PH == kFwd ? C : 1); ++g) r[g] = Tile::total(lds, en, g * JB + ej);
     }
   }
   if (!eown) return;
@@ -255,12 +154,14 @@ rhn_step_kernel(RhnParams p) {
       if (l == 0) a[g] = add4(a[g], ld4(zx + g * Hp));
     }
     const float4 sp = skip ? zero4() : ld4(p.h + ((rowr0 + en) * 2 + d) * Hp + jg);
-    const float4 hh = make_float4(rhn_act(p.act, p.clip, a[0].x), rhn_act(p.act, p.clip, a[0].y),
-                                  rhn_act(p.act, p.clip, a[0].z), rhn_act(p.act, p.clip, a[0].w));
-    const float4 tg = make_float4(hs(a[1].x), hs(a[1].y), hs(a[1].z), hs(a[1].w));
+    const float4 hh = make_float4(rec_act(p.act, p.clip, a[0].x), rec_act(p.act, p.clip, a[0].y),
+                                  rec_act(p.act, p.clip, a[0].z), rec_act(p.act, p.clip, a[0].w));
+    const float4 tg = make_float4(hard_sigmoid(a[1].x), hard_sigmoid(a[1].y),
+                                  hard_sigmoid(a[1].z), hard_sigmoid(a[1].w));
     float4 cg;
     if (C == 2) cg = make_float4(1.f - tg.x, 1.f - tg.y, 1.f - tg.z, 1.f - tg.w);
-    else cg = make_float4(hs(a[C - 1].x), hs(a[C - 1].y), hs(a[C - 1].z), hs(a[C - 1].w));
+    else cg = make_float4(hard_sigmoid(a[C - 1].x), hard_sigmoid(a[C - 1].y),
+                          hard_sigmoid(a[C - 1].z), hard_sigmoid(a[C - 1].w));
     st4(p.gates + og, hh);
     st4(p.gates + og + Hp, tg);
     if (C == 3) st4(p.gates + og + 2 * Hp, cg);
@@ -319,68 +220,6 @@ __global__ void rhn_interleave_kernel(const float* __restrict__ U, float* __rest
   }
 }
 
-// U (Z, R, Cc) -> U^T (Z, Cc, R), Z = blockIdx.z
-__global__ void rhn_transpose_kernel(const float* __restrict__ U, float* __restrict__ Ut, int R,
-                                     int Cc) {
-  __shared__ float tile[32][33];
-  const float* src = U + (size_t)blockIdx.z * R * Cc;
-  float* dst = Ut + (size_t)blockIdx.z * R * Cc;
-  const int bx = blockIdx.x * 32, by = blockIdx.y * 32;
-  for (int i = threadIdx.y; i < 32; i += 8) {
-    const int r = by + i, c = bx + threadIdx.x;
-    if (r < R && c < Cc) tile[i][threadIdx.x] = src[(size_t)r * Cc + c];
-  }
-  __syncthreads();
-  for (int i = threadIdx.y; i < 32; i += 8) {
-    const int r = bx + i, c = by + threadIdx.x;
-    if (r < Cc && c < R) dst[(size_t)r * R + c] = tile[threadIdx.x][i];
-  }
-}
-
-// y_sum (T, n_pad, Hp) = h[:, :, 0] + h[:, :, 1] (merge_mode='sum')
-__global__ void rhn_sum_kernel(const float4* __restrict__ h, float4* __restrict__ y, long long rows,
-                               int hq) {
-  const long long n = rows * hq;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x) {
-    const long long r = i / hq, q = i % hq;
-    const float4 a = h[(r * 2) * hq + q], b = h[(r * 2 + 1) * hq + q];
-    y[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-  }
-}
-
-// db_part (n_pad / 16, 2, L, W): sums of da over the 16 rows of a batch tile and all frames of a
-// level, in a fixed order (16 columns x 16 interleaved slices per workgroup, the slices added in
-// sequence); max |da| beside it.  blockIdx.z = d * L + l.
-__global__ void __launch_bounds__(kThreads)
-rhn_dbias_kernel(const float* __restrict__ da, float* __restrict__ db_part, unsigned* dz_absmax,
-                 int T, int n_pad, int L, int W) {
-  __shared__ float part[16][17];
-  const int cl = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const int c = blockIdx.x * 16 + cl;
-  const int tile = blockIdx.y, d = blockIdx.z / L, l = blockIdx.z % L;
-  float sum = 0.f, mx = 0.f;
-  if (c < W) {
-    for (int i = sl; i < T * 16; i += 16) {
-      const int t = i >> 4, n = tile * 16 + (i & 15);
-      const float v = da[((((size_t)l * T + t) * n_pad + n) * 2 + d) * W + c];
-      sum += v;
-      mx = fmaxf(mx, fabsf(v));
-    }
-  }
-  part[sl][cl] = sum;
-  __syncthreads();
-  if (sl == 0 && c < W && db_part != nullptr) {
-    float tot = 0.f;
-    for (int k = 0; k < 16; ++k) tot += part[k][cl];
-    db_part[(((size_t)tile * 2 + d) * L + l) * W + c] = tot;
-  }
-  if (dz_absmax != nullptr) {
-    mx = asr_wave_max(mx);
-    if ((threadIdx.x & 63) == 0) atomicMax(dz_absmax, __float_as_uint(mx));
-  }
-}
-
 // ---- host side -------------------------------------------------------------------------------
 struct RhnPlan {
   int NR, J, JB, NBT, C, blocks;
@@ -388,22 +227,13 @@ struct RhnPlan {
   size_t ui_floats;
 };
 
-bool act_ok(int id) { return id == 0 || id == 1 || id == 4 || id == kActClipped; }
-
 int make_rhn_plan(const asr_rhn_args* a, bool bwd, RhnPlan* pl) {
-  ASR_CHECK_ARG(a != nullptr, "rhn: null arguments");
-  ASR_CHECK_ARG(a->T >= 1 && a->n_pad >= 16 && a->n_pad % 16 == 0 && a->H >= 4 && a->H % 4 == 0,
-                "rhn: T >= 1, n_pad a multiple of 16, H a positive multiple of 4 (T=%d n_pad=%d H=%d)",
-                a->T, a->n_pad, a->H);
+  const int rc = rec_check_args("rhn", a, false);
+  if (rc != ASR_OK) return rc;
   ASR_CHECK_ARG(a->depth >= 1, "rhn: depth %d < 1", a->depth);
   ASR_CHECK_ARG(a->coupling == 0 || a->coupling == 1, "rhn: coupling %d (0 or 1)", a->coupling);
-  ASR_CHECK_ARG(a->mode == 0 || a->mode == 1, "rhn: mode %d: only the stepwise form exists "
-                "(0 = the plan's form, 1 = stepwise)", a->mode);
-  ASR_CHECK_ARG(act_ok(a->activation), "rhn: activation id %d (tanh 0, relu 1, linear 4, "
-                "clipped relu 7)", a->activation);
-  ASR_CHECK_ARG(a->activation != kActClipped || a->clip > 0.f, "rhn: clipped relu needs clip > 0");
   pl->C = a->coupling ? 2 : 3;
-  pl->NR = a->n_pad % 64 == 0 ? 64 : (a->n_pad % 32 == 0 ? 32 : 16);
+  pl->NR = rec_rows(a->n_pad);
   pl->J = 1024 / pl->NR;
   pl->JB = bwd ? pl->J : pl->J / (a->coupling ? 2 : 4);
   pl->NBT = a->n_pad / pl->NR;
@@ -428,9 +258,9 @@ int rhn_launch(bool bwd, const RhnParams& p, int jb, int nbt, hipStream_t stream
 
 template <int C>
 int rhn_step_c(const RhnPlan& pl, bool bwd, const RhnParams& p, hipStream_t stream) {
-  return pl.NR == 64 ? rhn_launch<64, C>(bwd, p, pl.JB, pl.NBT, stream)
-       : pl.NR == 32 ? rhn_launch<32, C>(bwd, p, pl.JB, pl.NBT, stream)
-                     : rhn_launch<16, C>(bwd, p, pl.JB, pl.NBT, stream);
+  return rec_with_rows(pl.NR, [&](auto nr) {
+    return rhn_launch<decltype(nr)::value, C>(bwd, p, pl.JB, pl.NBT, stream);
+  });
 }
 
 int rhn_step(const RhnPlan& pl, bool bwd, const RhnParams& p, hipStream_t stream) {
@@ -472,19 +302,12 @@ int rhn_run(const asr_rhn_args* a, bool bwd, void* workspace, size_t ws_bytes, h
       }
     if (a->y_sum) {
       const long long rows = (long long)T * a->n_pad;
-      const long long n4 = rows * (H / 4);
-      const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-      hipLaunchKernelGGL(rhn_sum_kernel, dim3(blocks), dim3(256), 0, stream,
-                         reinterpret_cast<const float4*>(a->h + (size_t)(L - 1) * rows * 2 * H),
-                         reinterpret_cast<float4*>(a->y_sum), rows, H / 4);
-      ASR_CHECK_LAUNCH();
+      return rec_sum(a->h + (size_t)(L - 1) * rows * 2 * H, a->y_sum, rows, H, stream);
     }
     return ASR_OK;
   }
   float* Ut = reinterpret_cast<float*>(ws + 256);
-  hipLaunchKernelGGL(rhn_transpose_kernel, dim3((W + 31) / 32, (H + 31) / 32, 2 * L), dim3(32, 8),
-                     0, stream, a->U, Ut, H, W);
-  ASR_CHECK_LAUNCH();
+  if ((rc = rec_transpose(a->U, Ut, 2 * L, H, W, stream)) != ASR_OK) return rc;
   p.U = Ut;
   // every launch also forms the da of the level below: s = T is the prologue (nothing above)
   p.s = T; p.l = 0;
@@ -495,13 +318,8 @@ int rhn_run(const asr_rhn_args* a, bool bwd, void* workspace, size_t ws_bytes, h
       p.s = s; p.l = l;
       if ((rc = rhn_step(pl, true, p, stream)) != ASR_OK) return rc;
     }
-  if (a->db_part || a->dz_absmax) {
-    if (a->dz_absmax) ASR_CHECK_HIP(hipMemsetAsync(a->dz_absmax, 0, sizeof(float), stream));
-    hipLaunchKernelGGL(rhn_dbias_kernel, dim3((W + 15) / 16, a->n_pad / 16, 2 * L), dim3(kThreads),
-                       0, stream, a->da, a->db_part, reinterpret_cast<unsigned*>(a->dz_absmax), T,
-                       a->n_pad, L, W);
-    ASR_CHECK_LAUNCH();
-  }
+  if (a->db_part || a->dz_absmax)
+    return rec_dbias(a->da, a->db_part, a->dz_absmax, T, a->n_pad, L, W, stream);
   return ASR_OK;
 }
 

@@ -25,12 +25,12 @@
 // Activation ids (asr_rnn_args.activation): 0 tanh, 1 relu, 4 linear (asr_act_apply), 7 clipped
 // ReLU min(max(z, 0), clip).  The BPTT derivative is taken from h alone; the clipped ReLU's is 1 on
 // 0 < h < clip and 0 elsewhere (csrc/conv.hip's convention: the two end points count as clipped).
-#include "lstm_common.h"
+//
+// rec_tile.h gives the activation pair, the U transpose, the direction sum and the argument checks.
+// The reduction is not RecTile's: it stages the operand transposed and polls a tagged exchange.
+#include "rec_tile.h"
 
 namespace {
-
-constexpr int kKc = 256;                   // reduction chunk
-constexpr int kActClipped = 7;
 
 struct RnnParams {
   int T, n_pad, Hp, NBT, P;
@@ -51,15 +51,6 @@ struct RnnParams {
   unsigned* xbuf;          // persistent: [2 * NBT chains][2 slots][NR][Hp] tagged words
   int* status;
 };
-
-__device__ __forceinline__ float rnn_act(int id, float clip, float z) {
-  if (id == kActClipped) return fminf(fmaxf(z, 0.f), clip);
-  return asr_act_apply(id, z);
-}
-__device__ __forceinline__ float rnn_slope(int id, float clip, float h) {
-  if (id == kActClipped) return (h > 0.f && h < clip) ? 1.f : 0.f;
-  return asr_act_slope(id, h);
-}
 
 // One operand chunk (NR rows x kKc reduction columns) and one U chunk (kKc x J), as float4
 // registers of this thread: OPV + UV of them.
@@ -243,8 +234,8 @@ rnn_seq_kernel(RnnParams p) {
       float4 out;
       if (!BWD) {
         const float4 z = *reinterpret_cast<const float4*>(p.zx + o);
-        out = make_float4(rnn_act(p.act, p.clip, z.x + r.x), rnn_act(p.act, p.clip, z.y + r.y),
-                          rnn_act(p.act, p.clip, z.z + r.z), rnn_act(p.act, p.clip, z.w + r.w));
+        out = make_float4(rec_act(p.act, p.clip, z.x + r.x), rec_act(p.act, p.clip, z.y + r.y),
+                          rec_act(p.act, p.clip, z.z + r.z), rec_act(p.act, p.clip, z.w + r.w));
         *reinterpret_cast<float4*>(p.h + o) = out;
       } else {
         if (mu != nullptr) {                             // d h_{t-1} = (dz @ U^T) (.) B_U
@@ -254,10 +245,10 @@ rnn_seq_kernel(RnnParams p) {
         const float4 g = *reinterpret_cast<const float4*>(p.dy + row * p.dy_ld +
                                                           (size_t)d * p.dy_dstride + jg);
         const float4 hv = *reinterpret_cast<const float4*>(p.h + o);
-        out = make_float4((g.x + r.x) * rnn_slope(p.act, p.clip, hv.x),
-                          (g.y + r.y) * rnn_slope(p.act, p.clip, hv.y),
-                          (g.z + r.z) * rnn_slope(p.act, p.clip, hv.z),
-                          (g.w + r.w) * rnn_slope(p.act, p.clip, hv.w));
+        out = make_float4((g.x + r.x) * rec_slope(p.act, p.clip, hv.x),
+                          (g.y + r.y) * rec_slope(p.act, p.clip, hv.y),
+                          (g.z + r.z) * rec_slope(p.act, p.clip, hv.z),
+                          (g.w + r.w) * rec_slope(p.act, p.clip, hv.w));
         *reinterpret_cast<float4*>(p.dz + o) = out;
         dbs.x += out.x; dbs.y += out.y; dbs.z += out.z; dbs.w += out.w;
         zmax = fmaxf(zmax, fmaxf(fmaxf(fabsf(out.x), fabsf(out.y)), fmaxf(fabsf(out.z), fabsf(out.w))));
@@ -295,47 +286,18 @@ rnn_seq_kernel(RnnParams p) {
   }
 }
 
-__global__ void rnn_transpose_kernel(const float* __restrict__ U, float* __restrict__ Ut, int Hp) {
-  __shared__ float tile[32][33];
-  const int d = blockIdx.z;
-  const float* src = U + (size_t)d * Hp * Hp;
-  float* dst = Ut + (size_t)d * Hp * Hp;
-  const int bx = blockIdx.x * 32, by = blockIdx.y * 32;
-  for (int i = threadIdx.y; i < 32; i += 8) {
-    const int r = by + i, c = bx + threadIdx.x;
-    if (r < Hp && c < Hp) tile[i][threadIdx.x] = src[(size_t)r * Hp + c];
-  }
-  __syncthreads();
-  for (int i = threadIdx.y; i < 32; i += 8) {
-    const int r = bx + i, c = by + threadIdx.x;
-    if (r < Hp && c < Hp) dst[(size_t)r * Hp + c] = tile[threadIdx.x][i];
-  }
-}
-
-// y_sum (T, n_pad, Hp) = h[:, :, 0] + h[:, :, 1] (merge_mode='sum')
-__global__ void rnn_sum_kernel(const float4* __restrict__ h, float4* __restrict__ y, long long rows,
-                               int hq) {
-  const long long n = rows * hq;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x) {
-    const long long r = i / hq, q = i % hq;
-    const float4 a = h[(r * 2) * hq + q], b = h[(r * 2 + 1) * hq + q];
-    y[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-  }
-}
-
 __global__ void act_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long long n,
                                int act, float clip) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (long long)gridDim.x * blockDim.x)
-    y[i] = rnn_act(act, clip, x[i]);
+    y[i] = rec_act(act, clip, x[i]);
 }
 
 __global__ void act_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                float* __restrict__ dx, long long n, int act, float clip) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (long long)gridDim.x * blockDim.x)
-    dx[i] = dy[i] * rnn_slope(act, clip, y[i]);
+    dx[i] = dy[i] * rec_slope(act, clip, y[i]);
 }
 
 // ---- host side -------------------------------------------------------------------------------
@@ -359,18 +321,10 @@ int rnn_num_cus() {
   return cus;
 }
 
-bool act_ok(int id) { return id == 0 || id == 1 || id == 4 || id == kActClipped; }
-
 int make_rnn_plan(const asr_rnn_args* a, bool bwd, RnnPlan* pl) {
-  ASR_CHECK_ARG(a != nullptr, "rnn: null arguments");
-  ASR_CHECK_ARG(a->T >= 1 && a->n_pad >= 16 && a->n_pad % 16 == 0 && a->H >= 4 && a->H % 4 == 0,
-                "rnn: T >= 1, n_pad a multiple of 16, H a positive multiple of 4 (T=%d n_pad=%d H=%d)",
-                a->T, a->n_pad, a->H);
-  ASR_CHECK_ARG(a->mode >= 0 && a->mode <= 2, "rnn: mode %d not in 0..2", a->mode);
-  ASR_CHECK_ARG(act_ok(a->activation), "rnn: activation id %d (tanh 0, relu 1, linear 4, "
-                "clipped relu 7)", a->activation);
-  ASR_CHECK_ARG(a->activation != kActClipped || a->clip > 0.f, "rnn: clipped relu needs clip > 0");
-  pl->NR = a->n_pad % 64 == 0 ? 64 : (a->n_pad % 32 == 0 ? 32 : 16);
+  const int rc = rec_check_args("rnn", a, true);
+  if (rc != ASR_OK) return rc;
+  pl->NR = rec_rows(a->n_pad);
   pl->J = 1024 / pl->NR;
   pl->P = (a->H + pl->J - 1) / pl->J;
   pl->NBT = a->n_pad / pl->NR;
@@ -399,7 +353,7 @@ void* pick_kernel(bool bwd, bool persistent) {
 
 int rnn_run(const asr_rnn_args* a, bool bwd, void* workspace, size_t ws_bytes, hipStream_t stream) {
   RnnPlan pl;
-  const int rc = make_rnn_plan(a, bwd, &pl);
+  int rc = make_rnn_plan(a, bwd, &pl);
   if (rc != ASR_OK) return rc;
   const size_t need = kHeadBytes + pl.ut_bytes + pl.x_bytes;
   ASR_CHECK_ARG(workspace != nullptr && ws_bytes >= need, "rnn: workspace %zu bytes < %zu",
@@ -425,9 +379,7 @@ int rnn_run(const asr_rnn_args* a, bool bwd, void* workspace, size_t ws_bytes, h
   if (pl.persistent) ASR_CHECK_HIP(hipMemsetAsync(p.xbuf, 0xFF, pl.x_bytes, stream));
   if (bwd) {
     float* Ut = reinterpret_cast<float*>(ws + kHeadBytes);
-    hipLaunchKernelGGL(rnn_transpose_kernel, dim3((a->H + 31) / 32, (a->H + 31) / 32, 2),
-                       dim3(32, 8), 0, stream, a->U, Ut, a->H);
-    ASR_CHECK_LAUNCH();
+    if ((rc = rec_transpose(a->U, Ut, 2, a->H, a->H, stream)) != ASR_OK) return rc;
     p.U = Ut;
     if (a->db_part)
       ASR_CHECK_HIP(hipMemsetAsync(a->db_part, 0, (size_t)(a->n_pad / 16) * 2 * a->H * sizeof(float), stream));
@@ -435,8 +387,9 @@ int rnn_run(const asr_rnn_args* a, bool bwd, void* workspace, size_t ws_bytes, h
   } else {
     p.U = a->U;
   }
-  void* k = pl.NR == 64 ? pick_kernel<64>(bwd, pl.persistent)
-          : pl.NR == 32 ? pick_kernel<32>(bwd, pl.persistent) : pick_kernel<16>(bwd, pl.persistent);
+  void* k = rec_with_rows(pl.NR, [&](auto nr) {
+    return pick_kernel<decltype(nr)::value>(bwd, pl.persistent);
+  });
   const dim3 grid(pl.P, pl.NBT, 2);
   const int per_launch = pl.persistent ? a->T : 1;
   for (int s0 = 0; s0 < a->T; s0 += per_launch) {
@@ -445,15 +398,8 @@ int rnn_run(const asr_rnn_args* a, bool bwd, void* workspace, size_t ws_bytes, h
     void* args[] = {&p};
     ASR_CHECK_HIP(hipLaunchKernel(k, grid, dim3(kThreads), args, 0, stream));
   }
-  if (!bwd && a->y_sum) {
-    const long long rows = (long long)a->T * a->n_pad;
-    const long long n4 = rows * (a->H / 4);
-    const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-    hipLaunchKernelGGL(rnn_sum_kernel, dim3(blocks), dim3(256), 0, stream,
-                       reinterpret_cast<const float4*>(a->h), reinterpret_cast<float4*>(a->y_sum),
-                       rows, a->H / 4);
-    ASR_CHECK_LAUNCH();
-  }
+  if (!bwd && a->y_sum)
+    return rec_sum(a->h, a->y_sum, (long long)a->T * a->n_pad, a->H, stream);
   return ASR_OK;
 }
 
@@ -489,7 +435,7 @@ extern "C" int asr_rnn_plan(const asr_rnn_args* a, int backward, int* persistent
 
 extern "C" int asr_activation_fwd(const float* x, float* y, int64_t n, int activation, float clip,
                                   asr_stream_t stream) {
-  ASR_CHECK_ARG(x && y && n >= 0 && act_ok(activation), "activation_fwd: bad arguments");
+  ASR_CHECK_ARG(x && y && n >= 0 && rec_act_ok(activation), "activation_fwd: bad arguments");
   if (n == 0) return ASR_OK;
   const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
   hipLaunchKernelGGL(act_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y,
@@ -500,7 +446,7 @@ extern "C" int asr_activation_fwd(const float* x, float* y, int64_t n, int activ
 
 extern "C" int asr_activation_bwd(const float* dy, const float* y, float* dx, int64_t n,
                                   int activation, float clip, asr_stream_t stream) {
-  ASR_CHECK_ARG(dy && y && dx && n >= 0 && act_ok(activation), "activation_bwd: bad arguments");
+  ASR_CHECK_ARG(dy && y && dx && n >= 0 && rec_act_ok(activation), "activation_bwd: bad arguments");
   if (n == 0) return ASR_OK;
   const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
   hipLaunchKernelGGL(act_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, y, dx,

@@ -299,32 +299,53 @@ def rnn_activation_id(act):
                                   % (act,))
 
 
-def _rnn_args(T, n_pad, H, U, act, mode, mask_u=None):
-    a = L.RnnArgs()
+def _rec_args(a, T, n_pad, H, mode, U=None, act=None, mask_u=None, **fields):
+    """The fields the args blocks of the recurrent layers share (asr_rnn_args, asr_gru_args,
+    asr_rhn_args); `fields`: tensors (or None) stored as pointers.  A plan query gives no U."""
     a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
-    a.activation, a.clip = rnn_activation_id(act)
-    a.U = U.data_ptr()
-    a.mask_u = mask_u.data_ptr() if mask_u is not None else None
+    if U is not None:
+        a.activation, a.clip = rnn_activation_id(act)
+        fields.update(U=U, mask_u=mask_u)
+    for name, t in fields.items():
+        setattr(a, name, t.data_ptr() if t is not None else None)
     return a
+
+
+def _rec_dy(a, H, shared_dy):
+    a.dy_ld, a.dy_dir_stride = (int(H), 0) if shared_dy else (2 * int(H), int(H))
+
+
+def _rec_run(kind, a, backward, ws_name, device, check=False):
+    """asr_<kind>_seq_fwd / _bwd on a workspace of the size the library asks for; returns it."""
+    lib = L.load()
+    fn = 'asr_%s_seq_%s' % (kind, 'bwd' if backward else 'fwd')
+    nbytes = getattr(lib, 'asr_%s_workspace_bytes' % kind)(C.byref(a), int(backward))
+    if nbytes == 0:
+        L.check(-1, 'asr_%s_workspace_bytes' % kind)
+    ws = WS.get(ws_name, nbytes, device)
+    L.check(getattr(lib, fn)(C.byref(a), _ptr(ws), nbytes, _stream()), fn)
+    if check:
+        L.check(lib.asr_lstm_status(_ptr(ws), _stream()),
+                'asr_%s status (%s)' % (kind, 'bwd' if backward else 'fwd'))
+    return ws
+
+
+def _rec_plan(kind, a, backward):
+    per, rows, units, blocks = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    fn = 'asr_%s_plan' % kind
+    L.check(getattr(L.load(), fn)(C.byref(a), int(bool(backward)), C.byref(per), C.byref(rows),
+                                  C.byref(units), C.byref(blocks)), fn)
+    return {'persistent': bool(per.value), 'rows': rows.value, 'units': units.value,
+            'blocks': blocks.value}
 
 
 def rnn_seq_fwd(zx, U, h, T, n_pad, H, act='tanh', mask_u=None, y_sum=None, mode=0, check=False):
     """Both directions of a SimpleRNN layer: h (T, n_pad, 2, H) from zx = x@W + b (same shape),
     U (2, H, H), optional B_U (2, n_pad, H); y_sum (T, n_pad, H) <- h_f + h_b when given.
     mode: 0 = the library's form, 1 = stepwise, 2 = persistent."""
-    lib = L.load()
     _check_f32(zx, U, h, mask_u, y_sum)
-    a = _rnn_args(T, n_pad, H, U, act, mode, mask_u)
-    a.zx, a.h = zx.data_ptr(), h.data_ptr()
-    a.y_sum = y_sum.data_ptr() if y_sum is not None else None
-    nbytes = lib.asr_rnn_workspace_bytes(C.byref(a), 0)
-    if nbytes == 0:
-        L.check(-1, 'asr_rnn_workspace_bytes')
-    ws = WS.get(RNN_WS[0], nbytes, zx.device)
-    L.check(lib.asr_rnn_seq_fwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_rnn_seq_fwd')
-    if check:
-        L.check(lib.asr_lstm_status(_ptr(ws), _stream()), 'asr_rnn status (fwd)')
-    return ws
+    a = _rec_args(L.RnnArgs(), T, n_pad, H, mode, U, act, mask_u, zx=zx, h=h, y_sum=y_sum)
+    return _rec_run('rnn', a, False, RNN_WS[0], zx.device, check)
 
 
 def rnn_seq_bwd(dy, U, h, dz, T, n_pad, H, act='tanh', mask_u=None, shared_dy=False, mode=0,
@@ -333,33 +354,17 @@ def rnn_seq_bwd(dy, U, h, dz, T, n_pad, H, act='tanh', mask_u=None, shared_dy=Fa
     gradient of the layer output: (T, n_pad, 2H) for 'concat', (T, n_pad, H) shared by both
     directions for 'sum' (shared_dy).  db_part (n_pad/16, 2, H): per-batch-tile sums of dz;
     dz_absmax (1,): max |dz|."""
-    lib = L.load()
     _check_f32(dy, U, h, dz, mask_u, db_part, dz_absmax)
-    a = _rnn_args(T, n_pad, H, U, act, mode, mask_u)
-    a.h, a.dy, a.dz = h.data_ptr(), dy.data_ptr(), dz.data_ptr()
-    a.dy_ld, a.dy_dir_stride = (int(H), 0) if shared_dy else (2 * int(H), int(H))
-    a.db_part = db_part.data_ptr() if db_part is not None else None
-    a.dz_absmax = dz_absmax.data_ptr() if dz_absmax is not None else None
-    nbytes = lib.asr_rnn_workspace_bytes(C.byref(a), 1)
-    if nbytes == 0:
-        L.check(-1, 'asr_rnn_workspace_bytes')
-    ws = WS.get(RNN_WS[1], nbytes, dy.device)
-    L.check(lib.asr_rnn_seq_bwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_rnn_seq_bwd')
-    if check:
-        L.check(lib.asr_lstm_status(_ptr(ws), _stream()), 'asr_rnn status (bwd)')
-    return ws
+    a = _rec_args(L.RnnArgs(), T, n_pad, H, mode, U, act, mask_u, h=h, dy=dy, dz=dz,
+                  db_part=db_part, dz_absmax=dz_absmax)
+    _rec_dy(a, H, shared_dy)
+    return _rec_run('rnn', a, True, RNN_WS[1], dy.device, check)
 
 
 def rnn_plan(T, n_pad, H, backward=False, mode=0):
     """{'persistent': bool, 'rows': batch rows, 'units': units per workgroup, 'blocks':
     workgroups per launch} of the form the library would run (asr_rnn_plan)."""
-    a = L.RnnArgs()
-    a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
-    per, rows, units, blocks = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    L.check(L.load().asr_rnn_plan(C.byref(a), int(bool(backward)), C.byref(per), C.byref(rows),
-                                  C.byref(units), C.byref(blocks)), 'asr_rnn_plan')
-    return {'persistent': bool(per.value), 'rows': rows.value, 'units': units.value,
-            'blocks': blocks.value}
+    return _rec_plan('rnn', _rec_args(L.RnnArgs(), T, n_pad, H, mode), backward)
 
 
 def activation_fwd(x, y, act):
@@ -384,31 +389,15 @@ def activation_bwd(dy, y, dx, act):
 GRU_WS = ('gru_fwd', 'gru_bwd')     # scratch only: the stepwise form has no status words
 
 
-def _gru_args(T, n_pad, H, U, h, gates, act, mode, mask_u=None):
-    a = L.GruArgs()
-    a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
-    a.activation, a.clip = rnn_activation_id(act)
-    a.U, a.h, a.gates = U.data_ptr(), h.data_ptr(), gates.data_ptr()
-    a.mask_u = mask_u.data_ptr() if mask_u is not None else None
-    return a
-
-
 def gru_seq_fwd(zx, U, h, gates, rm, T, n_pad, H, act='tanh', mask_u=None, y_sum=None, mode=0):
     """Both directions of a GRU layer: h (T, n_pad, 2, H), gates (T, n_pad, 2, 3H) = z | r | hh and
     rm (T, n_pad, 2, H) = r (.) h_prev (.) B_U from zx = x@W + b (T, n_pad, 2, 3H), U (2, H, 3H),
     optional B_U (2, n_pad, H); y_sum (T, n_pad, H) <- h_f + h_b when given.
     mode: 0 = the library's form, 1 = stepwise (the only form there is)."""
-    lib = L.load()
     _check_f32(zx, U, h, gates, rm, mask_u, y_sum)
-    a = _gru_args(T, n_pad, H, U, h, gates, act, mode, mask_u)
-    a.zx, a.rm = zx.data_ptr(), rm.data_ptr()
-    a.y_sum = y_sum.data_ptr() if y_sum is not None else None
-    nbytes = lib.asr_gru_workspace_bytes(C.byref(a), 0)
-    if nbytes == 0:
-        L.check(-1, 'asr_gru_workspace_bytes')
-    ws = WS.get(GRU_WS[0], nbytes, zx.device)
-    L.check(lib.asr_gru_seq_fwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_gru_seq_fwd')
-    return ws
+    a = _rec_args(L.GruArgs(), T, n_pad, H, mode, U, act, mask_u, h=h, gates=gates, zx=zx, rm=rm,
+                  y_sum=y_sum)
+    return _rec_run('gru', a, False, GRU_WS[0], zx.device)
 
 
 def gru_seq_bwd(dy, U, h, gates, da, T, n_pad, H, act='tanh', mask_u=None, shared_dy=False,
@@ -417,45 +406,27 @@ def gru_seq_bwd(dy, U, h, gates, da, T, n_pad, H, act='tanh', mask_u=None, share
     gate pre-activations.  dy is the gradient of the layer output: (T, n_pad, 2H) for 'concat',
     (T, n_pad, H) shared by both directions for 'sum' (shared_dy).  db_part (n_pad/16, 2, 3H):
     per-batch-tile sums of da; dz_absmax (1,): max |da|."""
-    lib = L.load()
     _check_f32(dy, U, h, gates, da, mask_u, db_part, dz_absmax)
-    a = _gru_args(T, n_pad, H, U, h, gates, act, mode, mask_u)
-    a.dy, a.da = dy.data_ptr(), da.data_ptr()
-    a.dy_ld, a.dy_dir_stride = (int(H), 0) if shared_dy else (2 * int(H), int(H))
-    a.db_part = db_part.data_ptr() if db_part is not None else None
-    a.dz_absmax = dz_absmax.data_ptr() if dz_absmax is not None else None
-    nbytes = lib.asr_gru_workspace_bytes(C.byref(a), 1)
-    if nbytes == 0:
-        L.check(-1, 'asr_gru_workspace_bytes')
-    ws = WS.get(GRU_WS[1], nbytes, dy.device)
-    L.check(lib.asr_gru_seq_bwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_gru_seq_bwd')
-    return ws
+    a = _rec_args(L.GruArgs(), T, n_pad, H, mode, U, act, mask_u, h=h, gates=gates, dy=dy, da=da,
+                  db_part=db_part, dz_absmax=dz_absmax)
+    _rec_dy(a, H, shared_dy)
+    return _rec_run('gru', a, True, GRU_WS[1], dy.device)
 
 
 def gru_plan(T, n_pad, H, backward=False, mode=0):
     """{'persistent': False, 'rows': batch rows, 'units': output columns per workgroup, 'blocks':
     workgroups of the widest launch of a step} (asr_gru_plan)."""
-    a = L.GruArgs()
-    a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
-    per, rows, units, blocks = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    L.check(L.load().asr_gru_plan(C.byref(a), int(bool(backward)), C.byref(per), C.byref(rows),
-                                  C.byref(units), C.byref(blocks)), 'asr_gru_plan')
-    return {'persistent': bool(per.value), 'rows': rows.value, 'units': units.value,
-            'blocks': blocks.value}
+    return _rec_plan('gru', _rec_args(L.GruArgs(), T, n_pad, H, mode), backward)
 
 
 # --------------------------------------------------------------------------- RHN (K17)
 RHN_WS = ('rhn_fwd', 'rhn_bwd')     # scratch only: the stepwise form has no status words
 
 
-def _rhn_args(T, n_pad, H, depth, coupling, U, h, gates, act, mode, mask_u=None):
+def _rhn_args(T, n_pad, H, depth, coupling, mode, *rest, **fields):
     a = L.RhnArgs()
-    a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
     a.depth, a.coupling = int(depth), int(bool(coupling))
-    a.activation, a.clip = rnn_activation_id(act)
-    a.U, a.h, a.gates = U.data_ptr(), h.data_ptr(), gates.data_ptr()
-    a.mask_u = mask_u.data_ptr() if mask_u is not None else None
-    return a
+    return _rec_args(a, T, n_pad, H, mode, *rest, **fields)
 
 
 def rhn_seq_fwd(zx, U, b, h, gates, T, n_pad, H, depth, coupling=True, act='tanh', mask_u=None,
@@ -466,17 +437,10 @@ def rhn_seq_fwd(zx, U, b, h, gates, T, n_pad, H, depth, coupling=True, act='tanh
     U (2, L, H, C H), b (2, L, C H), optional B_U (2, L, n_pad, H); y_sum (T, n_pad, H) <- the sum
     of the two directions' outputs when given.
     mode: 0 = the library's form, 1 = stepwise (the only form there is)."""
-    lib = L.load()
     _check_f32(zx, U, b, h, gates, mask_u, y_sum)
-    a = _rhn_args(T, n_pad, H, depth, coupling, U, h, gates, act, mode, mask_u)
-    a.zx, a.b = zx.data_ptr(), b.data_ptr()
-    a.y_sum = y_sum.data_ptr() if y_sum is not None else None
-    nbytes = lib.asr_rhn_workspace_bytes(C.byref(a), 0)
-    if nbytes == 0:
-        L.check(-1, 'asr_rhn_workspace_bytes')
-    ws = WS.get(RHN_WS[0], nbytes, zx.device)
-    L.check(lib.asr_rhn_seq_fwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_rhn_seq_fwd')
-    return ws
+    a = _rhn_args(T, n_pad, H, depth, coupling, mode, U, act, mask_u, h=h, gates=gates, zx=zx,
+                  b=b, y_sum=y_sum)
+    return _rec_run('rhn', a, False, RHN_WS[0], zx.device)
 
 
 def rhn_seq_bwd(dy, U, h, gates, da, T, n_pad, H, depth, coupling=True, act='tanh', mask_u=None,
@@ -485,32 +449,17 @@ def rhn_seq_bwd(dy, U, h, gates, da, T, n_pad, H, depth, coupling=True, act='tan
     every level's pre-activations.  dy is the gradient of the layer output: (T, n_pad, 2H) for
     'concat', (T, n_pad, H) shared by both directions for 'sum' (shared_dy).  db_part
     (n_pad/16, 2, L, C H): per-batch-tile sums of da; dz_absmax (1,): max |da|."""
-    lib = L.load()
     _check_f32(dy, U, h, gates, da, mask_u, db_part, dz_absmax)
-    a = _rhn_args(T, n_pad, H, depth, coupling, U, h, gates, act, mode, mask_u)
-    a.dy, a.da = dy.data_ptr(), da.data_ptr()
-    a.dy_ld, a.dy_dir_stride = (int(H), 0) if shared_dy else (2 * int(H), int(H))
-    a.db_part = db_part.data_ptr() if db_part is not None else None
-    a.dz_absmax = dz_absmax.data_ptr() if dz_absmax is not None else None
-    nbytes = lib.asr_rhn_workspace_bytes(C.byref(a), 1)
-    if nbytes == 0:
-        L.check(-1, 'asr_rhn_workspace_bytes')
-    ws = WS.get(RHN_WS[1], nbytes, dy.device)
-    L.check(lib.asr_rhn_seq_bwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_rhn_seq_bwd')
-    return ws
+    a = _rhn_args(T, n_pad, H, depth, coupling, mode, U, act, mask_u, h=h, gates=gates, dy=dy,
+                  da=da, db_part=db_part, dz_absmax=dz_absmax)
+    _rec_dy(a, H, shared_dy)
+    return _rec_run('rhn', a, True, RHN_WS[1], dy.device)
 
 
 def rhn_plan(T, n_pad, H, depth=1, coupling=True, backward=False, mode=0):
     """{'persistent': False, 'rows': batch rows, 'units': state columns per workgroup, 'blocks':
     workgroups of a launch} (asr_rhn_plan)."""
-    a = L.RhnArgs()
-    a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
-    a.depth, a.coupling = int(depth), int(bool(coupling))
-    per, rows, units, blocks = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    L.check(L.load().asr_rhn_plan(C.byref(a), int(bool(backward)), C.byref(per), C.byref(rows),
-                                  C.byref(units), C.byref(blocks)), 'asr_rhn_plan')
-    return {'persistent': bool(per.value), 'rows': rows.value, 'units': units.value,
-            'blocks': blocks.value}
+    return _rec_plan('rhn', _rhn_args(T, n_pad, H, depth, coupling, mode), backward)
 
 
 # --------------------------------------------------------------------------- BatchNormalization

@@ -351,12 +351,14 @@ def small_batch(rs):
 # as long as there.
 KERNEL_SHAPES = [(4, 16, 1), (4, 64, 50), (36, 16, 200), (36, 64, 7), (100, 16, 50),
                  (100, 64, 200), (256, 16, 50), (256, 64, 50), (512, 16, 20), (512, 64, 20),
-                 (1024, 16, 7), (1024, 64, 7)]
+                 (1024, 16, 7), (1024, 64, 7),
+                 # NR = 32 (part-filled last column tile; two reduction chunks); n_pad = 48 -> NR = 16
+                 (36, 32, 7), (260, 32, 5), (132, 48, 3)]
 PAIRS = [(1, True), (2, True), (4, True), (1, False), (2, False), (4, False)]   # (depth, coupling)
 
 
 def case_options(i, k):
-    """Options of activation k of shape i: the six (depth, coupling) pairs cycle over the 48
+    """Options of activation k of shape i: the six (depth, coupling) pairs cycle over the 60
     cases, so that each meets a width below 64 (shapes 0-3), H = 512 (8, 9) and H = 1024 (10, 11);
     masks and the merge mode alternate.  -> depth, coupling, masked, merge"""
     depth, coupling = PAIRS[(4 * i + k) % 6]

@@ -18,7 +18,10 @@ ACTS = ['tanh', 'relu', 'linear', ('clipped_relu', 20.0)]
 # oracle stays well under a minute per case
 SHAPES = [(4, 16, 1), (4, 64, 50), (36, 16, 200), (36, 64, 7), (100, 16, 50), (100, 64, 200),
           (256, 16, 50), (256, 64, 50), (512, 16, 20), (512, 64, 20), (1024, 16, 7),
-          (1024, 64, 7)]
+          (1024, 64, 7),
+          # NR = 32 (part-filled last column tile; two reduction chunks) and n_pad = 48 -> NR = 16
+          # with BPTT phase B's K = 2 * 132 crossing a chunk edge on a part-filled tile
+          (36, 32, 7), (260, 32, 5), (132, 48, 3)]
 
 
 def _dev(a):

@@ -465,7 +465,7 @@ def test_parity_inputs_keep_their_sides_in_float32(case, masks_on):
 
 
 def test_kernel_case_options_cover_the_grid():
-    """The 48 kernel cases of the GPU suite: every (depth, coupling) pair meets a width below 64,
+    """The 60 kernel cases of the GPU suite: every (depth, coupling) pair meets a width below 64,
     H = 512 and H = 1024; masks on / off and both merge modes occur; every activation meets every
     shape (k runs over all of them for each shape)."""
     seen = {}
