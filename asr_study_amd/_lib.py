@@ -209,6 +209,14 @@ SIGNATURES = {
                                       C.c_size_t, void_p]),
     'asr_ctc_beam_device_counters': (C.c_int, [void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                C.c_int, void_p, void_p]),
+    'asr_ctc_beam_lm_host': (C.c_int, [void_p, void_p] + [C.c_int] * 6 + [void_p, C.c_int,
+                                                                           void_p, void_p, void_p]),
+    'asr_ctc_beam_lm_device_workspace_bytes': (C.c_size_t, [C.c_int] * 4),
+    'asr_ctc_beam_lm_device': (C.c_int, [void_p, void_p] + [C.c_int] * 6 +
+                               [void_p, C.c_int, void_p, void_p, void_p, void_p, C.c_size_t,
+                                void_p]),
+    'asr_ctc_beam_lm_device_counters': (C.c_int, [void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, void_p, void_p]),
     'asr_edit_distance_host': (C.c_int, [void_p, void_p, C.c_int, void_p, void_p, C.c_int,
                                          C.c_int, void_p]),
     'asr_optim_workspace_bytes': (C.c_size_t, [C.c_int64]),

@@ -22,6 +22,11 @@ _DEVICE_FLAGS = [
     ('--gpu', dict(default='0', type=str)),
     ('--allow_growth', dict(default=False, action='store_true')),
 ]
+_LM_FLAGS = [                                           # no --lm: today's beam search, exactly
+    ('--lm', dict(default=None, type=str)),             # a CharLM file (extras/make_lm.py)
+    ('--lm_alpha', dict(default=1.0, type=float)),      # weight of log P(label | context)
+    ('--lm_beta', dict(default=0.0, type=float)),       # bonus per label
+]
 TRAIN_FLAGS = [
     ('--load', dict(default=None, type=str)),
     ('--model', dict(default='brsmv1', type=str)),
@@ -49,7 +54,7 @@ EVAL_FLAGS = [
 ] + _PLUGIN_FLAGS + _DEVICE_FLAGS + [
     ('--save_transcriptions', dict(default=None, type=str)),
     ('--beam_width', dict(default=400, type=int)),      # utils/core_utils.py:70-71
-]
+] + _LM_FLAGS
 PREDICT_FLAGS = [
     ('--model', dict(required=True, type=str)),
     ('--dataset', dict(default=None, type=str)),
@@ -61,6 +66,15 @@ PREDICT_FLAGS = [
     ('--save', dict(default=None, type=str)),
     ('--override', dict(default=False, action='store_true')),
     ('--beam_width', dict(default=400, type=int)),
+] + _LM_FLAGS
+MAKE_LM_FLAGS = [
+    ('--dataset', dict(default=None, type=str)),
+    ('--subset', dict(type=str, default='train')),
+    ('--text', dict(default=None, type=str)),           # a text file, one sentence per line
+    ('--label_parser', dict(type=str, default='simple_char_parser')),
+    ('--label_parser_params', dict(nargs='+', default=[])),
+    ('--order', dict(default=3, type=int)),
+    ('--output_file', dict(type=str, default='lm.npz')),
 ]
 MAKE_DATASET_FLAGS = [
     ('--parser', dict(type=str, default='dummy')),
@@ -184,6 +198,14 @@ def train_main(argv=None):
     parallel.finalize()
 
 
+def _check_lm(model, label_parser):
+    """A --lm counted over other symbols than the label parser's is refused before decoding
+    (its label count is checked against the network's classes at the first batch)."""
+    lm = (model.decoder or {}).get('lm')
+    if lm is not None:
+        lm.check(label_parser=label_parser)
+
+
 # ------------------------------------------------------------------ eval
 def eval_main(argv=None):
     parser = make_parser('Evaluating an ASR system.', EVAL_FLAGS)
@@ -193,9 +215,11 @@ def eval_main(argv=None):
     from .datasets.dataset_generator import DatasetGenerator
     from .utils.core_utils import setup_gpu, load_model
     setup_gpu(args.gpu, args.allow_growth)
-    model, meta = load_model(args.model, return_meta=True, mode='eval', beam_width=args.beam_width)
+    model, meta = load_model(args.model, return_meta=True, mode='eval', beam_width=args.beam_width,
+                             lm=args.lm, lm_alpha=args.lm_alpha, lm_beta=args.lm_beta)
     args = merged_args(args, meta['training_args'], explicit)
     feature, labels = resolve_plugins(args)
+    _check_lm(model, labels)
     flow = DatasetGenerator(feature, labels, batch_size=args.batch_size, seed=0) \
         .flow_from_fname(args.dataset, datasets=args.subset)
     values = model.evaluate_generator(flow, flow.len, max_q_size=10, nb_worker=1)
@@ -221,7 +245,9 @@ def predict_main(argv=None):
     from .utils.core_utils import setup_gpu, load_model
     setup_gpu(args.gpu, args.allow_growth)
     model, meta = load_model(args.model, return_meta=True, mode='predict',
-                             decoder=(not args.no_decoder), beam_width=args.beam_width)
+                             decoder=(not args.no_decoder), beam_width=args.beam_width,
+                             lm=None if args.no_decoder else args.lm, lm_alpha=args.lm_alpha,
+                             lm_beta=args.lm_beta)
     # only the feature / label plugins are inherited from the training run (the reference
     # overlays every stored argument, predict.py:60, which would also import its --save)
     stored = {k: v for k, v in meta['training_args'].items()
@@ -229,6 +255,7 @@ def predict_main(argv=None):
                        'label_parser_params')}
     args = merged_args(args, stored, explicit)
     feature, labels = resolve_plugins(args)
+    _check_lm(model, labels)
     if args.dataset is not None:
         flow = DatasetGenerator(feature, labels, batch_size=1, seed=0, mode='predict',
                                 shuffle=False).flow_from_fname(args.dataset, datasets=args.subset)
@@ -274,3 +301,38 @@ def make_dataset_main(argv=None):
                        override=args.override, fmt=fmt)
     print('dataset written to', out)
     return out
+
+
+# ------------------------------------------------------------------ make_lm
+def make_lm_main(argv=None):
+    """extras/make_lm.py: count the label sequences the label parser yields for one split of a
+    dataset and / or the lines of a text file, estimate a character n-gram model
+    (asr_study_amd.lm.CharLM: interpolated Witten-Bell) and write it for eval.py / predict.py
+    ``--lm``."""
+    parser = make_parser('Estimates a character n-gram language model (npz file).', MAKE_LM_FLAGS)
+    args = parser.parse_args(argv)
+    if args.dataset is None and args.text is None:
+        raise ValueError('dataset or text args must be set.')
+    from .lm import CharLM, parser_vocab
+    labels = utils.get_from_module('preprocessing.text', args.label_parser,
+                                   params=args.label_parser_params)
+    sentences = []
+    if args.dataset is not None:
+        from .datasets.dataset_generator import DatasetGenerator
+        flow = DatasetGenerator(None, labels, batch_size=1, shuffle=False) \
+            .flow_from_fname(args.dataset, datasets=args.subset)
+        sentences += [t.decode('utf-8') if isinstance(t, bytes) else str(t)
+                      for t in flow.labels[list(range(flow.len))]]
+    if args.text is not None:
+        import io
+        with io.open(args.text, encoding='utf-8') as f:
+            sentences += [line.strip() for line in f if line.strip()]
+    symbols = parser_vocab(labels)
+    num_labels = len(symbols) if symbols is not None else None
+    if num_labels is None:
+        raise ValueError('the label parser %s has no symbol table' % args.label_parser)
+    model = CharLM.estimate([labels(t) for t in sentences], num_labels, args.order, vocab=symbols)
+    model.save(args.output_file)
+    print('order-%d language model over %d labels from %d sentences written to %s'
+          % (model.order, model.num_labels, len(sentences), args.output_file))
+    return args.output_file

@@ -2310,14 +2310,26 @@ class Model(object):
         """core/ctc_utils.py:48-50 (K9): the library's host decoder (decode_host.cpp: one
         utterance per host thread, on a copy of the logits) or the device decoder (beam.hip: the
         logits stay in HBM) -- same strings either way; ops.beam_decoder_choice picks (host
-        while every utterance gets its own host thread, ASR_BEAM=device / host force one)."""
+        while every utterance gets its own host thread, ASR_BEAM=device / host force one).  With
+        a character LM in self.decoder (``lm``, ``lm_alpha``, ``lm_beta``) the LM forms of both."""
         width = int(self.decoder.get('beam_width', 100))
         merge = self.decoder.get('merge_repeated', True)
+        from .ctc_utils import lm_of
+        lm = lm_of(self.decoder, logits.shape[2])   # (CharLM, alpha, beta) or None
         if ops.beam_decoder_choice(N, width, logits.shape[2]) == 'device':
-            dec, dlen, _ = ops.ctc_beam_search(logits, seq_len_dev, N, width, merge)
+            if lm is None:
+                dec, dlen, _ = ops.ctc_beam_search(logits, seq_len_dev, N, width, merge)
+            else:
+                dec, dlen, _ = ops.ctc_beam_search_lm(
+                    logits, seq_len_dev, N, width, merge,
+                    lm[0].fused_device(lm[1], lm[2], logits.device), lm[0].order)
             return dec, dlen
         lens = seq_len_dev.cpu().numpy()
-        hyps, _ = ops.ctc_beam_search_host(logits.cpu().numpy(), lens, N, width, merge)
+        if lm is None:
+            hyps, _ = ops.ctc_beam_search_host(logits.cpu().numpy(), lens, N, width, merge)
+        else:
+            hyps, _ = ops.ctc_beam_search_lm_host(logits.cpu().numpy(), lens, N, width, merge,
+                                                  lm[0].fused(lm[1], lm[2]), lm[0].order)
         T = logits.shape[0]
         dec = np.full((N, T), -1, np.int32)
         for n, h in enumerate(hyps):

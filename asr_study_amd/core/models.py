@@ -24,7 +24,8 @@ def ctc_model(inputs, output, **kwargs):
     inputs_length]``, outputs ``[ctc, decoder]`` (core/models.py:31-52).
 
     kwargs: ``is_greedy`` / ``beam_width`` / ``merge_repeated`` for the decoder
-    (core/ctc_utils.py:8-52), ``device``, ``seed``.
+    (core/ctc_utils.py:8-52) and ``lm`` / ``lm_alpha`` / ``lm_beta`` for a character language
+    model in the beam search (asr_study_amd.lm), ``device``, ``seed``.
     """
     root, chain = output.chain()
     if root is not inputs:
@@ -92,7 +93,8 @@ def ctc_model(inputs, output, **kwargs):
                   seed=kwargs.get('seed', 0))
     model.decoder = ctc_utils.decoder_config(**{k: v for k, v in kwargs.items()
                                                 if k in ('is_greedy', 'beam_width',
-                                                         'merge_repeated', 'top_paths')})
+                                                         'merge_repeated', 'top_paths', 'lm',
+                                                         'lm_alpha', 'lm_beta')})
     return model
 
 

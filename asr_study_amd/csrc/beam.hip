@@ -21,6 +21,16 @@
 //    candidate is inserted, then the rest is re-evaluated (an insertion can evict a sibling
 //    that was active).  The turn loop ends at the first branch whose old total does not beat
 //    the bottom of a full beam (the branches are sorted by it).
+//
+// With a character language model (asr_ctc_beam_lm_device, the LM = true instantiations) a tree
+// entry also has the LM context of its prefix and the constant w_e = w[ctx(parent) * K + label]
+// from the fused float32 table w (n_ctx, K): w_e is added to what the parent feeds a branch's
+// label path (phase B) and to a child's first offer (phase D).  The context of the node that
+// owns a child block is stored per block (block_ctx, next to block_parent), the contexts of the
+// frame's branches in LDS (b_ctx), so phase B reads one float per branch and phase D one
+// coalesced row of K floats per turn, fetched one turn ahead.  The early exit of the turn loop
+// rests on the branches' OLD totals and a rising bottom, not on a child scoring below its
+// parent, so a positive w_e (beta > 0) changes nothing there.
 #include "common.h"
 
 #include <limits.h>
@@ -45,6 +55,8 @@ struct BeamParams {
   char* ws;
   size_t ws_per_utt;
   int max_blocks;
+  const float* w;                       // LM only: fused table (n_ctx, C - 1)
+  int n_ctx;                            // LM only: (C - 1 + 1)^(order - 1)
 };
 
 __device__ __forceinline__ double neg_inf() { return -__builtin_huge_val(); }
@@ -79,9 +91,11 @@ __device__ __forceinline__ double shl1_d(double x, double carry) {
                           shl1_i<DPP>(__double2loint(x), __double2loint(carry)));
 }
 
-size_t lds_bytes(int W) { return (size_t)W * 100 + 72 * 8 + 64 * 4 + 16 * 4; }
+size_t lds_bytes(int W, bool lm) {
+  return (size_t)W * 100 + 72 * 8 + 64 * 4 + 16 * 4 + (lm ? (size_t)W * 4 : 0);
+}
 
-template <int E, bool DPP>
+template <int E, bool DPP, bool LM>
 __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int W = p.W, C = p.C, K = p.C - 1, blank = p.C - 1;
@@ -103,6 +117,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   int* h_ord = b_evicted + W;
   int* h_tag = h_ord + W;                                // >= 0: branch turn; else -(parent + 2)
   int* s_misc = h_tag + W;                               // nb, nblocks, hn
+  int* b_ctx = s_misc + 16;                              // LM: context of the branch's prefix
 
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // head of the utterance's workspace: 100 MHz ticks spent in phases B, C, D, E, then the
@@ -111,6 +126,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   long long tk_b = 0, tk_c = 0, tk_d = 0, tk_e = 0, n_turn = 0, n_ins = 0;
   Rec* rec = reinterpret_cast<Rec*>(p.ws + (size_t)n * p.ws_per_utt + 64);
   int* block_parent = reinterpret_cast<int*>(rec + (1 + (size_t)p.max_blocks * K));
+  int* block_ctx = block_parent + p.max_blocks;          // LM: context of the block's owner
   int Tn = p.seq_len[n];
   Tn = Tn < 0 ? 0 : (Tn > p.T ? p.T : Tn);
 
@@ -121,6 +137,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
     b_evicted[0] = 0; b_kidhead[0] = -1;
     rec[0] = Rec{-1, 0};
     s_misc[0] = 1; s_misc[1] = 0; s_misc[2] = 1;
+    if (LM) b_ctx[0] = p.n_ctx - 1;                      // "before the sentence"
   }
   float xnext = (tid < C && Tn > 0) ? p.logits[(size_t)n * C + tid] : 0.f;
   __syncthreads();
@@ -149,7 +166,9 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
         pt = rec[par].turn;
         if (pt >= 0) {
           const int plabel = par == 0 ? -1 : (par - 1) % K;
-          nl = lse(nl, label == plabel ? b_ob[pt] : b_ot[pt]);
+          double prev = label == plabel ? b_ob[pt] : b_ot[pt];
+          if (LM) prev += (double)p.w[b_ctx[pt] * K + label];      // (-inf stays -inf)
+          nl = lse(nl, prev);
           b_kidnext[q] = (atomicExch(&b_kidhead[pt], q) + 1) | (label << 12);
         }
         nl += inp[label];
@@ -213,7 +232,13 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
       // while the frame runs -- a reset -- so that one is read from LDS at the turn)
       double c_ot0 = 0.0, c_ob = 0.0;
       int c_node = 0, c_child = -1, c_kid = -1, c_label = -1;
+      // LM: the row of the turn's context, read one turn ahead (a turn that ends up not
+      // expanding costs a row that is not used)
+      float w_next = 0.f;
+      if (LM) w_next = lane < K ? p.w[b_ctx[0] * K + lane] : 0.f;
       for (int r = 0; r < nb; ++r) {
+        const float w_row = w_next;
+        if (LM) w_next = lane < K ? p.w[b_ctx[r + 1 < nb ? r + 1 : r] * K + lane] : 0.f;
         if ((r & 63) == 0) {
           const int rr = r + lane < nb ? r + lane : nb - 1;
           c_ot0 = b_ot0[rr]; c_ob = b_ob[rr]; c_node = b_node[rr]; c_child = b_child[rr];
@@ -231,7 +256,10 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
         int blk = readlane_i(c_child, r & 63);
         if (blk < 0) {                                     // first expansion: a block of ids
           blk = nblk++;
-          if (lane == 0) { block_parent[blk] = node; rec[node].children = blk; }
+          if (lane == 0) {
+            block_parent[blk] = node; rec[node].children = blk;
+            if (LM) block_ctx[blk] = b_ctx[r];
+          }
           if (lane < K) rec[1 + (size_t)blk * K + lane] = Rec{-1, -1};
         }
         ++n_turn;
@@ -247,7 +275,8 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
         bool active = false;
         if (__ballot(q >= 0) != 0ull) active = q >= 0 && b_evicted[q] == 0;
         const double prev = lane == blabel ? ob : ot;
-        const double v = (lane < K && prev != neg_inf()) ? inp_c + prev : neg_inf();
+        const double v = (lane < K && prev != neg_inf())
+                             ? (LM ? inp_c + (prev + (double)w_row) : inp_c + prev) : neg_inf();
         unsigned long long undecided = (1ull << K) - 1ull;
         while (undecided) {
           theta = readlane_d(nt[0], 0);
@@ -335,7 +364,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
     // ---- phase E: the beam is the next frame's branch table, in its sorted order
     const int hn = s_misc[2];
     double e_nt[4], e_nb[4], e_nl[4];
-    int e_node[4], e_par[4];
+    int e_node[4], e_par[4], e_ctx[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int j = tid + k * kThreads;
@@ -346,6 +375,12 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
         e_par[k] = g >= 0 ? b_par[g] : -(g + 2);
         e_nb[k] = g >= 0 ? b_nb[g] : neg_inf();
         e_nl[k] = g >= 0 ? b_nl[g] : e_nt[k];
+        if (LM) {                                          // a new child: its parent's, moved on
+          const int id = e_node[k];
+          e_ctx[k] = g >= 0 ? b_ctx[g]
+                            : (int)(((long long)block_ctx[(id - 1) / K] * C + (id - 1) % K) %
+                                    p.n_ctx);
+        }
       }
     }
     for (int q = tid; q < nb; q += kThreads) rec[b_node[q]].turn = -1;
@@ -357,6 +392,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
         b_node[j] = e_node[k]; b_par[j] = e_par[k];
         b_ob[j] = e_nb[k]; b_ol[j] = e_nl[k]; b_ot[j] = e_nt[k]; b_ot0[j] = e_nt[k];
         b_evicted[j] = 0; b_kidhead[j] = -1;
+        if (LM) b_ctx[j] = e_ctx[k];
         rec[e_node[k]].turn = j;
       }
     }
@@ -395,18 +431,44 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
 
 typedef void (*beam_kern_t)(BeamParams);
 
+template <bool LM>
 beam_kern_t pick(int W) {           // (the lane shift of the sorted beam: DPP wave_shr:1)
-  if (W <= 128) return ctc_beam_kernel<2, true>;
-  if (W <= 448) return ctc_beam_kernel<7, true>;
-  return ctc_beam_kernel<16, true>;
+  if (W <= 128) return ctc_beam_kernel<2, true, LM>;
+  if (W <= 448) return ctc_beam_kernel<7, true, LM>;
+  return ctc_beam_kernel<16, true, LM>;
 }
 
-size_t ws_per_utt(int T, int C, int W, int* max_blocks) {
+size_t ws_per_utt(int T, int C, int W, int* max_blocks, bool lm = false) {
   // a node expands for the first time at most once, a frame has at most W branches
   const size_t blocks = (size_t)(T > 0 ? T : 1) * (size_t)W;
   *max_blocks = (int)blocks;
-  return asr_align_up(64 + (1 + blocks * (size_t)(C - 1)) * sizeof(Rec) + blocks * sizeof(int),
-                      256);
+  return asr_align_up(64 + (1 + blocks * (size_t)(C - 1)) * sizeof(Rec) +
+                          blocks * sizeof(int) * (lm ? 2 : 1), 256);
+}
+
+int launch(BeamParams p, int N, bool lm, size_t ws_bytes, asr_stream_t stream) {
+  p.ws_per_utt = ws_per_utt(p.T, p.C, p.W, &p.max_blocks, lm);
+  ASR_CHECK_ARG(ws_bytes >= p.ws_per_utt * (size_t)N, "beam: workspace too small");
+  beam_kern_t k = lm ? pick<true>(p.W) : pick<false>(p.W);
+  const size_t shm = lds_bytes(p.W, lm);
+  if (shm > 64 * 1024)
+    ASR_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)shm));
+  hipLaunchKernelGGL(k, dim3(N), dim3(kThreads), shm, (hipStream_t)stream, p);
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
+}
+
+int check_shape(const void* logits, const void* seq_len, const void* decoded,
+                const void* decoded_len, const void* workspace, int T, int N, int n_pad, int C,
+                int beam_width) {
+  ASR_CHECK_ARG(logits && seq_len && decoded && decoded_len && workspace, "beam: null pointer");
+  ASR_CHECK_ARG(T > 0 && N > 0 && n_pad >= N && C >= 2, "beam: bad shape");
+  ASR_CHECK_ARG(C <= kMaxC, "beam: at most %d classes", kMaxC);
+  ASR_CHECK_ARG(beam_width >= 1 && beam_width <= 1024, "beam: width must be 1 .. 1024");
+  ASR_CHECK_ARG((size_t)T * (size_t)beam_width * (size_t)(C - 1) < (size_t)INT_MAX,
+                "beam: T * width * labels overflows the node ids");
+  return ASR_OK;
 }
 
 }  // namespace
@@ -417,42 +479,74 @@ extern "C" size_t asr_ctc_beam_device_workspace_bytes(int T, int N, int C, int b
   return ws_per_utt(T, C, beam_width, &mb) * (size_t)N;
 }
 
-extern "C" int asr_ctc_beam_device_counters(const void* workspace, int T, int N, int C,
-                                            int beam_width, int utterance, long long* out7,
-                                            asr_stream_t stream) {
+namespace {
+int read_counters(const void* workspace, int T, int N, int C, int beam_width, int utterance,
+                  long long* out7, bool lm, asr_stream_t stream) {
   ASR_CHECK_ARG(workspace && out7 && utterance >= 0 && utterance < N, "beam counters: bad args");
   int mb;
-  const size_t per = ws_per_utt(T, C, beam_width, &mb);
+  const size_t per = ws_per_utt(T, C, beam_width, &mb, lm);
   ASR_CHECK_HIP(hipMemcpyAsync(out7, reinterpret_cast<const char*>(workspace) + per * utterance,
                                7 * sizeof(long long), hipMemcpyDeviceToHost,
                                (hipStream_t)stream));
   ASR_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
   return ASR_OK;
 }
+}  // namespace
+
+extern "C" int asr_ctc_beam_device_counters(const void* workspace, int T, int N, int C,
+                                            int beam_width, int utterance, long long* out7,
+                                            asr_stream_t stream) {
+  return read_counters(workspace, T, N, C, beam_width, utterance, out7, false, stream);
+}
+
+extern "C" int asr_ctc_beam_lm_device_counters(const void* workspace, int T, int N, int C,
+                                               int beam_width, int utterance, long long* out7,
+                                               asr_stream_t stream) {
+  return read_counters(workspace, T, N, C, beam_width, utterance, out7, true, stream);
+}
 
 extern "C" int asr_ctc_beam_device(const float* logits, const int* seq_len, int T, int N, int n_pad,
                                    int C, int beam_width, int merge_repeated, int* decoded,
                                    int* decoded_len, float* log_score, void* workspace,
                                    size_t ws_bytes, asr_stream_t stream) {
-  ASR_CHECK_ARG(logits && seq_len && decoded && decoded_len && workspace, "beam: null pointer");
-  ASR_CHECK_ARG(T > 0 && N > 0 && n_pad >= N && C >= 2, "beam: bad shape");
-  ASR_CHECK_ARG(C <= kMaxC, "beam: at most %d classes", kMaxC);
-  ASR_CHECK_ARG(beam_width >= 1 && beam_width <= 1024, "beam: width must be 1 .. 1024");
-  ASR_CHECK_ARG((size_t)T * (size_t)beam_width * (size_t)(C - 1) < (size_t)INT_MAX,
-                "beam: T * width * labels overflows the node ids");
+  const int rc = check_shape(logits, seq_len, decoded, decoded_len, workspace, T, N, n_pad, C,
+                             beam_width);
+  if (rc != ASR_OK) return rc;
   BeamParams p;
   p.logits = logits; p.seq_len = seq_len; p.T = T; p.n_pad = n_pad; p.C = C; p.W = beam_width;
   p.merge = merge_repeated ? 1 : 0;
   p.decoded = decoded; p.decoded_len = decoded_len; p.score = log_score;
   p.ws = reinterpret_cast<char*>(workspace);
-  p.ws_per_utt = ws_per_utt(T, C, beam_width, &p.max_blocks);
-  ASR_CHECK_ARG(ws_bytes >= p.ws_per_utt * (size_t)N, "beam: workspace too small");
-  beam_kern_t k = pick(beam_width);
-  const size_t shm = lds_bytes(beam_width);
-  if (shm > 64 * 1024)
-    ASR_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)shm));
-  hipLaunchKernelGGL(k, dim3(N), dim3(kThreads), shm, (hipStream_t)stream, p);
-  ASR_CHECK_LAUNCH();
-  return ASR_OK;
+  p.w = nullptr; p.n_ctx = 1;
+  return launch(p, N, false, ws_bytes, stream);
+}
+
+extern "C" size_t asr_ctc_beam_lm_device_workspace_bytes(int T, int N, int C, int beam_width) {
+  if (T < 0 || N <= 0 || C < 2 || beam_width < 1) return 0;
+  int mb;
+  return ws_per_utt(T, C, beam_width, &mb, true) * (size_t)N;
+}
+
+extern "C" int asr_ctc_beam_lm_device(const float* logits, const int* seq_len, int T, int N,
+                                      int n_pad, int C, int beam_width, int merge_repeated,
+                                      const float* w, int order, int* decoded, int* decoded_len,
+                                      float* log_score, void* workspace, size_t ws_bytes,
+                                      asr_stream_t stream) {
+  const int rc = check_shape(logits, seq_len, decoded, decoded_len, workspace, T, N, n_pad, C,
+                             beam_width);
+  if (rc != ASR_OK) return rc;
+  ASR_CHECK_ARG(w, "beam lm: null table");
+  ASR_CHECK_ARG(order >= 1 && order <= 5, "beam lm: order must be 1 .. 5");
+  long long n_ctx = 1;                                   // (K + 1)^(order - 1), K = C - 1
+  for (int i = 1; i < order; ++i) {
+    n_ctx *= C;
+    ASR_CHECK_ARG(n_ctx * (C - 1) <= (long long)INT_MAX, "beam lm: table does not fit an int32");
+  }
+  BeamParams p;
+  p.logits = logits; p.seq_len = seq_len; p.T = T; p.n_pad = n_pad; p.C = C; p.W = beam_width;
+  p.merge = merge_repeated ? 1 : 0;
+  p.decoded = decoded; p.decoded_len = decoded_len; p.score = log_score;
+  p.ws = reinterpret_cast<char*>(workspace);
+  p.w = w; p.n_ctx = (int)n_ctx;
+  return launch(p, N, true, ws_bytes, stream);
 }

@@ -18,6 +18,7 @@
 #include "common.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <limits>
 #include <thread>
@@ -40,6 +41,8 @@ struct Node {
   int order;             // creation rank AS IF all C-1 children were created when their
                          // parent first expanded (the tie-break of the eviction order)
   double ob, ol, ot, nb, nl, nt;
+  int ctx;               // LM context of the prefix (0 without a language model)
+  double w;              // fused LM score of this label after the parent's context (0 without)
 };
 
 // The beam as a binary min-heap ordered worst-first: lowest total, newest entry first
@@ -82,13 +85,18 @@ struct Beam {
   }
 };
 
+// ``w`` (null: the plain decoder) is the fused character-LM table (n_ctx, C-1), n_ctx =
+// C^(order-1): w[ctx(parent) * (C-1) + label] is added where TensorFlow's decoder calls its
+// scorer -- when a branch's label path is fed from its parent and when a child is first offered.
 void beam_one(const float* logits, size_t row_stride, int T, int C, int beam_width,
-              bool merge_repeated, std::vector<int>* out, float* score) {
+              bool merge_repeated, std::vector<int>* out, float* score, const float* w = nullptr,
+              long long n_ctx = 1) {
   const int blank = C - 1;
   std::vector<Node> nodes;
   std::vector<int> child_table;                  // (C-1) slots per expanded node, -1 = absent
   nodes.reserve((size_t)beam_width * 64 + 16);
-  nodes.push_back(Node{-1, -1, -1, 0, kLogZero, kLogZero, kLogZero, 0.0, kLogZero, 0.0});
+  nodes.push_back(Node{-1, -1, -1, 0, kLogZero, kLogZero, kLogZero, 0.0, kLogZero, 0.0,
+                       (int)(n_ctx - 1), 0.0});
   int next_order = 1;
   std::vector<int> order_base;                   // per child-table block
   std::vector<int> leaves(1, 0), branches;
@@ -114,7 +122,8 @@ void beam_one(const float* logits, size_t row_stride, int T, int C, int beam_wid
       if (e.parent >= 0) {
         const Node& par = nodes[e.parent];
         if (par.nt != kLogZero) {
-          const double prev = (e.label == par.label) ? par.ob : par.ot;
+          double prev = (e.label == par.label) ? par.ob : par.ot;
+          if (w) prev += e.w;
           e.nl = lse(e.nl, prev);
         }
         e.nl += inp[e.label];
@@ -139,11 +148,13 @@ void beam_one(const float* logits, size_t row_stride, int T, int C, int beam_wid
       }
       const int slots = nodes[b].children;
       const double b_ob = nodes[b].ob, b_ot = nodes[b].ot;
-      const int b_label = nodes[b].label;
+      const int b_label = nodes[b].label, b_ctx = nodes[b].ctx;
       for (int c = 0; c < C - 1; ++c) {          // label ids 0 .. C-2 (blank is C-1)
         const int idx = child_table[slots + c];
         if (idx >= 0 && nodes[idx].nt != kLogZero) continue;   // already in the beam
-        const double prev = (c == b_label) ? b_ob : b_ot;
+        double prev = (c == b_label) ? b_ob : b_ot;
+        const double w_e = w ? (double)w[(size_t)b_ctx * (C - 1) + c] : 0.0;
+        if (w) prev += w_e;                      // (-inf stays -inf)
         const double nl = prev == kLogZero ? kLogZero : inp[c] + prev;
         if (!is_candidate(nl)) {
           // TF resets the rejected child's OLD probabilities too: if that child is itself
@@ -155,7 +166,8 @@ void beam_one(const float* logits, size_t row_stride, int T, int C, int beam_wid
         if (id < 0) {
           id = (int)nodes.size();
           nodes.push_back(Node{b, c, -1, order_base[slots / (C - 1)] + c, kLogZero, kLogZero,
-                               kLogZero, kLogZero, kLogZero, kLogZero});
+                               kLogZero, kLogZero, kLogZero, kLogZero,
+                               (int)(((long long)b_ctx * C + c) % n_ctx), w_e});
           child_table[slots + c] = id;
         }
         nodes[id].nb = kLogZero;
@@ -203,10 +215,40 @@ int levenshtein(const int* a, int la, const int* b, int lb) {
 
 }  // namespace
 
+namespace {
+int beam_batch_host(const float* logits_host, const int* seq_len_host, int T, int N, int n_pad,
+                    int C, int beam_width, int merge_repeated, int* decoded, int* decoded_len,
+                    float* log_score, const float* w, long long n_ctx);
+}  // namespace
+
 extern "C" int asr_ctc_beam_search_host(const float* logits_host, const int* seq_len_host,
                                         int T, int N, int n_pad, int C, int beam_width,
                                         int merge_repeated, int* decoded, int* decoded_len,
                                         float* log_score) {
+  return beam_batch_host(logits_host, seq_len_host, T, N, n_pad, C, beam_width, merge_repeated,
+                         decoded, decoded_len, log_score, nullptr, 1);
+}
+
+extern "C" int asr_ctc_beam_lm_host(const float* logits_host, const int* seq_len_host, int T,
+                                    int N, int n_pad, int C, int beam_width, int merge_repeated,
+                                    const float* w_host, int order, int* decoded,
+                                    int* decoded_len, float* log_score) {
+  ASR_CHECK_ARG(w_host, "beam lm: null table");
+  ASR_CHECK_ARG(order >= 1 && order <= 5, "beam lm: order must be 1 .. 5");
+  ASR_CHECK_ARG(C >= 2, "beam: bad shape");
+  long long n_ctx = 1;                                   // (K + 1)^(order - 1), K = C - 1
+  for (int i = 1; i < order; ++i) {
+    n_ctx *= C;
+    ASR_CHECK_ARG(n_ctx * (C - 1) <= (long long)INT_MAX, "beam lm: table does not fit an int32");
+  }
+  return beam_batch_host(logits_host, seq_len_host, T, N, n_pad, C, beam_width, merge_repeated,
+                         decoded, decoded_len, log_score, w_host, n_ctx);
+}
+
+namespace {
+int beam_batch_host(const float* logits_host, const int* seq_len_host, int T, int N, int n_pad,
+                    int C, int beam_width, int merge_repeated, int* decoded, int* decoded_len,
+                    float* log_score, const float* w, long long n_ctx) {
   ASR_CHECK_ARG(logits_host && seq_len_host && decoded && decoded_len, "beam: null pointer");
   ASR_CHECK_ARG(T > 0 && N > 0 && n_pad >= N && C >= 2 && beam_width >= 1, "beam: bad shape");
   const size_t row_stride = (size_t)n_pad * C;
@@ -220,7 +262,7 @@ extern "C" int asr_ctc_beam_search_host(const float* logits_host, const int* seq
       Tn = Tn < 0 ? 0 : (Tn > T ? T : Tn);
       float sc = 0.f;
       beam_one(logits_host + (size_t)n * C, row_stride, Tn, C, beam_width, merge_repeated != 0,
-               &path, &sc);
+               &path, &sc, w, n_ctx);
       const int L = (int)path.size();
       for (int i = 0; i < T; ++i) decoded[(size_t)n * T + i] = i < L ? path[i] : -1;
       decoded_len[n] = L;
@@ -236,6 +278,7 @@ extern "C" int asr_ctc_beam_search_host(const float* logits_host, const int* seq
   }
   return ASR_OK;
 }
+}  // namespace
 
 extern "C" int asr_edit_distance_host(const int* hyp, const int* hyp_len, int hyp_ld,
                                       const int* truth, const int* truth_len, int truth_ld,

@@ -716,6 +716,78 @@ def ctc_beam_search(logits, seq_len, N, beam_width=100, merge_repeated=True):
     return dec, dlen, score
 
 
+def _lm_table_shape(w, Cc, order):
+    order = int(order)
+    if not 1 <= order <= 5:
+        raise ValueError('ctc_beam_search_lm: order must be 1 .. 5, got %d' % order)
+    want = (int(Cc) ** (order - 1), int(Cc) - 1)
+    if tuple(w.shape) != want:
+        raise ValueError('ctc_beam_search_lm: the fused table has shape %s, order %d over %d '
+                         'classes needs %s' % (tuple(w.shape), order, Cc, want))
+    return order
+
+
+def ctc_beam_search_lm(logits, seq_len, N, beam_width, merge_repeated, w, order):
+    """K9 with a character LM on the device (asr_ctc_beam_lm_device): as ctc_beam_search, plus
+    ``w`` -- the FUSED table CharLM.fused(alpha, beta) as a float32 DEVICE tensor (n_ctx, C - 1)
+    -- and the model's ``order``.  Same results as ctc_beam_search_lm_host."""
+    lib = L.load()
+    T, n_pad, Cc = logits.shape
+    _check_f32(logits, w)
+    order = _lm_table_shape(w, Cc, order)
+    if w.device != logits.device or not w.is_contiguous():
+        raise ValueError('ctc_beam_search_lm: the fused table must be contiguous on %s'
+                         % logits.device)
+    dev = logits.device
+    dec = torch.empty((int(N), T), dtype=torch.int32, device=dev)
+    dlen = torch.empty(int(N), dtype=torch.int32, device=dev)
+    score = torch.empty(int(N), dtype=torch.float32, device=dev)
+    nbytes = lib.asr_ctc_beam_lm_device_workspace_bytes(T, int(N), Cc, int(beam_width))
+    key = ('beam_lm', str(dev))
+    ws = WS.bufs.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = WS.bufs[key] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+    L.check(lib.asr_ctc_beam_lm_device(_ptr(logits), _ptr(seq_len), T, int(N), n_pad, Cc,
+                                       int(beam_width), int(bool(merge_repeated)), _ptr(w),
+                                       order, _ptr(dec), _ptr(dlen), _ptr(score), _ptr(ws),
+                                       nbytes, _stream()),
+            'asr_ctc_beam_lm_device')
+    return dec, dlen, score
+
+
+def ctc_beam_lm_counters(logits_shape, N, beam_width, utterance=0, device='cuda:0'):
+    """ctc_beam_counters for the last ctc_beam_search_lm call of that shape."""
+    lib = L.load()
+    T, n_pad, Cc = logits_shape
+    ws = WS.bufs[('beam_lm', str(torch.device(device)))]
+    out = (C.c_longlong * 7)()
+    L.check(lib.asr_ctc_beam_lm_device_counters(_ptr(ws), int(T), int(N), int(Cc),
+                                                int(beam_width), int(utterance), out, _stream()),
+            'asr_ctc_beam_lm_device_counters')
+    return dict(update_s=out[0] * 1e-8, rank_s=out[1] * 1e-8, turns_s=out[2] * 1e-8,
+                handover_s=out[3] * 1e-8, turns=out[4], insertions=out[5], blocks=out[6])
+
+
+def ctc_beam_search_lm_host(logits_host, seq_len_host, N, beam_width, merge_repeated, w, order):
+    """ctc_beam_search_host with a character LM: ``w`` is the fused float32 table (n_ctx, C - 1)
+    as a numpy array (asr_ctc_beam_lm_host)."""
+    lib = L.load()
+    logits_host = np.ascontiguousarray(logits_host, dtype=np.float32)
+    seq = np.ascontiguousarray(seq_len_host, dtype=np.int32)
+    T, n_pad, Cc = logits_host.shape
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    order = _lm_table_shape(w, Cc, order)
+    dec = np.empty((int(N), T), dtype=np.int32)
+    dlen = np.empty(int(N), dtype=np.int32)
+    score = np.empty(int(N), dtype=np.float32)
+    L.check(lib.asr_ctc_beam_lm_host(
+        logits_host.ctypes.data_as(C.c_void_p), seq.ctypes.data_as(C.c_void_p), T, int(N),
+        n_pad, Cc, int(beam_width), int(bool(merge_repeated)), w.ctypes.data_as(C.c_void_p),
+        order, dec.ctypes.data_as(C.c_void_p), dlen.ctypes.data_as(C.c_void_p),
+        score.ctypes.data_as(C.c_void_p)), 'asr_ctc_beam_lm_host')
+    return [dec[n, :dlen[n]].tolist() for n in range(int(N))], score
+
+
 HOST_BEAM_MAX_UTTERANCES = 64
 
 

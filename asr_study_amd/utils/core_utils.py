@@ -3,8 +3,9 @@
 ``load_model(fname, return_meta, mode)``: mode 'train' rebuilds the model as
 core.models defines it; mode 'eval' swaps the greedy decoder for beam search with
 the reference's defaults (is_greedy=False, beam_width=400: utils/core_utils.py
-:67-72) and renames the metric to beam_search_ler; ``setup_gpu`` selects the visible
-device(s) (:22-35)."""
+:67-72) and renames the metric to beam_search_ler, and takes ``lm`` (a CharLM or a path),
+``lm_alpha`` and ``lm_beta`` for a character language model in that search; ``setup_gpu``
+selects the visible device(s) (:22-35)."""
 import os
 
 import numpy as np
@@ -95,6 +96,12 @@ def load_model(model_fname, return_meta=False, mode='train', **kwargs):
             model.decoder = dict(is_greedy=kwargs.get('is_greedy', False),
                                  beam_width=kwargs.get('beam_width', 400),
                                  merge_repeated=True)
+            if kwargs.get('lm') is not None:
+                # a decode-time argument: neither the model config nor the checkpoint has it
+                from ..core.ctc_utils import decoder_config
+                model.decoder = decoder_config(
+                    lm=kwargs['lm'], lm_alpha=kwargs.get('lm_alpha', 1.0),
+                    lm_beta=kwargs.get('lm_beta', 0.0), **model.decoder)
         else:                       # predict.py --no_decoder: the network output itself
             model.decoder = None
         model.metrics_names = ['loss', 'ctc_loss', 'beam_search_loss', 'beam_search_ler']

@@ -242,7 +242,9 @@ def model_config(model):
                                  'sparse': True, 'name': 'labels'}, [])
     add('InputLayer', 'inputs_length', {'batch_input_shape': [None, None], 'input_dtype': 'int32',
                                         'sparse': False, 'name': 'inputs_length'}, [])
-    dec = dict(model.decoder or {'is_greedy': True})
+    # (a language model is a decode-time argument, not part of the model file)
+    dec = {k: v for k, v in (model.decoder or {'is_greedy': True}).items()
+           if k not in ('lm', 'lm_alpha', 'lm_beta')}
     add('Lambda', 'decoder', _lambda_config('decoder', 'decode',
                                              ('decode_output_shape', 'function'),
                                              {k: dec[k] for k in sorted(dec)}),

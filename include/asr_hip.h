@@ -720,6 +720,28 @@ int asr_ctc_beam_device(const float* logits, const int* seq_len, int T, int N, i
 int asr_ctc_beam_device_counters(const void* workspace, int T, int N, int C, int beam_width,
                                  int utterance, long long* out7, asr_stream_t stream);
 
+/* K9  Beam search with a character language model.  w is the FUSED float32 table            */
+/* alpha * log P(label | context) + beta of shape (n_ctx, C - 1), n_ctx = C^(order - 1), order  */
+/* 1 .. 5, n_ctx * (C - 1) <= INT_MAX; the context index is the last order - 1 labels read as   */
+/* base-C digits, oldest first, the digit C - 1 standing for "before the sentence".  w[ctx of   */
+/* the parent prefix][label] is added where TensorFlow's decoder calls its scorer: when a       */
+/* branch's label path is fed from its parent and when a child is first offered.  Everything    */
+/* else (candidate tests, eviction, tie-breaking, the emitted score, merge_repeated) is the     */
+/* plain decoder's; an all-zero table gives its results bit for bit.  Host form: every pointer  */
+/* is a HOST pointer; device form: every pointer is a DEVICE pointer, same limits as            */
+/* asr_ctc_beam_device, its own workspace size and counters.                                    */
+int asr_ctc_beam_lm_host(const float* logits_host, const int* seq_len_host, int T, int N,
+                         int n_pad, int C, int beam_width, int merge_repeated,
+                         const float* w_host, int order, int* decoded, int* decoded_len,
+                         float* log_score);
+size_t asr_ctc_beam_lm_device_workspace_bytes(int T, int N, int C, int beam_width);
+int asr_ctc_beam_lm_device(const float* logits, const int* seq_len, int T, int N, int n_pad,
+                           int C, int beam_width, int merge_repeated, const float* w, int order,
+                           int* decoded, int* decoded_len, float* log_score, void* workspace,
+                           size_t ws_bytes, asr_stream_t stream);
+int asr_ctc_beam_lm_device_counters(const void* workspace, int T, int N, int C, int beam_width,
+                                    int utterance, long long* out7, asr_stream_t stream);
+
 /* K10 Edit distance (host).  Replaces core/metrics.py:8 -> tf.edit_distance */
 /* (normalize=True).  Ragged inputs as (N, max) padded + lengths.            */
 int asr_edit_distance_host(const int* hyp, const int* hyp_len, int hyp_ld,
