@@ -21,6 +21,7 @@ import numpy as np
 import yaml
 
 from ..datasets import h5lite
+from .params import LN_PARTS, MI_PARTS, keras_names
 
 
 class Callback(object):
@@ -38,82 +39,20 @@ class Callback(object):
 
 
 LSTM_PARTS = ('W', 'U', 'b')
-# GRU(batch_norm=True): beta takes the place of b; the running moments follow (running_std holds
-# the variance, as in keras.layers.BatchNormalization)
-GRU_BN_PARTS = ('W', 'U', 'gamma', 'beta', 'running_mean', 'running_std')
-MI_PARTS = ('mi_alpha', 'mi_beta1', 'mi_beta2')
-# the reference iterates a dict literal {'Uh', 'Wx', 'new_c'} (core/layers.py:409): its
-# Python-2 order is unspecified, so files are written in this order and READ BY NAME
-LN_PARTS = ('ln_gain_Uh', 'ln_bias_Uh', 'ln_gain_Wx', 'ln_bias_Wx', 'ln_gain_new_c',
-            'ln_bias_new_c')
 
 
 def lstm_weight_parts(stage):
     """Per-direction weight suffixes of a BiLSTM stage in get_weights() order: Keras' W, U, b
     (base LSTM.build), then the reference's add_weight names (core/layers.py:388-422)."""
-    parts = list(LSTM_PARTS)
-    if getattr(stage, 'mi', None) is not None:
-        parts += list(MI_PARTS)
-    if getattr(stage, 'ln', None) is not None:
-        parts += list(LN_PARTS)
-    return parts
+    return [t.name for t in stage.tensors if t.layer.startswith('forward_')]
 
 
 def keras_layers(model, weights):
     """[(layer name, [(weight name, array), ...])] in Keras-1.2.2 naming for the model's
     weight-bearing stages (get_weights() order); every array of ``weights`` is consumed."""
     it = iter(weights)
-    out, nb, nd, nc, ntd, nbn = [], 0, 0, 0, 0, 0
-    for s in model.stages:
-        # (Keras names a TimeDistributed layer by its own counter; the weight group of a Dense
-        # is named after the TimeDistributed around it)
-        if s.kind in ('act', 'dropout') and getattr(s, 'wrapped', False):
-            ntd += 1
-        if s.kind == 'conv':        # keras.layers.Convolution2D: '<name>_W', '<name>_b'
-            nc += 1
-            out.append(('convolution2d_%d' % nc, [('convolution2d_%d_W:0' % nc, next(it)),
-                                                  ('convolution2d_%d_b:0' % nc, next(it))]))
-        elif s.kind == 'bilstm':
-            nb += 1
-            ws = []
-            for d in ('forward', 'backward'):
-                for part in lstm_weight_parts(s):
-                    ws.append(('%s_lstm_%d_%s:0' % (d, nb, part), next(it)))
-            out.append(('bidirectional_%d' % nb, ws))
-        elif s.kind == 'birnn':     # Bidirectional(SimpleRNN): forward W, U, b, then backward
-            nb += 1
-            ws = []
-            for d in ('forward', 'backward'):
-                for part in LSTM_PARTS:
-                    ws.append(('%s_simplernn_%d_%s:0' % (d, nb, part), next(it)))
-            out.append(('bidirectional_%d' % nb, ws))
-        elif s.kind == 'bigru':     # Bidirectional(GRU), fused 'gpu' layout: W, U, b per direction
-            nb += 1
-            ws = []
-            parts = GRU_BN_PARTS if getattr(s, 'bn', False) else LSTM_PARTS
-            for d in ('forward', 'backward'):
-                for part in parts:
-                    ws.append(('%s_gru_%d_%s:0' % (d, nb, part), next(it)))
-            out.append(('bidirectional_%d' % nb, ws))
-        elif s.kind == 'birhn':     # Bidirectional(RHN): '<name>_W', '<name>_<l>_U', '<name>_<l>_b'
-            nb += 1
-            ws = []
-            for d in ('forward', 'backward'):
-                ws.append(('%s_rhn_%d_W:0' % (d, nb), next(it)))
-                for part in ('U', 'b'):
-                    for l in range(s.depth):
-                        ws.append(('%s_rhn_%d_%d_%s:0' % (d, nb, l, part), next(it)))
-            out.append(('bidirectional_%d' % nb, ws))
-        elif s.kind == 'bn':        # keras.layers.BatchNormalization: gamma, beta, running moments
-            nbn += 1
-            out.append(('batchnormalization_%d' % nbn,
-                        [('batchnormalization_%d_%s:0' % (nbn, part), next(it))
-                         for part in ('gamma', 'beta', 'running_mean', 'running_std')]))
-        elif s.kind == 'dense':
-            nd += 1
-            ntd += 1
-            out.append(('timedistributed_%d' % ntd, [('dense_%d_W:0' % nd, next(it)),
-                                                    ('dense_%d_b:0' % nd, next(it))]))
+    out = [(layer, [(name, next(it)) for name in names])
+           for layer, names in keras_names(model.stages)]
     rest = sum(1 for _ in it)
     if rest:
         raise ValueError('keras_layers: %d weight arrays left over (get_weights() and the '

@@ -14,7 +14,8 @@ single launches); LSTM gate axes are stored unit-major/gate-minor (see
 include/asr_hip.h) and hidden sizes are rounded up to a multiple of 4 with zero
 weights (eyben's 78/27-unit layers).  get_weights()/set_weights() speak the
 reference's Keras layout: per Bidirectional layer [W (in,4H), U (H,4H), b (4H)] for
-the forward then the backward copy, gate blocks i,f,c,o; Dense [W, b].
+the forward then the backward copy, gate blocks i,f,c,o; Dense [W, b].  Where each weight
+lies in the flat buffer, and how it is padded, is the parameter table of core/params.py.
 """
 import math
 import os
@@ -25,51 +26,8 @@ import torch
 
 from .. import ops
 from . import optimizers as _opt
-
-
-def _pad4(n):
-    return (int(n) + 3) // 4 * 4
-
-
-def _gm2um(a, H, Hp):
-    """(..., 4H) gate-major -> (..., 4Hp) unit-major/gate-minor, zero padded."""
-    sh = a.shape[:-1]
-    g = a.reshape(sh + (4, H))
-    out = np.zeros(sh + (Hp, 4), a.dtype)
-    out[..., :H, :] = np.swapaxes(g, -1, -2)
-    return out.reshape(sh + (4 * Hp,))
-
-
-def _um2gm(a, H, Hp):
-    sh = a.shape[:-1]
-    u = a.reshape(sh + (Hp, 4))[..., :H, :]
-    return np.ascontiguousarray(np.swapaxes(u, -1, -2)).reshape(sh + (4 * H,))
-
-
-def _blocks_pad(a, H, Hp):
-    """(..., 3H) GRU column blocks z | r | h -> (..., 3Hp): each block zero padded to Hp."""
-    sh = a.shape[:-1]
-    out = np.zeros(sh + (3, Hp), a.dtype)
-    out[..., :H] = a.reshape(sh + (3, H))
-    return out.reshape(sh + (3 * Hp,))
-
-
-def _blocks_unpad(a, H, Hp):
-    sh = a.shape[:-1]
-    return np.ascontiguousarray(a.reshape(sh + (3, Hp))[..., :H]).reshape(sh + (3 * H,))
-
-
-def _cblocks_pad(a, H, Hp, C):
-    """(..., C H) RHN column blocks h | t | [c] -> (..., C Hp): each block zero padded to Hp."""
-    sh = a.shape[:-1]
-    out = np.zeros(sh + (C, Hp), a.dtype)
-    out[..., :H] = a.reshape(sh + (C, H))
-    return out.reshape(sh + (C * Hp,))
-
-
-def _cblocks_unpad(a, H, Hp, C):
-    sh = a.shape[:-1]
-    return np.ascontiguousarray(a.reshape(sh + (C, Hp))[..., :H]).reshape(sh + (C * H,))
+from . import params as P
+from .params import _pad4
 
 
 # where a Model lives when the factory is given no ``device`` (host-only tests build on 'cpu':
@@ -155,24 +113,23 @@ class Model(object):
         self._ar_covered = []
         # weight-gradient GEMMs run on a side stream, concurrently with the next
         # layer's persistent BPTT kernel (which occupies only H/16 x chains CUs)
-        import os as _os
         # ASR_OVERLAP: 1 = always, 0 = never, auto (default) = unless a layer's recurrence
         # fills every CU (cfg3: 2 directions x 4 batch tiles x 32 workgroups = 256): its waves
         # hold 480 of a SIMD's 512 registers, no GEMM wave fits beside them, and a GEMM launched
         # on the side stream only waits (measured: 51.9 vs 52.5 ms per cfg3 step, but every
         # GEMM duration in a profile doubled by the wait) -- decided per batch in forward()
-        self._overlap_mode = _os.environ.get('ASR_OVERLAP', 'auto')
+        self._overlap_mode = os.environ.get('ASR_OVERLAP', 'auto')
         self.overlap = self._overlap_mode != '0'
         self._side = torch.cuda.Stream(device=self.device) if self.device.type == 'cuda' else None
         # the GEMMs either side of a recurrence are pipelined against its last steps
         # (frames whose both directions are already final), on a third stream
         # 'auto': only when a layer's recurrence leaves at least half of the CUs to the GEMMs
         # it is pipelined against (cfg2: 64 of 256 workgroups; not cfg3's 256 of 256)
-        self._pipeline_mode = _os.environ.get('ASR_PIPELINE', 'auto')
+        self._pipeline_mode = os.environ.get('ASR_PIPELINE', 'auto')
         # the recurrence is cut after split/16 of its steps (frames [T-S, S) are final then)
-        self._pipe_split16 = min(15, max(9, int(_os.environ.get('ASR_PIPE_SPLIT', '13'))))
+        self._pipe_split16 = min(15, max(9, int(os.environ.get('ASR_PIPE_SPLIT', '13'))))
         # (ASR_PIPE_HALVES=0: the pipelined GEMMs wait for whole frames -- comparison switch)
-        self._pipe_halves = _os.environ.get('ASR_PIPE_HALVES', '1') != '0'
+        self._pipe_halves = os.environ.get('ASR_PIPE_HALVES', '1') != '0'
         self.pipeline = self.overlap and self._pipeline_mode == '1'
         # ASR_BPTT_COMPACT: auto (default) = where a layer's BPTT would fill every CU (cfg3) it is
         # launched in the COMPACT geometry (asr_lstm_args.compact: H/32 workgroups per chain,
@@ -180,11 +137,11 @@ class Model(object):
         # GEMMs of the layer above are waiting, and those run beside it on the side stream
         # instead of behind it; 0 = never (the serial schedule of rounds 1-4), 1 = wherever the
         # compact kernel exists
-        self._compact_mode = _os.environ.get('ASR_BPTT_COMPACT', 'auto')
+        self._compact_mode = os.environ.get('ASR_BPTT_COMPACT', 'auto')
         # ASR_BPTT_PLANES=0: BPTT always writes the fp32 dz slab and a pack pass follows (the
         # round 1-5 path; A/B switch).  Default: BPTT writes the packed planes itself where its
         # kernel can (backward()); per-stage bounds of max|dz| live in _buf('dzbound<si>')
-        self._dz_planes_mode = _os.environ.get('ASR_BPTT_PLANES', '1') != '0'
+        self._dz_planes_mode = os.environ.get('ASR_BPTT_PLANES', '1') != '0'
         self._dz_bound_key = {}         # stage -> (fault generation, weights epoch) of its bound
         self._weights_epoch = 0         # bumped when weights are replaced from outside
         self._dz_measure_passes = 0     # measuring BPTT passes run so far (first step of a layer)
@@ -194,7 +151,7 @@ class Model(object):
         # 'auto': from 512 hidden units on (measured: +4 % at 5 x BiLSTM(512) with the 256 x 256
         # tile, -6 % at 5 x BiLSTM(256), where the frame-range pipelining of the per-tile path
         # and the absent pack passes win)
-        self._packed_mode = _os.environ.get('ASR_GEMM_PACKED', 'auto')
+        self._packed_mode = os.environ.get('ASR_GEMM_PACKED', 'auto')
         self.packed = False                       # decided in _layout (needs the stage list)
         self._hl = {}
         # training-time noise comes from the library's counter-based streams (ops.dropout_masks
@@ -213,29 +170,20 @@ class Model(object):
 
     # ------------------------------------------------------------------ params
     def _layout(self, seed):
-        rs = np.random.RandomState(seed)
-        off = 0
+        """Reads the stage list: per stage its attributes and, for a trainable kind, its rows of
+        the parameter table (core/params.py), which allocates its blocks of the flat buffers."""
         self.stages = []
-        segs = []
         # the input features are padded to a multiple of 4 columns (zero column(s), zero
         # weight rows) so that the first layer's GEMMs qualify for the 16-byte fast path
         f_real, f_pad = self.num_features, _pad4(self.num_features)
         self.f_in_pad0 = f_pad
-        init = []
-        run_off = 0                     # BatchNormalization running moments (self.bn_running)
-        tail = 4                        # ... and their moments blocks behind the flag slots
-
-        def take(n):
-            nonlocal off
-            o = off
-            off += _pad4(n)
-            return o
-
+        alloc = P.Alloc()
         for st in self.spec:
             s = Stage()
             s.kind = st['type']
-            s.p_lo = off                    # this stage's slice of the flat param / grad buffers
+            s.p_lo = alloc.params           # this stage's slice of the flat param / grad buffers
             s.f_in, s.f_in_pad = f_real, f_pad
+            s.tensors = []                  # (core/params.py; stays empty without weights)
             if s.kind in ('noise', 'dropout'):
                 s.value = st['value']
                 s.wrapped = bool(st.get('wrapped', False))      # TimeDistributed(Dropout)
@@ -260,29 +208,17 @@ class Model(object):
                                      '(asr_conv2d_* keeps one plane shift per time tap)' % s.kt)
                 if s.st < 1 or s.sf < 1:
                     raise ValueError('conv stage: strides must be >= 1')
-                if s.st > 1 and any(p.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn', 'bigru',
-                                                   'birhn') for p in self.stages):
+                if s.st > 1 and any(p.tensors for p in self.stages):
                     raise ValueError(
                         'conv stage with time stride %d behind a trainable stage: asr_conv2d_dgrad '
                         'exists for time stride 1 only, so a time-strided convolution must be the '
                         'FIRST trainable stage (its input is data and needs no gradient)' % s.st)
-                nw = s.kt * s.kf * s.C_in * s.C_out
-                s.oW = take(nw)
-                s.ob = take(s.C_out)
-                segs += [(s.oW, _pad4(nw), s.l2), (s.ob, _pad4(s.C_out), 0.0)]
-                lim = math.sqrt(6.0 / (s.kt * s.kf * (s.C_in + s.C_out)))      # glorot_uniform
-                W = rs.uniform(-lim, lim, size=(s.kt, s.kf, s.C_in, s.C_out))
-                init.append((s, 'conv', [W.astype(np.float32), np.zeros(s.C_out, np.float32)]))
+                s.tensors = P.conv(s, alloc, None)
                 f_real = f_pad = s.F_out * s.C_out
             elif s.kind == 'dense':
                 s.n_out = st['n_out']
                 s.l2 = st.get('l2', 0.0)
-                s.oW = take(f_pad * s.n_out)
-                s.ob = take(s.n_out)
-                segs += [(s.oW, _pad4(f_pad * s.n_out), s.l2), (s.ob, _pad4(s.n_out), 0.0)]
-                lim = math.sqrt(6.0 / (f_real + s.n_out))
-                W = rs.uniform(-lim, lim, size=(f_real, s.n_out))
-                init.append((s, 'dense', [W.astype(np.float32), np.zeros(s.n_out, np.float32)]))
+                s.tensors = P.dense(s, alloc, self._real_rows(s))
                 f_real = f_pad = s.n_out
                 s.in_map = None
             elif s.kind == 'bilstm':
@@ -291,159 +227,38 @@ class Model(object):
                 s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
                 s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
                 s.mi = st.get('mi')                     # [alpha, beta1, beta2] inits or None
+                s.ln = st.get('layer_norm')             # [gain_init, bias_init] or None
                 s.zoneout_c = float(st.get('zoneout_c') or 0.0)
                 s.zoneout_h = float(st.get('zoneout_h') or 0.0)
                 s.act = st.get('activation') or 'tanh'      # core/layers.py:452, :463
-                s.oW = take(f_pad * 8 * s.Hp)
-                s.oU = take(2 * s.Hp * 4 * s.Hp)
-                segs += [(s.oW, _pad4(f_pad * 8 * s.Hp), s.l2_W),
-                         (s.oU, _pad4(2 * s.Hp * 4 * s.Hp), s.l2_U)]
-                s.ln = st.get('layer_norm')             # [gain_init, bias_init] or None
-                if s.ln is not None:
-                    if s.Hp != s.H:
-                        raise NotImplementedError('layer_norm needs num_hiddens % 4 == 0')
-                    # (2, 34H): alpha, beta1, beta2, bias, LN(h@U) gain/bias, LN(x@W)
-                    # gain/bias (4H each), LN(c) gain/bias (H each)  -- csrc/lstm_ln.hip
-                    s.ocell = take(68 * s.Hp)
-                    s.ob = None
-                    segs.append((s.ocell, _pad4(68 * s.Hp), 0.0))
-                elif s.mi is None:
-                    s.ob = take(8 * s.Hp)
-                    segs.append((s.ob, _pad4(8 * s.Hp), 0.0))
-                else:       # (2, 4, 4Hp): alpha, beta1, beta2, bias per direction
-                    s.omi = take(32 * s.Hp)
-                    s.ob = None
-                    segs.append((s.omi, _pad4(32 * s.Hp), 0.0))
-                ws = []
-                for _ in range(2):      # Keras-1.2.2 consume_less='gpu' init
-                    lim = math.sqrt(6.0 / (f_real + 4 * s.H))
-                    W = rs.uniform(-lim, lim, size=(f_real, 4 * s.H))
-                    a = rs.normal(0.0, 1.0, (s.H, 4 * s.H))
-                    u, _, v = np.linalg.svd(a, full_matrices=False)
-                    U = 1.1 * (u if u.shape == (s.H, 4 * s.H) else v)
-                    b = np.zeros(4 * s.H)
-                    b[s.H:2 * s.H] = 1.0
-                    ws += [W.astype(np.float32), U.astype(np.float32), b.astype(np.float32)]
-                    if s.mi is not None:            # k_init: constant vectors (core/initializers.py)
-                        ws += [np.full(4 * s.H, float(k), np.float32) for k in s.mi]
-                    if s.ln is not None:            # gain, bias of LN(h@U), LN(x@W), LN(c)
-                        for width in (4 * s.H, 4 * s.H, s.H):
-                            ws += [np.full(width, float(s.ln[0]), np.float32),
-                                   np.full(width, float(s.ln[1]), np.float32)]
-                init.append((s, 'bilstm', ws))
+                s.tensors = P.bilstm(s, alloc, self._real_rows(s))
                 f_real, f_pad = 2 * s.H, 2 * s.Hp
             elif s.kind == 'act':
                 s.act = st['activation']        # 'tanh' / 'relu' / 'linear' / clipped_relu()
                 s.wrapped = bool(st.get('wrapped', False))      # TimeDistributed(Activation)
-            elif s.kind == 'birnn':
-                # Bidirectional(SimpleRNN) (csrc/rnn.hip): W (in, 2, Hp), U (2, Hp, Hp), b (2, Hp)
+            elif s.kind in ('birnn', 'bigru', 'birhn'):
+                # Bidirectional(SimpleRNN | GRU | RHN) (csrc/rnn.hip, gru.hip, rhn.hip)
                 s.H = st['H']
                 s.Hp = _pad4(s.H)
                 s.merge = st.get('merge_mode', 'concat')
                 s.act = st.get('activation') or 'tanh'
                 s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
                 s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
-                s.init = st.get('init', 'glorot_uniform')
-                s.oW = take(f_pad * 2 * s.Hp)
-                s.oU = take(2 * s.Hp * s.Hp)
-                s.ob = take(2 * s.Hp)
-                segs += [(s.oW, _pad4(f_pad * 2 * s.Hp), s.l2_W),
-                         (s.oU, _pad4(2 * s.Hp * s.Hp), s.l2_U), (s.ob, _pad4(2 * s.Hp), 0.0)]
-                ws = []
-                for _ in range(2):      # Keras 1.2.2 SimpleRNN.build: init, inner_init, zeros
-                    if s.init == 'he_normal':       # normal(0, sqrt(2 / fan_in)), not truncated
-                        W = rs.normal(0.0, math.sqrt(2.0 / f_real), size=(f_real, s.H))
-                    else:
-                        lim = math.sqrt(6.0 / (f_real + s.H))
-                        W = rs.uniform(-lim, lim, size=(f_real, s.H))
-                    u, _, v = np.linalg.svd(rs.normal(0.0, 1.0, (s.H, s.H)), full_matrices=False)
-                    ws += [W.astype(np.float32), (1.1 * u).astype(np.float32),
-                           np.zeros(s.H, np.float32)]
-                init.append((s, 'birnn', ws))
-                f_real, f_pad = (2 * s.H, 2 * s.Hp) if s.merge == 'concat' else (s.H, s.Hp)
-            elif s.kind == 'bigru':
-                # Bidirectional(GRU) (csrc/gru.hip): W (in, 2, 3Hp), U (2, Hp, 3Hp), b (2, 3Hp),
-                # column blocks z, r, h of Hp each
-                s.H = st['H']
-                s.Hp = _pad4(s.H)
-                s.merge = st.get('merge_mode', 'concat')
-                s.act = st.get('activation') or 'tanh'
-                s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
-                s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
-                # batch_norm (K18, csrc/batchnorm.hip): sequence-wise BN of the input projection;
-                # no b segment -- gamma, beta (2, 3Hp) each (l2 0) instead, the running moments
-                # and the moments block kept where the bn stage keeps its own
-                s.bn = bool(st.get('batch_norm', False))
-                s.oW = take(f_pad * 6 * s.Hp)
-                s.oU = take(2 * s.Hp * 3 * s.Hp)
-                segs += [(s.oW, _pad4(f_pad * 6 * s.Hp), s.l2_W),
-                         (s.oU, _pad4(2 * s.Hp * 3 * s.Hp), s.l2_U)]
-                if s.bn:
-                    s.bn_eps = float(st.get('bn_epsilon', 1e-3))
-                    s.bn_momentum = float(st.get('bn_momentum', 0.99))
-                    s.ob = None
-                    s.og = take(6 * s.Hp)
-                    s.obeta = take(6 * s.Hp)
-                    segs += [(s.og, _pad4(6 * s.Hp), 0.0), (s.obeta, _pad4(6 * s.Hp), 0.0)]
-                    s.orun = run_off
-                    run_off += 2 * 6 * s.Hp
-                    s.omom = tail
-                    tail += _pad4(ops.bn_moments_len(6 * s.Hp))
+                if s.kind == 'birnn':
+                    s.init = st.get('init', 'glorot_uniform')
+                elif s.kind == 'bigru':
+                    # batch_norm (K18, csrc/batchnorm.hip): sequence-wise BN of the input projection
+                    s.bn = bool(st.get('batch_norm', False))
+                    if s.bn:
+                        s.bn_eps = float(st.get('bn_epsilon', 1e-3))
+                        s.bn_momentum = float(st.get('bn_momentum', 0.99))
                 else:
-                    s.ob = take(6 * s.Hp)
-                    segs.append((s.ob, _pad4(6 * s.Hp), 0.0))
-                ws = []
-                for _ in range(2):      # Keras-1.2.2 consume_less='gpu' init, as the BiLSTM stage
-                    lim = math.sqrt(6.0 / (f_real + 3 * s.H))
-                    W = rs.uniform(-lim, lim, size=(f_real, 3 * s.H))
-                    a = rs.normal(0.0, 1.0, (s.H, 3 * s.H))
-                    u, _, v = np.linalg.svd(a, full_matrices=False)
-                    U = 1.1 * (u if u.shape == (s.H, 3 * s.H) else v)
-                    ws += [W.astype(np.float32), U.astype(np.float32)]
-                    if s.bn:            # gamma, beta, running mean, running variance
-                        ws += [np.ones(3 * s.H, np.float32), np.zeros(3 * s.H, np.float32),
-                               np.zeros(3 * s.H, np.float32), np.ones(3 * s.H, np.float32)]
-                    else:
-                        ws.append(np.zeros(3 * s.H, np.float32))
-                init.append((s, 'bigru', ws))
-                f_real, f_pad = (2 * s.H, 2 * s.Hp) if s.merge == 'concat' else (s.H, s.Hp)
-            elif s.kind == 'birhn':
-                # Bidirectional(RHN) (csrc/rhn.hip): W (in, 2, C Hp), U (2, L, Hp, C Hp),
-                # b (2, L, C Hp), column blocks h, t [, c] of Hp each (C = 2 when coupled)
-                s.H = st['H']
-                s.Hp = _pad4(s.H)
-                s.depth = int(st.get('depth', 1))
-                s.coupling = bool(st.get('coupling', True))
-                s.nblk = 2 if s.coupling else 3
-                s.merge = st.get('merge_mode', 'concat')
-                s.act = st.get('activation') or 'tanh'
-                s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
-                s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
-                Wd = s.nblk * s.Hp
-                s.oW = take(f_pad * 2 * Wd)
-                s.oU = take(2 * s.depth * s.Hp * Wd)
-                s.ob = take(2 * s.depth * Wd)
-                segs += [(s.oW, _pad4(f_pad * 2 * Wd), s.l2_W),
-                         (s.oU, _pad4(2 * s.depth * s.Hp * Wd), s.l2_U),
-                         (s.ob, _pad4(2 * s.depth * Wd), 0.0)]
-                ws = []
-                for _ in range(2):      # the reference's RHN.build: init, inner_init, highway bias
-                    lim = math.sqrt(6.0 / (f_real + s.nblk * s.H))
-                    ws.append(rs.uniform(-lim, lim, size=(f_real, s.nblk * s.H)).astype(np.float32))
-                    for _l in range(s.depth):
-                        a = rs.normal(0.0, 1.0, (s.H, s.nblk * s.H))
-                        u, _, v = np.linalg.svd(a, full_matrices=False)
-                        ws.append((1.1 * (u if u.shape == a.shape else v)).astype(np.float32))
-                    b = np.zeros(s.nblk * s.H, np.float32)
-                    b[s.H:] = -2.0              # highway_bias_initializer on t (and c)
-                    ws += [b.copy() for _l in range(s.depth)]
-                init.append((s, 'birhn', ws))
+                    s.depth = int(st.get('depth', 1))
+                    s.coupling = bool(st.get('coupling', True))
+                    s.nblk = 2 if s.coupling else 3
+                s.tensors = getattr(P, s.kind)(s, alloc, self._real_rows(s))
                 f_real, f_pad = (2 * s.H, 2 * s.Hp) if s.merge == 'concat' else (s.H, s.Hp)
             elif s.kind == 'bn':
-                # BatchNormalization (csrc/batchnorm.hip): gamma, beta (C each) in the flat
-                # parameters (l2 0); running mean / variance in self.bn_running (not trainable);
-                # the moments block of the running update behind the gradients' flag slots, so
-                # that data parallel the gradient all-reduce pools it over the ranks
                 s.eps, s.momentum = float(st.get('epsilon', 1e-3)), float(st.get('momentum', 0.99))
                 fc = st.get('fc')
                 s.grouped = fc is not None and int(fc[1]) < f_pad
@@ -460,17 +275,7 @@ class Model(object):
                                                   'width must be a multiple of 4' % f_real)
                 s.n_real = s.C if s.grouped else f_real
                 s.clip = 0.0                    # > 0: a following clipped ReLU fused (below)
-                s.og = take(s.C)
-                s.obeta = take(s.C)
-                segs += [(s.og, _pad4(s.C), 0.0), (s.obeta, _pad4(s.C), 0.0)]
-                s.orun = run_off
-                run_off += 2 * _pad4(s.C)
-                s.omom = tail
-                tail += _pad4(ops.bn_moments_len(s.C))
-                init.append((s, 'bn', [np.ones(s.n_real, np.float32),
-                                       np.zeros(s.n_real, np.float32),
-                                       np.zeros(s.n_real, np.float32),
-                                       np.ones(s.n_real, np.float32)]))
+                s.tensors = P.bn(s, alloc, self._bn_cols(s))
             elif s.kind == 'merge':
                 s.mode, s.skip = st['mode'], int(st['skip'])
                 src = self.stages[s.skip]
@@ -480,11 +285,10 @@ class Model(object):
             else:
                 raise ValueError(s.kind)
             s.f_out, s.f_out_pad = f_real, f_pad
-            s.p_hi = off
+            s.p_hi = alloc.params
             self.stages.append(s)
-        import os as _os
         widest = max([st.Hp for st in self.stages if st.kind == 'bilstm'] + [0])
-        self.packed = (_os.environ.get('ASR_GEMM_PREC', '1') != '0' and
+        self.packed = (os.environ.get('ASR_GEMM_PREC', '1') != '0' and
                        (self._packed_mode == '1' or (self._packed_mode == 'auto' and widest >= 512)))
         self.num_classes = f_real
         self._has_rnn = any(st.kind == 'birnn' for st in self.stages)
@@ -503,33 +307,34 @@ class Model(object):
                 nxt.fused = True
         self.time_strides = [st.st for st in self.stages if st.kind == 'conv' and st.st > 1]
         self._convs = {}
-        self.n_params = off
+        self.n_params = off = alloc.params
         self.params = torch.zeros(off, dtype=torch.float32, device=self.device)
         # gradients + 4 trailing floats: [0:2] carry this rank's recurrent-kernel timeout flags
         # through the gradient all-reduce (sum > 0 on every rank if ANY rank timed out), so a
         # veto of the update is collective and costs no collective of its own; behind them the
         # BatchNormalization stages' moments blocks (none without such a stage)
-        self._gbuf = torch.zeros(off + tail, dtype=torch.float32, device=self.device)
+        self._gbuf = torch.zeros(off + alloc.moments, dtype=torch.float32, device=self.device)
         self.grads = self._gbuf[:off]
-        self.bn_running = torch.zeros(max(run_off, 4), dtype=torch.float32, device=self.device)
-        self._segments = sorted(segs)
+        self.bn_running = torch.zeros(max(alloc.running, 4), dtype=torch.float32,
+                                      device=self.device)
+        self._segments = P.segments(self.stages)
         self._segs_dev, self._nseg = ops.make_segments(self._segments, self.device)
         self._norm = torch.zeros(2, dtype=torch.float64, device=self.device)
-        weights = []
-        for s, kind, ws in init:
-            weights += ws
-        self.set_weights(weights)
+        # initial values: all from ONE stream, in stage order and Keras order within a stage
+        rs = np.random.RandomState(seed)
+        self.set_weights([P.draw(t, rs) for s in self.stages for t in s.tensors])
 
     def _real_rows(self, s):
-        """Map of the padded input-feature rows of a stage to its real rows."""
+        """Map of the padded input-feature rows of a stage to its real rows: the output columns
+        of the last stage before it that has an input projection (BatchNormalization keeps the
+        columns it is given), whose two directions are padded apart when it concatenates them."""
         prev = None
         for st in self.stages:
             if st is s:
                 break
-            if st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bigru', 'birhn'):
+            if hasattr(st, 'oW'):
                 prev = st
-        if (prev is not None and prev.kind in ('bilstm', 'birnn', 'bigru', 'birhn')
-                and prev.Hp != prev.H
+        if (prev is not None and hasattr(prev, 'Hp') and prev.Hp != prev.H
                 and getattr(prev, 'merge', 'concat') == 'concat'):
             idx = np.concatenate([np.arange(prev.H), prev.Hp + np.arange(prev.H)])
         else:
@@ -538,143 +343,30 @@ class Model(object):
 
     def set_weights(self, weights):
         """weights: flat list in the reference's Keras order (see module doc)."""
-        host = self.params.detach().cpu().numpy().copy()
-        run = self.bn_running.detach().cpu().numpy().copy()
+        bufs = {'params': self.params.detach().cpu().numpy().copy(),
+                'running': self.bn_running.detach().cpu().numpy().copy()}
+        tensors = [t for s in self.stages for t in s.tensors]
+        names = [n for _, ns in P.keras_names(self.stages) for n in ns]
+        for t in tensors:                   # (pads: 0, running variances 1)
+            P.clear(t, bufs[t.buf])
         it = iter(weights)
-        for s in self.stages:
-            if s.kind == 'conv':
-                W, b = np.asarray(next(it), np.float32), np.asarray(next(it), np.float32)
-                assert W.shape == (s.kt, s.kf, s.C_in, s.C_out), W.shape
-                host[s.oW:s.oW + W.size] = W.ravel()
-                host[s.ob:s.ob + s.C_out] = b
-            elif s.kind == 'dense':
-                W, b = np.asarray(next(it), np.float32), np.asarray(next(it), np.float32)
-                rows = self._real_rows(s)
-                Wp = np.zeros((s.f_in_pad, s.n_out), np.float32)
-                Wp[rows] = W
-                host[s.oW:s.oW + Wp.size] = Wp.ravel()
-                host[s.ob:s.ob + s.n_out] = b
-            elif s.kind == 'bilstm':
-                rows = self._real_rows(s)
-                Wp = np.zeros((s.f_in_pad, 2, 4 * s.Hp), np.float32)
-                Up = np.zeros((2, s.Hp, 4 * s.Hp), np.float32)
-                bp = np.zeros((2, 4 * s.Hp), np.float32)
-                mip = np.zeros((2, 4, 4 * s.Hp), np.float32)
-                for d in range(2):
-                    W, U, b = [np.asarray(next(it), np.float32) for _ in range(3)]
-                    Wp[rows, d] = _gm2um(W, s.H, s.Hp)
-                    Up[d, :s.H] = _gm2um(U, s.H, s.Hp)
-                    bp[d] = _gm2um(b, s.H, s.Hp)
-                    if s.mi is not None:            # Keras order: W, U, b, alpha, beta1, beta2
-                        for k in range(3):
-                            mip[d, k] = _gm2um(np.asarray(next(it), np.float32), s.H, s.Hp)
-                        mip[d, 3] = bp[d]
-                    if s.ln is not None:            # ... then the LN pairs (Uh, Wx, new_c)
-                        H = s.H
-                        blk = np.zeros(34 * H, np.float32)
-                        if s.mi is not None:
-                            blk[:12 * H] = mip[d, :3].ravel()
-                        blk[12 * H:16 * H] = bp[d]
-                        for k in range(4):          # gain_u, bias_u, gain_w, bias_w
-                            blk[(16 + 4 * k) * H:(20 + 4 * k) * H] = \
-                                _gm2um(np.asarray(next(it), np.float32), H, H)
-                        blk[32 * H:33 * H] = np.asarray(next(it), np.float32)
-                        blk[33 * H:34 * H] = np.asarray(next(it), np.float32)
-                        host[s.ocell + d * 34 * H:s.ocell + (d + 1) * 34 * H] = blk
-                host[s.oW:s.oW + Wp.size] = Wp.ravel()
-                host[s.oU:s.oU + Up.size] = Up.ravel()
-                if s.ln is not None:
-                    pass
-                elif s.mi is None:
-                    host[s.ob:s.ob + bp.size] = bp.ravel()
-                else:
-                    host[s.omi:s.omi + mip.size] = mip.ravel()
-            elif s.kind == 'birnn':
-                rows = self._real_rows(s)
-                Wp = np.zeros((s.f_in_pad, 2, s.Hp), np.float32)
-                Up = np.zeros((2, s.Hp, s.Hp), np.float32)
-                bp = np.zeros((2, s.Hp), np.float32)
-                for d in range(2):          # Keras order: forward W, U, b, then backward
-                    W, U, b = [np.asarray(next(it), np.float32) for _ in range(3)]
-                    assert W.shape == (len(rows), s.H) and U.shape == (s.H, s.H), (W.shape, U.shape)
-                    Wp[rows, d, :s.H] = W
-                    Up[d, :s.H, :s.H] = U
-                    bp[d, :s.H] = b
-                host[s.oW:s.oW + Wp.size] = Wp.ravel()
-                host[s.oU:s.oU + Up.size] = Up.ravel()
-                host[s.ob:s.ob + bp.size] = bp.ravel()
-            elif s.kind == 'bigru':
-                rows = self._real_rows(s)
-                Wp = np.zeros((s.f_in_pad, 2, 3 * s.Hp), np.float32)
-                Up = np.zeros((2, s.Hp, 3 * s.Hp), np.float32)
-                bp = np.zeros((2, 3 * s.Hp), np.float32)
-                gp = np.zeros((2, 3 * s.Hp), np.float32)
-                for d in range(2):          # Keras order: forward W, U, b, then backward
-                    W, U = [np.asarray(next(it), np.float32) for _ in range(2)]
-                    assert W.shape == (len(rows), 3 * s.H) and U.shape == (s.H, 3 * s.H), \
-                        (W.shape, U.shape)
-                    Wp[rows, d] = _blocks_pad(W, s.H, s.Hp)
-                    Up[d, :s.H] = _blocks_pad(U, s.H, s.Hp)
-                    if s.bn:                # ... W, U, gamma, beta, running_mean, running_std
-                        g, b, rm, rv = [np.asarray(next(it), np.float32).reshape(-1)
-                                        for _ in range(4)]
-                        assert g.shape == (3 * s.H,) and rv.shape == (3 * s.H,), (g.shape, rv.shape)
-                        gp[d] = _blocks_pad(g, s.H, s.Hp)
-                        o = s.orun + d * 3 * s.Hp
-                        run[o:o + 3 * s.Hp] = _blocks_pad(rm, s.H, s.Hp)
-                        o += 6 * s.Hp       # (pad columns: variance 1, like the bn stage's)
-                        real = _blocks_pad(np.ones_like(rv), s.H, s.Hp) > 0
-                        run[o:o + 3 * s.Hp] = np.where(real, _blocks_pad(rv, s.H, s.Hp), 1.0)
-                    else:
-                        b = np.asarray(next(it), np.float32)
-                    bp[d] = _blocks_pad(b, s.H, s.Hp)
-                host[s.oW:s.oW + Wp.size] = Wp.ravel()
-                host[s.oU:s.oU + Up.size] = Up.ravel()
-                if s.bn:
-                    host[s.og:s.og + gp.size] = gp.ravel()
-                    host[s.obeta:s.obeta + bp.size] = bp.ravel()
-                else:
-                    host[s.ob:s.ob + bp.size] = bp.ravel()
-            elif s.kind == 'birhn':
-                rows = self._real_rows(s)
-                Ld, Cb, Wd = s.depth, s.nblk, s.nblk * s.Hp
-                Wp = np.zeros((s.f_in_pad, 2, Wd), np.float32)
-                Up = np.zeros((2, Ld, s.Hp, Wd), np.float32)
-                bp = np.zeros((2, Ld, Wd), np.float32)     # (pad entries stay 0, not -2)
-                for d in range(2):          # per direction: W, U_0 .. U_{L-1}, b_0 .. b_{L-1}
-                    W = np.asarray(next(it), np.float32)
-                    assert W.shape == (len(rows), Cb * s.H), W.shape
-                    Wp[rows, d] = _cblocks_pad(W, s.H, s.Hp, Cb)
-                    for l in range(Ld):
-                        U = np.asarray(next(it), np.float32)
-                        assert U.shape == (s.H, Cb * s.H), U.shape
-                        Up[d, l, :s.H] = _cblocks_pad(U, s.H, s.Hp, Cb)
-                    for l in range(Ld):
-                        bp[d, l] = _cblocks_pad(np.asarray(next(it), np.float32), s.H, s.Hp, Cb)
-                host[s.oW:s.oW + Wp.size] = Wp.ravel()
-                host[s.oU:s.oU + Up.size] = Up.ravel()
-                host[s.ob:s.ob + bp.size] = bp.ravel()
-            elif s.kind == 'bn':            # Keras order: gamma, beta, running_mean, running_std
-                idx = self._bn_cols(s)
-                g, b, rm, rv = [np.asarray(next(it), np.float32).reshape(-1) for _ in range(4)]
-                assert g.shape == (len(idx),) and rv.shape == (len(idx),), (g.shape, rv.shape)
-                for o, v, pad in ((s.og, g, 0.0), (s.obeta, b, 0.0)):
-                    vp = np.full(s.C, pad, np.float32)
-                    vp[idx] = v
-                    host[o:o + s.C] = vp
-                Cp = _pad4(s.C)
-                run[s.orun:s.orun + s.C] = 0.0
-                run[s.orun + Cp:s.orun + Cp + s.C] = 1.0
-                run[s.orun + idx] = rm
-                run[s.orun + Cp + idx] = rv
-        self.params.copy_(torch.from_numpy(host))
-        if self._bn or self._seqbn:
-            self.bn_running.copy_(torch.from_numpy(run))
+        for t, name in zip(tensors, names):
+            P.write(t, bufs[t.buf], next(it), name)
+        self.params.copy_(torch.from_numpy(bufs['params']))
+        self.bn_running.copy_(torch.from_numpy(bufs['running']))
         self._weights_epoch += 1        # (bounds measured under the old weights are dropped)
 
     def _bn_cols(self, s):
         """Physical channels of a BatchNormalization stage that carry real features."""
         return np.arange(s.C) if s.grouped else self._real_rows(s)
+
+    def _bn_views(self, s, n):
+        """(running mean, running variance, moments block) of the n channels of a
+        BatchNormalization stage (n = C) or a GRU(batch_norm=True) stage (n = 6 Hp)."""
+        o = self.n_params + s.omom
+        return (self.bn_running[s.orun:s.orun + n],
+                self.bn_running[s.orun + _pad4(n):s.orun + _pad4(n) + n],
+                self._gbuf[o:o + ops.bn_moments_len(n)])
 
     def _unpack(self, flat, running=None):
         """flat (params / grads / optimiser slots) -> Keras-order arrays.  running: the host copy
@@ -682,83 +374,13 @@ class Model(object):
         None (optimiser slots: trainable weights only)."""
         out = []
         for s in self.stages:
-            if s.kind == 'conv':
-                nw = s.kt * s.kf * s.C_in * s.C_out
-                out += [flat[s.oW:s.oW + nw].reshape(s.kt, s.kf, s.C_in, s.C_out).copy(),
-                        flat[s.ob:s.ob + s.C_out].copy()]
-            elif s.kind == 'dense':
-                rows = self._real_rows(s)
-                W = flat[s.oW:s.oW + s.f_in_pad * s.n_out].reshape(s.f_in_pad, s.n_out)[rows]
-                out += [W.copy(), flat[s.ob:s.ob + s.n_out].copy()]
-            elif s.kind == 'bilstm':
-                rows = self._real_rows(s)
-                Wp = flat[s.oW:s.oW + s.f_in_pad * 8 * s.Hp].reshape(s.f_in_pad, 2, 4 * s.Hp)
-                Up = flat[s.oU:s.oU + 2 * s.Hp * 4 * s.Hp].reshape(2, s.Hp, 4 * s.Hp)
-                if s.ln is not None:
-                    cp = flat[s.ocell:s.ocell + 68 * s.Hp].reshape(2, 34 * s.Hp)
-                    mip = cp[:, :16 * s.Hp].reshape(2, 4, 4 * s.Hp)
-                    bp = mip[:, 3]
-                elif s.mi is None:
-                    bp = flat[s.ob:s.ob + 8 * s.Hp].reshape(2, 4 * s.Hp)
-                else:
-                    mip = flat[s.omi:s.omi + 32 * s.Hp].reshape(2, 4, 4 * s.Hp)
-                    bp = mip[:, 3]
-                for d in range(2):
-                    out += [_um2gm(Wp[rows, d], s.H, s.Hp), _um2gm(Up[d, :s.H], s.H, s.Hp),
-                            _um2gm(bp[d], s.H, s.Hp)]
-                    if s.mi is not None:
-                        out += [_um2gm(mip[d, k], s.H, s.Hp) for k in range(3)]
-                    if s.ln is not None:
-                        H = s.H
-                        out += [_um2gm(cp[d, (16 + 4 * k) * H:(20 + 4 * k) * H], H, H)
-                                for k in range(4)]
-                        out += [cp[d, 32 * H:33 * H].copy(), cp[d, 33 * H:34 * H].copy()]
-            elif s.kind == 'birnn':
-                rows = self._real_rows(s)
-                Wp = flat[s.oW:s.oW + s.f_in_pad * 2 * s.Hp].reshape(s.f_in_pad, 2, s.Hp)
-                Up = flat[s.oU:s.oU + 2 * s.Hp * s.Hp].reshape(2, s.Hp, s.Hp)
-                bp = flat[s.ob:s.ob + 2 * s.Hp].reshape(2, s.Hp)
-                for d in range(2):
-                    out += [Wp[rows, d, :s.H].copy(), Up[d, :s.H, :s.H].copy(),
-                            bp[d, :s.H].copy()]
-            elif s.kind == 'bigru':
-                rows = self._real_rows(s)
-                Wp = flat[s.oW:s.oW + s.f_in_pad * 6 * s.Hp].reshape(s.f_in_pad, 2, 3 * s.Hp)
-                Up = flat[s.oU:s.oU + 2 * s.Hp * 3 * s.Hp].reshape(2, s.Hp, 3 * s.Hp)
-                ob = s.obeta if s.bn else s.ob
-                bp = flat[ob:ob + 6 * s.Hp].reshape(2, 3 * s.Hp)
-                for d in range(2):
-                    out += [_blocks_unpad(Wp[rows, d], s.H, s.Hp),
-                            _blocks_unpad(Up[d, :s.H], s.H, s.Hp)]
-                    if not s.bn:
-                        out.append(_blocks_unpad(bp[d], s.H, s.Hp))
-                        continue
-                    gp = flat[s.og:s.og + 6 * s.Hp].reshape(2, 3 * s.Hp)
-                    out += [_blocks_unpad(gp[d], s.H, s.Hp), _blocks_unpad(bp[d], s.H, s.Hp)]
-                    if isinstance(running, str):
-                        out += [np.zeros(3 * s.H, np.float32), np.zeros(3 * s.H, np.float32)]
-                    elif running is not None:
-                        o = s.orun + d * 3 * s.Hp
-                        out += [_blocks_unpad(running[o + k * 6 * s.Hp:o + k * 6 * s.Hp + 3 * s.Hp],
-                                              s.H, s.Hp) for k in range(2)]
-            elif s.kind == 'birhn':
-                rows = self._real_rows(s)
-                Ld, Cb, Wd = s.depth, s.nblk, s.nblk * s.Hp
-                Wp = flat[s.oW:s.oW + s.f_in_pad * 2 * Wd].reshape(s.f_in_pad, 2, Wd)
-                Up = flat[s.oU:s.oU + 2 * Ld * s.Hp * Wd].reshape(2, Ld, s.Hp, Wd)
-                bp = flat[s.ob:s.ob + 2 * Ld * Wd].reshape(2, Ld, Wd)
-                for d in range(2):
-                    out.append(_cblocks_unpad(Wp[rows, d], s.H, s.Hp, Cb))
-                    out += [_cblocks_unpad(Up[d, l, :s.H], s.H, s.Hp, Cb) for l in range(Ld)]
-                    out += [_cblocks_unpad(bp[d, l], s.H, s.Hp, Cb) for l in range(Ld)]
-            elif s.kind == 'bn':
-                idx = self._bn_cols(s)
-                out += [flat[s.og:s.og + s.C][idx].copy(), flat[s.obeta:s.obeta + s.C][idx].copy()]
-                if isinstance(running, str):
-                    out += [np.zeros(len(idx), np.float32), np.zeros(len(idx), np.float32)]
+            for t in s.tensors:
+                if t.buf == 'params':
+                    out.append(P.read(t, flat))
+                elif isinstance(running, str):
+                    out.append(np.zeros(t.shape, np.float32))
                 elif running is not None:
-                    Cp = _pad4(s.C)
-                    out += [running[s.orun + idx].copy(), running[s.orun + Cp + idx].copy()]
+                    out.append(P.read(t, running))
         return out
 
     def get_weights(self):
@@ -1166,13 +788,11 @@ class Model(object):
         p3 = p.view(T, n_pad, Wd)
         y = self._buf('gzxbn_%d' % Wd, (T, n_pad, Wd))
         gamma, beta = self._view(s.og, Wd), self._view(s.obeta, Wd)
-        rm = self.bn_running[s.orun:s.orun + Wd]
-        rv = self.bn_running[s.orun + Wd:s.orun + 2 * Wd]
+        rm, rv, mom = self._bn_views(s, Wd)
         if not training:
             ops.seqbn_fwd_infer(p3, y, gamma, beta, rm, rv, N, Wd, s.bn_eps)
             return y.view(T, n_pad, 2, 3 * s.Hp)
         stats = self._buf('gbnstats%d' % si, (ops.seqbn_stats_len(Wd),))
-        mom = self._gbuf[self.n_params + s.omom:self.n_params + s.omom + ops.bn_moments_len(Wd)]
         # (data parallel: moments about the running mean, pooled by the gradient all-reduce, as
         # in _bn_forward; the weight |V| is counted on the device, 0 for a zero-weight dummy)
         dist = self._dist_active()
@@ -1274,14 +894,11 @@ class Model(object):
         T, n_pad, ld = a.shape
         y = self._buf('bn%d' % si, a.shape)
         gamma, beta = self._view(s.og, s.C), self._view(s.obeta, s.C)
-        Cp = _pad4(s.C)
-        rm = self.bn_running[s.orun:s.orun + s.C]
-        rv = self.bn_running[s.orun + Cp:s.orun + Cp + s.C]
+        rm, rv, mom = self._bn_views(s, s.C)
         if not training:
             return ops.bn_fwd_infer(a, y, gamma, beta, rm, rv, min(n_real, n_pad), ld, s.C,
                                     s.eps, s.clip)
         stats = self._buf('bnstats%d' % si, (ops.bn_stats_len(s.C),))
-        mom = self._gbuf[self.n_params + s.omom:self.n_params + s.omom + ops.bn_moments_len(s.C)]
         # data parallel the moments are taken about the running mean (the same on every rank),
         # weighted by the rank's real frames, and pooled by the gradient all-reduce
         dist = self._dist_active()
@@ -1298,26 +915,14 @@ class Model(object):
         if not (self._bn or self._seqbn) or not getattr(self, '_acts', None):
             return
         flags = self.veto_flags()
-        for si, s in self._seqbn:       # GRU(batch_norm=True): one channel per column of zx
+        # GRU(batch_norm=True): one channel per column of zx
+        for si, s, n, momentum in ([(si, s, 6 * s.Hp, s.bn_momentum) for si, s in self._seqbn] +
+                                   [(si, s, s.C, s.momentum) for si, s in self._bn]):
             rec = self._acts[si]
             if 'stats' not in rec:
                 continue
-            Wd = 6 * s.Hp
-            mom = self._gbuf[self.n_params + s.omom:self.n_params + s.omom +
-                             ops.bn_moments_len(Wd)]
-            ops.bn_update_running(self.bn_running[s.orun:s.orun + Wd],
-                                  self.bn_running[s.orun + Wd:s.orun + 2 * Wd], mom, Wd,
-                                  s.bn_momentum, shift=rec['shift'], flags=flags)
-        for si, s in self._bn:
-            rec = self._acts[si]
-            if 'stats' not in rec:
-                continue
-            Cp = _pad4(s.C)
-            mom = self._gbuf[self.n_params + s.omom:self.n_params + s.omom +
-                             ops.bn_moments_len(s.C)]
-            ops.bn_update_running(self.bn_running[s.orun:s.orun + s.C],
-                                  self.bn_running[s.orun + Cp:s.orun + Cp + s.C], mom, s.C,
-                                  s.momentum, shift=rec['shift'], flags=flags)
+            rm, rv, mom = self._bn_views(s, n)
+            ops.bn_update_running(rm, rv, mom, n, momentum, shift=rec['shift'], flags=flags)
 
     # The GEMMs around a recurrence (SimpleRNN, GRU, RHN).  G is the gate width of one direction:
     # the rows of zx and of the gate gradient dg hold both directions, 2 G wide, and so do W's.

@@ -116,12 +116,20 @@ def test_keras_layout_writer_roundtrip_and_h5py_view(tmp_path):
     if not h5lite.available():
         pytest.skip('libhdf5 not present')
 
+    from asr_study_amd.core.params import Tensor
+
     class Stage(object):
-        def __init__(self, kind):
+        def __init__(self, kind, layers=(), shapes=()):
             self.kind = kind
+            # (the weights are named from the stage's rows of the parameter table)
+            self.tensors = [Tensor(layer, name, shape, 0, shape, ()) for layer in layers
+                            for name, shape in zip('WUb' if len(shapes) == 3 else 'Wb', shapes)]
+
+    def lstm(f):
+        return Stage('bilstm', ('forward_lstm', 'backward_lstm'), [(f, 16), (4, 16), (16,)])
 
     class Fake(object):
-        stages = [Stage('noise'), Stage('bilstm'), Stage('bilstm'), Stage('dense')]
+        stages = [Stage('noise'), lstm(5), lstm(8), Stage('dense', ('dense',), [(8, 7), (7,)])]
         optimizer = None
         config = {'name': 'brsmv1', 'kwargs': {'num_hiddens': 4}}
 
