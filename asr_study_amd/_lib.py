@@ -217,6 +217,10 @@ SIGNATURES = {
                                 void_p]),
     'asr_ctc_beam_lm_device_counters': (C.c_int, [void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                   C.c_int, void_p, void_p]),
+    'asr_ctc_align_workspace_bytes': (C.c_size_t, [C.c_int] * 5),
+    'asr_ctc_align': (C.c_int, [void_p] * 4 + [C.c_int] * 5 + [void_p, void_p, void_p,
+                                                                C.c_size_t, void_p]),
+    'asr_ctc_align_host': (C.c_int, [void_p] * 4 + [C.c_int] * 5 + [void_p, void_p]),
     'asr_edit_distance_host': (C.c_int, [void_p, void_p, C.c_int, void_p, void_p, C.c_int,
                                          C.c_int, void_p]),
     'asr_optim_workspace_bytes': (C.c_size_t, [C.c_int64]),

@@ -67,6 +67,16 @@ PREDICT_FLAGS = [
     ('--override', dict(default=False, action='store_true')),
     ('--beam_width', dict(default=400, type=int)),
 ] + _LM_FLAGS
+ALIGN_FLAGS = [
+    ('--model', dict(required=True, type=str)),
+    ('--dataset', dict(default=None, type=str)),
+    ('--file', dict(default=None, type=str)),
+    ('--text', dict(default=None, type=str)),            # the transcript of --file
+    ('--subset', dict(type=str, default='test')),
+] + _PLUGIN_FLAGS + _DEVICE_FLAGS + [
+    ('--save', dict(default=None, type=str)),            # JSON lines, one utterance per line
+    ('--override', dict(default=False, action='store_true')),
+]
 MAKE_LM_FLAGS = [
     ('--dataset', dict(default=None, type=str)),
     ('--subset', dict(type=str, default='train')),
@@ -284,6 +294,72 @@ def predict_main(argv=None):
                                                for r in results],
                                attrs={'num_labels': int(results[0]['best'].shape[-1])})
             f.write_strings('labels', [str(r['label']) for r in results])
+    return results
+
+
+# ------------------------------------------------------------------ align
+def align_main(argv=None):
+    """align.py: where in its utterance each character of a KNOWN transcript lies (CTC forced
+    alignment, Model.align), for a dataset split (its stored transcripts) or one audio file with
+    ``--text``.  One utterance per forward pass, as predict.py.  Each result -- and each line of
+    ``--save`` (JSON lines) -- holds ``label`` (the transcript), ``score`` (log-probability of
+    the alignment) and ``chars``: per character ``char``, ``label`` (class id), ``start_frame`` /
+    ``end_frame`` (exclusive) in frames of the network's output and ``start`` / ``end`` in seconds
+    (frame x ``time_stride`` x the feature extractor's ``win_step``; null when the input parser
+    has none)."""
+    import json
+    import numpy as np
+    parser = make_parser('Aligning transcripts with an ASR system.', ALIGN_FLAGS)
+    args = parser.parse_args(argv)
+    if args.dataset is None and args.file is None:
+        raise ValueError('dataset or file args must be set.')
+    if args.dataset and args.file:
+        print('Both dataset and file args was set. Ignoring file args.')
+    if args.dataset is None and args.text is None:
+        raise ValueError('text arg must be set with file.')
+    if args.save is not None and os.path.exists(args.save) and not args.override:
+        raise IOError('Unable to create file')
+    explicit = utils.parse_nondefault_args(args, parser.parse_args(['--model', args.model]), argv)
+    from .datasets.dataset_generator import DatasetGenerator, DatasetIterator
+    from .utils.core_utils import setup_gpu, load_model
+    setup_gpu(args.gpu, args.allow_growth)
+    model, meta = load_model(args.model, return_meta=True, mode='predict', decoder=False)
+    stored = {k: v for k, v in meta['training_args'].items()
+              if k in ('input_parser', 'input_parser_params', 'label_parser',
+                       'label_parser_params')}
+    args = merged_args(args, stored, explicit)
+    feature, labels = resolve_plugins(args)
+    if args.dataset is not None:
+        flow = DatasetGenerator(feature, labels, batch_size=1, seed=0, mode='predict',
+                                shuffle=False).flow_from_fname(args.dataset, datasets=args.subset)
+        truth = list(flow.labels[list(range(flow.len))])
+    else:
+        flow = DatasetIterator(np.array([args.file]), None, input_parser=feature,
+                               label_parser=labels, mode='predict', shuffle=False, batch_size=1)
+        truth = [args.text]
+    truth = [t.decode('utf-8') if isinstance(t, bytes) else str(t) for t in truth]
+    win_step = getattr(feature, 'win_step', None)
+    results = []
+    for index in range(flow.len):
+        x, lens = flow.next()
+        ids = labels(truth[index])
+        out = model.align(x, [ids], lens)
+        stride, al = out['time_stride'], out['alignments'][0]
+        chars = []
+        for q, lab, lo, hi in al['segments']:
+            chars.append({'char': labels.imap([lab]), 'label': int(lab), 'start_frame': int(lo),
+                          'end_frame': int(hi),
+                          'start': None if win_step is None else float(lo * stride * win_step),
+                          'end': None if win_step is None else float(hi * stride * win_step)})
+        results.append({'label': truth[index], 'score': al['score'], 'time_stride': stride,
+                        'chars': chars})
+        print('%s  (log p = %.3f)' % (labels._sanitize(truth[index]), al['score']))
+        print('   ' + ' '.join('%s[%d:%d]' % (c['char'], c['start_frame'], c['end_frame'])
+                               for c in chars) + '\n')
+    if args.save is not None:
+        with open(args.save, 'w') as f:
+            for r in results:
+                f.write(json.dumps(r) + '\n')
     return results
 
 

@@ -86,6 +86,41 @@ def ctc_lambda_func(args):
         torch.as_tensor(np.asarray(inputs_length, np.int32).reshape(-1)).to(dev), N)
 
 
+def _pack_labels(labels):
+    lmax = max([len(l) for l in labels] + [1])
+    lab = np.zeros((len(labels), lmax), np.int32)
+    for n, l in enumerate(labels):
+        lab[n, :len(l)] = np.asarray(l, np.int32).reshape(-1)
+    return lab, np.array([len(l) for l in labels], np.int32)
+
+
+def align_paths(y_pred, lab, lab_len, seq_len, N):
+    """K19 on whichever side the logits are: the device kernel for a CUDA slab, the library's
+    host form otherwise.  -> (path (N, T), score (N,)) numpy arrays."""
+    if y_pred.is_cuda:
+        dev = y_pred.device
+        path, score = ops.ctc_align(y_pred, torch.as_tensor(lab).to(dev),
+                                    torch.as_tensor(lab_len).to(dev),
+                                    torch.as_tensor(seq_len).to(dev), N)
+        return path.cpu().numpy(), score.cpu().numpy()
+    lab, lab_len, seq_len = [a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+                             for a in (lab, lab_len, seq_len)]
+    return ops.ctc_align_host(y_pred.detach().numpy(), lab, lab_len, seq_len, N)
+
+
+def align(args):
+    """(y_pred slab (T, n_pad, C), labels list, inputs_length) -> list of N (segments, score):
+    the most probable CTC alignment of each KNOWN transcript, as ops.ctc_segments entries
+    (label_index, label, start_frame, end_frame_exclusive) and its natural-log probability
+    ([] and -inf for a transcript that does not fit its frames)."""
+    y_pred, labels, inputs_length = args
+    N = len(labels)
+    lab, lab_len = _pack_labels(labels)
+    seq = np.asarray(inputs_length, np.int32).reshape(-1)
+    path, score = align_paths(y_pred, lab, lab_len, seq, N)
+    return [(ops.ctc_segments(path[n], labels[n]), float(score[n])) for n in range(N)]
+
+
 def ctc_dummy_loss(y_true, y_pred):
     """Keras needed a loss callable; the model output already IS the loss."""
     return y_pred

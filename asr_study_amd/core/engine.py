@@ -1911,6 +1911,28 @@ class Model(object):
         dec, dlen = dec.cpu().numpy(), dlen.cpu().numpy()
         return [dec[n, :dlen[n]].tolist() for n in range(N)]
 
+    def align(self, x, labels, inputs_length):
+        """Forced alignment (K19): where in its utterance each label of a KNOWN transcript lies.
+        ``x`` as predict takes it, ``labels`` a list of label lists, ``inputs_length`` in input
+        frames.  A transcript too long for its utterance raises the ValueError training raises.
+        Returns {'alignments': [{'segments': [(label_index, label, start, end_exclusive), ...],
+        'score': log-probability of the path, 'path': lattice state per logit frame}, ...],
+        'time_stride': input frames per logit frame}; segment bounds are in LOGIT frames."""
+        if isinstance(x, tuple) and x[0] == 'slab':
+            x = x[1]
+        slab = x if (torch.is_tensor(x) and x.dim() == 3 and x.shape[1] % 16 == 0) else self.to_slab(x)
+        labels = [np.asarray(l).reshape(-1) for l in labels]
+        N = len(labels)
+        lens = np.asarray(inputs_length).reshape(-1)
+        lab, lab_len, sl = self._prep_labels(labels, lens, slab.shape[0])
+        logits = self.forward(slab, training=False, need_grad=False, n_valid=N)
+        from .ctc_utils import align_paths
+        path, score = align_paths(logits, lab, lab_len, sl, N)
+        sl_h = sl.cpu().numpy()
+        out = [{'segments': ops.ctc_segments(path[n], labels[n]), 'score': float(score[n]),
+                'path': path[n, :int(sl_h[n])].tolist()} for n in range(N)]
+        return {'alignments': out, 'time_stride': int(np.prod(self.time_strides or [1]))}
+
     def _beam(self, logits, seq_len_dev, N):
         """core/ctc_utils.py:48-50 (K9): the library's host decoder (decode_host.cpp: one
         utterance per host thread, on a copy of the logits) or the device decoder (beam.hip: the

@@ -158,6 +158,31 @@ struct CtcLane {
       sl[p] = valid[p] ? lse2_b2(xl[p], yn) : kNegInf;
     }
   }
+  // K19: the max-plus twin of alpha_step -- v_t from v_{t-1} with the emissions of frame t, same
+  // single wave shift, compares where alpha_step has log-sum-exps.  Returns the lane's
+  // back-pointers, 4 bits per pair: bits 4p..4p+1 the move into the blank state (0 stay, 1 from
+  // the previous label), bits 4p+2..4p+3 the move into the label state (0 stay, 1 from its blank,
+  // 2 the skip from the previous label).  A strict > keeps the smaller move on equal values.
+  __device__ __forceinline__ unsigned viterbi_step(float (&sb)[PPL], float (&sl)[PPL], float eb,
+                                                   const float (&el)[PPL]) const {
+    const float lprev = wave_shift_up(sl[PPL - 1], kNegInf);
+    float nsb[PPL], nsl[PPL];
+    unsigned w = 0;
+#pragma unroll
+    for (int p = 0; p < PPL; ++p) {
+      const float lp1 = (p == 0) ? lprev : sl[p - 1];
+      const bool b1 = lp1 > sb[p];
+      nsb[p] = fmaxf(sb[p], lp1) + eb;
+      const bool l1 = sb[p] > sl[p];
+      const float m1 = fmaxf(sl[p], sb[p]);
+      const bool l2 = diffp[p] && lp1 > m1;
+      nsl[p] = (l2 ? lp1 : m1) + (valid[p] ? el[p] : kNegInf);
+      w |= ((b1 ? 1u : 0u) | (l2 ? 8u : (l1 ? 4u : 0u))) << (4 * p);
+    }
+#pragma unroll
+    for (int p = 0; p < PPL; ++p) { sb[p] = nsb[p]; sl[p] = nsl[p]; }
+    return w;
+  }
   __device__ __forceinline__ static void recentre(float (&sb)[PPL], float (&sl)[PPL], double* off) {
     float m = kNegInf;
 #pragma unroll
@@ -514,6 +539,155 @@ ctc_greedy_kernel(const float* __restrict__ logits, const int* __restrict__ seq_
   if (tid == 0) decoded_len[n] = total;
 }
 
+// ---------------------------------------------------------------------------
+// K19 forced alignment.  The forward pass is the alpha chain in the (max, +) semiring: same
+// lane geometry, same prefetch groups, one re-centring per group (so comparisons are taken on
+// O(10) values, the removed amount summed in float64), and per frame ONE coalesced store of the
+// lanes' back-pointer words (4 PPL bits each: 64 / 64 / 128 / 256 bytes per frame and utterance
+// at PPL 1 / 2 / 4 / 8).  The backtrace is a second one-wave-per-utterance kernel.
+template <int PPL> struct BpWord { typedef uint32_t type; };
+template <> struct BpWord<1> { typedef uint8_t type; };
+template <> struct BpWord<2> { typedef uint8_t type; };
+template <> struct BpWord<4> { typedef uint16_t type; };
+
+template <int PPL>
+__global__ void __launch_bounds__(64)
+ctc_viterbi_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
+                   const int* __restrict__ labels, const int* __restrict__ label_len,
+                   const int* __restrict__ seq_len, int T, int N, int n_pad, int C, int l_max,
+                   typename BpWord<PPL>::type* __restrict__ bp, int* __restrict__ end_state,
+                   float* __restrict__ score) {
+  typedef typename BpWord<PPL>::type W;
+  constexpr int UNR = PPL == 1 ? 16 : (PPL == 2 ? 8 : 4);
+  const int lane = threadIdx.x;
+  const int n = blockIdx.x;
+  const int blank = C - 1;
+  int L = label_len[n];
+  L = L < 0 ? 0 : (L > l_max ? l_max : L);      // (the end state below indexes fin[] with it)
+  int Tn = seq_len[n];
+  Tn = Tn < 1 ? 1 : (Tn > T ? T : Tn);
+  __shared__ float fin[2 * 64 * PPL];
+  CtcLane<PPL> ln;
+  ln.init(labels, n, l_max, L, C, lane);
+
+  float sb[PPL], sl[PPL];
+#pragma unroll
+  for (int p = 0; p < PPL; ++p) { sb[p] = kNegInf; sl[p] = kNegInf; }
+  if (lane == 0) sb[0] = 0.f;     // virtual state before t = 0: "blank 0", as in the alpha chain
+  double off = 0.0;
+
+  const size_t row_stride = (size_t)n_pad * C;
+  const float* lg_n = logits + (size_t)n * C;
+  const float* lse_n = lse + n;
+  W* bp_n = bp + (size_t)n * T * 64 + lane;
+  const int ngroups = (Tn + UNR - 1) / UNR;
+  float eb[UNR], el[UNR][PPL];
+  auto load_group = [&](int g, float (&b)[UNR], float (&l)[UNR][PPL]) {
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      int t = g * UNR + u; t = t < Tn ? t : Tn - 1;
+      const float* r = lg_n + (size_t)t * row_stride;
+      const float ls = lse_n[(size_t)t * n_pad];
+      b[u] = (r[blank] - ls) * kLog2e;
+#pragma unroll
+      for (int p = 0; p < PPL; ++p) l[u][p] = (r[ln.lab[p]] - ls) * kLog2e;
+    }
+  };
+  load_group(0, eb, el);
+  for (int g = 0; g < ngroups; ++g) {
+    float nb[UNR], nl[UNR][PPL];
+    load_group(g + 1 < ngroups ? g + 1 : g, nb, nl);
+    CtcLane<PPL>::recentre(sb, sl, &off);
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int t = g * UNR + u;
+      if (t < Tn) bp_n[(size_t)t * 64] = (W)ln.viterbi_step(sb, sl, eb[u], el[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      eb[u] = nb[u];
+#pragma unroll
+      for (int p = 0; p < PPL; ++p) el[u][p] = nl[u][p];
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < PPL; ++p) {
+    fin[2 * (lane * PPL + p)] = sb[p];
+    fin[2 * (lane * PPL + p) + 1] = sl[p];
+  }
+  __syncthreads();
+  if (lane == 0) {
+    const float e1 = fin[2 * L];                                // final blank
+    const float e2 = L > 0 ? fin[2 * (L - 1) + 1] : kNegInf;    // last label
+    const bool last_blank = e1 >= e2;
+    const float best = last_blank ? e1 : e2;
+    end_state[n] = best > kNegInf ? (last_blank ? 2 * L : 2 * L - 1) : -1;
+    score[n] = best > kNegInf ? (float)(((double)best + off) * kLn2) : kNegInf;
+  }
+}
+
+// Backtrace, one wave per utterance.  The walk is one dependent read per frame; instead of
+// chasing it through global memory the whole wave stages kBtG frames of back-pointer words
+// (kBtG coalesced rows) into LDS, the next group's rows already in flight in registers, lane 0
+// walks the group out of LDS, and the wave writes that stretch of the path with one store.
+constexpr int kBtG = 64;
+
+template <int PPL>
+__global__ void __launch_bounds__(64)
+ctc_backtrace_kernel(const typename BpWord<PPL>::type* __restrict__ bp,
+                     const int* __restrict__ end_state, const int* __restrict__ seq_len,
+                     int T, int* __restrict__ path) {
+  typedef typename BpWord<PPL>::type W;
+  const int lane = threadIdx.x;
+  const int n = blockIdx.x;
+  int Tn = seq_len[n];
+  Tn = Tn < 1 ? 1 : (Tn > T ? T : Tn);
+  int* path_n = path + (size_t)n * T;
+  const int s_end = end_state[n];
+  const int t_done = s_end < 0 ? 0 : Tn;          // no alignment: the whole row is -1
+  for (int t = t_done + lane; t < T; t += 64) path_n[t] = -1;
+  if (s_end < 0) return;
+  __shared__ W rows[kBtG * 64];
+  __shared__ int pth[kBtG];
+  __shared__ int s_cur;
+  const W* bp_n = bp + (size_t)n * T * 64 + lane;
+  const int ngroups = (Tn + kBtG - 1) / kBtG;
+  W regs[kBtG];
+  auto load_group = [&](int g) {
+#pragma unroll
+    for (int j = 0; j < kBtG; ++j) {
+      int t = g * kBtG + j; t = t < Tn ? t : Tn - 1;
+      regs[j] = bp_n[(size_t)t * 64];
+    }
+  };
+  if (lane == 0) s_cur = s_end;
+  load_group(ngroups - 1);
+  for (int g = ngroups - 1; g >= 0; --g) {
+#pragma unroll
+    for (int j = 0; j < kBtG; ++j) rows[j * 64 + lane] = regs[j];
+    if (g > 0) load_group(g - 1);
+    __syncthreads();
+    const int lo = g * kBtG;
+    const int hi = lo + kBtG < Tn ? lo + kBtG : Tn;
+    if (lane == 0) {
+      int s = s_cur;
+      for (int t = hi - 1; t >= lo; --t) {
+        pth[t - lo] = s;
+        const int q = s >> 1;
+        const unsigned w = rows[(t - lo) * 64 + q / PPL];
+        const int mv = (int)((w >> (4 * (q % PPL) + 2 * (s & 1))) & 3u);
+        // (the word of frame 0 is the move out of the virtual start state: not a move)
+        s = t > 0 ? s - mv : s;
+        s = s < 0 ? 0 : s;
+      }
+      s_cur = s;
+    }
+    __syncthreads();
+    if (lo + lane < hi) path_n[lo + lane] = pth[lane];
+    __syncthreads();
+  }
+}
+
 int pick_ppl(int l_max) {
   const int pairs = l_max + 1;
   if (pairs <= 64) return 1;
@@ -612,6 +786,71 @@ extern "C" int asr_ctc_greedy(const float* logits, const int* seq_len, int T, in
   ASR_CHECK_ARG(T > 0 && N > 0 && n_pad >= N && C >= 2, "greedy: bad shape");
   hipLaunchKernelGGL(ctc_greedy_kernel, dim3(N), dim3(256), 0, stream, logits, seq_len,
                      T, N, n_pad, C, decoded, decoded_len);
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// K19 host entry points.  Workspace: one lse per frame, the end state per utterance, the
+// back-pointer words (N x T x 64 words of 1 / 1 / 2 / 4 bytes at PPL 1 / 2 / 4 / 8); every byte
+// that is read has been written by this call.
+namespace {
+size_t align_bp_word_bytes(int ppl) { return ppl <= 2 ? 1 : (ppl == 4 ? 2 : 4); }
+}  // namespace
+
+extern "C" size_t asr_ctc_align_workspace_bytes(int T, int N, int n_pad, int C, int l_max) {
+  const int ppl = pick_ppl(l_max);
+  if (ppl == 0 || T <= 0 || N <= 0) return 0;
+  (void)C;
+  const int n_pad16 = n_pad > N ? n_pad : N;
+  return asr_align_up((size_t)T * n_pad16 * sizeof(float), 256) +
+         asr_align_up((size_t)N * sizeof(int), 256) +
+         asr_align_up((size_t)N * T * 64 * align_bp_word_bytes(ppl), 256);
+}
+
+extern "C" int asr_ctc_align(const float* logits, const int* labels, const int* label_len,
+                             const int* seq_len, int T, int N, int n_pad, int C, int l_max,
+                             int* path, float* score, void* workspace, size_t ws_bytes,
+                             asr_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ASR_CHECK_ARG(logits && labels && label_len && seq_len && path && score,
+                "ctc align: null pointer");
+  ASR_CHECK_ARG(T > 0 && N > 0 && n_pad >= N && C >= 2 && l_max >= 1,
+                "ctc align: bad shape T=%d N=%d n_pad=%d C=%d l_max=%d", T, N, n_pad, C, l_max);
+  const int ppl = pick_ppl(l_max);
+  ASR_CHECK_ARG(ppl != 0, "ctc align: l_max=%d unsupported (max 511)", l_max);
+  const size_t need = asr_ctc_align_workspace_bytes(T, N, n_pad, C, l_max);
+  if (!workspace || ws_bytes < need) {
+    asr_set_error("ctc align: workspace %zu < %zu bytes", ws_bytes, need);
+    return ASR_ERR_WORKSPACE;
+  }
+  char* wsb = reinterpret_cast<char*>(workspace);
+  float* lse = reinterpret_cast<float*>(wsb);
+  const size_t lse_bytes = asr_align_up((size_t)T * n_pad * sizeof(float), 256);
+  int* end_state = reinterpret_cast<int*>(wsb + lse_bytes);
+  void* bp = wsb + lse_bytes + asr_align_up((size_t)N * sizeof(int), 256);
+  const int rows = T * n_pad;
+  hipLaunchKernelGGL(ctc_lse_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, logits, lse,
+                     rows, C);
+  ASR_CHECK_LAUNCH();
+#define LAUNCH_V(P)                                                                          \
+  do {                                                                                       \
+    typedef BpWord<P>::type W;                                                               \
+    hipLaunchKernelGGL(ctc_viterbi_kernel<P>, dim3(N), dim3(64), 0, stream, logits, lse,     \
+                       labels, label_len, seq_len, T, N, n_pad, C, l_max,                    \
+                       reinterpret_cast<W*>(bp), end_state, score);                          \
+    ASR_CHECK_LAUNCH();                                                                      \
+    hipLaunchKernelGGL(ctc_backtrace_kernel<P>, dim3(N), dim3(64), 0, stream,                \
+                       reinterpret_cast<const W*>(bp), (const int*)end_state, seq_len, T,    \
+                       path);                                                                \
+  } while (0)
+  switch (ppl) {
+    case 1: LAUNCH_V(1); break;
+    case 2: LAUNCH_V(2); break;
+    case 4: LAUNCH_V(4); break;
+    default: LAUNCH_V(8); break;
+  }
+#undef LAUNCH_V
   ASR_CHECK_LAUNCH();
   return ASR_OK;
 }

@@ -293,3 +293,92 @@ extern "C" int asr_edit_distance_host(const int* hyp, const int* hyp_len, int hy
   }
   return ASR_OK;
 }
+
+// ---------------------------------------------------------------------------
+// K19 forced alignment, host form: the recursion and the tie rule of ctc.hip's Viterbi kernel
+// in plain float32 (natural log; each emission is logit - log-sum-exp of its frame, the
+// log-sum-exp taken in double), a byte per back-pointer, one utterance per host thread.
+namespace {
+void align_one(const float* logits, size_t row_stride, int T, int Tn, int C, const int* lab_raw,
+               int L, int* path, float* score) {
+  const float ninf = -std::numeric_limits<float>::infinity();
+  const int blank = C - 1;
+  const int S = 2 * L + 1;
+  std::vector<int> cls(S, blank);                // class of every lattice state
+  std::vector<char> skip(S, 0);                  // the move -2 into this state is legal
+  for (int q = 0; q < L; ++q) {
+    const int l = lab_raw[q];
+    cls[2 * q + 1] = (l < 0 || l >= C) ? blank : l;      // (as CtcLane::init)
+    skip[2 * q + 1] = q >= 1 && l != lab_raw[q - 1];
+  }
+  std::vector<float> v(S, ninf), nv(S), e(C);
+  std::vector<unsigned char> bp((size_t)Tn * S, 0);
+  for (int t = 0; t < Tn; ++t) {
+    const float* x = logits + (size_t)t * row_stride;
+    double mx = x[0];
+    for (int c = 1; c < C; ++c) mx = std::max(mx, (double)x[c]);
+    double sum = 0.0;
+    for (int c = 0; c < C; ++c) sum += std::exp((double)x[c] - mx);
+    const double lse_t = mx + std::log(sum);
+    for (int c = 0; c < C; ++c) e[c] = (float)((double)x[c] - lse_t);
+    if (t == 0) {
+      v[0] = e[cls[0]];
+      if (S > 1) v[1] = e[cls[1]];
+      continue;
+    }
+    unsigned char* b = bp.data() + (size_t)t * S;
+    for (int s = 0; s < S; ++s) {
+      float m = v[s];
+      unsigned char k = 0;
+      if (s >= 1 && v[s - 1] > m) { m = v[s - 1]; k = 1; }
+      if (skip[s] && v[s - 2] > m) { m = v[s - 2]; k = 2; }
+      nv[s] = m + e[cls[s]];
+      b[s] = k;
+    }
+    v.swap(nv);
+  }
+  for (int t = 0; t < T; ++t) path[t] = -1;
+  const float e1 = v[S - 1], e2 = L > 0 ? v[S - 2] : ninf;
+  const bool last_blank = e1 >= e2;
+  const float best = last_blank ? e1 : e2;
+  *score = best;
+  if (!(best > ninf)) return;
+  int s = last_blank ? S - 1 : S - 2;
+  for (int t = Tn - 1; t >= 0; --t) {
+    path[t] = s;
+    if (t > 0) s -= bp[(size_t)t * S + s];
+  }
+}
+}  // namespace
+
+extern "C" int asr_ctc_align_host(const float* logits_host, const int* labels,
+                                  const int* label_len, const int* seq_len, int T, int N,
+                                  int n_pad, int C, int l_max, int* path, float* score) {
+  ASR_CHECK_ARG(logits_host && labels && label_len && seq_len && path && score,
+                "ctc align: null pointer");
+  ASR_CHECK_ARG(T > 0 && N > 0 && n_pad >= N && C >= 2 && l_max >= 1,
+                "ctc align: bad shape T=%d N=%d n_pad=%d C=%d l_max=%d", T, N, n_pad, C, l_max);
+  ASR_CHECK_ARG(l_max <= 511, "ctc align: l_max=%d unsupported (max 511)", l_max);
+  const size_t row_stride = (size_t)n_pad * C;
+  unsigned hw = std::thread::hardware_concurrency();
+  int nthreads = (int)std::min<unsigned>(hw ? hw : 1, (unsigned)N);
+  if (nthreads < 1) nthreads = 1;
+  auto work = [&](int tid) {
+    for (int n = tid; n < N; n += nthreads) {
+      int Tn = seq_len[n];
+      Tn = Tn < 1 ? 1 : (Tn > T ? T : Tn);
+      int L = label_len[n];
+      L = L < 0 ? 0 : (L > l_max ? l_max : L);
+      align_one(logits_host + (size_t)n * C, row_stride, T, Tn, C, labels + (size_t)n * l_max, L,
+                path + (size_t)n * T, score + n);
+    }
+  };
+  if (nthreads == 1) {
+    work(0);
+  } else {
+    std::vector<std::thread> pool;
+    for (int i = 0; i < nthreads; ++i) pool.emplace_back(work, i);
+    for (auto& th : pool) th.join();
+  }
+  return ASR_OK;
+}

@@ -692,6 +692,99 @@ def ctc_greedy(logits, seq_len, N):
     return dec, dlen
 
 
+def _check_align_labels(labels, label_len, N, Cc):
+    """Host-side argument checks of ctc_align / ctc_align_host (numpy views of the labels)."""
+    if labels.ndim != 2 or labels.shape[0] < N or labels.shape[1] < 1 or len(label_len) < N:
+        raise ValueError('ctc_align: labels must be (N, l_max >= 1) with N label lengths, got %s '
+                         'and %d lengths for N = %d' % (tuple(labels.shape), len(label_len), N))
+    if N and (label_len[:N].min() < 0 or label_len[:N].max() > labels.shape[1]):
+        raise ValueError('ctc_align: label lengths must lie in [0, %d]' % labels.shape[1])
+    used = np.arange(labels.shape[1])[None, :] < label_len[:N, None]
+    bad = used & ((labels[:N] < 0) | (labels[:N] > Cc - 2))
+    if bad.any():
+        n, q = np.argwhere(bad)[0]
+        raise ValueError('ctc_align: label %d of utterance %d is %d, outside [0, %d] (the blank '
+                         'is %d)' % (q, n, labels[n, q], Cc - 2, Cc - 1))
+
+
+def ctc_align(logits, labels, label_len, seq_len, N):
+    """K19 forced alignment on the device (asr_ctc_align).  logits (T, n_pad, C) float32, labels
+    (N, l_max) int32, label_len / seq_len (N,) int32, all DEVICE tensors as ctc_loss_grad takes
+    them -> (path (N, T) int32, score (N,) float32) device tensors: path[n, t] is the state of
+    the CTC lattice at frame t (even: a blank, odd s: label (s - 1) // 2), -1 past seq_len[n] and
+    on the whole row when the transcript does not fit; score is the natural-log probability of
+    the path (-inf then).  Labels outside [0, C - 2] raise ValueError."""
+    lib = L.load()
+    T, n_pad, Cc = logits.shape
+    N = int(N)
+    _check_f32(logits)
+    _check_align_labels(labels.cpu().numpy(), label_len.cpu().numpy(), N, Cc)
+    l_max = int(labels.shape[1])
+    dev = logits.device
+    labels = labels.to(dev, torch.int32).contiguous()
+    label_len = label_len.to(dev, torch.int32).contiguous()
+    seq_len = seq_len.to(dev, torch.int32).contiguous()
+    path = torch.empty((N, T), dtype=torch.int32, device=dev)
+    score = torch.empty(N, dtype=torch.float32, device=dev)
+    nbytes = lib.asr_ctc_align_workspace_bytes(T, N, n_pad, Cc, l_max)
+    key = ('ctc_align', str(dev))
+    ws = WS.bufs.get(key)                       # (never read before it is written: no zero fill)
+    if ws is None or ws.numel() < nbytes:
+        ws = WS.bufs[key] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+    L.check(lib.asr_ctc_align(_ptr(logits), _ptr(labels), _ptr(label_len), _ptr(seq_len), T, N,
+                              n_pad, Cc, l_max, _ptr(path), _ptr(score), _ptr(ws), nbytes,
+                              _stream()), 'asr_ctc_align')
+    return path, score
+
+
+def ctc_align_host(logits_host, labels, label_len, seq_len, N):
+    """ctc_align on the host (asr_ctc_align_host: float32, one utterance per host thread): numpy
+    arrays in, (path (N, T) int32, score (N,) float32) numpy arrays out."""
+    lib = L.load()
+    logits_host = np.ascontiguousarray(logits_host, dtype=np.float32)
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    label_len = np.ascontiguousarray(label_len, dtype=np.int32).reshape(-1)
+    seq = np.ascontiguousarray(seq_len, dtype=np.int32).reshape(-1)
+    if logits_host.ndim != 3:
+        raise ValueError('ctc_align_host: logits must be (T, n_pad, C)')
+    T, n_pad, Cc = logits_host.shape
+    N = int(N)
+    _check_align_labels(labels, label_len, N, Cc)
+    if len(seq) < N:
+        raise ValueError('ctc_align_host: %d sequence lengths for N = %d' % (len(seq), N))
+    path = np.empty((N, T), dtype=np.int32)
+    score = np.empty(N, dtype=np.float32)
+    as_p = lambda a: a.ctypes.data_as(C.c_void_p)
+    L.check(lib.asr_ctc_align_host(as_p(logits_host), as_p(labels), as_p(label_len), as_p(seq), T,
+                                   N, n_pad, Cc, int(labels.shape[1]), as_p(path), as_p(score)),
+            'asr_ctc_align_host')
+    return path, score
+
+
+def ctc_segments(path_row, labels_row):
+    """One row of an alignment path -> [(label_index, label, start_frame, end_frame_exclusive)],
+    one entry per label of the transcript, in order; blank frames belong to no entry.  A row of
+    -1 (no alignment) gives []; a path that does not spell ``labels_row`` raises ValueError."""
+    path_row = np.asarray(path_row).reshape(-1)
+    labels_row = [int(l) for l in np.asarray(labels_row).reshape(-1)]
+    segs = []
+    for t, s in enumerate(path_row.tolist()):
+        if s < 0:
+            break
+        if s & 1:
+            q = (s - 1) // 2
+            if segs and segs[-1][0] == q and segs[-1][3] == t:
+                segs[-1][3] = t + 1
+            else:
+                segs.append([q, labels_row[q] if q < len(labels_row) else -1, t, t + 1])
+    if not segs and (len(path_row) == 0 or path_row[0] < 0):
+        return []
+    if [g[0] for g in segs] != list(range(len(labels_row))):
+        raise ValueError('ctc_segments: the path visits labels %s, the transcript has %d'
+                         % ([g[0] for g in segs], len(labels_row)))
+    return [tuple(g) for g in segs]
+
+
 def ctc_beam_search(logits, seq_len, N, beam_width=100, merge_repeated=True):
     """K9 on the device: logits (T, n_pad, C) float32 and seq_len (N,) int32 DEVICE tensors ->
     (decoded (N, T) int32 padded with -1, decoded_len (N,), log_score (N,)) device tensors; same

@@ -742,6 +742,23 @@ int asr_ctc_beam_lm_device(const float* logits, const int* seq_len, int T, int N
 int asr_ctc_beam_lm_device_counters(const void* workspace, int T, int N, int C, int beam_width,
                                     int utterance, long long* out7, asr_stream_t stream);
 
+/* K19 CTC forced alignment: the most probable alignment of a KNOWN transcript (Viterbi over   */
+/* the CTC lattice of 2 L + 1 states: even s a blank, odd s label (s - 1) / 2; moves 0, 1, and  */
+/* 2 onto a label that differs from the previous one; end state 2 L or 2 L - 1).  Arguments as  */
+/* asr_ctc_loss_grad (blank = C - 1, seq_len clamped to [1, T], l_max <= 511).  path (N, T)     */
+/* int32: the lattice state of every frame t < seq_len[n], -1 beyond it and on the whole row    */
+/* when no alignment exists; score (N): natural-log probability of that path, -inf when none.  */
+/* Ties: the smaller move wins (stay, then 1, then 2), and state 2 L ends the path when it is   */
+/* at least as good as 2 L - 1.  The workspace need not be initialised.  The host form takes    */
+/* HOST pointers throughout and computes in float32, one utterance per host thread.            */
+size_t asr_ctc_align_workspace_bytes(int T, int N, int n_pad, int C, int l_max);
+int asr_ctc_align(const float* logits, const int* labels, const int* label_len,
+                  const int* seq_len, int T, int N, int n_pad, int C, int l_max, int* path,
+                  float* score, void* workspace, size_t ws_bytes, asr_stream_t stream);
+int asr_ctc_align_host(const float* logits_host, const int* labels, const int* label_len,
+                       const int* seq_len, int T, int N, int n_pad, int C, int l_max,
+                       int* path, float* score);
+
 /* K10 Edit distance (host).  Replaces core/metrics.py:8 -> tf.edit_distance */
 /* (normalize=True).  Ragged inputs as (N, max) padded + lengths.            */
 int asr_edit_distance_host(const int* hyp, const int* hyp_len, int hyp_ld,
