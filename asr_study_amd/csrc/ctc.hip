@@ -214,7 +214,8 @@ ctc_alpha_beta_kernel(const float* __restrict__ logits, const float* __restrict_
   const int n = do_beta ? (blockIdx.x >> 1) : blockIdx.x;
   const int dir = do_beta ? (blockIdx.x & 1) : 0;
   const int blank = C - 1;
-  const int L = label_len[n];
+  int L = label_len[n];
+  L = L < 0 ? 0 : (L > l_max ? l_max : L);      // (fin[] and the labels row are indexed with it)
   int Tn = seq_len[n];
   Tn = Tn < 1 ? 1 : (Tn > T ? T : Tn);
   const int SP = 2 * 64 * PPL;
@@ -371,6 +372,7 @@ ctc_grad_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
     Tn = Tn < 1 ? 1 : (Tn > T ? T : Tn);
     active = t < Tn;
     L = label_len[n];
+    L = L < 0 ? 0 : (L > l_max ? l_max : L);    // as in the chains: the same lattice
     const double lz = logz[n];
     if (!(lz > -1.0e300)) active = false;    // infeasible target: zero gradient
   }

@@ -111,6 +111,35 @@ def test_brsmv1_small_forward_backward_adam(H, wd, use_masks):
         assert report('weights ' + name, b, a) < 5e-5, name
 
 
+def test_brsmv1_labels_wider_than_one_state_pair_per_lane():
+    """Labels of 64, 90 and 5 symbols: the label matrix _prep_labels builds is 90 wide, so the
+    CTC kernels run with two state pairs per lane -- the only end-to-end use of that layout."""
+    from asr_study_amd.core import models
+    from tests.ctc_cases import random_label
+    rs = np.random.RandomState(21)
+    N, T, F, C, H, L = 3, 140, 9, 7, 12, 2
+    model = models.brsmv1(num_features=F, num_classes=C, num_hiddens=H, num_layers=L,
+                          dropout=0.0, weight_decay=0.0, seed=3)
+    w = [a + rs.randn(*a.shape).astype(np.float32) * 0.2 for a in model.get_weights()]
+    model.set_weights(w)
+    lens = np.array([131, T, 77], np.int64)
+    x = rs.randn(N, T, F).astype(np.float32)
+    for n in range(N):
+        x[n, lens[n]:] = 0.0
+    labels = [random_label(rs, Ln, C, int(lens[n])) for n, Ln in enumerate((64, 90, 5))]
+    params = _oracle_params(w, L)
+    xt = np.ascontiguousarray(x.transpose(1, 0, 2)).astype(np.float64)
+    want = OL.loss_and_grads(params, xt, labels, lens, weight_decay=0.0)
+    slab = model.to_slab(x)
+    ctc, logits, _ = model.loss_and_grads(slab, labels, lens, training=True)
+    torch.cuda.synchronize()
+    assert report('wide-label logits', logits.cpu().numpy()[:, :N], want['logits']) < 1e-4
+    np.testing.assert_allclose(ctc.cpu().numpy(), want['ctc'], rtol=1e-4)
+    for (name, g), gg in zip(OL.flatten(want['grads']), model.get_gradients()):
+        scale = max(1e-3, np.abs(g).max())
+        assert report('wide-label grad ' + name, gg, g) < 1e-4 * scale + 1e-6, name
+
+
 def test_cfg1_graves_ragged_batch():
     """BASELINE cfg1: F=26, 1 x BiLSTM(100), 28 classes, batch 4, T in [99, 999]."""
     from asr_study_amd.core import models
