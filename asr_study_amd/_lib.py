@@ -268,6 +268,10 @@ SIGNATURES = {
                             [C.c_float, void_p, C.c_size_t, void_p]),
     'asr_seqbn_fwd_infer': (C.c_int, [void_p] * 6 + [C.c_int] * 5 + [C.c_float, void_p]),
     'asr_seqbn_bwd': (C.c_int, [void_p] * 9 + [C.c_int] * 5 + [void_p, C.c_size_t, void_p]),
+    'asr_ln_max_width': (C.c_int, []),
+    'asr_ln_workspace_bytes': (C.c_size_t, [C.c_int] * 7),
+    'asr_ln_fwd': (C.c_int, [void_p] * 5 + [C.c_int] * 7 + [C.c_float, void_p]),
+    'asr_ln_bwd': (C.c_int, [void_p] * 7 + [C.c_int] * 7 + [void_p, C.c_size_t, void_p]),
     # operation-level entry points (csrc/roles.cpp)
     'asr_frontend_mfcc_batch': (C.c_int, [C.POINTER(FrontendCfg), void_p, void_p, void_p,
                                           c_int_p, C.c_int, C.c_int, void_p, void_p, void_p,

@@ -276,6 +276,26 @@ class Model(object):
                 s.n_real = s.C if s.grouped else f_real
                 s.clip = 0.0                    # > 0: a following clipped ReLU fused (below)
                 s.tensors = P.bn(s, alloc, self._bn_cols(s))
+            elif s.kind == 'ln':
+                # LayerNormalization (K20, csrc/layernorm.hip): per frame over its real columns,
+                # which it keeps as it is given them (like 'bn': no projection of its own)
+                s.eps = float(st.get('epsilon', 1e-5))
+                cols = self._real_rows(s)
+                s.ld = f_pad
+                if np.array_equal(cols, np.arange(f_real)):
+                    s.segs, s.seg_H, s.seg_Hp = 1, f_real, f_pad
+                else:       # [0, H) and [Hp, Hp + H): two directions padded apart
+                    s.segs, s.seg_H = 2, len(cols) // 2
+                    s.seg_Hp = int(cols[s.seg_H])
+                if f_pad % 4 or s.seg_Hp % 4 or s.segs * s.seg_Hp > f_pad:
+                    raise NotImplementedError('LayerNormalization over %d features: the width '
+                                              'must be a multiple of 4' % f_real)
+                if f_pad > ops.LN_MAX_WIDTH:
+                    raise NotImplementedError(
+                        'LayerNormalization over %d features (%d columns): the asr_ln_* kernels '
+                        'keep a row in the registers of one wave, at most %d columns'
+                        % (f_real, f_pad, ops.LN_MAX_WIDTH))
+                s.tensors = P.ln(s, alloc, cols)
             elif s.kind == 'merge':
                 s.mode, s.skip = st['mode'], int(st['skip'])
                 src = self.stages[s.skip]
@@ -326,8 +346,9 @@ class Model(object):
 
     def _real_rows(self, s):
         """Map of the padded input-feature rows of a stage to its real rows: the output columns
-        of the last stage before it that has an input projection (BatchNormalization keeps the
-        columns it is given), whose two directions are padded apart when it concatenates them."""
+        of the last stage before it that has an input projection (BatchNormalization and
+        LayerNormalization keep the columns they are given), whose two directions are padded
+        apart when it concatenates them."""
         prev = None
         for st in self.stages:
             if st is s:
@@ -731,6 +752,8 @@ class Model(object):
                     a = ops.activation_fwd(a.contiguous(), out, s.act)
             elif s.kind == 'bn':
                 a = self._bn_forward(s, si, a.contiguous(), rec, training, n_real, bn_weight)
+            elif s.kind == 'ln':
+                a = self._ln_forward(s, si, a.contiguous(), rec, need_grad, n_real)
             elif s.kind == 'birnn':
                 Hp = s.Hp
                 BW, BU = stage_masks(si)[:2]
@@ -906,6 +929,18 @@ class Model(object):
                          moments=mom, shift=rm if dist else None,
                          weight=float(bn_weight * T))
         rec.update(stats=stats, N=min(n_real, n_pad), shift=None if dist else stats[:s.C])
+        return y
+
+    def _ln_forward(self, s, si, a, rec, need_grad, n_real):
+        """LayerNormalization stage: the same pass in training and inference; (mu, 1 / sigma)
+        of every row is kept only when a backward pass will read it."""
+        T, n_pad, ld = a.shape
+        y = self._buf('ln%d' % si, a.shape)
+        N = min(n_real, n_pad)
+        stats = self._buf('lnstats%d' % si, (ops.ln_stats_len(T, n_pad),)) if need_grad else None
+        ops.ln_fwd(a, y, self._view(s.og, ld), self._view(s.obeta, ld), N, s.seg_H, s.seg_Hp,
+                   s.segs, s.eps, stats=stats)
+        rec.update(stats=stats, N=N)
         return y
 
     def _bn_update(self):
@@ -1272,7 +1307,8 @@ class Model(object):
                     da = ops.axpby(s.coef, da, 0.0, da, self._buf('dmerge%d' % si, da.shape))
                 skip_grads[s.skip] = da
                 continue
-            first = not any(st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn', 'bigru', 'birhn')
+            first = not any(st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn', 'bigru', 'birhn',
+                                        'ln')
                             for st in self.stages[:si])
             if s.kind in ('noise', 'reshape'):
                 continue
@@ -1303,6 +1339,16 @@ class Model(object):
                 ops.bn_bwd(a_in.contiguous(), da.contiguous(), self._view(s.og, s.C),
                            self._view(s.obeta, s.C), rec['stats'], dx, self._gview(s.og, s.C),
                            self._gview(s.obeta, s.C), rec['N'], a_in.shape[2], s.C, s.clip)
+                if dx is not None:
+                    da = dx
+                continue
+            if s.kind == 'ln':
+                # dgain / dbias into the gradients, dx from the saved (mu, 1 / sigma) (x re-read)
+                ld = a_in.shape[2]
+                dx = None if first else self._buf('dln%d' % si, a_in.shape)
+                ops.ln_bwd(a_in.contiguous(), da.contiguous(), self._view(s.og, ld), rec['stats'],
+                           dx, self._gview(s.og, ld), self._gview(s.obeta, ld), rec['N'],
+                           s.seg_H, s.seg_Hp, s.segs)
                 if dx is not None:
                     da = dx
                 continue

@@ -15,6 +15,8 @@ hard_sigmoid gates, Bidirectional 'concat' or 'sum') runs on csrc/gru.hip and is
 ``rnn_type='gru'`` cell.  ``RHN`` (the reference's Recurrent Highway Network layer) runs on
 csrc/rhn.hip and is the cell of the ``rhn`` factory.  ``BatchNormalization`` (mode 0, axis -1) runs
 bare or on the (N, T, F, C) image of the convolution front-end (csrc/batchnorm.hip).
+``LayerNormalization`` (the reference's fourth layer class, core/layers.py:24-89) normalises every
+frame over its features on csrc/layernorm.hip.
 """
 
 
@@ -428,6 +430,41 @@ class BatchNormalization(Layer):
     def __call__(self, x):
         self.in_fc = x.fc
         return Layer.__call__(self, x)
+
+
+class LayerNormalization(Layer):
+    """The reference's LayerNormalization (core/layers.py:24-89; arXiv 1607.06450), which is dead
+    code there (it calls an ``LN`` it never imports): built here as what the class says it is.
+    For every frame (n, t) of an (N, T, F) tensor
+
+        y = (x - mu) / sqrt(var + epsilon) * gain + bias
+
+    with mu and the BIASED variance taken over the F features of that one frame, epsilon inside
+    the square root (core/layers_utils.py:16-19).  Weights: gain, bias (F each), in that order.
+
+    The axis: the reference's helper takes ``tf.nn.moments(x, [1])``, the feature axis of the
+    (N, 4H) step tensors it was written for; read literally on a 3-D layer input that would be
+    the time axis.  This layer normalises the FEATURE axis -- what the class docstring says
+    ("all of the summed inputs to the neurons in a layer on a single training case"), what the
+    paper does and what ``LSTM(layer_norm=...)`` does inside the cell.  On the (N, T, F, C)
+    image between the convolution front-end's Reshapes the whole F * C vector of a frame is
+    one group (gain / bias have F * C entries; no per-channel grouping).
+
+    No mask: a time-padding frame is a frame like any other (a zero row gives y = bias).  No
+    batch statistics, no running state: training and inference are the same computation, and a
+    sample's output does not depend on what else is in the batch.  No l2 on gain or bias."""
+
+    def __init__(self, epsilon=1e-5, weights=None, gain_init='one', bias_init='zero', **kwargs):
+        if kwargs:
+            raise NotImplementedError('LayerNormalization: unknown arguments %s' % sorted(kwargs))
+        if gain_init != 'one' or bias_init != 'zero':
+            raise NotImplementedError("LayerNormalization: gain_init='one', bias_init='zero' only")
+        if weights is not None:
+            raise NotImplementedError('LayerNormalization(weights=...): use set_weights')
+        if not float(epsilon) > 0:
+            raise ValueError('LayerNormalization: epsilon must be > 0')
+        self.epsilon = float(epsilon)
+        self.gain_init, self.bias_init = 'one', 'zero'
 
 
 class Reshape(Layer):

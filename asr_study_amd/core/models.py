@@ -15,7 +15,7 @@ from . import ctc_utils
 from .engine import Model
 from .layers import (Input, GaussianNoise, TimeDistributed, Dense, LSTM, Bidirectional,
                      Dropout, Merge, merge, l2, Reshape, Convolution2D, clipped_relu, SimpleRNN,
-                     Activation, BatchNormalization, GRU, RHN)
+                     Activation, BatchNormalization, GRU, RHN, LayerNormalization)
 
 
 def ctc_model(inputs, output, **kwargs):
@@ -56,6 +56,8 @@ def ctc_model(inputs, output, **kwargs):
         elif isinstance(layer, BatchNormalization):
             spec.append({'type': 'bn', 'epsilon': layer.epsilon, 'momentum': layer.momentum,
                          'fc': None if layer.in_fc is None else list(layer.in_fc)})
+        elif isinstance(layer, LayerNormalization):
+            spec.append({'type': 'ln', 'epsilon': layer.epsilon})
         elif isinstance(layer, TimeDistributed) and layer.dense is None:
             spec.append(_elementwise_spec(layer.layer, wrapped=True))
         elif isinstance(layer, (Dropout, Activation)):
@@ -252,14 +254,21 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
     projection W x inside the layer, its statistics taken over the valid frames of every utterance
     (the time-padding frames count for nothing; arXiv 1510.01378).
 
+    batch_norm='layer' (with either rnn_type): LayerNormalization where batch_norm=True puts
+    BatchNormalization -- behind each (linear) Convolution2D, over the whole F * C vector of a
+    frame, followed by Activation(clipped_relu(max_value)), and in front of every recurrent
+    layer.  Per frame: no batch statistics, no running state, the same result at any batch size.
+
     rnn_type='gru': every Bidirectional(LSTM) becomes a Bidirectional(GRU) (the cell of the
     published Deep Speech 2; Keras-1.2.2 GRU on csrc/gru.hip) with the same regularisers and
     dropouts; it composes with batch_norm."""
     if rnn_type not in ('lstm', 'gru'):
         raise ValueError("deep_speech2: rnn_type %r ('lstm' or 'gru')" % (rnn_type,))
-    if batch_norm not in (False, True, 'recurrent'):
-        raise ValueError("deep_speech2: batch_norm %r (False, True or 'recurrent')" % (batch_norm,))
+    if batch_norm not in (False, True, 'recurrent', 'layer'):
+        raise ValueError("deep_speech2: batch_norm %r (False, True, 'recurrent' or 'layer')"
+                         % (batch_norm,))
     recurrent_bn = batch_norm == 'recurrent'
+    norm = LayerNormalization if batch_norm == 'layer' else BatchNormalization
     if recurrent_bn and rnn_type != 'gru':
         raise ValueError("deep_speech2: batch_norm='recurrent' needs rnn_type='gru': only the GRU "
                          "layer normalises its input projection (LSTM has no batch_norm argument)")
@@ -275,12 +284,12 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
                           activation=None if batch_norm else clipped_relu(max_value),
                           W_regularizer=l2(weight_decay))(o)
         if batch_norm:
-            o = BatchNormalization()(o)
+            o = norm()(o)
             o = Activation(clipped_relu(max_value))(o)
     o = Reshape((-1, o.features))(o)
     for _ in range(num_layers):
         if batch_norm and not recurrent_bn:
-            o = BatchNormalization()(o)
+            o = norm()(o)
         o = Bidirectional(cell(num_hiddens, return_sequences=True,
                                W_regularizer=l2(weight_decay), U_regularizer=l2(weight_decay),
                                dropout_W=dropout, dropout_U=dropout, **cell_kw))(o)
@@ -293,7 +302,7 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
         max_value=max_value, dropout=dropout, weight_decay=weight_decay,
         input_std_noise=input_std_noise)}
     if batch_norm:          # (only then: default checkpoints keep their config byte for byte)
-        model.config['kwargs']['batch_norm'] = 'recurrent' if recurrent_bn else True
+        model.config['kwargs']['batch_norm'] = batch_norm if isinstance(batch_norm, str) else True
     if rnn_type != 'lstm':  # (likewise)
         model.config['kwargs']['rnn_type'] = rnn_type
     return model

@@ -141,7 +141,7 @@ def keras_names(stages):
     layer, except a Dense's: its group is named after the TimeDistributed around it, and Keras
     counts the TimeDistributed(Dropout / Activation) layers with those."""
     groups = {'convolution2d': 'convolution2d', 'batchnormalization': 'batchnormalization',
-              'dense': 'timedistributed'}
+              'layernormalization': 'layernormalization', 'dense': 'timedistributed'}
     out, n = [], Counter()
     for s in stages:
         if not s.tensors:
@@ -301,3 +301,13 @@ def bn(s, alloc, cols):
             Tensor(layer, 'running_mean', (n,), s.orun, (C,), (cols,), buf='running'),
             Tensor(layer, 'running_std', (n,), ovar, (C,), (cols,), init=ONES, buf='running',
                    fill=1.0)]
+
+
+def ln(s, alloc, cols):
+    """LayerNormalization (csrc/layernorm.hip): gain, bias (one entry per physical column of the
+    slab row, s.ld) in the flat parameters, no l2; the pad columns stay 0.  cols: the columns
+    that carry real features."""
+    W, n, layer = s.ld, len(cols), 'layernormalization'
+    s.og, s.obeta = alloc.take(W), alloc.take(W)
+    return [Tensor(layer, 'gain', (n,), s.og, (W,), (cols,), init=ONES),
+            Tensor(layer, 'bias', (n,), s.obeta, (W,), (cols,))]

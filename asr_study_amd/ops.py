@@ -543,6 +543,42 @@ def bn_update_running(running_mean, running_var, moments, C, momentum, shift=Non
             'asr_bn_update_running')
 
 
+# --------------------------------------------------------------------------- LayerNormalization (K20)
+LN_MAX_WIDTH = 4096       # widest slab row (physical columns) of asr_ln_* (asr_ln_max_width())
+
+
+def ln_stats_len(T, n_pad):
+    """Floats of a stage's stats block: (mu, 1 / sqrt(var + eps)) per slab row."""
+    return 2 * int(T) * int(n_pad)
+
+
+def ln_fwd(x, y, gain, bias, N, H, Hp, segs=1, eps=1e-5, stats=None):
+    """LayerNormalization of x (T, n_pad, ld) over the real columns of each row (segs blocks of H
+    at a stride of Hp) for the N real rows of every frame; stats (ln_stats_len) kept for ln_bwd
+    when given.  The same call serves training and inference."""
+    _check_f32(x, y, gain, bias, stats)
+    T, n_pad, ld = x.shape
+    L.check(L.load().asr_ln_fwd(_ptr(x), _ptr(y), _ptr(gain), _ptr(bias), _ptr(stats), int(T),
+                                int(N), int(n_pad), int(ld), int(H), int(Hp), int(segs),
+                                float(eps), _stream()), 'asr_ln_fwd')
+    return y
+
+
+def ln_bwd(x, dy, gain, stats, dx, dgain, dbias, N, H, Hp, segs=1):
+    """dgain, dbias (ld, written) and dx (same shape as x, or None) from the saved stats."""
+    _check_f32(x, dy, gain, stats, dx, dgain, dbias)
+    T, n_pad, ld = x.shape
+    geo = (int(T), int(N), int(n_pad), int(ld), int(H), int(Hp), int(segs))
+    nbytes = L.load().asr_ln_workspace_bytes(*geo)
+    if nbytes == 0:
+        L.check(-1, 'asr_ln_workspace_bytes (T %d N %d n_pad %d ld %d H %d Hp %d segs %d)' % geo)
+    ws = WS.get('ln', nbytes, x.device)
+    L.check(L.load().asr_ln_bwd(_ptr(x), _ptr(dy), _ptr(gain), _ptr(stats), _ptr(dx),
+                                _ptr(dgain), _ptr(dbias), *geo, _ptr(ws), nbytes, _stream()),
+            'asr_ln_bwd')
+    return dx
+
+
 # --------------------------------------------------------------------------- sequence-wise BN (K18)
 def seqbn_stats_len(W):
     """Floats of a stats block: [mean_hi | mean_lo | invstd | var] (W each) + [|V|, 0, 0, 0]."""

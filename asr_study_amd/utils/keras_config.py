@@ -212,6 +212,11 @@ def model_config(model):
                 'name': name, 'trainable': True, 'epsilon': float(s.eps), 'mode': 0, 'axis': -1,
                 'momentum': float(s.momentum), 'gamma_regularizer': None,
                 'beta_regularizer': None}, [prev])
+        elif s.kind == 'ln':
+            name = nm('layernormalization')
+            add('LayerNormalization', name, {
+                'name': name, 'trainable': True, 'epsilon': float(s.eps), 'gain_init': 'one',
+                'bias_init': 'zero'}, [prev])
         elif s.kind == 'reshape':
             name = nm('reshape')
             add('Reshape', name, {'name': name, 'trainable': True,
@@ -339,6 +344,10 @@ def topology_from_config(text):
         elif kind == 'BatchNormalization':
             o = L.BatchNormalization(epsilon=c.get('epsilon', 1e-3), mode=c.get('mode', 0),
                                      axis=c.get('axis', -1), momentum=c.get('momentum', 0.99))(o)
+        elif kind == 'LayerNormalization':
+            o = L.LayerNormalization(epsilon=c.get('epsilon', 1e-5),
+                                     gain_init=c.get('gain_init', 'one'),
+                                     bias_init=c.get('bias_init', 'zero'))(o)
         elif kind == 'TimeDistributed' and c['layer']['class_name'] == 'Activation':
             o = L.TimeDistributed(L.Activation(_act_from(c['layer']['config'])))(o)
         elif kind == 'TimeDistributed' and c['layer']['class_name'] == 'Dropout':

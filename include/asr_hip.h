@@ -672,6 +672,35 @@ int asr_seqbn_bwd(const float* p, const float* da, const float* gamma, const int
                   asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
+/* K20 LayerNormalization over the feature axis (arXiv 1607.06450;           */
+/* csrc/layernorm.hip).  x, y, dy, dx are time-major slabs (T, n_pad, ld),   */
+/* ld a multiple of 4 and at most asr_ln_max_width() (4096), 16-byte         */
+/* aligned.  The real columns of a row are `segs` blocks of H columns at a   */
+/* stride of Hp (Hp a multiple of 4, H <= Hp, segs * Hp <= ld); every other  */
+/* column is padding, may hold anything and is never read into a sum.  Per   */
+/* real row (n < N of every frame): y = (x - mu) r gain + bias, mu and the   */
+/* BIASED variance over the segs * H real columns, r = 1 / sqrt(var + eps).  */
+/* Pad columns and the padding rows n >= N of y / dx are written as zeros.   */
+/*  gain, bias, dgain, dbias: ld floats, indexed by physical column.         */
+/*  stats (2 T n_pad floats; NULL in asr_ln_fwd: not kept): (mu, r) of row   */
+/*    t * n_pad + n, written for the real rows only.                         */
+/*  asr_ln_bwd: dx = r (g - mean(g) - xhat mean(g xhat)) with xhat = (x -    */
+/*    mu) r and g = gain dy (NULL: no input gradient); dgain = sum dy xhat   */
+/*    and dbias = sum dy over the real rows, WRITTEN, not accumulated (zeros */
+/*    in the pad columns).  Per-workgroup partials in the workspace, added   */
+/*    in a fixed order: no float atomics, bit-identical repeats.             */
+/* Plain scalar arguments, no struct: the ABI version stays.                 */
+/* ------------------------------------------------------------------------ */
+int asr_ln_max_width(void);
+size_t asr_ln_workspace_bytes(int T, int N, int n_pad, int ld, int H, int Hp, int segs);
+int asr_ln_fwd(const float* x, float* y, const float* gain, const float* bias, float* stats,
+               int T, int N, int n_pad, int ld, int H, int Hp, int segs, float eps,
+               asr_stream_t stream);
+int asr_ln_bwd(const float* x, const float* dy, const float* gain, const float* stats, float* dx,
+               float* dgain, float* dbias, int T, int N, int n_pad, int ld, int H, int Hp,
+               int segs, void* workspace, size_t ws_bytes, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
 /* K7  CTC loss + gradient.  Replaces core/ctc_utils.py:60-70 ->             */
 /* tf.nn.ctc_loss (blank = C-1, internal softmax, ctc_merge_repeated=True).  */
 /* logits/grad: (T, n_pad, C) time-major.  labels (N, l_max) int32 padded,   */
