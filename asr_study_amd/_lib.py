@@ -136,6 +136,13 @@ class RhnArgs(C.Structure):
                 ('dz_absmax', void_p)]
 
 
+class AttnArgs(C.Structure):
+    _fields_ = [('T', C.c_int), ('N', C.c_int), ('n_pad', C.c_int), ('heads', C.c_int),
+                ('dh', C.c_int), ('ld', C.c_int), ('ld_out', C.c_int), ('scale', C.c_float),
+                ('qkv', void_p), ('lens', void_p), ('out', void_p), ('lse', void_p),
+                ('dout', void_p), ('dqkv', void_p)]
+
+
 class Segment(C.Structure):
     _fields_ = [('offset', C.c_int64), ('len', C.c_int64), ('l2', C.c_float),
                 ('reserved', C.c_float)]
@@ -272,6 +279,11 @@ SIGNATURES = {
     'asr_ln_workspace_bytes': (C.c_size_t, [C.c_int] * 7),
     'asr_ln_fwd': (C.c_int, [void_p] * 5 + [C.c_int] * 7 + [C.c_float, void_p]),
     'asr_ln_bwd': (C.c_int, [void_p] * 7 + [C.c_int] * 7 + [void_p, C.c_size_t, void_p]),
+    'asr_attn_workspace_bytes': (C.c_size_t, [C.POINTER(AttnArgs)]),
+    'asr_attn_fwd': (C.c_int, [C.POINTER(AttnArgs), void_p]),
+    'asr_attn_bwd': (C.c_int, [C.POINTER(AttnArgs), void_p, C.c_size_t, void_p]),
+    'asr_attn_plan': (C.c_int, [C.POINTER(AttnArgs), C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
+    'asr_posenc_add': (C.c_int, [void_p] * 3 + [C.c_int] * 5 + [void_p]),
     # operation-level entry points (csrc/roles.cpp)
     'asr_frontend_mfcc_batch': (C.c_int, [C.POINTER(FrontendCfg), void_p, void_p, void_p,
                                           c_int_p, C.c_int, C.c_int, void_p, void_p, void_p,

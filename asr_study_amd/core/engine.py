@@ -296,6 +296,19 @@ class Model(object):
                         'keep a row in the registers of one wave, at most %d columns'
                         % (f_real, f_pad, ops.LN_MAX_WIDTH))
                 s.tensors = P.ln(s, alloc, cols)
+            elif s.kind == 'mha':
+                # multi-head self-attention (K21, csrc/attention.hip): the [Q | K | V] projection,
+                # the fused attention core, the output projection
+                s.heads, s.dh = int(st['heads']), int(st['dh'])
+                s.D, s.n_out, s.l2 = s.heads * s.dh, int(st['n_out']), float(st.get('l2', 0.0))
+                if s.heads < 1 or s.dh % 16 or not 16 <= s.dh <= 128:
+                    raise NotImplementedError(
+                        'MultiHeadAttention: head_dim %d (a multiple of 16 in 16 .. 128: the tile '
+                        'of the asr_attn_* kernels), %d heads' % (s.dh, s.heads))
+                s.tensors = P.mha(s, alloc, self._real_rows(s))
+                f_real = f_pad = s.n_out
+            elif s.kind == 'posenc':
+                s.D = f_real                    # (no parameters: the table depends on (T, D) only)
             elif s.kind == 'merge':
                 s.mode, s.skip = st['mode'], int(st['skip'])
                 src = self.stages[s.skip]
@@ -312,6 +325,7 @@ class Model(object):
                        (self._packed_mode == '1' or (self._packed_mode == 'auto' and widest >= 512)))
         self.num_classes = f_real
         self._has_rnn = any(st.kind == 'birnn' for st in self.stages)
+        self._has_mha = any(st.kind == 'mha' for st in self.stages)     # forward needs seq_len
         self._bn = [(i, st) for i, st in enumerate(self.stages) if st.kind == 'bn']
         self._seqbn = [(i, st) for i, st in enumerate(self.stages)
                        if st.kind == 'bigru' and st.bn]
@@ -556,8 +570,9 @@ class Model(object):
         n_pad), over which BatchNormalization takes its training statistics; bn_weight: samples
         this rank contributes to the running moments (default n_real; 0 = a zero-weight dummy).
         seq_len: device int32 lengths of the real samples on the recurrent stack's time axis (what
-        CTC gets): the valid frames of a GRU(batch_norm=True) stage's training statistics (None:
-        every frame).
+        CTC gets): the valid frames of a GRU(batch_norm=True) stage's training statistics and the
+        visible keys of a MultiHeadAttention stage, in training and inference (None: every
+        frame).
 
         masks: optional explicit variational-dropout masks (parity tests):
         {stage_index: (BW (2, n_pad, f_in_pad), BU (2, n_pad, Hp))}.
@@ -754,6 +769,11 @@ class Model(object):
                 a = self._bn_forward(s, si, a.contiguous(), rec, training, n_real, bn_weight)
             elif s.kind == 'ln':
                 a = self._ln_forward(s, si, a.contiguous(), rec, need_grad, n_real)
+            elif s.kind == 'mha':
+                a = self._mha_forward(s, si, a.contiguous(), rec, need_grad, n_real, seq_len)
+            elif s.kind == 'posenc':
+                out = self._buf('posenc%d' % si, a.shape)
+                a = ops.posenc_add(a.contiguous(), out, min(n_real, n_pad), s.D)
             elif s.kind == 'birnn':
                 Hp = s.Hp
                 BW, BU = stage_masks(si)[:2]
@@ -942,6 +962,57 @@ class Model(object):
                    s.segs, s.eps, stats=stats)
         rec.update(stats=stats, N=N)
         return y
+
+    def _mha_forward(self, s, si, a, rec, need_grad, n_real, seq_len):
+        """MultiHeadAttention stage: qkv = a W_qkv + b_qkv (one GEMM), the fused attention core
+        over each utterance's valid keys (seq_len: device lengths on this time axis; None: every
+        frame), the output projection.  The row log-sum-exp is kept only for a backward pass."""
+        T, n_pad, _ = a.shape
+        rows, D, N = T * n_pad, s.D, min(n_real, n_pad)
+        qkv = self._buf('qkv%d' % si, (T, n_pad, 3 * D))
+        ops.gemm(a, self.params, qkv, rows, 3 * D, s.f_in_pad, b_off=s.oW,
+                 bias=self._view(s.ob, 3 * D))
+        ctx = self._buf('attn%d' % si, (T, n_pad, D))
+        lse = self._buf('lse%d' % si, (ops.attn_lse_len(T, n_pad, s.heads),)) if need_grad \
+            else None
+        ops.attn_fwd(qkv, ctx, N, s.heads, s.dh, lens=seq_len, lse=lse)
+        out = self._buf('mha%d' % si, (T, n_pad, s.n_out))
+        ops.gemm(ctx, self.params, out, rows, s.n_out, D, b_off=s.oWo,
+                 bias=self._view(s.obo, s.n_out))
+        rec.update(qkv=qkv, ctx=ctx, lse=lse, N=N, lens=seq_len)
+        return out
+
+    def _mha_backward(self, s, si, rec, a_in, da, first, split):
+        """The two projections' wgrad / colsum / dgrad GEMMs around asr_attn_bwd; returns dx, or
+        None for the first trainable stage."""
+        T, n_pad, _ = a_in.shape
+        rows, D = T * n_pad, s.D
+        da = da.contiguous()
+        gmx = ops.absmax(da, self._buf('damax%d' % si, (1,)))
+        ops.gemm(rec['ctx'], da, self.grads, D, s.n_out, rows, trans_a=True, c_off=s.oWo,
+                 split_k=split, b_absmax=gmx)
+        ops.colsum(da, rows, s.n_out, s.n_out, self._gview(s.obo, s.n_out))
+        dctx = self._buf('dattn%d' % si, (T, n_pad, D))
+        ops.gemm(da, self.params, dctx, rows, D, s.n_out, trans_b=True, b_off=s.oWo,
+                 a_absmax=gmx)
+        dqkv = self._buf('dqkv%d' % si, (T, n_pad, 3 * D))
+        ops.attn_bwd(rec['qkv'], rec['ctx'], rec['lse'], dctx, dqkv, rec['N'], s.heads, s.dh,
+                     lens=rec['lens'])
+        qmx = ops.absmax(dqkv, self._buf('dqkvmax%d' % si, (1,)))
+        ops.gemm(a_in, dqkv, self.grads, s.f_in_pad, 3 * D, rows, trans_a=True, c_off=s.oW,
+                 split_k=split, b_absmax=qmx)
+        # db_q and db_v.  Softmax does not see a shift of all scores of a row, so the key bias
+        # has no effect and its gradient is identically 0: a column sum of dK would leave
+        # rounding noise there, which Adam would normalise into steps of +-lr.  It is never
+        # produced: that third of the gradient keeps the zero the buffer is created with.
+        ops.colsum(dqkv, rows, D, 3 * D, self._gview(s.ob, D))
+        ops.colsum(dqkv, rows, D, 3 * D, self._gview(s.ob + 2 * D, D), x_off=2 * D)
+        if first:
+            return None
+        dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
+        ops.gemm(dqkv, self.params, dx, rows, s.f_in_pad, 3 * D, trans_b=True, b_off=s.oW,
+                 a_absmax=qmx)
+        return dx
 
     def _bn_update(self):
         """Running-moment update of every BatchNormalization stage, once per optimisation step,
@@ -1308,9 +1379,14 @@ class Model(object):
                 skip_grads[s.skip] = da
                 continue
             first = not any(st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn', 'bigru', 'birhn',
-                                        'ln')
+                                        'ln', 'mha')
                             for st in self.stages[:si])
-            if s.kind in ('noise', 'reshape'):
+            if s.kind in ('noise', 'reshape', 'posenc'):    # (posenc: d(x + pe) / dx = 1)
+                continue
+            if s.kind == 'mha':
+                dx = self._mha_backward(s, si, rec, a_in.contiguous(), da, first, split)
+                if dx is not None:
+                    da = dx
                 continue
             if s.kind == 'conv':
                 flush_side()
@@ -1658,11 +1734,23 @@ class Model(object):
         return da
 
     # ------------------------------------------------------------------ batches
+    def _key_lens(self, lens, T):
+        """lens: host lengths on the logits' time axis of a batch of T input frames.  A model
+        with a MultiHeadAttention stage refuses lengths outside 1 .. out_frames(T) here, while
+        they are on the host (the kernel would clamp them silently)."""
+        lens = np.asarray(lens).reshape(-1)
+        if self._has_mha and lens.size and (lens.min() < 1 or lens.max() > self.out_frames(T)):
+            raise ValueError('inputs_length: every utterance needs 1 .. %d frames on the '
+                             'attention layers\' time axis (%d input frames), got %d .. %d'
+                             % (self.out_frames(T), T, lens.min(), lens.max()))
+        return lens
+
     def _prep_labels(self, labels, seq_len, T):
         N = len(labels)
         lmax = max([len(l) for l in labels] + [1])
         lab = np.zeros((N, lmax), np.int32)
         seq_len = self.out_lengths(np.asarray(seq_len).reshape(-1))   # on the logits' time axis
+        seq_len = self._key_lens(seq_len, T)
         for n, l in enumerate(labels):
             l = np.asarray(l, np.int64).reshape(-1)
             need = len(l) + int(np.sum(l[1:] == l[:-1])) if len(l) else 0
@@ -1911,7 +1999,8 @@ class Model(object):
         slab, labels, lens = self._unpack_inputs(inputs)
         N = len(labels)
         lab, lab_len, sl = self._prep_labels(labels, lens, slab.shape[0])
-        logits = self.forward(slab, training=False, need_grad=False, n_valid=N)
+        logits = self.forward(slab, training=False, need_grad=False, n_valid=N,
+                              seq_len=sl if self._has_mha else None)
         ctc = ops.ctc_loss_grad(logits, lab, lab_len, sl, N, grad=None)
         hyps = None
         dec = dlen = None
@@ -1945,10 +2034,14 @@ class Model(object):
         slab = x if (torch.is_tensor(x) and x.dim() == 3 and x.shape[1] % 16 == 0) else self.to_slab(x)
         N = len(inputs_length) if inputs_length is not None else slab.shape[1]
         lens = np.asarray(inputs_length if inputs_length is not None else [slab.shape[0]] * N).reshape(-1)
-        logits = self.forward(slab, training=False, need_grad=False, n_valid=N)
+        sl = None
+        if self._has_mha or self.decoder is not None:
+            sl = self._key_lens(self.out_lengths(lens), slab.shape[0]).astype(np.int32)
+            sl = torch.as_tensor(sl).to(self.device)
+        logits = self.forward(slab, training=False, need_grad=False, n_valid=N,
+                              seq_len=sl if self._has_mha else None)
         if self.decoder is None:
             return logits[:, :N].permute(1, 0, 2).contiguous().cpu().numpy()
-        sl = torch.as_tensor(np.asarray(self.out_lengths(lens)).astype(np.int32)).to(self.device)
         if self.decoder.get('is_greedy', True):
             dec, dlen = ops.ctc_greedy(logits, sl, N)
             dec, dlen = dec.cpu().numpy(), dlen.cpu().numpy()
@@ -1971,7 +2064,8 @@ class Model(object):
         N = len(labels)
         lens = np.asarray(inputs_length).reshape(-1)
         lab, lab_len, sl = self._prep_labels(labels, lens, slab.shape[0])
-        logits = self.forward(slab, training=False, need_grad=False, n_valid=N)
+        logits = self.forward(slab, training=False, need_grad=False, n_valid=N,
+                              seq_len=sl if self._has_mha else None)
         from .ctc_utils import align_paths
         path, score = align_paths(logits, lab, lab_len, sl, N)
         sl_h = sl.cpu().numpy()

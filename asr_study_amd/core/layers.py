@@ -17,6 +17,8 @@ csrc/rhn.hip and is the cell of the ``rhn`` factory.  ``BatchNormalization`` (mo
 bare or on the (N, T, F, C) image of the convolution front-end (csrc/batchnorm.hip).
 ``LayerNormalization`` (the reference's fourth layer class, core/layers.py:24-89) normalises every
 frame over its features on csrc/layernorm.hip.
+``MultiHeadAttention`` and ``PositionalEncoding`` (no reference counterpart) run on
+csrc/attention.hip and make the ``transformer`` factory.
 """
 
 
@@ -465,6 +467,74 @@ class LayerNormalization(Layer):
             raise ValueError('LayerNormalization: epsilon must be > 0')
         self.epsilon = float(epsilon)
         self.gain_init, self.bias_init = 'one', 'zero'
+
+
+class MultiHeadAttention(Layer):
+    """Multi-head self-attention over the frames of an utterance (arXiv 1706.03762) on
+    csrc/attention.hip.  For an (N, T, F) input, D = num_heads * head_dim:
+
+        [Q | K | V] = x W_qkv + b_qkv               (F, 3D): one projection, head h in columns
+                                                    h * head_dim .. of each block
+        P_h = softmax(Q_h K_h^T / sqrt(head_dim))   over the utterance's VALID frames (the keys
+                                                    past its length carry probability 0)
+        y = concat_h(P_h V_h) W_o + b_o             (D, output_dim)
+
+    Every frame is a query, time-padding frames included (a frame like any other, as everywhere in
+    this library); only keys are masked, by the utterance lengths the model is called with.
+    Weights: W_qkv, b_qkv, W_o, b_o, in that order; W_regularizer (l2) applies to both matrices.
+    head_dim defaults to features / num_heads, output_dim to the input width.  head_dim must be a
+    multiple of 16 in 16 .. 128 (the kernel's tile).  Not built: dropout on the probabilities
+    (use Dropout behind the layer), causal masks, relative positions, cross-attention."""
+
+    def __init__(self, num_heads, head_dim=None, output_dim=None, W_regularizer=None,
+                 attention_dropout=0., **kwargs):
+        if kwargs:
+            raise NotImplementedError('MultiHeadAttention: unknown arguments %s' % sorted(kwargs))
+        if attention_dropout:
+            raise NotImplementedError('MultiHeadAttention(attention_dropout=%r): dropout on the '
+                                      'attention probabilities is not implemented; put Dropout '
+                                      'behind the layer' % (attention_dropout,))
+        if int(num_heads) != num_heads or num_heads < 1:
+            raise NotImplementedError('MultiHeadAttention: num_heads %r (an integer >= 1)'
+                                      % (num_heads,))
+        self.num_heads = int(num_heads)
+        self.head_dim = None if head_dim is None else self._check_dh(head_dim)
+        self.output_dim = None if output_dim is None else int(output_dim)
+        self.l2 = W_regularizer.l2 if W_regularizer is not None else 0.0
+        self.attention_dropout = 0.0
+
+    @staticmethod
+    def _check_dh(dh):
+        if int(dh) != dh or dh < 16 or dh > 128 or int(dh) % 16:
+            raise NotImplementedError('MultiHeadAttention: head_dim %r is not implemented (a '
+                                      'multiple of 16 in 16 .. 128: the tile of the asr_attn_* '
+                                      'kernels)' % (dh,))
+        return int(dh)
+
+    def __call__(self, x):
+        if self.head_dim is None:
+            if x.features % self.num_heads:
+                raise NotImplementedError('MultiHeadAttention: %d heads do not divide the %d '
+                                          'input features (pass head_dim)'
+                                          % (self.num_heads, x.features))
+            self.head_dim = self._check_dh(x.features // self.num_heads)
+        if self.output_dim is None:
+            self.output_dim = int(x.features)
+        return Layer.__call__(self, x)
+
+    def out_features(self, f):
+        return self.output_dim
+
+
+class PositionalEncoding(Layer):
+    """Adds the sinusoidal position table of arXiv 1706.03762 to an (N, T, F) tensor:
+    pe[t, 2i] = sin(t / 10000^(2i / F)), pe[t, 2i + 1] = cos(t / 10000^(2i / F)); t counts the
+    frames of the tensor it is applied to (behind a time-strided front-end: the strided frames).
+    No parameters; the gradient passes through."""
+
+    def __init__(self, **kwargs):
+        if kwargs:
+            raise NotImplementedError('PositionalEncoding: unknown arguments %s' % sorted(kwargs))
 
 
 class Reshape(Layer):

@@ -1,7 +1,8 @@
 """Model factories with the reference's names and hyper-parameters
 (core/models.py): ``ctc_model``, ``graves2006``, ``eyben``, ``maas``, ``deep_speech``,
 ``brsmv1``, plus this build's ``deep_speech2`` (BiLSTM or, with ``rnn_type='gru'``, BiGRU) and
-``rhn`` (brsmv1's topology on the reference's own RHN cell).
+``rhn`` (brsmv1's topology on the reference's own RHN cell) and ``transformer`` (a pre-LN
+self-attention encoder, csrc/attention.hip).
 
 ``train.py`` resolves them by name -- ``get_from_module('core.models', 'brsmv1')
 (**hparams)`` (train.py:127-129) -- and gets back an object with the Keras
@@ -15,7 +16,8 @@ from . import ctc_utils
 from .engine import Model
 from .layers import (Input, GaussianNoise, TimeDistributed, Dense, LSTM, Bidirectional,
                      Dropout, Merge, merge, l2, Reshape, Convolution2D, clipped_relu, SimpleRNN,
-                     Activation, BatchNormalization, GRU, RHN, LayerNormalization)
+                     Activation, BatchNormalization, GRU, RHN, LayerNormalization,
+                     MultiHeadAttention, PositionalEncoding)
 
 
 def ctc_model(inputs, output, **kwargs):
@@ -58,6 +60,11 @@ def ctc_model(inputs, output, **kwargs):
                          'fc': None if layer.in_fc is None else list(layer.in_fc)})
         elif isinstance(layer, LayerNormalization):
             spec.append({'type': 'ln', 'epsilon': layer.epsilon})
+        elif isinstance(layer, MultiHeadAttention):
+            spec.append({'type': 'mha', 'heads': layer.num_heads, 'dh': layer.head_dim,
+                         'n_out': layer.output_dim, 'l2': layer.l2})
+        elif isinstance(layer, PositionalEncoding):
+            spec.append({'type': 'posenc'})
         elif isinstance(layer, TimeDistributed) and layer.dense is None:
             spec.append(_elementwise_spec(layer.layer, wrapped=True))
         elif isinstance(layer, (Dropout, Activation)):
@@ -338,4 +345,49 @@ def rhn(num_features=39, num_classes=28, num_hiddens=256, num_layers=5, depth=2,
         num_layers=num_layers, depth=depth, coupling=coupling, dropout=dropout,
         input_dropout=input_dropout, input_std_noise=input_std_noise,
         weight_decay=weight_decay, merge_mode=merge_mode, activation=activation)}
+    return model
+
+
+def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_layers=6,
+                d_ff=1024, dropout=0.1, conv=True, conv_filters=32,
+                conv_kernels=((11, 41), (11, 21)), weight_decay=0., **kw):
+    """A CTC-trained pre-LN transformer encoder (arXiv 1706.03762, 2002.04745).  NO REFERENCE
+    COUNTERPART.  conv=True: deep_speech2's front-end first -- Reshape, two Convolution2D with
+    clipped ReLU (strides (2, 2) and (1, 2): time stride 2), Reshape.  Then
+    TimeDistributed(Dense(d_model)), PositionalEncoding, Dropout, and ``num_layers`` blocks
+
+        x = merge([Dropout(MultiHeadAttention(num_heads)(LayerNormalization(x))), x], 'sum')
+        x = merge([Dropout(Dense(d_model)(relu(Dense(d_ff)(LayerNormalization(x))))), x], 'sum')
+
+    a final LayerNormalization and TimeDistributed(Dense(num_classes)).  The attention keys of an
+    utterance are its valid frames (the strided lengths).  weight_decay: l2 on every matrix."""
+    reg = l2(weight_decay)
+    x = Input(name='inputs', shape=(None, num_features))
+    o = x
+    if conv:
+        o = Reshape((-1, num_features, 1))(o)
+        for (kt, kf), (st, sf) in zip(conv_kernels, ((2, 2), (1, 2))):
+            o = Convolution2D(conv_filters, kt, kf, subsample=(st, sf), border_mode='same',
+                              activation=clipped_relu(20), W_regularizer=reg)(o)
+        o = Reshape((-1, o.features))(o)
+    o = TimeDistributed(Dense(d_model, W_regularizer=reg))(o)
+    o = PositionalEncoding()(o)
+    o = Dropout(dropout)(o)
+    for _ in range(num_layers):
+        y = LayerNormalization()(o)
+        y = MultiHeadAttention(num_heads, W_regularizer=reg)(y)
+        o = merge([Dropout(dropout)(y), o], mode='sum')
+        y = LayerNormalization()(o)
+        y = TimeDistributed(Dense(d_ff, W_regularizer=reg))(y)
+        y = Activation('relu')(y)
+        y = TimeDistributed(Dense(d_model, W_regularizer=reg))(y)
+        o = merge([Dropout(dropout)(y), o], mode='sum')
+    o = LayerNormalization()(o)
+    o = TimeDistributed(Dense(num_classes, W_regularizer=reg))(o)
+    model = ctc_model(x, o, **kw)
+    model.config = {'name': 'transformer', 'kwargs': dict(
+        num_features=num_features, num_classes=num_classes, d_model=d_model,
+        num_heads=num_heads, num_layers=num_layers, d_ff=d_ff, dropout=dropout, conv=conv,
+        conv_filters=conv_filters, conv_kernels=[list(k) for k in conv_kernels],
+        weight_decay=weight_decay)}
     return model

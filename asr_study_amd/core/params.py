@@ -141,7 +141,8 @@ def keras_names(stages):
     layer, except a Dense's: its group is named after the TimeDistributed around it, and Keras
     counts the TimeDistributed(Dropout / Activation) layers with those."""
     groups = {'convolution2d': 'convolution2d', 'batchnormalization': 'batchnormalization',
-              'layernormalization': 'layernormalization', 'dense': 'timedistributed'}
+              'layernormalization': 'layernormalization',
+              'multiheadattention': 'multiheadattention', 'dense': 'timedistributed'}
     out, n = [], Counter()
     for s in stages:
         if not s.tensors:
@@ -311,3 +312,19 @@ def ln(s, alloc, cols):
     s.og, s.obeta = alloc.take(W), alloc.take(W)
     return [Tensor(layer, 'gain', (n,), s.og, (W,), (cols,), init=ONES),
             Tensor(layer, 'bias', (n,), s.obeta, (W,), (cols,))]
+
+
+def mha(s, alloc, rows):
+    """MultiHeadAttention (csrc/attention.hip): W_qkv (F, 3D) = [W_q | W_k | W_v], b_qkv (3D),
+    W_o (D, n_out), b_o (n_out), D = heads * dh; each of the three projection blocks is drawn
+    glorot-uniform on its own (limit sqrt(6 / (F + D))); l2 on the two matrices."""
+    F, D, layer = len(rows), s.D, 'multiheadattention'
+    lim = math.sqrt(6.0 / (F + D))
+    s.oW, s.ob = alloc.take(s.f_in_pad * 3 * D), alloc.take(3 * D)
+    s.oWo, s.obo = alloc.take(D * s.n_out), alloc.take(s.n_out)
+    return [Tensor(layer, 'W_qkv', (F, 3 * D), s.oW, (s.f_in_pad, 3 * D), (rows,), l2=s.l2,
+                   init=('uniform', lim)),
+            Tensor(layer, 'b_qkv', (3 * D,), s.ob, (3 * D,), ()),
+            Tensor(layer, 'W_o', (D, s.n_out), s.oWo, (D, s.n_out), (), l2=s.l2,
+                   init=_glorot(D, s.n_out)),
+            Tensor(layer, 'b_o', (s.n_out,), s.obo, (s.n_out,), ())]

@@ -1,0 +1,524 @@
+// K21 multi-head self-attention core (softmax(scale Q K^T) V, key-masked by length), forward and
+// backward, fused, and the sinusoidal positional-encoding add.
+//
+// qkv is a time-major slab (T, n_pad, ld >= 3D), column blocks [Q | K | V] of D = heads * dh
+// columns each, head h in columns h dh .. (h + 1) dh - 1 of its block: what one x @ W_qkv + b_qkv
+// GEMM writes.  For every real sample n < N, head h and query frame t (ALL T frames are queries):
+//   s[t,u] = scale q_t . k_u for u < lens[n] (u < T without lens), p = softmax_u(s), keys
+//   u >= lens[n] carry probability exactly 0, out_t = sum_u p[t,u] v_u, lse_t = log sum_u exp s.
+// Backward, with D_t = dout_t . out_t:  dV = P^T dO,  dS = P (.) (dO V^T - D),  dQ = scale dS K,
+// dK = scale dS^T Q; masked keys get dK = dV = exactly 0.  Rows n >= N and the pad columns of
+// out / dqkv are written as exact zeros.
+//
+// ARITHMETIC: exact fp32 -- every product is an fmaf on fp32 operands with fp32 accumulation
+// (vector FMAs, which the compiler packs two to a v_pk_fma_f32 where it can; no MFMA, no split
+// planes); exponentials are base 2 (v_exp_f32) on scores pre-multiplied by scale log2(e), as
+// ctc.hip does.
+//
+// TILING: a workgroup of 256 threads (16 x 16) owns a 64-row tile of one (sample, head) and
+// streams 64-row tiles of the other side through LDS; T is not bounded by LDS.  A tile row is
+// dh + 4 floats apart ((dh + 4) / 4 is odd: the 16 lanes of a row group read 16-byte pieces of 16
+// different rows without a bank conflict).  A 64 x 64 score tile lives in registers, 4 x 4 per
+// thread (rows 4 ty + i, columns tx + 16 j); the row statistics are xor butterflies over the 16
+// tx lanes; the tile then goes through LDS once for the second product (64 x dh, 4 x dh / 16 per
+// thread).  The T x T matrix never reaches HBM: the forward keeps the running maximum / sum, the
+// backward recomputes p = exp2(s - lse) from the saved lse.
+//   forward:  grid (query tiles, heads, n_pad); key tiles up to lens[n].
+//   backward: (1) the same grid over query tiles: D (to the workspace) and dQ;
+//             (2) grid (key tiles, heads, n_pad): dK and dV over all query tiles.
+// Every output element is written by exactly one thread, which adds its terms in one fixed
+// order: no float atomics, repeats are bit-identical.  No workgroup waits on another one.
+#include "common.h"
+
+namespace {
+
+constexpr int AT_TILE = 64;               // Bq = Bk
+constexpr int AT_THREADS = 256;
+constexpr int AT_PP = AT_TILE + 4;        // pitch of the probability tile
+constexpr float AT_LOG2E = 1.4426950408889634f;
+constexpr float AT_LN2 = 0.6931471805599453f;
+
+__device__ __forceinline__ float4 at_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void at_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+
+__device__ __forceinline__ float at_max16(float v) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, ASR_WAVE));
+  return v;
+}
+__device__ __forceinline__ float at_sum16(float v) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, ASR_WAVE);
+  return v;
+}
+
+// rows [r0, r0 + 64) of one column block of a slab -> LDS tile (64, DH + 4); rows >= r_end: zeros
+template <int DH>
+__device__ __forceinline__ void at_load_tile(float* tile, const float* src, size_t row_stride,
+                                             int r0, int r_end, int tid) {
+  constexpr int V = DH / 4, DP = DH + 4;
+#pragma unroll
+  for (int e = tid; e < AT_TILE * V; e += AT_THREADS) {
+    const int r = e / V, c = (e - r * V) * 4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r0 + r < r_end) v = at_ld4(src + (size_t)(r0 + r) * row_stride + c);
+    at_st4(tile + r * DP + c, v);
+  }
+}
+
+// acc[i][j] = A[4 ty + i] . B[tx + 16 j] over DH columns
+template <int DH>
+__device__ __forceinline__ void at_dot(const float* A, const float* B, int ty, int tx,
+                                       float (&acc)[4][4]) {
+  constexpr int DP = DH + 4;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+#pragma unroll 4
+  for (int d = 0; d < DH; d += 4) {
+    float4 a[4], b[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = at_ld4(A + (4 * ty + i) * DP + d);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b[j] = at_ld4(B + (tx + 16 * j) * DP + d);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        acc[i][j] = fmaf(a[i].x, b[j].x, acc[i][j]);
+        acc[i][j] = fmaf(a[i].y, b[j].y, acc[i][j]);
+        acc[i][j] = fmaf(a[i].z, b[j].z, acc[i][j]);
+        acc[i][j] = fmaf(a[i].w, b[j].w, acc[i][j]);
+      }
+  }
+}
+
+// o[i][jj] += sum_k P[4 ty + i][k] B[k][tx + 16 jj], k ascending
+template <int DH>
+__device__ __forceinline__ void at_acc(const float* P, const float* B, int ty, int tx,
+                                       float (&o)[4][DH / 16]) {
+  constexpr int DP = DH + 4, NJ = DH / 16;
+#pragma unroll 2
+  for (int k = 0; k < AT_TILE; k += 4) {
+    float4 p[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) p[i] = at_ld4(P + (4 * ty + i) * AT_PP + k);
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) {
+      const float b0 = B[(k + 0) * DP + tx + 16 * jj], b1 = B[(k + 1) * DP + tx + 16 * jj];
+      const float b2 = B[(k + 2) * DP + tx + 16 * jj], b3 = B[(k + 3) * DP + tx + 16 * jj];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        o[i][jj] = fmaf(p[i].x, b0, o[i][jj]);
+        o[i][jj] = fmaf(p[i].y, b1, o[i][jj]);
+        o[i][jj] = fmaf(p[i].z, b2, o[i][jj]);
+        o[i][jj] = fmaf(p[i].w, b3, o[i][jj]);
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ void at_put_tile(float* P, const float (&s)[4][4], int ty, int tx) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) P[(4 * ty + i) * AT_PP + tx + 16 * j] = s[i][j];
+}
+
+// zeros into columns [c0, c0 + w) of rows [r0, min(r0 + 64, r_end)) of a slab (any w >= 0)
+__device__ __forceinline__ void at_zero_cols(float* dst, size_t row_stride, int r0, int r_end,
+                                             int c0, int w, int tid) {
+  for (int e = tid; e < AT_TILE * w; e += AT_THREADS) {
+    const int r = e / w, c = e - r * w;
+    if (r0 + r < r_end) dst[(size_t)(r0 + r) * row_stride + c0 + c] = 0.f;
+  }
+}
+
+__device__ __forceinline__ int at_len(const int* lens, int n, int T) {
+  int len = lens ? lens[n] : T;
+  // the engine refuses lengths outside 1 .. T on the host (Model._key_lens); a direct caller's
+  // are clamped here, so that no length can index out of bounds
+  return len < 1 ? 1 : (len > T ? T : len);
+}
+
+struct AtGeo {
+  int T, N, n_pad, heads, ld, ld_out;
+  float c2;         // scale * log2(e)
+  float scale;
+};
+
+template <int DH>
+__global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(const float* __restrict__ qkv,
+                                                              const int* __restrict__ lens,
+                                                              float* __restrict__ out,
+                                                              float* __restrict__ lse, AtGeo g) {
+  constexpr int DP = DH + 4, NJ = DH / 16;
+  extern __shared__ float4 at_lds4[];
+  float* Qs = reinterpret_cast<float*>(at_lds4);
+  float* Ks = Qs + AT_TILE * DP;
+  float* Vs = Ks + AT_TILE * DP;
+  float* Ps = Vs + AT_TILE * DP;
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int q0 = blockIdx.x * AT_TILE, h = blockIdx.y, n = blockIdx.z;
+  const int D = g.heads * DH;
+  const size_t rs = (size_t)g.n_pad * g.ld, rso = (size_t)g.n_pad * g.ld_out;
+  float* o_base = out + (size_t)n * g.ld_out;
+  if (h == 0) at_zero_cols(o_base, rso, q0, g.T, D, g.ld_out - D, tid);
+  if (n >= g.N) {
+    at_zero_cols(o_base, rso, q0, g.T, h * DH, DH, tid);
+    return;
+  }
+  const float* base = qkv + (size_t)n * g.ld + h * DH;
+  const int len = at_len(lens, n, g.T);
+  at_load_tile<DH>(Qs, base, rs, q0, g.T, tid);
+  float m[4], l[4], o[4][NJ];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    m[i] = asr_neg_inf();
+    l[i] = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) o[i][jj] = 0.f;
+  }
+  for (int k0 = 0; k0 < len; k0 += AT_TILE) {
+    at_load_tile<DH>(Ks, base + D, rs, k0, len, tid);
+    at_load_tile<DH>(Vs, base + 2 * D, rs, k0, len, tid);
+    __syncthreads();
+    float s[4][4];
+    at_dot<DH>(Qs, Ks, ty, tx, s);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float mx = asr_neg_inf();
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        s[i][j] = (k0 + tx + 16 * j < len) ? s[i][j] * g.c2 : asr_neg_inf();
+        mx = fmaxf(mx, s[i][j]);
+      }
+      mx = fmaxf(m[i], at_max16(mx));       // finite: key k0 of every tile is a valid one
+      const float alpha = exp2f(m[i] - mx);
+      float sum = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        s[i][j] = exp2f(s[i][j] - mx);
+        sum += s[i][j];
+      }
+      l[i] = fmaf(l[i], alpha, at_sum16(sum));
+      m[i] = mx;
+#pragma unroll
+      for (int jj = 0; jj < NJ; ++jj) o[i][jj] *= alpha;
+    }
+    at_put_tile(Ps, s, ty, tx);
+    __syncthreads();
+    at_acc<DH>(Ps, Vs, ty, tx, o);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int t = q0 + 4 * ty + i;
+    if (t >= g.T) continue;
+    float* orow = o_base + (size_t)t * rso + h * DH;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) orow[tx + 16 * jj] = o[i][jj] / l[i];
+    if (lse != nullptr && tx == 0)
+      lse[((size_t)t * g.n_pad + n) * g.heads + h] = (m[i] + log2f(l[i])) * AT_LN2;
+  }
+}
+
+// backward pass 1: D = dout . out (to dvec, laid out like lse) and dQ, per query tile
+template <int DH>
+__global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(
+    const float* __restrict__ qkv, const int* __restrict__ lens, const float* __restrict__ out,
+    const float* __restrict__ lse, const float* __restrict__ dout, float* __restrict__ dqkv,
+    float* __restrict__ dvec, AtGeo g) {
+  constexpr int DP = DH + 4, NJ = DH / 16;
+  extern __shared__ float4 at_lds4[];
+  float* Qs = reinterpret_cast<float*>(at_lds4);
+  float* Gs = Qs + AT_TILE * DP;            // dO tile
+  float* Ks = Gs + AT_TILE * DP;
+  float* Vs = Ks + AT_TILE * DP;
+  float* Ps = Vs + AT_TILE * DP;
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int q0 = blockIdx.x * AT_TILE, h = blockIdx.y, n = blockIdx.z;
+  const int D = g.heads * DH;
+  const size_t rs = (size_t)g.n_pad * g.ld, rso = (size_t)g.n_pad * g.ld_out;
+  float* dq_base = dqkv + (size_t)n * g.ld;
+  if (n >= g.N) {
+    at_zero_cols(dq_base, rs, q0, g.T, h * DH, DH, tid);
+    return;
+  }
+  const float* base = qkv + (size_t)n * g.ld + h * DH;
+  const float* do_base = dout + (size_t)n * g.ld_out + h * DH;
+  const float* o_base = out + (size_t)n * g.ld_out + h * DH;
+  const int len = at_len(lens, n, g.T);
+  at_load_tile<DH>(Qs, base, rs, q0, g.T, tid);
+  at_load_tile<DH>(Gs, do_base, rso, q0, g.T, tid);
+  __syncthreads();
+  float lse2[4], dsum[4], dq[4][NJ];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int t = q0 + 4 * ty + i;
+    float acc = 0.f;
+    if (t < g.T) {
+#pragma unroll
+      for (int jj = 0; jj < NJ; ++jj)
+        acc = fmaf(Gs[(4 * ty + i) * DP + tx + 16 * jj], o_base[(size_t)t * rso + tx + 16 * jj], acc);
+    }
+    dsum[i] = at_sum16(acc);
+    const size_t li = ((size_t)(t < g.T ? t : 0) * g.n_pad + n) * g.heads + h;
+    lse2[i] = lse[li] * AT_LOG2E;
+    if (t < g.T && tx == 0) dvec[li] = dsum[i];
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) dq[i][jj] = 0.f;
+  }
+  for (int k0 = 0; k0 < len; k0 += AT_TILE) {
+    at_load_tile<DH>(Ks, base + D, rs, k0, len, tid);
+    at_load_tile<DH>(Vs, base + 2 * D, rs, k0, len, tid);
+    __syncthreads();
+    float s[4][4], dp[4][4];
+    at_dot<DH>(Qs, Ks, ty, tx, s);
+    at_dot<DH>(Gs, Vs, ty, tx, dp);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float p = (k0 + tx + 16 * j < len) ? exp2f(fmaf(s[i][j], g.c2, -lse2[i])) : 0.f;
+        s[i][j] = p * (dp[i][j] - dsum[i]) * g.scale;
+      }
+    at_put_tile(Ps, s, ty, tx);
+    __syncthreads();
+    at_acc<DH>(Ps, Ks, ty, tx, dq);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int t = q0 + 4 * ty + i;
+    if (t >= g.T) continue;
+    float* row = dq_base + (size_t)t * rs + h * DH;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) row[tx + 16 * jj] = dq[i][jj];
+  }
+}
+
+// backward pass 2: dK and dV of one key tile over all query tiles (query tiles ascending)
+template <int DH>
+__global__ __launch_bounds__(AT_THREADS) void attn_bwd_dkv_kernel(
+    const float* __restrict__ qkv, const int* __restrict__ lens, const float* __restrict__ lse,
+    const float* __restrict__ dout, float* __restrict__ dqkv, const float* __restrict__ dvec,
+    AtGeo g) {
+  constexpr int DP = DH + 4, NJ = DH / 16;
+  extern __shared__ float4 at_lds4[];
+  float* Ks = reinterpret_cast<float*>(at_lds4);
+  float* Vs = Ks + AT_TILE * DP;
+  float* Qs = Vs + AT_TILE * DP;
+  float* Gs = Qs + AT_TILE * DP;            // dO tile
+  float* Ps = Gs + AT_TILE * DP;
+  float* Ls = Ps + AT_TILE * AT_PP;         // lse (base 2) of the query tile
+  float* Ds = Ls + AT_TILE;                 // D of the query tile
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int k0 = blockIdx.x * AT_TILE, h = blockIdx.y, n = blockIdx.z;
+  const int D = g.heads * DH;
+  const size_t rs = (size_t)g.n_pad * g.ld, rso = (size_t)g.n_pad * g.ld_out;
+  float* d_base = dqkv + (size_t)n * g.ld;
+  if (h == 0) at_zero_cols(d_base, rs, k0, g.T, 3 * D, g.ld - 3 * D, tid);
+  const int len = n < g.N ? at_len(lens, n, g.T) : 0;
+  if (k0 >= len) {          // a padding sample, or a tile of masked keys only
+    at_zero_cols(d_base, rs, k0, g.T, D + h * DH, DH, tid);
+    at_zero_cols(d_base, rs, k0, g.T, 2 * D + h * DH, DH, tid);
+    return;
+  }
+  const float* base = qkv + (size_t)n * g.ld + h * DH;
+  const float* do_base = dout + (size_t)n * g.ld_out + h * DH;
+  at_load_tile<DH>(Ks, base + D, rs, k0, len, tid);
+  at_load_tile<DH>(Vs, base + 2 * D, rs, k0, len, tid);
+  float dk[4][NJ], dv[4][NJ];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) dk[i][jj] = dv[i][jj] = 0.f;
+  for (int q0 = 0; q0 < g.T; q0 += AT_TILE) {
+    at_load_tile<DH>(Qs, base, rs, q0, g.T, tid);
+    at_load_tile<DH>(Gs, do_base, rso, q0, g.T, tid);
+    if (tid < AT_TILE) {
+      const int t = q0 + tid;
+      const size_t li = ((size_t)(t < g.T ? t : 0) * g.n_pad + n) * g.heads + h;
+      Ls[tid] = lse[li] * AT_LOG2E;
+      Ds[tid] = dvec[li];
+    }
+    __syncthreads();
+    float s[4][4], dp[4][4];
+    at_dot<DH>(Ks, Qs, ty, tx, s);          // s[i][j]: key 4 ty + i, query tx + 16 j
+    at_dot<DH>(Vs, Gs, ty, tx, dp);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int q = tx + 16 * j;
+        const bool live = (k0 + 4 * ty + i < len) && (q0 + q < g.T);
+        s[i][j] = live ? exp2f(fmaf(s[i][j], g.c2, -Ls[q])) : 0.f;
+        dp[i][j] = s[i][j] * (dp[i][j] - Ds[q]) * g.scale;
+      }
+    at_put_tile(Ps, s, ty, tx);
+    __syncthreads();
+    at_acc<DH>(Ps, Gs, ty, tx, dv);
+    __syncthreads();
+    at_put_tile(Ps, dp, ty, tx);
+    __syncthreads();
+    at_acc<DH>(Ps, Qs, ty, tx, dk);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int u = k0 + 4 * ty + i;
+    if (u >= g.T) continue;
+    float* row = d_base + (size_t)u * rs + h * DH;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) {       // (rows u >= len accumulated p = 0 only: exact zeros)
+      row[D + tx + 16 * jj] = dk[i][jj];
+      row[2 * D + tx + 16 * jj] = dv[i][jj];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void posenc_add_kernel(const float* __restrict__ x,
+                                                        const float* __restrict__ pe,
+                                                        float* __restrict__ y, long long total,
+                                                        int N, int n_pad, int D, int ld) {
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+       e += (long long)gridDim.x * blockDim.x) {
+    const int f = (int)(e % ld);
+    const long long row = e / ld;
+    const int n = (int)(row % n_pad);
+    const long long t = row / n_pad;
+    y[e] = (n < N && f < D) ? x[e] + pe[t * D + f] : 0.f;
+  }
+}
+
+bool at_geo_ok(const asr_attn_args* a) {
+  if (a == nullptr || a->T < 1 || a->N < 1 || a->n_pad < a->N || a->n_pad > 65535) return false;
+  if (a->heads < 1 || a->heads > 65535 || a->dh < 16 || a->dh > 128 || (a->dh & 15)) return false;
+  const long long D = (long long)a->heads * a->dh;
+  if ((a->ld & 3) || a->ld < 3 * D || (a->ld_out & 3) || a->ld_out < D) return false;
+  return a->scale > 0.f && a->scale < 1e30f;
+}
+
+size_t at_lds_bytes(int dh, int backward) {
+  const size_t tile = (size_t)AT_TILE * (dh + 4) * sizeof(float);
+  const size_t p = (size_t)AT_TILE * AT_PP * sizeof(float);
+  return backward ? 4 * tile + p + 2 * AT_TILE * sizeof(float) : 3 * tile + p;
+}
+
+bool at_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+AtGeo at_geo(const asr_attn_args* a) {
+  AtGeo g;
+  g.T = a->T, g.N = a->N, g.n_pad = a->n_pad, g.heads = a->heads, g.ld = a->ld;
+  g.ld_out = a->ld_out, g.scale = a->scale, g.c2 = a->scale * AT_LOG2E;
+  return g;
+}
+
+template <typename K>
+int at_allow_lds(K kernel, size_t bytes) {
+  ASR_CHECK_HIP(hipFuncSetAttribute((const void*)kernel,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  return ASR_OK;
+}
+
+}  // namespace
+
+#define AT_DISPATCH(LAUNCH)                         \
+  switch (a->dh) {                                  \
+    case 16: LAUNCH(16); break;                     \
+    case 32: LAUNCH(32); break;                     \
+    case 48: LAUNCH(48); break;                     \
+    case 64: LAUNCH(64); break;                     \
+    case 80: LAUNCH(80); break;                     \
+    case 96: LAUNCH(96); break;                     \
+    case 112: LAUNCH(112); break;                   \
+    default: LAUNCH(128); break;                    \
+  }
+
+extern "C" size_t asr_attn_workspace_bytes(const asr_attn_args* a) {
+  if (!at_geo_ok(a)) return 0;
+  return asr_align_up((size_t)a->T * a->n_pad * a->heads * sizeof(float), 256);
+}
+
+extern "C" int asr_attn_plan(const asr_attn_args* a, int backward, int* bq, int* bk, int* blocks,
+                             int* lds_bytes) {
+  ASR_CHECK_ARG(at_geo_ok(a), "attn_plan: bad geometry (dh a multiple of 16 in 16..128, heads "
+                              ">= 1, ld >= 3 heads dh, ld_out >= heads dh, both multiples of 4)");
+  if (bq) *bq = AT_TILE;
+  if (bk) *bk = AT_TILE;
+  if (blocks) *blocks = (a->T + AT_TILE - 1) / AT_TILE * a->heads * a->n_pad;
+  if (lds_bytes) *lds_bytes = (int)at_lds_bytes(a->dh, backward);
+  return ASR_OK;
+}
+
+extern "C" int asr_attn_fwd(const asr_attn_args* a, asr_stream_t stream) {
+  ASR_CHECK_ARG(at_geo_ok(a), "attn_fwd: bad geometry (T %d N %d n_pad %d heads %d dh %d ld %d "
+                "ld_out %d; dh a multiple of 16 in 16..128, ld >= 3 heads dh, ld_out >= heads dh, "
+                "both multiples of 4)", a ? a->T : 0, a ? a->N : 0, a ? a->n_pad : 0,
+                a ? a->heads : 0, a ? a->dh : 0, a ? a->ld : 0, a ? a->ld_out : 0);
+  ASR_CHECK_ARG(a->qkv && a->out && a->out != a->qkv, "attn_fwd: qkv and out are required");
+  ASR_CHECK_ARG(at_aligned(a->qkv) && at_aligned(a->out), "attn_fwd: qkv, out 16-byte aligned");
+  const AtGeo g = at_geo(a);
+  const dim3 grid((a->T + AT_TILE - 1) / AT_TILE, a->heads, a->n_pad);
+  const size_t lds = at_lds_bytes(a->dh, 0);
+#define AT_FWD(DH)                                                                              \
+  {                                                                                             \
+    if (at_allow_lds(attn_fwd_kernel<DH>, lds) != ASR_OK) return ASR_ERR_LAUNCH;                \
+    hipLaunchKernelGGL((attn_fwd_kernel<DH>), grid, dim3(AT_THREADS), lds, (hipStream_t)stream, \
+                       a->qkv, a->lens, a->out, a->lse, g);                                     \
+  }
+  AT_DISPATCH(AT_FWD)
+#undef AT_FWD
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
+}
+
+extern "C" int asr_attn_bwd(const asr_attn_args* a, void* workspace, size_t ws_bytes,
+                            asr_stream_t stream) {
+  ASR_CHECK_ARG(at_geo_ok(a), "attn_bwd: bad geometry (T %d N %d n_pad %d heads %d dh %d ld %d "
+                "ld_out %d)", a ? a->T : 0, a ? a->N : 0, a ? a->n_pad : 0, a ? a->heads : 0,
+                a ? a->dh : 0, a ? a->ld : 0, a ? a->ld_out : 0);
+  ASR_CHECK_ARG(a->qkv && a->out && a->lse && a->dout && a->dqkv && a->dqkv != a->qkv,
+                "attn_bwd: qkv, out, lse, dout and dqkv are required");
+  ASR_CHECK_ARG(at_aligned(a->qkv) && at_aligned(a->dout) && at_aligned(a->dqkv),
+                "attn_bwd: qkv, dout, dqkv 16-byte aligned");
+  const size_t need = asr_attn_workspace_bytes(a);
+  if (workspace == nullptr || ws_bytes < need) {
+    asr_set_error("attn_bwd: workspace too small (%zu bytes needed)", need);
+    return ASR_ERR_WORKSPACE;
+  }
+  const AtGeo g = at_geo(a);
+  float* dvec = (float*)workspace;
+  const dim3 grid((a->T + AT_TILE - 1) / AT_TILE, a->heads, a->n_pad);
+  const size_t lds = at_lds_bytes(a->dh, 1);
+  hipStream_t s = (hipStream_t)stream;
+#define AT_BWD(DH)                                                                              \
+  {                                                                                             \
+    if (at_allow_lds(attn_bwd_dq_kernel<DH>, lds) != ASR_OK) return ASR_ERR_LAUNCH;             \
+    if (at_allow_lds(attn_bwd_dkv_kernel<DH>, lds) != ASR_OK) return ASR_ERR_LAUNCH;            \
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<DH>), grid, dim3(AT_THREADS), lds, s, a->qkv,        \
+                       a->lens, a->out, a->lse, a->dout, a->dqkv, dvec, g);                     \
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<DH>), grid, dim3(AT_THREADS), lds, s, a->qkv,       \
+                       a->lens, a->lse, a->dout, a->dqkv, dvec, g);                             \
+  }
+  AT_DISPATCH(AT_BWD)
+#undef AT_BWD
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
+}
+
+extern "C" int asr_posenc_add(const float* x, const float* pe, float* y, int T, int N, int n_pad,
+                              int D, int ld, asr_stream_t stream) {
+  ASR_CHECK_ARG(x && pe && y, "posenc_add: x, pe, y are required");
+  ASR_CHECK_ARG(T >= 1 && N >= 1 && n_pad >= N && D >= 1 && ld >= D,
+                "posenc_add: bad geometry (T %d N %d n_pad %d D %d ld %d)", T, N, n_pad, D, ld);
+  const long long total = (long long)T * n_pad * ld;
+  const long long want = (total + 255) / 256;
+  const int blocks = (int)(want < 4096 ? want : 4096);
+  hipLaunchKernelGGL(posenc_add_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, pe, y,
+                     total, N, n_pad, D, ld);
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
+}

@@ -5,6 +5,7 @@ torch is used ONLY as a device-memory / stream provider: every function here tak
 ctypes.  No torch.nn, no torch math on the hot path.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -577,6 +578,100 @@ def ln_bwd(x, dy, gain, stats, dx, dgain, dbias, N, H, Hp, segs=1):
                                 _ptr(dgain), _ptr(dbias), *geo, _ptr(ws), nbytes, _stream()),
             'asr_ln_bwd')
     return dx
+
+
+# --------------------------------------------------------------------------- self-attention (K21)
+def _attn_args(qkv, N, heads, dh, ld_out, scale=None, lens=None, out=None, lse=None, dout=None,
+               dqkv=None):
+    T, n_pad, ld = qkv.shape
+    a = L.AttnArgs()
+    a.T, a.N, a.n_pad, a.heads, a.dh = int(T), int(N), int(n_pad), int(heads), int(dh)
+    a.ld, a.ld_out = int(ld), int(ld_out)
+    a.scale = float(scale if scale is not None else 1.0 / math.sqrt(dh))
+    for k, t in (('qkv', qkv), ('lens', lens), ('out', out), ('lse', lse), ('dout', dout),
+                 ('dqkv', dqkv)):
+        setattr(a, k, None if t is None else t.data_ptr())
+    return a
+
+
+def attn_lse_len(T, n_pad, heads):
+    """Floats of the row log-sum-exp block attn_fwd keeps for attn_bwd: (T, n_pad, heads)."""
+    return int(T) * int(n_pad) * int(heads)
+
+
+def attn_plan(T, n_pad, heads, dh, backward=False):
+    """{'bq', 'bk': query / key tile lengths, 'blocks': workgroups of a launch, 'lds': bytes of LDS
+    per workgroup} of the geometry (asr_attn_plan)."""
+    a = L.AttnArgs()
+    a.T, a.N, a.n_pad, a.heads, a.dh = int(T), 1, int(n_pad), int(heads), int(dh)
+    a.ld, a.ld_out, a.scale = 3 * int(heads) * int(dh), int(heads) * int(dh), 1.0
+    v = [C.c_int(0) for _ in range(4)]
+    L.check(L.load().asr_attn_plan(C.byref(a), int(bool(backward)), *[C.byref(x) for x in v]),
+            'asr_attn_plan')
+    return dict(zip(('bq', 'bk', 'blocks', 'lds'), (x.value for x in v)))
+
+
+def attn_fwd(qkv, out, N, heads, dh, lens=None, lse=None, scale=None):
+    """out (T, n_pad, ld_out >= heads dh) = softmax(scale Q K^T) V per real sample and head of the
+    slab qkv (T, n_pad, ld >= 3 heads dh) = [Q | K | V]; keys u >= lens[n] (device int32,
+    1 <= lens <= T) carry probability 0; lse (attn_lse_len) kept for attn_bwd when given."""
+    _check_f32(qkv, out, lse)
+    _check_lens(lens, N)
+    assert qkv.dim() == 3 and out.dim() == 3 and out.shape[:2] == qkv.shape[:2]
+    a = _attn_args(qkv, N, heads, dh, out.shape[2], scale, lens, out, lse)
+    L.check(L.load().asr_attn_fwd(C.byref(a), _stream()), 'asr_attn_fwd')
+    return out
+
+
+def attn_bwd(qkv, out, lse, dout, dqkv, N, heads, dh, lens=None, scale=None):
+    """dqkv (like qkv) = dQ | dK | dV from dout (like out), recomputing p from lse."""
+    _check_f32(qkv, out, lse, dout, dqkv)
+    _check_lens(lens, N)
+    assert dqkv.shape == qkv.shape and dout.shape == out.shape
+    a = _attn_args(qkv, N, heads, dh, out.shape[2], scale, lens, out, lse, dout, dqkv)
+    nbytes = L.load().asr_attn_workspace_bytes(C.byref(a))
+    if nbytes == 0:
+        L.check(-1, 'asr_attn_workspace_bytes (T %d N %d n_pad %d heads %d dh %d ld %d ld_out %d)'
+                % (a.T, a.N, a.n_pad, a.heads, a.dh, a.ld, a.ld_out))
+    ws = WS.get('attn', nbytes, qkv.device)
+    L.check(L.load().asr_attn_bwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_attn_bwd')
+    return dqkv
+
+
+def posenc_table(T, D):
+    """The (T, D) sinusoidal table in float64 (host): pe[t, 2i] = sin(t / 10000^(2i / D)),
+    pe[t, 2i + 1] = cos(t / 10000^(2i / D))."""
+    t = np.arange(int(T), dtype=np.float64)[:, None]
+    i2 = (np.arange(int(D)) // 2 * 2).astype(np.float64)[None, :]
+    ang = t / np.power(10000.0, i2 / float(D))
+    return np.where(np.arange(int(D))[None, :] % 2 == 0, np.sin(ang), np.cos(ang))
+
+
+_PE = {}
+
+
+def posenc_get(T, D, device):
+    """The table rounded to fp32 on the device, computed and uploaded once per (T, D)."""
+    key = (int(T), int(D), str(device))
+    pe = _PE.get(key)
+    if pe is None:
+        if len(_PE) >= 64:
+            _PE.clear()
+        pe = _PE[key] = torch.from_numpy(posenc_table(T, D).astype(np.float32)).to(device)
+    return pe
+
+
+def posenc_add(x, y, N, D, pe=None):
+    """y[t, n, f] = x[t, n, f] + pe[t, f] for n < N, f < D of the slab x (T, n_pad, ld); zeros in
+    the pad rows and columns."""
+    _check_f32(x, y, pe)
+    T, n_pad, ld = x.shape
+    if pe is None:
+        pe = posenc_get(T, D, x.device)
+    assert tuple(pe.shape) == (T, D) and y.shape == x.shape
+    L.check(L.load().asr_posenc_add(_ptr(x), _ptr(pe), _ptr(y), int(T), int(N), int(n_pad),
+                                    int(D), int(ld), _stream()), 'asr_posenc_add')
+    return y
 
 
 # --------------------------------------------------------------------------- sequence-wise BN (K18)

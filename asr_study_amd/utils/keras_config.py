@@ -217,6 +217,15 @@ def model_config(model):
             add('LayerNormalization', name, {
                 'name': name, 'trainable': True, 'epsilon': float(s.eps), 'gain_init': 'one',
                 'bias_init': 'zero'}, [prev])
+        elif s.kind == 'mha':
+            name = nm('multiheadattention')
+            add('MultiHeadAttention', name, {
+                'name': name, 'trainable': True, 'num_heads': int(s.heads),
+                'head_dim': int(s.dh), 'output_dim': int(s.n_out),
+                'W_regularizer': _regularizer(s.l2), 'attention_dropout': 0.0}, [prev])
+        elif s.kind == 'posenc':
+            name = nm('positionalencoding')
+            add('PositionalEncoding', name, {'name': name, 'trainable': True}, [prev])
         elif s.kind == 'reshape':
             name = nm('reshape')
             add('Reshape', name, {'name': name, 'trainable': True,
@@ -348,6 +357,13 @@ def topology_from_config(text):
             o = L.LayerNormalization(epsilon=c.get('epsilon', 1e-5),
                                      gain_init=c.get('gain_init', 'one'),
                                      bias_init=c.get('bias_init', 'zero'))(o)
+        elif kind == 'MultiHeadAttention':
+            o = L.MultiHeadAttention(c['num_heads'], head_dim=c.get('head_dim'),
+                                     output_dim=c.get('output_dim'),
+                                     W_regularizer=reg(c.get('W_regularizer')),
+                                     attention_dropout=c.get('attention_dropout', 0.))(o)
+        elif kind == 'PositionalEncoding':
+            o = L.PositionalEncoding()(o)
         elif kind == 'TimeDistributed' and c['layer']['class_name'] == 'Activation':
             o = L.TimeDistributed(L.Activation(_act_from(c['layer']['config'])))(o)
         elif kind == 'TimeDistributed' and c['layer']['class_name'] == 'Dropout':

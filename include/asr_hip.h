@@ -701,6 +701,57 @@ int asr_ln_bwd(const float* x, const float* dy, const float* gain, const float* 
                int segs, void* workspace, size_t ws_bytes, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
+/* K21 multi-head self-attention core, fused, forward and backward           */
+/* (arXiv 1706.03762; csrc/attention.hip).  qkv is a time-major slab         */
+/* (T, n_pad, ld >= 3D), column blocks [Q | K | V] of D = heads * dh columns */
+/* each, head h in columns h dh .. (h + 1) dh - 1 of its block (what one     */
+/* x @ W_qkv + b_qkv GEMM writes).  For every real sample n < N, head h and  */
+/* query frame t (all T frames are queries; only keys are masked):           */
+/*   s[t,u] = scale q_t . k_u   for u < lens[n]  (u < T when lens is NULL)   */
+/*   p      = softmax_u(s)      keys u >= lens[n] carry probability exactly 0*/
+/*   out_t  = sum_u p[t,u] v_u,   lse_t = log sum_u exp s[t,u]               */
+/* Backward, with D_t = dout_t . out_t:  dV = P^T dO,                        */
+/*   dS = P (.) (dO V^T - D),  dQ = scale dS K,  dK = scale dS^T Q;          */
+/*   masked keys get dK = dV = exactly 0.                                    */
+/* Rows n >= N and the pad columns (>= D of out, >= 3D of dqkv) are written  */
+/* as exact zeros.  The T x T scores never reach memory: 64-frame query and  */
+/* key tiles go through LDS with a running maximum / sum (forward) or p      */
+/* recomputed from lse (backward).  Exact fp32 products (FMA), fp32 sums,    */
+/* base-2 exponentials; no float atomics (bit-identical repeats); no         */
+/* workgroup waits on another.  dh a multiple of 16 in 16 .. 128, heads >= 1,*/
+/* any T >= 1, ld and ld_out multiples of 4, 16-byte aligned slabs; anything */
+/* else is ASR_ERR_INVALID.                                                  */
+/* ------------------------------------------------------------------------ */
+typedef struct asr_attn_args {
+  int T, N, n_pad;       /* frames, real samples, padded samples per frame               */
+  int heads, dh;         /* D = heads * dh                                               */
+  int ld, ld_out;        /* floats per (t, n) row of qkv / dqkv and of out / dout        */
+  float scale;           /* of the scores, usually 1 / sqrt(dh)                          */
+  const float* qkv;      /* (T, n_pad, ld)                                               */
+  const int* lens;       /* optional device int32 (N): 1 <= lens[n] <= T valid keys      */
+                         /*   (a value outside is clamped into that range)               */
+  float* out;            /* (T, n_pad, ld_out): forward writes it, backward reads it     */
+  float* lse;            /* (T, n_pad, heads): forward writes it when not NULL (real     */
+                         /*   samples only), backward reads it                           */
+  const float* dout;     /* backward: (T, n_pad, ld_out)                                 */
+  float* dqkv;           /* backward: (T, n_pad, ld), dQ | dK | dV                       */
+} asr_attn_args;
+/* Workspace of asr_attn_bwd (D of every row); 0 for a geometry that is refused.             */
+size_t asr_attn_workspace_bytes(const asr_attn_args* a);
+int asr_attn_fwd(const asr_attn_args* a, asr_stream_t stream);
+int asr_attn_bwd(const asr_attn_args* a, void* workspace, size_t ws_bytes, asr_stream_t stream);
+/* The geometry the library runs: query and key tile lengths, workgroups of one launch, LDS   */
+/* bytes per workgroup (any pointer may be NULL).                                             */
+int asr_attn_plan(const asr_attn_args* a, int backward, int* bq, int* bk, int* blocks,
+                  int* lds_bytes);
+/* Sinusoidal positional encoding added to a slab: y[t, n, f] = x[t, n, f] + pe[t, f] for    */
+/* n < N and f < D, zeros elsewhere; x, y (T, n_pad, ld >= D), pe (T, D) with                 */
+/* pe[t, 2i] = sin(t / 10000^(2i / D)), pe[t, 2i + 1] = cos(t / 10000^(2i / D)), computed by  */
+/* the caller (in float64, rounded once).  Its backward pass is the identity.                */
+int asr_posenc_add(const float* x, const float* pe, float* y, int T, int N, int n_pad, int D,
+                   int ld, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
 /* K7  CTC loss + gradient.  Replaces core/ctc_utils.py:60-70 ->             */
 /* tf.nn.ctc_loss (blank = C-1, internal softmax, ctc_merge_repeated=True).  */
 /* logits/grad: (T, n_pad, C) time-major.  labels (N, l_max) int32 padded,   */
