@@ -284,6 +284,14 @@ SIGNATURES = {
     'asr_attn_bwd': (C.c_int, [C.POINTER(AttnArgs), void_p, C.c_size_t, void_p]),
     'asr_attn_plan': (C.c_int, [C.POINTER(AttnArgs), C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
     'asr_posenc_add': (C.c_int, [void_p] * 3 + [C.c_int] * 5 + [void_p]),
+    'asr_dwconv1d_workspace_bytes': (C.c_size_t, [C.c_int] * 6),
+    'asr_dwconv1d_plan': (C.c_int, [C.c_int] * 7 + [c_int_p] * 3),
+    'asr_dwconv1d_fwd': (C.c_int, [void_p] * 5 + [C.c_int] * 6 + [void_p]),
+    'asr_dwconv1d_bwd': (C.c_int, [void_p] * 7 + [C.c_int] * 6 + [void_p, C.c_size_t, void_p]),
+    'asr_glu_fwd': (C.c_int, [void_p] * 2 + [C.c_int64] + [C.c_int] * 3 + [void_p]),
+    'asr_glu_bwd': (C.c_int, [void_p] * 3 + [C.c_int64] + [C.c_int] * 3 + [void_p]),
+    'asr_swish_fwd': (C.c_int, [void_p] * 2 + [C.c_int64, void_p]),
+    'asr_swish_bwd': (C.c_int, [void_p] * 3 + [C.c_int64, void_p]),
     # operation-level entry points (csrc/roles.cpp)
     'asr_frontend_mfcc_batch': (C.c_int, [C.POINTER(FrontendCfg), void_p, void_p, void_p,
                                           c_int_p, C.c_int, C.c_int, void_p, void_p, void_p,

@@ -309,8 +309,31 @@ class Model(object):
                 f_real = f_pad = s.n_out
             elif s.kind == 'posenc':
                 s.D = f_real                    # (no parameters: the table depends on (T, D) only)
+            elif s.kind == 'dwconv':
+                # depthwise convolution over time (K22, csrc/dwconv.hip); its limits are checked
+                # here, when the model is built, not at the first launch
+                s.k, s.C, s.l2 = int(st['k']), f_real, float(st.get('l2', 0.0))
+                if s.k < 1 or s.k > ops.DWCONV_MAX_KERNEL or s.k % 2 == 0:
+                    raise NotImplementedError(
+                        "DepthwiseConvolution1D: kernel_size %d (odd, in 1 .. %d: 'same' padding, "
+                        'the tile of asr_dwconv1d_*)' % (s.k, ops.DWCONV_MAX_KERNEL))
+                if f_real % 4 or f_pad != f_real:
+                    raise NotImplementedError(
+                        'DepthwiseConvolution1D over %d channels (%d columns): the width must be '
+                        'a multiple of 4 without pad columns' % (f_real, f_pad))
+                s.tensors = P.dwconv(s, alloc, None)
+            elif s.kind == 'glu':
+                if f_real % 8 or f_pad != f_real:
+                    raise NotImplementedError(
+                        'GLU over %d features (%d columns): the width must be a multiple of 8 '
+                        'without pad columns' % (f_real, f_pad))
+                s.C = f_real // 2
+                f_real = f_pad = s.C
             elif s.kind == 'merge':
                 s.mode, s.skip = st['mode'], int(st['skip'])
+                s.scale = float(st.get('scale', 1.0))   # of the first input ('sum' only)
+                if s.scale != 1.0 and s.mode != 'sum':
+                    raise NotImplementedError("merge(scale=%r): with mode='sum' only" % s.scale)
                 src = self.stages[s.skip]
                 if (src.f_out, src.f_out_pad) != (f_real, f_pad):
                     raise ValueError('merge: widths differ (%d vs %d)' % (src.f_out, f_real))
@@ -325,7 +348,9 @@ class Model(object):
                        (self._packed_mode == '1' or (self._packed_mode == 'auto' and widest >= 512)))
         self.num_classes = f_real
         self._has_rnn = any(st.kind == 'birnn' for st in self.stages)
-        self._has_mha = any(st.kind == 'mha' for st in self.stages)     # forward needs seq_len
+        # forward needs seq_len: the attention keys and the depthwise convolution's frames
+        self._has_mha = any(st.kind == 'mha' for st in self.stages)
+        self._needs_lens = self._has_mha or any(st.kind == 'dwconv' for st in self.stages)
         self._bn = [(i, st) for i, st in enumerate(self.stages) if st.kind == 'bn']
         self._seqbn = [(i, st) for i, st in enumerate(self.stages)
                        if st.kind == 'bigru' and st.bn]
@@ -339,6 +364,17 @@ class Model(object):
                     and i not in skips and os.environ.get('ASR_BN_FUSE', '1') != '0'):
                 st.clip = float(nxt.act[1])
                 nxt.fused = True
+        for i, st in enumerate(self.stages):
+            # a depthwise convolution straight in front of a per-column BatchNormalization: the
+            # batch mean takes its bias out again, so the bias gradient (the sum of the BN input
+            # gradient over exactly the frames BN averages) is identically 0.  A column sum
+            # would leave rounding noise there, which Adam would normalise into steps of +-lr:
+            # it is never produced and keeps the zero the gradient buffer is created with (as
+            # the key bias of the mha stage).
+            if st.kind == 'dwconv':
+                nxt = self.stages[i + 1] if i + 1 < len(self.stages) else None
+                st.bias_dead = (nxt is not None and nxt.kind == 'bn' and not nxt.grouped
+                                and i not in skips)
         self.time_strides = [st.st for st in self.stages if st.kind == 'conv' and st.st > 1]
         self._convs = {}
         self.n_params = off = alloc.params
@@ -571,8 +607,8 @@ class Model(object):
         this rank contributes to the running moments (default n_real; 0 = a zero-weight dummy).
         seq_len: device int32 lengths of the real samples on the recurrent stack's time axis (what
         CTC gets): the valid frames of a GRU(batch_norm=True) stage's training statistics and the
-        visible keys of a MultiHeadAttention stage, in training and inference (None: every
-        frame).
+        visible keys of a MultiHeadAttention stage and the frames a DepthwiseConvolution1D stage
+        reads, in training and inference (None: every frame).
 
         masks: optional explicit variational-dropout masks (parity tests):
         {stage_index: (BW (2, n_pad, f_in_pad), BU (2, n_pad, Hp))}.
@@ -649,9 +685,9 @@ class Model(object):
                     a = ops.dropout_apply(a, out, keep, s.value, 1.0 / (1.0 - s.value),
                                           self.rng_seed, 4 * si, self._step)
                     rec['mask'] = keep
-            elif s.kind == 'merge':       # residual: c * (new + skip)
+            elif s.kind == 'merge':       # residual: c * (scale * new + skip)
                 out = self._buf('merge%d' % si, a.shape)
-                a = ops.axpby(s.coef, a, s.coef, self._acts[s.skip]['out'], out)
+                a = ops.axpby(s.coef * s.scale, a, s.coef, self._acts[s.skip]['out'], out)
             elif s.kind == 'dense':
                 out = self._buf('dense%d' % si, (T, n_pad, s.n_out))
                 ops.gemm(a, self.params, out, rows, s.n_out, s.f_in_pad, b_off=s.oW,
@@ -765,6 +801,17 @@ class Model(object):
                 if not getattr(s, 'fused', False):     # (else applied by the BN stage before)
                     out = self._buf('act%d' % si, a.shape)
                     a = ops.activation_fwd(a.contiguous(), out, s.act)
+            elif s.kind == 'dwconv':
+                N = min(n_real, n_pad)
+                a = a.contiguous()
+                rec.update(**{'in': a, 'N': N, 'lens': seq_len})
+                out = self._buf('dwconv%d' % si, a.shape)
+                a = ops.dwconv1d_fwd(a, self._view(s.oW, s.k * s.C), self._view(s.ob, s.C), out,
+                                     N, s.k, lens=seq_len)
+            elif s.kind == 'glu':
+                a = a.contiguous()
+                rec['in'] = a
+                a = ops.glu_fwd(a, self._buf('glu%d' % si, (T, n_pad, s.C)))
             elif s.kind == 'bn':
                 a = self._bn_forward(s, si, a.contiguous(), rec, training, n_real, bn_weight)
             elif s.kind == 'ln':
@@ -1377,9 +1424,11 @@ class Model(object):
                 if s.coef != 1.0:
                     da = ops.axpby(s.coef, da, 0.0, da, self._buf('dmerge%d' % si, da.shape))
                 skip_grads[s.skip] = da
+                if s.scale != 1.0:          # the branch gets scale * d, the skip d
+                    da = ops.axpby(s.scale, da, 0.0, da, self._buf('dscale%d' % si, da.shape))
                 continue
             first = not any(st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn', 'bigru', 'birhn',
-                                        'ln', 'mha')
+                                        'ln', 'mha', 'dwconv')
                             for st in self.stages[:si])
             if s.kind in ('noise', 'reshape', 'posenc'):    # (posenc: d(x + pe) / dx = 1)
                 continue
@@ -1406,8 +1455,24 @@ class Model(object):
                 continue
             if s.kind == 'act':
                 if not first and not getattr(s, 'fused', False):
+                    # (swish: its derivative is read from the stage INPUT)
                     da = ops.activation_bwd(da.contiguous(), rec['out'],
-                                            self._buf('dact%d' % si, da.shape), s.act)
+                                            self._buf('dact%d' % si, da.shape), s.act,
+                                            x=a_in.contiguous() if s.act == 'swish' else None)
+                continue
+            if s.kind == 'glu':
+                if not first:
+                    da = ops.glu_bwd(a_in, da.contiguous(), self._buf('dglu%d' % si, a_in.shape))
+                continue
+            if s.kind == 'dwconv':
+                # dW / db into the gradients, dx behind the same length mask
+                dx = None if first else self._buf('ddwconv%d' % si, a_in.shape)
+                ops.dwconv1d_bwd(a_in, self._view(s.oW, s.k * s.C), da.contiguous(), dx,
+                                 self._gview(s.oW, s.k * s.C),
+                                 self._buf('dwdb%d' % si, (s.C,)) if s.bias_dead
+                                 else self._gview(s.ob, s.C), rec['N'], s.k, lens=rec['lens'])
+                if dx is not None:
+                    da = dx
                 continue
             if s.kind == 'bn':
                 # dgamma / dbeta into the gradients, dx from the saved statistics (x re-read)
@@ -1736,12 +1801,14 @@ class Model(object):
     # ------------------------------------------------------------------ batches
     def _key_lens(self, lens, T):
         """lens: host lengths on the logits' time axis of a batch of T input frames.  A model
-        with a MultiHeadAttention stage refuses lengths outside 1 .. out_frames(T) here, while
-        they are on the host (the kernel would clamp them silently)."""
+        with a MultiHeadAttention or DepthwiseConvolution1D stage refuses lengths outside
+        1 .. out_frames(T) here, while they are on the host (the kernels would clamp them
+        silently)."""
         lens = np.asarray(lens).reshape(-1)
-        if self._has_mha and lens.size and (lens.min() < 1 or lens.max() > self.out_frames(T)):
+        if self._needs_lens and lens.size and (lens.min() < 1 or lens.max() > self.out_frames(T)):
             raise ValueError('inputs_length: every utterance needs 1 .. %d frames on the '
-                             'attention layers\' time axis (%d input frames), got %d .. %d'
+                             'attention / convolution layers\' time axis (%d input frames), '
+                             'got %d .. %d'
                              % (self.out_frames(T), T, lens.min(), lens.max()))
         return lens
 
@@ -2000,7 +2067,7 @@ class Model(object):
         N = len(labels)
         lab, lab_len, sl = self._prep_labels(labels, lens, slab.shape[0])
         logits = self.forward(slab, training=False, need_grad=False, n_valid=N,
-                              seq_len=sl if self._has_mha else None)
+                              seq_len=sl if self._needs_lens else None)
         ctc = ops.ctc_loss_grad(logits, lab, lab_len, sl, N, grad=None)
         hyps = None
         dec = dlen = None
@@ -2035,11 +2102,11 @@ class Model(object):
         N = len(inputs_length) if inputs_length is not None else slab.shape[1]
         lens = np.asarray(inputs_length if inputs_length is not None else [slab.shape[0]] * N).reshape(-1)
         sl = None
-        if self._has_mha or self.decoder is not None:
+        if self._needs_lens or self.decoder is not None:
             sl = self._key_lens(self.out_lengths(lens), slab.shape[0]).astype(np.int32)
             sl = torch.as_tensor(sl).to(self.device)
         logits = self.forward(slab, training=False, need_grad=False, n_valid=N,
-                              seq_len=sl if self._has_mha else None)
+                              seq_len=sl if self._needs_lens else None)
         if self.decoder is None:
             return logits[:, :N].permute(1, 0, 2).contiguous().cpu().numpy()
         if self.decoder.get('is_greedy', True):
@@ -2065,7 +2132,7 @@ class Model(object):
         lens = np.asarray(inputs_length).reshape(-1)
         lab, lab_len, sl = self._prep_labels(labels, lens, slab.shape[0])
         logits = self.forward(slab, training=False, need_grad=False, n_valid=N,
-                              seq_len=sl if self._has_mha else None)
+                              seq_len=sl if self._needs_lens else None)
         from .ctc_utils import align_paths
         path, score = align_paths(logits, lab, lab_len, sl, N)
         sl_h = sl.cpu().numpy()

@@ -19,6 +19,8 @@ bare or on the (N, T, F, C) image of the convolution front-end (csrc/batchnorm.h
 frame over its features on csrc/layernorm.hip.
 ``MultiHeadAttention`` and ``PositionalEncoding`` (no reference counterpart) run on
 csrc/attention.hip and make the ``transformer`` factory.
+``DepthwiseConvolution1D``, ``GLU``, ``Activation('swish')`` and ``merge(..., scale=)`` (no
+reference counterpart either) run on csrc/dwconv.hip and make the ``conformer`` factory.
 """
 
 
@@ -331,12 +333,14 @@ class RHN(object):
 
 
 class Activation(Layer):
-    """keras.layers.Activation: 'tanh', 'relu', 'linear' or ``clipped_relu(max_value)``,
-    element-wise (bare or inside TimeDistributed)."""
+    """keras.layers.Activation: 'tanh', 'relu', 'linear', ``clipped_relu(max_value)`` or 'swish'
+    (x sigmoid(x); this layer only, no recurrent layer takes it), element-wise (bare or inside
+    TimeDistributed)."""
 
     def __init__(self, activation):
         from .. import ops
-        ops.rnn_activation_id(activation)           # NotImplementedError for anything else
+        if activation != 'swish':
+            ops.rnn_activation_id(activation)       # NotImplementedError for anything else
         self.activation = activation
 
 
@@ -379,20 +383,25 @@ class Bidirectional(Layer):
 
 class Merge(Layer):
     """keras.layers.merge([a, b], mode): element-wise 'sum' or 'ave' of two tensors of
-    the same width (brsmv1's residual connection, core/models.py:273-276)."""
+    the same width (brsmv1's residual connection, core/models.py:273-276).  ``scale`` (not in
+    Keras) weighs the FIRST input of a 'sum': out = scale * a + b, the half-step residual of a
+    Conformer's feed-forward modules."""
 
-    def __init__(self, mode, skip):
+    def __init__(self, mode, skip, scale=1.0):
         if mode not in ('sum', 'ave'):
             raise NotImplementedError('merge mode %r (implemented: sum, ave)' % (mode,))
+        if float(scale) != 1.0 and mode != 'sum':
+            raise NotImplementedError("merge(scale=%r): with mode='sum' only" % (scale,))
         self.mode = mode
         self.skip = skip
+        self.scale = float(scale)
 
 
-def merge(inputs, mode=None):
+def merge(inputs, mode=None, scale=1.0):
     a, b = inputs
     if a.features != b.features:
         raise ValueError('merge: widths differ (%s vs %s)' % (a.features, b.features))
-    return Merge(mode, b)(a)
+    return Merge(mode, b, scale)(a)
 
 
 
@@ -535,6 +544,61 @@ class PositionalEncoding(Layer):
     def __init__(self, **kwargs):
         if kwargs:
             raise NotImplementedError('PositionalEncoding: unknown arguments %s' % sorted(kwargs))
+
+
+class DepthwiseConvolution1D(Layer):
+    """A depthwise convolution over the time axis of an (N, T, C) tensor (the convolution of a
+    Conformer's convolution module, arXiv 2005.08100) on csrc/dwconv.hip: one filter of
+    ``kernel_size`` taps per channel, cross-correlation with 'same' padding,
+
+        y[t, c] = b[c] + sum_j W[j, c] x[t + j - (k - 1) / 2, c]
+
+    where the frames at or past the utterance's length (the lengths the model is called with)
+    count as the zero padding, like the frames before 0: an utterance's valid frames do not
+    depend on how far its batch is padded.  Every frame is an output.  Weights: W (k, C), b (C);
+    W_regularizer (l2) applies to W.  kernel_size is odd, in 1 .. 63; the input width is a
+    multiple of 4.  Straight in front of a BatchNormalization the bias has no effect on the
+    training output (the batch mean takes it out); its gradient is then exactly zero and b keeps
+    its value.  Not built: strides, dilation, a depth multiplier, causal padding."""
+
+    MAX_KERNEL = 63
+
+    def __init__(self, kernel_size, W_regularizer=None, **kwargs):
+        if kwargs:
+            raise NotImplementedError('DepthwiseConvolution1D: unknown arguments %s'
+                                      % sorted(kwargs))
+        if (int(kernel_size) != kernel_size or kernel_size < 1 or kernel_size > self.MAX_KERNEL
+                or int(kernel_size) % 2 == 0):
+            raise NotImplementedError('DepthwiseConvolution1D: kernel_size %r (an odd integer in '
+                                      "1 .. %d: 'same' padding, the tile of asr_dwconv1d_*)"
+                                      % (kernel_size, self.MAX_KERNEL))
+        self.kernel_size = int(kernel_size)
+        self.l2 = W_regularizer.l2 if W_regularizer is not None else 0.0
+
+    def __call__(self, x):
+        if x.features % 4:
+            raise NotImplementedError('DepthwiseConvolution1D over %d channels: the width must '
+                                      'be a multiple of 4' % x.features)
+        return Layer.__call__(self, x)
+
+
+class GLU(Layer):
+    """Gated linear unit over the feature axis (arXiv 1612.08083): y = a * sigmoid(g) with
+    [a | g] the two halves of the input.  No weights; the width halves.  The input width must
+    be a multiple of 8."""
+
+    def __init__(self, **kwargs):
+        if kwargs:
+            raise NotImplementedError('GLU: unknown arguments %s' % sorted(kwargs))
+
+    def __call__(self, x):
+        if x.features % 8:
+            raise NotImplementedError('GLU over %d features: the width must be a multiple of 8 '
+                                      '(two halves of whole 16-byte groups)' % x.features)
+        return Layer.__call__(self, x)
+
+    def out_features(self, f):
+        return f // 2
 
 
 class Reshape(Layer):

@@ -2,7 +2,7 @@
 (core/models.py): ``ctc_model``, ``graves2006``, ``eyben``, ``maas``, ``deep_speech``,
 ``brsmv1``, plus this build's ``deep_speech2`` (BiLSTM or, with ``rnn_type='gru'``, BiGRU) and
 ``rhn`` (brsmv1's topology on the reference's own RHN cell) and ``transformer`` (a pre-LN
-self-attention encoder, csrc/attention.hip).
+self-attention encoder, csrc/attention.hip) and ``conformer`` (arXiv 2005.08100, csrc/dwconv.hip).
 
 ``train.py`` resolves them by name -- ``get_from_module('core.models', 'brsmv1')
 (**hparams)`` (train.py:127-129) -- and gets back an object with the Keras
@@ -17,7 +17,7 @@ from .engine import Model
 from .layers import (Input, GaussianNoise, TimeDistributed, Dense, LSTM, Bidirectional,
                      Dropout, Merge, merge, l2, Reshape, Convolution2D, clipped_relu, SimpleRNN,
                      Activation, BatchNormalization, GRU, RHN, LayerNormalization,
-                     MultiHeadAttention, PositionalEncoding)
+                     MultiHeadAttention, PositionalEncoding, DepthwiseConvolution1D, GLU)
 
 
 def ctc_model(inputs, output, **kwargs):
@@ -47,6 +47,8 @@ def ctc_model(inputs, output, **kwargs):
             if not src:
                 raise ValueError('merge: the skip input is not on the path from inputs')
             spec.append({'type': 'merge', 'mode': layer.mode, 'skip': src[0]})
+            if layer.scale != 1.0:  # (only then: the spec of every other model is unchanged)
+                spec[-1]['scale'] = layer.scale
         elif isinstance(layer, Reshape):
             spec.append({'type': 'reshape', 'target': list(layer.target)})   # a view: no data moves
         elif isinstance(layer, Convolution2D):
@@ -65,6 +67,10 @@ def ctc_model(inputs, output, **kwargs):
                          'n_out': layer.output_dim, 'l2': layer.l2})
         elif isinstance(layer, PositionalEncoding):
             spec.append({'type': 'posenc'})
+        elif isinstance(layer, DepthwiseConvolution1D):
+            spec.append({'type': 'dwconv', 'k': layer.kernel_size, 'l2': layer.l2})
+        elif isinstance(layer, GLU):
+            spec.append({'type': 'glu'})
         elif isinstance(layer, TimeDistributed) and layer.dense is None:
             spec.append(_elementwise_spec(layer.layer, wrapped=True))
         elif isinstance(layer, (Dropout, Activation)):
@@ -390,4 +396,72 @@ def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_l
         num_heads=num_heads, num_layers=num_layers, d_ff=d_ff, dropout=dropout, conv=conv,
         conv_filters=conv_filters, conv_kernels=[list(k) for k in conv_kernels],
         weight_decay=weight_decay)}
+    return model
+
+
+def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_layers=6,
+              d_ff=1024, kernel_size=31, conv_norm='batch', dropout=0.1, conv=True,
+              conv_filters=32, conv_kernels=((11, 41), (11, 21)), weight_decay=0., **kw):
+    """A CTC-trained Conformer encoder (arXiv 2005.08100).  NO REFERENCE COUNTERPART.  The
+    front-end and input projection of ``transformer`` (conv=True: deep_speech2's two strided
+    Convolution2D; then TimeDistributed(Dense(d_model)), PositionalEncoding, Dropout), then
+    ``num_layers`` blocks, with FFN(x) = Dense(d_model)(swish(Dense(d_ff)(LN(x)))):
+
+        x = merge([Dropout(FFN(x)), x], 'sum', scale=0.5)               half-step feed-forward
+        x = merge([Dropout(MultiHeadAttention(num_heads)(LN(x))), x], 'sum')
+        x = merge([Dropout(Dense(d_model)(swish(Norm(DepthwiseConvolution1D(kernel_size)(
+                   GLU(Dense(2 d_model)(LN(x)))))))), x], 'sum')          convolution module
+        x = merge([Dropout(FFN(x)), x], 'sum', scale=0.5)
+        x = LN(x)
+
+    and TimeDistributed(Dense(num_classes)).  conv_norm: 'batch' (the paper: BatchNormalization,
+    with this library's semantics: training statistics over every frame of the real samples, time
+    padding included) or 'layer' (LayerNormalization).  The attention keys and the depthwise
+    convolution's input of an utterance are its valid frames (the strided lengths).  Positions
+    are the absolute sinusoidal table: the paper's relative positional attention is not built.
+    weight_decay: l2 on every matrix and depthwise filter."""
+    if conv_norm not in ('batch', 'layer'):
+        raise ValueError("conformer(conv_norm=%r): 'batch' or 'layer'" % (conv_norm,))
+    reg = l2(weight_decay)
+    x = Input(name='inputs', shape=(None, num_features))
+    o = x
+    if conv:
+        o = Reshape((-1, num_features, 1))(o)
+        for (kt, kf), (st, sf) in zip(conv_kernels, ((2, 2), (1, 2))):
+            o = Convolution2D(conv_filters, kt, kf, subsample=(st, sf), border_mode='same',
+                              activation=clipped_relu(20), W_regularizer=reg)(o)
+        o = Reshape((-1, o.features))(o)
+    o = TimeDistributed(Dense(d_model, W_regularizer=reg))(o)
+    o = PositionalEncoding()(o)
+    o = Dropout(dropout)(o)
+
+    def ffn(o):
+        y = LayerNormalization()(o)
+        y = TimeDistributed(Dense(d_ff, W_regularizer=reg))(y)
+        y = Activation('swish')(y)
+        y = TimeDistributed(Dense(d_model, W_regularizer=reg))(y)
+        return merge([Dropout(dropout)(y), o], mode='sum', scale=0.5)
+
+    for _ in range(num_layers):
+        o = ffn(o)
+        y = LayerNormalization()(o)
+        y = MultiHeadAttention(num_heads, W_regularizer=reg)(y)
+        o = merge([Dropout(dropout)(y), o], mode='sum')
+        y = LayerNormalization()(o)
+        y = TimeDistributed(Dense(2 * d_model, W_regularizer=reg))(y)
+        y = GLU()(y)
+        y = DepthwiseConvolution1D(kernel_size, W_regularizer=reg)(y)
+        y = BatchNormalization()(y) if conv_norm == 'batch' else LayerNormalization()(y)
+        y = Activation('swish')(y)
+        y = TimeDistributed(Dense(d_model, W_regularizer=reg))(y)
+        o = merge([Dropout(dropout)(y), o], mode='sum')
+        o = ffn(o)
+        o = LayerNormalization()(o)
+    o = TimeDistributed(Dense(num_classes, W_regularizer=reg))(o)
+    model = ctc_model(x, o, **kw)
+    model.config = {'name': 'conformer', 'kwargs': dict(
+        num_features=num_features, num_classes=num_classes, d_model=d_model,
+        num_heads=num_heads, num_layers=num_layers, d_ff=d_ff, kernel_size=kernel_size,
+        conv_norm=conv_norm, dropout=dropout, conv=conv, conv_filters=conv_filters,
+        conv_kernels=[list(k) for k in conv_kernels], weight_decay=weight_decay)}
     return model

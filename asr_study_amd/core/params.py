@@ -142,7 +142,8 @@ def keras_names(stages):
     counts the TimeDistributed(Dropout / Activation) layers with those."""
     groups = {'convolution2d': 'convolution2d', 'batchnormalization': 'batchnormalization',
               'layernormalization': 'layernormalization',
-              'multiheadattention': 'multiheadattention', 'dense': 'timedistributed'}
+              'multiheadattention': 'multiheadattention',
+              'depthwiseconvolution1d': 'depthwiseconvolution1d', 'dense': 'timedistributed'}
     out, n = [], Counter()
     for s in stages:
         if not s.tensors:
@@ -328,3 +329,12 @@ def mha(s, alloc, rows):
             Tensor(layer, 'W_o', (D, s.n_out), s.oWo, (D, s.n_out), (), l2=s.l2,
                    init=_glorot(D, s.n_out)),
             Tensor(layer, 'b_o', (s.n_out,), s.obo, (s.n_out,), ())]
+
+
+def dwconv(s, alloc, rows):
+    """DepthwiseConvolution1D (csrc/dwconv.hip): W (k, C) tap major, glorot-uniform with fan_in =
+    fan_out = k (one filter per channel: limit sqrt(3 / k)), b (C); l2 on W."""
+    layer = 'depthwiseconvolution1d'
+    s.oW, s.ob = alloc.take(s.k * s.C), alloc.take(s.C)
+    return [Tensor(layer, 'W', (s.k, s.C), s.oW, (s.k, s.C), (), l2=s.l2, init=_glorot(s.k, s.k)),
+            Tensor(layer, 'b', (s.C,), s.ob, (s.C,), ())]

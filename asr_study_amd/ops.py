@@ -371,15 +371,20 @@ def rnn_plan(T, n_pad, H, backward=False, mode=0):
 def activation_fwd(x, y, act):
     """y = act(x), element-wise (the Activation layer)."""
     _check_f32(x, y)
+    if act == 'swish':
+        return swish_fwd(x, y)
     aid, clip = rnn_activation_id(act)
     L.check(L.load().asr_activation_fwd(_ptr(x), _ptr(y), x.numel(), aid, clip, _stream()),
             'asr_activation_fwd')
     return y
 
 
-def activation_bwd(dy, y, dx, act):
-    """dx = dy (.) act'(y), the derivative read from the output."""
+def activation_bwd(dy, y, dx, act, x=None):
+    """dx = dy (.) act'(y), the derivative read from the output; 'swish' reads it from the input
+    x instead (its derivative is not a function of y)."""
     _check_f32(dy, y, dx)
+    if act == 'swish':
+        return swish_bwd(x, dy, dx)
     aid, clip = rnn_activation_id(act)
     L.check(L.load().asr_activation_bwd(_ptr(dy), _ptr(y), _ptr(dx), dy.numel(), aid, clip,
                                         _stream()), 'asr_activation_bwd')
@@ -672,6 +677,93 @@ def posenc_add(x, y, N, D, pe=None):
     L.check(L.load().asr_posenc_add(_ptr(x), _ptr(pe), _ptr(y), int(T), int(N), int(n_pad),
                                     int(D), int(ld), _stream()), 'asr_posenc_add')
     return y
+
+
+# --------------------------------------------------------------------------- dwconv, GLU, Swish (K22)
+DWCONV_MAX_KERNEL = 63    # taps of asr_dwconv1d_* (odd, 'same' padding)
+
+
+def dwconv1d_plan(T, n_pad, channels, k, ld=None, N=1, backward=False):
+    """{'tile': frames per time tile, 'blocks': workgroups of the forward / weight-gradient launch,
+    'lds': bytes of LDS per workgroup} of the geometry (asr_dwconv1d_plan)."""
+    v = [C.c_int(0) for _ in range(3)]
+    L.check(L.load().asr_dwconv1d_plan(int(T), int(N), int(n_pad), int(channels),
+                                       int(ld or channels), int(k), int(bool(backward)),
+                                       *[C.byref(x) for x in v]), 'asr_dwconv1d_plan')
+    return dict(zip(('tile', 'blocks', 'lds'), (x.value for x in v)))
+
+
+def dwconv1d_fwd(x, w, b, y, N, k, lens=None, C_=None):
+    """y[t, n, c] = b[c] + sum_j w[j, c] xm[t + j - (k - 1) / 2, n, c] over the slab x (T, n_pad,
+    ld >= C), xm = x with the frames >= lens[n] (device int32; None: every frame) as zeros;
+    w (k, C) tap major; zeros in the rows n >= N and the columns >= C (C_: default ld)."""
+    _check_f32(x, w, b, y)
+    _check_lens(lens, N)
+    T, n_pad, ld = x.shape
+    Cc = int(C_ or ld)
+    assert y.shape == x.shape and w.numel() == k * Cc and b.numel() == Cc
+    L.check(L.load().asr_dwconv1d_fwd(_ptr(x), _ptr(w), _ptr(b), _ptr(lens), _ptr(y), int(T),
+                                      int(N), int(n_pad), Cc, int(ld), int(k), _stream()),
+            'asr_dwconv1d_fwd')
+    return y
+
+
+def dwconv1d_bwd(x, w, dy, dx, dw, db, N, k, lens=None, C_=None):
+    """dw (k, C), db (C) (written) and dx (like x, or None) of dwconv1d_fwd."""
+    _check_f32(x, w, dy, dx, dw, db)
+    _check_lens(lens, N)
+    T, n_pad, ld = x.shape
+    Cc = int(C_ or ld)
+    assert dy.shape == x.shape and dw.numel() == k * Cc and db.numel() == Cc
+    geo = (int(T), int(N), int(n_pad), Cc, int(ld), int(k))
+    nbytes = L.load().asr_dwconv1d_workspace_bytes(*geo)
+    if nbytes == 0:
+        L.check(-1, 'asr_dwconv1d_workspace_bytes (T %d N %d n_pad %d C %d ld %d k %d)' % geo)
+    ws = WS.get('dwconv', nbytes, x.device)
+    L.check(L.load().asr_dwconv1d_bwd(_ptr(x), _ptr(w), _ptr(dy), _ptr(lens), _ptr(dx), _ptr(dw),
+                                      _ptr(db), *geo, _ptr(ws), nbytes, _stream()),
+            'asr_dwconv1d_bwd')
+    return dx
+
+
+def glu_fwd(x, y, C_=None):
+    """y[..., c] = x[..., c] * sigmoid(x[..., C + c]) for c < C (default: half of x's last axis),
+    zeros in the other columns of y."""
+    _check_f32(x, y)
+    ld_in, ld_out = x.shape[-1], y.shape[-1]
+    Cc = int(C_ or ld_in // 2)
+    rows = x.numel() // ld_in
+    assert y.numel() // ld_out == rows
+    L.check(L.load().asr_glu_fwd(_ptr(x), _ptr(y), rows, Cc, int(ld_in), int(ld_out), _stream()),
+            'asr_glu_fwd')
+    return y
+
+
+def glu_bwd(x, dy, dx, C_=None):
+    """dx (like x) = [dy sigma(g) | dy a sigma(g) (1 - sigma(g)) | zeros], sigma recomputed."""
+    _check_f32(x, dy, dx)
+    ld_in, ld_out = x.shape[-1], dy.shape[-1]
+    Cc = int(C_ or ld_in // 2)
+    rows = x.numel() // ld_in
+    assert dx.shape == x.shape and dy.numel() // ld_out == rows
+    L.check(L.load().asr_glu_bwd(_ptr(x), _ptr(dy), _ptr(dx), rows, Cc, int(ld_in), int(ld_out),
+                                 _stream()), 'asr_glu_bwd')
+    return dx
+
+
+def swish_fwd(x, y):
+    """y = x * sigmoid(x), element-wise."""
+    _check_f32(x, y)
+    L.check(L.load().asr_swish_fwd(_ptr(x), _ptr(y), x.numel(), _stream()), 'asr_swish_fwd')
+    return y
+
+
+def swish_bwd(x, dy, dx):
+    """dx = dy * sigma(x) (1 + x (1 - sigma(x))), read from the input x."""
+    _check_f32(x, dy, dx)
+    L.check(L.load().asr_swish_bwd(_ptr(x), _ptr(dy), _ptr(dx), x.numel(), _stream()),
+            'asr_swish_bwd')
+    return dx
 
 
 # --------------------------------------------------------------------------- sequence-wise BN (K18)

@@ -241,13 +241,24 @@ def model_config(model):
                 'max_value': float(s.clip), 'W_regularizer': _regularizer(s.l2),
                 'b_regularizer': None, 'activity_regularizer': None, 'W_constraint': None,
                 'b_constraint': None, 'bias': True}, [prev])
+        elif s.kind == 'dwconv':
+            name = nm('depthwiseconvolution1d')
+            add('DepthwiseConvolution1D', name, {
+                'name': name, 'trainable': True, 'kernel_size': int(s.k),
+                'border_mode': 'same', 'init': 'glorot_uniform',
+                'W_regularizer': _regularizer(s.l2), 'bias': True}, [prev])
+        elif s.kind == 'glu':
+            name = nm('glu')
+            add('GLU', name, {'name': name, 'trainable': True}, [prev])
         elif s.kind == 'merge':
             name = nm('merge')
-            add('Merge', name, {'name': name, 'mode': s.mode, 'mode_type': 'raw',
-                                'concat_axis': -1, 'dot_axes': -1, 'output_shape': None,
-                                'output_shape_type': 'raw', 'output_mask': None,
-                                'output_mask_type': 'raw', 'arguments': {}},
-                [prev, out_names[s.skip]])
+            cfg = {'name': name, 'mode': s.mode, 'mode_type': 'raw',
+                   'concat_axis': -1, 'dot_axes': -1, 'output_shape': None,
+                   'output_shape_type': 'raw', 'output_mask': None,
+                   'output_mask_type': 'raw', 'arguments': {}}
+            if s.scale != 1.0:      # (only then: every other model's config text is unchanged)
+                cfg['scale'] = float(s.scale)
+            add('Merge', name, cfg, [prev, out_names[s.skip]])
         else:
             raise ValueError(s.kind)
         out_names.append(name)
@@ -364,6 +375,11 @@ def topology_from_config(text):
                                      attention_dropout=c.get('attention_dropout', 0.))(o)
         elif kind == 'PositionalEncoding':
             o = L.PositionalEncoding()(o)
+        elif kind == 'DepthwiseConvolution1D':
+            o = L.DepthwiseConvolution1D(c['kernel_size'],
+                                         W_regularizer=reg(c.get('W_regularizer')))(o)
+        elif kind == 'GLU':
+            o = L.GLU()(o)
         elif kind == 'TimeDistributed' and c['layer']['class_name'] == 'Activation':
             o = L.TimeDistributed(L.Activation(_act_from(c['layer']['config'])))(o)
         elif kind == 'TimeDistributed' and c['layer']['class_name'] == 'Dropout':
@@ -417,7 +433,7 @@ def topology_from_config(text):
                 merge_mode=c.get('merge_mode', 'concat'))(o)
         elif kind == 'Merge':
             other = l['inbound_nodes'][0][1][0]
-            o = L.merge([o, syms[other]], mode=c['mode'])
+            o = L.merge([o, syms[other]], mode=c['mode'], scale=c.get('scale', 1.0))
         else:
             raise NotImplementedError('model_config: layer class %r' % kind)
         syms[name] = o

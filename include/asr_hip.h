@@ -55,7 +55,8 @@ const char* asr_last_error(void);
  * entry points (K15: plain scalar arguments, no struct, so the version stays); asr_gru_args
  * and the asr_gru_* entry points (K16: additions only, no existing layout changes); asr_rhn_args
  * and the asr_rhn_* entry points (K17: additions only as well); the asr_seqbn_* entry points
- * (K18: plain scalar arguments again). */
+ * (K18: plain scalar arguments again); the asr_dwconv1d_* / asr_glu_* / asr_swish_* entry points
+ * (K22: plain scalar arguments, additions only). */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -750,6 +751,51 @@ int asr_attn_plan(const asr_attn_args* a, int backward, int* bq, int* bk, int* b
 /* the caller (in float64, rounded once).  Its backward pass is the identity.                */
 int asr_posenc_add(const float* x, const float* pe, float* y, int T, int N, int n_pad, int D,
                    int ld, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K22 depthwise 1-D convolution over the time axis of a time-major slab     */
+/* (T, n_pad, ld >= C), and the element-wise pairs of a Conformer block      */
+/* (arXiv 2005.08100; csrc/dwconv.hip).  Cross-correlation, 'same' padding,  */
+/* k odd in 1 .. 63, p = (k - 1) / 2, w (k, C) tap major, b (C):             */
+/*   xm[u,n,c] = x[u,n,c] if 0 <= u < lens[n] else 0   (lens NULL: all T)    */
+/*   y[t,n,c]  = b[c] + sum_j w[j,c] xm[t + j - p, n, c]   for EVERY t < T   */
+/*   dx[u]     = sum_j w[j,c] dy[u - j + p] for u < lens[n], exactly 0 past  */
+/*   dw[j,c]   = sum_{t, n < N} dy[t,n,c] xm[t + j - p, n, c]                */
+/*   db[c]     = sum_{t, n < N} dy[t,n,c]                                    */
+/* The mask is a select (nothing a frame >= lens[n] holds reaches an         */
+/* output); lens (device int32, N) is clamped to 0 .. T.  Rows n >= N and    */
+/* columns C <= col < ld of y and dx are written as exact zeros and never    */
+/* read.  dw (k, C) and db (C) are WRITTEN (as asr_ln_bwd writes dgain and   */
+/* dbias): per-workgroup partials in the workspace, added in a fixed order.  */
+/* Exact fp32 FMAs, no float atomics (bit-identical repeats), no workgroup   */
+/* waits on another.  C and ld multiples of 4, 16-byte aligned pointers;     */
+/* anything else is ASR_ERR_INVALID before any device call.                  */
+/* ------------------------------------------------------------------------ */
+/* Workspace of asr_dwconv1d_bwd; 0 for a geometry that is refused.           */
+size_t asr_dwconv1d_workspace_bytes(int T, int N, int n_pad, int C, int ld, int k);
+/* The geometry the library runs: frames per time tile, workgroups of the     */
+/* forward (backward = 0) or weight-gradient (1) launch, LDS bytes per        */
+/* workgroup (any pointer may be NULL).                                       */
+int asr_dwconv1d_plan(int T, int N, int n_pad, int C, int ld, int k, int backward, int* tile,
+                      int* blocks, int* lds_bytes);
+int asr_dwconv1d_fwd(const float* x, const float* w, const float* b, const int* lens, float* y,
+                     int T, int N, int n_pad, int C, int ld, int k, asr_stream_t stream);
+/* dx may be NULL (no input gradient wanted). */
+int asr_dwconv1d_bwd(const float* x, const float* w, const float* dy, const int* lens, float* dx,
+                     float* dw, float* db, int T, int N, int n_pad, int C, int ld, int k,
+                     void* workspace, size_t ws_bytes, asr_stream_t stream);
+/* Gated linear unit over rows of ld_in >= 2C floats: y[r, c] = x[r, c] sigma(x[r, C + c]) for  */
+/* c < C, zeros in C <= c < ld_out; backward recomputes sigma from x: dx[r, c] = dy sigma(g),   */
+/* dx[r, C + c] = dy a sigma(g) (1 - sigma(g)), zeros in 2C <= c < ld_in.  C, ld_in, ld_out     */
+/* multiples of 4.                                                                            */
+int asr_glu_fwd(const float* x, float* y, int64_t rows, int C, int ld_in, int ld_out,
+                asr_stream_t stream);
+int asr_glu_bwd(const float* x, const float* dy, float* dx, int64_t rows, int C, int ld_in,
+                int ld_out, asr_stream_t stream);
+/* Swish: y = x sigma(x); dx = dy sigma(x) (1 + x (1 - sigma(x))), read from the INPUT x (the  */
+/* derivative is not a function of y).  Finite for every finite x.                            */
+int asr_swish_fwd(const float* x, float* y, int64_t n, asr_stream_t stream);
+int asr_swish_bwd(const float* x, const float* dy, float* dx, int64_t n, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* K7  CTC loss + gradient.  Replaces core/ctc_utils.py:60-70 ->             */
