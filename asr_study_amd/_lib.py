@@ -292,6 +292,8 @@ SIGNATURES = {
     'asr_glu_bwd': (C.c_int, [void_p] * 3 + [C.c_int64] + [C.c_int] * 3 + [void_p]),
     'asr_swish_fwd': (C.c_int, [void_p] * 2 + [C.c_int64, void_p]),
     'asr_swish_bwd': (C.c_int, [void_p] * 3 + [C.c_int64, void_p]),
+    'asr_specaug_apply': (C.c_int, [void_p] * 3 + [C.c_int] * 10 + [C.c_float] * 2 +
+                          [C.c_uint64, C.c_uint32, C.c_uint32, void_p, void_p]),
     # operation-level entry points (csrc/roles.cpp)
     'asr_frontend_mfcc_batch': (C.c_int, [C.POINTER(FrontendCfg), void_p, void_p, void_p,
                                           c_int_p, C.c_int, C.c_int, void_p, void_p, void_p,

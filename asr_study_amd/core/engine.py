@@ -189,6 +189,19 @@ class Model(object):
                 s.wrapped = bool(st.get('wrapped', False))      # TimeDistributed(Dropout)
             elif s.kind == 'reshape':
                 s.target = [int(v) for v in st['target']]
+            elif s.kind == 'specaug':
+                # SpecAugment (K23, csrc/specaug.hip): augments DATA, so nothing trainable and no
+                # time stride may come before it (no backward pass exists for it, and its
+                # lengths are the input's); its limits are checked here, not at the first launch
+                s.policy = {k: st[k] for k in ('time_warp', 'freq_masks', 'freq_width',
+                                               'time_masks', 'time_width', 'time_ratio')}
+                ops.specaug_check(**s.policy)
+                s.policy['mask_value'] = float(st.get('mask_value', 0.0))
+                if any(p.tensors or getattr(p, 'st', 1) > 1 for p in self.stages):
+                    raise ValueError(
+                        'SpecAugment behind a trainable or time-strided layer: it augments the '
+                        'input data (per utterance, on the input time axis), not activations, '
+                        'and belongs directly behind Input')
             elif s.kind == 'conv':
                 # 2-D convolution front-end (K13): W (kt, kf, C_in, C_out) + b (C_out), Keras
                 # 'tf' kernel layout; the slab keeps its channel-minor rows (F * C)
@@ -351,6 +364,8 @@ class Model(object):
         # forward needs seq_len: the attention keys and the depthwise convolution's frames
         self._has_mha = any(st.kind == 'mha' for st in self.stages)
         self._needs_lens = self._has_mha or any(st.kind == 'dwconv' for st in self.stages)
+        # ... and in_len, the lengths on the INPUT time axis: a SpecAugment stage's utterances
+        self._has_specaug = any(st.kind == 'specaug' for st in self.stages)
         self._bn = [(i, st) for i, st in enumerate(self.stages) if st.kind == 'bn']
         self._seqbn = [(i, st) for i, st in enumerate(self.stages)
                        if st.kind == 'bigru' and st.bn]
@@ -598,7 +613,7 @@ class Model(object):
 
     # ------------------------------------------------------------------ forward
     def forward(self, x, training=False, masks=None, need_grad=True, n_valid=0, n_real=None,
-                bn_weight=None, seq_len=None):
+                bn_weight=None, seq_len=None, in_len=None):
         """x: (T, n_pad, F) float32 CUDA slab -> logits (T, n_pad, C).
         need_grad=False (evaluation / prediction) skips what only BPTT would read; n_valid=1
         with it (one utterance, predict.py) selects the tile-free recurrent kernel.
@@ -609,6 +624,8 @@ class Model(object):
         CTC gets): the valid frames of a GRU(batch_norm=True) stage's training statistics and the
         visible keys of a MultiHeadAttention stage and the frames a DepthwiseConvolution1D stage
         reads, in training and inference (None: every frame).
+        in_len: device int32 lengths of the real samples on the INPUT time axis (x's frames): the
+        utterances a SpecAugment stage warps and masks within, in training (None: every frame).
 
         masks: optional explicit variational-dropout masks (parity tests):
         {stage_index: (BW (2, n_pad, f_in_pad), BU (2, n_pad, Hp))}.
@@ -676,8 +693,15 @@ class Model(object):
                 if training and s.value > 0:
                     out = self._buf('noise%d' % si, a.shape)
                     a = ops.gaussian_noise(a, out, s.value, self.rng_seed, 4 * si, self._step)
-                    if s.f_out_pad != s.f_out and si == 0:
+                    if s.f_out_pad != s.f_out and all(p.kind == 'specaug'
+                                                      for p in self.stages[:si]):
                         a[:, :, s.f_out:] = 0.0        # keep the input pad columns zero
+            elif s.kind == 'specaug':
+                if training:        # (never in place: the caller keeps its slab)
+                    out = self._buf('specaug%d' % si, a.shape)
+                    a = ops.specaug_apply(a.contiguous(), out, min(n_real, n_pad), s.f_in,
+                                          self.rng_seed, 4 * si, self._step, lens=in_len,
+                                          **s.policy)
             elif s.kind == 'dropout':
                 if training and s.value > 0:
                     keep = self._buf('dropmask%d' % si, a.shape)
@@ -1430,7 +1454,7 @@ class Model(object):
             first = not any(st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn', 'bigru', 'birhn',
                                         'ln', 'mha', 'dwconv')
                             for st in self.stages[:si])
-            if s.kind in ('noise', 'reshape', 'posenc'):    # (posenc: d(x + pe) / dx = 1)
+            if s.kind in ('noise', 'reshape', 'posenc', 'specaug'):  # (posenc: d(x + pe) / dx = 1)
                 continue
             if s.kind == 'mha':
                 dx = self._mha_backward(s, si, rec, a_in.contiguous(), da, first, split)
@@ -1863,12 +1887,17 @@ class Model(object):
         """One forward + CTC + backward.  Returns per-sample CTC loss (device) and
         logits; self.grads holds d(mean ctc)/d params."""
         lab, lab_len, sl = self._prep_labels(labels, seq_len, slab.shape[0])
+        in_len = None
+        if self._has_specaug and training:
+            # the batch's input lengths, for the SpecAugment stage (a copy like the three above)
+            in_len = torch.as_tensor(np.asarray(seq_len, np.int32).reshape(-1)).to(self.device)
         return self.loss_and_grads_device(slab, lab, lab_len, sl, len(labels), training, masks,
-                                          n_global, n_ref)
+                                          n_global, n_ref, in_len=in_len)
 
     def loss_and_grads_device(self, slab, lab, lab_len, sl, N, training=True, masks=None,
-                              n_global=None, n_ref=None):
+                              n_global=None, n_ref=None, in_len=None):
         """Same with labels (N, l_max) / label_len / seq_len already on the device.
+        in_len: device int32 input lengths for a SpecAugment stage (None: every frame is valid).
         n_global: samples of the GLOBAL batch (gradient scale 1/n_global; 0 = this rank holds a
         zero-weight dummy); n_ref: the global batch size again, for decisions every rank must
         take alike (it survives n_global = 0)."""
@@ -1877,7 +1906,7 @@ class Model(object):
         ng = int(n_ref or n_global or N * world)
         self._ar_ref_pad = ops.pad16((ng + world - 1) // world)
         logits = self.forward(slab, training=training, masks=masks, n_real=N,
-                              bn_weight=0 if n_global == 0 else N, seq_len=sl)
+                              bn_weight=0 if n_global == 0 else N, seq_len=sl, in_len=in_len)
         dlog = self._buf('dlogits', logits.shape)
         # n_global = 0: a zero-weight dummy shard (parallel.ShardedBatch.n_local == 0)
         ctc = ops.ctc_loss_grad(logits, lab, lab_len, sl, N, grad=dlog,
@@ -1890,9 +1919,10 @@ class Model(object):
         synchronisation: forward, CTC, BPTT, (RCCL all-reduce), clip + update, greedy
         decode for the LER metric.  Returns device tensors (ctc, decoded, lengths)."""
         self._maybe_retry_persistent()
+        in_len = sl.to(torch.int32) if self._has_specaug else None      # (input frames)
         sl = self.out_lengths(sl)
         ctc, logits, sl = self.loss_and_grads_device(slab, lab, lab_len, sl, N, training=True,
-                                                     n_global=N * world)
+                                                     n_global=N * world, in_len=in_len)
         self._allreduce()
         self._step += 1
         self.optimizer.step(self)

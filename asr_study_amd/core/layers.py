@@ -21,6 +21,8 @@ frame over its features on csrc/layernorm.hip.
 csrc/attention.hip and make the ``transformer`` factory.
 ``DepthwiseConvolution1D``, ``GLU``, ``Activation('swish')`` and ``merge(..., scale=)`` (no
 reference counterpart either) run on csrc/dwconv.hip and make the ``conformer`` factory.
+``SpecAugment`` (no reference counterpart) augments the input slab on csrc/specaug.hip; the
+``spec_augment`` argument of deep_speech2 / transformer / conformer puts it behind ``Input``.
 """
 
 
@@ -73,6 +75,36 @@ class GaussianNoise(Layer):
 
     def __init__(self, sigma):
         self.sigma = float(sigma or 0.0)
+
+
+class SpecAugment(Layer):
+    """SpecAugment (arXiv 1904.08779) of the model INPUT, in the training phase only, on
+    csrc/specaug.hip: per utterance a piecewise-linear time warp of at most ``time_warp`` frames
+    (0: none), ``freq_masks`` frequency masks of width 0 .. ``freq_width`` and ``time_masks`` time
+    masks of width 0 .. min(``time_width`` (0: no absolute cap), ``time_ratio`` * length), set to
+    ``mask_value``.  The defaults are the Conformer paper's policy (arXiv 2005.08100, section 3.2:
+    two frequency masks of up to 27 channels, ten time masks of up to 5 % of the utterance).
+    Drawn per utterance from the library's Philox streams (seed, stage, step, rank), within each
+    utterance's own length.  It augments data: it goes directly behind ``Input``, in front of
+    every trainable layer.  No parameters; identity at inference.  Not built: the paper's sparse
+    image warp (the piecewise-linear form replaces it), mask values other than a constant."""
+
+    def __init__(self, time_warp=0, freq_masks=2, freq_width=27, time_masks=10, time_width=0,
+                 time_ratio=0.05, mask_value=0.0, **kwargs):
+        if kwargs:
+            raise NotImplementedError('SpecAugment: unknown arguments %s' % sorted(kwargs))
+        from .. import ops
+        ops.specaug_check(time_warp, freq_masks, freq_width, time_masks, time_width, time_ratio)
+        self.time_warp, self.freq_masks = int(time_warp), int(freq_masks)
+        self.freq_width, self.time_masks = int(freq_width), int(time_masks)
+        self.time_width, self.time_ratio = int(time_width), float(time_ratio)
+        self.mask_value = float(mask_value)
+
+    POLICY = ('time_warp', 'freq_masks', 'freq_width', 'time_masks', 'time_width', 'time_ratio',
+              'mask_value')
+
+    def policy(self):
+        return {k: getattr(self, k) for k in self.POLICY}
 
 
 class Dropout(Layer):

@@ -3,6 +3,7 @@
 ``brsmv1``, plus this build's ``deep_speech2`` (BiLSTM or, with ``rnn_type='gru'``, BiGRU) and
 ``rhn`` (brsmv1's topology on the reference's own RHN cell) and ``transformer`` (a pre-LN
 self-attention encoder, csrc/attention.hip) and ``conformer`` (arXiv 2005.08100, csrc/dwconv.hip).
+The last three take ``spec_augment`` (a SpecAugment layer behind Input, csrc/specaug.hip).
 
 ``train.py`` resolves them by name -- ``get_from_module('core.models', 'brsmv1')
 (**hparams)`` (train.py:127-129) -- and gets back an object with the Keras
@@ -17,7 +18,8 @@ from .engine import Model
 from .layers import (Input, GaussianNoise, TimeDistributed, Dense, LSTM, Bidirectional,
                      Dropout, Merge, merge, l2, Reshape, Convolution2D, clipped_relu, SimpleRNN,
                      Activation, BatchNormalization, GRU, RHN, LayerNormalization,
-                     MultiHeadAttention, PositionalEncoding, DepthwiseConvolution1D, GLU)
+                     MultiHeadAttention, PositionalEncoding, DepthwiseConvolution1D, GLU,
+                     SpecAugment)
 
 
 def ctc_model(inputs, output, **kwargs):
@@ -57,6 +59,8 @@ def ctc_model(inputs, output, **kwargs):
                          'st': layer.st, 'sf': layer.sf, 'clip': layer.clip, 'l2': layer.l2})
         elif isinstance(layer, GaussianNoise):
             spec.append({'type': 'noise', 'value': layer.sigma})
+        elif isinstance(layer, SpecAugment):
+            spec.append(dict({'type': 'specaug'}, **layer.policy()))
         elif isinstance(layer, BatchNormalization):
             spec.append({'type': 'bn', 'epsilon': layer.epsilon, 'momentum': layer.momentum,
                          'fc': None if layer.in_fc is None else list(layer.in_fc)})
@@ -119,6 +123,25 @@ def _elementwise_spec(layer, wrapped=False):
     if isinstance(layer, Dropout):
         return {'type': 'dropout', 'value': layer.p, 'wrapped': wrapped}
     return {'type': 'act', 'activation': layer.activation, 'wrapped': wrapped}
+
+
+def _spec_augment(o, spec_augment):
+    """The ``spec_augment`` argument of a factory, applied to the symbolic input ``o``: False /
+    None (no layer), True (SpecAugment() with its defaults, the Conformer paper's policy) or a
+    dict of its keyword arguments."""
+    if spec_augment is False or spec_augment is None:
+        return o
+    if spec_augment is not True and not isinstance(spec_augment, dict):
+        raise ValueError('spec_augment=%r: False, True or a dict of SpecAugment arguments'
+                         % (spec_augment,))
+    return SpecAugment(**({} if spec_augment is True else spec_augment))(o)
+
+
+def _record_spec_augment(model, spec_augment):
+    """... and recorded in the factory record only when set (a default model keeps its config)."""
+    if spec_augment is not False and spec_augment is not None:
+        model.config['kwargs']['spec_augment'] = (True if spec_augment is True
+                                                  else dict(spec_augment))
 
 
 def graves2006(num_features=26, num_hiddens=100, num_classes=28, std=.6, **kw):
@@ -244,7 +267,7 @@ def brsmv1(num_features=39, num_classes=28, num_hiddens=256, num_layers=5,
 def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
                  conv_filters=32, conv_kernels=((11, 41), (11, 21)), conv_strides=((2, 2), (1, 2)),
                  max_value=20, dropout=0.2, weight_decay=1e-4, input_std_noise=.0,
-                 batch_norm=False, rnn_type='lstm', **kw):
+                 batch_norm=False, rnn_type='lstm', spec_augment=False, **kw):
     """BASELINE.json configs[2]: "DeepSpeech2-style 5xBiLSTM(512) + 2 conv front-end, 80-dim
     log-mel".  NO REFERENCE COUNTERPART: the reference lists Deep Speech 2 as TODO
     (README.md:118) and its ``deep_speech`` factory (core/models.py:148-214) is dead code
@@ -274,7 +297,9 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
 
     rnn_type='gru': every Bidirectional(LSTM) becomes a Bidirectional(GRU) (the cell of the
     published Deep Speech 2; Keras-1.2.2 GRU on csrc/gru.hip) with the same regularisers and
-    dropouts; it composes with batch_norm."""
+    dropouts; it composes with batch_norm.
+
+    spec_augment=True (or a dict of its arguments): a SpecAugment layer directly behind Input."""
     if rnn_type not in ('lstm', 'gru'):
         raise ValueError("deep_speech2: rnn_type %r ('lstm' or 'gru')" % (rnn_type,))
     if batch_norm not in (False, True, 'recurrent', 'layer'):
@@ -288,7 +313,7 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
     cell = GRU if rnn_type == 'gru' else LSTM
     cell_kw = dict(batch_norm=True) if recurrent_bn else {}
     x = Input(name='inputs', shape=(None, num_features))
-    o = x
+    o = _spec_augment(x, spec_augment)
     if input_std_noise is not None:
         o = GaussianNoise(input_std_noise)(o)
     o = Reshape((-1, num_features, 1))(o)
@@ -318,6 +343,7 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
         model.config['kwargs']['batch_norm'] = batch_norm if isinstance(batch_norm, str) else True
     if rnn_type != 'lstm':  # (likewise)
         model.config['kwargs']['rnn_type'] = rnn_type
+    _record_spec_augment(model, spec_augment)
     return model
 
 
@@ -356,7 +382,7 @@ def rhn(num_features=39, num_classes=28, num_hiddens=256, num_layers=5, depth=2,
 
 def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_layers=6,
                 d_ff=1024, dropout=0.1, conv=True, conv_filters=32,
-                conv_kernels=((11, 41), (11, 21)), weight_decay=0., **kw):
+                conv_kernels=((11, 41), (11, 21)), weight_decay=0., spec_augment=False, **kw):
     """A CTC-trained pre-LN transformer encoder (arXiv 1706.03762, 2002.04745).  NO REFERENCE
     COUNTERPART.  conv=True: deep_speech2's front-end first -- Reshape, two Convolution2D with
     clipped ReLU (strides (2, 2) and (1, 2): time stride 2), Reshape.  Then
@@ -366,10 +392,11 @@ def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_l
         x = merge([Dropout(Dense(d_model)(relu(Dense(d_ff)(LayerNormalization(x))))), x], 'sum')
 
     a final LayerNormalization and TimeDistributed(Dense(num_classes)).  The attention keys of an
-    utterance are its valid frames (the strided lengths).  weight_decay: l2 on every matrix."""
+    utterance are its valid frames (the strided lengths).  weight_decay: l2 on every matrix.
+    spec_augment=True (or a dict of its arguments): a SpecAugment layer directly behind Input."""
     reg = l2(weight_decay)
     x = Input(name='inputs', shape=(None, num_features))
-    o = x
+    o = _spec_augment(x, spec_augment)
     if conv:
         o = Reshape((-1, num_features, 1))(o)
         for (kt, kf), (st, sf) in zip(conv_kernels, ((2, 2), (1, 2))):
@@ -396,12 +423,14 @@ def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_l
         num_heads=num_heads, num_layers=num_layers, d_ff=d_ff, dropout=dropout, conv=conv,
         conv_filters=conv_filters, conv_kernels=[list(k) for k in conv_kernels],
         weight_decay=weight_decay)}
+    _record_spec_augment(model, spec_augment)
     return model
 
 
 def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_layers=6,
               d_ff=1024, kernel_size=31, conv_norm='batch', dropout=0.1, conv=True,
-              conv_filters=32, conv_kernels=((11, 41), (11, 21)), weight_decay=0., **kw):
+              conv_filters=32, conv_kernels=((11, 41), (11, 21)), weight_decay=0.,
+              spec_augment=False, **kw):
     """A CTC-trained Conformer encoder (arXiv 2005.08100).  NO REFERENCE COUNTERPART.  The
     front-end and input projection of ``transformer`` (conv=True: deep_speech2's two strided
     Convolution2D; then TimeDistributed(Dense(d_model)), PositionalEncoding, Dropout), then
@@ -419,12 +448,14 @@ def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_lay
     padding included) or 'layer' (LayerNormalization).  The attention keys and the depthwise
     convolution's input of an utterance are its valid frames (the strided lengths).  Positions
     are the absolute sinusoidal table: the paper's relative positional attention is not built.
-    weight_decay: l2 on every matrix and depthwise filter."""
+    weight_decay: l2 on every matrix and depthwise filter.  spec_augment=True (or a dict of its
+    arguments): a SpecAugment layer directly behind Input; its defaults are the paper's policy
+    (section 3.2) without the time warp."""
     if conv_norm not in ('batch', 'layer'):
         raise ValueError("conformer(conv_norm=%r): 'batch' or 'layer'" % (conv_norm,))
     reg = l2(weight_decay)
     x = Input(name='inputs', shape=(None, num_features))
-    o = x
+    o = _spec_augment(x, spec_augment)
     if conv:
         o = Reshape((-1, num_features, 1))(o)
         for (kt, kf), (st, sf) in zip(conv_kernels, ((2, 2), (1, 2))):
@@ -464,4 +495,5 @@ def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_lay
         num_heads=num_heads, num_layers=num_layers, d_ff=d_ff, kernel_size=kernel_size,
         conv_norm=conv_norm, dropout=dropout, conv=conv, conv_filters=conv_filters,
         conv_kernels=[list(k) for k in conv_kernels], weight_decay=weight_decay)}
+    _record_spec_augment(model, spec_augment)
     return model

@@ -1552,6 +1552,50 @@ def gaussian_noise(x, out, sigma, seed, stream_id, step):
     return out
 
 
+SPECAUG_MAX_MASKS = 64    # frequency + time masks of one asr_specaug_apply call
+
+
+def specaug_check(time_warp, freq_masks, freq_width, time_masks, time_width, time_ratio):
+    """The limits of asr_specaug_apply on a policy (csrc/specaug.hip), as a ValueError: what the
+    SpecAugment layer and the engine's stage refuse when the model is built."""
+    ints = dict(time_warp=time_warp, freq_masks=freq_masks, freq_width=freq_width,
+                time_masks=time_masks, time_width=time_width)
+    for k, v in ints.items():
+        if isinstance(v, bool) or int(v) != v or v < 0 or v >= 2 ** 31:
+            raise ValueError('SpecAugment: %s %r (a non-negative integer)' % (k, v))
+    if freq_masks + time_masks > SPECAUG_MAX_MASKS:
+        raise ValueError('SpecAugment: %d frequency + %d time masks (at most %d together)'
+                         % (freq_masks, time_masks, SPECAUG_MAX_MASKS))
+    if not 0.0 <= float(time_ratio) <= 1.0:
+        raise ValueError('SpecAugment: time_ratio %r (in [0, 1])' % (time_ratio,))
+
+
+def specaug_params_len(freq_masks, time_masks):
+    """int32 words per sample of asr_specaug_apply's params_out: (c, c', f, f0, ..., tau, t0, ...)."""
+    return 2 + 2 * (int(freq_masks) + int(time_masks))
+
+
+def specaug_apply(x, out, N, F, seed, stream_id, step, lens=None, time_warp=0, freq_masks=2,
+                  freq_width=27, time_masks=10, time_width=0, time_ratio=0.05, mask_value=0.0,
+                  params_out=None):
+    """SpecAugment of the (T, n_pad, ld) slab x into out (another buffer) on the stream (seed,
+    stream_id, step): include/asr_hip.h K23.  N real samples of F <= ld real columns; lens: device
+    int32 (N) lengths on x's time axis or None (every frame); params_out: device int32
+    (N, specaug_params_len(...)) or None."""
+    _check_f32(x, out)
+    T, n_pad, ld = x.shape
+    assert out.shape == x.shape
+    for t, n in ((lens, N), (params_out, N * specaug_params_len(freq_masks, time_masks))):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= n
+    L.check(L.load().asr_specaug_apply(
+        _ptr(x), _ptr(out), _ptr(lens), int(T), int(N), int(n_pad), int(F), int(ld),
+        int(time_warp), int(freq_masks), int(freq_width), int(time_masks), int(time_width),
+        float(time_ratio), float(mask_value), int(seed) & (2 ** 64 - 1), int(stream_id), int(step),
+        _ptr(params_out), _stream()), 'asr_specaug_apply')
+    return out
+
+
 def random_words(n, seed, stream_id, step, device):
     out = torch.empty(int(n), dtype=torch.int32, device=device)
     L.check(L.load().asr_random_words(_ptr(out), int(n), int(seed) & (2 ** 64 - 1),

@@ -10,7 +10,8 @@ reads back:
   (``inputs``, sparse int32 ``labels``, int32 ``inputs_length``), the chain of
   ``GaussianNoise`` / ``TimeDistributed(Dense)`` / ``Dropout`` / ``Bidirectional(LSTM)`` /
   ``Bidirectional(SimpleRNN)`` ('concat' or 'sum') / ``TimeDistributed(Activation)`` /
-  ``TimeDistributed(Dropout)`` / ``BatchNormalization`` / ``Merge`` layers and the two ``Lambda``s
+  ``TimeDistributed(Dropout)`` / ``BatchNormalization`` / ``Merge`` / ``SpecAugment`` layers and
+  the two ``Lambda``s
   ``decoder`` and ``ctc``;
 * root attribute ``training_config``: JSON with the optimizer's class and config, the loss /
   metric names and ``loss_weights`` of ``train.py:140-143``;
@@ -149,6 +150,9 @@ def model_config(model):
             name = nm('gaussiannoise')
             add('GaussianNoise', name, {'name': name, 'trainable': True, 'sigma': float(s.value)},
                 [prev])
+        elif s.kind == 'specaug':
+            name = nm('specaugment')
+            add('SpecAugment', name, dict({'name': name, 'trainable': True}, **s.policy), [prev])
         elif s.kind == 'dropout' and getattr(s, 'wrapped', False):
             name = nm('timedistributed')
             inner = nm('dropout')
@@ -348,6 +352,8 @@ def topology_from_config(text):
         kind = l['class_name']
         if kind == 'GaussianNoise':
             o = L.GaussianNoise(c['sigma'])(o)
+        elif kind == 'SpecAugment':
+            o = L.SpecAugment(**{k: c[k] for k in L.SpecAugment.POLICY if k in c})(o)
         elif kind == 'Reshape':
             o = L.Reshape(tuple(c['target_shape']))(o)
         elif kind == 'Convolution2D':

@@ -56,7 +56,7 @@ const char* asr_last_error(void);
  * and the asr_gru_* entry points (K16: additions only, no existing layout changes); asr_rhn_args
  * and the asr_rhn_* entry points (K17: additions only as well); the asr_seqbn_* entry points
  * (K18: plain scalar arguments again); the asr_dwconv1d_* / asr_glu_* / asr_swish_* entry points
- * (K22: plain scalar arguments, additions only). */
+ * (K22: plain scalar arguments, additions only); asr_specaug_apply (K23: likewise). */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -796,6 +796,44 @@ int asr_glu_bwd(const float* x, const float* dy, float* dx, int64_t rows, int C,
 /* derivative is not a function of y).  Finite for every finite x.                            */
 int asr_swish_fwd(const float* x, float* y, int64_t n, asr_stream_t stream);
 int asr_swish_bwd(const float* x, const float* dy, float* dx, int64_t n, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K23 SpecAugment (arXiv 1904.08779; csrc/specaug.hip) of an input slab     */
+/* `in` (T, n_pad, ld) time-major with F <= ld real columns into `out` (the  */
+/* same shape, ANOTHER buffer): per utterance n < N a piecewise-linear time  */
+/* warp, mF frequency masks and mT time masks, drawn from the K12 streams.   */
+/* len = lens[n] clamped to 0 .. T (lens NULL: T).  rand(w, K) = the high    */
+/* 32 bits of w * K, an integer in [0, K).  Sample n owns the B = 1 +        */
+/* ceil((mF + mT) / 2) Philox blocks from n * B on (counter and key as K12): */
+/* block 0 = the warp (word 0 the centre, word 1 the displacement); mask m   */
+/* (frequency masks first, then time masks) = block 1 + m / 2, word 2 (m %   */
+/* 2) its width and word 2 (m % 2) + 1 its start.                            */
+/*   warp : Wn = min(W, (len - 1) / 2); none if Wn = 0; else                 */
+/*          c = Wn + rand(w0, len - 2 Wn), c' = c + rand(w1, 2 Wn + 1) - Wn; */
+/*          output frame t < c' reads source position t c / c', frame c' <=  */
+/*          t < len reads c + (t - c') (len - c) / (len - c'); a position    */
+/*          base + num / den is i = base + num div den (64-bit integers),    */
+/*          frac = (float)(num mod den) / (float)den, and                    */
+/*          y = x[i] + frac (x[min(i + 1, len - 1)] - x[i])                  */
+/*   freq : f = rand(., min(Fw, F) + 1), f0 = rand(., F - f + 1): columns    */
+/*          f0 <= col < f0 + f of every frame t < len become mask_value      */
+/*   time : cap = min(Tw > 0 ? Tw : len, (int)floorf(p * (float)len), len),  */
+/*          tau = rand(., cap + 1), t0 = rand(., len - tau + 1): frames t0   */
+/*          <= t < t0 + tau become mask_value (columns < F)                  */
+/* The warp comes first, then the masks; a masked element is a SELECT (a     */
+/* non-finite input under a mask comes out as exactly mask_value).  Frames   */
+/* t >= len, rows n >= N and columns col >= F are copied bit for bit.        */
+/* params_out (device int32, N x (2 + 2 (mF + mT)), or NULL) receives per    */
+/* sample (c, c', f_0, f0_0, ..., tau_0, t0_0, ...); c = c' = -1: no warp.   */
+/* One launch, no workspace, no atomics, no workgroup waits on another.      */
+/* ASR_ERR_INVALID before any device call: a NULL or aliased slab, ld < F, a */
+/* negative count or width, N > n_pad, p outside [0, 1], mF + mT > 64,       */
+/* misalignment (in / out: 16 bytes where ld % 4 == 0, else 4).              */
+/* ------------------------------------------------------------------------ */
+int asr_specaug_apply(const float* in, float* out, const int* lens, int T, int N, int n_pad,
+                      int F, int ld, int W, int mF, int Fw, int mT, int Tw, float p,
+                      float mask_value, uint64_t seed, uint32_t stream_id, uint32_t step,
+                      int* params_out, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* K7  CTC loss + gradient.  Replaces core/ctc_utils.py:60-70 ->             */
