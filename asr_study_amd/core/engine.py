@@ -16,6 +16,11 @@ weights (eyben's 78/27-unit layers).  get_weights()/set_weights() speak the
 reference's Keras layout: per Bidirectional layer [W (in,4H), U (H,4H), b (4H)] for
 the forward then the backward copy, gate blocks i,f,c,o; Dense [W, b].  Where each weight
 lies in the flat buffer, and how it is padded, is the parameter table of core/params.py.
+
+What a stage kind reads from its spec, computes and differentiates is its entry of the stage-kind
+table of core/stages.py; ``_layout`` / ``forward`` / ``backward`` here are the prologues, one loop
+over the stages and the epilogues.  Only the two BiLSTM bodies, whose launches are scheduled over
+three streams, live here (``_bilstm_forward`` / ``_bilstm_backward``).
 """
 import math
 import os
@@ -28,6 +33,7 @@ from .. import ops
 from . import optimizers as _opt
 from . import params as P
 from .params import _pad4
+from .stages import KINDS, Pass
 
 
 # where a Model lives when the factory is given no ``device`` (host-only tests build on 'cpu':
@@ -171,201 +177,43 @@ class Model(object):
     # ------------------------------------------------------------------ params
     def _layout(self, seed):
         """Reads the stage list: per stage its attributes and, for a trainable kind, its rows of
-        the parameter table (core/params.py), which allocates its blocks of the flat buffers."""
+        the parameter table (core/params.py), which allocates its blocks of the flat buffers --
+        both by the kind's ``build`` of the stage-kind table (core/stages.py).  Then the passes
+        that look at more than one stage."""
         self.stages = []
         # the input features are padded to a multiple of 4 columns (zero column(s), zero
         # weight rows) so that the first layer's GEMMs qualify for the 16-byte fast path
         f_real, f_pad = self.num_features, _pad4(self.num_features)
         self.f_in_pad0 = f_pad
-        alloc = P.Alloc()
+        alloc = self._alloc = P.Alloc()     # (the builders of core/stages.py allocate from it)
+        trainable_below = False
         for st in self.spec:
             s = Stage()
             s.kind = st['type']
+            if s.kind not in KINDS:
+                raise ValueError(s.kind)
             s.p_lo = alloc.params           # this stage's slice of the flat param / grad buffers
             s.f_in, s.f_in_pad = f_real, f_pad
             s.tensors = []                  # (core/params.py; stays empty without weights)
-            if s.kind in ('noise', 'dropout'):
-                s.value = st['value']
-                s.wrapped = bool(st.get('wrapped', False))      # TimeDistributed(Dropout)
-            elif s.kind == 'reshape':
-                s.target = [int(v) for v in st['target']]
-            elif s.kind == 'specaug':
-                # SpecAugment (K23, csrc/specaug.hip): augments DATA, so nothing trainable and no
-                # time stride may come before it (no backward pass exists for it, and its
-                # lengths are the input's); its limits are checked here, not at the first launch
-                s.policy = {k: st[k] for k in ('time_warp', 'freq_masks', 'freq_width',
-                                               'time_masks', 'time_width', 'time_ratio')}
-                ops.specaug_check(**s.policy)
-                s.policy['mask_value'] = float(st.get('mask_value', 0.0))
-                if any(p.tensors or getattr(p, 'st', 1) > 1 for p in self.stages):
-                    raise ValueError(
-                        'SpecAugment behind a trainable or time-strided layer: it augments the '
-                        'input data (per utterance, on the input time axis), not activations, '
-                        'and belongs directly behind Input')
-            elif s.kind == 'conv':
-                # 2-D convolution front-end (K13): W (kt, kf, C_in, C_out) + b (C_out), Keras
-                # 'tf' kernel layout; the slab keeps its channel-minor rows (F * C)
-                for k in ('F_in', 'C_in', 'C_out', 'kt', 'kf', 'st', 'sf'):
-                    setattr(s, k, int(st[k]))
-                s.clip, s.l2 = float(st['clip']), float(st.get('l2', 0.0))
-                s.F_out = -(-s.F_in // s.sf)
-                if f_real != s.F_in * s.C_in or f_pad != f_real:
-                    raise ValueError('conv stage: %d input features (a multiple of 4) expected, '
-                                     'got %d (padded %d)' % (s.F_in * s.C_in, f_real, f_pad))
-                if (s.F_out * s.C_out) % 4:
-                    raise ValueError('conv stage: F_out * C_out must be a multiple of 4')
-                # limits of asr_conv2d_* (csrc/conv.hip), checked when the model is BUILT rather
-                # than at the first launch / the first backward pass (ADVICE r4):
-                if not 1 <= s.kt <= 16:
-                    raise ValueError('conv stage: kernel length over time %d not in 1..16 '
-                                     '(asr_conv2d_* keeps one plane shift per time tap)' % s.kt)
-                if s.st < 1 or s.sf < 1:
-                    raise ValueError('conv stage: strides must be >= 1')
-                if s.st > 1 and any(p.tensors for p in self.stages):
-                    raise ValueError(
-                        'conv stage with time stride %d behind a trainable stage: asr_conv2d_dgrad '
-                        'exists for time stride 1 only, so a time-strided convolution must be the '
-                        'FIRST trainable stage (its input is data and needs no gradient)' % s.st)
-                s.tensors = P.conv(s, alloc, None)
-                f_real = f_pad = s.F_out * s.C_out
-            elif s.kind == 'dense':
-                s.n_out = st['n_out']
-                s.l2 = st.get('l2', 0.0)
-                s.tensors = P.dense(s, alloc, self._real_rows(s))
-                f_real = f_pad = s.n_out
-                s.in_map = None
-            elif s.kind == 'bilstm':
-                s.H = st['H']
-                s.Hp = _pad4(s.H)
-                s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
-                s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
-                s.mi = st.get('mi')                     # [alpha, beta1, beta2] inits or None
-                s.ln = st.get('layer_norm')             # [gain_init, bias_init] or None
-                s.zoneout_c = float(st.get('zoneout_c') or 0.0)
-                s.zoneout_h = float(st.get('zoneout_h') or 0.0)
-                s.act = st.get('activation') or 'tanh'      # core/layers.py:452, :463
-                s.tensors = P.bilstm(s, alloc, self._real_rows(s))
-                f_real, f_pad = 2 * s.H, 2 * s.Hp
-            elif s.kind == 'act':
-                s.act = st['activation']        # 'tanh' / 'relu' / 'linear' / clipped_relu()
-                s.wrapped = bool(st.get('wrapped', False))      # TimeDistributed(Activation)
-            elif s.kind in ('birnn', 'bigru', 'birhn'):
-                # Bidirectional(SimpleRNN | GRU | RHN) (csrc/rnn.hip, gru.hip, rhn.hip)
-                s.H = st['H']
-                s.Hp = _pad4(s.H)
-                s.merge = st.get('merge_mode', 'concat')
-                s.act = st.get('activation') or 'tanh'
-                s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
-                s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
-                if s.kind == 'birnn':
-                    s.init = st.get('init', 'glorot_uniform')
-                elif s.kind == 'bigru':
-                    # batch_norm (K18, csrc/batchnorm.hip): sequence-wise BN of the input projection
-                    s.bn = bool(st.get('batch_norm', False))
-                    if s.bn:
-                        s.bn_eps = float(st.get('bn_epsilon', 1e-3))
-                        s.bn_momentum = float(st.get('bn_momentum', 0.99))
-                else:
-                    s.depth = int(st.get('depth', 1))
-                    s.coupling = bool(st.get('coupling', True))
-                    s.nblk = 2 if s.coupling else 3
-                s.tensors = getattr(P, s.kind)(s, alloc, self._real_rows(s))
-                f_real, f_pad = (2 * s.H, 2 * s.Hp) if s.merge == 'concat' else (s.H, s.Hp)
-            elif s.kind == 'bn':
-                s.eps, s.momentum = float(st.get('epsilon', 1e-3)), float(st.get('momentum', 0.99))
-                fc = st.get('fc')
-                s.grouped = fc is not None and int(fc[1]) < f_pad
-                if s.grouped:
-                    s.C = int(fc[1])            # per channel of the (N, T, F, C) conv image
-                    if f_pad != f_real or f_pad != int(fc[0]) * s.C or s.C % 4 or s.C > 256:
-                        raise NotImplementedError(
-                            'BatchNormalization on an (N, T, %d, %d) image: the channel count '
-                            'must be a multiple of 4, at most 256' % (int(fc[0]), s.C))
-                else:
-                    s.C = f_pad                 # per column, pad columns get gamma = beta = 0
-                    if f_pad % 4:
-                        raise NotImplementedError('BatchNormalization over %d features: the '
-                                                  'width must be a multiple of 4' % f_real)
-                s.n_real = s.C if s.grouped else f_real
-                s.clip = 0.0                    # > 0: a following clipped ReLU fused (below)
-                s.tensors = P.bn(s, alloc, self._bn_cols(s))
-            elif s.kind == 'ln':
-                # LayerNormalization (K20, csrc/layernorm.hip): per frame over its real columns,
-                # which it keeps as it is given them (like 'bn': no projection of its own)
-                s.eps = float(st.get('epsilon', 1e-5))
-                cols = self._real_rows(s)
-                s.ld = f_pad
-                if np.array_equal(cols, np.arange(f_real)):
-                    s.segs, s.seg_H, s.seg_Hp = 1, f_real, f_pad
-                else:       # [0, H) and [Hp, Hp + H): two directions padded apart
-                    s.segs, s.seg_H = 2, len(cols) // 2
-                    s.seg_Hp = int(cols[s.seg_H])
-                if f_pad % 4 or s.seg_Hp % 4 or s.segs * s.seg_Hp > f_pad:
-                    raise NotImplementedError('LayerNormalization over %d features: the width '
-                                              'must be a multiple of 4' % f_real)
-                if f_pad > ops.LN_MAX_WIDTH:
-                    raise NotImplementedError(
-                        'LayerNormalization over %d features (%d columns): the asr_ln_* kernels '
-                        'keep a row in the registers of one wave, at most %d columns'
-                        % (f_real, f_pad, ops.LN_MAX_WIDTH))
-                s.tensors = P.ln(s, alloc, cols)
-            elif s.kind == 'mha':
-                # multi-head self-attention (K21, csrc/attention.hip): the [Q | K | V] projection,
-                # the fused attention core, the output projection
-                s.heads, s.dh = int(st['heads']), int(st['dh'])
-                s.D, s.n_out, s.l2 = s.heads * s.dh, int(st['n_out']), float(st.get('l2', 0.0))
-                if s.heads < 1 or s.dh % 16 or not 16 <= s.dh <= 128:
-                    raise NotImplementedError(
-                        'MultiHeadAttention: head_dim %d (a multiple of 16 in 16 .. 128: the tile '
-                        'of the asr_attn_* kernels), %d heads' % (s.dh, s.heads))
-                s.tensors = P.mha(s, alloc, self._real_rows(s))
-                f_real = f_pad = s.n_out
-            elif s.kind == 'posenc':
-                s.D = f_real                    # (no parameters: the table depends on (T, D) only)
-            elif s.kind == 'dwconv':
-                # depthwise convolution over time (K22, csrc/dwconv.hip); its limits are checked
-                # here, when the model is built, not at the first launch
-                s.k, s.C, s.l2 = int(st['k']), f_real, float(st.get('l2', 0.0))
-                if s.k < 1 or s.k > ops.DWCONV_MAX_KERNEL or s.k % 2 == 0:
-                    raise NotImplementedError(
-                        "DepthwiseConvolution1D: kernel_size %d (odd, in 1 .. %d: 'same' padding, "
-                        'the tile of asr_dwconv1d_*)' % (s.k, ops.DWCONV_MAX_KERNEL))
-                if f_real % 4 or f_pad != f_real:
-                    raise NotImplementedError(
-                        'DepthwiseConvolution1D over %d channels (%d columns): the width must be '
-                        'a multiple of 4 without pad columns' % (f_real, f_pad))
-                s.tensors = P.dwconv(s, alloc, None)
-            elif s.kind == 'glu':
-                if f_real % 8 or f_pad != f_real:
-                    raise NotImplementedError(
-                        'GLU over %d features (%d columns): the width must be a multiple of 8 '
-                        'without pad columns' % (f_real, f_pad))
-                s.C = f_real // 2
-                f_real = f_pad = s.C
-            elif s.kind == 'merge':
-                s.mode, s.skip = st['mode'], int(st['skip'])
-                s.scale = float(st.get('scale', 1.0))   # of the first input ('sum' only)
-                if s.scale != 1.0 and s.mode != 'sum':
-                    raise NotImplementedError("merge(scale=%r): with mode='sum' only" % s.scale)
-                src = self.stages[s.skip]
-                if (src.f_out, src.f_out_pad) != (f_real, f_pad):
-                    raise ValueError('merge: widths differ (%d vs %d)' % (src.f_out, f_real))
-                s.coef = 1.0 if s.mode == 'sum' else 0.5
-            else:
-                raise ValueError(s.kind)
+            s.first = not trainable_below   # no weights below: nothing there needs a gradient
+            f_real, f_pad = KINDS[s.kind].build(self, s, st, (f_real, f_pad))
+            trainable_below = trainable_below or bool(s.tensors)
             s.f_out, s.f_out_pad = f_real, f_pad
             s.p_hi = alloc.params
             self.stages.append(s)
+        del self._alloc
         widest = max([st.Hp for st in self.stages if st.kind == 'bilstm'] + [0])
         self.packed = (os.environ.get('ASR_GEMM_PREC', '1') != '0' and
                        (self._packed_mode == '1' or (self._packed_mode == 'auto' and widest >= 512)))
         self.num_classes = f_real
-        self._has_rnn = any(st.kind == 'birnn' for st in self.stages)
+        kinds = [KINDS[st.kind] for st in self.stages]
+        # (slots 2, 3 of the timeout flags: the SimpleRNN workspaces', ops.collect_timeout_flags)
+        self._has_rnn = any(k.extra_timeout_flags for k in kinds)
         # forward needs seq_len: the attention keys and the depthwise convolution's frames
-        self._has_mha = any(st.kind == 'mha' for st in self.stages)
-        self._needs_lens = self._has_mha or any(st.kind == 'dwconv' for st in self.stages)
+        self._has_mha = any(k.attention for k in kinds)
+        self._needs_lens = any(k.needs_lens for k in kinds)
         # ... and in_len, the lengths on the INPUT time axis: a SpecAugment stage's utterances
-        self._has_specaug = any(st.kind == 'specaug' for st in self.stages)
+        self._has_specaug = any(k.needs_in_len for k in kinds)
         self._bn = [(i, st) for i, st in enumerate(self.stages) if st.kind == 'bn']
         self._seqbn = [(i, st) for i, st in enumerate(self.stages)
                        if st.kind == 'bigru' and st.bn]
@@ -632,7 +480,6 @@ class Model(object):
         """
         T, n_pad, F = x.shape
         assert F in (self.num_features, self.f_in_pad0) and n_pad % 16 == 0
-        rows = T * n_pad
         if F != self.f_in_pad0:
             # (T, n_pad, F) -> zero-padded (T, n_pad, pad4(F)); the pad columns of the
             # buffer are written once (zeros) and never touched again
@@ -646,7 +493,6 @@ class Model(object):
         a = x
         self._acts = []
         drawn = [None]
-        nb = 0
         if self._overlap_mode == 'auto':
             self.overlap = not self._recurrence_fills_chip(n_pad)
         self._pipe_now = self._pipeline_on(n_pad)
@@ -657,7 +503,6 @@ class Model(object):
         self._pipe_now = self._pipe_now and not self.packed
         if n_valid == 1 and not need_grad:      # one utterance: the tile-free kernel, whole layers
             pipe = False
-        pre = {}
         if any(self._stage_packed(st) for st in self.stages):
             self._pack_weights()
         n_real = int(n_real or n_valid or n_pad)
@@ -672,418 +517,128 @@ class Model(object):
                     drawn[0] = self._draw_all_masks(n_pad)
                 return drawn[0][i]
             return None, None
+        fp = Pass(training=training, masks=masks, need_grad=need_grad, n_valid=n_valid,
+                  n_real=n_real, bn_weight=bn_weight, seq_len=seq_len, in_len=in_len,
+                  n_pad=n_pad, pipe=pipe, pre={}, nb=0, stage_masks=stage_masks)
         for si, s in enumerate(self.stages):
             rec = {'in': a}
-            T = a.shape[0]                      # (a time-strided convolution shortens the slab)
-            rows = T * n_pad
-            S = (self._pipe_split16 * T) // 16
-            if s.kind == 'reshape':
-                pass
-            elif s.kind == 'conv':
-                op = self._conv_op(si, s, T, n_pad)
-                # clipped ReLU: applied in the GEMM epilogue, only y exists (its mask
-                # 0 < z < clip reads the same from y); linear: y is z
-                y = self._buf('convy%d' % si, (op.T_out, n_pad, s.F_out * s.C_out))
-                nw = s.kt * s.kf * s.C_in * s.C_out
-                op.fwd(a.contiguous(), self._view(s.oW, nw), self._view(s.ob, s.C_out),
-                       None if s.clip > 0 else y, y, x_absmax=self._clip_bound(si))
-                rec.update(op=op, z=y)
-                a = y
-            elif s.kind == 'noise':
-                if training and s.value > 0:
-                    out = self._buf('noise%d' % si, a.shape)
-                    a = ops.gaussian_noise(a, out, s.value, self.rng_seed, 4 * si, self._step)
-                    if s.f_out_pad != s.f_out and all(p.kind == 'specaug'
-                                                      for p in self.stages[:si]):
-                        a[:, :, s.f_out:] = 0.0        # keep the input pad columns zero
-            elif s.kind == 'specaug':
-                if training:        # (never in place: the caller keeps its slab)
-                    out = self._buf('specaug%d' % si, a.shape)
-                    a = ops.specaug_apply(a.contiguous(), out, min(n_real, n_pad), s.f_in,
-                                          self.rng_seed, 4 * si, self._step, lens=in_len,
-                                          **s.policy)
-            elif s.kind == 'dropout':
-                if training and s.value > 0:
-                    keep = self._buf('dropmask%d' % si, a.shape)
-                    out = self._buf('dropout%d' % si, a.shape)
-                    a = ops.dropout_apply(a, out, keep, s.value, 1.0 / (1.0 - s.value),
-                                          self.rng_seed, 4 * si, self._step)
-                    rec['mask'] = keep
-            elif s.kind == 'merge':       # residual: c * (scale * new + skip)
-                out = self._buf('merge%d' % si, a.shape)
-                a = ops.axpby(s.coef * s.scale, a, s.coef, self._acts[s.skip]['out'], out)
-            elif s.kind == 'dense':
-                out = self._buf('dense%d' % si, (T, n_pad, s.n_out))
-                ops.gemm(a, self.params, out, rows, s.n_out, s.f_in_pad, b_off=s.oW,
-                         bias=self._view(s.ob, s.n_out))
-                a = out
-            elif s.kind == 'bilstm':
-                Hp = s.Hp
-                BW, BU = stage_masks(si)[:2]
-                rec['BW'], rec['BU'] = BW, BU
-                var = self._variant_args(s, si, T, n_pad, training, masks)
-                rec['var'] = var
-                if s.mi is None and s.ln is None:
-                    zx = self._buf('zx%d_%d' % (nb % 2, Hp), (T, n_pad, 2, 4 * Hp))
-                else:       # x@W is needed again by BPTT: one buffer per layer
-                    zx = self._buf('zxmi%d' % si, (T, n_pad, 2, 4 * Hp))
-                    rec['zx'] = zx
-                nb += 1
-                main = torch.cuda.current_stream(self.device)
-                inner_done, halves = pre.pop(si, (None, False))
-                if self._stage_packed(s):
-                    # |y| < 1 behind a BiLSTM stage with a bounded activation; anything else
-                    # is measured
-                    prev = self.stages[si - 1] if si > 0 else None
-                    bound = self._clip_bound(si)
-                    amax = self._const_one() if (prev is not None and self._y_bounded(prev)) \
-                        else (bound if bound is not None
-                              else ops.absmax(a, self._buf('aamax%d' % si, (1,))))
-                    rec['pa'] = self._pack_input(si, s, a, BW, rows, n_pad, amax)
-                    self._gate_gemm_hl(s, si, rec['pa'], zx, rows)
-                elif inner_done is None:
-                    self._gate_gemm(a, s, zx, BW, 0, rows, n_pad)
-                elif halves:
-                    # frames [T-S, S) were projected while the previous layer ran, and of the
-                    # others the half of the reduction that was final by then (below): what is
-                    # left on the critical path is the other half of those frames
-                    main.wait_event(inner_done)
-                    # (r6) the two row ranges are independent and each is two launch-bound GEMMs
-                    # of ~25 us: one range on the pipe stream (idle by now), the other here
-                    fork = (self._pipe is not None
-                            and os.environ.get('ASR_PIPE_TAIL_FORK', '1') != '0')
-                    if fork:
-                        ev0 = torch.cuda.Event()
-                        ev0.record(main)
-                        with torch.cuda.stream(self._pipe):
-                            self._pipe.wait_event(ev0)
-                            self._gate_gemm_half(a, s, zx, BW, S * n_pad, rows, n_pad, 0, False)
-                            ev1 = torch.cuda.Event()
-                            ev1.record(self._pipe)
-                        self._gate_gemm_half(a, s, zx, BW, 0, (T - S) * n_pad, n_pad, 1, False)
-                        main.wait_event(ev1)
-                    else:
-                        self._gate_gemm_half(a, s, zx, BW, 0, (T - S) * n_pad, n_pad, 1, False)
-                        self._gate_gemm_half(a, s, zx, BW, S * n_pad, rows, n_pad, 0, False)
-                else:       # frames [T-S, S) were projected while the previous layer ran
-                    self._gate_gemm(a, s, zx, BW, 0, (T - S) * n_pad, n_pad)
-                    self._gate_gemm(a, s, zx, BW, S * n_pad, rows, n_pad)
-                    main.wait_event(inner_done)
-                # (the single-utterance kernel writes row 0 only: no junk in the padding rows)
-                one = n_valid == 1 and not need_grad
-                y = self._buf('y%d' % si, (T, n_pad, 2 * Hp), zero=one)
-                cell = self._buf('cell%d' % si, (T, n_pad, 2, Hp), zero=one)
-                gates = self._buf('gates%d' % si, (T, n_pad, 2, 4 * Hp), zero=one)
-                U = self._view(s.oU, 2 * Hp * 4 * Hp)
-                nxt = self.stages[si + 1] if si + 1 < len(self.stages) else None
-                if s.ln is not None:        # generic row-per-workgroup cell (csrc/lstm_ln.hip)
-                    uh = self._buf('uh%d' % si, (T, n_pad, 2, 4 * Hp))
-                    rec['uh'] = uh
-                    ops.lstm_ln_seq_fwd(zx, U, self._view(s.ocell, 68 * Hp), uh, y, cell, gates, T,
-                                        n_pad, Hp, has_mi=s.mi is not None, mask_u=BU,
-                                        zone_c=var.get('zone_c'), zone_h=var.get('zone_h'),
-                                        act=s.act)
-                elif pipe and nxt is not None and nxt.kind == 'bilstm' and not var \
-                        and nxt.mi is None and nxt.ln is None:
-                    # after S = 13T/16 steps the frames [T-S, S) of y are final in BOTH
-                    # directions: the next layer's input projection of those frames runs
-                    # on the pipe stream while this recurrence finishes its last steps
-                    # (nothing runs beside the first S steps: the library's choice of geometry;
-                    # the GEMMs of the next layer run beside the last T - S: sixteen units per
-                    # workgroup there, i.e. the fewest CUs)
-                    ops.lstm_seq_fwd(zx, U, y, cell, gates, T, n_pad, Hp, mask_u=BU,
-                                     mode=self.lstm_mode, steps=(0, S))
-                    ev = torch.cuda.Event()
-                    ev.record(main)
-                    zx_n = self._buf('zx%d_%d' % (nb % 2, nxt.Hp), (T, n_pad, 2, 4 * nxt.Hp))
-                    with torch.cuda.stream(self._pipe):
-                        self._pipe.wait_event(ev)
-                        BWn = stage_masks(si + 1)[0]
-                        self._gate_gemm(y, nxt, zx_n, BWn, (T - S) * n_pad, S * n_pad, n_pad)
-                        # (the next stage's input must be exactly [y_f, y_b] of this one)
-                        halves = self._pipe_halves and nxt.f_in_pad == 2 * Hp
-                        if halves:
-                            # x = [y_f, y_b]: after S steps y_f is final on the frames [0, T-S)
-                            # too and y_b on [S, T) -- their halves of the reduction
-                            # (+ bias) go ahead as well
-                            self._gate_gemm_half(y, nxt, zx_n, BWn, 0, (T - S) * n_pad, n_pad,
-                                                 0, True)
-                            self._gate_gemm_half(y, nxt, zx_n, BWn, S * n_pad, rows, n_pad,
-                                                 1, True)
-                        done = torch.cuda.Event()
-                        done.record(self._pipe)
-                    pre[si + 1] = (done, halves)
-                    rec['ws'] = ops.lstm_seq_fwd(zx, U, y, cell, gates, T, n_pad, Hp, mask_u=BU,
-                                                 mode=self.lstm_mode, steps=(S, T - S), units=16)
-                else:
-                    rec['ws'] = ops.lstm_seq_fwd(
-                        zx, U, y, cell, gates, T, n_pad, Hp, mask_u=BU, mode=self.lstm_mode,
-                        n_valid=n_valid if not need_grad else 0, **var)
-                rec.update(y=y, cell=cell, gates=gates)
-                a = y
-            elif s.kind == 'act':
-                if not getattr(s, 'fused', False):     # (else applied by the BN stage before)
-                    out = self._buf('act%d' % si, a.shape)
-                    a = ops.activation_fwd(a.contiguous(), out, s.act)
-            elif s.kind == 'dwconv':
-                N = min(n_real, n_pad)
-                a = a.contiguous()
-                rec.update(**{'in': a, 'N': N, 'lens': seq_len})
-                out = self._buf('dwconv%d' % si, a.shape)
-                a = ops.dwconv1d_fwd(a, self._view(s.oW, s.k * s.C), self._view(s.ob, s.C), out,
-                                     N, s.k, lens=seq_len)
-            elif s.kind == 'glu':
-                a = a.contiguous()
-                rec['in'] = a
-                a = ops.glu_fwd(a, self._buf('glu%d' % si, (T, n_pad, s.C)))
-            elif s.kind == 'bn':
-                a = self._bn_forward(s, si, a.contiguous(), rec, training, n_real, bn_weight)
-            elif s.kind == 'ln':
-                a = self._ln_forward(s, si, a.contiguous(), rec, need_grad, n_real)
-            elif s.kind == 'mha':
-                a = self._mha_forward(s, si, a.contiguous(), rec, need_grad, n_real, seq_len)
-            elif s.kind == 'posenc':
-                out = self._buf('posenc%d' % si, a.shape)
-                a = ops.posenc_add(a.contiguous(), out, min(n_real, n_pad), s.D)
-            elif s.kind == 'birnn':
-                Hp = s.Hp
-                BW, BU = stage_masks(si)[:2]
-                rec['BW'], rec['BU'] = BW, BU
-                zx = self._buf('rzx%d' % si, (T, n_pad, 2, Hp))
-                self._rec_proj(a.contiguous(), s, zx, Hp, BW, rows, n_pad,
-                               bias=self._view(s.ob, 2 * Hp))
-                h = self._buf('rh%d' % si, (T, n_pad, 2, Hp))
-                ysum = self._buf('rsum%d' % si, (T, n_pad, Hp)) if s.merge == 'sum' else None
-                rec['ws'] = ops.rnn_seq_fwd(zx, self._view(s.oU, 2 * Hp * Hp), h, T, n_pad, Hp,
-                                            act=s.act, mask_u=BU, y_sum=ysum, mode=self.lstm_mode)
-                rec['h'] = h
-                a = ysum if ysum is not None else h.view(T, n_pad, 2 * Hp)
-            elif s.kind == 'bigru':
-                a = self._gru_forward(s, si, a.contiguous(), rec, stage_masks(si)[:2], n_pad,
-                                      training, n_real, bn_weight, seq_len)
-            elif s.kind == 'birhn':
-                a = self._rhn_forward(s, si, a.contiguous(), rec, stage_masks(si)[:2], n_pad)
-            rec['out'] = a
+            a = rec['out'] = KINDS[s.kind].forward(self, s, si, a, rec, fp)
             self._acts.append(rec)
         return a
 
-    def _gru_forward(self, s, si, a, rec, masks, n_pad, training=False, n_real=None,
-                     bn_weight=None, seq_len=None):
-        """Bidirectional(GRU) stage (csrc/gru.hip): zx = (a (.) B_W[d]) @ W_d + b_d from the
-        GEMMs, then the recurrence; h, the gates z | r | hh and r (.) m are kept for BPTT.
-        batch_norm: the GEMMs write the bias-free projection p into a buffer of the layer (the
-        backward pass reads it again), and zx = BN(p) goes to a scratch all layers share (BPTT
-        never reads zx)."""
-        T, Hp = a.shape[0], s.Hp
+    def _bilstm_forward(self, s, si, a, rec, fp):
+        """The BiLSTM entry of the stage table (core/stages.py): the input projection (whole, or
+        what the layer below has not projected already on the pipe stream), the recurrence, and
+        the next BiLSTM layer's projection of the frames that are final before its last steps."""
+        training, masks, need_grad, n_valid = fp.training, fp.masks, fp.need_grad, fp.n_valid
+        n_pad, pipe, pre, stage_masks = fp.n_pad, fp.pipe, fp.pre, fp.stage_masks
+        T = a.shape[0]                      # (a time-strided convolution shortens the slab)
         rows = T * n_pad
-        BW, BU = masks
+        S = (self._pipe_split16 * T) // 16
+        Hp = s.Hp
+        BW, BU = stage_masks(si)[:2]
         rec['BW'], rec['BU'] = BW, BU
-        zx = self._buf('gzx%d' % si, (T, n_pad, 2, 3 * Hp))
-        self._rec_proj(a, s, zx, 3 * Hp, BW, rows, n_pad,
-                       bias=None if s.bn else self._view(s.ob, 6 * Hp))
-        if s.bn:
-            zx = self._seqbn_forward(s, si, zx, rec, training, n_real, bn_weight, seq_len)
-        h = self._buf('gh%d' % si, (T, n_pad, 2, Hp))
-        gates = self._buf('ggates%d' % si, (T, n_pad, 2, 3 * Hp))
-        rm = self._buf('grm%d' % si, (T, n_pad, 2, Hp))
-        ysum = self._buf('gsum%d' % si, (T, n_pad, Hp)) if s.merge == 'sum' else None
-        ops.gru_seq_fwd(zx, self._view(s.oU, 2 * Hp * 3 * Hp), h, gates, rm, T, n_pad, Hp,
-                        act=s.act, mask_u=BU, y_sum=ysum)
-        rec.update(h=h, gates=gates, rm=rm)
-        return ysum if ysum is not None else h.view(T, n_pad, 2 * Hp)
-
-    def _seqbn_forward(self, s, si, p, rec, training, n_real, bn_weight, seq_len):
-        """zx = BN(p) of a GRU(batch_norm=True) stage (K18): batch statistics over the valid frames
-        in training (saved, with p, for the backward pass; the moments block of the running
-        update written behind the flag slots), the running moments otherwise."""
-        T, n_pad = p.shape[0], p.shape[1]
-        Wd = 6 * s.Hp
-        N = min(int(n_real or n_pad), n_pad)
-        p3 = p.view(T, n_pad, Wd)
-        y = self._buf('gzxbn_%d' % Wd, (T, n_pad, Wd))
-        gamma, beta = self._view(s.og, Wd), self._view(s.obeta, Wd)
-        rm, rv, mom = self._bn_views(s, Wd)
-        if not training:
-            ops.seqbn_fwd_infer(p3, y, gamma, beta, rm, rv, N, Wd, s.bn_eps)
-            return y.view(T, n_pad, 2, 3 * s.Hp)
-        stats = self._buf('gbnstats%d' % si, (ops.seqbn_stats_len(Wd),))
-        # (data parallel: moments about the running mean, pooled by the gradient all-reduce, as
-        # in _bn_forward; the weight |V| is counted on the device, 0 for a zero-weight dummy)
-        dist = self._dist_active()
-        ops.seqbn_fwd_train(p3, y, gamma, beta, stats, N, Wd, lens=seq_len, eps=s.bn_eps,
-                            moments=mom, shift=rm if dist else None,
-                            weight=0.0 if bn_weight == 0 else 1.0)
-        rec.update(p=p3, stats=stats, N=N, lens=seq_len, shift=None if dist else stats[:Wd])
-        return y.view(T, n_pad, 2, 3 * s.Hp)
-
-    def _gru_backward(self, s, si, rec, da, first, split):
-        """BPTT of a GRU stage (csrc/gru.hip), then its weight gradients and dx from the GEMMs:
-        dU_z, dU_r [d] = (h_prev (.) B_U)^T [da_z | da_r], dU_h[d] = (r (.) m)^T da_h (r (.) m
-        kept by the forward pass), dW[d] = (x (.) B_W)^T da_d, db from the per-batch-tile sums,
-        dx = sum_d B_W[d] (.) (da_d @ W_d^T).  Returns dx (or None)."""
-        T, n_pad = da.shape[0], da.shape[1]
-        rows, Hp = T * n_pad, s.Hp
-        BW, BU, h, a_in = rec['BW'], rec['BU'], rec['h'], rec['in']
-        dg = self._buf('gda%d' % si, (T, n_pad, 2, 3 * Hp))
-        dbp = self._buf('gdbp%d' % si, (n_pad // 16, 2, 3 * Hp))
-        zmx = self._buf('gdamax%d' % si, (1,))
-        ops.gru_seq_bwd(da.contiguous(), self._view(s.oU, 2 * Hp * 3 * Hp), h, rec['gates'],
-                        dg, T, n_pad, Hp, act=s.act, mask_u=BU,
-                        shared_dy=s.merge == 'sum', db_part=dbp, dz_absmax=zmx)
-        if not s.bn:
-            ops.colsum(dbp, n_pad // 16, 6 * Hp, 6 * Hp, self._gview(s.ob, 6 * Hp))
-        for d in range(2):
-            oU = s.oU + d * Hp * 3 * Hp
-            self._rec_du_prev(h, dg, oU, d, 3 * Hp, 2 * Hp, T, n_pad, Hp,
-                              None if BU is None else BU[d], split, zmx)
-            ops.gemm(rec['rm'], dg, self.grads, Hp, Hp, rows, trans_a=True, lda=2 * Hp,
-                     ldb=6 * Hp, ldc=3 * Hp, a_off=d * Hp, b_off=d * 3 * Hp + 2 * Hp,
-                     c_off=oU + 2 * Hp, split_k=split, b_absmax=zmx)
-        if s.bn:
-            # dU above came from da; dW and dx come from dp = BN'(da), which has its own absmax
-            # (dbeta is what colsum(db_part) would give: the one reduction pass writes both)
-            dp = self._buf('gdp_%d' % (6 * Hp), (T, n_pad, 6 * Hp))
-            zmx = self._buf('gdpmax%d' % si, (1,))
-            ops.seqbn_bwd(rec['p'], dg.view(T, n_pad, 6 * Hp), self._view(s.og, 6 * Hp),
-                          rec['stats'], dp, self._gview(s.og, 6 * Hp), rec['N'], 6 * Hp,
-                          lens=rec['lens'], dbeta=self._gview(s.obeta, 6 * Hp), dp_absmax=zmx)
-            dg = dp
-        self._rec_dw(a_in.contiguous(), dg, s, 3 * Hp, BW, rows, n_pad, split, zmx)
-        return self._rec_dx(dg, s, si, 3 * Hp, BW, T, n_pad, zmx, first)
-
-    def _rhn_forward(self, s, si, a, rec, masks, n_pad):
-        """Bidirectional(RHN) stage (csrc/rhn.hip): zx = (a (.) B_W[d]) @ W_d from the GEMMs (the
-        kernel adds every level's bias), then the recurrence; the states and gates of all levels
-        are kept for BPTT, level-major.  B_U is (2, L, n_pad, Hp): one mask per level."""
-        T, Hp, Ld, Wd = a.shape[0], s.Hp, s.depth, s.nblk * s.Hp
-        rows = T * n_pad
-        BW, BU = masks
-        rec['BW'], rec['BU'] = BW, BU
-        zx = self._buf('hzx%d' % si, (T, n_pad, 2, Wd))
-        self._rec_proj(a, s, zx, Wd, BW, rows, n_pad)
-        h = self._buf('hh%d' % si, (Ld, T, n_pad, 2, Hp))
-        gates = self._buf('hgates%d' % si, (Ld, T, n_pad, 2, Wd))
-        ysum = self._buf('hsum%d' % si, (T, n_pad, Hp)) if s.merge == 'sum' else None
-        ops.rhn_seq_fwd(zx, self._view(s.oU, 2 * Ld * Hp * Wd), self._view(s.ob, 2 * Ld * Wd), h,
-                        gates, T, n_pad, Hp, Ld, coupling=s.coupling, act=s.act, mask_u=BU,
-                        y_sum=ysum)
-        rec.update(h=h, gates=gates)
-        return ysum if ysum is not None else h[Ld - 1].view(T, n_pad, 2 * Hp)
-
-    def _rhn_backward(self, s, si, rec, da, first, split):
-        """BPTT of an RHN stage (csrc/rhn.hip), then its weight gradients and dx from the GEMMs:
-        dU_l[d] = (s_prev^l (.) B_U[d, l])^T da^l, where s_prev^l is the states slab of level
-        l - 1 or, for l = 0, slab L - 1 one frame earlier in the direction's processing order;
-        dW[d] = (x (.) B_W)^T da^0_d, db from the per-batch-tile sums,
-        dx = sum_d B_W[d] (.) (da^0_d @ W_d^T).  Returns dx (or None)."""
-        T, n_pad = da.shape[0], da.shape[1]
-        rows, Hp, Ld, Wd = T * n_pad, s.Hp, s.depth, s.nblk * s.Hp
-        BW, BU, h, a_in = rec['BW'], rec['BU'], rec['h'], rec['in']
-        dg = self._buf('hda%d' % si, (Ld, T, n_pad, 2, Wd))
-        dbp = self._buf('hdbp%d' % si, (n_pad // 16, 2, Ld, Wd))
-        zmx = self._buf('hdamax%d' % si, (1,))
-        ops.rhn_seq_bwd(da.contiguous(), self._view(s.oU, 2 * Ld * Hp * Wd), h, rec['gates'], dg,
-                        T, n_pad, Hp, Ld, coupling=s.coupling, act=s.act, mask_u=BU,
-                        shared_dy=s.merge == 'sum', db_part=dbp, dz_absmax=zmx)
-        ops.colsum(dbp, n_pad // 16, 2 * Ld * Wd, 2 * Ld * Wd, self._gview(s.ob, 2 * Ld * Wd))
-        for d in range(2):
-            for l in range(Ld):
-                oU = s.oU + (d * Ld + l) * Hp * Wd
-                scale = None if BU is None else BU[d, l]
-                if l > 0:
-                    ops.gemm(h, dg, self.grads, Hp, Wd, rows, trans_a=True, lda=2 * Hp,
-                             ldb=2 * Wd, ldc=Wd, a_off=(l - 1) * rows * 2 * Hp + d * Hp,
-                             b_off=l * rows * 2 * Wd + d * Wd, c_off=oU, split_k=split,
-                             a_scale=scale, a_scale_period=n_pad, b_absmax=zmx)
-                else:
-                    self._rec_du_prev(h, dg, oU, d, Wd, Wd, T, n_pad, Hp, scale, split, zmx,
-                                      h_off=(Ld - 1) * rows * 2 * Hp)
-        self._rec_dw(a_in.contiguous(), dg, s, Wd, BW, rows, n_pad, split, zmx)
-        return self._rec_dx(dg, s, si, Wd, BW, T, n_pad, zmx, first)
-
-    def _bn_forward(self, s, si, a, rec, training, n_real, bn_weight):
-        """BatchNormalization stage: batch statistics of the n_real real rows in training (saved
-        for the backward pass; the moments block of the running update written behind the flag
-        slots), the running moments otherwise."""
-        T, n_pad, ld = a.shape
-        y = self._buf('bn%d' % si, a.shape)
-        gamma, beta = self._view(s.og, s.C), self._view(s.obeta, s.C)
-        rm, rv, mom = self._bn_views(s, s.C)
-        if not training:
-            return ops.bn_fwd_infer(a, y, gamma, beta, rm, rv, min(n_real, n_pad), ld, s.C,
-                                    s.eps, s.clip)
-        stats = self._buf('bnstats%d' % si, (ops.bn_stats_len(s.C),))
-        # data parallel the moments are taken about the running mean (the same on every rank),
-        # weighted by the rank's real frames, and pooled by the gradient all-reduce
-        dist = self._dist_active()
-        ops.bn_fwd_train(a, y, gamma, beta, stats, min(n_real, n_pad), ld, s.C, s.eps, s.clip,
-                         moments=mom, shift=rm if dist else None,
-                         weight=float(bn_weight * T))
-        rec.update(stats=stats, N=min(n_real, n_pad), shift=None if dist else stats[:s.C])
-        return y
-
-    def _ln_forward(self, s, si, a, rec, need_grad, n_real):
-        """LayerNormalization stage: the same pass in training and inference; (mu, 1 / sigma)
-        of every row is kept only when a backward pass will read it."""
-        T, n_pad, ld = a.shape
-        y = self._buf('ln%d' % si, a.shape)
-        N = min(n_real, n_pad)
-        stats = self._buf('lnstats%d' % si, (ops.ln_stats_len(T, n_pad),)) if need_grad else None
-        ops.ln_fwd(a, y, self._view(s.og, ld), self._view(s.obeta, ld), N, s.seg_H, s.seg_Hp,
-                   s.segs, s.eps, stats=stats)
-        rec.update(stats=stats, N=N)
-        return y
-
-    def _mha_forward(self, s, si, a, rec, need_grad, n_real, seq_len):
-        """MultiHeadAttention stage: qkv = a W_qkv + b_qkv (one GEMM), the fused attention core
-        over each utterance's valid keys (seq_len: device lengths on this time axis; None: every
-        frame), the output projection.  The row log-sum-exp is kept only for a backward pass."""
-        T, n_pad, _ = a.shape
-        rows, D, N = T * n_pad, s.D, min(n_real, n_pad)
-        qkv = self._buf('qkv%d' % si, (T, n_pad, 3 * D))
-        ops.gemm(a, self.params, qkv, rows, 3 * D, s.f_in_pad, b_off=s.oW,
-                 bias=self._view(s.ob, 3 * D))
-        ctx = self._buf('attn%d' % si, (T, n_pad, D))
-        lse = self._buf('lse%d' % si, (ops.attn_lse_len(T, n_pad, s.heads),)) if need_grad \
-            else None
-        ops.attn_fwd(qkv, ctx, N, s.heads, s.dh, lens=seq_len, lse=lse)
-        out = self._buf('mha%d' % si, (T, n_pad, s.n_out))
-        ops.gemm(ctx, self.params, out, rows, s.n_out, D, b_off=s.oWo,
-                 bias=self._view(s.obo, s.n_out))
-        rec.update(qkv=qkv, ctx=ctx, lse=lse, N=N, lens=seq_len)
-        return out
-
-    def _mha_backward(self, s, si, rec, a_in, da, first, split):
-        """The two projections' wgrad / colsum / dgrad GEMMs around asr_attn_bwd; returns dx, or
-        None for the first trainable stage."""
-        T, n_pad, _ = a_in.shape
-        rows, D = T * n_pad, s.D
-        da = da.contiguous()
-        gmx = ops.absmax(da, self._buf('damax%d' % si, (1,)))
-        ops.gemm(rec['ctx'], da, self.grads, D, s.n_out, rows, trans_a=True, c_off=s.oWo,
-                 split_k=split, b_absmax=gmx)
-        ops.colsum(da, rows, s.n_out, s.n_out, self._gview(s.obo, s.n_out))
-        dctx = self._buf('dattn%d' % si, (T, n_pad, D))
-        ops.gemm(da, self.params, dctx, rows, D, s.n_out, trans_b=True, b_off=s.oWo,
-                 a_absmax=gmx)
-        dqkv = self._buf('dqkv%d' % si, (T, n_pad, 3 * D))
-        ops.attn_bwd(rec['qkv'], rec['ctx'], rec['lse'], dctx, dqkv, rec['N'], s.heads, s.dh,
-                     lens=rec['lens'])
-        qmx = ops.absmax(dqkv, self._buf('dqkvmax%d' % si, (1,)))
-        ops.gemm(a_in, dqkv, self.grads, s.f_in_pad, 3 * D, rows, trans_a=True, c_off=s.oW,
-                 split_k=split, b_absmax=qmx)
-        # db_q and db_v.  Softmax does not see a shift of all scores of a row, so the key bias
-        # has no effect and its gradient is identically 0: a column sum of dK would leave
-        # rounding noise there, which Adam would normalise into steps of +-lr.  It is never
-        # produced: that third of the gradient keeps the zero the buffer is created with.
-        ops.colsum(dqkv, rows, D, 3 * D, self._gview(s.ob, D))
-        ops.colsum(dqkv, rows, D, 3 * D, self._gview(s.ob + 2 * D, D), x_off=2 * D)
-        if first:
-            return None
-        dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-        ops.gemm(dqkv, self.params, dx, rows, s.f_in_pad, 3 * D, trans_b=True, b_off=s.oW,
-                 a_absmax=qmx)
-        return dx
+        var = self._variant_args(s, si, T, n_pad, training, masks)
+        rec['var'] = var
+        if s.mi is None and s.ln is None:
+            zx = self._buf('zx%d_%d' % (fp.nb % 2, Hp), (T, n_pad, 2, 4 * Hp))
+        else:       # x@W is needed again by BPTT: one buffer per layer
+            zx = self._buf('zxmi%d' % si, (T, n_pad, 2, 4 * Hp))
+            rec['zx'] = zx
+        fp.nb += 1
+        main = torch.cuda.current_stream(self.device)
+        inner_done, halves = pre.pop(si, (None, False))
+        if self._stage_packed(s):
+            # |y| < 1 behind a BiLSTM stage with a bounded activation; anything else
+            # is measured
+            prev = self.stages[si - 1] if si > 0 else None
+            bound = self._clip_bound(si)
+            amax = self._const_one() if (prev is not None and self._y_bounded(prev)) \
+                else (bound if bound is not None
+                      else ops.absmax(a, self._buf('aamax%d' % si, (1,))))
+            rec['pa'] = self._pack_input(si, s, a, BW, rows, n_pad, amax)
+            self._gate_gemm_hl(s, si, rec['pa'], zx, rows)
+        elif inner_done is None:
+            self._gate_gemm(a, s, zx, BW, 0, rows, n_pad)
+        elif halves:
+            # frames [T-S, S) were projected while the previous layer ran, and of the
+            # others the half of the reduction that was final by then (below): what is
+            # left on the critical path is the other half of those frames
+            main.wait_event(inner_done)
+            # (r6) the two row ranges are independent and each is two launch-bound GEMMs
+            # of ~25 us: one range on the pipe stream (idle by now), the other here
+            fork = (self._pipe is not None
+                    and os.environ.get('ASR_PIPE_TAIL_FORK', '1') != '0')
+            if fork:
+                ev0 = torch.cuda.Event()
+                ev0.record(main)
+                with torch.cuda.stream(self._pipe):
+                    self._pipe.wait_event(ev0)
+                    self._gate_gemm_half(a, s, zx, BW, S * n_pad, rows, n_pad, 0, False)
+                    ev1 = torch.cuda.Event()
+                    ev1.record(self._pipe)
+                self._gate_gemm_half(a, s, zx, BW, 0, (T - S) * n_pad, n_pad, 1, False)
+                main.wait_event(ev1)
+            else:
+                self._gate_gemm_half(a, s, zx, BW, 0, (T - S) * n_pad, n_pad, 1, False)
+                self._gate_gemm_half(a, s, zx, BW, S * n_pad, rows, n_pad, 0, False)
+        else:       # frames [T-S, S) were projected while the previous layer ran
+            self._gate_gemm(a, s, zx, BW, 0, (T - S) * n_pad, n_pad)
+            self._gate_gemm(a, s, zx, BW, S * n_pad, rows, n_pad)
+            main.wait_event(inner_done)
+        # (the single-utterance kernel writes row 0 only: no junk in the padding rows)
+        one = n_valid == 1 and not need_grad
+        y = self._buf('y%d' % si, (T, n_pad, 2 * Hp), zero=one)
+        cell = self._buf('cell%d' % si, (T, n_pad, 2, Hp), zero=one)
+        gates = self._buf('gates%d' % si, (T, n_pad, 2, 4 * Hp), zero=one)
+        U = self._view(s.oU, 2 * Hp * 4 * Hp)
+        nxt = self.stages[si + 1] if si + 1 < len(self.stages) else None
+        if s.ln is not None:        # generic row-per-workgroup cell (csrc/lstm_ln.hip)
+            uh = self._buf('uh%d' % si, (T, n_pad, 2, 4 * Hp))
+            rec['uh'] = uh
+            ops.lstm_ln_seq_fwd(zx, U, self._view(s.ocell, 68 * Hp), uh, y, cell, gates, T,
+                                n_pad, Hp, has_mi=s.mi is not None, mask_u=BU,
+                                zone_c=var.get('zone_c'), zone_h=var.get('zone_h'),
+                                act=s.act)
+        elif pipe and nxt is not None and nxt.kind == 'bilstm' and not var \
+                and nxt.mi is None and nxt.ln is None:
+            # after S = 13T/16 steps the frames [T-S, S) of y are final in BOTH
+            # directions: the next layer's input projection of those frames runs
+            # on the pipe stream while this recurrence finishes its last steps
+            # (nothing runs beside the first S steps: the library's choice of geometry;
+            # the GEMMs of the next layer run beside the last T - S: sixteen units per
+            # workgroup there, i.e. the fewest CUs)
+            ops.lstm_seq_fwd(zx, U, y, cell, gates, T, n_pad, Hp, mask_u=BU,
+                             mode=self.lstm_mode, steps=(0, S))
+            ev = torch.cuda.Event()
+            ev.record(main)
+            zx_n = self._buf('zx%d_%d' % (fp.nb % 2, nxt.Hp), (T, n_pad, 2, 4 * nxt.Hp))
+            with torch.cuda.stream(self._pipe):
+                self._pipe.wait_event(ev)
+                BWn = stage_masks(si + 1)[0]
+                self._gate_gemm(y, nxt, zx_n, BWn, (T - S) * n_pad, S * n_pad, n_pad)
+                # (the next stage's input must be exactly [y_f, y_b] of this one)
+                halves = self._pipe_halves and nxt.f_in_pad == 2 * Hp
+                if halves:
+                    # x = [y_f, y_b]: after S steps y_f is final on the frames [0, T-S)
+                    # too and y_b on [S, T) -- their halves of the reduction
+                    # (+ bias) go ahead as well
+                    self._gate_gemm_half(y, nxt, zx_n, BWn, 0, (T - S) * n_pad, n_pad,
+                                         0, True)
+                    self._gate_gemm_half(y, nxt, zx_n, BWn, S * n_pad, rows, n_pad,
+                                         1, True)
+                done = torch.cuda.Event()
+                done.record(self._pipe)
+            pre[si + 1] = (done, halves)
+            rec['ws'] = ops.lstm_seq_fwd(zx, U, y, cell, gates, T, n_pad, Hp, mask_u=BU,
+                                         mode=self.lstm_mode, steps=(S, T - S), units=16)
+        else:
+            rec['ws'] = ops.lstm_seq_fwd(
+                zx, U, y, cell, gates, T, n_pad, Hp, mask_u=BU, mode=self.lstm_mode,
+                n_valid=n_valid if not need_grad else 0, **var)
+        rec.update(y=y, cell=cell, gates=gates)
+        a = y
+        return a
 
     def _bn_update(self):
         """Running-moment update of every BatchNormalization stage, once per optimisation step,
@@ -1101,80 +656,6 @@ class Model(object):
             rm, rv, mom = self._bn_views(s, n)
             ops.bn_update_running(rm, rv, mom, n, momentum, shift=rec['shift'], flags=flags)
 
-    # The GEMMs around a recurrence (SimpleRNN, GRU, RHN).  G is the gate width of one direction:
-    # the rows of zx and of the gate gradient dg hold both directions, 2 G wide, and so do W's.
-    def _rec_proj(self, a, s, zx, G, BW, rows, n_pad, bias=None):
-        """zx = (a (.) B_W[d]) @ W_d (+ b_d), both directions; bias (2 G) or None."""
-        if BW is None:
-            ops.gemm(a, self.params, zx, rows, 2 * G, s.f_in_pad, b_off=s.oW, bias=bias)
-            return
-        for d in range(2):
-            ops.gemm(a, self.params, zx, rows, G, s.f_in_pad, ldb=2 * G, ldc=2 * G,
-                     b_off=s.oW + d * G, c_off=d * G,
-                     bias=None if bias is None else bias[d * G:(d + 1) * G],
-                     a_scale=BW[d], a_scale_period=n_pad)
-
-    def _rec_dw(self, a_in, dg, s, G, BW, rows, n_pad, split, zmx):
-        """dW[d] = (x (.) B_W[d])^T dg_d."""
-        if BW is None:
-            ops.gemm(a_in, dg, self.grads, s.f_in_pad, 2 * G, rows, trans_a=True, c_off=s.oW,
-                     split_k=split, b_absmax=zmx)
-            return
-        for d in range(2):
-            ops.gemm(a_in, dg, self.grads, s.f_in_pad, G, rows, trans_a=True, ldb=2 * G,
-                     ldc=2 * G, b_off=d * G, c_off=s.oW + d * G, split_k=split,
-                     a_scale=BW[d], a_scale_period=n_pad, b_absmax=zmx)
-
-    def _rec_dx(self, dg, s, si, G, BW, T, n_pad, zmx, first):
-        """dx = sum_d B_W[d] (.) (dg_d @ W_d^T); None for the first stage."""
-        if first:
-            return None
-        rows = T * n_pad
-        dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-        if BW is None:
-            ops.gemm(dg, self.params, dx, rows, s.f_in_pad, 2 * G, trans_b=True, b_off=s.oW,
-                     a_absmax=zmx)
-            return dx
-        for d in range(2):
-            ops.gemm(dg, self.params, dx, rows, s.f_in_pad, G, trans_b=True, lda=2 * G,
-                     ldb=2 * G, a_off=d * G, b_off=s.oW + d * G, c_scale=BW[d],
-                     c_scale_period=n_pad, beta=0.0 if d == 0 else 1.0, a_absmax=zmx)
-        return dx
-
-    def _rec_du_prev(self, h, dg, c_off, d, G, N, T, n_pad, Hp, scale, split, zmx, h_off=0):
-        """grads[c_off:] (Hp, G), columns [0, N) = (h_prev (.) scale)^T dg_d[:, :N], where h_prev is
-        the slab h (T, n_pad, 2, Hp) at h_off one frame earlier in direction d's processing
-        order: 0 before the first frame, so T == 1 leaves zeros."""
-        kk = (T - 1) * n_pad
-        if kk > 0:
-            ops.gemm(h, dg, self.grads, Hp, N, kk, trans_a=True, lda=2 * Hp, ldb=2 * G, ldc=G,
-                     a_off=h_off + d * Hp + (0 if d == 0 else n_pad * 2 * Hp),
-                     b_off=d * G + (n_pad * 2 * G if d == 0 else 0), c_off=c_off,
-                     split_k=split, a_scale=scale, a_scale_period=n_pad, b_absmax=zmx)
-        else:
-            self._gview(c_off, Hp * G).view(Hp, G)[:, :N].zero_()
-
-    def _rnn_backward(self, s, si, rec, da, first, split):
-        """BPTT of a SimpleRNN stage (csrc/rnn.hip), then its weight gradients and dx from the
-        GEMMs: dU[d] = (h_prev (.) B_U)^T dz_d, dW[d] = (x (.) B_W)^T dz_d, db from BPTT's
-        per-batch-tile sums, dx = sum_d B_W[d] (.) (dz_d @ W_d^T).  Returns dx (or None)."""
-        T, n_pad = da.shape[0], da.shape[1]
-        rows, Hp = T * n_pad, s.Hp
-        BW, BU, h, a_in = rec['BW'], rec['BU'], rec['h'], rec['in']
-        dz = self._buf('rdz%d' % si, (T, n_pad, 2, Hp))
-        dbp = self._buf('rdbp%d' % si, (n_pad // 16, 2, Hp))
-        zmx = self._buf('rdzmax%d' % si, (1,))
-        rec['ws_b'] = ops.rnn_seq_bwd(da.contiguous(), self._view(s.oU, 2 * Hp * Hp), h, dz, T,
-                                      n_pad, Hp, act=s.act, mask_u=BU,
-                                      shared_dy=s.merge == 'sum', mode=self.lstm_mode,
-                                      db_part=dbp, dz_absmax=zmx)
-        ops.colsum(dbp, n_pad // 16, 2 * Hp, 2 * Hp, self._gview(s.ob, 2 * Hp))
-        for d in range(2):
-            self._rec_du_prev(h, dz, s.oU + d * Hp * Hp, d, Hp, Hp, T, n_pad, Hp,
-                              None if BU is None else BU[d], split, zmx)
-        self._rec_dw(a_in, dz, s, Hp, BW, rows, n_pad, split, zmx)
-        return self._rec_dx(dz, s, si, Hp, BW, T, n_pad, zmx, first)
-
     def _clip_bound(self, si):
         """1-element device tensor >= max|input of stage si| when that input is a clipped-ReLU
         convolution's output (0 <= y <= clip), seen through reshapes; else None (measure)."""
@@ -1189,18 +670,6 @@ class Model(object):
             t = self._bufs[key] = torch.full((1,), float(self.stages[j].clip),
                                               dtype=torch.float32, device=self.device)
         return t
-
-    def _conv_op(self, si, s, T, n_pad):
-        """The ops.Conv2d of stage si for this slab shape (owns the layer's workspace: the
-        packed planes of x and dz live there between the forward and backward calls)."""
-        key = (si, int(T), int(n_pad))
-        op = self._convs.get(key)
-        if op is None:
-            for k in [k for k in self._convs if k[0] == si]:
-                del self._convs[k]
-            op = self._convs[key] = ops.Conv2d(T, n_pad, s.F_in, s.C_in, s.C_out, s.kt, s.kf,
-                                               s.st, s.sf, s.clip, self.device)
-        return op
 
     def out_frames(self, T):
         """Frames of the logits for T input frames (ceil(T / st) per time-strided layer)."""
@@ -1353,13 +822,11 @@ class Model(object):
         B_U per level: (2, L, n_pad, H), all from that one stream."""
         out = {}
         for si, s in enumerate(self.stages):
-            if s.kind not in ('bilstm', 'birnn', 'bigru', 'birhn') \
-                    or not (s.dropout_W > 0 or s.dropout_U > 0):
+            mask_shape = KINDS[s.kind].mask_shape
+            if mask_shape is None or not (s.dropout_W > 0 or s.dropout_U > 0):
                 continue
             BW = self._buf('BW%d' % si, (2, n_pad, s.f_in_pad))
-            # (an RHN stage: one B_U per level, all from the one stream 4 * stage + 1)
-            BU = self._buf('BU%d' % si, (2, s.depth, n_pad, s.Hp) if s.kind == 'birhn'
-                           else (2, n_pad, s.Hp))
+            BU = self._buf('BU%d' % si, mask_shape(s, n_pad))
             for k, (t, p) in enumerate(((BW, s.dropout_W), (BU, s.dropout_U))):
                 if p > 0:
                     ops.dropout_masks(t, p, 1.0 / (1.0 - p), self.rng_seed, 4 * si + k, self._step)
@@ -1436,390 +903,299 @@ class Model(object):
         side_slots = int(os.environ.get('ASR_SIDE_SLOTS', '0'))
         split_side = ('auto:%d' % side_slots) if (compact_any and not self.overlap and side_slots) \
             else split
-        skip_grads = {}        # stage index -> gradient to add to that stage's OUTPUT
+        bp = Pass(T=T, n_pad=n_pad, rows=rows, n_ref=n_ref, split=split, split_side=split_side,
+                  overlap=overlap, reduce_now=reduce_now, pending=pending,
+                  skip_grads={},        # stage index -> gradient to add to that stage's OUTPUT
+                  flush_side=flush_side, reduce_async=reduce_async, first=False)
         for si in range(len(self.stages) - 1, -1, -1):
             s = self.stages[si]
-            rec = self._acts[si]
-            a_in = rec['in']
-            if si in skip_grads:            # the residual branch rejoins here
-                g = skip_grads.pop(si)
+            if si in bp.skip_grads:         # the residual branch rejoins here
+                g = bp.skip_grads.pop(si)
                 da = ops.axpby(1.0, da, 1.0, g, self._buf('dskip%d' % si, da.shape))
-            if s.kind == 'merge':
-                if s.coef != 1.0:
-                    da = ops.axpby(s.coef, da, 0.0, da, self._buf('dmerge%d' % si, da.shape))
-                skip_grads[s.skip] = da
-                if s.scale != 1.0:          # the branch gets scale * d, the skip d
-                    da = ops.axpby(s.scale, da, 0.0, da, self._buf('dscale%d' % si, da.shape))
-                continue
-            first = not any(st.kind in ('dense', 'bilstm', 'conv', 'birnn', 'bn', 'bigru', 'birhn',
-                                        'ln', 'mha', 'dwconv')
-                            for st in self.stages[:si])
-            if s.kind in ('noise', 'reshape', 'posenc', 'specaug'):  # (posenc: d(x + pe) / dx = 1)
-                continue
-            if s.kind == 'mha':
-                dx = self._mha_backward(s, si, rec, a_in.contiguous(), da, first, split)
-                if dx is not None:
-                    da = dx
-                continue
-            if s.kind == 'conv':
-                flush_side()
-                op, z = rec['op'], rec['z']
-                nw = s.kt * s.kf * s.C_in * s.C_out
-                da = da.contiguous()
-                dz_ready = False
-                if not first:
-                    dx = self._buf('da_s%d' % si, a_in.shape)
-                    op.dgrad(da, z, self._view(s.oW, nw), dx)
-                    dz_ready = True
-                # (x planes: still in the layer's workspace from the forward call)
-                op.wgrad(a_in, da, z, self._gview(s.oW, nw), self._gview(s.ob, s.C_out),
-                         reuse_x=True, reuse_dz=dz_ready)
-                if not first:
-                    da = dx
-                continue
-            if s.kind == 'act':
-                if not first and not getattr(s, 'fused', False):
-                    # (swish: its derivative is read from the stage INPUT)
-                    da = ops.activation_bwd(da.contiguous(), rec['out'],
-                                            self._buf('dact%d' % si, da.shape), s.act,
-                                            x=a_in.contiguous() if s.act == 'swish' else None)
-                continue
-            if s.kind == 'glu':
-                if not first:
-                    da = ops.glu_bwd(a_in, da.contiguous(), self._buf('dglu%d' % si, a_in.shape))
-                continue
-            if s.kind == 'dwconv':
-                # dW / db into the gradients, dx behind the same length mask
-                dx = None if first else self._buf('ddwconv%d' % si, a_in.shape)
-                ops.dwconv1d_bwd(a_in, self._view(s.oW, s.k * s.C), da.contiguous(), dx,
-                                 self._gview(s.oW, s.k * s.C),
-                                 self._buf('dwdb%d' % si, (s.C,)) if s.bias_dead
-                                 else self._gview(s.ob, s.C), rec['N'], s.k, lens=rec['lens'])
-                if dx is not None:
-                    da = dx
-                continue
-            if s.kind == 'bn':
-                # dgamma / dbeta into the gradients, dx from the saved statistics (x re-read)
-                dx = None if first else self._buf('dbn%d' % si, a_in.shape)
-                ops.bn_bwd(a_in.contiguous(), da.contiguous(), self._view(s.og, s.C),
-                           self._view(s.obeta, s.C), rec['stats'], dx, self._gview(s.og, s.C),
-                           self._gview(s.obeta, s.C), rec['N'], a_in.shape[2], s.C, s.clip)
-                if dx is not None:
-                    da = dx
-                continue
-            if s.kind == 'ln':
-                # dgain / dbias into the gradients, dx from the saved (mu, 1 / sigma) (x re-read)
-                ld = a_in.shape[2]
-                dx = None if first else self._buf('dln%d' % si, a_in.shape)
-                ops.ln_bwd(a_in.contiguous(), da.contiguous(), self._view(s.og, ld), rec['stats'],
-                           dx, self._gview(s.og, ld), self._gview(s.obeta, ld), rec['N'],
-                           s.seg_H, s.seg_Hp, s.segs)
-                if dx is not None:
-                    da = dx
-                continue
-            if s.kind == 'birnn':
-                dx = self._rnn_backward(s, si, rec, da, first, split)
-                if dx is not None:
-                    da = dx
-                continue
-            if s.kind == 'bigru':
-                dx = self._gru_backward(s, si, rec, da, first, split)
-                if dx is not None:
-                    da = dx
-                continue
-            if s.kind == 'birhn':
-                dx = self._rhn_backward(s, si, rec, da, first, split)
-                if dx is not None:
-                    da = dx
-                continue
-            if s.kind == 'dropout':
-                if first:               # nothing trainable upstream: no gradient needed there
-                    continue
-                if 'mask' in rec:
-                    da = ops.mul(da, rec['mask'], self._buf('ddrop%d' % si, da.shape))
-                continue
-            if s.kind == 'dense':
-                gmx = ops.absmax(da, self._buf('damax%d' % si, (1,)))
-                ops.gemm(a_in, da, self.grads, s.f_in_pad, s.n_out, rows, trans_a=True,
-                         c_off=s.oW, split_k=split, b_absmax=gmx)
-                ops.colsum(da, rows, s.n_out, s.n_out, self._gview(s.ob, s.n_out))
-                if not first:
-                    dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-                    ops.gemm(da, self.params, dx, rows, s.f_in_pad, s.n_out, trans_b=True,
-                             b_off=s.oW, a_absmax=gmx)
-                    da = dx
-            elif s.kind == 'bilstm':
-                Hp = s.Hp
-                BW, BU = rec['BW'], rec['BU']
-                # two dz buffers alternate so that the side stream may still read layer
-                # l's dz while layer l-1's BPTT writes the other one
-                par = self._dz_parity = 1 - getattr(self, '_dz_parity', 0)
-                dz = self._buf('dz%d' % par, (T, n_pad, 2, 4 * Hp))
-                main = torch.cuda.current_stream(self.device)
-                if overlap and self._dz_free[par] is not None:
-                    main.wait_event(self._dz_free[par])
-                U = self._view(s.oU, 2 * Hp * 4 * Hp)
-                zmx = self._buf('dzmax%d' % par, (1,))
-                var = dict(rec.get('var') or {})
-                gsrc = dz                  # slab the dW / dX GEMMs read
-                pgrad = None               # (per-row parameter-gradient sums, rows, cols, offset)
-                if s.ln is not None:
-                    gsrc = self._buf('dwx%d' % par, (T, n_pad, 2, 4 * Hp))
-                    dpar = self._buf('dcellp%d' % si, (n_pad, 2, 34 * Hp))
-                    pgrad = (dpar, n_pad, 68 * Hp, s.ocell)
-                elif s.mi is not None:
-                    gsrc = self._buf('dwx%d' % par, (T, n_pad, 2, 4 * Hp))
-                    dmi = self._buf('dmi%d' % si, (n_pad // 16, 2, 4, 4 * Hp))
-                    var.update(wx=rec['zx'], dwx=gsrc, dmi=dmi)
-                    pgrad = (dmi, n_pad // 16, 32 * Hp, s.omi)
-                else:
-                    # plain cell: BPTT leaves the bias gradient as per-batch-tile sums of dz
-                    # (accumulated in registers over the steps), so nothing re-reads the dz
-                    # slab for it; the tiles are added up on the side stream
-                    dbp = self._buf('dbpart%d' % si, (n_pad // 16, 2, 4 * Hp))
-                    pgrad = (dbp, n_pad // 16, 8 * Hp, s.ob)
-                planes_now, pdz_r = False, None
-                pipe_b = (getattr(self, '_pipe_now', False) and self._pipe is not None
-                          and not first and self.lstm_mode == 0 and T >= 16 and not var
-                          and s.ln is None)
-                S = (self._pipe_split16 * T) // 16
-                dx = None
-                if pipe_b:
-                    # after S BPTT steps the gate gradients of frames [T-S, S) are final
-                    # in both directions: their dX GEMMs overlap the last steps
-                    dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-                    ops.lstm_seq_bwd(da, U, rec['cell'], rec['gates'], dz, T, n_pad, Hp,
-                                     mask_u=BU, mode=self.lstm_mode, dz_absmax=zmx, steps=(0, S),
-                                     db_part=pgrad[0])
-                    ev = torch.cuda.Event()
-                    ev.record(main)
-                    flush_side()    # previous layer's dW/dU/db now overlap this BPTT
-                    with torch.cuda.stream(self._pipe):
-                        self._pipe.wait_event(ev)
-                        self._dx_gemm(dz, s, dx, BW, (T - S) * n_pad, S * n_pad, n_pad, zmx)
-                        if self._pipe_halves:
-                            # the forward direction's BPTT (frames T-1 .. 0) has also finished
-                            # [S, T), the backward direction's [0, T-S): their terms of dx
-                            self._dx_gemm_dir(dz, s, dx, BW, S * n_pad, rows, n_pad, zmx, 0, 0.0)
-                            self._dx_gemm_dir(dz, s, dx, BW, 0, (T - S) * n_pad, n_pad, zmx, 1,
-                                              0.0)
-                        dx_inner = torch.cuda.Event()
-                        dx_inner.record(self._pipe)
-                    rec['ws_b'] = ops.lstm_seq_bwd(da, U, rec['cell'], rec['gates'], dz, T, n_pad,
-                                                   Hp, mask_u=BU, mode=self.lstm_mode,
-                                                   dz_absmax=zmx, steps=(S, T - S),
-                                                   db_part=pgrad[0])
-                elif s.ln is not None:
-                    ops.lstm_ln_seq_bwd(da, rec['zx'], U, self._view(s.ocell, 68 * Hp), rec['uh'],
-                                        rec['y'], rec['cell'], rec['gates'], dz, gsrc, pgrad[0], T,
-                                        n_pad, Hp, has_mi=s.mi is not None, mask_u=BU,
-                                        zone_c=var.get('zone_c'), zone_h=var.get('zone_h'),
-                                        act=s.act)
-                    # one pre-scale for the gradient GEMMs: max over both gradient slabs
-                    ops.absmax(dz, zmx)
-                    tmp = ops.absmax(gsrc, self._buf('dzmax_t', (1,)))
-                    torch.maximum(zmx, tmp, out=zmx)
-                    flush_side()
-                else:
-                    if s.mi is None:
-                        var['db_part'] = pgrad[0]
-                    # compact geometry only while there is work to run beside it (the top
-                    # layer's BPTT has none: it keeps the whole chip and the shorter step)
-                    cmp_now = bool(pending) and not self.overlap and self._bptt_compact(s, n_ref)
-                    self._compact_launches += int(cmp_now)
-                    # BPTT writes dz as packed planes itself where its kernel can (the plain cell
-                    # at H = 256 / 512 on the two-dimensional-split kernels): the pack pass over
-                    # the fp32 slab (2.1 GB per layer at cfg3) disappears.  The planes' scale has
-                    # to be known before the pass: a per-layer bound kept at ~64 x the measured
-                    # max|dz| by asr_lstm_dz_guard (hysteresis: identical inputs see identical
-                    # scales); a layer without a bound yet -- first step, after a fault or new
-                    # weights -- runs one MEASURING pass first (fp32 slab, discarded).
-                    plain = not any(var.get(k) is not None
-                                    for k in ('act', 'zone_c', 'zone_h', 'mi', 'uh'))
-                    planes_now = (self._dz_planes_mode and self._stage_packed(s) and plain
-                                  and self.lstm_mode == 0
-                                  and ops.lstm_dz_hl_supported(T, n_pad, Hp, compact=cmp_now))
-                    if planes_now:
-                        pdz_r = self._planes('dzr%d' % par, rows, 8 * Hp)
-                        bound = self._buf('dzbound%d' % si, (1,))
-                        key = (self._fault_gen, self._weights_epoch)
-                        if self._dz_bound_key.get(si) != key:
-                            bound.zero_()
-                            ops.lstm_seq_bwd(da, U, rec['cell'], rec['gates'], dz, T, n_pad, Hp,
-                                             mask_u=BU, mode=self.lstm_mode, dz_absmax=zmx,
-                                             compact=cmp_now, **var)
-                            ops.lstm_dz_guard(zmx, bound, False)
-                            self._dz_bound_key[si] = key
-                            self._dz_measure_passes += 1
-                        rec['ws_b'] = ops.lstm_seq_bwd(
-                            da, U, rec['cell'], rec['gates'], None, T, n_pad, Hp, mask_u=BU,
-                            mode=self.lstm_mode, dz_absmax=zmx, compact=cmp_now,
-                            dz_planes=pdz_r, dz_bound=bound, **var)
-                        ops.lstm_dz_guard(zmx, bound, True)
-                    else:
-                        rec['ws_b'] = ops.lstm_seq_bwd(
-                            da, U, rec['cell'], rec['gates'], dz, T, n_pad, Hp, mask_u=BU,
-                            mode=self.lstm_mode, dz_absmax=zmx, compact=cmp_now, **var)
-                    flush_side()    # previous layer's dW/dU/db now overlap this BPTT
-                y = rec['y']
-                hl = self._stage_packed(s)
-                if hl and not planes_now:
-                    # dz -> (rows, 8H) planes, once: dX reduces over their gate columns, the
-                    # weight gradients over their rows (k_major); the scale is the BPTT kernel's
-                    # own max|dz|
-                    pdz_r = self._planes('dzr%d' % par, rows, 8 * Hp)
-                    ops.pack_hl(dz, rows, 8 * Hp, absmax=zmx, r=pdz_r)
-                # bound of |y| for its planes (dU): 1 behind a bounded activation, else measured
-                # (here, on the main stream, before the side stream's packs read it)
-                ymx = self._const_one() if (not hl or self._y_bounded(s)) \
-                    else ops.absmax(y, self._buf('yamax%d' % si, (1,)))
-
-                def grads_U_hl(wsn, s=s, y=y, BU=BU, Hp=Hp, pdz_r=pdz_r, ymx=ymx):
-                    # dU[d] = (h_prev (.) B_U)^T dz[d], reduced over the plane rows; h_prev = y
-                    # one frame earlier in the direction's processing order = a row offset
-                    kk = (T - 1) * n_pad
-                    for d in range(2):
-                        if kk <= 0:
-                            self._gview(s.oU + d * Hp * 4 * Hp, Hp * 4 * Hp).zero_()
-                            continue
-                        # (one pair of buffers per stream: the bottom layer's gradients run on
-                        # the main stream while the side stream may still read its own pair)
-                        yu = self._planes('yu%d%s' % (d, '' if wsn == 'gemm_side' else '_m'),
-                                          rows, Hp)
-                        ops.pack_hl(y, rows, Hp, ld=2 * Hp, src_off=d * Hp,
-                                    mask=None if BU is None else BU[d], mask_period=n_pad,
-                                    absmax=ymx, r=yu)
-                        ops.gemm_hl(yu, pdz_r, self.grads, Hp, 4 * Hp, kk,
-                                    a_row=0 if d == 0 else n_pad, b_k=d * 4 * Hp,
-                                    b_row=n_pad if d == 0 else 0, c_off=s.oU + d * Hp * 4 * Hp,
-                                    split_k=split_side if wsn == 'gemm_side' else split,
-                                    ws_name=wsn, k_major=True)
-
-                def grads_W_hl(wsn, s=s, pa=rec.get('pa'), Hp=Hp, pdz_r=pdz_r, pgrad=pgrad):
-                    sp = split_side if wsn == 'gemm_side' else split
-                    if len(pa) == 1:
-                        ops.gemm_hl(pa[0], pdz_r, self.grads, s.f_in_pad, 8 * Hp, rows,
-                                    c_off=s.oW, split_k=sp, ws_name=wsn, k_major=True)
-                    else:
-                        for d in range(2):
-                            ops.gemm_hl(pa[d], pdz_r, self.grads, s.f_in_pad, 4 * Hp, rows,
-                                        b_k=d * 4 * Hp, c_off=s.oW + d * 4 * Hp, ldc=8 * Hp,
-                                        split_k=sp, ws_name=wsn, k_major=True)
-                    buf, nrow, ncol, goff = pgrad
-                    ops.colsum(buf, nrow, ncol, ncol, self._gview(goff, ncol), ws_name=wsn + '_cs')
-
-                def grads_U(wsn, s=s, dz=dz, y=y, BU=BU, Hp=Hp, zmx=zmx):
-                    # dU[d] = (h_prev (.) B_U)^T dz[d]: h_prev is y shifted by one step in
-                    # the direction's processing order (zero at its first step)
-                    kk = (T - 1) * n_pad
-                    for d in range(2):
-                        a_off = d * Hp + (0 if d == 0 else n_pad * 2 * Hp)
-                        b_off = d * 4 * Hp + (n_pad * 8 * Hp if d == 0 else 0)
-                        if kk > 0:
-                            ops.gemm(y, dz, self.grads, Hp, 4 * Hp, kk, trans_a=True, lda=2 * Hp,
-                                     ldb=8 * Hp, ldc=4 * Hp, a_off=a_off, b_off=b_off,
-                                     c_off=s.oU + d * Hp * 4 * Hp, split_k=split,
-                                     a_scale=None if BU is None else BU[d],
-                                     a_scale_period=n_pad, ws_name=wsn, b_absmax=zmx)
-                        else:
-                            self._gview(s.oU + d * Hp * 4 * Hp, Hp * 4 * Hp).zero_()
-
-                def grads_W(wsn, s=s, dz=gsrc, a_in=a_in, BW=BW, Hp=Hp, zmx=zmx, pgrad=pgrad):
-                    # dW = (x (.) B_W)^T d(x@W); the bias (or MI / LN parameter) gradients come
-                    # from BPTT's per-tile partial sums, never from a pass over the dz slab
-                    if BW is None:
-                        ops.gate_gemm('wgrad', rows, n_pad, s.f_in_pad, 8 * Hp, self.params, s.oW,
-                                      8 * Hp, 8 * Hp, x=a_in, dz=dz, dz_absmax=zmx,
-                                      dW=self.grads, dw_off=s.oW, split_k=split, ws_name=wsn)
-                    else:
-                        for d in range(2):
-                            ops.gate_gemm('wgrad', rows, n_pad, s.f_in_pad, 4 * Hp, self.params,
-                                          s.oW + d * 4 * Hp, 8 * Hp, 8 * Hp, x=a_in,
-                                          mask_w=BW[d], dz=dz, z_off=d * 4 * Hp, dz_absmax=zmx,
-                                          dW=self.grads, dw_off=s.oW + d * 4 * Hp, split_k=split,
-                                          ws_name=wsn)
-                    buf, nrow, ncol, goff = pgrad
-                    ops.colsum(buf, nrow, ncol, ncol, self._gview(goff, ncol), ws_name=wsn + '_cs')
-
-                if hl:
-                    grads_U, grads_W = grads_U_hl, grads_W_hl
-
-                def weight_grads(wsn, gu=grads_U, gw=grads_W):
-                    gu(wsn)
-                    gw(wsn)
-
-                if pipe_b and self._pipe_halves:
-                    main.wait_event(dx_inner)
-                    # (r6: two independent row ranges, one launch-bound GEMM each: two streams)
-                    if os.environ.get('ASR_PIPE_TAIL_FORK', '1') != '0':
-                        ev0 = torch.cuda.Event()
-                        ev0.record(main)
-                        with torch.cuda.stream(self._pipe):
-                            self._pipe.wait_event(ev0)
-                            self._dx_gemm_dir(dz, s, dx, BW, 0, (T - S) * n_pad, n_pad, zmx, 0, 1.0)
-                            ev1 = torch.cuda.Event()
-                            ev1.record(self._pipe)
-                        self._dx_gemm_dir(dz, s, dx, BW, S * n_pad, rows, n_pad, zmx, 1, 1.0)
-                        main.wait_event(ev1)
-                    else:
-                        self._dx_gemm_dir(dz, s, dx, BW, S * n_pad, rows, n_pad, zmx, 1, 1.0)
-                        self._dx_gemm_dir(dz, s, dx, BW, 0, (T - S) * n_pad, n_pad, zmx, 0, 1.0)
-                    da = dx
-                elif pipe_b:
-                    self._dx_gemm(dz, s, dx, BW, 0, (T - S) * n_pad, n_pad, zmx)
-                    self._dx_gemm(dz, s, dx, BW, S * n_pad, rows, n_pad, zmx)
-                    main.wait_event(dx_inner)
-                    da = dx
-                elif not first and hl:
-                    dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-                    Wn = self._planes('Wn%d' % si, s.f_in_pad, 8 * Hp)
-                    if BW is None:
-                        ops.gemm_hl(pdz_r, Wn, dx, rows, s.f_in_pad, 8 * Hp)
-                    else:       # dx = sum_d B_W[d] (.) (dz_d @ W_d^T)
-                        for d in range(2):
-                            ops.gemm_hl(pdz_r, Wn, dx, rows, s.f_in_pad, 4 * Hp, a_k=d * 4 * Hp,
-                                        b_k=d * 4 * Hp, c_scale=BW[d], c_scale_period=n_pad,
-                                        beta=0.0 if d == 0 else 1.0)
-                    da = dx
-                elif not first:
-                    dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-                    self._dx_gemm(gsrc, s, dx, BW, 0, rows, n_pad, zmx)
-                    da = dx
-                # (compact schedule: is there a BiLSTM stage below whose BPTT this layer's
-                # weight gradients could run beside?  A convolution / Dense / nothing below:
-                # chip-filling GEMMs either way -- one stream, as in the serial schedule)
-                below = any(st.kind == 'bilstm' for st in self.stages[:si])
-                if not overlap:
-                    weight_grads('gemm')
-                    if reduce_now and not first:
-                        # no side stream (a recurrence fills the chip): this layer's gradients
-                        # are final on the main stream; their all-reduce runs beside the layers
-                        # below instead of after them all
-                        reduce_async(s.p_lo, s.p_hi, main)
-                elif (first or not below) and not self.overlap:
-                    # (compact schedule: the tail's GEMMs each fill the chip -- one stream)
-                    weight_grads('gemm')
-                    if reduce_now and not first:
-                        reduce_async(s.p_lo, s.p_hi, main)
-                    if not first:
-                        da = dx
-                elif first:
-                    # nothing left to hide behind: share the tail between both streams
-                    ready = torch.cuda.Event()
-                    ready.record(main)
-                    pending.append((grads_U, ready, par, None))
-                    flush_side()
-                    grads_W('gemm')
-                else:
-                    # the side stream starts once the dX GEMMs (critical path) are done,
-                    # i.e. together with the next layer's BPTT kernel
-                    ready = torch.cuda.Event()
-                    ready.record(main)
-                    pending.append((weight_grads, ready, par, (s.p_lo, s.p_hi)))
-                    da = dx
+            bp.first = s.first
+            dx = KINDS[s.kind].backward(self, s, si, self._acts[si], da, bp)
+            da = dx if dx is not None else da
         flush_side()
         if overlap and self._side is not None:
             torch.cuda.current_stream(self.device).wait_stream(self._side)
+        return da
+
+    def _bilstm_backward(self, s, si, rec, da, bp):
+        """The BiLSTM entry of the stage table (core/stages.py): BPTT, the dX GEMMs on the
+        critical path, and the weight-gradient GEMMs -- run here, or deferred in bp.pending to
+        run on the side stream beside the BPTT of the layer below (bp.flush_side())."""
+        T, n_pad, rows, n_ref, first = bp.T, bp.n_pad, bp.rows, bp.n_ref, bp.first
+        split, split_side, overlap, reduce_now = bp.split, bp.split_side, bp.overlap, bp.reduce_now
+        pending, flush_side, reduce_async = bp.pending, bp.flush_side, bp.reduce_async
+        a_in = rec['in']
+        Hp = s.Hp
+        BW, BU = rec['BW'], rec['BU']
+        # two dz buffers alternate so that the side stream may still read layer
+        # l's dz while layer l-1's BPTT writes the other one
+        par = self._dz_parity = 1 - getattr(self, '_dz_parity', 0)
+        dz = self._buf('dz%d' % par, (T, n_pad, 2, 4 * Hp))
+        main = torch.cuda.current_stream(self.device)
+        if overlap and self._dz_free[par] is not None:
+            main.wait_event(self._dz_free[par])
+        U = self._view(s.oU, 2 * Hp * 4 * Hp)
+        zmx = self._buf('dzmax%d' % par, (1,))
+        var = dict(rec.get('var') or {})
+        gsrc = dz                  # slab the dW / dX GEMMs read
+        pgrad = None               # (per-row parameter-gradient sums, rows, cols, offset)
+        if s.ln is not None:
+            gsrc = self._buf('dwx%d' % par, (T, n_pad, 2, 4 * Hp))
+            dpar = self._buf('dcellp%d' % si, (n_pad, 2, 34 * Hp))
+            pgrad = (dpar, n_pad, 68 * Hp, s.ocell)
+        elif s.mi is not None:
+            gsrc = self._buf('dwx%d' % par, (T, n_pad, 2, 4 * Hp))
+            dmi = self._buf('dmi%d' % si, (n_pad // 16, 2, 4, 4 * Hp))
+            var.update(wx=rec['zx'], dwx=gsrc, dmi=dmi)
+            pgrad = (dmi, n_pad // 16, 32 * Hp, s.omi)
+        else:
+            # plain cell: BPTT leaves the bias gradient as per-batch-tile sums of dz
+            # (accumulated in registers over the steps), so nothing re-reads the dz
+            # slab for it; the tiles are added up on the side stream
+            dbp = self._buf('dbpart%d' % si, (n_pad // 16, 2, 4 * Hp))
+            pgrad = (dbp, n_pad // 16, 8 * Hp, s.ob)
+        planes_now, pdz_r = False, None
+        pipe_b = (getattr(self, '_pipe_now', False) and self._pipe is not None
+                  and not first and self.lstm_mode == 0 and T >= 16 and not var
+                  and s.ln is None)
+        S = (self._pipe_split16 * T) // 16
+        dx = None
+        if pipe_b:
+            # after S BPTT steps the gate gradients of frames [T-S, S) are final
+            # in both directions: their dX GEMMs overlap the last steps
+            dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
+            ops.lstm_seq_bwd(da, U, rec['cell'], rec['gates'], dz, T, n_pad, Hp,
+                             mask_u=BU, mode=self.lstm_mode, dz_absmax=zmx, steps=(0, S),
+                             db_part=pgrad[0])
+            ev = torch.cuda.Event()
+            ev.record(main)
+            flush_side()    # previous layer's dW/dU/db now overlap this BPTT
+            with torch.cuda.stream(self._pipe):
+                self._pipe.wait_event(ev)
+                self._dx_gemm(dz, s, dx, BW, (T - S) * n_pad, S * n_pad, n_pad, zmx)
+                if self._pipe_halves:
+                    # the forward direction's BPTT (frames T-1 .. 0) has also finished
+                    # [S, T), the backward direction's [0, T-S): their terms of dx
+                    self._dx_gemm_dir(dz, s, dx, BW, S * n_pad, rows, n_pad, zmx, 0, 0.0)
+                    self._dx_gemm_dir(dz, s, dx, BW, 0, (T - S) * n_pad, n_pad, zmx, 1,
+                                      0.0)
+                dx_inner = torch.cuda.Event()
+                dx_inner.record(self._pipe)
+            rec['ws_b'] = ops.lstm_seq_bwd(da, U, rec['cell'], rec['gates'], dz, T, n_pad,
+                                           Hp, mask_u=BU, mode=self.lstm_mode,
+                                           dz_absmax=zmx, steps=(S, T - S),
+                                           db_part=pgrad[0])
+        elif s.ln is not None:
+            ops.lstm_ln_seq_bwd(da, rec['zx'], U, self._view(s.ocell, 68 * Hp), rec['uh'],
+                                rec['y'], rec['cell'], rec['gates'], dz, gsrc, pgrad[0], T,
+                                n_pad, Hp, has_mi=s.mi is not None, mask_u=BU,
+                                zone_c=var.get('zone_c'), zone_h=var.get('zone_h'),
+                                act=s.act)
+            # one pre-scale for the gradient GEMMs: max over both gradient slabs
+            ops.absmax(dz, zmx)
+            tmp = ops.absmax(gsrc, self._buf('dzmax_t', (1,)))
+            torch.maximum(zmx, tmp, out=zmx)
+            flush_side()
+        else:
+            if s.mi is None:
+                var['db_part'] = pgrad[0]
+            # compact geometry only while there is work to run beside it (the top
+            # layer's BPTT has none: it keeps the whole chip and the shorter step)
+            cmp_now = bool(pending) and not self.overlap and self._bptt_compact(s, n_ref)
+            self._compact_launches += int(cmp_now)
+            # BPTT writes dz as packed planes itself where its kernel can (the plain cell
+            # at H = 256 / 512 on the two-dimensional-split kernels): the pack pass over
+            # the fp32 slab (2.1 GB per layer at cfg3) disappears.  The planes' scale has
+            # to be known before the pass: a per-layer bound kept at ~64 x the measured
+            # max|dz| by asr_lstm_dz_guard (hysteresis: identical inputs see identical
+            # scales); a layer without a bound yet -- first step, after a fault or new
+            # weights -- runs one MEASURING pass first (fp32 slab, discarded).
+            plain = not any(var.get(k) is not None
+                            for k in ('act', 'zone_c', 'zone_h', 'mi', 'uh'))
+            planes_now = (self._dz_planes_mode and self._stage_packed(s) and plain
+                          and self.lstm_mode == 0
+                          and ops.lstm_dz_hl_supported(T, n_pad, Hp, compact=cmp_now))
+            if planes_now:
+                pdz_r = self._planes('dzr%d' % par, rows, 8 * Hp)
+                bound = self._buf('dzbound%d' % si, (1,))
+                key = (self._fault_gen, self._weights_epoch)
+                if self._dz_bound_key.get(si) != key:
+                    bound.zero_()
+                    ops.lstm_seq_bwd(da, U, rec['cell'], rec['gates'], dz, T, n_pad, Hp,
+                                     mask_u=BU, mode=self.lstm_mode, dz_absmax=zmx,
+                                     compact=cmp_now, **var)
+                    ops.lstm_dz_guard(zmx, bound, False)
+                    self._dz_bound_key[si] = key
+                    self._dz_measure_passes += 1
+                rec['ws_b'] = ops.lstm_seq_bwd(
+                    da, U, rec['cell'], rec['gates'], None, T, n_pad, Hp, mask_u=BU,
+                    mode=self.lstm_mode, dz_absmax=zmx, compact=cmp_now,
+                    dz_planes=pdz_r, dz_bound=bound, **var)
+                ops.lstm_dz_guard(zmx, bound, True)
+            else:
+                rec['ws_b'] = ops.lstm_seq_bwd(
+                    da, U, rec['cell'], rec['gates'], dz, T, n_pad, Hp, mask_u=BU,
+                    mode=self.lstm_mode, dz_absmax=zmx, compact=cmp_now, **var)
+            flush_side()    # previous layer's dW/dU/db now overlap this BPTT
+        y = rec['y']
+        hl = self._stage_packed(s)
+        if hl and not planes_now:
+            # dz -> (rows, 8H) planes, once: dX reduces over their gate columns, the
+            # weight gradients over their rows (k_major); the scale is the BPTT kernel's
+            # own max|dz|
+            pdz_r = self._planes('dzr%d' % par, rows, 8 * Hp)
+            ops.pack_hl(dz, rows, 8 * Hp, absmax=zmx, r=pdz_r)
+        # bound of |y| for its planes (dU): 1 behind a bounded activation, else measured
+        # (here, on the main stream, before the side stream's packs read it)
+        ymx = self._const_one() if (not hl or self._y_bounded(s)) \
+            else ops.absmax(y, self._buf('yamax%d' % si, (1,)))
+
+        def grads_U_hl(wsn, s=s, y=y, BU=BU, Hp=Hp, pdz_r=pdz_r, ymx=ymx):
+            # dU[d] = (h_prev (.) B_U)^T dz[d], reduced over the plane rows; h_prev = y
+            # one frame earlier in the direction's processing order = a row offset
+            kk = (T - 1) * n_pad
+            for d in range(2):
+                if kk <= 0:
+                    self._gview(s.oU + d * Hp * 4 * Hp, Hp * 4 * Hp).zero_()
+                    continue
+                # (one pair of buffers per stream: the bottom layer's gradients run on
+                # the main stream while the side stream may still read its own pair)
+                yu = self._planes('yu%d%s' % (d, '' if wsn == 'gemm_side' else '_m'),
+                                  rows, Hp)
+                ops.pack_hl(y, rows, Hp, ld=2 * Hp, src_off=d * Hp,
+                            mask=None if BU is None else BU[d], mask_period=n_pad,
+                            absmax=ymx, r=yu)
+                ops.gemm_hl(yu, pdz_r, self.grads, Hp, 4 * Hp, kk,
+                            a_row=0 if d == 0 else n_pad, b_k=d * 4 * Hp,
+                            b_row=n_pad if d == 0 else 0, c_off=s.oU + d * Hp * 4 * Hp,
+                            split_k=split_side if wsn == 'gemm_side' else split,
+                            ws_name=wsn, k_major=True)
+
+        def grads_W_hl(wsn, s=s, pa=rec.get('pa'), Hp=Hp, pdz_r=pdz_r, pgrad=pgrad):
+            sp = split_side if wsn == 'gemm_side' else split
+            if len(pa) == 1:
+                ops.gemm_hl(pa[0], pdz_r, self.grads, s.f_in_pad, 8 * Hp, rows,
+                            c_off=s.oW, split_k=sp, ws_name=wsn, k_major=True)
+            else:
+                for d in range(2):
+                    ops.gemm_hl(pa[d], pdz_r, self.grads, s.f_in_pad, 4 * Hp, rows,
+                                b_k=d * 4 * Hp, c_off=s.oW + d * 4 * Hp, ldc=8 * Hp,
+                                split_k=sp, ws_name=wsn, k_major=True)
+            buf, nrow, ncol, goff = pgrad
+            ops.colsum(buf, nrow, ncol, ncol, self._gview(goff, ncol), ws_name=wsn + '_cs')
+
+        def grads_U(wsn, s=s, dz=dz, y=y, BU=BU, Hp=Hp, zmx=zmx):
+            # dU[d] = (h_prev (.) B_U)^T dz[d]: h_prev is y shifted by one step in
+            # the direction's processing order (zero at its first step)
+            kk = (T - 1) * n_pad
+            for d in range(2):
+                a_off = d * Hp + (0 if d == 0 else n_pad * 2 * Hp)
+                b_off = d * 4 * Hp + (n_pad * 8 * Hp if d == 0 else 0)
+                if kk > 0:
+                    ops.gemm(y, dz, self.grads, Hp, 4 * Hp, kk, trans_a=True, lda=2 * Hp,
+                             ldb=8 * Hp, ldc=4 * Hp, a_off=a_off, b_off=b_off,
+                             c_off=s.oU + d * Hp * 4 * Hp, split_k=split,
+                             a_scale=None if BU is None else BU[d],
+                             a_scale_period=n_pad, ws_name=wsn, b_absmax=zmx)
+                else:
+                    self._gview(s.oU + d * Hp * 4 * Hp, Hp * 4 * Hp).zero_()
+
+        def grads_W(wsn, s=s, dz=gsrc, a_in=a_in, BW=BW, Hp=Hp, zmx=zmx, pgrad=pgrad):
+            # dW = (x (.) B_W)^T d(x@W); the bias (or MI / LN parameter) gradients come
+            # from BPTT's per-tile partial sums, never from a pass over the dz slab
+            if BW is None:
+                ops.gate_gemm('wgrad', rows, n_pad, s.f_in_pad, 8 * Hp, self.params, s.oW,
+                              8 * Hp, 8 * Hp, x=a_in, dz=dz, dz_absmax=zmx,
+                              dW=self.grads, dw_off=s.oW, split_k=split, ws_name=wsn)
+            else:
+                for d in range(2):
+                    ops.gate_gemm('wgrad', rows, n_pad, s.f_in_pad, 4 * Hp, self.params,
+                                  s.oW + d * 4 * Hp, 8 * Hp, 8 * Hp, x=a_in,
+                                  mask_w=BW[d], dz=dz, z_off=d * 4 * Hp, dz_absmax=zmx,
+                                  dW=self.grads, dw_off=s.oW + d * 4 * Hp, split_k=split,
+                                  ws_name=wsn)
+            buf, nrow, ncol, goff = pgrad
+            ops.colsum(buf, nrow, ncol, ncol, self._gview(goff, ncol), ws_name=wsn + '_cs')
+
+        if hl:
+            grads_U, grads_W = grads_U_hl, grads_W_hl
+
+        def weight_grads(wsn, gu=grads_U, gw=grads_W):
+            gu(wsn)
+            gw(wsn)
+
+        if pipe_b and self._pipe_halves:
+            main.wait_event(dx_inner)
+            # (r6: two independent row ranges, one launch-bound GEMM each: two streams)
+            if os.environ.get('ASR_PIPE_TAIL_FORK', '1') != '0':
+                ev0 = torch.cuda.Event()
+                ev0.record(main)
+                with torch.cuda.stream(self._pipe):
+                    self._pipe.wait_event(ev0)
+                    self._dx_gemm_dir(dz, s, dx, BW, 0, (T - S) * n_pad, n_pad, zmx, 0, 1.0)
+                    ev1 = torch.cuda.Event()
+                    ev1.record(self._pipe)
+                self._dx_gemm_dir(dz, s, dx, BW, S * n_pad, rows, n_pad, zmx, 1, 1.0)
+                main.wait_event(ev1)
+            else:
+                self._dx_gemm_dir(dz, s, dx, BW, S * n_pad, rows, n_pad, zmx, 1, 1.0)
+                self._dx_gemm_dir(dz, s, dx, BW, 0, (T - S) * n_pad, n_pad, zmx, 0, 1.0)
+            da = dx
+        elif pipe_b:
+            self._dx_gemm(dz, s, dx, BW, 0, (T - S) * n_pad, n_pad, zmx)
+            self._dx_gemm(dz, s, dx, BW, S * n_pad, rows, n_pad, zmx)
+            main.wait_event(dx_inner)
+            da = dx
+        elif not first and hl:
+            dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
+            Wn = self._planes('Wn%d' % si, s.f_in_pad, 8 * Hp)
+            if BW is None:
+                ops.gemm_hl(pdz_r, Wn, dx, rows, s.f_in_pad, 8 * Hp)
+            else:       # dx = sum_d B_W[d] (.) (dz_d @ W_d^T)
+                for d in range(2):
+                    ops.gemm_hl(pdz_r, Wn, dx, rows, s.f_in_pad, 4 * Hp, a_k=d * 4 * Hp,
+                                b_k=d * 4 * Hp, c_scale=BW[d], c_scale_period=n_pad,
+                                beta=0.0 if d == 0 else 1.0)
+            da = dx
+        elif not first:
+            dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
+            self._dx_gemm(gsrc, s, dx, BW, 0, rows, n_pad, zmx)
+            da = dx
+        # (compact schedule: is there a BiLSTM stage below whose BPTT this layer's
+        # weight gradients could run beside?  A convolution / Dense / nothing below:
+        # chip-filling GEMMs either way -- one stream, as in the serial schedule)
+        below = any(st.kind == 'bilstm' for st in self.stages[:si])
+        if not overlap:
+            weight_grads('gemm')
+            if reduce_now and not first:
+                # no side stream (a recurrence fills the chip): this layer's gradients
+                # are final on the main stream; their all-reduce runs beside the layers
+                # below instead of after them all
+                reduce_async(s.p_lo, s.p_hi, main)
+        elif (first or not below) and not self.overlap:
+            # (compact schedule: the tail's GEMMs each fill the chip -- one stream)
+            weight_grads('gemm')
+            if reduce_now and not first:
+                reduce_async(s.p_lo, s.p_hi, main)
+            if not first:
+                da = dx
+        elif first:
+            # nothing left to hide behind: share the tail between both streams
+            ready = torch.cuda.Event()
+            ready.record(main)
+            pending.append((grads_U, ready, par, None))
+            flush_side()
+            grads_W('gemm')
+        else:
+            # the side stream starts once the dX GEMMs (critical path) are done,
+            # i.e. together with the next layer's BPTT kernel
+            ready = torch.cuda.Event()
+            ready.record(main)
+            pending.append((weight_grads, ready, par, (s.p_lo, s.p_hi)))
+            da = dx
         return da
 
     # ------------------------------------------------------------------ batches
