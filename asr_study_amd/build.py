@@ -24,6 +24,8 @@ def _deps():
         os.path.join(CSRC, 'common.h'),
         os.path.join(CSRC, 'lstm_common.h'),
         os.path.join(CSRC, 'rec_tile.h'),
+        os.path.join(CSRC, 'vec4.h'),
+        os.path.join(CSRC, 'philox.h'),
         os.path.join(os.path.dirname(HERE), 'include', 'asr_hip.h')]
 
 

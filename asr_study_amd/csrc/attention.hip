@@ -28,7 +28,7 @@
 //             (2) grid (key tiles, heads, n_pad): dK and dV over all query tiles.
 // Every output element is written by exactly one thread, which adds its terms in one fixed
 // order: no float atomics, repeats are bit-identical.  No workgroup waits on another one.
-#include "common.h"
+#include "vec4.h"
 
 namespace {
 
@@ -37,9 +37,6 @@ constexpr int AT_THREADS = 256;
 constexpr int AT_PP = AT_TILE + 4;        // pitch of the probability tile
 constexpr float AT_LOG2E = 1.4426950408889634f;
 constexpr float AT_LN2 = 0.6931471805599453f;
-
-__device__ __forceinline__ float4 at_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void at_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 __device__ __forceinline__ float at_max16(float v) {
 #pragma unroll
@@ -61,8 +58,8 @@ __device__ __forceinline__ void at_load_tile(float* tile, const float* src, size
   for (int e = tid; e < AT_TILE * V; e += AT_THREADS) {
     const int r = e / V, c = (e - r * V) * 4;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r0 + r < r_end) v = at_ld4(src + (size_t)(r0 + r) * row_stride + c);
-    at_st4(tile + r * DP + c, v);
+    if (r0 + r < r_end) v = ld4(src + (size_t)(r0 + r) * row_stride + c);
+    st4(tile + r * DP + c, v);
   }
 }
 
@@ -79,9 +76,9 @@ __device__ __forceinline__ void at_dot(const float* A, const float* B, int ty, i
   for (int d = 0; d < DH; d += 4) {
     float4 a[4], b[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = at_ld4(A + (4 * ty + i) * DP + d);
+    for (int i = 0; i < 4; ++i) a[i] = ld4(A + (4 * ty + i) * DP + d);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) b[j] = at_ld4(B + (tx + 16 * j) * DP + d);
+    for (int j = 0; j < 4; ++j) b[j] = ld4(B + (tx + 16 * j) * DP + d);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -103,7 +100,7 @@ __device__ __forceinline__ void at_acc(const float* P, const float* B, int ty, i
   for (int k = 0; k < AT_TILE; k += 4) {
     float4 p[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) p[i] = at_ld4(P + (4 * ty + i) * AT_PP + k);
+    for (int i = 0; i < 4; ++i) p[i] = ld4(P + (4 * ty + i) * AT_PP + k);
 #pragma unroll
     for (int jj = 0; jj < NJ; ++jj) {
       const float b0 = B[(k + 0) * DP + tx + 16 * jj], b1 = B[(k + 1) * DP + tx + 16 * jj];

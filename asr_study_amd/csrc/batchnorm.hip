@@ -1,4 +1,6 @@
-// K15 BatchNormalization (Keras 1.2.2, mode 0, axis -1) over a time-major slab (T, n_pad, ld).
+// K15 BatchNormalization (Keras 1.2.2, mode 0, axis -1) over a time-major slab (T, n_pad, ld), and
+// K18, the sequence-wise BatchNormalization of a recurrent layer's input projection: one kernel
+// family (reduce, finalize, apply) behind both sets of entry points.
 //
 // Training: y = gamma * (x - mu) * invstd + beta, mu / var the biased moments of every real row
 // (n < N of each frame, all T frames) per channel; channel = column % C (C == W: a plain 2-D
@@ -6,6 +8,22 @@
 // running moments.  Backward: dbeta = sum dy, dgamma = sum dy * xhat, dx = gamma * invstd *
 // (dy - mean(dy) - xhat * mean(dy * xhat)).  An optional clip fuses a following clipped ReLU
 // (forward min(max(y, 0), clip); backward masks dy with 0 < y < clip, y recomputed from x).
+//
+// What a caller may turn on, each on its own:
+//   channel grouping  C < W, the conv image (K15 only asks for it);
+//   clip              the fused clipped ReLU (K15 only asks for it);
+//   lengths           the statistics are taken over the VALID rows only (n < N, t < min(len_n, T));
+//                     every real row is still normalised with them, so time-padding frames
+//                     contribute nothing to mu / var but get a value.  Backward: dx = gamma *
+//                     invstd * (dy - [valid] (dbeta / |V| + xhat * dgamma / |V|)), the sums over
+//                     all real rows.  lens == NULL: every frame is valid;
+//   counted rows      |V| is counted on the device from the lengths and kept behind the
+//                     statistics: stats (4C + 4 floats) = [mean_hi | mean_lo | invstd | var |
+//                     |V|, 0, 0, 0]; the moments are weighted by weight * |V|.  Without it the
+//                     count comes from the host and stats has 4C floats;
+//   max |dx|          of the backward pass (bits of a non-negative float: an integer atomicMax,
+//                     order-independent).
+// K18 is lengths + counted rows + max |dp| on an ungrouped slab (C == W) without clip.
 //
 // Every pass walks the slab with one 16-byte column group per thread: a workgroup is rw row
 // lanes x cw column lanes (cw float4 groups = a tile of 4 * cw columns), so a thread's channel
@@ -15,7 +33,7 @@
 // (partition, tile, slot), and a finalize kernel adds the partials in a fixed order.  No float
 // atomics: two identical calls give identical bits.  Padding rows (n >= N) and padding columns
 // (W <= col < ld) of y and dx are written as zeros.
-#include "common.h"
+#include "vec4.h"
 
 namespace {
 
@@ -66,22 +84,26 @@ int bn_apply_py(const BnGeo& g, long long rows) {
   return (int)(py < 1 ? 1 : py);
 }
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float f4get(const float4& v, int k) {
-  return k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w));
+// valid frames of sample n: len_n clamped to 0 .. T; all T without lengths
+__device__ __forceinline__ int bn_len(const int* __restrict__ lens, int n, int T) {
+  if (lens == nullptr) return T;
+  const int l = lens[n];
+  return l < 0 ? 0 : (l > T ? T : l);
 }
 
 // Sums of one thread's column group over its rows, folded over the workgroup's row lanes (and
 // over the channel's columns for the conv image), written as one partial per slot.
-// mode 0: statistics (x - shift, (x - shift)^2); mode 1: backward (dy', dy' * xhat).
-template <int MODE>
+// mode 0: statistics (x - shift, (x - shift)^2), shift = row (0, 0) of the column; LENS: over the
+// valid rows only (a compile-time policy: without it the inner loop has no length load);
+// mode 1: backward (dy', dy' * xhat) over all real rows.
+template <int MODE, bool LENS>
 __global__ void __launch_bounds__(BN_THREADS)
 bn_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                  const float* __restrict__ gamma, const float* __restrict__ beta,
-                 const float* __restrict__ stats, int N, int n_pad, int ld, int W, int C,
-                 int cw, int rw, int tw, int ntiles, int slots, int grouped, long long nreal,
-                 long long rpp, float clip, double2* __restrict__ part) {
+                 const float* __restrict__ stats, const int* __restrict__ lens, int T, int N,
+                 int n_pad, int ld, int W, int C, int cw, int rw, int tw, int ntiles, int slots,
+                 int grouped, long long nreal, long long rpp, float clip,
+                 double2* __restrict__ part) {
   __shared__ double red[2][BN_THREADS * 4];
   const int tid = threadIdx.x, tile = blockIdx.x, p = blockIdx.y;
   const int cl = tid % cw, rl = tid / cw;
@@ -97,6 +119,7 @@ bn_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dy,
       const float4 k = ld4(x + ch);           // row 0 (frame 0, sample 0) is always real
       for (long long i = i0 + rl; i < i1; i += rw) {
         const long long t = i / N, n = i - t * N;
+        if (LENS && t >= bn_len(lens, (int)n, T)) continue;   // (skipped before its load)
         const float4 v = ld4(x + (size_t)(t * n_pad + n) * ld + col);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -106,7 +129,8 @@ bn_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dy,
         }
       }
     } else {
-      // (scalar loads: C need not be a multiple of 4, pad columns have no coefficients)
+      // (scalar loads: C need not be a multiple of 4, pad columns have no coefficients;
+      // gamma / beta are needed for the clip mask alone and may be NULL without it)
       float mh[4], ml[4], is[4], ga[4], be[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -114,8 +138,8 @@ bn_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dy,
         mh[q] = stats[c];
         ml[q] = stats[C + c];
         is[q] = stats[2 * C + c];
-        ga[q] = gamma[c];
-        be[q] = beta[c];
+        ga[q] = clip > 0.f ? gamma[c] : 0.f;
+        be[q] = clip > 0.f ? beta[c] : 0.f;
       }
       for (long long i = i0 + rl; i < i1; i += rw) {
         const long long t = i / N, n = i - t * N;
@@ -179,11 +203,14 @@ bn_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dy,
 // One wave per channel: adds the partials in a fixed order.
 // mode 0 -> stats [mean_hi | mean_lo | invstd | var] (4C floats) and the optional moments of the
 // running update [w, 0, 0, 0 | w * d (C) | w * (var + d^2) (C)], d = mean - shift.
-// mode 1 -> dgamma, dbeta and coef [mean(dy') | mean(dy' * xhat)] (2C floats).
-template <int MODE>
+// mode 1 -> dgamma, dbeta (optional) and coef [sum dy' / cnt | sum dy' * xhat / cnt] (2C floats).
+// COUNTED: cnt is not the host's but max(|V|, 1), |V| counted here from the lengths in mode 0,
+// kept in stats[4C .. 4C + 3] and read back from there in mode 1; w = weight * |V|.
+template <int MODE, bool COUNTED>
 __global__ void bn_finalize_kernel(const double2* __restrict__ part, const float* __restrict__ x,
-                                   int C, int W, int ntiles, int tw, int slots, int P,
-                                   int grouped, double cnt, float eps, float* __restrict__ stats,
+                                   const int* __restrict__ lens, int T, int N, int C, int W,
+                                   int ntiles, int tw, int slots, int P, int grouped, double cnt,
+                                   float eps, float* __restrict__ stats,
                                    float* __restrict__ moments, const float* __restrict__ shift,
                                    float weight, float* __restrict__ dgamma,
                                    float* __restrict__ dbeta, float* __restrict__ coef) {
@@ -206,7 +233,19 @@ __global__ void bn_finalize_kernel(const double2* __restrict__ part, const float
   }
   a = asr_wave_sum_d(a);
   b = asr_wave_sum_d(b);
+  double nv = 1.;
+  if (COUNTED && MODE == 0) {
+    // |V| of a channel: the valid rows times its W / C columns (integers: exact in any order);
+    // all 64 lanes take part in the wave sum, so it stands before the lanes past 0 leave
+    nv = 0.;
+    for (int n = lane; n < N; n += ASR_WAVE) nv += (double)bn_len(lens, n, T);
+    nv = asr_wave_sum_d(nv) * (double)(W / C);
+  }
   if (lane != 0) return;
+  if (COUNTED) {
+    if (MODE == 1) nv = (double)stats[4 * C];
+    cnt = nv > 0. ? nv : 1.;
+  }
   if (MODE == 0) {
     const double dm = a / cnt;
     const double mean = (double)x[c] + dm;
@@ -217,88 +256,111 @@ __global__ void bn_finalize_kernel(const double2* __restrict__ part, const float
     stats[C + c] = (float)(mean - (double)mh);
     stats[2 * C + c] = (float)(1.0 / sqrt(var + (double)eps));
     stats[3 * C + c] = (float)var;
+    if (COUNTED && c == 0) {
+      stats[4 * C] = (float)nv;
+      stats[4 * C + 1] = stats[4 * C + 2] = stats[4 * C + 3] = 0.f;
+    }
     if (moments != nullptr) {
+      const double w = (double)weight * nv;   // (nv = 1 where the rows are not counted: exact)
       const double d = mean - (double)(shift != nullptr ? shift[c] : mh);
-      moments[4 + c] = (float)((double)weight * d);
-      moments[4 + C + c] = (float)((double)weight * (var + d * d));
+      moments[4 + c] = (float)(w * d);
+      moments[4 + C + c] = (float)(w * (var + d * d));
       if (c == 0) {
-        moments[0] = weight;
+        moments[0] = (float)w;
         moments[1] = moments[2] = moments[3] = 0.f;
       }
     }
   } else {
-    dbeta[c] = (float)a;
     dgamma[c] = (float)b;
+    if (dbeta != nullptr) dbeta[c] = (float)a;
     coef[c] = (float)(a / cnt);
     coef[C + c] = (float)(b / cnt);
   }
-  (void)W;
 }
 
 // Element-wise passes over all T * n_pad rows.  MODE 0: training apply (stats), 1: inference
-// apply (running mean / variance), 2: backward dx (stats + coef).
-template <int MODE>
+// apply (running mean / variance), 2: backward dx (stats + coef); of the backward pass, LENS:
+// the valid / padded split of the lengths, ABSMAX: max |dx|.
+template <int MODE, bool LENS, bool ABSMAX>
 __global__ void __launch_bounds__(BN_THREADS)
 bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                 const float* __restrict__ gamma, const float* __restrict__ beta,
                 const float* __restrict__ stats, const float* __restrict__ rmean,
                 const float* __restrict__ rvar, const float* __restrict__ coef,
-                float* __restrict__ out, int N, int n_pad, int ld, int W, int C, int cw, int rw,
-                int tw, int grouped, long long rows, float eps, float clip) {
+                const int* __restrict__ lens, float* __restrict__ out,
+                unsigned* __restrict__ absmax, int T, int N, int n_pad, int ld, int W, int C,
+                int cw, int rw, int tw, int grouped, long long rows, float eps, float clip) {
   const int tid = threadIdx.x, tile = blockIdx.x;
   const int cl = tid % cw, rl = tid / cw;
   const int col = tile * tw + cl * 4;
-  if (rl >= rw || col >= ld) return;
-  const int ch = grouped ? col % C : col;
-  // the thread's four columns: coefficients (pad columns W <= col < ld: written as zeros)
-  float mh[4], ml[4], is[4], ga[4], be[4], cb[4], cc[4];
-  bool ok[4];
+  float mx = 0.f;
+  // (idle threads skip the walk, not the kernel: the wave maximum below needs every lane)
+  if (rl < rw && col < ld) {
+    const int ch = grouped ? col % C : col;
+    // the thread's four columns: coefficients (pad columns W <= col < ld: written as zeros);
+    // the backward pass needs beta for the clip mask alone, and it may be NULL without it
+    float mh[4], ml[4], is[4], sc[4], be[4], cb[4], cc[4];
+    bool ok[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    ok[q] = col + q < W;
-    const int c = ok[q] ? ch + q : 0;
-    ga[q] = gamma[c];
-    be[q] = beta[c];
-    if (MODE == 1) {
-      mh[q] = rmean[c];
-      ml[q] = 0.f;
-      is[q] = 1.f / sqrtf(rvar[c] + eps);
-    } else {
-      mh[q] = stats[c];
-      ml[q] = stats[C + c];
-      is[q] = stats[2 * C + c];
-    }
-    if (MODE == 2) {
-      cb[q] = coef[c];
-      cc[q] = coef[C + c];
-    }
-  }
-  const long long step = (long long)rw * gridDim.y;
-  for (long long r = (long long)blockIdx.y * rw + rl; r < rows; r += step) {
-    const size_t o = (size_t)r * ld + col;
-    const int n = (int)(r % n_pad);
-    float res[4] = {0.f, 0.f, 0.f, 0.f};
-    if (n < N) {
-      const float4 v = ld4(x + o);
-      float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (MODE == 2) g = ld4(dy + o);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float xc = (f4get(v, q) - mh[q]) - ml[q];
-        const float a = is[q] * ga[q];
-        const float z = fmaf(xc, a, be[q]);
-        if (MODE == 2) {
-          float d = f4get(g, q);
-          if (clip > 0.f) d = (z > 0.f && z < clip) ? d : 0.f;
-          const float xh = xc * is[q];
-          res[q] = ok[q] ? a * ((d - cb[q]) - xh * cc[q]) : 0.f;
-        } else {
-          const float y = clip > 0.f ? fminf(fmaxf(z, 0.f), clip) : z;
-          res[q] = ok[q] ? y : 0.f;
-        }
+    for (int q = 0; q < 4; ++q) {
+      ok[q] = col + q < W;
+      const int c = ok[q] ? ch + q : 0;
+      be[q] = (MODE == 2 && !(clip > 0.f)) ? 0.f : beta[c];
+      if (MODE == 1) {
+        mh[q] = rmean[c];
+        ml[q] = 0.f;
+        is[q] = 1.f / sqrtf(rvar[c] + eps);
+      } else {
+        mh[q] = stats[c];
+        ml[q] = stats[C + c];
+        is[q] = stats[2 * C + c];
+      }
+      sc[q] = is[q] * gamma[c];
+      if (MODE == 2) {
+        cb[q] = coef[c];
+        cc[q] = coef[C + c];
       }
     }
-    st4(out + o, make_float4(res[0], res[1], res[2], res[3]));
+    const long long step = (long long)rw * gridDim.y;
+    for (long long r = (long long)blockIdx.y * rw + rl; r < rows; r += step) {
+      const size_t o = (size_t)r * ld + col;
+      const long long t = r / n_pad;
+      const int n = (int)(r - t * n_pad);
+      float res[4] = {0.f, 0.f, 0.f, 0.f};
+      if (n < N) {
+        const float4 v = ld4(x + o);
+        if (MODE == 2) {
+          const float4 g = ld4(dy + o);
+          const bool valid = !LENS || t < bn_len(lens, n, T);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float xc = (f4get(v, q) - mh[q]) - ml[q];
+            const float xh = xc * is[q];
+            float d = f4get(g, q);
+            if (clip > 0.f) {
+              const float z = fmaf(xc, sc[q], be[q]);
+              d = (z > 0.f && z < clip) ? d : 0.f;
+            }
+            const float e = valid ? (d - cb[q]) - xh * cc[q] : d;
+            res[q] = ok[q] ? sc[q] * e : 0.f;
+            if (ABSMAX) mx = fmaxf(mx, fabsf(res[q]));
+          }
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float xc = (f4get(v, q) - mh[q]) - ml[q];
+            const float z = fmaf(xc, sc[q], be[q]);
+            const float y = clip > 0.f ? fminf(fmaxf(z, 0.f), clip) : z;
+            res[q] = ok[q] ? y : 0.f;
+          }
+        }
+      }
+      st4(out + o, make_float4(res[0], res[1], res[2], res[3]));
+    }
+  }
+  if (ABSMAX) {
+    mx = asr_wave_max(mx);
+    if ((tid & (ASR_WAVE - 1)) == 0 && mx > 0.f) atomicMax(absmax, __float_as_uint(mx));
   }
 }
 
@@ -324,232 +386,75 @@ __global__ void bn_update_kernel(float* __restrict__ rmean, float* __restrict__ 
   rvar[c] = mom * rvar[c] + one_m * bv;
 }
 
-// ---------------------------------------------------------------------------------------------
-// K18 sequence-wise BatchNormalization of a recurrent layer's input projection p (T, n_pad, ld),
-// W real columns, one channel per column (cell-agnostic: only the slab width is known here).
-// The statistics are taken over the VALID rows (n < N, t < min(len_n, T)); every real row (n < N,
-// all T frames) is normalised with them, so time-padding frames contribute nothing to mu / var
-// but still get a value.  Backward: dbeta = sum_R da, dgamma = sum_R da * xhat, dp = gamma *
-// invstd * (da - [valid] (dbeta / |V| + xhat * dgamma / |V|)).  Same workgroup geometry, fp64
-// partials and fixed-order folds as K15 above (the plain 2-D case, C == W).
-// stats (4W + 4 floats): [mean_hi | mean_lo | invstd | var | |V|, 0, 0, 0].
-
-__device__ __forceinline__ int seqbn_len(const int* __restrict__ lens, int n, int T) {
-  if (lens == nullptr) return T;
-  const int l = lens[n];
-  return l < 0 ? 0 : (l > T ? T : l);
+// The three launch sequences behind the entry points (arguments checked by the caller).
+// COUNTED as in bn_finalize_kernel; lens == NULL takes the instantiations without a length load.
+template <bool COUNTED>
+int bn_launch_fwd_train(const float* x, float* y, const float* gamma, const float* beta,
+                        const int* lens, float* stats, float* moments, const float* shift,
+                        float weight, int T, int N, int n_pad, int ld, int W, int C, float eps,
+                        float clip, const BnGeo& g, void* workspace, hipStream_t s) {
+  double2* part = (double2*)workspace;
+  const auto reduce = lens ? bn_reduce_kernel<0, true> : bn_reduce_kernel<0, false>;
+  hipLaunchKernelGGL(reduce, dim3(g.ntiles, g.P), dim3(BN_THREADS), 0, s, x, nullptr, nullptr,
+                     nullptr, nullptr, lens, T, N, n_pad, ld, W, C, g.cw, g.rw, g.tw, g.ntiles,
+                     g.slots, g.grouped, g.nreal, g.rpp, 0.f, part);
+  ASR_CHECK_LAUNCH();
+  const double cnt = (double)g.nreal * (W / C);
+  hipLaunchKernelGGL((bn_finalize_kernel<0, COUNTED>), dim3(C), dim3(ASR_WAVE), 0, s, part, x,
+                     lens, T, N, C, W, g.ntiles, g.tw, g.slots, g.P, g.grouped, cnt, eps, stats,
+                     moments, shift, weight, nullptr, nullptr, nullptr);
+  ASR_CHECK_LAUNCH();
+  const long long rows = (long long)T * n_pad;
+  hipLaunchKernelGGL((bn_apply_kernel<0, false, false>), dim3(g.ntiles, bn_apply_py(g, rows)),
+                     dim3(BN_THREADS), 0, s, x, nullptr, gamma, beta, stats, nullptr, nullptr,
+                     nullptr, nullptr, y, nullptr, T, N, n_pad, ld, W, C, g.cw, g.rw, g.tw,
+                     g.grouped, rows, eps, clip);
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
 }
 
-// mode 0: statistics over V (p - shift, (p - shift)^2), shift = row (0, 0) of the column;
-// mode 1: backward sums over R (da, da * xhat).
-template <int MODE>
-__global__ void __launch_bounds__(BN_THREADS)
-seqbn_reduce_kernel(const float* __restrict__ p, const float* __restrict__ da,
-                    const float* __restrict__ stats, const int* __restrict__ lens, int T, int N,
-                    int n_pad, int ld, int W, int cw, int rw, int tw, int ntiles,
-                    long long nreal, long long rpp, double2* __restrict__ part) {
-  __shared__ double red[2][BN_THREADS * 4];
-  const int tid = threadIdx.x, tile = blockIdx.x, pt = blockIdx.y;
-  const int cl = tid % cw, rl = tid / cw;
-  const int col = tile * tw + cl * 4;
-  const bool act = rl < rw && col < ld;
-  double s1[4] = {0., 0., 0., 0.}, s2[4] = {0., 0., 0., 0.};
-  if (act) {
-    const long long i0 = (long long)pt * rpp;
-    long long i1 = i0 + rpp;
-    if (i1 > nreal) i1 = nreal;
-    if (MODE == 0) {
-      const float4 k = ld4(p + col);
-      for (long long i = i0 + rl; i < i1; i += rw) {
-        const long long t = i / N;
-        const int n = (int)(i - t * N);
-        if (t >= seqbn_len(lens, n, T)) continue;
-        const float4 v = ld4(p + (size_t)(t * n_pad + n) * ld + col);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const double d = (double)f4get(v, q) - (double)f4get(k, q);
-          s1[q] += d;
-          s2[q] = fma(d, d, s2[q]);
-        }
-      }
-    } else {
-      float mh[4], ml[4], is[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c = col + q < W ? col + q : 0;
-        mh[q] = stats[c];
-        ml[q] = stats[W + c];
-        is[q] = stats[2 * W + c];
-      }
-      for (long long i = i0 + rl; i < i1; i += rw) {
-        const long long t = i / N, n = i - t * N;
-        const size_t o = (size_t)(t * n_pad + n) * ld + col;
-        const float4 v = ld4(p + o), g = ld4(da + o);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float xh = ((f4get(v, q) - mh[q]) - ml[q]) * is[q];
-          const float d = f4get(g, q);
-          s1[q] += (double)d;
-          s2[q] = fma((double)d, (double)xh, s2[q]);
-        }
-      }
-    }
-  }
-  if (rl < rw) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      red[0][rl * tw + cl * 4 + q] = act ? s1[q] : 0.;
-      red[1][rl * tw + cl * 4 + q] = act ? s2[q] : 0.;
-    }
-  }
-  __syncthreads();
-  // fold the row lanes: thread j owns column j of the tile (fixed order)
-  if (tid < tw) {
-    double a = 0., b = 0.;
-    for (int r = 0; r < rw; ++r) {
-      a += red[0][r * tw + tid];
-      b += red[1][r * tw + tid];
-    }
-    part[((size_t)pt * ntiles + tile) * tw + tid] = make_double2(a, b);
-  }
+int bn_launch_fwd_infer(const float* x, float* y, const float* gamma, const float* beta,
+                        const float* running_mean, const float* running_var, int T, int N,
+                        int n_pad, int ld, int W, int C, float eps, float clip, const BnGeo& g,
+                        hipStream_t s) {
+  const long long rows = (long long)T * n_pad;
+  hipLaunchKernelGGL((bn_apply_kernel<1, false, false>), dim3(g.ntiles, bn_apply_py(g, rows)),
+                     dim3(BN_THREADS), 0, s, x, nullptr, gamma, beta, nullptr, running_mean,
+                     running_var, nullptr, nullptr, y, nullptr, T, N, n_pad, ld, W, C, g.cw, g.rw,
+                     g.tw, g.grouped, rows, eps, clip);
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
 }
 
-// One wave per column: adds the partials in a fixed order.
-// mode 0 -> stats and the optional moments block [w, 0, 0, 0 | w d (W) | w (var + d^2) (W)],
-// w = weight * |V| (|V| counted here from the lengths), d = mean - shift.
-// mode 1 -> dgamma, dbeta (optional) and coef [sum da / |V| | sum da * xhat / |V|] (2W floats).
-template <int MODE>
-__global__ void seqbn_finalize_kernel(const double2* __restrict__ part,
-                                      const float* __restrict__ p, const int* __restrict__ lens,
-                                      int T, int N, int W, int ntiles, int tw, int P, float eps,
-                                      float* __restrict__ stats, float* __restrict__ moments,
-                                      const float* __restrict__ shift, float weight,
-                                      float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                      float* __restrict__ coef) {
-  const int c = blockIdx.x, lane = threadIdx.x;
-  const int t = c / tw, s = c % tw;
-  double a = 0., b = 0.;
-  for (int q = lane; q < P; q += ASR_WAVE) {
-    const double2 v = part[((size_t)q * ntiles + t) * tw + s];
-    a += v.x;
-    b += v.y;
-  }
-  a = asr_wave_sum_d(a);
-  b = asr_wave_sum_d(b);
-  if (MODE == 0) {
-    double nv = 0.;                 // |V| (integers: exact in any order)
-    for (int n = lane; n < N; n += ASR_WAVE) nv += (double)seqbn_len(lens, n, T);
-    nv = asr_wave_sum_d(nv);
-    if (lane != 0) return;
-    const double cnt = nv > 0. ? nv : 1.;
-    const double dm = a / cnt;
-    const double mean = (double)p[c] + dm;
-    double var = b / cnt - dm * dm;
-    var = var > 0. ? var : 0.;
-    const float mh = (float)mean;
-    stats[c] = mh;
-    stats[W + c] = (float)(mean - (double)mh);
-    stats[2 * W + c] = (float)(1.0 / sqrt(var + (double)eps));
-    stats[3 * W + c] = (float)var;
-    if (c == 0) {
-      stats[4 * W] = (float)nv;
-      stats[4 * W + 1] = stats[4 * W + 2] = stats[4 * W + 3] = 0.f;
-    }
-    if (moments != nullptr) {
-      const double w = (double)weight * nv;
-      const double d = mean - (double)(shift != nullptr ? shift[c] : mh);
-      moments[4 + c] = (float)(w * d);
-      moments[4 + W + c] = (float)(w * (var + d * d));
-      if (c == 0) {
-        moments[0] = (float)w;
-        moments[1] = moments[2] = moments[3] = 0.f;
-      }
-    }
-  } else {
-    if (lane != 0) return;
-    const double nv = (double)stats[4 * W];
-    const double cnt = nv > 0. ? nv : 1.;
-    dgamma[c] = (float)b;
-    if (dbeta != nullptr) dbeta[c] = (float)a;
-    coef[c] = (float)(a / cnt);
-    coef[W + c] = (float)(b / cnt);
-  }
-}
-
-// Element-wise passes over all T * n_pad rows.  MODE 0: training apply (stats), 1: inference
-// apply (running mean / variance), 2: backward dp (stats + coef; the valid / padded split) and
-// max |dp| (bits of a non-negative float: an integer atomicMax, order-independent).
-template <int MODE>
-__global__ void __launch_bounds__(BN_THREADS)
-seqbn_apply_kernel(const float* __restrict__ p, const float* __restrict__ da,
-                   const float* __restrict__ gamma, const float* __restrict__ beta,
-                   const float* __restrict__ stats, const float* __restrict__ rmean,
-                   const float* __restrict__ rvar, const float* __restrict__ coef,
-                   const int* __restrict__ lens, float* __restrict__ out,
-                   unsigned* __restrict__ absmax, int T, int N, int n_pad, int ld, int W, int cw,
-                   int rw, int tw, long long rows, float eps) {
-  const int tid = threadIdx.x, tile = blockIdx.x;
-  const int cl = tid % cw, rl = tid / cw;
-  const int col = tile * tw + cl * 4;
-  float mx = 0.f;
-  if (rl < rw && col < ld) {
-    // the thread's four columns: coefficients (pad columns W <= col < ld: written as zeros)
-    float mh[4], ml[4], sc[4], is[4], be[4], cb[4], cc[4];
-    bool ok[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      ok[q] = col + q < W;
-      const int c = ok[q] ? col + q : 0;
-      be[q] = MODE == 2 ? 0.f : beta[c];
-      if (MODE == 1) {
-        mh[q] = rmean[c];
-        ml[q] = 0.f;
-        is[q] = 1.f / sqrtf(rvar[c] + eps);
-      } else {
-        mh[q] = stats[c];
-        ml[q] = stats[W + c];
-        is[q] = stats[2 * W + c];
-      }
-      sc[q] = is[q] * gamma[c];
-      if (MODE == 2) {
-        cb[q] = coef[c];
-        cc[q] = coef[W + c];
-      }
-    }
-    const long long step = (long long)rw * gridDim.y;
-    for (long long r = (long long)blockIdx.y * rw + rl; r < rows; r += step) {
-      const size_t o = (size_t)r * ld + col;
-      const long long t = r / n_pad;
-      const int n = (int)(r - t * n_pad);
-      float res[4] = {0.f, 0.f, 0.f, 0.f};
-      if (n < N) {
-        const float4 v = ld4(p + o);
-        if (MODE == 2) {
-          const float4 g = ld4(da + o);
-          const bool valid = t < seqbn_len(lens, n, T);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float xh = ((f4get(v, q) - mh[q]) - ml[q]) * is[q];
-            const float d = f4get(g, q);
-            const float e = valid ? (d - cb[q]) - xh * cc[q] : d;
-            res[q] = ok[q] ? sc[q] * e : 0.f;
-            mx = fmaxf(mx, fabsf(res[q]));
-          }
-        } else {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float xc = (f4get(v, q) - mh[q]) - ml[q];
-            res[q] = ok[q] ? fmaf(xc, sc[q], be[q]) : 0.f;
-          }
-        }
-      }
-      st4(out + o, make_float4(res[0], res[1], res[2], res[3]));
-    }
-  }
-  if (MODE == 2 && absmax != nullptr) {
-    mx = asr_wave_max(mx);
-    if ((tid & (ASR_WAVE - 1)) == 0 && mx > 0.f) atomicMax(absmax, __float_as_uint(mx));
-  }
+// beta may be NULL where clip == 0; dbeta, dx and dx_absmax where they are not wanted
+template <bool COUNTED>
+int bn_launch_bwd(const float* x, const float* dy, const float* gamma, const float* beta,
+                  const int* lens, const float* stats, float* dx, float* dgamma, float* dbeta,
+                  float* dx_absmax, int T, int N, int n_pad, int ld, int W, int C, float clip,
+                  const BnGeo& g, void* workspace, hipStream_t s) {
+  double2* part = (double2*)workspace;
+  float* coef = (float*)((char*)workspace + bn_partial_bytes(g));
+  hipLaunchKernelGGL((bn_reduce_kernel<1, false>), dim3(g.ntiles, g.P), dim3(BN_THREADS), 0, s, x,
+                     dy, gamma, beta, stats, nullptr, T, N, n_pad, ld, W, C, g.cw, g.rw, g.tw,
+                     g.ntiles, g.slots, g.grouped, g.nreal, g.rpp, clip, part);
+  ASR_CHECK_LAUNCH();
+  const double cnt = (double)g.nreal * (W / C);
+  hipLaunchKernelGGL((bn_finalize_kernel<1, COUNTED>), dim3(C), dim3(ASR_WAVE), 0, s, part, x,
+                     nullptr, T, N, C, W, g.ntiles, g.tw, g.slots, g.P, g.grouped, cnt, 0.f,
+                     const_cast<float*>(stats), nullptr, nullptr, 0.f, dgamma, dbeta, coef);
+  ASR_CHECK_LAUNCH();
+  if (dx == nullptr) return ASR_OK;
+  if (dx_absmax) ASR_CHECK_HIP(hipMemsetAsync(dx_absmax, 0, sizeof(float), s));
+  const auto apply =
+      lens ? (dx_absmax ? bn_apply_kernel<2, true, true> : bn_apply_kernel<2, true, false>)
+           : (dx_absmax ? bn_apply_kernel<2, false, true> : bn_apply_kernel<2, false, false>);
+  const long long rows = (long long)T * n_pad;
+  hipLaunchKernelGGL(apply, dim3(g.ntiles, bn_apply_py(g, rows)), dim3(BN_THREADS), 0, s, x, dy,
+                     gamma, beta, stats, nullptr, nullptr, coef, lens, dx,
+                     reinterpret_cast<unsigned*>(dx_absmax), T, N, n_pad, ld, W, C, g.cw, g.rw,
+                     g.tw, g.grouped, rows, 0.f, clip);
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
 }
 
 }  // namespace
@@ -575,23 +480,9 @@ extern "C" int asr_bn_fwd_train(const float* x, float* y, const float* gamma, co
   ASR_CHECK_ARG(x && y && gamma && beta && stats && eps > 0.f && clip >= 0.f,
                 "bn_fwd_train: bad arguments");
   BN_GEO_OR_FAIL("bn_fwd_train");
-  hipStream_t s = (hipStream_t)stream;
-  double2* part = (double2*)workspace;
-  hipLaunchKernelGGL(bn_reduce_kernel<0>, dim3(g.ntiles, g.P), dim3(BN_THREADS), 0, s, x,
-                     nullptr, nullptr, nullptr, nullptr, N, n_pad, ld, W, C, g.cw, g.rw, g.tw,
-                     g.ntiles, g.slots, g.grouped, g.nreal, g.rpp, 0.f, part);
-  ASR_CHECK_LAUNCH();
-  const double cnt = (double)g.nreal * (W / C);
-  hipLaunchKernelGGL(bn_finalize_kernel<0>, dim3(C), dim3(ASR_WAVE), 0, s, part, x, C,
-                     W, g.ntiles, g.tw, g.slots, g.P, g.grouped, cnt, eps, stats, moments, shift,
-                     weight, nullptr, nullptr, nullptr);
-  ASR_CHECK_LAUNCH();
-  const long long rows = (long long)T * n_pad;
-  hipLaunchKernelGGL(bn_apply_kernel<0>, dim3(g.ntiles, bn_apply_py(g, rows)), dim3(BN_THREADS),
-                     0, s, x, nullptr, gamma, beta, stats, nullptr, nullptr, nullptr, y, N, n_pad,
-                     ld, W, C, g.cw, g.rw, g.tw, g.grouped, rows, eps, clip);
-  ASR_CHECK_LAUNCH();
-  return ASR_OK;
+  return bn_launch_fwd_train<false>(x, y, gamma, beta, nullptr, stats, moments, shift, weight, T,
+                                    N, n_pad, ld, W, C, eps, clip, g, workspace,
+                                    (hipStream_t)stream);
 }
 
 extern "C" int asr_bn_fwd_infer(const float* x, float* y, const float* gamma, const float* beta,
@@ -603,13 +494,8 @@ extern "C" int asr_bn_fwd_infer(const float* x, float* y, const float* gamma, co
                 "bn_fwd_infer: bad arguments");
   BnGeo g;
   ASR_CHECK_ARG(bn_geo(T, N, n_pad, ld, W, C, &g), "bn_fwd_infer: bad geometry");
-  const long long rows = (long long)T * n_pad;
-  hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(g.ntiles, bn_apply_py(g, rows)), dim3(BN_THREADS),
-                     0, (hipStream_t)stream, x, nullptr, gamma, beta, nullptr, running_mean,
-                     running_var, nullptr, y, N, n_pad, ld, W, C, g.cw, g.rw, g.tw, g.grouped,
-                     rows, eps, clip);
-  ASR_CHECK_LAUNCH();
-  return ASR_OK;
+  return bn_launch_fwd_infer(x, y, gamma, beta, running_mean, running_var, T, N, n_pad, ld, W, C,
+                             eps, clip, g, (hipStream_t)stream);
 }
 
 extern "C" int asr_bn_bwd(const float* x, const float* dy, const float* gamma, const float* beta,
@@ -620,25 +506,8 @@ extern "C" int asr_bn_bwd(const float* x, const float* dy, const float* gamma, c
                 "bn_bwd: bad arguments");
   ASR_CHECK_ARG(dx != dy && dx != x, "bn_bwd: dx must not alias x or dy");
   BN_GEO_OR_FAIL("bn_bwd");
-  hipStream_t s = (hipStream_t)stream;
-  double2* part = (double2*)workspace;
-  float* coef = (float*)((char*)workspace + bn_partial_bytes(g));
-  hipLaunchKernelGGL(bn_reduce_kernel<1>, dim3(g.ntiles, g.P), dim3(BN_THREADS), 0, s, x, dy,
-                     gamma, beta, stats, N, n_pad, ld, W, C, g.cw, g.rw, g.tw, g.ntiles, g.slots,
-                     g.grouped, g.nreal, g.rpp, clip, part);
-  ASR_CHECK_LAUNCH();
-  const double cnt = (double)g.nreal * (W / C);
-  hipLaunchKernelGGL(bn_finalize_kernel<1>, dim3(C), dim3(ASR_WAVE), 0, s, part, x, C,
-                     W, g.ntiles, g.tw, g.slots, g.P, g.grouped, cnt, 0.f, nullptr, nullptr,
-                     nullptr, 0.f, dgamma, dbeta, coef);
-  ASR_CHECK_LAUNCH();
-  if (dx == nullptr) return ASR_OK;
-  const long long rows = (long long)T * n_pad;
-  hipLaunchKernelGGL(bn_apply_kernel<2>, dim3(g.ntiles, bn_apply_py(g, rows)), dim3(BN_THREADS),
-                     0, s, x, dy, gamma, beta, stats, nullptr, nullptr, coef, dx, N, n_pad, ld,
-                     W, C, g.cw, g.rw, g.tw, g.grouped, rows, 0.f, clip);
-  ASR_CHECK_LAUNCH();
-  return ASR_OK;
+  return bn_launch_bwd<false>(x, dy, gamma, beta, nullptr, stats, dx, dgamma, dbeta, nullptr, T,
+                              N, n_pad, ld, W, C, clip, g, workspace, (hipStream_t)stream);
 }
 
 extern "C" int asr_bn_update_running(float* running_mean, float* running_var,
@@ -656,6 +525,8 @@ extern "C" int asr_bn_update_running(float* running_mean, float* running_var,
 }
 
 // ------------------------------------------------------------------------------- K18 entry points
+// p (T, n_pad, ld) with W real columns, one channel per column (cell-agnostic: only the slab
+// width is known here): lengths, counted rows, no grouping, no clip.
 extern "C" size_t asr_seqbn_workspace_bytes(int T, int N, int n_pad, int ld, int W) {
   BnGeo g;
   if (!bn_geo(T, N, n_pad, ld, W, W, &g)) return 0;
@@ -677,23 +548,8 @@ extern "C" int asr_seqbn_fwd_train(const float* p, float* y, const float* gamma,
   ASR_CHECK_ARG(p && y && gamma && beta && stats && eps > 0.f && weight >= 0.f,
                 "seqbn_fwd_train: bad arguments");
   SEQBN_GEO_OR_FAIL("seqbn_fwd_train");
-  hipStream_t s = (hipStream_t)stream;
-  double2* part = (double2*)workspace;
-  hipLaunchKernelGGL(seqbn_reduce_kernel<0>, dim3(g.ntiles, g.P), dim3(BN_THREADS), 0, s, p,
-                     nullptr, nullptr, lens, T, N, n_pad, ld, W, g.cw, g.rw, g.tw, g.ntiles,
-                     g.nreal, g.rpp, part);
-  ASR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(seqbn_finalize_kernel<0>, dim3(W), dim3(ASR_WAVE), 0, s, part, p, lens, T,
-                     N, W, g.ntiles, g.tw, g.P, eps, stats, moments, shift, weight, nullptr,
-                     nullptr, nullptr);
-  ASR_CHECK_LAUNCH();
-  const long long rows = (long long)T * n_pad;
-  hipLaunchKernelGGL(seqbn_apply_kernel<0>, dim3(g.ntiles, bn_apply_py(g, rows)),
-                     dim3(BN_THREADS), 0, s, p, nullptr, gamma, beta, stats, nullptr, nullptr,
-                     nullptr, nullptr, y, nullptr, T, N, n_pad, ld, W, g.cw, g.rw, g.tw, rows,
-                     eps);
-  ASR_CHECK_LAUNCH();
-  return ASR_OK;
+  return bn_launch_fwd_train<true>(p, y, gamma, beta, lens, stats, moments, shift, weight, T, N,
+                                   n_pad, ld, W, W, eps, 0.f, g, workspace, (hipStream_t)stream);
 }
 
 extern "C" int asr_seqbn_fwd_infer(const float* p, float* y, const float* gamma,
@@ -704,13 +560,8 @@ extern "C" int asr_seqbn_fwd_infer(const float* p, float* y, const float* gamma,
                 "seqbn_fwd_infer: bad arguments");
   BnGeo g;
   ASR_CHECK_ARG(bn_geo(T, N, n_pad, ld, W, W, &g), "seqbn_fwd_infer: bad geometry");
-  const long long rows = (long long)T * n_pad;
-  hipLaunchKernelGGL(seqbn_apply_kernel<1>, dim3(g.ntiles, bn_apply_py(g, rows)),
-                     dim3(BN_THREADS), 0, (hipStream_t)stream, p, nullptr, gamma, beta, nullptr,
-                     running_mean, running_var, nullptr, nullptr, y, nullptr, T, N, n_pad, ld, W,
-                     g.cw, g.rw, g.tw, rows, eps);
-  ASR_CHECK_LAUNCH();
-  return ASR_OK;
+  return bn_launch_fwd_infer(p, y, gamma, beta, running_mean, running_var, T, N, n_pad, ld, W, W,
+                             eps, 0.f, g, (hipStream_t)stream);
 }
 
 extern "C" int asr_seqbn_bwd(const float* p, const float* da, const float* gamma,
@@ -720,23 +571,6 @@ extern "C" int asr_seqbn_bwd(const float* p, const float* da, const float* gamma
   ASR_CHECK_ARG(p && da && gamma && stats && dp && dgamma, "seqbn_bwd: bad arguments");
   ASR_CHECK_ARG(dp != da && dp != p, "seqbn_bwd: dp must not alias p or da");
   SEQBN_GEO_OR_FAIL("seqbn_bwd");
-  hipStream_t s = (hipStream_t)stream;
-  double2* part = (double2*)workspace;
-  float* coef = (float*)((char*)workspace + bn_partial_bytes(g));
-  hipLaunchKernelGGL(seqbn_reduce_kernel<1>, dim3(g.ntiles, g.P), dim3(BN_THREADS), 0, s, p, da,
-                     stats, nullptr, T, N, n_pad, ld, W, g.cw, g.rw, g.tw, g.ntiles, g.nreal,
-                     g.rpp, part);
-  ASR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(seqbn_finalize_kernel<1>, dim3(W), dim3(ASR_WAVE), 0, s, part, p, nullptr,
-                     T, N, W, g.ntiles, g.tw, g.P, 0.f, const_cast<float*>(stats), nullptr,
-                     nullptr, 0.f, dgamma, dbeta, coef);
-  ASR_CHECK_LAUNCH();
-  if (dp_absmax) ASR_CHECK_HIP(hipMemsetAsync(dp_absmax, 0, sizeof(float), s));
-  const long long rows = (long long)T * n_pad;
-  hipLaunchKernelGGL(seqbn_apply_kernel<2>, dim3(g.ntiles, bn_apply_py(g, rows)),
-                     dim3(BN_THREADS), 0, s, p, da, gamma, nullptr, stats, nullptr, nullptr, coef,
-                     lens, dp, reinterpret_cast<unsigned*>(dp_absmax), T, N, n_pad, ld, W, g.cw,
-                     g.rw, g.tw, rows, 0.f);
-  ASR_CHECK_LAUNCH();
-  return ASR_OK;
+  return bn_launch_bwd<true>(p, da, gamma, nullptr, lens, stats, dp, dgamma, dbeta, dp_absmax, T,
+                             N, n_pad, ld, W, W, 0.f, g, workspace, (hipStream_t)stream);
 }

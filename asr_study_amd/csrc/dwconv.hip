@@ -26,7 +26,7 @@
 // walks every S-th tile of its columns and writes one partial per (segment, tap, column); a
 // finishing kernel adds the partials of a channel over segments and samples in a fixed order.
 // No float atomics: two identical calls give identical bits.  No workgroup waits on another.
-#include "common.h"
+#include "vec4.h"
 
 namespace {
 
@@ -40,14 +40,6 @@ constexpr int DW_TAPS = (DW_MAXK + DW_TS - 1) / DW_TS;   // most taps a thread o
 static_assert(DW_TAPS == 4, "dw_wgrad_kernel is instantiated for 1 .. 4 taps per thread");
 constexpr int DW_WG_BLOCKS = 1024;        // workgroups the weight-gradient launch aims at
 constexpr float DW_LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
-  return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z),
-                     fmaf(a.w, b.w, c.w));
-}
 
 struct DwGeo {
   int T, N, n_pad, C, ld, k, p;
@@ -108,7 +100,7 @@ __device__ __forceinline__ void dw_stage(float4* __restrict__ dst, const float* 
                                          int lim) {
   for (int r = threadIdx.x / DW_CG; r < rows; r += DW_TS) {
     const int u = u0 + r;
-    float4 v = f4zero();
+    float4 v = zero4();
     if (q.real && u >= 0 && u < lim) v = ld4(src + (size_t)u * W + q.col);
     dst[r * DW_CG + cg] = v;
   }
@@ -132,11 +124,11 @@ dw_conv_kernel(const float* __restrict__ in, const float* __restrict__ w,
   const bool any_real = ((long long)blockIdx.x * DW_CG * 4) / ld < N;
   float4 acc[DW_R];
 #pragma unroll
-  for (int r = 0; r < DW_R; ++r) acc[r] = f4zero();
+  for (int r = 0; r < DW_R; ++r) acc[r] = zero4();
   if (any_real) {
     dw_stage(Xs, in, q, cg, W, t0 - p, rows, mask_in ? q.len : T);
     for (int j = ts; j < k; j += DW_TS)
-      Ws[j * DW_CG + cg] = q.real ? ld4(w + (size_t)(flip ? k - 1 - j : j) * C + q.c) : f4zero();
+      Ws[j * DW_CG + cg] = q.real ? ld4(w + (size_t)(flip ? k - 1 - j : j) * C + q.c) : zero4();
     __syncthreads();
     if (q.real && bias != nullptr) {
       const float4 b = ld4(bias + q.c);
@@ -162,7 +154,7 @@ dw_conv_kernel(const float* __restrict__ in, const float* __restrict__ w,
     const int t = t0 + ts * DW_R + r;
     if (t >= T) break;
     const bool on = q.real && (!mask_out || t < q.len);
-    st4(out + (size_t)t * W + q.col, on ? acc[r] : f4zero());
+    st4(out + (size_t)t * W + q.col, on ? acc[r] : zero4());
   }
 }
 
@@ -180,9 +172,9 @@ dw_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
   const int cg = threadIdx.x % DW_CG, js = threadIdx.x / DW_CG;
   const DwCol q = dw_column(cg, T, N, C, ld, W, lens);
   const bool any_real = ((long long)blockIdx.x * DW_CG * 4) / ld < N;
-  float4 acc[RR], accb = f4zero();
+  float4 acc[RR], accb = zero4();
 #pragma unroll
-  for (int r = 0; r < RR; ++r) acc[r] = f4zero();
+  for (int r = 0; r < RR; ++r) acc[r] = zero4();
   if (any_real) {
     for (int tile = blockIdx.y; tile < tiles; tile += S) {
       const int t0 = tile * DW_TT;
@@ -225,7 +217,7 @@ dw_finish_kernel(const float* __restrict__ part, int S, int N, int C, int ld, lo
   __shared__ float4 red[DW_TS][DW_CG];
   const int cg = threadIdx.x % DW_CG, sl = threadIdx.x / DW_CG;
   const int j = blockIdx.x, c = (blockIdx.y * DW_CG + cg) * 4;
-  float4 a = f4zero();
+  float4 a = zero4();
   if (c < C) {
     const int items = S * N;
 #pragma unroll 4
@@ -304,7 +296,7 @@ glu_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t rows,
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
     const int64_t row = i / g4;
     const int c = (int)(i - row * g4) * 4;
-    float4 o = f4zero();
+    float4 o = zero4();
     if (c < C) {
       const float4 a = ld4(x + row * ld_in + c), g = ld4(x + row * ld_in + C + c);
       o = make_float4(dw_glu(a.x, g.x), dw_glu(a.y, g.y), dw_glu(a.z, g.z), dw_glu(a.w, g.w));
@@ -329,7 +321,7 @@ glu_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
     const int64_t row = i / g4;
     const int col = (int)(i - row * g4) * 4;
-    float4 o = f4zero();
+    float4 o = zero4();
     if (col < 2 * C) {
       const bool gate = col >= C;
       const int c = gate ? col - C : col;

@@ -20,7 +20,7 @@
 // of a workgroup through LDS one after the other, writes one partial per workgroup, and a
 // finishing kernel adds the partials in a fixed order.  No float atomics anywhere: two
 // identical calls give identical bits.
-#include "common.h"
+#include "vec4.h"
 
 namespace {
 
@@ -54,9 +54,6 @@ int ln_blocks(const LnGeo& g, int cap) { return (int)(g.groups < cap ? g.groups 
 size_t ln_partial_bytes(const LnGeo& g, int ld) {
   return asr_align_up((size_t)ln_blocks(g, LN_BWD_BLOCKS) * 2 * ld * sizeof(float), 256);
 }
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 template <int LPR>
 __device__ __forceinline__ float ln_row_sum(float v) {

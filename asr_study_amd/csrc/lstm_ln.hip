@@ -12,7 +12,7 @@
 // inside a workgroup.  About 3 launches per step: several times slower than the
 // persistent kernels, but complete: LN combines freely with multiplicative integration
 // and zoneout.  All 4H axes are unit-major / gate-minor like everywhere else.
-#include "common.h"
+#include "vec4.h"
 
 namespace {
 
@@ -50,8 +50,6 @@ __device__ __forceinline__ void block_sums(float (&v)[NV], float* lds) {
   for (int i = 0; i < NV; ++i) v[i] = (lds[i] + lds[NV + i]) + (lds[2 * NV + i] + lds[3 * NV + i]);
 }
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float sum4(float4 a) { return (a.x + a.y) + (a.z + a.w); }
 __device__ __forceinline__ float sumsq4(float4 a, float m) {
   const float x = a.x - m, y = a.y - m, z = a.z - m, w = a.w - m;
@@ -60,13 +58,8 @@ __device__ __forceinline__ float sumsq4(float4 a, float m) {
 __device__ __forceinline__ float4 norm4(float4 a, float m, float r) {
   return make_float4((a.x - m) * r, (a.y - m) * r, (a.z - m) * r, (a.w - m) * r);
 }
-__device__ __forceinline__ float4 mul4(float4 a, float4 b) {
-  return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) {
-  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-}
-__device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {   // a*b + c
+// (a * b + c as written, not vec4.h's fmaf form: that one changes this file's device code)
+__device__ __forceinline__ float4 muladd4(float4 a, float4 b, float4 c) {
   return make_float4(a.x * b.x + c.x, a.y * b.y + c.y, a.z * b.z + c.z, a.w * b.w + c.w);
 }
 __device__ __forceinline__ float dot4(float4 a, float4 b) {
@@ -147,8 +140,8 @@ cell_ln_fwd_kernel(CellArgs a) {
     cnew[m] = 0.f; hprev[m] = 0.f; kh[m] = 1.f; g4[m] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (!ok[m]) continue;
     const int j = 4 * un[m];
-    const float4 unn = fma4(norm4(uh[m], mu_u, rs_u), ld4(P + o.gu + j), ld4(P + o.bu + j));
-    const float4 wnn = fma4(norm4(wx[m], mu_w, rs_w), ld4(P + o.gw + j), ld4(P + o.bw + j));
+    const float4 unn = muladd4(norm4(uh[m], mu_u, rs_u), ld4(P + o.gu + j), ld4(P + o.bu + j));
+    const float4 wnn = muladd4(norm4(wx[m], mu_w, rs_w), ld4(P + o.gw + j), ld4(P + o.bw + j));
     float4 z;
     if (a.has_mi) {
       const float4 al = ld4(P + o.alpha + j), b1 = ld4(P + o.beta1 + j), b2 = ld4(P + o.beta2 + j);
@@ -260,14 +253,14 @@ cell_ln_bwd_kernel(CellArgs a) {
     what[m] = norm4(wx[m], mu_w, rs_w);
     const float4 gu = ld4(P + o.gu + j), gw = ld4(P + o.gw + j);
     if (a.has_mi) {
-      const float4 unn = fma4(uhat[m], gu, ld4(P + o.bu + j));
-      const float4 wnn = fma4(what[m], gw, ld4(P + o.bw + j));
+      const float4 unn = muladd4(uhat[m], gu, ld4(P + o.bu + j));
+      const float4 wnn = muladd4(what[m], gw, ld4(P + o.bw + j));
       const float4 al = ld4(P + o.alpha + j), b1 = ld4(P + o.beta1 + j), b2 = ld4(P + o.beta2 + j);
       st4(G + o.alpha + j, add4(ld4(G + o.alpha + j), mul4(mul4(dz, wnn), unn)));
       st4(G + o.beta1 + j, add4(ld4(G + o.beta1 + j), mul4(dz, unn)));
       st4(G + o.beta2 + j, add4(ld4(G + o.beta2 + j), mul4(dz, wnn)));
-      dun[m] = mul4(dz, fma4(al, wnn, b1));
-      dwn[m] = mul4(dz, fma4(al, unn, b2));
+      dun[m] = mul4(dz, muladd4(al, wnn, b1));
+      dwn[m] = mul4(dz, muladd4(al, unn, b2));
     } else {
       dun[m] = dz; dwn[m] = dz;
     }

@@ -12,26 +12,9 @@
 //   keep mask = u >= p ? scale : 0            (scale = 1/(1-p): inverted dropout; 1: zoneout)
 //   normal    = sqrt(-2 ln u1) * cos / sin (2 pi u2), u1 = (w0 + 1) 2^-32, u2 = w1 2^-32
 // HBM-bound: one 16-byte store per thread and block of four values.
-#include "common.h"
+#include "philox.h"
 
 namespace {
-
-struct Philox { unsigned c[4]; };
-
-__device__ __forceinline__ Philox philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
-                                                unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  Philox p;
-  p.c[0] = c0; p.c[1] = c1; p.c[2] = c2; p.c[3] = c3;
-  return p;
-}
 
 // mode 0: keep mask; 1: out = in * keep mask (mask also stored if mask_out); 2: out = in +
 // sigma * normal (in may be NULL: pure noise); 3: raw 32-bit words (tests)

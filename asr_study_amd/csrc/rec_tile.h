@@ -12,21 +12,12 @@
 // FMAs; no float atomics: repeats are bit-identical.
 #pragma once
 #include "lstm_common.h"
+#include "vec4.h"
 
 namespace {
 
 constexpr int kKc = 256;                   // reduction chunk
 constexpr int kActClipped = 7;             // clipped ReLU min(max(z, 0), clip)
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 mul4(float4 a, float4 b) {
-  return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) {
-  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-}
 
 // Activation ids 0 tanh, 1 relu, 4 linear (asr_act_apply) and 7; the BPTT slope is taken from the
 // output alone, the clipped ReLU's is 1 on 0 < h < clip and 0 elsewhere (the end points count as

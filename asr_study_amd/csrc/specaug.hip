@@ -21,7 +21,7 @@
 // A masked element is a select, never a product; what is not augmented is copied bit for bit.
 // Memory-bound: one read and one write of the slab; warped rows read two neighbouring source
 // rows of the same sample, which neighbouring tiles read too (L2).
-#include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -32,24 +32,6 @@ constexpr int MAX_MASKS = 64;     // mF + mT
 constexpr int FM_WORDS = 32;      // the frequency masks as a bitmap of the columns < 32 * FM_WORDS
 
 enum { ROW_PRESENT = 1, ROW_VALID = 2, ROW_WARP = 4, ROW_TMASK = 8 };
-
-struct Philox { unsigned c[4]; };
-
-// (random.hip's generator, restated: that file keeps it in its own anonymous namespace)
-__device__ __forceinline__ Philox philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
-                                                unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  Philox p;
-  p.c[0] = c0; p.c[1] = c1; p.c[2] = c2; p.c[3] = c3;
-  return p;
-}
 
 __device__ __forceinline__ int rand_below(unsigned word, int k) {
   return (int)__umulhi(word, (unsigned)k);

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import batchnorm_oracle as BO
+from tests.bn_cases import BN_CASES as CASES, bn_inputs, run_bn_kernels as _run_kernels
 
 pytestmark = pytest.mark.gpu
 
@@ -23,48 +24,11 @@ def _rel(got, want):
     return float(np.abs(got - want).max() / max(np.abs(want).max(), 1e-30))
 
 
-def _run_kernels(x, N, W, C, gamma, beta, dy, clip, rm=None, rv=None):
-    """x (T, n_pad, ld) host float32 -> y, stats, dx, dgamma, dbeta, infer y (host arrays)."""
-    from asr_study_amd import ops
-    xd, dyd = _dev(x), _dev(dy)
-    y = torch.full_like(xd, 7.0)            # pads must be written, not left alone
-    stats = torch.empty(ops.bn_stats_len(C), device='cuda:0')
-    mom = torch.empty(ops.bn_moments_len(C), device='cuda:0')
-    g, b = _dev(gamma), _dev(beta)
-    ops.bn_fwd_train(xd, y, g, b, stats, N, W, C, 1e-3, clip, moments=mom, weight=float(N))
-    dx = torch.full_like(xd, 7.0)
-    dg, db = torch.empty(C, device='cuda:0'), torch.empty(C, device='cuda:0')
-    ops.bn_bwd(xd, dyd, g, b, stats, dx, dg, db, N, W, C, clip)
-    yi = torch.full_like(xd, 7.0)
-    if rm is not None:
-        ops.bn_fwd_infer(xd, yi, g, b, _dev(rm), _dev(rv), N, W, C, 1e-3, clip)
-    torch.cuda.synchronize()
-    return [t.cpu().numpy() for t in (y, stats, dx, dg, db, yi, mom)]
-
-
-# (T, N, n_pad, ld, W, C): 2-D widths 1, 3, 32, 1024, 1026 (with pads) and 2048, the 40 x 32
-# conv image, rows from 1 to 64 000 with n_pad > N
-CASES = [(1, 1, 16, 4, 1, None), (7, 5, 16, 4, 3, None), (50, 13, 16, 32, 32, None),
-         (100, 64, 64, 1024, 1024, None), (33, 20, 32, 1028, 1026, None),
-         (20, 50, 64, 2048, 2048, None), (60, 9, 16, 1280, 1280, 32), (1000, 64, 64, 32, 32, None),
-         (31, 3, 16, 80, 80, 8)]
-
-
 @pytest.mark.parametrize('clip', [0.0, 2.0], ids=['plain', 'clip'])
 @pytest.mark.parametrize('T,N,n_pad,ld,W,C', CASES)
 def test_kernel_parity(T, N, n_pad, ld, W, C, clip):
-    rs = np.random.RandomState(T + W)
     Cn = W if C is None else C
-    x = np.zeros((T, n_pad, ld), np.float32)
-    x[:, :N, :W] = rs.randn(T, N, W) * 1.5 + rs.randn(W) * 0.5
-    x[:, N:, :] = rs.randn(T, n_pad - N, ld)       # junk in padding rows / columns: ignored
-    x[:, :N, W:] = rs.randn(T, N, ld - W)
-    if C is None and W >= 3:
-        x[:, :N, 1] = 1e3 + 0.1 * rs.randn(T, N)    # stability: |mean| 1e3, std 0.1
-        x[:, :N, 2] = 0.25                          # a constant column: var 0
-    gamma, beta = rs.rand(Cn) + 0.5, rs.randn(Cn) * 0.3
-    dy = rs.randn(T, n_pad, ld).astype(np.float32)
-    rm, rv = rs.randn(Cn), rs.rand(Cn) + 0.5
+    x, gamma, beta, dy, rm, rv = bn_inputs(T, N, n_pad, ld, W, C)
     y, stats, dx, dg, db, yi, mom = _run_kernels(x, N, W, Cn, gamma, beta, dy, clip, rm, rv)
     xr = x[:, :N, :W].astype(np.float64)
     yw, c = BO.bn_forward(xr, gamma, beta, 1e-3, C, clip)

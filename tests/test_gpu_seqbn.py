@@ -11,6 +11,8 @@ import pytest
 import torch
 
 from tests import seqbn_oracle as SO
+from tests.bn_cases import (SEQBN_CASES as CASES, ragged as _ragged, seqbn_inputs,
+                            run_seqbn_kernels as _run_kernels)
 from tests.test_gpu_gru import _gpu_gates, _gpu_masks, _labels, ds2_batch, stack_batch
 
 pytestmark = pytest.mark.gpu
@@ -27,71 +29,10 @@ def _rel(got, want):
     return float(np.abs(got - want).max() / max(np.abs(want).max(), 1e-30))
 
 
-def _lens_dev(lens):
-    return None if lens is None else torch.tensor(np.asarray(lens), dtype=torch.int32,
-                                                  device='cuda:0')
-
-
-def _run_kernels(p, N, W, lens, gamma, beta, da, rm=None, rv=None, shift=None, weight=1.0):
-    """p, da (T, n_pad, ld) host float32 -> y, stats, dp, dgamma, dbeta, infer y, moments,
-    max |dp| (host arrays)."""
-    from asr_study_amd import ops
-    pd, dad, ld = _dev(p), _dev(da), _lens_dev(lens)
-    y = torch.full_like(pd, 7.0)            # pads must be written, not left alone
-    stats = torch.empty(ops.seqbn_stats_len(W), device='cuda:0')
-    mom = torch.empty(ops.bn_moments_len(W), device='cuda:0')
-    g, b = _dev(gamma), _dev(beta)
-    ops.seqbn_fwd_train(pd, y, g, b, stats, N, W, lens=ld, eps=1e-3, moments=mom,
-                        shift=None if shift is None else _dev(shift), weight=weight)
-    dp = torch.full_like(pd, 7.0)
-    dg, db = torch.empty(W, device='cuda:0'), torch.empty(W, device='cuda:0')
-    mx = torch.full((1,), 7.0, device='cuda:0')
-    ops.seqbn_bwd(pd, dad, g, stats, dp, dg, N, W, lens=ld, dbeta=db, dp_absmax=mx)
-    yi = torch.full_like(pd, 7.0)
-    if rm is not None:
-        ops.seqbn_fwd_infer(pd, yi, g, b, _dev(rm), _dev(rv), N, W, 1e-3)
-    torch.cuda.synchronize()
-    return [t.cpu().numpy() for t in (y, stats, dp, dg, db, yi, mom, mx)]
-
-
-def _ragged(rs, T, N):
-    """Lengths in [1, T] with one sample of length 1 and one of length T (N >= 2)."""
-    lens = rs.randint(1, T + 1, size=N)
-    lens[0] = T
-    if N > 1:
-        lens[-1] = 1
-    return lens
-
-
-# (T, N, n_pad, ld, W, Hp, H): the slab of a GRU with H = 18 (Hp = 20: pad columns inside every
-# block), pad columns behind W, the cfg3 width 3072 with N = n_pad and N < n_pad, a narrow slab
-CASES = [(30, 5, 16, 120, 120, 20, 18), (33, 20, 32, 1028, 1026, None, None),
-         (60, 64, 64, 3072, 3072, None, None), (50, 13, 16, 3072, 3072, None, None),
-         (7, 3, 16, 24, 24, None, None), (1, 1, 16, 4, 3, None, None)]
-
-
 @pytest.mark.parametrize('ragged', [True, False], ids=['ragged', 'full'])
 @pytest.mark.parametrize('T,N,n_pad,ld,W,Hp,H', CASES)
 def test_kernel_parity(T, N, n_pad, ld, W, Hp, H, ragged):
-    rs = np.random.RandomState(T + W)
-    p = np.zeros((T, n_pad, ld), np.float32)
-    p[:, :N, :W] = rs.randn(T, N, W) * 1.5 + rs.randn(W) * 0.5
-    p[:, N:, :] = rs.randn(T, n_pad - N, ld)       # junk in padding rows / columns: ignored
-    p[:, :N, W:] = rs.randn(T, N, ld - W)
-    if W >= 3:
-        p[:, :N, 1] = 1e3 + 0.1 * rs.randn(T, N)    # stability: |mean| 1e3, std 0.1
-        p[:, :N, 2] = 0.25                          # a constant column: var 0
-    gamma, beta = rs.rand(W) + 0.5, rs.randn(W) * 0.3
-    gamma[0] = 0.0                                  # xhat comes from p, never from y
-    pad = np.zeros(W, bool)
-    if Hp is not None:      # pad columns of a GRU slab: p = 0 (zero weight columns), gamma = beta = 0
-        pad = (np.arange(W) % Hp) >= H
-        p[:, :N, :W][..., pad] = 0.0
-        gamma[pad] = 0.0
-        beta[pad] = 0.0
-    da = rs.randn(T, n_pad, ld).astype(np.float32)  # non-zero on padded frames and pads
-    lens = _ragged(rs, T, N) if ragged else (None if T % 2 else np.full(N, T))
-    rm, rv = rs.randn(W), rs.rand(W) + 0.5
+    p, gamma, beta, da, lens, rm, rv, pad = seqbn_inputs(T, N, n_pad, ld, W, Hp, H, ragged)
     y, stats, dp, dg, db, yi, mom, mx = _run_kernels(p, N, W, lens, gamma, beta, da, rm, rv)
     pr = p[:, :N, :W].astype(np.float64)
     yw, c = SO.seqbn_forward(pr, gamma, beta, lens, 1e-3)
