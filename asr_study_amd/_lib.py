@@ -143,6 +143,15 @@ class AttnArgs(C.Structure):
                 ('dout', void_p), ('dqkv', void_p)]
 
 
+class RelAttnArgs(C.Structure):
+    _fields_ = [('T', C.c_int), ('N', C.c_int), ('n_pad', C.c_int), ('heads', C.c_int),
+                ('dh', C.c_int), ('ld', C.c_int), ('ld_out', C.c_int), ('ld_pos', C.c_int),
+                ('scale', C.c_float),
+                ('qkv', void_p), ('lens', void_p), ('out', void_p), ('lse', void_p),
+                ('dout', void_p), ('dqkv', void_p), ('pos', void_p), ('bias_u', void_p),
+                ('bias_v', void_p), ('dpos', void_p), ('dbias_u', void_p), ('dbias_v', void_p)]
+
+
 class Segment(C.Structure):
     _fields_ = [('offset', C.c_int64), ('len', C.c_int64), ('l2', C.c_float),
                 ('reserved', C.c_float)]
@@ -284,6 +293,11 @@ SIGNATURES = {
     'asr_attn_bwd': (C.c_int, [C.POINTER(AttnArgs), void_p, C.c_size_t, void_p]),
     'asr_attn_plan': (C.c_int, [C.POINTER(AttnArgs), C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
     'asr_posenc_add': (C.c_int, [void_p] * 3 + [C.c_int] * 5 + [void_p]),
+    'asr_relattn_workspace_bytes': (C.c_size_t, [C.POINTER(RelAttnArgs)]),
+    'asr_relattn_fwd': (C.c_int, [C.POINTER(RelAttnArgs), void_p]),
+    'asr_relattn_bwd': (C.c_int, [C.POINTER(RelAttnArgs), void_p, C.c_size_t, void_p]),
+    'asr_relattn_plan': (C.c_int, [C.POINTER(RelAttnArgs), C.c_int, c_int_p, c_int_p, c_int_p,
+                                   c_int_p]),
     'asr_dwconv1d_workspace_bytes': (C.c_size_t, [C.c_int] * 6),
     'asr_dwconv1d_plan': (C.c_int, [C.c_int] * 7 + [c_int_p] * 3),
     'asr_dwconv1d_fwd': (C.c_int, [void_p] * 5 + [C.c_int] * 6 + [void_p]),

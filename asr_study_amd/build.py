@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libasr_hip.so')
 SOURCES = ['capi.cpp', 'ctc.hip', 'beam.hip', 'frontend.hip', 'conv.hip', 'gemm.hip', 'lstm.hip', 'lstm_fwd.hip', 'lstm_bwd.hip', 'lstm_ln.hip', 'rnn.hip',
-           'batchnorm.hip', 'gru.hip', 'rhn.hip', 'layernorm.hip', 'attention.hip', 'dwconv.hip',
+           'batchnorm.hip', 'gru.hip', 'rhn.hip', 'layernorm.hip', 'attention.hip', 'rel_attention.hip', 'dwconv.hip',
            'specaug.hip', 'optim.hip', 'random.hip', 'decode_host.cpp', 'comm.cpp', 'roles.cpp']
 ARCH = 'gfx950'
 
@@ -25,6 +25,7 @@ def _deps():
         os.path.join(CSRC, 'lstm_common.h'),
         os.path.join(CSRC, 'rec_tile.h'),
         os.path.join(CSRC, 'vec4.h'),
+        os.path.join(CSRC, 'attn_tile.h'),
         os.path.join(CSRC, 'philox.h'),
         os.path.join(os.path.dirname(HERE), 'include', 'asr_hip.h')]
 

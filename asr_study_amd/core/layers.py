@@ -19,6 +19,8 @@ bare or on the (N, T, F, C) image of the convolution front-end (csrc/batchnorm.h
 frame over its features on csrc/layernorm.hip.
 ``MultiHeadAttention`` and ``PositionalEncoding`` (no reference counterpart) run on
 csrc/attention.hip and make the ``transformer`` factory.
+``RelativeMultiHeadAttention`` (relative sinusoidal positions inside the scores) runs on
+csrc/rel_attention.hip; ``positions='relative'`` of transformer / conformer uses it.
 ``DepthwiseConvolution1D``, ``GLU``, ``Activation('swish')`` and ``merge(..., scale=)`` (no
 reference counterpart either) run on csrc/dwconv.hip and make the ``conformer`` factory.
 ``SpecAugment`` (no reference counterpart) augments the input slab on csrc/specaug.hip; the
@@ -525,7 +527,8 @@ class MultiHeadAttention(Layer):
     Weights: W_qkv, b_qkv, W_o, b_o, in that order; W_regularizer (l2) applies to both matrices.
     head_dim defaults to features / num_heads, output_dim to the input width.  head_dim must be a
     multiple of 16 in 16 .. 128 (the kernel's tile).  Not built: dropout on the probabilities
-    (use Dropout behind the layer), causal masks, relative positions, cross-attention."""
+    (use Dropout behind the layer), causal masks, cross-attention.  Relative positions are
+    RelativeMultiHeadAttention."""
 
     def __init__(self, num_heads, head_dim=None, output_dim=None, W_regularizer=None,
                  attention_dropout=0., **kwargs):
@@ -565,6 +568,45 @@ class MultiHeadAttention(Layer):
 
     def out_features(self, f):
         return self.output_dim
+
+
+class RelativeMultiHeadAttention(MultiHeadAttention):
+    """Multi-head self-attention with the relative sinusoidal positions of Transformer-XL
+    (arXiv 1901.02860 section 3.3), as the Conformer uses it (arXiv 2005.08100 section 2.1), on
+    csrc/rel_attention.hip.  For an (N, T, F) input, D = num_heads * head_dim:
+
+        [Q | K | V] = x W_qkv + b_qkv
+        pe[r, 2i] = sin(r 10000^(-2i / D)), pe[r, 2i + 1] = cos(r 10000^(-2i / D)),
+                    r = -(T - 1) .. T - 1;   Pos = pe W_pos   (D, D), no bias
+        s[t, u] = ((q_t + pos_bias_u[h]) . k_u + (q_t + pos_bias_v[h]) . pos_{t - u}) / sqrt(dh)
+        y = concat_h(softmax_u(s) V_h) W_o + b_o
+
+    The relative index is t - u, query frame minus key frame.  Everything else is
+    MultiHeadAttention's: every frame is a query, only keys are masked by the utterance lengths.
+    No PositionalEncoding layer is needed in front.  Weights: W_qkv, b_qkv, W_pos, pos_bias_u,
+    pos_bias_v (num_heads, head_dim), W_o, b_o, in that order; W_regularizer (l2) applies to the
+    three matrices.  head_dim must be a multiple of 16 in 16 .. 64 (the kernels stage a band of
+    Pos rows beside the tiles of MultiHeadAttention, which leaves no LDS for more).  Not built:
+    dropout on the probabilities, causal masks, cross-attention, learned relative tables."""
+
+    MAX_HEAD_DIM = 64
+
+    def __init__(self, num_heads, head_dim=None, output_dim=None, W_regularizer=None, **kwargs):
+        if kwargs:
+            raise NotImplementedError('RelativeMultiHeadAttention: unknown arguments %s'
+                                      % sorted(kwargs))
+        MultiHeadAttention.__init__(self, num_heads, head_dim=head_dim, output_dim=output_dim,
+                                    W_regularizer=W_regularizer)
+
+    @staticmethod
+    def _check_dh(dh):
+        if int(dh) != dh or dh < 16 or dh > RelativeMultiHeadAttention.MAX_HEAD_DIM or \
+                int(dh) % 16:
+            raise NotImplementedError('RelativeMultiHeadAttention: head_dim %r is not implemented '
+                                      '(a multiple of 16 in 16 .. %d: the limit of the '
+                                      'asr_relattn_* kernels, whose band tiles fill the LDS)'
+                                      % (dh, RelativeMultiHeadAttention.MAX_HEAD_DIM))
+        return int(dh)
 
 
 class PositionalEncoding(Layer):

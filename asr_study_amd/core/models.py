@@ -18,8 +18,8 @@ from .engine import Model
 from .layers import (Input, GaussianNoise, TimeDistributed, Dense, LSTM, Bidirectional,
                      Dropout, Merge, merge, l2, Reshape, Convolution2D, clipped_relu, SimpleRNN,
                      Activation, BatchNormalization, GRU, RHN, LayerNormalization,
-                     MultiHeadAttention, PositionalEncoding, DepthwiseConvolution1D, GLU,
-                     SpecAugment)
+                     MultiHeadAttention, RelativeMultiHeadAttention, PositionalEncoding,
+                     DepthwiseConvolution1D, GLU, SpecAugment)
 
 
 def ctc_model(inputs, output, **kwargs):
@@ -69,6 +69,8 @@ def ctc_model(inputs, output, **kwargs):
         elif isinstance(layer, MultiHeadAttention):
             spec.append({'type': 'mha', 'heads': layer.num_heads, 'dh': layer.head_dim,
                          'n_out': layer.output_dim, 'l2': layer.l2})
+            if isinstance(layer, RelativeMultiHeadAttention):   # (only then: as for merge)
+                spec[-1]['relative'] = True
         elif isinstance(layer, PositionalEncoding):
             spec.append({'type': 'posenc'})
         elif isinstance(layer, DepthwiseConvolution1D):
@@ -142,6 +144,19 @@ def _record_spec_augment(model, spec_augment):
     if spec_augment is not False and spec_augment is not None:
         model.config['kwargs']['spec_augment'] = (True if spec_augment is True
                                                   else dict(spec_augment))
+
+
+def _attention_layer(factory, positions):
+    """The ``positions`` argument of a factory: the attention layer class of its blocks."""
+    if positions not in ('absolute', 'relative'):
+        raise ValueError("%s(positions=%r): 'absolute' or 'relative'" % (factory, positions))
+    return RelativeMultiHeadAttention if positions == 'relative' else MultiHeadAttention
+
+
+def _record_positions(model, positions):
+    """... recorded in the factory record only when not the default, like spec_augment."""
+    if positions != 'absolute':
+        model.config['kwargs']['positions'] = positions
 
 
 def graves2006(num_features=26, num_hiddens=100, num_classes=28, std=.6, **kw):
@@ -382,7 +397,8 @@ def rhn(num_features=39, num_classes=28, num_hiddens=256, num_layers=5, depth=2,
 
 def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_layers=6,
                 d_ff=1024, dropout=0.1, conv=True, conv_filters=32,
-                conv_kernels=((11, 41), (11, 21)), weight_decay=0., spec_augment=False, **kw):
+                conv_kernels=((11, 41), (11, 21)), weight_decay=0., spec_augment=False,
+                positions='absolute', **kw):
     """A CTC-trained pre-LN transformer encoder (arXiv 1706.03762, 2002.04745).  NO REFERENCE
     COUNTERPART.  conv=True: deep_speech2's front-end first -- Reshape, two Convolution2D with
     clipped ReLU (strides (2, 2) and (1, 2): time stride 2), Reshape.  Then
@@ -393,7 +409,9 @@ def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_l
 
     a final LayerNormalization and TimeDistributed(Dense(num_classes)).  The attention keys of an
     utterance are its valid frames (the strided lengths).  weight_decay: l2 on every matrix.
-    spec_augment=True (or a dict of its arguments): a SpecAugment layer directly behind Input."""
+    spec_augment=True (or a dict of its arguments): a SpecAugment layer directly behind Input.
+    positions='relative': RelativeMultiHeadAttention in every block and no PositionalEncoding."""
+    attention = _attention_layer('transformer', positions)
     reg = l2(weight_decay)
     x = Input(name='inputs', shape=(None, num_features))
     o = _spec_augment(x, spec_augment)
@@ -404,11 +422,12 @@ def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_l
                               activation=clipped_relu(20), W_regularizer=reg)(o)
         o = Reshape((-1, o.features))(o)
     o = TimeDistributed(Dense(d_model, W_regularizer=reg))(o)
-    o = PositionalEncoding()(o)
+    if positions == 'absolute':
+        o = PositionalEncoding()(o)
     o = Dropout(dropout)(o)
     for _ in range(num_layers):
         y = LayerNormalization()(o)
-        y = MultiHeadAttention(num_heads, W_regularizer=reg)(y)
+        y = attention(num_heads, W_regularizer=reg)(y)
         o = merge([Dropout(dropout)(y), o], mode='sum')
         y = LayerNormalization()(o)
         y = TimeDistributed(Dense(d_ff, W_regularizer=reg))(y)
@@ -424,13 +443,14 @@ def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_l
         conv_filters=conv_filters, conv_kernels=[list(k) for k in conv_kernels],
         weight_decay=weight_decay)}
     _record_spec_augment(model, spec_augment)
+    _record_positions(model, positions)
     return model
 
 
 def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_layers=6,
               d_ff=1024, kernel_size=31, conv_norm='batch', dropout=0.1, conv=True,
               conv_filters=32, conv_kernels=((11, 41), (11, 21)), weight_decay=0.,
-              spec_augment=False, **kw):
+              spec_augment=False, positions='absolute', **kw):
     """A CTC-trained Conformer encoder (arXiv 2005.08100).  NO REFERENCE COUNTERPART.  The
     front-end and input projection of ``transformer`` (conv=True: deep_speech2's two strided
     Convolution2D; then TimeDistributed(Dense(d_model)), PositionalEncoding, Dropout), then
@@ -446,13 +466,16 @@ def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_lay
     and TimeDistributed(Dense(num_classes)).  conv_norm: 'batch' (the paper: BatchNormalization,
     with this library's semantics: training statistics over every frame of the real samples, time
     padding included) or 'layer' (LayerNormalization).  The attention keys and the depthwise
-    convolution's input of an utterance are its valid frames (the strided lengths).  Positions
-    are the absolute sinusoidal table: the paper's relative positional attention is not built.
+    convolution's input of an utterance are its valid frames (the strided lengths).  positions:
+    'absolute' (the sinusoidal table added once, PositionalEncoding) or 'relative' (the paper's
+    relative positional attention: RelativeMultiHeadAttention in every block and no
+    PositionalEncoding layer).
     weight_decay: l2 on every matrix and depthwise filter.  spec_augment=True (or a dict of its
     arguments): a SpecAugment layer directly behind Input; its defaults are the paper's policy
     (section 3.2) without the time warp."""
     if conv_norm not in ('batch', 'layer'):
         raise ValueError("conformer(conv_norm=%r): 'batch' or 'layer'" % (conv_norm,))
+    attention = _attention_layer('conformer', positions)
     reg = l2(weight_decay)
     x = Input(name='inputs', shape=(None, num_features))
     o = _spec_augment(x, spec_augment)
@@ -463,7 +486,8 @@ def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_lay
                               activation=clipped_relu(20), W_regularizer=reg)(o)
         o = Reshape((-1, o.features))(o)
     o = TimeDistributed(Dense(d_model, W_regularizer=reg))(o)
-    o = PositionalEncoding()(o)
+    if positions == 'absolute':
+        o = PositionalEncoding()(o)
     o = Dropout(dropout)(o)
 
     def ffn(o):
@@ -476,7 +500,7 @@ def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_lay
     for _ in range(num_layers):
         o = ffn(o)
         y = LayerNormalization()(o)
-        y = MultiHeadAttention(num_heads, W_regularizer=reg)(y)
+        y = attention(num_heads, W_regularizer=reg)(y)
         o = merge([Dropout(dropout)(y), o], mode='sum')
         y = LayerNormalization()(o)
         y = TimeDistributed(Dense(2 * d_model, W_regularizer=reg))(y)
@@ -496,4 +520,5 @@ def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_lay
         conv_norm=conv_norm, dropout=dropout, conv=conv, conv_filters=conv_filters,
         conv_kernels=[list(k) for k in conv_kernels], weight_decay=weight_decay)}
     _record_spec_augment(model, spec_augment)
+    _record_positions(model, positions)
     return model

@@ -143,6 +143,7 @@ def keras_names(stages):
     groups = {'convolution2d': 'convolution2d', 'batchnormalization': 'batchnormalization',
               'layernormalization': 'layernormalization',
               'multiheadattention': 'multiheadattention',
+              'relativemultiheadattention': 'relativemultiheadattention',
               'depthwiseconvolution1d': 'depthwiseconvolution1d', 'dense': 'timedistributed'}
     out, n = [], Counter()
     for s in stages:
@@ -326,6 +327,28 @@ def mha(s, alloc, rows):
     return [Tensor(layer, 'W_qkv', (F, 3 * D), s.oW, (s.f_in_pad, 3 * D), (rows,), l2=s.l2,
                    init=('uniform', lim)),
             Tensor(layer, 'b_qkv', (3 * D,), s.ob, (3 * D,), ()),
+            Tensor(layer, 'W_o', (D, s.n_out), s.oWo, (D, s.n_out), (), l2=s.l2,
+                   init=_glorot(D, s.n_out)),
+            Tensor(layer, 'b_o', (s.n_out,), s.obo, (s.n_out,), ())]
+
+
+def relmha(s, alloc, rows):
+    """RelativeMultiHeadAttention (csrc/rel_attention.hip): mha's W_qkv, b_qkv, then W_pos (D, D),
+    the projection of the relative sinusoidal table (no bias), pos_bias_u and pos_bias_v
+    (heads, dh), then W_o, b_o.  W_pos and the two position biases are glorot-uniform over their
+    own shapes; l2 on the three matrices."""
+    F, D, layer = len(rows), s.D, 'relativemultiheadattention'
+    lim = math.sqrt(6.0 / (F + D))
+    s.oW, s.ob = alloc.take(s.f_in_pad * 3 * D), alloc.take(3 * D)
+    s.oWp, s.obu, s.obv = alloc.take(D * D), alloc.take(D), alloc.take(D)
+    s.oWo, s.obo = alloc.take(D * s.n_out), alloc.take(s.n_out)
+    hd = (s.heads, s.dh)
+    return [Tensor(layer, 'W_qkv', (F, 3 * D), s.oW, (s.f_in_pad, 3 * D), (rows,), l2=s.l2,
+                   init=('uniform', lim)),
+            Tensor(layer, 'b_qkv', (3 * D,), s.ob, (3 * D,), ()),
+            Tensor(layer, 'W_pos', (D, D), s.oWp, (D, D), (), l2=s.l2, init=_glorot(D, D)),
+            Tensor(layer, 'pos_bias_u', hd, s.obu, hd, (), init=_glorot(*hd)),
+            Tensor(layer, 'pos_bias_v', hd, s.obv, hd, (), init=_glorot(*hd)),
             Tensor(layer, 'W_o', (D, s.n_out), s.oWo, (D, s.n_out), (), l2=s.l2,
                    init=_glorot(D, s.n_out)),
             Tensor(layer, 'b_o', (s.n_out,), s.obo, (s.n_out,), ())]

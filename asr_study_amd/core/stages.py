@@ -461,6 +461,8 @@ def _mha_build(m, s, st, width):
     # the fused attention core, the output projection
     s.heads, s.dh = int(st['heads']), int(st['dh'])
     s.D, s.n_out, s.l2 = s.heads * s.dh, int(st['n_out']), float(st.get('l2', 0.0))
+    if st.get('relative'):          # (only then: the stages of every other model are unchanged)
+        return _relmha_build(m, s, st, width)
     if s.heads < 1 or s.dh % 16 or not 16 <= s.dh <= 128:
         raise NotImplementedError(
             'MultiHeadAttention: head_dim %d (a multiple of 16 in 16 .. 128: the tile '
@@ -473,6 +475,8 @@ def _mha_forward(m, s, si, a, rec, fp):
     """MultiHeadAttention stage: qkv = a W_qkv + b_qkv (one GEMM), the fused attention core
     over each utterance's valid keys (seq_len: device lengths on this time axis; None: every
     frame), the output projection.  The row log-sum-exp is kept only for a backward pass."""
+    if getattr(s, 'relative', False):
+        return _relmha_forward(m, s, si, a, rec, fp)
     a = a.contiguous()
     T, n_pad, _ = a.shape
     rows, D, N = T * n_pad, s.D, min(fp.n_real, n_pad)
@@ -492,7 +496,8 @@ def _mha_forward(m, s, si, a, rec, fp):
 
 def _mha_backward(m, s, si, rec, da, bp):
     """The two projections' wgrad / colsum / dgrad GEMMs around asr_attn_bwd; returns dx, or
-    None for the first trainable stage."""
+    None for the first trainable stage.  The relative variant: asr_relattn_bwd in its place,
+    which also writes dpos and the two position-bias gradients; dW_pos = pe^T dpos."""
     a_in = rec['in'].contiguous()
     split = bp.split
     T, n_pad, _ = a_in.shape
@@ -506,8 +511,18 @@ def _mha_backward(m, s, si, rec, da, bp):
     ops.gemm(da, m.params, dctx, rows, D, s.n_out, trans_b=True, b_off=s.oWo,
              a_absmax=gmx)
     dqkv = m._buf('dqkv%d' % si, (T, n_pad, 3 * D))
-    ops.attn_bwd(rec['qkv'], rec['ctx'], rec['lse'], dctx, dqkv, rec['N'], s.heads, s.dh,
-                 lens=rec['lens'])
+    if getattr(s, 'relative', False):
+        dpos = m._buf('drelpos%d' % si, (2 * T - 1, D))
+        ops.relattn_bwd(rec['qkv'], rec['pos'], m._view(s.obu, D), m._view(s.obv, D),
+                        rec['ctx'], rec['lse'], dctx, dqkv, dpos, m._gview(s.obu, D),
+                        m._gview(s.obv, D), rec['N'], s.heads, s.dh, lens=rec['lens'])
+        # dW_pos = pe^T dpos with the constant 1 taken off the cosine columns (sum_r dpos_r = 0:
+        # ops.relpos_grad_table), in exact fp32: the table's small entries are below fp16's range
+        ops.gemm(ops.relpos_get(T, D, dpos.device, grad=True), dpos, m.grads, D, D, 2 * T - 1,
+                 trans_a=True, c_off=s.oWp, split_k=split, precision=0)
+    else:
+        ops.attn_bwd(rec['qkv'], rec['ctx'], rec['lse'], dctx, dqkv, rec['N'], s.heads, s.dh,
+                     lens=rec['lens'])
     qmx = ops.absmax(dqkv, m._buf('dqkvmax%d' % si, (1,)))
     ops.gemm(a_in, dqkv, m.grads, s.f_in_pad, 3 * D, rows, trans_a=True, c_off=s.oW,
              split_k=split, b_absmax=qmx)
@@ -523,6 +538,43 @@ def _mha_backward(m, s, si, rec, da, bp):
     ops.gemm(dqkv, m.params, dx, rows, s.f_in_pad, 3 * D, trans_b=True, b_off=s.oW,
              a_absmax=qmx)
     return dx
+
+
+def _relmha_build(m, s, st, width):
+    # the relative variant of the mha kind (K24, csrc/rel_attention.hip): RelativeMultiHeadAttention
+    s.relative = True
+    if s.heads < 1 or s.dh % 16 or not 16 <= s.dh <= ops.RELATTN_MAX_HEAD_DIM:
+        raise NotImplementedError(
+            'RelativeMultiHeadAttention: head_dim %d (a multiple of 16 in 16 .. %d: the band '
+            'tiles of the asr_relattn_* kernels leave no LDS for more), %d heads'
+            % (s.dh, ops.RELATTN_MAX_HEAD_DIM, s.heads))
+    s.tensors = P.relmha(s, m._alloc, m._real_rows(s))
+    return s.n_out, s.n_out
+
+
+def _relmha_forward(m, s, si, a, rec, fp):
+    """RelativeMultiHeadAttention stage: the qkv GEMM, Pos = pe W_pos (the (2T - 1, D) relative
+    table: it does not depend on the batch, one GEMM per forward pass of the stage), the fused
+    relative attention core, the output projection."""
+    a = a.contiguous()
+    T, n_pad, _ = a.shape
+    rows, D, N = T * n_pad, s.D, min(fp.n_real, n_pad)
+    qkv = m._buf('qkv%d' % si, (T, n_pad, 3 * D))
+    ops.gemm(a, m.params, qkv, rows, 3 * D, s.f_in_pad, b_off=s.oW,
+             bias=m._view(s.ob, 3 * D))
+    pe = ops.relpos_get(T, D, a.device)
+    pos = m._buf('relpos%d' % si, (2 * T - 1, D))
+    ops.gemm(pe, m.params, pos, 2 * T - 1, D, D, b_off=s.oWp, precision=0)    # (exact fp32)
+    ctx = m._buf('attn%d' % si, (T, n_pad, D))
+    lse = m._buf('lse%d' % si, (ops.attn_lse_len(T, n_pad, s.heads),)) if fp.need_grad \
+        else None
+    ops.relattn_fwd(qkv, pos, m._view(s.obu, D), m._view(s.obv, D), ctx, N, s.heads, s.dh,
+                    lens=fp.seq_len, lse=lse)
+    out = m._buf('mha%d' % si, (T, n_pad, s.n_out))
+    ops.gemm(ctx, m.params, out, rows, s.n_out, D, b_off=s.oWo,
+             bias=m._view(s.obo, s.n_out))
+    rec.update(qkv=qkv, ctx=ctx, lse=lse, N=N, lens=fp.seq_len, pos=pos)
+    return out
 
 
 # --------------------------------------------------------------------------- bilstm

@@ -679,6 +679,110 @@ def posenc_add(x, y, N, D, pe=None):
     return y
 
 
+# --------------------------------------------------------------------------- relative attention (K24)
+RELATTN_MAX_HEAD_DIM = 64     # of asr_relattn_*: the band tiles leave no LDS for dh 80 .. 128
+
+
+def relpos_table(T, D):
+    """The (2T - 1, D) relative sinusoidal table in float64 (host): row r + T - 1 holds
+    pe[r, 2i] = sin(r / 10000^(2i / D)), pe[r, 2i + 1] = cos(r / 10000^(2i / D)) for the relative
+    index r = -(T - 1) .. T - 1 (query frame minus key frame)."""
+    r = np.arange(-(int(T) - 1), int(T), dtype=np.float64)[:, None]
+    i2 = (np.arange(int(D)) // 2 * 2).astype(np.float64)[None, :]
+    ang = r * np.power(10000.0, -i2 / float(D))
+    return np.where(np.arange(int(D))[None, :] % 2 == 0, np.sin(ang), np.cos(ang))
+
+
+def relpos_grad_table(T, D):
+    """The fp32 table with 1 taken off its cosine columns (float32): what dW_pos = pe^T dpos is
+    computed with.  The rows of dS sum to zero, so sum_r dpos_r = 0 and a constant column of pe has
+    no gradient: (pe - 1)^T dpos is the same matrix, without the cancellation that would leave
+    rounding noise in the rows of the slow cosines (true size ~ (r / 10000)^2 of the others),
+    which Adam would normalise into steps of +-lr.  The 1 comes off the ROUNDED cosines, the ones
+    the forward pass multiplies with (an exact fp32 difference for cos x >= 1 / 2, the slow
+    columns), not off the float64 ones: where cos x - 1 is below 1e-7, the rounding of cos x is
+    most of what the forward pass sees of it."""
+    pe = relpos_table(T, D).astype(np.float32)
+    pe[:, 1::2] -= np.float32(1.0)
+    return pe
+
+
+_RPE = {}
+
+
+def relpos_get(T, D, device, grad=False):
+    """The table (grad: relpos_grad_table) rounded once to fp32 on the device, computed and
+    uploaded once per (T, D)."""
+    key = (int(T), int(D), str(device), bool(grad))
+    pe = _RPE.get(key)
+    if pe is None:
+        if len(_RPE) >= 64:
+            _RPE.clear()
+        table = (relpos_grad_table if grad else relpos_table)(T, D)
+        pe = _RPE[key] = torch.from_numpy(table.astype(np.float32)).to(device)
+    return pe
+
+
+def _relattn_args(qkv, N, heads, dh, ld_out, ld_pos, scale=None, **tensors):
+    T, n_pad, ld = qkv.shape
+    a = L.RelAttnArgs()
+    a.T, a.N, a.n_pad, a.heads, a.dh = int(T), int(N), int(n_pad), int(heads), int(dh)
+    a.ld, a.ld_out, a.ld_pos = int(ld), int(ld_out), int(ld_pos)
+    a.scale = float(scale if scale is not None else 1.0 / math.sqrt(dh))
+    a.qkv = qkv.data_ptr()
+    for k, t in tensors.items():
+        setattr(a, k, None if t is None else t.data_ptr())
+    return a
+
+
+def relattn_plan(T, n_pad, heads, dh, backward=False):
+    """{'bq', 'bk': query / key tile lengths, 'blocks': workgroups of a launch, 'lds': bytes of LDS
+    per workgroup (backward: of the largest pass)} of the geometry (asr_relattn_plan)."""
+    a = L.RelAttnArgs()
+    a.T, a.N, a.n_pad, a.heads, a.dh = int(T), 1, int(n_pad), int(heads), int(dh)
+    a.ld, a.ld_out, a.scale = 3 * int(heads) * int(dh), int(heads) * int(dh), 1.0
+    a.ld_pos = a.ld_out
+    v = [C.c_int(0) for _ in range(4)]
+    L.check(L.load().asr_relattn_plan(C.byref(a), int(bool(backward)), *[C.byref(x) for x in v]),
+            'asr_relattn_plan')
+    return dict(zip(('bq', 'bk', 'blocks', 'lds'), (x.value for x in v)))
+
+
+def relattn_fwd(qkv, pos, bias_u, bias_v, out, N, heads, dh, lens=None, lse=None, scale=None):
+    """out (T, n_pad, ld_out >= heads dh) of the relative positional attention core on the slab
+    qkv (T, n_pad, ld >= 3 heads dh) = [Q | K | V]: s[t, u] = scale ((q_t + bias_u) . k_u +
+    (q_t + bias_v) . pos[t - u + T - 1]) over the keys u < lens[n]; pos (2T - 1, ld_pos >= heads
+    dh) is the projected table, bias_u / bias_v (heads dh); lse kept for relattn_bwd when given."""
+    _check_f32(qkv, pos, bias_u, bias_v, out, lse)
+    _check_lens(lens, N)
+    assert qkv.dim() == 3 and out.dim() == 3 and out.shape[:2] == qkv.shape[:2]
+    assert pos.dim() == 2 and pos.shape[0] == 2 * qkv.shape[0] - 1 and pos.is_contiguous()
+    a = _relattn_args(qkv, N, heads, dh, out.shape[2], pos.shape[1], scale, lens=lens, out=out,
+                      lse=lse, pos=pos, bias_u=bias_u, bias_v=bias_v)
+    L.check(L.load().asr_relattn_fwd(C.byref(a), _stream()), 'asr_relattn_fwd')
+    return out
+
+
+def relattn_bwd(qkv, pos, bias_u, bias_v, out, lse, dout, dqkv, dpos, dbias_u, dbias_v, N, heads,
+                dh, lens=None, scale=None):
+    """dqkv (like qkv) = dQ | dK | dV, dpos (like pos), dbias_u, dbias_v (heads dh) from dout (like
+    out), recomputing p from lse; all four are written, not accumulated."""
+    _check_f32(qkv, pos, bias_u, bias_v, out, lse, dout, dqkv, dpos, dbias_u, dbias_v)
+    _check_lens(lens, N)
+    assert dqkv.shape == qkv.shape and dout.shape == out.shape and dpos.shape == pos.shape
+    assert pos.is_contiguous() and dpos.is_contiguous()
+    a = _relattn_args(qkv, N, heads, dh, out.shape[2], pos.shape[1], scale, lens=lens, out=out,
+                      lse=lse, dout=dout, dqkv=dqkv, pos=pos, bias_u=bias_u, bias_v=bias_v,
+                      dpos=dpos, dbias_u=dbias_u, dbias_v=dbias_v)
+    nbytes = L.load().asr_relattn_workspace_bytes(C.byref(a))
+    if nbytes == 0:
+        L.check(-1, 'asr_relattn_workspace_bytes (T %d N %d n_pad %d heads %d dh %d ld %d ld_out '
+                '%d ld_pos %d)' % (a.T, a.N, a.n_pad, a.heads, a.dh, a.ld, a.ld_out, a.ld_pos))
+    ws = WS.get('relattn', nbytes, qkv.device)
+    L.check(L.load().asr_relattn_bwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_relattn_bwd')
+    return dqkv
+
+
 # --------------------------------------------------------------------------- dwconv, GLU, Swish (K22)
 DWCONV_MAX_KERNEL = 63    # taps of asr_dwconv1d_* (odd, 'same' padding)
 

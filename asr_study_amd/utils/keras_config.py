@@ -221,6 +221,12 @@ def model_config(model):
             add('LayerNormalization', name, {
                 'name': name, 'trainable': True, 'epsilon': float(s.eps), 'gain_init': 'one',
                 'bias_init': 'zero'}, [prev])
+        elif s.kind == 'mha' and getattr(s, 'relative', False):
+            name = nm('relativemultiheadattention')
+            add('RelativeMultiHeadAttention', name, {
+                'name': name, 'trainable': True, 'num_heads': int(s.heads),
+                'head_dim': int(s.dh), 'output_dim': int(s.n_out),
+                'W_regularizer': _regularizer(s.l2)}, [prev])
         elif s.kind == 'mha':
             name = nm('multiheadattention')
             add('MultiHeadAttention', name, {
@@ -379,6 +385,10 @@ def topology_from_config(text):
                                      output_dim=c.get('output_dim'),
                                      W_regularizer=reg(c.get('W_regularizer')),
                                      attention_dropout=c.get('attention_dropout', 0.))(o)
+        elif kind == 'RelativeMultiHeadAttention':
+            o = L.RelativeMultiHeadAttention(c['num_heads'], head_dim=c.get('head_dim'),
+                                             output_dim=c.get('output_dim'),
+                                             W_regularizer=reg(c.get('W_regularizer')))(o)
         elif kind == 'PositionalEncoding':
             o = L.PositionalEncoding()(o)
         elif kind == 'DepthwiseConvolution1D':

@@ -753,6 +753,65 @@ int asr_posenc_add(const float* x, const float* pe, float* y, int T, int N, int 
                    int ld, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
+/* K24 relative positional self-attention core, fused, forward and backward  */
+/* (arXiv 1901.02860 3.3 as used by arXiv 2005.08100 2.1;                    */
+/* csrc/rel_attention.hip).  qkv, lens, out, lse, dout, dqkv and every       */
+/* convention of K21 carry over.  pos is the projected relative table        */
+/* (2T - 1, ld_pos >= D): row r + T - 1 holds pos_r, where the RELATIVE      */
+/* INDEX is r = t - u, QUERY FRAME MINUS KEY FRAME (positive when the key    */
+/* lies in the past), r = -(T - 1) .. T - 1; head h reads columns            */
+/* h dh .. (h + 1) dh - 1.  bias_u, bias_v (D each): the position biases.    */
+/*   s[t,u] = scale ((q_t + b_u) . k_u + (q_t + b_v) . pos_{t-u}), u < len_n */
+/*   p = softmax_u(s),  out_t = sum_u p[t,u] v_u,  lse_t = log sum_u exp s   */
+/* Backward, dS = P (.) (dO V^T - D_t):                                      */
+/*   dq_t = scale sum_u dS[t,u] (k_u + pos_{t-u})                            */
+/*   dk_u = scale sum_t dS[t,u] (q_t + b_u),  dv = P^T dO                    */
+/*   dbias_u = scale sum_{n,t,u} dS[t,u] k_u                                 */
+/*   dbias_v = scale sum_{n,t,u} dS[t,u] pos_{t-u}                           */
+/*   dpos_r  = scale sum_n sum_{t-u=r, u<len_n} dS[t,u] (q_t + b_v)          */
+/* dqkv, dpos, dbias_u, dbias_v are sums over all real samples and all T     */
+/* query frames, WRITTEN, not accumulated; dpos rows that no valid (t, u)    */
+/* pair reaches and its pad columns are exact zeros.  Neither the T x T      */
+/* scores nor a T x (2T - 1) intermediate reaches memory.  No float atomics: */
+/* per-sample partials of dpos and the two parts of dQ go through the        */
+/* workspace and are added in a fixed order (asr_colsum).                    */
+/* dh a multiple of 16 in 16 .. 64: the band of pos rows a tile pair needs   */
+/* takes two more LDS tiles, with which dh 80 .. 128 does not fit the 160 KB */
+/* of a CU in the backward passes; it is refused (ASR_ERR_INVALID), like any */
+/* other invalid geometry, before anything touches a device.                 */
+/* A new struct and new entry points only: the ABI version stays.            */
+/* ------------------------------------------------------------------------ */
+typedef struct asr_relattn_args {
+  int T, N, n_pad;       /* frames, real samples, padded samples per frame               */
+  int heads, dh;         /* D = heads * dh                                               */
+  int ld, ld_out;        /* floats per (t, n) row of qkv / dqkv and of out / dout        */
+  int ld_pos;            /* floats per row of pos / dpos, >= D, a multiple of 4          */
+  float scale;           /* of the scores, usually 1 / sqrt(dh)                          */
+  const float* qkv;      /* (T, n_pad, ld)                                               */
+  const int* lens;       /* optional device int32 (N), clamped to 1 .. T                 */
+  float* out;            /* (T, n_pad, ld_out)                                           */
+  float* lse;            /* (T, n_pad, heads)                                            */
+  const float* dout;     /* backward: (T, n_pad, ld_out)                                 */
+  float* dqkv;           /* backward: (T, n_pad, ld), dQ | dK | dV                       */
+  const float* pos;      /* (2T - 1, ld_pos), 16-byte aligned                            */
+  const float* bias_u;   /* (D)                                                          */
+  const float* bias_v;   /* (D)                                                          */
+  float* dpos;           /* backward: (2T - 1, ld_pos), contiguous                       */
+  float* dbias_u;        /* backward: (D)                                                */
+  float* dbias_v;        /* backward: (D)                                                */
+} asr_relattn_args;
+/* Workspace of asr_relattn_bwd (D of every row, the two dQ slabs, the per-sample partials    */
+/* of dpos, the column-sum partials); 0 for a geometry that is refused.                       */
+size_t asr_relattn_workspace_bytes(const asr_relattn_args* a);
+int asr_relattn_fwd(const asr_relattn_args* a, asr_stream_t stream);
+int asr_relattn_bwd(const asr_relattn_args* a, void* workspace, size_t ws_bytes,
+                    asr_stream_t stream);
+/* Tile lengths, workgroups of the forward (or dQ / dK dV) launch and LDS bytes per workgroup */
+/* (backward: of the largest of its three passes); any pointer may be NULL.                   */
+int asr_relattn_plan(const asr_relattn_args* a, int backward, int* bq, int* bk, int* blocks,
+                     int* lds_bytes);
+
+/* ------------------------------------------------------------------------ */
 /* K22 depthwise 1-D convolution over the time axis of a time-major slab     */
 /* (T, n_pad, ld >= C), and the element-wise pairs of a Conformer block      */
 /* (arXiv 2005.08100; csrc/dwconv.hip).  Cross-correlation, 'same' padding,  */
