@@ -152,6 +152,11 @@ class RelAttnArgs(C.Structure):
                 ('bias_v', void_p), ('dpos', void_p), ('dbias_u', void_p), ('dbias_v', void_p)]
 
 
+class AttnWindow(C.Structure):
+    # asr_attn_window (K25): chunk >= 1, left >= -1 (-1: unlimited), right >= 0, in frames
+    _fields_ = [('chunk', C.c_int), ('left', C.c_int), ('right', C.c_int)]
+
+
 class Segment(C.Structure):
     _fields_ = [('offset', C.c_int64), ('len', C.c_int64), ('l2', C.c_float),
                 ('reserved', C.c_float)]
@@ -292,16 +297,29 @@ SIGNATURES = {
     'asr_attn_fwd': (C.c_int, [C.POINTER(AttnArgs), void_p]),
     'asr_attn_bwd': (C.c_int, [C.POINTER(AttnArgs), void_p, C.c_size_t, void_p]),
     'asr_attn_plan': (C.c_int, [C.POINTER(AttnArgs), C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
+    'asr_attn_win_fwd': (C.c_int, [C.POINTER(AttnArgs), C.POINTER(AttnWindow), void_p]),
+    'asr_attn_win_bwd': (C.c_int, [C.POINTER(AttnArgs), C.POINTER(AttnWindow), void_p,
+                                   C.c_size_t, void_p]),
+    'asr_attn_win_plan': (C.c_int, [C.POINTER(AttnArgs), C.POINTER(AttnWindow), C.c_int, c_int_p,
+                                    c_int_p, c_int_p, c_int_p, C.POINTER(C.c_longlong)]),
     'asr_posenc_add': (C.c_int, [void_p] * 3 + [C.c_int] * 5 + [void_p]),
     'asr_relattn_workspace_bytes': (C.c_size_t, [C.POINTER(RelAttnArgs)]),
     'asr_relattn_fwd': (C.c_int, [C.POINTER(RelAttnArgs), void_p]),
     'asr_relattn_bwd': (C.c_int, [C.POINTER(RelAttnArgs), void_p, C.c_size_t, void_p]),
     'asr_relattn_plan': (C.c_int, [C.POINTER(RelAttnArgs), C.c_int, c_int_p, c_int_p, c_int_p,
                                    c_int_p]),
+    'asr_relattn_win_fwd': (C.c_int, [C.POINTER(RelAttnArgs), C.POINTER(AttnWindow), void_p]),
+    'asr_relattn_win_bwd': (C.c_int, [C.POINTER(RelAttnArgs), C.POINTER(AttnWindow), void_p,
+                                      C.c_size_t, void_p]),
+    'asr_relattn_win_plan': (C.c_int, [C.POINTER(RelAttnArgs), C.POINTER(AttnWindow), C.c_int,
+                                       c_int_p, c_int_p, c_int_p, c_int_p,
+                                       C.POINTER(C.c_longlong)]),
     'asr_dwconv1d_workspace_bytes': (C.c_size_t, [C.c_int] * 6),
     'asr_dwconv1d_plan': (C.c_int, [C.c_int] * 7 + [c_int_p] * 3),
     'asr_dwconv1d_fwd': (C.c_int, [void_p] * 5 + [C.c_int] * 6 + [void_p]),
     'asr_dwconv1d_bwd': (C.c_int, [void_p] * 7 + [C.c_int] * 6 + [void_p, C.c_size_t, void_p]),
+    'asr_dwconv1d_pad_fwd': (C.c_int, [void_p] * 5 + [C.c_int] * 7 + [void_p]),
+    'asr_dwconv1d_pad_bwd': (C.c_int, [void_p] * 7 + [C.c_int] * 7 + [void_p, C.c_size_t, void_p]),
     'asr_glu_fwd': (C.c_int, [void_p] * 2 + [C.c_int64] + [C.c_int] * 3 + [void_p]),
     'asr_glu_bwd': (C.c_int, [void_p] * 3 + [C.c_int64] + [C.c_int] * 3 + [void_p]),
     'asr_swish_fwd': (C.c_int, [void_p] * 2 + [C.c_int64, void_p]),

@@ -526,12 +526,25 @@ class MultiHeadAttention(Layer):
     this library); only keys are masked, by the utterance lengths the model is called with.
     Weights: W_qkv, b_qkv, W_o, b_o, in that order; W_regularizer (l2) applies to both matrices.
     head_dim defaults to features / num_heads, output_dim to the input width.  head_dim must be a
-    multiple of 16 in 16 .. 128 (the kernel's tile).  Not built: dropout on the probabilities
-    (use Dropout behind the layer), causal masks, cross-attention.  Relative positions are
-    RelativeMultiHeadAttention."""
+    multiple of 16 in 16 .. 128 (the kernel's tile).
+
+    context: None (the whole utterance), 'causal' (= (1, -1, 0)) or a (chunk, left, right) window
+    in frames, chunk >= 1, left >= -1 (-1: unlimited), right >= 0.  For query frame t, with
+    c0 = (t // chunk) * chunk, key u is visible iff lo(t) <= u < hi(t) and u is a valid frame,
+
+        hi(t) = c0 + chunk + right        lo(t) = 0 if left < 0 else max(0, c0 - left)
+
+    chunk 1, right 0 is the causal mask (a finite left: a sliding window); chunk 1, right R a
+    symmetric window; chunk C chunk-wise attention, whose look-ahead of chunk - 1 + right frames
+    per layer does not grow with the number of layers when right = 0.  A time-padding query that sees no
+    valid key (lo(t) at or past the utterance's length) gives a zero attention output and passes
+    no gradient.  The kernels visit only the 64 x 64 tiles that hold a visible pair.
+
+    Not built: dropout on the probabilities (use Dropout behind the layer), cross-attention,
+    cached chunk-by-chunk inference.  Relative positions are RelativeMultiHeadAttention."""
 
     def __init__(self, num_heads, head_dim=None, output_dim=None, W_regularizer=None,
-                 attention_dropout=0., **kwargs):
+                 attention_dropout=0., context=None, **kwargs):
         if kwargs:
             raise NotImplementedError('MultiHeadAttention: unknown arguments %s' % sorted(kwargs))
         if attention_dropout:
@@ -546,6 +559,31 @@ class MultiHeadAttention(Layer):
         self.output_dim = None if output_dim is None else int(output_dim)
         self.l2 = W_regularizer.l2 if W_regularizer is not None else 0.0
         self.attention_dropout = 0.0
+        self.context = self._check_context(context)
+
+    @classmethod
+    def _check_context(cls, context):
+        """None, or the (chunk, left, right) triple of ``context``."""
+        if context is None:
+            return None
+        if isinstance(context, str):
+            if context != 'causal':
+                raise NotImplementedError("%s(context=%r): None, 'causal' or (chunk, left, right)"
+                                          % (cls.__name__, context))
+            return (1, -1, 0)
+        try:
+            w = tuple(context)
+            ok = len(w) == 3 and all(not isinstance(v, bool) and int(v) == v for v in w)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise NotImplementedError("%s(context=%r): None, 'causal' or three integers (chunk, "
+                                      'left, right)' % (cls.__name__, context))
+        w = tuple(int(v) for v in w)
+        if w[0] < 1 or w[1] < -1 or w[2] < 0:
+            raise ValueError('%s(context=%r): chunk >= 1, left >= -1 (-1: unlimited), right >= 0'
+                             % (cls.__name__, context))
+        return w
 
     @staticmethod
     def _check_dh(dh):
@@ -586,17 +624,21 @@ class RelativeMultiHeadAttention(MultiHeadAttention):
     No PositionalEncoding layer is needed in front.  Weights: W_qkv, b_qkv, W_pos, pos_bias_u,
     pos_bias_v (num_heads, head_dim), W_o, b_o, in that order; W_regularizer (l2) applies to the
     three matrices.  head_dim must be a multiple of 16 in 16 .. 64 (the kernels stage a band of
-    Pos rows beside the tiles of MultiHeadAttention, which leaves no LDS for more).  Not built:
-    dropout on the probabilities, causal masks, cross-attention, learned relative tables."""
+    Pos rows beside the tiles of MultiHeadAttention, which leaves no LDS for more).  context:
+    MultiHeadAttention's window (None, 'causal' or (chunk, left, right)); the positions a row uses
+    are then the relative indices -(chunk - 1 + right) .. left + chunk - 1 only.  Not built:
+    dropout on the probabilities, cross-attention, learned relative tables, cached chunk-by-chunk
+    inference."""
 
     MAX_HEAD_DIM = 64
 
-    def __init__(self, num_heads, head_dim=None, output_dim=None, W_regularizer=None, **kwargs):
+    def __init__(self, num_heads, head_dim=None, output_dim=None, W_regularizer=None,
+                 context=None, **kwargs):
         if kwargs:
             raise NotImplementedError('RelativeMultiHeadAttention: unknown arguments %s'
                                       % sorted(kwargs))
         MultiHeadAttention.__init__(self, num_heads, head_dim=head_dim, output_dim=output_dim,
-                                    W_regularizer=W_regularizer)
+                                    W_regularizer=W_regularizer, context=context)
 
     @staticmethod
     def _check_dh(dh):
@@ -633,11 +675,16 @@ class DepthwiseConvolution1D(Layer):
     W_regularizer (l2) applies to W.  kernel_size is odd, in 1 .. 63; the input width is a
     multiple of 4.  Straight in front of a BatchNormalization the bias has no effect on the
     training output (the batch mean takes it out); its gradient is then exactly zero and b keeps
-    its value.  Not built: strides, dilation, a depth multiplier, causal padding."""
+    its value.  causal=True pads k - 1 frames on the left and none on the right,
+
+        y[t, c] = b[c] + sum_j W[j, c] x[t + j - (k - 1), c]
+
+    so that no output frame reads a later input frame.  Not built: strides, dilation, a depth
+    multiplier."""
 
     MAX_KERNEL = 63
 
-    def __init__(self, kernel_size, W_regularizer=None, **kwargs):
+    def __init__(self, kernel_size, W_regularizer=None, causal=False, **kwargs):
         if kwargs:
             raise NotImplementedError('DepthwiseConvolution1D: unknown arguments %s'
                                       % sorted(kwargs))
@@ -646,8 +693,12 @@ class DepthwiseConvolution1D(Layer):
             raise NotImplementedError('DepthwiseConvolution1D: kernel_size %r (an odd integer in '
                                       "1 .. %d: 'same' padding, the tile of asr_dwconv1d_*)"
                                       % (kernel_size, self.MAX_KERNEL))
+        if not isinstance(causal, (bool, int)) or causal not in (0, 1):
+            raise NotImplementedError('DepthwiseConvolution1D(causal=%r): True or False'
+                                      % (causal,))
         self.kernel_size = int(kernel_size)
         self.l2 = W_regularizer.l2 if W_regularizer is not None else 0.0
+        self.causal = bool(causal)
 
     def __call__(self, x):
         if x.features % 4:

@@ -71,10 +71,14 @@ def ctc_model(inputs, output, **kwargs):
                          'n_out': layer.output_dim, 'l2': layer.l2})
             if isinstance(layer, RelativeMultiHeadAttention):   # (only then: as for merge)
                 spec[-1]['relative'] = True
+            if layer.context is not None:
+                spec[-1]['context'] = list(layer.context)
         elif isinstance(layer, PositionalEncoding):
             spec.append({'type': 'posenc'})
         elif isinstance(layer, DepthwiseConvolution1D):
             spec.append({'type': 'dwconv', 'k': layer.kernel_size, 'l2': layer.l2})
+            if layer.causal:
+                spec[-1]['causal'] = True
         elif isinstance(layer, GLU):
             spec.append({'type': 'glu'})
         elif isinstance(layer, TimeDistributed) and layer.dense is None:
@@ -157,6 +161,15 @@ def _record_positions(model, positions):
     """... recorded in the factory record only when not the default, like spec_augment."""
     if positions != 'absolute':
         model.config['kwargs']['positions'] = positions
+
+
+def _record_context(model, context, causal_conv=False):
+    """... and so are the attention window (as the layer normalised it: a list of three integers)
+    and the causal convolution."""
+    if context is not None:
+        model.config['kwargs']['context'] = list(MultiHeadAttention._check_context(context))
+    if causal_conv:
+        model.config['kwargs']['causal_conv'] = True
 
 
 def graves2006(num_features=26, num_hiddens=100, num_classes=28, std=.6, **kw):
@@ -398,7 +411,7 @@ def rhn(num_features=39, num_classes=28, num_hiddens=256, num_layers=5, depth=2,
 def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_layers=6,
                 d_ff=1024, dropout=0.1, conv=True, conv_filters=32,
                 conv_kernels=((11, 41), (11, 21)), weight_decay=0., spec_augment=False,
-                positions='absolute', **kw):
+                positions='absolute', context=None, **kw):
     """A CTC-trained pre-LN transformer encoder (arXiv 1706.03762, 2002.04745).  NO REFERENCE
     COUNTERPART.  conv=True: deep_speech2's front-end first -- Reshape, two Convolution2D with
     clipped ReLU (strides (2, 2) and (1, 2): time stride 2), Reshape.  Then
@@ -410,7 +423,19 @@ def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_l
     a final LayerNormalization and TimeDistributed(Dense(num_classes)).  The attention keys of an
     utterance are its valid frames (the strided lengths).  weight_decay: l2 on every matrix.
     spec_augment=True (or a dict of its arguments): a SpecAugment layer directly behind Input.
-    positions='relative': RelativeMultiHeadAttention in every block and no PositionalEncoding."""
+    positions='relative': RelativeMultiHeadAttention in every block and no PositionalEncoding.
+    context: None, 'causal' or a (chunk, left, right) window in strided frames, the ``context`` of
+    MultiHeadAttention, given to every block: an encoder with a bounded look-ahead.  A block looks
+    chunk - 1 + right frames ahead; with right = 0 that is the look-ahead of the whole stack,
+    chunk - 1, not multiplied by the depth (every layer stays inside the chunk); with a non-zero
+    right the blocks add up, num_layers * right for chunk = 1 and at most num_layers * (chunk - 1
+    + right) otherwise (a frame seen past the chunk brings its own chunk along).  conv=True adds the fixed look-ahead of the two
+    'same'-padded Convolution2D: the first reads kt1 - 1 - p1 input frames past input frame 2 t,
+    p1 = (kt1 - 1) // 2 for an odd and (kt1 - 2) // 2 for an even number of input frames
+    (TensorFlow's 'same' rule at stride 2), the second (kt2 - 1) // 2 strided frames; a strided
+    frame t with an encoder look-ahead of A strided frames reads the input frames up to
+    2 (t + A + (kt2 - 1) // 2) + kt1 - 1 - p1, which is 2 (t + A) + 16 with the default kernels
+    and an even number of input frames."""
     attention = _attention_layer('transformer', positions)
     reg = l2(weight_decay)
     x = Input(name='inputs', shape=(None, num_features))
@@ -427,7 +452,7 @@ def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_l
     o = Dropout(dropout)(o)
     for _ in range(num_layers):
         y = LayerNormalization()(o)
-        y = attention(num_heads, W_regularizer=reg)(y)
+        y = attention(num_heads, W_regularizer=reg, context=context)(y)
         o = merge([Dropout(dropout)(y), o], mode='sum')
         y = LayerNormalization()(o)
         y = TimeDistributed(Dense(d_ff, W_regularizer=reg))(y)
@@ -444,13 +469,14 @@ def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_l
         weight_decay=weight_decay)}
     _record_spec_augment(model, spec_augment)
     _record_positions(model, positions)
+    _record_context(model, context)
     return model
 
 
 def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_layers=6,
               d_ff=1024, kernel_size=31, conv_norm='batch', dropout=0.1, conv=True,
               conv_filters=32, conv_kernels=((11, 41), (11, 21)), weight_decay=0.,
-              spec_augment=False, positions='absolute', **kw):
+              spec_augment=False, positions='absolute', context=None, causal_conv=False, **kw):
     """A CTC-trained Conformer encoder (arXiv 2005.08100).  NO REFERENCE COUNTERPART.  The
     front-end and input projection of ``transformer`` (conv=True: deep_speech2's two strided
     Convolution2D; then TimeDistributed(Dense(d_model)), PositionalEncoding, Dropout), then
@@ -472,7 +498,18 @@ def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_lay
     PositionalEncoding layer).
     weight_decay: l2 on every matrix and depthwise filter.  spec_augment=True (or a dict of its
     arguments): a SpecAugment layer directly behind Input; its defaults are the paper's policy
-    (section 3.2) without the time warp."""
+    (section 3.2) without the time warp.
+    context: None, 'causal' or a (chunk, left, right) window in strided frames, the ``context`` of
+    the attention layer, given to every block; causal_conv=True: DepthwiseConvolution1D(causal=
+    True) in every block.  Together they bound the look-ahead of the encoder, in strided frames:
+    chunk - 1 when right = 0 (not multiplied by the depth: every layer stays inside the chunk);
+    with a non-zero right the blocks add up (num_layers * right for chunk = 1, at most num_layers
+    * (chunk - 1 + right) otherwise); plus (kernel_size - 1) / 2 per convolution module that is
+    not causal; plus, with conv=True, the fixed look-ahead of the two
+    'same'-padded Convolution2D of the front-end as ``transformer`` states it: with an encoder
+    look-ahead of A strided frames the strided frame t reads the input frames up to
+    2 (t + A + (kt2 - 1) // 2) + kt1 - 1 - p1.  With conv_norm='batch' the bound holds at inference only: the training statistics
+    run over all frames."""
     if conv_norm not in ('batch', 'layer'):
         raise ValueError("conformer(conv_norm=%r): 'batch' or 'layer'" % (conv_norm,))
     attention = _attention_layer('conformer', positions)
@@ -500,12 +537,12 @@ def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_lay
     for _ in range(num_layers):
         o = ffn(o)
         y = LayerNormalization()(o)
-        y = attention(num_heads, W_regularizer=reg)(y)
+        y = attention(num_heads, W_regularizer=reg, context=context)(y)
         o = merge([Dropout(dropout)(y), o], mode='sum')
         y = LayerNormalization()(o)
         y = TimeDistributed(Dense(2 * d_model, W_regularizer=reg))(y)
         y = GLU()(y)
-        y = DepthwiseConvolution1D(kernel_size, W_regularizer=reg)(y)
+        y = DepthwiseConvolution1D(kernel_size, W_regularizer=reg, causal=causal_conv)(y)
         y = BatchNormalization()(y) if conv_norm == 'batch' else LayerNormalization()(y)
         y = Activation('swish')(y)
         y = TimeDistributed(Dense(d_model, W_regularizer=reg))(y)
@@ -521,4 +558,5 @@ def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_lay
         conv_kernels=[list(k) for k in conv_kernels], weight_decay=weight_decay)}
     _record_spec_augment(model, spec_augment)
     _record_positions(model, positions)
+    _record_context(model, context, causal_conv)
     return model

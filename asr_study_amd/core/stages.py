@@ -325,6 +325,8 @@ def _dwconv_build(m, s, st, width):
         raise NotImplementedError(
             'DepthwiseConvolution1D over %d channels (%d columns): the width must be '
             'a multiple of 4 without pad columns' % (f_real, f_pad))
+    if st.get('causal'):            # (only then: the stages of every other model are unchanged)
+        s.pad_left = s.k - 1        # the causal left padding, in place of the 'same' (k - 1) / 2
     s.tensors = P.dwconv(s, m._alloc, None)
     return width
 
@@ -332,10 +334,12 @@ def _dwconv_build(m, s, st, width):
 def _dwconv_forward(m, s, si, a, rec, fp):
     N = min(fp.n_real, fp.n_pad)
     a = a.contiguous()
-    rec.update(**{'in': a, 'N': N, 'lens': fp.seq_len})
+    # (the keyword only when set: the calls of every other model are what they were)
+    pad = {'pad_left': s.pad_left} if hasattr(s, 'pad_left') else {}
+    rec.update(**{'in': a, 'N': N, 'lens': fp.seq_len, 'pad': pad})
     out = m._buf('dwconv%d' % si, a.shape)
     return ops.dwconv1d_fwd(a, m._view(s.oW, s.k * s.C), m._view(s.ob, s.C), out,
-                            N, s.k, lens=fp.seq_len)
+                            N, s.k, lens=fp.seq_len, **pad)
 
 
 def _dwconv_backward(m, s, si, rec, da, bp):
@@ -345,7 +349,8 @@ def _dwconv_backward(m, s, si, rec, da, bp):
     ops.dwconv1d_bwd(a_in, m._view(s.oW, s.k * s.C), da.contiguous(), dx,
                      m._gview(s.oW, s.k * s.C),
                      m._buf('dwdb%d' % si, (s.C,)) if s.bias_dead
-                     else m._gview(s.ob, s.C), rec['N'], s.k, lens=rec['lens'])
+                     else m._gview(s.ob, s.C), rec['N'], s.k, lens=rec['lens'],
+                     **rec['pad'])
     return dx
 
 
@@ -461,6 +466,8 @@ def _mha_build(m, s, st, width):
     # the fused attention core, the output projection
     s.heads, s.dh = int(st['heads']), int(st['dh'])
     s.D, s.n_out, s.l2 = s.heads * s.dh, int(st['n_out']), float(st.get('l2', 0.0))
+    if st.get('context') is not None:       # (only then, like relative below)
+        s.window = _mha_window(st['context'])   # (chunk, left, right) of K25, csrc/attn_tile.h
     if st.get('relative'):          # (only then: the stages of every other model are unchanged)
         return _relmha_build(m, s, st, width)
     if s.heads < 1 or s.dh % 16 or not 16 <= s.dh <= 128:
@@ -469,6 +476,14 @@ def _mha_build(m, s, st, width):
             'of the asr_attn_* kernels), %d heads' % (s.dh, s.heads))
     s.tensors = P.mha(s, m._alloc, m._real_rows(s))
     return s.n_out, s.n_out
+
+
+def _mha_window(context):
+    w = tuple(int(v) for v in context)
+    if len(w) != 3 or w[0] < 1 or w[1] < -1 or w[2] < 0:
+        raise ValueError('MultiHeadAttention: context %r ([chunk >= 1, left >= -1 (-1: unlimited), '
+                         'right >= 0] in frames)' % (context,))
+    return w
 
 
 def _mha_forward(m, s, si, a, rec, fp):
@@ -480,17 +495,19 @@ def _mha_forward(m, s, si, a, rec, fp):
     a = a.contiguous()
     T, n_pad, _ = a.shape
     rows, D, N = T * n_pad, s.D, min(fp.n_real, n_pad)
+    # (the keyword only when set: the calls of every other model are what they were)
+    win = {'window': s.window} if hasattr(s, 'window') else {}
     qkv = m._buf('qkv%d' % si, (T, n_pad, 3 * D))
     ops.gemm(a, m.params, qkv, rows, 3 * D, s.f_in_pad, b_off=s.oW,
              bias=m._view(s.ob, 3 * D))
     ctx = m._buf('attn%d' % si, (T, n_pad, D))
     lse = m._buf('lse%d' % si, (ops.attn_lse_len(T, n_pad, s.heads),)) if fp.need_grad \
         else None
-    ops.attn_fwd(qkv, ctx, N, s.heads, s.dh, lens=fp.seq_len, lse=lse)
+    ops.attn_fwd(qkv, ctx, N, s.heads, s.dh, lens=fp.seq_len, lse=lse, **win)
     out = m._buf('mha%d' % si, (T, n_pad, s.n_out))
     ops.gemm(ctx, m.params, out, rows, s.n_out, D, b_off=s.oWo,
              bias=m._view(s.obo, s.n_out))
-    rec.update(qkv=qkv, ctx=ctx, lse=lse, N=N, lens=fp.seq_len)
+    rec.update(qkv=qkv, ctx=ctx, lse=lse, N=N, lens=fp.seq_len, win=win)
     return out
 
 
@@ -515,14 +532,15 @@ def _mha_backward(m, s, si, rec, da, bp):
         dpos = m._buf('drelpos%d' % si, (2 * T - 1, D))
         ops.relattn_bwd(rec['qkv'], rec['pos'], m._view(s.obu, D), m._view(s.obv, D),
                         rec['ctx'], rec['lse'], dctx, dqkv, dpos, m._gview(s.obu, D),
-                        m._gview(s.obv, D), rec['N'], s.heads, s.dh, lens=rec['lens'])
+                        m._gview(s.obv, D), rec['N'], s.heads, s.dh, lens=rec['lens'],
+                        **rec['win'])
         # dW_pos = pe^T dpos with the constant 1 taken off the cosine columns (sum_r dpos_r = 0:
         # ops.relpos_grad_table), in exact fp32: the table's small entries are below fp16's range
         ops.gemm(ops.relpos_get(T, D, dpos.device, grad=True), dpos, m.grads, D, D, 2 * T - 1,
                  trans_a=True, c_off=s.oWp, split_k=split, precision=0)
     else:
         ops.attn_bwd(rec['qkv'], rec['ctx'], rec['lse'], dctx, dqkv, rec['N'], s.heads, s.dh,
-                     lens=rec['lens'])
+                     lens=rec['lens'], **rec['win'])
     qmx = ops.absmax(dqkv, m._buf('dqkvmax%d' % si, (1,)))
     ops.gemm(a_in, dqkv, m.grads, s.f_in_pad, 3 * D, rows, trans_a=True, c_off=s.oW,
              split_k=split, b_absmax=qmx)
@@ -559,6 +577,8 @@ def _relmha_forward(m, s, si, a, rec, fp):
     a = a.contiguous()
     T, n_pad, _ = a.shape
     rows, D, N = T * n_pad, s.D, min(fp.n_real, n_pad)
+    # (the keyword only when set: the calls of every other model are what they were)
+    win = {'window': s.window} if hasattr(s, 'window') else {}
     qkv = m._buf('qkv%d' % si, (T, n_pad, 3 * D))
     ops.gemm(a, m.params, qkv, rows, 3 * D, s.f_in_pad, b_off=s.oW,
              bias=m._view(s.ob, 3 * D))
@@ -569,11 +589,11 @@ def _relmha_forward(m, s, si, a, rec, fp):
     lse = m._buf('lse%d' % si, (ops.attn_lse_len(T, n_pad, s.heads),)) if fp.need_grad \
         else None
     ops.relattn_fwd(qkv, pos, m._view(s.obu, D), m._view(s.obv, D), ctx, N, s.heads, s.dh,
-                    lens=fp.seq_len, lse=lse)
+                    lens=fp.seq_len, lse=lse, **win)
     out = m._buf('mha%d' % si, (T, n_pad, s.n_out))
     ops.gemm(ctx, m.params, out, rows, s.n_out, D, b_off=s.oWo,
              bias=m._view(s.obo, s.n_out))
-    rec.update(qkv=qkv, ctx=ctx, lse=lse, N=N, lens=fp.seq_len, pos=pos)
+    rec.update(qkv=qkv, ctx=ctx, lse=lse, N=N, lens=fp.seq_len, pos=pos, win=win)
     return out
 
 

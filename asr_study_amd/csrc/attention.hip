@@ -30,6 +30,19 @@
 // order: no float atomics, repeats are bit-identical.  No workgroup waits on another one.
 // The tile pieces (loads, the two products, the butterflies) are in attn_tile.h, which
 // rel_attention.hip shares.
+//
+// K25, THE WINDOW (asr_attn_win_*; defined once in attn_tile.h): chunk >= 1, left >= -1 frames
+// (-1: unlimited), right >= 0 frames.  For query frame t, c0 = (t / chunk) * chunk, key u is
+// visible iff lo(t) <= u < hi(t) and u < lens[n], hi(t) = c0 + chunk + right, lo(t) = left < 0 ?
+// 0 : max(0, c0 - left).  The kernels are templates on a bool: without the window they are the
+// code above, bit for bit.  With it the mask stays a select (a key outside meets p = exactly 0
+// only) and the loops visit only the tiles that hold a visible pair:
+//   forward, dQ: the key tiles that meet [lo(q0), min(hi(last query of the tile), len));
+//   dK / dV:     the query tiles with lo(first) <= k0 + 63 and hi(last) > k0 (lo, hi monotone:
+//                one contiguous range; a key tile no query sees writes exact zeros).
+// A row with NO visible key (a padding query with lo(t) >= len) has out = lse = exactly 0: the
+// forward guards exp2f(-inf - -inf) and the division by l = 0; the backward recomputes p = 0 for
+// it everywhere, so dQ_t = 0 and it adds nothing to dK, dV.
 #include "attn_tile.h"
 
 namespace {
@@ -40,11 +53,14 @@ struct AtGeo {
   float scale;
 };
 
-template <int DH>
+// WIN: under the window w of attn_tile.h (K25); without it w is not read and the code is the
+// unwindowed kernel's, instruction for instruction.
+template <int DH, bool WIN>
 __global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(const float* __restrict__ qkv,
                                                               const int* __restrict__ lens,
                                                               float* __restrict__ out,
-                                                              float* __restrict__ lse, AtGeo g) {
+                                                              float* __restrict__ lse, AtGeo g,
+                                                              asr_attn_window w) {
   constexpr int DP = DH + 4, NJ = DH / 16;
   extern __shared__ float4 at_lds4[];
   float* Qs = reinterpret_cast<float*>(at_lds4);
@@ -72,7 +88,16 @@ __global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(const float* __res
 #pragma unroll
     for (int jj = 0; jj < NJ; ++jj) o[i][jj] = 0.f;
   }
-  for (int k0 = 0; k0 < len; k0 += AT_TILE) {
+  int kb = 0, ke = len, wlo[4], whi[4];     // key tiles to visit; the visible keys of row i
+  if constexpr (WIN) {
+    at_win_keys(w, q0, g.T, len, &kb, &ke);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      wlo[i] = at_win_lo(w, q0 + 4 * ty + i);
+      whi[i] = min(at_win_hi(w, q0 + 4 * ty + i), len);
+    }
+  }
+  for (int k0 = kb; k0 < ke; k0 += AT_TILE) {
     at_load_tile<DH>(Ks, base + D, rs, k0, len, tid);
     at_load_tile<DH>(Vs, base + 2 * D, rs, k0, len, tid);
     __syncthreads();
@@ -83,15 +108,23 @@ __global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(const float* __res
       float mx = asr_neg_inf();
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        s[i][j] = (k0 + tx + 16 * j < len) ? s[i][j] * g.c2 : asr_neg_inf();
+        const int u = k0 + tx + 16 * j;
+        bool vis = u < len;
+        if constexpr (WIN) vis = u >= wlo[i] && u < whi[i];
+        s[i][j] = vis ? s[i][j] * g.c2 : asr_neg_inf();
         mx = fmaxf(mx, s[i][j]);
       }
-      mx = fmaxf(m[i], at_max16(mx));       // finite: key k0 of every tile is a valid one
-      const float alpha = exp2f(m[i] - mx);
+      // without a window finite: key k0 of every tile is a valid one.  Under a window a row may
+      // have seen no key yet (m, mx both -inf): exp2f(-inf - -inf) is NaN, so subtract 0 then --
+      // alpha = 0 scales sums that are 0, every p = exp2f(-inf) = 0, l stays 0
+      mx = fmaxf(m[i], at_max16(mx));
+      float mref = mx;
+      if constexpr (WIN) mref = mx == asr_neg_inf() ? 0.f : mx;
+      const float alpha = exp2f(m[i] - mref);
       float sum = 0.f;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        s[i][j] = exp2f(s[i][j] - mx);
+        s[i][j] = exp2f(s[i][j] - mref);
         sum += s[i][j];
       }
       l[i] = fmaf(l[i], alpha, at_sum16(sum));
@@ -110,18 +143,25 @@ __global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(const float* __res
     if (t >= g.T) continue;
     float* orow = o_base + (size_t)t * rso + h * DH;
 #pragma unroll
-    for (int jj = 0; jj < NJ; ++jj) orow[tx + 16 * jj] = o[i][jj] / l[i];
-    if (lse != nullptr && tx == 0)
-      lse[((size_t)t * g.n_pad + n) * g.heads + h] = (m[i] + log2f(l[i])) * AT_LN2;
+    for (int jj = 0; jj < NJ; ++jj) {
+      float v = o[i][jj] / l[i];
+      if constexpr (WIN) v = l[i] == 0.f ? 0.f : v;      // a row with no visible key: out = lse = 0
+      orow[tx + 16 * jj] = v;
+    }
+    if (lse != nullptr && tx == 0) {
+      float v = (m[i] + log2f(l[i])) * AT_LN2;
+      if constexpr (WIN) v = l[i] == 0.f ? 0.f : v;
+      lse[((size_t)t * g.n_pad + n) * g.heads + h] = v;
+    }
   }
 }
 
 // backward pass 1: D = dout . out (to dvec, laid out like lse) and dQ, per query tile
-template <int DH>
+template <int DH, bool WIN>
 __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(
     const float* __restrict__ qkv, const int* __restrict__ lens, const float* __restrict__ out,
     const float* __restrict__ lse, const float* __restrict__ dout, float* __restrict__ dqkv,
-    float* __restrict__ dvec, AtGeo g) {
+    float* __restrict__ dvec, AtGeo g, asr_attn_window w) {
   constexpr int DP = DH + 4, NJ = DH / 16;
   extern __shared__ float4 at_lds4[];
   float* Qs = reinterpret_cast<float*>(at_lds4);
@@ -162,7 +202,16 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(
 #pragma unroll
     for (int jj = 0; jj < NJ; ++jj) dq[i][jj] = 0.f;
   }
-  for (int k0 = 0; k0 < len; k0 += AT_TILE) {
+  int kb = 0, ke = len, wlo[4], whi[4];     // as in the forward pass
+  if constexpr (WIN) {
+    at_win_keys(w, q0, g.T, len, &kb, &ke);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      wlo[i] = at_win_lo(w, q0 + 4 * ty + i);
+      whi[i] = min(at_win_hi(w, q0 + 4 * ty + i), len);
+    }
+  }
+  for (int k0 = kb; k0 < ke; k0 += AT_TILE) {
     at_load_tile<DH>(Ks, base + D, rs, k0, len, tid);
     at_load_tile<DH>(Vs, base + 2 * D, rs, k0, len, tid);
     __syncthreads();
@@ -173,7 +222,10 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float p = (k0 + tx + 16 * j < len) ? exp2f(fmaf(s[i][j], g.c2, -lse2[i])) : 0.f;
+        const int u = k0 + tx + 16 * j;
+        bool vis = u < len;
+        if constexpr (WIN) vis = u >= wlo[i] && u < whi[i];
+        const float p = vis ? exp2f(fmaf(s[i][j], g.c2, -lse2[i])) : 0.f;
         s[i][j] = p * (dp[i][j] - dsum[i]) * g.scale;
       }
     at_put_tile(Ps, s, ty, tx);
@@ -192,11 +244,11 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(
 }
 
 // backward pass 2: dK and dV of one key tile over all query tiles (query tiles ascending)
-template <int DH>
+template <int DH, bool WIN>
 __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dkv_kernel(
     const float* __restrict__ qkv, const int* __restrict__ lens, const float* __restrict__ lse,
     const float* __restrict__ dout, float* __restrict__ dqkv, const float* __restrict__ dvec,
-    AtGeo g) {
+    AtGeo g, asr_attn_window w) {
   constexpr int DP = DH + 4, NJ = DH / 16;
   extern __shared__ float4 at_lds4[];
   float* Ks = reinterpret_cast<float*>(at_lds4);
@@ -228,6 +280,17 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dkv_kernel(
 #pragma unroll
     for (int jj = 0; jj < NJ; ++jj) dk[i][jj] = dv[i][jj] = 0.f;
   for (int q0 = 0; q0 < g.T; q0 += AT_TILE) {
+    int qlo[4], qhi[4];                     // the visible keys of query tx + 16 j
+    if constexpr (WIN) {
+      // only the query tiles that see a key of this tile: one contiguous range, lo and hi being
+      // monotone (a tile no query sees accumulates nothing: exact zeros)
+      if (!at_win_pair(w, q0, min(q0 + AT_TILE, g.T) - 1, k0)) continue;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        qlo[j] = at_win_lo(w, q0 + tx + 16 * j);
+        qhi[j] = at_win_hi(w, q0 + tx + 16 * j);
+      }
+    }
     at_load_tile<DH>(Qs, base, rs, q0, g.T, tid);
     at_load_tile<DH>(Gs, do_base, rso, q0, g.T, tid);
     if (tid < AT_TILE) {
@@ -245,7 +308,8 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dkv_kernel(
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int q = tx + 16 * j;
-        const bool live = (k0 + 4 * ty + i < len) && (q0 + q < g.T);
+        bool live = (k0 + 4 * ty + i < len) && (q0 + q < g.T);
+        if constexpr (WIN) live = live && k0 + 4 * ty + i >= qlo[j] && k0 + 4 * ty + i < qhi[j];
         s[i][j] = live ? exp2f(fmaf(s[i][j], g.c2, -Ls[q])) : 0.f;
         dp[i][j] = s[i][j] * (dp[i][j] - Ds[q]) * g.scale;
       }
@@ -336,7 +400,19 @@ extern "C" int asr_attn_plan(const asr_attn_args* a, int backward, int* bq, int*
   return ASR_OK;
 }
 
-extern "C" int asr_attn_fwd(const asr_attn_args* a, asr_stream_t stream) {
+#define AT_WIN_TEXT "chunk >= 1, left >= -1 (-1: unlimited), right >= 0"
+
+extern "C" int asr_attn_win_plan(const asr_attn_args* a, const asr_attn_window* w, int backward,
+                                 int* bq, int* bk, int* blocks, int* lds_bytes,
+                                 long long* tile_pairs) {
+  ASR_CHECK_ARG(at_win_ok(w), "attn_win_plan: bad window (" AT_WIN_TEXT ")");
+  const int rc = asr_attn_plan(a, backward, bq, bk, blocks, lds_bytes);
+  if (rc == ASR_OK && tile_pairs) *tile_pairs = at_win_tile_pairs(*w, a->T);
+  return rc;
+}
+
+// w == nullptr: the unwindowed kernels
+static int at_fwd(const asr_attn_args* a, const asr_attn_window* w, asr_stream_t stream) {
   ASR_CHECK_ARG(at_geo_ok(a), "attn_fwd: bad geometry (T %d N %d n_pad %d heads %d dh %d ld %d "
                 "ld_out %d; dh a multiple of 16 in 16..128, ld >= 3 heads dh, ld_out >= heads dh, "
                 "both multiples of 4)", a ? a->T : 0, a ? a->N : 0, a ? a->n_pad : 0,
@@ -346,20 +422,34 @@ extern "C" int asr_attn_fwd(const asr_attn_args* a, asr_stream_t stream) {
   const AtGeo g = at_geo(a);
   const dim3 grid((a->T + AT_TILE - 1) / AT_TILE, a->heads, a->n_pad);
   const size_t lds = at_lds_bytes(a->dh, 0);
-#define AT_FWD(DH)                                                                              \
+  const asr_attn_window win = w ? *w : asr_attn_window{1, -1, 0};
+#define AT_FWD_W(DH, WIN)                                                                       \
   {                                                                                             \
-    if (at_allow_lds(attn_fwd_kernel<DH>, lds) != ASR_OK) return ASR_ERR_LAUNCH;                \
-    hipLaunchKernelGGL((attn_fwd_kernel<DH>), grid, dim3(AT_THREADS), lds, (hipStream_t)stream, \
-                       a->qkv, a->lens, a->out, a->lse, g);                                     \
+    if (at_allow_lds(attn_fwd_kernel<DH, WIN>, lds) != ASR_OK) return ASR_ERR_LAUNCH;           \
+    hipLaunchKernelGGL((attn_fwd_kernel<DH, WIN>), grid, dim3(AT_THREADS), lds,                 \
+                       (hipStream_t)stream, a->qkv, a->lens, a->out, a->lse, g, win);           \
   }
+#define AT_FWD(DH) \
+  if (w) AT_FWD_W(DH, true) else AT_FWD_W(DH, false)
   AT_DISPATCH(AT_FWD)
 #undef AT_FWD
+#undef AT_FWD_W
   ASR_CHECK_LAUNCH();
   return ASR_OK;
 }
 
-extern "C" int asr_attn_bwd(const asr_attn_args* a, void* workspace, size_t ws_bytes,
-                            asr_stream_t stream) {
+extern "C" int asr_attn_fwd(const asr_attn_args* a, asr_stream_t stream) {
+  return at_fwd(a, nullptr, stream);
+}
+
+extern "C" int asr_attn_win_fwd(const asr_attn_args* a, const asr_attn_window* w,
+                                asr_stream_t stream) {
+  ASR_CHECK_ARG(at_win_ok(w), "attn_win_fwd: bad window (" AT_WIN_TEXT ")");
+  return at_fwd(a, w, stream);
+}
+
+static int at_bwd(const asr_attn_args* a, const asr_attn_window* w, void* workspace,
+                  size_t ws_bytes, asr_stream_t stream) {
   ASR_CHECK_ARG(at_geo_ok(a), "attn_bwd: bad geometry (T %d N %d n_pad %d heads %d dh %d ld %d "
                 "ld_out %d)", a ? a->T : 0, a ? a->N : 0, a ? a->n_pad : 0, a ? a->heads : 0,
                 a ? a->dh : 0, a ? a->ld : 0, a ? a->ld_out : 0);
@@ -377,19 +467,34 @@ extern "C" int asr_attn_bwd(const asr_attn_args* a, void* workspace, size_t ws_b
   const dim3 grid((a->T + AT_TILE - 1) / AT_TILE, a->heads, a->n_pad);
   const size_t lds = at_lds_bytes(a->dh, 1);
   hipStream_t s = (hipStream_t)stream;
-#define AT_BWD(DH)                                                                              \
+  const asr_attn_window win = w ? *w : asr_attn_window{1, -1, 0};
+#define AT_BWD_W(DH, WIN)                                                                       \
   {                                                                                             \
-    if (at_allow_lds(attn_bwd_dq_kernel<DH>, lds) != ASR_OK) return ASR_ERR_LAUNCH;             \
-    if (at_allow_lds(attn_bwd_dkv_kernel<DH>, lds) != ASR_OK) return ASR_ERR_LAUNCH;            \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DH>), grid, dim3(AT_THREADS), lds, s, a->qkv,        \
-                       a->lens, a->out, a->lse, a->dout, a->dqkv, dvec, g);                     \
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<DH>), grid, dim3(AT_THREADS), lds, s, a->qkv,       \
-                       a->lens, a->lse, a->dout, a->dqkv, dvec, g);                             \
+    if (at_allow_lds(attn_bwd_dq_kernel<DH, WIN>, lds) != ASR_OK) return ASR_ERR_LAUNCH;        \
+    if (at_allow_lds(attn_bwd_dkv_kernel<DH, WIN>, lds) != ASR_OK) return ASR_ERR_LAUNCH;       \
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, WIN>), grid, dim3(AT_THREADS), lds, s, a->qkv,   \
+                       a->lens, a->out, a->lse, a->dout, a->dqkv, dvec, g, win);                \
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<DH, WIN>), grid, dim3(AT_THREADS), lds, s, a->qkv,  \
+                       a->lens, a->lse, a->dout, a->dqkv, dvec, g, win);                        \
   }
+#define AT_BWD(DH) \
+  if (w) AT_BWD_W(DH, true) else AT_BWD_W(DH, false)
   AT_DISPATCH(AT_BWD)
 #undef AT_BWD
+#undef AT_BWD_W
   ASR_CHECK_LAUNCH();
   return ASR_OK;
+}
+
+extern "C" int asr_attn_bwd(const asr_attn_args* a, void* workspace, size_t ws_bytes,
+                            asr_stream_t stream) {
+  return at_bwd(a, nullptr, workspace, ws_bytes, stream);
+}
+
+extern "C" int asr_attn_win_bwd(const asr_attn_args* a, const asr_attn_window* w, void* workspace,
+                                size_t ws_bytes, asr_stream_t stream) {
+  ASR_CHECK_ARG(at_win_ok(w), "attn_win_bwd: bad window (" AT_WIN_TEXT ")");
+  return at_bwd(a, w, workspace, ws_bytes, stream);
 }
 
 extern "C" int asr_posenc_add(const float* x, const float* pe, float* y, int T, int N, int n_pad,

@@ -116,6 +116,54 @@ __device__ __forceinline__ int at_len(const int* lens, int n, int T) {
   return len < 1 ? 1 : (len > T ? T : len);
 }
 
+// THE WINDOW (K25), defined here once for attention.hip, rel_attention.hip and their plans.
+// Three integers: chunk >= 1; left >= -1 frames (-1: unlimited); right >= 0 frames.  For query
+// frame t let c0 = (t / chunk) * chunk.  Key u is visible to t iff lo(t) <= u < hi(t) and
+// u < lens[n], with
+//   hi(t) = c0 + chunk + right            lo(t) = left < 0 ? 0 : max(0, c0 - left)
+// chunk 1, right 0 is the causal mask (a finite left: a sliding window); chunk 1, right R a
+// symmetric window; chunk C chunk-wise attention with a look-ahead of chunk - 1 + right frames,
+// which does not grow with depth.  lo and hi are non-decreasing in t, and lo(t + 1) <= c0(t) +
+// chunk <= hi(t): the keys the queries qa .. qb see together are the ONE range [lo(qa), hi(qb)),
+// which is what the tile ranges below rely on.  hi saturates at INT_MAX.
+__host__ __device__ __forceinline__ bool at_win_ok(const asr_attn_window* w) {
+  return w != nullptr && w->chunk >= 1 && w->left >= -1 && w->right >= 0;
+}
+__host__ __device__ __forceinline__ int at_win_lo(const asr_attn_window& w, int t) {
+  const int c0 = t / w.chunk * w.chunk;
+  return (w.left < 0 || c0 < w.left) ? 0 : c0 - w.left;
+}
+__host__ __device__ __forceinline__ int at_win_hi(const asr_attn_window& w, int t) {
+  const long long hi = (long long)(t / w.chunk * w.chunk) + w.chunk + w.right;
+  return hi > 0x7fffffffLL ? 0x7fffffff : (int)hi;
+}
+// The key tiles the query tile at q0 (queries q0 .. min(q0 + 63, T - 1)) visits: k0 = *kb,
+// *kb + 64, ... while k0 < *ke -- those that meet [lo(q0), min(hi(last query), len)); none when
+// *kb >= *ke (every row of the tile is then empty).
+__host__ __device__ __forceinline__ void at_win_keys(const asr_attn_window& w, int q0, int T,
+                                                     int len, int* kb, int* ke) {
+  const int ql = q0 + AT_TILE - 1 < T ? q0 + AT_TILE - 1 : T - 1;
+  const int hi = at_win_hi(w, ql);
+  *kb = at_win_lo(w, q0) / AT_TILE * AT_TILE;
+  *ke = hi < len ? hi : len;
+}
+// Whether the queries qa .. qb and the key tile at k0 hold a visible pair (the length aside):
+// the test of the passes that own a key tile and walk query tiles.
+__host__ __device__ __forceinline__ bool at_win_pair(const asr_attn_window& w, int qa, int qb,
+                                                     int k0) {
+  return at_win_lo(w, qa) <= k0 + AT_TILE - 1 && at_win_hi(w, qb) > k0;
+}
+// (query tile, key tile) pairs one (sample, head) of the forward launch visits, lens == NULL
+inline long long at_win_tile_pairs(const asr_attn_window& w, int T) {
+  long long pairs = 0;
+  for (int q0 = 0; q0 < T; q0 += AT_TILE) {
+    int kb, ke;
+    at_win_keys(w, q0, T, T, &kb, &ke);
+    if (ke > kb) pairs += (ke - kb + AT_TILE - 1) / AT_TILE;
+  }
+  return pairs;
+}
+
 bool at_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 template <typename K>

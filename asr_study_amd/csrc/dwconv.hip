@@ -1,7 +1,9 @@
 // K22 depthwise 1-D convolution over the time axis of a time-major slab (T, n_pad, ld), plus the
 // two element-wise pairs of a Conformer block (GLU, Swish).  Exact fp32.
 //
-// Cross-correlation with 'same' padding, k odd, p = (k - 1) / 2, w (k, C) tap major:
+// Cross-correlation, k odd, w (k, C) tap major, p the LEFT PADDING: (k - 1) / 2 ('same', the
+// asr_dwconv1d_fwd / _bwd entry points) or any 0 <= p <= k - 1 (asr_dwconv1d_pad_*; p = k - 1 is
+// the causal convolution: no output frame reads a later input frame):
 //   xm[u, n, c] = x[u, n, c] if 0 <= u < len_n else 0             (lens == NULL: len_n = T)
 //   y[t, n, c]  = b[c] + sum_j w[j, c] xm[t + j - p, n, c]        every t < T, n < N, c < C
 //   dx[u]       = sum_j w[j, c] dy[u - j + p]  for u < len_n, exactly 0 for u >= len_n
@@ -106,15 +108,15 @@ __device__ __forceinline__ void dw_stage(float4* __restrict__ dst, const float* 
   }
 }
 
-// out[t] = bias + sum_j w'[j] in_m[t + j - p] over the tile; flip: w'[j] = w[k - 1 - j] (the input
+// out[t] = bias + sum_j w'[j] in_m[t + j - p] over the tile, p the left padding; flip: w'[j] = w[k - 1 - j] (the input
 // gradient).  mask_in: the input's frames >= len are zeros; mask_out: the output's are.
 __global__ void __launch_bounds__(DW_THREADS)
 dw_conv_kernel(const float* __restrict__ in, const float* __restrict__ w,
                const float* __restrict__ bias, const int* __restrict__ lens,
-               float* __restrict__ out, int T, int N, int C, int ld, long long W, int k, int flip,
-               int mask_in, int mask_out) {
+               float* __restrict__ out, int T, int N, int C, int ld, long long W, int k, int p,
+               int flip, int mask_in, int mask_out) {
   extern __shared__ float4 dw_sm[];
-  const int p = (k - 1) / 2, rows = DW_TT + k - 1;
+  const int rows = DW_TT + k - 1;
   float4* Xs = dw_sm;                       // rows x DW_CG
   float4* Ws = dw_sm + rows * DW_CG;        // k x DW_CG
   const int cg = threadIdx.x % DW_CG, ts = threadIdx.x / DW_CG;
@@ -164,9 +166,9 @@ template <int RR>
 __global__ void __launch_bounds__(DW_THREADS)
 dw_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                 const int* __restrict__ lens, float* __restrict__ part, int T, int N, int C,
-                int ld, long long W, int k, int tiles, int S) {
+                int ld, long long W, int k, int p, int tiles, int S) {
   extern __shared__ float4 dw_sm[];
-  const int p = (k - 1) / 2, rows = DW_TT + k - 1;
+  const int rows = DW_TT + k - 1;
   float4* Xs = dw_sm;                       // rows x DW_CG
   float4* Ds = dw_sm + rows * DW_CG;        // DW_TT x DW_CG
   const int cg = threadIdx.x % DW_CG, js = threadIdx.x / DW_CG;
@@ -369,24 +371,37 @@ extern "C" int asr_dwconv1d_plan(int T, int N, int n_pad, int C, int ld, int k, 
   return ASR_OK;
 }
 
-extern "C" int asr_dwconv1d_fwd(const float* x, const float* w, const float* b, const int* lens,
-                                float* y, int T, int N, int n_pad, int C, int ld, int k,
-                                asr_stream_t stream) {
+#define DW_PAD_OR_FAIL(what)                                                                   \
+  ASR_CHECK_ARG(pad_left >= 0 && pad_left <= k - 1,                                            \
+                what ": pad_left %d outside 0 .. k - 1 = %d", pad_left, k - 1)
+
+extern "C" int asr_dwconv1d_pad_fwd(const float* x, const float* w, const float* b,
+                                    const int* lens, float* y, int T, int N, int n_pad, int C,
+                                    int ld, int k, int pad_left, asr_stream_t stream) {
   DW_GEO_OR_FAIL("dwconv1d_fwd");
+  DW_PAD_OR_FAIL("dwconv1d_fwd");
   ASR_CHECK_ARG(x && w && b && y && y != x, "dwconv1d_fwd: x, w, b, y are required (y != x)");
   ASR_CHECK_ARG(dw_aligned(x) && dw_aligned(w) && dw_aligned(b) && dw_aligned(y),
                 "dwconv1d_fwd: x, w, b, y must be 16-byte aligned");
   hipLaunchKernelGGL(dw_conv_kernel, dim3(g.chunks, g.tiles), dim3(DW_THREADS), dw_lds_fwd(g),
-                     (hipStream_t)stream, x, w, b, lens, y, T, N, C, ld, g.W, k, 0, 1, 0);
+                     (hipStream_t)stream, x, w, b, lens, y, T, N, C, ld, g.W, k, pad_left, 0, 1,
+                     0);
   ASR_CHECK_LAUNCH();
   return ASR_OK;
 }
 
-extern "C" int asr_dwconv1d_bwd(const float* x, const float* w, const float* dy, const int* lens,
-                                float* dx, float* dw, float* db, int T, int N, int n_pad, int C,
-                                int ld, int k, void* workspace, size_t ws_bytes,
+extern "C" int asr_dwconv1d_fwd(const float* x, const float* w, const float* b, const int* lens,
+                                float* y, int T, int N, int n_pad, int C, int ld, int k,
                                 asr_stream_t stream) {
+  return asr_dwconv1d_pad_fwd(x, w, b, lens, y, T, N, n_pad, C, ld, k, (k - 1) / 2, stream);
+}
+
+extern "C" int asr_dwconv1d_pad_bwd(const float* x, const float* w, const float* dy,
+                                    const int* lens, float* dx, float* dw, float* db, int T, int N,
+                                    int n_pad, int C, int ld, int k, int pad_left, void* workspace,
+                                    size_t ws_bytes, asr_stream_t stream) {
   DW_GEO_OR_FAIL("dwconv1d_bwd");
+  DW_PAD_OR_FAIL("dwconv1d_bwd");
   ASR_CHECK_ARG(x && w && dy && dw && db, "dwconv1d_bwd: x, w, dy, dw, db are required");
   ASR_CHECK_ARG(dx != x && dx != dy, "dwconv1d_bwd: dx must not alias x or dy");
   ASR_CHECK_ARG(dw_aligned(x) && dw_aligned(w) && dw_aligned(dy) && dw_aligned(dx) &&
@@ -400,12 +415,13 @@ extern "C" int asr_dwconv1d_bwd(const float* x, const float* w, const float* dy,
   float* part = (float*)workspace;
   if (dx != nullptr) {
     hipLaunchKernelGGL(dw_conv_kernel, dim3(g.chunks, g.tiles), dim3(DW_THREADS), dw_lds_fwd(g),
-                       s, dy, w, (const float*)nullptr, lens, dx, T, N, C, ld, g.W, k, 1, 0, 1);
+                       s, dy, w, (const float*)nullptr, lens, dx, T, N, C, ld, g.W, k,
+                       k - 1 - pad_left, 1, 0, 1);
     ASR_CHECK_LAUNCH();
   }
 #define DW_WGRAD(RR)                                                                              \
   hipLaunchKernelGGL(dw_wgrad_kernel<RR>, dim3(g.chunks, g.S), dim3(DW_THREADS), dw_lds_bwd(g),   \
-                     s, x, dy, lens, part, T, N, C, ld, g.W, k, g.tiles, g.S)
+                     s, x, dy, lens, part, T, N, C, ld, g.W, k, pad_left, g.tiles, g.S)
   switch ((k + DW_TS - 1) / DW_TS) {        // taps per thread: 1 .. DW_TAPS
     case 1: DW_WGRAD(1); break;
     case 2: DW_WGRAD(2); break;
@@ -418,6 +434,14 @@ extern "C" int asr_dwconv1d_bwd(const float* x, const float* w, const float* dy,
                      dim3(DW_THREADS), 0, s, part, g.S, N, C, ld, g.W, k, dw, db);
   ASR_CHECK_LAUNCH();
   return ASR_OK;
+}
+
+extern "C" int asr_dwconv1d_bwd(const float* x, const float* w, const float* dy, const int* lens,
+                                float* dx, float* dw, float* db, int T, int N, int n_pad, int C,
+                                int ld, int k, void* workspace, size_t ws_bytes,
+                                asr_stream_t stream) {
+  return asr_dwconv1d_pad_bwd(x, w, dy, lens, dx, dw, db, T, N, n_pad, C, ld, k, (k - 1) / 2,
+                              workspace, ws_bytes, stream);
 }
 
 extern "C" int asr_swish_fwd(const float* x, float* y, int64_t n, asr_stream_t stream) {

@@ -39,6 +39,16 @@
 //             then asr_colsum adds the partials over n in a fixed order and sums the two slabs.
 // Every output element is written by exactly one thread in one fixed order: no float atomics,
 // repeats are bit-identical; no workgroup waits on another one.
+//
+// K25, THE WINDOW (asr_relattn_win_*): the definition of attn_tile.h (key u visible to query t iff
+// lo(t) <= u < hi(t) and u < lens[n]), the empty-row rule and the tile ranges of passes (1), (2)
+// and the forward are attention.hip's.  Pass (3) applies the window in its `live` predicate and
+// skips the (key tile, query half) pairs that hold no visible pair; a visible pair has t - u in
+// [-(chunk - 1 + right), left + chunk - 1] (left unlimited: T - 1), so a table tile wholly outside
+// that range writes zeros without a walk, and the rows outside it are exact zeros in any tile.
+// dbias_u and dbias_v are column sums of the masked dQ parts.  "Window" names this mask; "band"
+// stays the staged rows of the position table.  Templates on a bool: without the window the code
+// above, bit for bit.
 #include "attn_tile.h"
 
 namespace {
@@ -114,11 +124,13 @@ __device__ __forceinline__ void ra_band_scores(const float* Qs, const float* Bs,
   }
 }
 
-template <int DH>
+// WIN (here and below): under the window w of attn_tile.h (K25); without it w is not read and
+// the code is the unwindowed kernel's.
+template <int DH, bool WIN>
 __global__ __launch_bounds__(AT_THREADS) void relattn_fwd_kernel(
     const float* __restrict__ qkv, const int* __restrict__ lens, const float* __restrict__ pos,
     const float* __restrict__ bias_u, const float* __restrict__ bias_v, float* __restrict__ out,
-    float* __restrict__ lse, RaGeo g) {
+    float* __restrict__ lse, RaGeo g, asr_attn_window w) {
   constexpr int DP = DH + 4, NJ = DH / 16;
   extern __shared__ float4 ra_lds4[];
   float* Qs = reinterpret_cast<float*>(ra_lds4);
@@ -152,7 +164,16 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_fwd_kernel(
 #pragma unroll
     for (int jj = 0; jj < NJ; ++jj) o[i][jj] = 0.f;
   }
-  for (int k0 = 0; k0 < len; k0 += AT_TILE) {
+  int kb = 0, ke = len, wlo[4], whi[4];     // key tiles to visit; the visible keys of row i
+  if constexpr (WIN) {
+    at_win_keys(w, q0, g.T, len, &kb, &ke);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      wlo[i] = at_win_lo(w, q0 + 4 * ty + i);
+      whi[i] = min(at_win_hi(w, q0 + 4 * ty + i), len);
+    }
+  }
+  for (int k0 = kb; k0 < ke; k0 += AT_TILE) {
     const int pr0 = q0 - k0 - 63 + g.T - 1;           // table row of band row 0
     at_load_tile<DH>(Ks, base + D, rs, k0, len, tid);
     at_load_tile<DH>(Vs, base + 2 * D, rs, k0, len, tid);
@@ -172,15 +193,21 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_fwd_kernel(
       for (int j = 0; j < 4; ++j) {
         const int col = tx + 16 * j;
         const float sp = Ps[row * AT_PP + col] + cP[row - col + 63];
-        s[i][j] = (k0 + col < len) ? (s[i][j] + sp) * g.c2 : asr_neg_inf();
+        bool vis = k0 + col < len;
+        if constexpr (WIN) vis = k0 + col >= wlo[i] && k0 + col < whi[i];
+        s[i][j] = vis ? (s[i][j] + sp) * g.c2 : asr_neg_inf();
         mx = fmaxf(mx, s[i][j]);
       }
-      mx = fmaxf(m[i], at_max16(mx));       // finite: key k0 of every tile is a valid one
-      const float alpha = exp2f(m[i] - mx);
+      // without a window finite: key k0 of every tile is a valid one.  Under a window a row may
+      // have seen no key yet (m, mx both -inf, attention.hip): subtract 0 then, l stays 0
+      mx = fmaxf(m[i], at_max16(mx));
+      float mref = mx;
+      if constexpr (WIN) mref = mx == asr_neg_inf() ? 0.f : mx;
+      const float alpha = exp2f(m[i] - mref);
       float sum = 0.f;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        s[i][j] = exp2f(s[i][j] - mx);
+        s[i][j] = exp2f(s[i][j] - mref);
         sum += s[i][j];
       }
       l[i] = fmaf(l[i], alpha, at_sum16(sum));
@@ -200,20 +227,27 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_fwd_kernel(
     if (t >= g.T) continue;
     float* orow = o_base + (size_t)t * rso + h * DH;
 #pragma unroll
-    for (int jj = 0; jj < NJ; ++jj) orow[tx + 16 * jj] = o[i][jj] / l[i];
-    if (lse != nullptr && tx == 0)
-      lse[((size_t)t * g.n_pad + n) * g.heads + h] = (m[i] + log2f(l[i])) * AT_LN2;
+    for (int jj = 0; jj < NJ; ++jj) {
+      float v = o[i][jj] / l[i];
+      if constexpr (WIN) v = l[i] == 0.f ? 0.f : v;      // a row with no visible key: out = lse = 0
+      orow[tx + 16 * jj] = v;
+    }
+    if (lse != nullptr && tx == 0) {
+      float v = (m[i] + log2f(l[i])) * AT_LN2;
+      if constexpr (WIN) v = l[i] == 0.f ? 0.f : v;
+      lse[((size_t)t * g.n_pad + n) * g.heads + h] = v;
+    }
   }
 }
 
 // backward pass 1: D (to dvec), dQ = dQ_c + dQ_p; dQ_c -> slab_c, dQ_p -> slab_p (T, n_pad, D)
-template <int DH>
+template <int DH, bool WIN>
 __global__ __launch_bounds__(AT_THREADS) void relattn_bwd_dq_kernel(
     const float* __restrict__ qkv, const int* __restrict__ lens, const float* __restrict__ pos,
     const float* __restrict__ bias_u, const float* __restrict__ bias_v,
     const float* __restrict__ out, const float* __restrict__ lse, const float* __restrict__ dout,
     float* __restrict__ dqkv, float* __restrict__ dvec, float* __restrict__ slab_c,
-    float* __restrict__ slab_p, RaGeo g) {
+    float* __restrict__ slab_p, RaGeo g, asr_attn_window w) {
   constexpr int DP = DH + 4, NJ = DH / 16;
   extern __shared__ float4 ra_lds4[];
   float* Qs = reinterpret_cast<float*>(ra_lds4);
@@ -266,7 +300,16 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_bwd_dq_kernel(
 #pragma unroll
     for (int jj = 0; jj < NJ; ++jj) dqc[i][jj] = dqp[i][jj] = 0.f;
   }
-  for (int k0 = 0; k0 < len; k0 += AT_TILE) {
+  int kb = 0, ke = len, wlo[4], whi[4];     // key tiles to visit; the visible keys of row i
+  if constexpr (WIN) {
+    at_win_keys(w, q0, g.T, len, &kb, &ke);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      wlo[i] = at_win_lo(w, q0 + 4 * ty + i);
+      whi[i] = min(at_win_hi(w, q0 + 4 * ty + i), len);
+    }
+  }
+  for (int k0 = kb; k0 < ke; k0 += AT_TILE) {
     const int pr0 = q0 - k0 - 63 + g.T - 1;
     at_load_tile<DH>(Ks, base + D, rs, k0, len, tid);
     at_load_tile<DH>(Vs, base + 2 * D, rs, k0, len, tid);
@@ -285,7 +328,9 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_bwd_dq_kernel(
       for (int j = 0; j < 4; ++j) {
         const int row = 4 * ty + i, col = tx + 16 * j;
         const float st = s[i][j] + (Ps[row * AT_PP + col] + cP[row - col + 63]);
-        const float p = (k0 + col < len) ? exp2f(fmaf(st, g.c2, -lse2[i])) : 0.f;
+        bool vis = k0 + col < len;
+        if constexpr (WIN) vis = k0 + col >= wlo[i] && k0 + col < whi[i];
+        const float p = vis ? exp2f(fmaf(st, g.c2, -lse2[i])) : 0.f;
         s[i][j] = p * (dp[i][j] - dsum[i]) * g.scale;
       }
     __syncthreads();
@@ -321,12 +366,12 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_bwd_dq_kernel(
 }
 
 // backward pass 2: dK and dV of one key tile over all query tiles (query tiles ascending)
-template <int DH>
+template <int DH, bool WIN>
 __global__ __launch_bounds__(AT_THREADS) void relattn_bwd_dkv_kernel(
     const float* __restrict__ qkv, const int* __restrict__ lens, const float* __restrict__ pos,
     const float* __restrict__ bias_u, const float* __restrict__ bias_v,
     const float* __restrict__ lse, const float* __restrict__ dout, float* __restrict__ dqkv,
-    const float* __restrict__ dvec, RaGeo g) {
+    const float* __restrict__ dvec, RaGeo g, asr_attn_window w) {
   constexpr int DP = DH + 4, NJ = DH / 16;
   extern __shared__ float4 ra_lds4[];
   float* Ks = reinterpret_cast<float*>(ra_lds4);
@@ -364,6 +409,16 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_bwd_dkv_kernel(
 #pragma unroll
     for (int jj = 0; jj < NJ; ++jj) dk[i][jj] = dv[i][jj] = 0.f;
   for (int q0 = 0; q0 < g.T; q0 += AT_TILE) {
+    int qlo[4], qhi[4];                     // the visible keys of query tx + 16 j
+    if constexpr (WIN) {
+      // only the query tiles that see a key of this tile: one contiguous range
+      if (!at_win_pair(w, q0, min(q0 + AT_TILE, g.T) - 1, k0)) continue;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        qlo[j] = at_win_lo(w, q0 + tx + 16 * j);
+        qhi[j] = at_win_hi(w, q0 + tx + 16 * j);
+      }
+    }
     const int pr0 = q0 - k0 - 63 + g.T - 1;
     ra_load_rows<DH>(Qs, base, rs, q0, g.T, vu, tid);
     at_load_tile<DH>(Gs, do_base, rso, q0, g.T, tid);
@@ -398,7 +453,8 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_bwd_dkv_kernel(
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int q = tx + 16 * j, kk = 4 * ty + i;
-        const bool live = (k0 + kk < len) && (q0 + q < g.T);
+        bool live = (k0 + kk < len) && (q0 + q < g.T);
+        if constexpr (WIN) live = live && k0 + kk >= qlo[j] && k0 + kk < qhi[j];
         const float st = s[i][j] + (Ps[kk * AT_PP + q] + cP[q - kk + 63]);
         s[i][j] = live ? exp2f(fmaf(st, g.c2, -Ls[q])) : 0.f;
         dp[i][j] = s[i][j] * (dp[i][j] - Ds[q]) * g.scale;
@@ -428,12 +484,12 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_bwd_dkv_kernel(
 
 // backward pass 3: the partial of sample n of the table rows [64 m, 64 m + 64), i.e. the relative
 // indices r0 + b with r0 = 64 m - (T - 1); part is (N, 2T - 1, ld_pos)
-template <int DH>
+template <int DH, bool WIN>
 __global__ __launch_bounds__(AT_THREADS) void relattn_bwd_dpos_kernel(
     const float* __restrict__ qkv, const int* __restrict__ lens, const float* __restrict__ pos,
     const float* __restrict__ bias_u, const float* __restrict__ bias_v,
     const float* __restrict__ lse, const float* __restrict__ dout, const float* __restrict__ dvec,
-    float* __restrict__ part, RaGeo g) {
+    float* __restrict__ part, RaGeo g, asr_attn_window w) {
   constexpr int DP = DH + 4, NJ = DH / 16;
   extern __shared__ float4 ra_lds4[];
   float* Bs = reinterpret_cast<float*>(ra_lds4);   // the 64 rows of this band tile
@@ -464,7 +520,13 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_bwd_dpos_kernel(
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int jj = 0; jj < NJ; ++jj) acc[i][jj] = 0.f;
-  for (int k0 = 0; k0 < len; k0 += AT_TILE) {
+  // under a window a pair (t, u) is visible only for t - u in [-(chunk - 1 + right), left + chunk
+  // - 1] (left unlimited: T - 1): a table tile wholly outside that range is all zeros, no walk
+  bool dead = false;
+  if constexpr (WIN)
+    dead = r0 + AT_TILE - 1 + (long long)w.chunk - 1 + w.right < 0 ||
+           (w.left >= 0 && r0 + 1 > (long long)w.left + w.chunk);
+  for (int k0 = 0; !dead && k0 < len; k0 += AT_TILE) {
     // the queries t = u + r of this key tile and band tile: a window of 128 frames from k0 + r0
     if (k0 + r0 + 127 < 0 || k0 + r0 >= g.T) continue;
     at_load_tile<DH>(Ks, base + D, rs, k0, len, tid);
@@ -473,6 +535,15 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_bwd_dpos_kernel(
     for (int hf = 0; hf < 2; ++hf) {
       const int tw = k0 + r0 + 64 * hf;
       if (tw + 63 < 0 || tw >= g.T) continue;
+      int wlo[4], whi[4];                   // the visible keys of query tw + 4 ty + i
+      if constexpr (WIN) {
+        if (!at_win_pair(w, max(tw, 0), min(tw + AT_TILE, g.T) - 1, k0)) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          wlo[i] = at_win_lo(w, max(tw + 4 * ty + i, 0));
+          whi[i] = at_win_hi(w, max(tw + 4 * ty + i, 0));
+        }
+      }
       ra_load_rows<DH>(Qs, base, rs, tw, g.T, vv, tid);
       ra_load_rows<DH>(Gs, do_base, rso, tw, g.T, nullptr, tid);
       if (tid < AT_TILE) {
@@ -504,7 +575,8 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_bwd_dpos_kernel(
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int q = 4 * ty + i, kk = tx + 16 * j, b = 64 * hf + q - kk;
-          const bool live = b >= 0 && b < AT_TILE && k0 + kk < len && tw + q >= 0 && tw + q < g.T;
+          bool live = b >= 0 && b < AT_TILE && k0 + kk < len && tw + q >= 0 && tw + q < g.T;
+          if constexpr (WIN) live = live && k0 + kk >= wlo[i] && k0 + kk < whi[i];
           const float st = s[i][j] + (Ps[q * AT_PP + kk] + cK[kk]);
           const float p = live ? exp2f(fmaf(st, g.c2, -Ls[q])) : 0.f;
           s[i][j] = p * (dp[i][j] - Ds[q]) * g.scale;
@@ -626,7 +698,19 @@ extern "C" int asr_relattn_plan(const asr_relattn_args* a, int backward, int* bq
   return ASR_OK;
 }
 
-extern "C" int asr_relattn_fwd(const asr_relattn_args* a, asr_stream_t stream) {
+#define RA_WIN_TEXT "chunk >= 1, left >= -1 (-1: unlimited), right >= 0"
+
+extern "C" int asr_relattn_win_plan(const asr_relattn_args* a, const asr_attn_window* w,
+                                    int backward, int* bq, int* bk, int* blocks, int* lds_bytes,
+                                    long long* tile_pairs) {
+  ASR_CHECK_ARG(at_win_ok(w), "relattn_win_plan: bad window (" RA_WIN_TEXT ")");
+  const int rc = asr_relattn_plan(a, backward, bq, bk, blocks, lds_bytes);
+  if (rc == ASR_OK && tile_pairs) *tile_pairs = at_win_tile_pairs(*w, a->T);
+  return rc;
+}
+
+// w == nullptr: the unwindowed kernels
+static int ra_fwd(const asr_relattn_args* a, const asr_attn_window* w, asr_stream_t stream) {
   ASR_CHECK_ARG(ra_geo_ok(a), "relattn_fwd: bad geometry (T %d N %d n_pad %d heads %d dh %d ld %d "
                 "ld_out %d ld_pos %d; " RA_GEO_TEXT ")", a ? a->T : 0, a ? a->N : 0,
                 a ? a->n_pad : 0, a ? a->heads : 0, a ? a->dh : 0, a ? a->ld : 0,
@@ -638,21 +722,35 @@ extern "C" int asr_relattn_fwd(const asr_relattn_args* a, asr_stream_t stream) {
   const RaGeo g = ra_geo(a);
   const dim3 grid((a->T + AT_TILE - 1) / AT_TILE, a->heads, a->n_pad);
   const size_t lds = ra_lds_bytes(a->dh, 0);
-#define RA_FWD(DH)                                                                              \
+  const asr_attn_window win = w ? *w : asr_attn_window{1, -1, 0};
+#define RA_FWD_W(DH, WIN)                                                                       \
   {                                                                                             \
-    if (at_allow_lds(relattn_fwd_kernel<DH>, lds) != ASR_OK) return ASR_ERR_LAUNCH;             \
-    hipLaunchKernelGGL((relattn_fwd_kernel<DH>), grid, dim3(AT_THREADS), lds,                   \
+    if (at_allow_lds(relattn_fwd_kernel<DH, WIN>, lds) != ASR_OK) return ASR_ERR_LAUNCH;        \
+    hipLaunchKernelGGL((relattn_fwd_kernel<DH, WIN>), grid, dim3(AT_THREADS), lds,              \
                        (hipStream_t)stream, a->qkv, a->lens, a->pos, a->bias_u, a->bias_v,      \
-                       a->out, a->lse, g);                                                      \
+                       a->out, a->lse, g, win);                                                 \
   }
+#define RA_FWD(DH) \
+  if (w) RA_FWD_W(DH, true) else RA_FWD_W(DH, false)
   RA_DISPATCH(RA_FWD)
 #undef RA_FWD
+#undef RA_FWD_W
   ASR_CHECK_LAUNCH();
   return ASR_OK;
 }
 
-extern "C" int asr_relattn_bwd(const asr_relattn_args* a, void* workspace, size_t ws_bytes,
-                               asr_stream_t stream) {
+extern "C" int asr_relattn_fwd(const asr_relattn_args* a, asr_stream_t stream) {
+  return ra_fwd(a, nullptr, stream);
+}
+
+extern "C" int asr_relattn_win_fwd(const asr_relattn_args* a, const asr_attn_window* w,
+                                   asr_stream_t stream) {
+  ASR_CHECK_ARG(at_win_ok(w), "relattn_win_fwd: bad window (" RA_WIN_TEXT ")");
+  return ra_fwd(a, w, stream);
+}
+
+static int ra_bwd(const asr_relattn_args* a, const asr_attn_window* wp, void* workspace,
+                  size_t ws_bytes, asr_stream_t stream) {
   ASR_CHECK_ARG(ra_geo_ok(a), "relattn_bwd: bad geometry (T %d N %d n_pad %d heads %d dh %d ld %d "
                 "ld_out %d ld_pos %d; " RA_GEO_TEXT ")", a ? a->T : 0, a ? a->N : 0,
                 a ? a->n_pad : 0, a ? a->heads : 0, a ? a->dh : 0, a ? a->ld : 0,
@@ -680,23 +778,27 @@ extern "C" int asr_relattn_bwd(const asr_relattn_args* a, void* workspace, size_
   const size_t lds1 = ra_lds_bytes(a->dh, 1), lds2 = ra_lds_bytes(a->dh, 2);
   const size_t lds3 = ra_lds_bytes(a->dh, 3);
   hipStream_t s = (hipStream_t)stream;
-#define RA_BWD(DH)                                                                              \
-  {                                                                                             \
-    if (at_allow_lds(relattn_bwd_dq_kernel<DH>, lds1) != ASR_OK) return ASR_ERR_LAUNCH;         \
-    if (at_allow_lds(relattn_bwd_dkv_kernel<DH>, lds2) != ASR_OK) return ASR_ERR_LAUNCH;        \
-    if (at_allow_lds(relattn_bwd_dpos_kernel<DH>, lds3) != ASR_OK) return ASR_ERR_LAUNCH;       \
-    hipLaunchKernelGGL((relattn_bwd_dq_kernel<DH>), grid, dim3(AT_THREADS), lds1, s, a->qkv,    \
-                       a->lens, a->pos, a->bias_u, a->bias_v, a->out, a->lse, a->dout, a->dqkv, \
-                       dvec, slab_c, slab_p, g);                                                \
-    hipLaunchKernelGGL((relattn_bwd_dkv_kernel<DH>), grid, dim3(AT_THREADS), lds2, s, a->qkv,   \
-                       a->lens, a->pos, a->bias_u, a->bias_v, a->lse, a->dout, a->dqkv, dvec,   \
-                       g);                                                                      \
-    hipLaunchKernelGGL((relattn_bwd_dpos_kernel<DH>), grid_pos, dim3(AT_THREADS), lds3, s,      \
-                       a->qkv, a->lens, a->pos, a->bias_u, a->bias_v, a->lse, a->dout, dvec,    \
-                       part, g);                                                                \
+  const asr_attn_window win = wp ? *wp : asr_attn_window{1, -1, 0};
+#define RA_BWD_W(DH, WIN)                                                                        \
+  {                                                                                              \
+    if (at_allow_lds(relattn_bwd_dq_kernel<DH, WIN>, lds1) != ASR_OK) return ASR_ERR_LAUNCH;     \
+    if (at_allow_lds(relattn_bwd_dkv_kernel<DH, WIN>, lds2) != ASR_OK) return ASR_ERR_LAUNCH;    \
+    if (at_allow_lds(relattn_bwd_dpos_kernel<DH, WIN>, lds3) != ASR_OK) return ASR_ERR_LAUNCH;   \
+    hipLaunchKernelGGL((relattn_bwd_dq_kernel<DH, WIN>), grid, dim3(AT_THREADS), lds1, s,        \
+                       a->qkv, a->lens, a->pos, a->bias_u, a->bias_v, a->out, a->lse, a->dout,   \
+                       a->dqkv, dvec, slab_c, slab_p, g, win);                                   \
+    hipLaunchKernelGGL((relattn_bwd_dkv_kernel<DH, WIN>), grid, dim3(AT_THREADS), lds2, s,       \
+                       a->qkv, a->lens, a->pos, a->bias_u, a->bias_v, a->lse, a->dout, a->dqkv,  \
+                       dvec, g, win);                                                            \
+    hipLaunchKernelGGL((relattn_bwd_dpos_kernel<DH, WIN>), grid_pos, dim3(AT_THREADS), lds3, s,  \
+                       a->qkv, a->lens, a->pos, a->bias_u, a->bias_v, a->lse, a->dout, dvec,     \
+                       part, g, win);                                                            \
   }
+#define RA_BWD(DH) \
+  if (wp) RA_BWD_W(DH, true) else RA_BWD_W(DH, false)
   RA_DISPATCH(RA_BWD)
 #undef RA_BWD
+#undef RA_BWD_W
   ASR_CHECK_LAUNCH();
   const int D = a->heads * a->dh, M = a->T * a->n_pad;
   int rc = asr_colsum(slab_c, M, D, D, a->dbias_u, 0.f, ws + w.colsum, w.colsum_bytes, stream);
@@ -705,4 +807,15 @@ extern "C" int asr_relattn_bwd(const asr_relattn_args* a, void* workspace, size_
   if (rc != ASR_OK) return rc;
   return asr_colsum(part, a->N, rows * a->ld_pos, rows * a->ld_pos, a->dpos, 0.f, ws + w.colsum,
                     w.colsum_bytes, stream);
+}
+
+extern "C" int asr_relattn_bwd(const asr_relattn_args* a, void* workspace, size_t ws_bytes,
+                               asr_stream_t stream) {
+  return ra_bwd(a, nullptr, workspace, ws_bytes, stream);
+}
+
+extern "C" int asr_relattn_win_bwd(const asr_relattn_args* a, const asr_attn_window* w,
+                                   void* workspace, size_t ws_bytes, asr_stream_t stream) {
+  ASR_CHECK_ARG(at_win_ok(w), "relattn_win_bwd: bad window (" RA_WIN_TEXT ")");
+  return ra_bwd(a, w, workspace, ws_bytes, stream);
 }

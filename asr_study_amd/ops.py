@@ -616,20 +616,51 @@ def attn_plan(T, n_pad, heads, dh, backward=False):
     return dict(zip(('bq', 'bk', 'blocks', 'lds'), (x.value for x in v)))
 
 
-def attn_fwd(qkv, out, N, heads, dh, lens=None, lse=None, scale=None):
+def attn_window(window):
+    """The asr_attn_window of a (chunk, left, right) triple (K25, csrc/attn_tile.h): for query
+    frame t, c0 = (t // chunk) * chunk, key u is visible iff lo(t) <= u < hi(t) and u < lens[n],
+    hi(t) = c0 + chunk + right, lo(t) = 0 if left < 0 else max(0, c0 - left).  The library checks
+    the values (chunk >= 1, left >= -1, right >= 0)."""
+    chunk, left, right = window
+    return L.AttnWindow(int(chunk), int(left), int(right))
+
+
+def attn_win_plan(T, n_pad, heads, dh, window, backward=False):
+    """attn_plan under a window, plus 'tile_pairs': the (query tile, key tile) pairs one (sample,
+    head) of the forward launch visits without lens (asr_attn_win_plan)."""
+    a = L.AttnArgs()
+    a.T, a.N, a.n_pad, a.heads, a.dh = int(T), 1, int(n_pad), int(heads), int(dh)
+    a.ld, a.ld_out, a.scale = 3 * int(heads) * int(dh), int(heads) * int(dh), 1.0
+    v = [C.c_int(0) for _ in range(4)]
+    pairs = C.c_longlong(0)
+    w = attn_window(window)
+    L.check(L.load().asr_attn_win_plan(C.byref(a), C.byref(w), int(bool(backward)),
+                                       *[C.byref(x) for x in v], C.byref(pairs)),
+            'asr_attn_win_plan')
+    return dict(zip(('bq', 'bk', 'blocks', 'lds'), (x.value for x in v)), tile_pairs=pairs.value)
+
+
+def attn_fwd(qkv, out, N, heads, dh, lens=None, lse=None, scale=None, window=None):
     """out (T, n_pad, ld_out >= heads dh) = softmax(scale Q K^T) V per real sample and head of the
     slab qkv (T, n_pad, ld >= 3 heads dh) = [Q | K | V]; keys u >= lens[n] (device int32,
-    1 <= lens <= T) carry probability 0; lse (attn_lse_len) kept for attn_bwd when given."""
+    1 <= lens <= T) carry probability 0; lse (attn_lse_len) kept for attn_bwd when given.
+    window: None, or (chunk, left, right) of attn_window (asr_attn_win_fwd): keys outside a
+    query's window carry probability 0 too, a row with no visible key has out = lse = 0."""
     _check_f32(qkv, out, lse)
     _check_lens(lens, N)
     assert qkv.dim() == 3 and out.dim() == 3 and out.shape[:2] == qkv.shape[:2]
     a = _attn_args(qkv, N, heads, dh, out.shape[2], scale, lens, out, lse)
-    L.check(L.load().asr_attn_fwd(C.byref(a), _stream()), 'asr_attn_fwd')
+    if window is None:
+        L.check(L.load().asr_attn_fwd(C.byref(a), _stream()), 'asr_attn_fwd')
+    else:
+        w = attn_window(window)
+        L.check(L.load().asr_attn_win_fwd(C.byref(a), C.byref(w), _stream()), 'asr_attn_win_fwd')
     return out
 
 
-def attn_bwd(qkv, out, lse, dout, dqkv, N, heads, dh, lens=None, scale=None):
-    """dqkv (like qkv) = dQ | dK | dV from dout (like out), recomputing p from lse."""
+def attn_bwd(qkv, out, lse, dout, dqkv, N, heads, dh, lens=None, scale=None, window=None):
+    """dqkv (like qkv) = dQ | dK | dV from dout (like out), recomputing p from lse (window: that
+    of the forward call)."""
     _check_f32(qkv, out, lse, dout, dqkv)
     _check_lens(lens, N)
     assert dqkv.shape == qkv.shape and dout.shape == out.shape
@@ -639,7 +670,12 @@ def attn_bwd(qkv, out, lse, dout, dqkv, N, heads, dh, lens=None, scale=None):
         L.check(-1, 'asr_attn_workspace_bytes (T %d N %d n_pad %d heads %d dh %d ld %d ld_out %d)'
                 % (a.T, a.N, a.n_pad, a.heads, a.dh, a.ld, a.ld_out))
     ws = WS.get('attn', nbytes, qkv.device)
-    L.check(L.load().asr_attn_bwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_attn_bwd')
+    if window is None:
+        L.check(L.load().asr_attn_bwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_attn_bwd')
+    else:
+        w = attn_window(window)
+        L.check(L.load().asr_attn_win_bwd(C.byref(a), C.byref(w), _ptr(ws), nbytes, _stream()),
+                'asr_attn_win_bwd')
     return dqkv
 
 
@@ -748,25 +784,48 @@ def relattn_plan(T, n_pad, heads, dh, backward=False):
     return dict(zip(('bq', 'bk', 'blocks', 'lds'), (x.value for x in v)))
 
 
-def relattn_fwd(qkv, pos, bias_u, bias_v, out, N, heads, dh, lens=None, lse=None, scale=None):
+def relattn_win_plan(T, n_pad, heads, dh, window, backward=False):
+    """relattn_plan under a window, plus 'tile_pairs' as attn_win_plan (asr_relattn_win_plan)."""
+    a = L.RelAttnArgs()
+    a.T, a.N, a.n_pad, a.heads, a.dh = int(T), 1, int(n_pad), int(heads), int(dh)
+    a.ld, a.ld_out, a.scale = 3 * int(heads) * int(dh), int(heads) * int(dh), 1.0
+    a.ld_pos = a.ld_out
+    v = [C.c_int(0) for _ in range(4)]
+    pairs = C.c_longlong(0)
+    w = attn_window(window)
+    L.check(L.load().asr_relattn_win_plan(C.byref(a), C.byref(w), int(bool(backward)),
+                                          *[C.byref(x) for x in v], C.byref(pairs)),
+            'asr_relattn_win_plan')
+    return dict(zip(('bq', 'bk', 'blocks', 'lds'), (x.value for x in v)), tile_pairs=pairs.value)
+
+
+def relattn_fwd(qkv, pos, bias_u, bias_v, out, N, heads, dh, lens=None, lse=None, scale=None,
+                window=None):
     """out (T, n_pad, ld_out >= heads dh) of the relative positional attention core on the slab
     qkv (T, n_pad, ld >= 3 heads dh) = [Q | K | V]: s[t, u] = scale ((q_t + bias_u) . k_u +
     (q_t + bias_v) . pos[t - u + T - 1]) over the keys u < lens[n]; pos (2T - 1, ld_pos >= heads
-    dh) is the projected table, bias_u / bias_v (heads dh); lse kept for relattn_bwd when given."""
+    dh) is the projected table, bias_u / bias_v (heads dh); lse kept for relattn_bwd when given.
+    window: None, or (chunk, left, right) as in attn_fwd (asr_relattn_win_fwd)."""
     _check_f32(qkv, pos, bias_u, bias_v, out, lse)
     _check_lens(lens, N)
     assert qkv.dim() == 3 and out.dim() == 3 and out.shape[:2] == qkv.shape[:2]
     assert pos.dim() == 2 and pos.shape[0] == 2 * qkv.shape[0] - 1 and pos.is_contiguous()
     a = _relattn_args(qkv, N, heads, dh, out.shape[2], pos.shape[1], scale, lens=lens, out=out,
                       lse=lse, pos=pos, bias_u=bias_u, bias_v=bias_v)
-    L.check(L.load().asr_relattn_fwd(C.byref(a), _stream()), 'asr_relattn_fwd')
+    if window is None:
+        L.check(L.load().asr_relattn_fwd(C.byref(a), _stream()), 'asr_relattn_fwd')
+    else:
+        w = attn_window(window)
+        L.check(L.load().asr_relattn_win_fwd(C.byref(a), C.byref(w), _stream()),
+                'asr_relattn_win_fwd')
     return out
 
 
 def relattn_bwd(qkv, pos, bias_u, bias_v, out, lse, dout, dqkv, dpos, dbias_u, dbias_v, N, heads,
-                dh, lens=None, scale=None):
+                dh, lens=None, scale=None, window=None):
     """dqkv (like qkv) = dQ | dK | dV, dpos (like pos), dbias_u, dbias_v (heads dh) from dout (like
-    out), recomputing p from lse; all four are written, not accumulated."""
+    out), recomputing p from lse; all four are written, not accumulated (window: that of the
+    forward call)."""
     _check_f32(qkv, pos, bias_u, bias_v, out, lse, dout, dqkv, dpos, dbias_u, dbias_v)
     _check_lens(lens, N)
     assert dqkv.shape == qkv.shape and dout.shape == out.shape and dpos.shape == pos.shape
@@ -779,7 +838,13 @@ def relattn_bwd(qkv, pos, bias_u, bias_v, out, lse, dout, dqkv, dpos, dbias_u, d
         L.check(-1, 'asr_relattn_workspace_bytes (T %d N %d n_pad %d heads %d dh %d ld %d ld_out '
                 '%d ld_pos %d)' % (a.T, a.N, a.n_pad, a.heads, a.dh, a.ld, a.ld_out, a.ld_pos))
     ws = WS.get('relattn', nbytes, qkv.device)
-    L.check(L.load().asr_relattn_bwd(C.byref(a), _ptr(ws), nbytes, _stream()), 'asr_relattn_bwd')
+    if window is None:
+        L.check(L.load().asr_relattn_bwd(C.byref(a), _ptr(ws), nbytes, _stream()),
+                'asr_relattn_bwd')
+    else:
+        w = attn_window(window)
+        L.check(L.load().asr_relattn_win_bwd(C.byref(a), C.byref(w), _ptr(ws), nbytes, _stream()),
+                'asr_relattn_win_bwd')
     return dqkv
 
 
@@ -797,23 +862,31 @@ def dwconv1d_plan(T, n_pad, channels, k, ld=None, N=1, backward=False):
     return dict(zip(('tile', 'blocks', 'lds'), (x.value for x in v)))
 
 
-def dwconv1d_fwd(x, w, b, y, N, k, lens=None, C_=None):
+def dwconv1d_fwd(x, w, b, y, N, k, lens=None, C_=None, pad_left=None):
     """y[t, n, c] = b[c] + sum_j w[j, c] xm[t + j - (k - 1) / 2, n, c] over the slab x (T, n_pad,
     ld >= C), xm = x with the frames >= lens[n] (device int32; None: every frame) as zeros;
-    w (k, C) tap major; zeros in the rows n >= N and the columns >= C (C_: default ld)."""
+    w (k, C) tap major; zeros in the rows n >= N and the columns >= C (C_: default ld).
+    pad_left: None, or the left padding 0 .. k - 1 in place of (k - 1) / 2 (asr_dwconv1d_pad_fwd;
+    k - 1 is the causal convolution)."""
     _check_f32(x, w, b, y)
     _check_lens(lens, N)
     T, n_pad, ld = x.shape
     Cc = int(C_ or ld)
     assert y.shape == x.shape and w.numel() == k * Cc and b.numel() == Cc
-    L.check(L.load().asr_dwconv1d_fwd(_ptr(x), _ptr(w), _ptr(b), _ptr(lens), _ptr(y), int(T),
-                                      int(N), int(n_pad), Cc, int(ld), int(k), _stream()),
-            'asr_dwconv1d_fwd')
+    if pad_left is None:
+        L.check(L.load().asr_dwconv1d_fwd(_ptr(x), _ptr(w), _ptr(b), _ptr(lens), _ptr(y), int(T),
+                                          int(N), int(n_pad), Cc, int(ld), int(k), _stream()),
+                'asr_dwconv1d_fwd')
+    else:
+        L.check(L.load().asr_dwconv1d_pad_fwd(_ptr(x), _ptr(w), _ptr(b), _ptr(lens), _ptr(y),
+                                              int(T), int(N), int(n_pad), Cc, int(ld), int(k),
+                                              int(pad_left), _stream()), 'asr_dwconv1d_pad_fwd')
     return y
 
 
-def dwconv1d_bwd(x, w, dy, dx, dw, db, N, k, lens=None, C_=None):
-    """dw (k, C), db (C) (written) and dx (like x, or None) of dwconv1d_fwd."""
+def dwconv1d_bwd(x, w, dy, dx, dw, db, N, k, lens=None, C_=None, pad_left=None):
+    """dw (k, C), db (C) (written) and dx (like x, or None) of dwconv1d_fwd (pad_left: that of the
+    forward call)."""
     _check_f32(x, w, dy, dx, dw, db)
     _check_lens(lens, N)
     T, n_pad, ld = x.shape
@@ -824,9 +897,14 @@ def dwconv1d_bwd(x, w, dy, dx, dw, db, N, k, lens=None, C_=None):
     if nbytes == 0:
         L.check(-1, 'asr_dwconv1d_workspace_bytes (T %d N %d n_pad %d C %d ld %d k %d)' % geo)
     ws = WS.get('dwconv', nbytes, x.device)
-    L.check(L.load().asr_dwconv1d_bwd(_ptr(x), _ptr(w), _ptr(dy), _ptr(lens), _ptr(dx), _ptr(dw),
-                                      _ptr(db), *geo, _ptr(ws), nbytes, _stream()),
-            'asr_dwconv1d_bwd')
+    if pad_left is None:
+        L.check(L.load().asr_dwconv1d_bwd(_ptr(x), _ptr(w), _ptr(dy), _ptr(lens), _ptr(dx),
+                                          _ptr(dw), _ptr(db), *geo, _ptr(ws), nbytes, _stream()),
+                'asr_dwconv1d_bwd')
+    else:
+        L.check(L.load().asr_dwconv1d_pad_bwd(_ptr(x), _ptr(w), _ptr(dy), _ptr(lens), _ptr(dx),
+                                              _ptr(dw), _ptr(db), *geo, int(pad_left), _ptr(ws),
+                                              nbytes, _stream()), 'asr_dwconv1d_pad_bwd')
     return dx
 
 

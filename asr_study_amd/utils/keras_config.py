@@ -227,12 +227,16 @@ def model_config(model):
                 'name': name, 'trainable': True, 'num_heads': int(s.heads),
                 'head_dim': int(s.dh), 'output_dim': int(s.n_out),
                 'W_regularizer': _regularizer(s.l2)}, [prev])
+            if getattr(s, 'window', None) is not None:    # (only then: every other model's config text is unchanged)
+                layers[-1]['config']['context'] = list(s.window)
         elif s.kind == 'mha':
             name = nm('multiheadattention')
             add('MultiHeadAttention', name, {
                 'name': name, 'trainable': True, 'num_heads': int(s.heads),
                 'head_dim': int(s.dh), 'output_dim': int(s.n_out),
                 'W_regularizer': _regularizer(s.l2), 'attention_dropout': 0.0}, [prev])
+            if getattr(s, 'window', None) is not None:
+                layers[-1]['config']['context'] = list(s.window)
         elif s.kind == 'posenc':
             name = nm('positionalencoding')
             add('PositionalEncoding', name, {'name': name, 'trainable': True}, [prev])
@@ -257,6 +261,8 @@ def model_config(model):
                 'name': name, 'trainable': True, 'kernel_size': int(s.k),
                 'border_mode': 'same', 'init': 'glorot_uniform',
                 'W_regularizer': _regularizer(s.l2), 'bias': True}, [prev])
+            if getattr(s, 'pad_left', None) is not None:
+                layers[-1]['config']['causal'] = True
         elif s.kind == 'glu':
             name = nm('glu')
             add('GLU', name, {'name': name, 'trainable': True}, [prev])
@@ -384,16 +390,19 @@ def topology_from_config(text):
             o = L.MultiHeadAttention(c['num_heads'], head_dim=c.get('head_dim'),
                                      output_dim=c.get('output_dim'),
                                      W_regularizer=reg(c.get('W_regularizer')),
-                                     attention_dropout=c.get('attention_dropout', 0.))(o)
+                                     attention_dropout=c.get('attention_dropout', 0.),
+                                     context=c.get('context'))(o)
         elif kind == 'RelativeMultiHeadAttention':
             o = L.RelativeMultiHeadAttention(c['num_heads'], head_dim=c.get('head_dim'),
                                              output_dim=c.get('output_dim'),
-                                             W_regularizer=reg(c.get('W_regularizer')))(o)
+                                             W_regularizer=reg(c.get('W_regularizer')),
+                                             context=c.get('context'))(o)
         elif kind == 'PositionalEncoding':
             o = L.PositionalEncoding()(o)
         elif kind == 'DepthwiseConvolution1D':
             o = L.DepthwiseConvolution1D(c['kernel_size'],
-                                         W_regularizer=reg(c.get('W_regularizer')))(o)
+                                         W_regularizer=reg(c.get('W_regularizer')),
+                                         causal=c.get('causal', False))(o)
         elif kind == 'GLU':
             o = L.GLU()(o)
         elif kind == 'TimeDistributed' and c['layer']['class_name'] == 'Activation':

@@ -56,7 +56,9 @@ const char* asr_last_error(void);
  * and the asr_gru_* entry points (K16: additions only, no existing layout changes); asr_rhn_args
  * and the asr_rhn_* entry points (K17: additions only as well); the asr_seqbn_* entry points
  * (K18: plain scalar arguments again); the asr_dwconv1d_* / asr_glu_* / asr_swish_* entry points
- * (K22: plain scalar arguments, additions only); asr_specaug_apply (K23: likewise). */
+ * (K22: plain scalar arguments, additions only); asr_specaug_apply (K23: likewise);
+ * asr_relattn_args and asr_relattn_* (K24), asr_attn_window and the asr_attn_win_* /
+ * asr_relattn_win_* / asr_dwconv1d_pad_* entry points (K25): additions only as well. */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -745,6 +747,32 @@ int asr_attn_bwd(const asr_attn_args* a, void* workspace, size_t ws_bytes, asr_s
 /* bytes per workgroup (any pointer may be NULL).                                             */
 int asr_attn_plan(const asr_attn_args* a, int backward, int* bq, int* bk, int* blocks,
                   int* lds_bytes);
+/* K25 limited-context attention: K21 (and, below, K24) under a WINDOW of three integers,      */
+/*   chunk >= 1;  left >= -1 frames (-1: unlimited);  right >= 0 frames.                      */
+/* For query frame t let c0 = (t / chunk) * chunk.  Key u is visible to t iff                 */
+/*   lo(t) <= u < hi(t)  and  u < lens[n],   hi(t) = c0 + chunk + right,                      */
+/*                                           lo(t) = left < 0 ? 0 : max(0, c0 - left).        */
+/* chunk 1, right 0 is the causal mask (a finite left: a sliding window); chunk 1, right R a  */
+/* symmetric window; chunk C chunk-wise attention, whose look-ahead chunk - 1 + right does    */
+/* not grow with depth.  lo and hi are non-decreasing in t.  Every other key carries          */
+/* probability exactly 0 (a select: nothing it holds reaches a result).  A row with NO        */
+/* visible key (a time-padding query with lo(t) >= lens[n]) has out_t = exactly 0 and lse_t = */
+/* exactly 0 and adds exactly 0 to every gradient (dQ_t = 0).  A key no query sees gets dK =  */
+/* dV = exactly 0.  A workgroup visits only the tiles that hold a visible (query, key) pair:  */
+/* for a query tile the key tiles that meet [lo(first query), min(hi(last query), len)), for  */
+/* a key tile at k0 the query tiles with lo(first) <= k0 + 63 and hi(last) > k0 -- one        */
+/* contiguous range each.  The argument struct, the workspace and everything else are those   */
+/* of the unwindowed calls, whose results do not change.  chunk < 1, left < -1, right < 0 or  */
+/* a NULL window: ASR_ERR_INVALID before any device call.                                     */
+typedef struct asr_attn_window { int chunk, left, right; } asr_attn_window;
+int asr_attn_win_fwd(const asr_attn_args* a, const asr_attn_window* w, asr_stream_t stream);
+int asr_attn_win_bwd(const asr_attn_args* a, const asr_attn_window* w, void* workspace,
+                     size_t ws_bytes, asr_stream_t stream);
+/* asr_attn_plan, and tile_pairs: the (query tile, key tile) pairs one (sample, head) of the  */
+/* forward launch visits when lens is NULL, from the helper the kernels take their loop       */
+/* bounds from (any pointer may be NULL).                                                     */
+int asr_attn_win_plan(const asr_attn_args* a, const asr_attn_window* w, int backward, int* bq,
+                      int* bk, int* blocks, int* lds_bytes, long long* tile_pairs);
 /* Sinusoidal positional encoding added to a slab: y[t, n, f] = x[t, n, f] + pe[t, f] for    */
 /* n < N and f < D, zeros elsewhere; x, y (T, n_pad, ld >= D), pe (T, D) with                 */
 /* pe[t, 2i] = sin(t / 10000^(2i / D)), pe[t, 2i + 1] = cos(t / 10000^(2i / D)), computed by  */
@@ -810,6 +838,16 @@ int asr_relattn_bwd(const asr_relattn_args* a, void* workspace, size_t ws_bytes,
 /* (backward: of the largest of its three passes); any pointer may be NULL.                   */
 int asr_relattn_plan(const asr_relattn_args* a, int backward, int* bq, int* bk, int* blocks,
                      int* lds_bytes);
+/* K25 under a window (asr_attn_window above: the same definition, the same empty-row rule,   */
+/* the same tile ranges).  dpos follows the masked dS: its rows with a relative index outside */
+/* [-(chunk - 1 + right), left + chunk - 1] (left unlimited: T - 1 on that side) are exact    */
+/* zeros, and a 64-row tile of the table wholly outside that range is written without a walk  */
+/* over the keys; dbias_u and dbias_v follow as well.                                         */
+int asr_relattn_win_fwd(const asr_relattn_args* a, const asr_attn_window* w, asr_stream_t stream);
+int asr_relattn_win_bwd(const asr_relattn_args* a, const asr_attn_window* w, void* workspace,
+                        size_t ws_bytes, asr_stream_t stream);
+int asr_relattn_win_plan(const asr_relattn_args* a, const asr_attn_window* w, int backward,
+                         int* bq, int* bk, int* blocks, int* lds_bytes, long long* tile_pairs);
 
 /* ------------------------------------------------------------------------ */
 /* K22 depthwise 1-D convolution over the time axis of a time-major slab     */
@@ -843,6 +881,20 @@ int asr_dwconv1d_fwd(const float* x, const float* w, const float* b, const int* 
 int asr_dwconv1d_bwd(const float* x, const float* w, const float* dy, const int* lens, float* dx,
                      float* dw, float* db, int T, int N, int n_pad, int C, int ld, int k,
                      void* workspace, size_t ws_bytes, asr_stream_t stream);
+/* The same with the left padding as an argument, 0 <= pad_left <= k - 1:                     */
+/*   y[t] = b + sum_j w[j] xm[t + j - pad_left],  dx[u] = sum_j w[j] dy[u - j + pad_left],    */
+/*   dw[j] = sum dy[t] xm[t + j - pad_left]                                                   */
+/* (the input gradient is the flipped filter with padding k - 1 - pad_left).  pad_left =      */
+/* k - 1 is the CAUSAL convolution: no output frame reads a later input frame.  pad_left =    */
+/* (k - 1) / 2 is asr_dwconv1d_fwd / _bwd, bit for bit (they are this call).  The length      */
+/* mask, the workspace, the plan and the order of the dw / db partials do not depend on it.   */
+int asr_dwconv1d_pad_fwd(const float* x, const float* w, const float* b, const int* lens,
+                         float* y, int T, int N, int n_pad, int C, int ld, int k, int pad_left,
+                         asr_stream_t stream);
+int asr_dwconv1d_pad_bwd(const float* x, const float* w, const float* dy, const int* lens,
+                         float* dx, float* dw, float* db, int T, int N, int n_pad, int C, int ld,
+                         int k, int pad_left, void* workspace, size_t ws_bytes,
+                         asr_stream_t stream);
 /* Gated linear unit over rows of ld_in >= 2C floats: y[r, c] = x[r, c] sigma(x[r, C + c]) for  */
 /* c < C, zeros in C <= c < ld_out; backward recomputes sigma from x: dx[r, c] = dy sigma(g),   */
 /* dx[r, C + c] = dy a sigma(g) (1 - sigma(g)), zeros in 2C <= c < ld_in.  C, ld_in, ld_out     */
