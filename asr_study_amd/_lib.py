@@ -157,6 +157,16 @@ class AttnWindow(C.Structure):
     _fields_ = [('chunk', C.c_int), ('left', C.c_int), ('right', C.c_int)]
 
 
+class AttnStreamArgs(C.Structure):
+    # asr_attn_stream_args (K26): a few new query frames against a ring of cached keys and values
+    _fields_ = [('Tq', C.c_int), ('N', C.c_int), ('n_pad', C.c_int), ('heads', C.c_int),
+                ('dh', C.c_int), ('ld', C.c_int), ('ld_kv', C.c_int), ('ld_out', C.c_int),
+                ('R', C.c_int), ('t0', C.c_int), ('P', C.c_int), ('ld_pos', C.c_int),
+                ('scale', C.c_float),
+                ('q', void_p), ('ring', void_p), ('kv_len', void_p), ('out', void_p),
+                ('pos', void_p), ('bias_u', void_p), ('bias_v', void_p)]
+
+
 class Segment(C.Structure):
     _fields_ = [('offset', C.c_int64), ('len', C.c_int64), ('l2', C.c_float),
                 ('reserved', C.c_float)]
@@ -320,6 +330,13 @@ SIGNATURES = {
     'asr_dwconv1d_bwd': (C.c_int, [void_p] * 7 + [C.c_int] * 6 + [void_p, C.c_size_t, void_p]),
     'asr_dwconv1d_pad_fwd': (C.c_int, [void_p] * 5 + [C.c_int] * 7 + [void_p]),
     'asr_dwconv1d_pad_bwd': (C.c_int, [void_p] * 7 + [C.c_int] * 7 + [void_p, C.c_size_t, void_p]),
+    'asr_ring_put': (C.c_int, [void_p] * 2 + [C.c_int] * 8 + [void_p]),
+    'asr_attn_stream_plan': (C.c_int, [C.POINTER(AttnWindow), C.c_int, c_int_p]),
+    'asr_attn_stream_fwd': (C.c_int, [C.POINTER(AttnStreamArgs), C.POINTER(AttnWindow), void_p]),
+    'asr_relattn_stream_fwd': (C.c_int, [C.POINTER(AttnStreamArgs), C.POINTER(AttnWindow),
+                                         void_p]),
+    'asr_dwconv1d_stream_fwd': (C.c_int, [void_p] * 5 + [C.c_int] * 8 + [void_p]),
+    'asr_ctc_greedy_stream': (C.c_int, [void_p] * 3 + [C.c_int] * 4 + [void_p] * 3),
     'asr_glu_fwd': (C.c_int, [void_p] * 2 + [C.c_int64] + [C.c_int] * 3 + [void_p]),
     'asr_glu_bwd': (C.c_int, [void_p] * 3 + [C.c_int64] + [C.c_int] * 3 + [void_p]),
     'asr_swish_fwd': (C.c_int, [void_p] * 2 + [C.c_int64, void_p]),

@@ -62,6 +62,9 @@ PREDICT_FLAGS = [
     ('--subset', dict(type=str, default='test')),
 ] + _PLUGIN_FLAGS + [
     ('--no_decoder', dict(action='store_true', default=False)),
+    # chunk-by-chunk inference (Model.stream): feed every utterance in pieces of this many
+    # milliseconds of features; the decoder is then the greedy one
+    ('--stream', dict(default=None, type=float)),
 ] + _DEVICE_FLAGS + [
     ('--save', dict(default=None, type=str)),
     ('--override', dict(default=False, action='store_true')),
@@ -242,7 +245,12 @@ def eval_main(argv=None):
 def predict_main(argv=None):
     """predict.py: transcribe one audio file or a dataset split, one utterance per
     forward pass (batch_size=1, the reference's latency path); ``--no_decoder`` saves the
-    per-frame network outputs instead (HDF5: predictions vlen-f32 + num_labels, labels)."""
+    per-frame network outputs instead (HDF5: predictions vlen-f32 + num_labels, labels).
+    ``--stream MS`` feeds each utterance to a Model.stream session in pieces of MS milliseconds of
+    features and prints the growing greedy hypothesis per piece and the final one, which is the
+    non-streaming greedy result (under a convolution front-end: of the utterance with one zero
+    frame appended where its number of frames is odd, StreamSession.finish); a model that cannot
+    stream is refused with the session's message."""
     import numpy as np
     parser = make_parser('Predicting with an ASR system.', PREDICT_FLAGS)
     args = parser.parse_args(argv)
@@ -257,7 +265,8 @@ def predict_main(argv=None):
     model, meta = load_model(args.model, return_meta=True, mode='predict',
                              decoder=(not args.no_decoder), beam_width=args.beam_width,
                              lm=None if args.no_decoder else args.lm, lm_alpha=args.lm_alpha,
-                             lm_beta=args.lm_beta)
+                             lm_beta=args.lm_beta, is_greedy=args.stream is not None)
+    session = model.stream(1) if args.stream is not None else None
     # only the feature / label plugins are inherited from the training run (the reference
     # overlays every stored argument, predict.py:60, which would also import its --save)
     stored = {k: v for k, v in meta['training_args'].items()
@@ -276,7 +285,11 @@ def predict_main(argv=None):
     truth = list(flow.labels) if flow.labels is not None else [u''] * flow.len
     results = []
     for index in range(flow.len):
-        out = model.predict(flow.next())
+        if session is not None:
+            out = [_predict_streamed(session, flow.next(), args.stream, feature,
+                                     None if args.no_decoder else labels)]
+        else:
+            out = model.predict(flow.next())
         best = out[0] if args.no_decoder else labels.imap(out[0])
         results.append({'label': truth[index], 'best': best})
         print('Ground Truth: %s' % labels._sanitize(truth[index]))
@@ -295,6 +308,37 @@ def predict_main(argv=None):
                                attrs={'num_labels': int(results[0]['best'].shape[-1])})
             f.write_strings('labels', [str(r['label']) for r in results])
     return results
+
+
+def _predict_streamed(session, batch, ms, feature, labels):
+    """One utterance through a StreamSession in pieces of ``ms`` milliseconds of features (the
+    input parser's ``win_step`` per frame, 10 ms where it has none): prints the hypothesis as it
+    grows (labels: the label parser; None: the logits' frame count) and returns the whole."""
+    import numpy as np
+    x, lens = batch
+    if isinstance(x, tuple) and x[0] == 'slab':     # (features extracted on the device)
+        x = x[1][:, :1].permute(1, 0, 2)
+    else:
+        x = np.asarray(x, np.float32)
+    T = int(np.asarray(lens).reshape(-1)[0])
+    piece = max(1, int(round(ms / 1000.0 / float(getattr(feature, 'win_step', None) or 0.01))))
+    session.reset()
+    parts = []
+    for pos in range(0, T, piece):
+        end = min(T, pos + piece)
+        parts.append(session.feed(x[:, pos:end], ended=[T] if end == T else None))
+        _print_partial(parts, labels, end)
+    parts.append(session.finish())
+    if labels is None:
+        return np.concatenate([p[0] for p in parts], 0)
+    return [l for p in parts for l in p[0]]
+
+
+def _print_partial(parts, labels, frames):
+    if labels is None:
+        print('  %6d frames in: %d frames out' % (frames, sum(p.shape[1] for p in parts)))
+    else:
+        print('  %6d frames in: %s' % (frames, labels.imap([l for p in parts for l in p[0]])))
 
 
 # ------------------------------------------------------------------ align

@@ -1523,6 +1523,16 @@ class Model(object):
         dec, dlen = dec.cpu().numpy(), dlen.cpu().numpy()
         return [dec[n, :dlen[n]].tolist() for n in range(N)]
 
+    def stream(self, n_streams=1, step=None):
+        """A StreamSession (core/stream.py, K26): cached chunk-by-chunk inference of n_streams
+        streams in lock-step, ``step`` strided frames per internal step (a multiple of the
+        attention chunk; default: the smallest one >= 16).  Raises ValueError, naming the stage
+        and the reason, before any device call unless every attention stage has a window (chunk,
+        left >= 0, 0), every depthwise convolution is causal and every other stage is per-frame at
+        inference or the two-convolution front-end; NotImplementedError for a beam decoder."""
+        from .stream import StreamSession
+        return StreamSession(self, n_streams, step)
+
     def align(self, x, labels, inputs_length):
         """Forced alignment (K19): where in its utterance each label of a KNOWN transcript lies.
         ``x`` as predict takes it, ``labels`` a list of label lists, ``inputs_length`` in input

@@ -45,7 +45,16 @@ class Pass(object):
 
 Kind = collections.namedtuple(
     'Kind', 'build forward backward mask_shape needs_lens attention needs_in_len '
-            'extra_timeout_flags', defaults=(None, False, False, False, False))
+            'extra_timeout_flags stream', defaults=(None, False, False, False, False, None))
+
+# K26, chunk-by-chunk inference (core/stream.py).  ``stream(m, s, si, a, ss)`` runs a stage on the
+# slab ``a`` of the ss.Tq new frames [ss.t0, ss.t0 + ss.Tq) of a StreamSession ``ss``, whose
+# ss.state[si] holds what the stage carries from step to step; ``stream_check(m, s, si)`` (below)
+# says why a stage cannot stream.  The kinds of STREAM_AS_FORWARD are per-frame or the identity
+# at inference (bn: the running moments): the session calls their ``forward`` on the chunk slab.
+# A 'conv' stage belongs to the front-end, which the session runs itself.
+STREAM_AS_FORWARD = ('dense', 'ln', 'act', 'glu', 'merge', 'reshape', 'dropout', 'noise',
+                     'specaug', 'bn')
 
 
 def _no_fields(m, s, st, width):
@@ -179,6 +188,12 @@ def _posenc_build(m, s, st, width):
 def _posenc_forward(m, s, si, a, rec, fp):
     out = m._buf('posenc%d' % si, a.shape)
     return ops.posenc_add(a.contiguous(), out, min(fp.n_real, fp.n_pad), s.D)
+
+
+def _posenc_stream(m, s, si, a, ss):
+    """The rows [t0, t0 + Tq) of the table: it has no end, the session takes it ever longer."""
+    out = m._buf('posenc%d' % si, a.shape)
+    return ops.posenc_add(a.contiguous(), out, ss.N, s.D, pe=ss.posenc_rows(s.D))
 
 
 # --------------------------------------------------------------------------- merge
@@ -352,6 +367,20 @@ def _dwconv_backward(m, s, si, rec, da, bp):
                      else m._gview(s.ob, s.C), rec['N'], s.k, lens=rec['lens'],
                      **rec['pad'])
     return dx
+
+
+def _dwconv_stream(m, s, si, a, ss):
+    """The causal convolution of the new frames: they go into the stage's ring of input frames
+    (k - 1 + step rows, zero-filled when created or reset), which holds the k - 1 frames before
+    them from the steps before."""
+    a = a.contiguous()
+    st = ss.state.setdefault(si, {})
+    if 'ring' not in st:
+        st['ring'] = ss.zeros((s.k - 1 + ss.step, a.shape[1], a.shape[2]))
+    ops.ring_put(a, st['ring'], ss.t0)
+    out = m._buf('dwconv%d' % si, a.shape)
+    return ops.dwconv1d_stream_fwd(st['ring'], m._view(s.oW, s.k * s.C), m._view(s.ob, s.C),
+                                   ss.lens, out, ss.N, s.k, ss.t0)
 
 
 # --------------------------------------------------------------------------- bn
@@ -595,6 +624,56 @@ def _relmha_forward(m, s, si, a, rec, fp):
              bias=m._view(s.obo, s.n_out))
     rec.update(qkv=qkv, ctx=ctx, lse=lse, N=N, lens=fp.seq_len, pos=pos, win=win)
     return out
+
+
+def _mha_stream(m, s, si, a, ss):
+    """Both attention variants on the new frames: the qkv GEMM of the chunk, its [K | V] columns
+    into the stage's ring (THE RING of csrc/attn_tile.h, zero-filled when created or reset), the
+    streaming attention core of the new queries against the ring, the output projection.  The
+    relative table covers the relative indices of a visible pair, -(P - 1) .. P - 1 with P = left
+    + chunk; it is projected once per session (pe W_pos, exact fp32, as _relmha_forward does)."""
+    a = a.contiguous()
+    Tq, n_pad, _ = a.shape
+    rows, D = Tq * n_pad, s.D
+    chunk, left, _ = s.window
+    st = ss.state.setdefault(si, {})
+    if 'ring' not in st:
+        st['ring'] = ss.zeros((ops.attn_stream_plan(s.window, ss.step), n_pad, 2 * D))
+    qkv = m._buf('qkv%d' % si, (Tq, n_pad, 3 * D))
+    ops.gemm(a, m.params, qkv, rows, 3 * D, s.f_in_pad, b_off=s.oW, bias=m._view(s.ob, 3 * D))
+    ops.ring_put(qkv, st['ring'], ss.t0, col0=D, cols=2 * D)
+    ctx = m._buf('attn%d' % si, (Tq, n_pad, D))
+    if getattr(s, 'relative', False):
+        if 'pos' not in st:
+            P_ = left + chunk
+            st['pos'] = ss.zeros((2 * P_ - 1, D))
+            ops.gemm(ops.relpos_get(P_, D, a.device), m.params, st['pos'], 2 * P_ - 1, D, D,
+                     b_off=s.oWp, precision=0)
+        ops.relattn_stream_fwd(qkv, st['ring'], ss.lens, st['pos'], m._view(s.obu, D),
+                               m._view(s.obv, D), ctx, ss.N, s.heads, s.dh, ss.t0, s.window)
+    else:
+        ops.attn_stream_fwd(qkv, st['ring'], ss.lens, ctx, ss.N, s.heads, s.dh, ss.t0, s.window)
+    out = m._buf('mha%d' % si, (Tq, n_pad, s.n_out))
+    ops.gemm(ctx, m.params, out, rows, s.n_out, D, b_off=s.oWo, bias=m._view(s.obo, s.n_out))
+    return out
+
+
+def stream_check(m, s, si):
+    """Why stage si cannot run chunk by chunk (K26), or None: no device is touched."""
+    kind = KINDS[s.kind]
+    if s.kind == 'mha':
+        w = getattr(s, 'window', None)
+        if w is None or w[1] < 0 or w[2] != 0:
+            return ('its context is %r: a streaming attention layer needs a window (chunk, left '
+                    '>= 0, 0), a bounded left context and no right context' % (w,))
+    elif s.kind == 'dwconv':
+        if getattr(s, 'pad_left', None) != s.k - 1:
+            return 'it is not causal (causal=True: no output frame reads a later input frame)'
+    elif s.kind == 'conv':
+        return None                 # (the front-end: checked as a whole by the session)
+    elif kind.stream is None and s.kind not in STREAM_AS_FORWARD:
+        return 'a %s stage reads the whole utterance' % s.kind
+    return None
 
 
 # --------------------------------------------------------------------------- bilstm
@@ -917,14 +996,17 @@ KINDS = {
     'specaug': Kind(_specaug_build, _specaug_forward, _pass_through, needs_in_len=True),
     'act': Kind(_act_build, _act_forward, _act_backward),
     'glu': Kind(_glu_build, _glu_forward, _glu_backward),
-    'posenc': Kind(_posenc_build, _posenc_forward, _pass_through),   # d(x + pe) / dx = 1
+    'posenc': Kind(_posenc_build, _posenc_forward, _pass_through,    # d(x + pe) / dx = 1
+                   stream=_posenc_stream),
     'merge': Kind(_merge_build, _merge_forward, _merge_backward),
     'dense': Kind(_dense_build, _dense_forward, _dense_backward),
     'conv': Kind(_conv_build, _conv_forward, _conv_backward),
-    'dwconv': Kind(_dwconv_build, _dwconv_forward, _dwconv_backward, needs_lens=True),
+    'dwconv': Kind(_dwconv_build, _dwconv_forward, _dwconv_backward, needs_lens=True,
+                   stream=_dwconv_stream),
     'bn': Kind(_bn_build, _bn_forward, _bn_backward),
     'ln': Kind(_ln_build, _ln_forward, _ln_backward),
-    'mha': Kind(_mha_build, _mha_forward, _mha_backward, needs_lens=True, attention=True),
+    'mha': Kind(_mha_build, _mha_forward, _mha_backward, needs_lens=True, attention=True,
+                stream=_mha_stream),
     'bilstm': Kind(_bilstm_build, _bilstm_forward, _bilstm_backward, mask_shape=_mask_shape),
     'birnn': Kind(_birnn_build, _birnn_forward, _birnn_backward, mask_shape=_mask_shape,
                   extra_timeout_flags=True),

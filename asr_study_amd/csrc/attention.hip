@@ -104,34 +104,15 @@ __global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(const float* __res
     float s[4][4];
     at_dot<DH>(Qs, Ks, ty, tx, s);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float mx = asr_neg_inf();
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int u = k0 + tx + 16 * j;
         bool vis = u < len;
         if constexpr (WIN) vis = u >= wlo[i] && u < whi[i];
         s[i][j] = vis ? s[i][j] * g.c2 : asr_neg_inf();
-        mx = fmaxf(mx, s[i][j]);
       }
-      // without a window finite: key k0 of every tile is a valid one.  Under a window a row may
-      // have seen no key yet (m, mx both -inf): exp2f(-inf - -inf) is NaN, so subtract 0 then --
-      // alpha = 0 scales sums that are 0, every p = exp2f(-inf) = 0, l stays 0
-      mx = fmaxf(m[i], at_max16(mx));
-      float mref = mx;
-      if constexpr (WIN) mref = mx == asr_neg_inf() ? 0.f : mx;
-      const float alpha = exp2f(m[i] - mref);
-      float sum = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s[i][j] = exp2f(s[i][j] - mref);
-        sum += s[i][j];
-      }
-      l[i] = fmaf(l[i], alpha, at_sum16(sum));
-      m[i] = mx;
-#pragma unroll
-      for (int jj = 0; jj < NJ; ++jj) o[i][jj] *= alpha;
-    }
+    at_softmax_tile<NJ, WIN>(s, m, l, o);
     at_put_tile(Ps, s, ty, tx);
     __syncthreads();
     at_acc<DH>(Ps, Vs, ty, tx, o);
@@ -153,6 +134,95 @@ __global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(const float* __res
       if constexpr (WIN) v = l[i] == 0.f ? 0.f : v;
       lse[((size_t)t * g.n_pad + n) * g.heads + h] = v;
     }
+  }
+}
+
+// K26, the streaming forward: the queries [t0, t0 + Tq) of the windowed forward above, Q from the
+// chunk's slab (Tq, n_pad, ld), K and V from THE RING of attn_tile.h, columns [K | V] of
+// (R, n_pad, ld_kv).  A workgroup owns up to 64 consecutive new queries and walks the ABSOLUTE
+// 64-aligned key tiles asr_attn_win_fwd walks: a row's running maximum and sum depend only on how
+// its visible keys are split into tiles and on each key's column inside its tile, and a tile
+// without a visible key for the row is an exact no-op (alpha = 1, or 0 on sums that are 0), so
+// the rows come out bit for bit as from the whole-utterance call.  kv_len[n] (device int32, the
+// absolute frames of stream n that are valid so far) plays the part of lens; a key at or past
+// t0 + Tq does not exist yet and is never visible.  No lse.
+struct AtsGeo {
+  int Tq, N, n_pad, heads, ld, ld_kv, ld_out, R, t0;
+  float c2;         // scale * log2(e)
+};
+
+__device__ __forceinline__ int ats_len(const int* kv_len, int n, int end) {
+  const int len = kv_len[n];
+  return len < 1 ? 1 : (len > end ? end : len);       // (as at_len)
+}
+
+template <int DH>
+__global__ __launch_bounds__(AT_THREADS) void attn_stream_kernel(const float* __restrict__ q,
+                                                                 const float* __restrict__ ring,
+                                                                 const int* __restrict__ kv_len,
+                                                                 float* __restrict__ out,
+                                                                 AtsGeo g, asr_attn_window w) {
+  constexpr int DP = DH + 4, NJ = DH / 16;
+  extern __shared__ float4 at_lds4[];
+  float* Qs = reinterpret_cast<float*>(at_lds4);
+  float* Ks = Qs + AT_TILE * DP;
+  float* Vs = Ks + AT_TILE * DP;
+  float* Ps = Vs + AT_TILE * DP;
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int r0 = blockIdx.x * AT_TILE, h = blockIdx.y, n = blockIdx.z;   // r0: row of the chunk
+  const int D = g.heads * DH;
+  const size_t rs = (size_t)g.n_pad * g.ld, rsk = (size_t)g.n_pad * g.ld_kv;
+  const size_t rso = (size_t)g.n_pad * g.ld_out;
+  float* o_base = out + (size_t)n * g.ld_out;
+  if (h == 0) at_zero_cols(o_base, rso, r0, g.Tq, D, g.ld_out - D, tid);
+  if (n >= g.N) {
+    at_zero_cols(o_base, rso, r0, g.Tq, h * DH, DH, tid);
+    return;
+  }
+  const float* kbase = ring + (size_t)n * g.ld_kv + h * DH;
+  const int len = ats_len(kv_len, n, g.t0 + g.Tq);
+  at_load_tile<DH>(Qs, q + (size_t)n * g.ld + h * DH, rs, r0, g.Tq, tid);
+  float m[4], l[4], o[4][NJ];
+  int wlo[4], whi[4];                       // the visible keys of row i
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    m[i] = asr_neg_inf();
+    l[i] = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) o[i][jj] = 0.f;
+    wlo[i] = at_win_lo(w, g.t0 + r0 + 4 * ty + i);
+    whi[i] = min(at_win_hi(w, g.t0 + r0 + 4 * ty + i), len);
+  }
+  const int qa = g.t0 + r0, qb = g.t0 + min(r0 + AT_TILE, g.Tq) - 1;
+  const int kb = at_win_lo(w, qa) / AT_TILE * AT_TILE, ke = min(at_win_hi(w, qb), len);
+  for (int k0 = kb; k0 < ke; k0 += AT_TILE) {
+    // (k0 and R are multiples of 64: the tile is 64 consecutive ring rows; rows >= len: zeros)
+    const float* tile = kbase + (size_t)(k0 % g.R) * rsk;
+    at_load_tile<DH>(Ks, tile, rsk, 0, len - k0, tid);
+    at_load_tile<DH>(Vs, tile + D, rsk, 0, len - k0, tid);
+    __syncthreads();
+    float s[4][4];
+    at_dot<DH>(Qs, Ks, ty, tx, s);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int u = k0 + tx + 16 * j;
+        s[i][j] = (u >= wlo[i] && u < whi[i]) ? s[i][j] * g.c2 : asr_neg_inf();
+      }
+    at_softmax_tile<NJ, true>(s, m, l, o);
+    at_put_tile(Ps, s, ty, tx);
+    __syncthreads();
+    at_acc<DH>(Ps, Vs, ty, tx, o);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int r = r0 + 4 * ty + i;
+    if (r >= g.Tq) continue;
+    float* orow = o_base + (size_t)r * rso + h * DH;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) orow[tx + 16 * jj] = l[i] == 0.f ? 0.f : o[i][jj] / l[i];
   }
 }
 
@@ -495,6 +565,36 @@ extern "C" int asr_attn_win_bwd(const asr_attn_args* a, const asr_attn_window* w
                                 size_t ws_bytes, asr_stream_t stream) {
   ASR_CHECK_ARG(at_win_ok(w), "attn_win_bwd: bad window (" AT_WIN_TEXT ")");
   return at_bwd(a, w, workspace, ws_bytes, stream);
+}
+
+extern "C" int asr_attn_stream_plan(const asr_attn_window* w, int max_tq, int* ring_rows) {
+  ASR_CHECK_ARG(at_stream_win_ok(w) && max_tq >= 1 && max_tq <= (1 << 20),
+                "attn_stream_plan: bad window (chunk >= 1, left >= 0, right = 0) or max_tq %d",
+                max_tq);
+  if (ring_rows) *ring_rows = at_ring_rows(*w, max_tq);
+  return ASR_OK;
+}
+
+extern "C" int asr_attn_stream_fwd(const asr_attn_stream_args* a, const asr_attn_window* w,
+                                   asr_stream_t stream) {
+  const char* bad = at_stream_bad(a, w, 128, false);
+  ASR_CHECK_ARG(bad == nullptr, "attn_stream_fwd: %s", bad);
+  AtsGeo g;
+  g.Tq = a->Tq, g.N = a->N, g.n_pad = a->n_pad, g.heads = a->heads, g.ld = a->ld;
+  g.ld_kv = a->ld_kv, g.ld_out = a->ld_out, g.R = a->R, g.t0 = a->t0;
+  g.c2 = a->scale * AT_LOG2E;
+  const dim3 grid((a->Tq + AT_TILE - 1) / AT_TILE, a->heads, a->n_pad);
+  const size_t lds = at_lds_bytes(a->dh, 0);
+#define AT_STREAM(DH)                                                                           \
+  {                                                                                             \
+    if (at_allow_lds(attn_stream_kernel<DH>, lds) != ASR_OK) return ASR_ERR_LAUNCH;             \
+    hipLaunchKernelGGL((attn_stream_kernel<DH>), grid, dim3(AT_THREADS), lds,                   \
+                       (hipStream_t)stream, a->q, a->ring, a->kv_len, a->out, g, *w);           \
+  }
+  AT_DISPATCH(AT_STREAM)
+#undef AT_STREAM
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
 }
 
 extern "C" int asr_posenc_add(const float* x, const float* pe, float* y, int T, int N, int n_pad,

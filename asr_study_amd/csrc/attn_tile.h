@@ -100,6 +100,37 @@ __device__ __forceinline__ void at_put_tile(float* P, const float (&s)[4][4], in
     for (int j = 0; j < 4; ++j) P[(4 * ty + i) * AT_PP + tx + 16 * j] = s[i][j];
 }
 
+// The running softmax of the forward kernels over one key tile: s holds the tile's scaled scores
+// of rows 4 ty + i (a key that is not visible: -inf) and leaves as p = exp2(s - max); m, l are the
+// rows' running maximum and sum, o their running output, rescaled by alpha.  GUARD (under a
+// window): a row may have seen no key yet (m, mx both -inf), and exp2f(-inf - -inf) is NaN, so 0
+// is subtracted then -- alpha = 0 scales sums that are 0, every p = exp2f(-inf) = 0, l stays 0.
+// Without it the maximum is finite: key k0 of every tile is a valid one.
+template <int NJ, bool GUARD>
+__device__ __forceinline__ void at_softmax_tile(float (&s)[4][4], float (&m)[4], float (&l)[4],
+                                                float (&o)[4][NJ]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float mx = asr_neg_inf();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) mx = fmaxf(mx, s[i][j]);
+    mx = fmaxf(m[i], at_max16(mx));
+    float mref = mx;
+    if constexpr (GUARD) mref = mx == asr_neg_inf() ? 0.f : mx;
+    const float alpha = exp2f(m[i] - mref);
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      s[i][j] = exp2f(s[i][j] - mref);
+      sum += s[i][j];
+    }
+    l[i] = fmaf(l[i], alpha, at_sum16(sum));
+    m[i] = mx;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) o[i][jj] *= alpha;
+  }
+}
+
 // zeros into columns [c0, c0 + w) of rows [r0, min(r0 + 64, r_end)) of a slab (any w >= 0)
 __device__ __forceinline__ void at_zero_cols(float* dst, size_t row_stride, int r0, int r_end,
                                              int c0, int w, int tid) {
@@ -164,7 +195,72 @@ inline long long at_win_tile_pairs(const asr_attn_window& w, int T) {
   return pairs;
 }
 
+// THE RING (K26), defined here once for the streaming forms of attention.hip and
+// rel_attention.hip and their plan.  A ring is a slab (R, n_pad, ld): absolute frame u of the
+// stream lives in ring row u % R.  R is a multiple of 64, so a 64-frame tile that starts at an
+// absolute multiple of 64 is contiguous in the ring and at_load_tile reads it through a shifted
+// base pointer.  A call states the absolute index t0 of its first new frame and their count Tq;
+// the caller has put the new frames into the ring beforehand.  The first key tile the call walks
+// starts at lo(t0) / 64 * 64, the last frame it holds is t0 + Tq - 1: the ring is valid for the
+// call iff R >= at_ring_need.  Rows that hold frames below a query's lo are stale (older frames,
+// or the zeros the owner filled the ring with): finite, and they meet p = exactly 0 only.
+__host__ __device__ __forceinline__ long long at_ring_need(const asr_attn_window& w, int t0,
+                                                           int Tq) {
+  return (long long)t0 + Tq - at_win_lo(w, t0) / AT_TILE * AT_TILE;
+}
+// The smallest ring that is valid for EVERY t0 >= 0 and every count up to Tq: never more than
+// left + chunk - 1 + Tq + 63 rounded up to 64 (t0 - lo(t0) <= left + chunk - 1, lo % 64 <= 63),
+// less where chunk and left keep lo(t0) % 64 away from 63.  lo(t0) % 64 has a period of at most 64
+// chunks once c0 >= left, and the last frame of a chunk is the worst t0 of that chunk.
+inline int at_ring_rows(const asr_attn_window& w, int Tq) {
+  long long need = 0;
+  const long long chunks = (long long)w.left / w.chunk + AT_TILE + 2;
+  for (long long m = 0; m < chunks; ++m) {
+    const long long n = at_ring_need(w, (int)(m * w.chunk + w.chunk - 1), Tq);
+    need = n > need ? n : need;
+  }
+  return (int)((need + AT_TILE - 1) / AT_TILE * AT_TILE);
+}
+// what a streaming call needs of its window and ring: a bounded left context, no right context
+// (a key past the newest frame does not exist yet)
+__host__ __device__ __forceinline__ bool at_stream_win_ok(const asr_attn_window* w) {
+  return at_win_ok(w) && w->left >= 0 && w->right == 0 && w->chunk <= (1 << 20) &&
+         w->left <= (1 << 20);
+}
+
 bool at_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// What is wrong with a streaming call (asr_attn_stream_fwd, asr_relattn_stream_fwd: rel, with
+// dh <= max_dh), or nullptr: checked on the host before any device call.
+inline const char* at_stream_bad(const asr_attn_stream_args* a, const asr_attn_window* w,
+                                 int max_dh, bool rel) {
+  if (!at_stream_win_ok(w)) return "bad window (chunk >= 1, left >= 0, right = 0)";
+  if (a == nullptr || a->Tq < 1 || a->N < 1 || a->n_pad < a->N || a->n_pad > 65535)
+    return "bad geometry (Tq >= 1, 1 <= N <= n_pad <= 65535)";
+  if (a->heads < 1 || a->heads > 65535 || a->dh < 16 || a->dh > max_dh || (a->dh & 15))
+    return "bad geometry (heads >= 1, dh a multiple of 16 within the kernel's range)";
+  const long long D = (long long)a->heads * a->dh;
+  if ((a->ld & 3) || a->ld < D || (a->ld_kv & 3) || a->ld_kv < 2 * D || (a->ld_out & 3) ||
+      a->ld_out < D)
+    return "bad geometry (ld >= heads dh, ld_kv >= 2 heads dh, ld_out >= heads dh, multiples of 4)";
+  if (a->t0 < 0 || (long long)a->t0 + a->Tq > 0x7fffffffLL - 2 * AT_TILE - w->chunk)
+    return "bad geometry (t0 >= 0, t0 + Tq below 2^31)";
+  if (a->R < AT_TILE || (a->R % AT_TILE) || a->R < at_ring_need(*w, a->t0, a->Tq))
+    return "bad ring (R a multiple of 64, R >= t0 + Tq - lo(t0) / 64 * 64)";
+  if (!(a->scale > 0.f && a->scale < 1e30f)) return "bad scale";
+  if (!a->q || !a->ring || !a->kv_len || !a->out || a->out == a->q)
+    return "q, ring, kv_len and out are required";
+  if (!at_aligned(a->q) || !at_aligned(a->ring) || !at_aligned(a->out))
+    return "q, ring, out 16-byte aligned";
+  if (rel) {
+    if (a->P < (long long)w->left + w->chunk || (a->ld_pos & 3) || a->ld_pos < D ||
+        (2LL * a->P - 1) * a->ld_pos > 0x7fffffffLL)
+      return "bad table (P >= left + chunk rows each side, ld_pos >= heads dh, a multiple of 4)";
+    if (!a->pos || !a->bias_u || !a->bias_v || !at_aligned(a->pos))
+      return "pos (16-byte aligned), bias_u and bias_v are required";
+  }
+  return nullptr;
+}
 
 template <typename K>
 int at_allow_lds(K kernel, size_t bytes) {

@@ -494,11 +494,15 @@ ctc_grad_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
 }
 
 // ---------------------------------------------------------------------------
-// greedy decode: one 256-thread block per utterance.
+// greedy decode: one 256-thread block per utterance.  CARRY (K26, asr_ctc_greedy_stream): the
+// logits are one chunk of a stream, and state[n] carries the arg-max of the stream's last valid
+// frame from call to call (-1: none yet), so a repeat across the boundary is merged; without it
+// `state` is not read and the code is what it was.
+template <bool CARRY>
 __global__ void __launch_bounds__(256)
 ctc_greedy_kernel(const float* __restrict__ logits, const int* __restrict__ seq_len,
                   int T, int N, int n_pad, int C, int* __restrict__ decoded,
-                  int* __restrict__ decoded_len) {
+                  int* __restrict__ decoded_len, int* __restrict__ state) {
   const int n = blockIdx.x;
   const int tid = threadIdx.x;
   const int blank = C - 1;
@@ -507,7 +511,11 @@ ctc_greedy_kernel(const float* __restrict__ logits, const int* __restrict__ seq_
   __shared__ int s_best[256 + 1];
   __shared__ int s_scan[256];
   __shared__ int s_base;
-  if (tid == 0) { s_base = 0; s_best[0] = -1; }
+  if (tid == 0) {
+    s_base = 0;
+    s_best[0] = -1;
+    if constexpr (CARRY) s_best[0] = state[n];
+  }
   __syncthreads();
   for (int t0 = 0; t0 < T; t0 += 256) {
     const int t = t0 + tid;
@@ -516,6 +524,9 @@ ctc_greedy_kernel(const float* __restrict__ logits, const int* __restrict__ seq_
       const float* r = logits + ((size_t)t * n_pad + n) * C;
       float bv = r[0]; best = 0;
       for (int c = 1; c < C; ++c) { const float v = r[c]; if (v > bv) { bv = v; best = c; } }
+      if constexpr (CARRY) {
+        if (t == Tn - 1) state[n] = best;   // (read above, before the first barrier)
+      }
     }
     // s_best[0] carries the previous chunk's last argmax
     s_best[tid + 1] = best;
@@ -786,8 +797,21 @@ extern "C" int asr_ctc_greedy(const float* logits, const int* seq_len, int T, in
   hipStream_t stream = (hipStream_t)stream_;
   ASR_CHECK_ARG(logits && seq_len && decoded && decoded_len, "greedy: null pointer");
   ASR_CHECK_ARG(T > 0 && N > 0 && n_pad >= N && C >= 2, "greedy: bad shape");
-  hipLaunchKernelGGL(ctc_greedy_kernel, dim3(N), dim3(256), 0, stream, logits, seq_len,
-                     T, N, n_pad, C, decoded, decoded_len);
+  hipLaunchKernelGGL(ctc_greedy_kernel<false>, dim3(N), dim3(256), 0, stream, logits, seq_len,
+                     T, N, n_pad, C, decoded, decoded_len, (int*)nullptr);
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
+}
+
+extern "C" int asr_ctc_greedy_stream(const float* logits, const int* seq_len, int* state, int T,
+                                     int N, int n_pad, int C, int* decoded, int* decoded_len,
+                                     asr_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ASR_CHECK_ARG(logits && seq_len && state && decoded && decoded_len,
+                "greedy_stream: null pointer");
+  ASR_CHECK_ARG(T > 0 && N > 0 && n_pad >= N && C >= 2, "greedy_stream: bad shape");
+  hipLaunchKernelGGL(ctc_greedy_kernel<true>, dim3(N), dim3(256), 0, stream, logits, seq_len,
+                     T, N, n_pad, C, decoded, decoded_len, state);
   ASR_CHECK_LAUNCH();
   return ASR_OK;
 }

@@ -108,6 +108,25 @@ __device__ __forceinline__ void dw_stage(float4* __restrict__ dst, const float* 
   }
 }
 
+// acc[r] += sum_j Ws[j] Xs[ts * DW_R + r + j], j ascending: the register window of the forward
+// kernels (one tap and ONE new frame read per tap)
+__device__ __forceinline__ void dw_taps(const float4* __restrict__ Xs,
+                                        const float4* __restrict__ Ws, int cg, int ts, int k,
+                                        float4 (&acc)[DW_R]) {
+  const float4* xr = Xs + (ts * DW_R) * DW_CG + cg;
+  float4 x0 = xr[0], x1 = xr[DW_CG], x2 = xr[2 * DW_CG];
+#pragma unroll 4
+  for (int j = 0; j < k; ++j) {
+    const float4 wv = Ws[j * DW_CG + cg];
+    const float4 x3 = xr[(j + 3) * DW_CG];        // (row ts * 4 + j + 3 <= DW_TT + k - 2)
+    acc[0] = fma4(wv, x0, acc[0]);
+    acc[1] = fma4(wv, x1, acc[1]);
+    acc[2] = fma4(wv, x2, acc[2]);
+    acc[3] = fma4(wv, x3, acc[3]);
+    x0 = x1, x1 = x2, x2 = x3;
+  }
+}
+
 // out[t] = bias + sum_j w'[j] in_m[t + j - p] over the tile, p the left padding; flip: w'[j] = w[k - 1 - j] (the input
 // gradient).  mask_in: the input's frames >= len are zeros; mask_out: the output's are.
 __global__ void __launch_bounds__(DW_THREADS)
@@ -137,18 +156,7 @@ dw_conv_kernel(const float* __restrict__ in, const float* __restrict__ w,
 #pragma unroll
       for (int r = 0; r < DW_R; ++r) acc[r] = b;
     }
-    const float4* xr = Xs + (ts * DW_R) * DW_CG + cg;
-    float4 x0 = xr[0], x1 = xr[DW_CG], x2 = xr[2 * DW_CG];
-#pragma unroll 4
-    for (int j = 0; j < k; ++j) {
-      const float4 wv = Ws[j * DW_CG + cg];
-      const float4 x3 = xr[(j + 3) * DW_CG];        // (row ts * 4 + j + 3 <= DW_TT + k - 2)
-      acc[0] = fma4(wv, x0, acc[0]);
-      acc[1] = fma4(wv, x1, acc[1]);
-      acc[2] = fma4(wv, x2, acc[2]);
-      acc[3] = fma4(wv, x3, acc[3]);
-      x0 = x1, x1 = x2, x2 = x3;
-    }
+    dw_taps(Xs, Ws, cg, ts, k, acc);
   }
   if (!q.in) return;
 #pragma unroll
@@ -157,6 +165,53 @@ dw_conv_kernel(const float* __restrict__ in, const float* __restrict__ w,
     if (t >= T) break;
     const bool on = q.real && (!mask_out || t < q.len);
     st4(out + (size_t)t * W + q.col, on ? acc[r] : zero4());
+  }
+}
+
+// K26, the streaming causal convolution: the output frames [t0, t0 + Tq) of dw_conv_kernel with
+// p = k - 1, whose input is a ring (Rc >= k - 1 + Tq, n_pad, ld) that holds absolute frame u in
+// row u % Rc (rows are indexed one by one: Rc need not be a multiple of anything).  Frames < 0
+// and frames >= lens[n] (absolute, clamped to 0 .. t0 + Tq) are zeros by a select.  The same
+// tiles, the same taps in the same order: bit for bit the rows of the whole-utterance call.
+__global__ void __launch_bounds__(DW_THREADS)
+dw_stream_kernel(const float* __restrict__ ring, const float* __restrict__ w,
+                 const float* __restrict__ bias, const int* __restrict__ lens,
+                 float* __restrict__ out, int Tq, int N, int C, int ld, long long W, int k, int Rc,
+                 int t0) {
+  extern __shared__ float4 dw_sm[];
+  const int rows = DW_TT + k - 1;
+  float4* Xs = dw_sm;                       // rows x DW_CG
+  float4* Ws = dw_sm + rows * DW_CG;        // k x DW_CG
+  const int cg = threadIdx.x % DW_CG, ts = threadIdx.x / DW_CG;
+  const int r0 = blockIdx.y * DW_TT;        // first output row of the tile within the chunk
+  const DwCol q = dw_column(cg, t0 + Tq, N, C, ld, W, lens);
+  const bool any_real = ((long long)blockIdx.x * DW_CG * 4) / ld < N;
+  float4 acc[DW_R];
+#pragma unroll
+  for (int r = 0; r < DW_R; ++r) acc[r] = zero4();
+  if (any_real) {
+    for (int r = ts; r < rows; r += DW_TS) {
+      const int u = t0 + r0 + r - (k - 1);
+      float4 v = zero4();
+      if (q.real && u >= 0 && u < q.len) v = ld4(ring + (size_t)(u % Rc) * W + q.col);
+      Xs[r * DW_CG + cg] = v;
+    }
+    for (int j = ts; j < k; j += DW_TS)
+      Ws[j * DW_CG + cg] = q.real ? ld4(w + (size_t)j * C + q.c) : zero4();
+    __syncthreads();
+    if (q.real) {
+      const float4 b = ld4(bias + q.c);
+#pragma unroll
+      for (int r = 0; r < DW_R; ++r) acc[r] = b;
+    }
+    dw_taps(Xs, Ws, cg, ts, k, acc);
+  }
+  if (!q.in) return;
+#pragma unroll
+  for (int r = 0; r < DW_R; ++r) {
+    const int t = r0 + ts * DW_R + r;
+    if (t >= Tq) break;
+    st4(out + (size_t)t * W + q.col, q.real ? acc[r] : zero4());
   }
 }
 
@@ -386,6 +441,27 @@ extern "C" int asr_dwconv1d_pad_fwd(const float* x, const float* w, const float*
   hipLaunchKernelGGL(dw_conv_kernel, dim3(g.chunks, g.tiles), dim3(DW_THREADS), dw_lds_fwd(g),
                      (hipStream_t)stream, x, w, b, lens, y, T, N, C, ld, g.W, k, pad_left, 0, 1,
                      0);
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
+}
+
+extern "C" int asr_dwconv1d_stream_fwd(const float* ring, const float* w, const float* b,
+                                       const int* lens, float* y, int Tq, int N, int n_pad, int C,
+                                       int ld, int k, int ring_rows, int t0,
+                                       asr_stream_t stream) {
+  const int T = Tq;
+  DW_GEO_OR_FAIL("dwconv1d_stream_fwd");
+  ASR_CHECK_ARG(t0 >= 0 && (long long)t0 + Tq <= 0x7fffffffLL - DW_TT - DW_MAXK,
+                "dwconv1d_stream_fwd: t0 %d (>= 0, t0 + Tq below 2^31)", t0);
+  ASR_CHECK_ARG(ring_rows >= k - 1 + Tq, "dwconv1d_stream_fwd: a ring of %d rows (k - 1 + Tq = "
+                "%d needed)", ring_rows, k - 1 + Tq);
+  ASR_CHECK_ARG(ring && w && b && lens && y && y != ring,
+                "dwconv1d_stream_fwd: ring, w, b, lens, y are required (y != ring)");
+  ASR_CHECK_ARG(dw_aligned(ring) && dw_aligned(w) && dw_aligned(b) && dw_aligned(y),
+                "dwconv1d_stream_fwd: ring, w, b, y must be 16-byte aligned");
+  hipLaunchKernelGGL(dw_stream_kernel, dim3(g.chunks, g.tiles), dim3(DW_THREADS), dw_lds_fwd(g),
+                     (hipStream_t)stream, ring, w, b, lens, y, Tq, N, C, ld, g.W, k, ring_rows,
+                     t0);
   ASR_CHECK_LAUNCH();
   return ASR_OK;
 }

@@ -285,7 +285,47 @@ axpby_kernel(int64_t n, float a, const float* __restrict__ x, float b,
   for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
     out[i] = a * x[i] + b * y[i];
 }
+
+// K26: rows [0, Tq) of the columns [col0, col0 + cols) of a slab (Tq, n_pad, ld_src) into the
+// columns [0, cols) of the ring rows (t0 + i) % R of (R, n_pad, ld_ring); one item = one float4
+__global__ void __launch_bounds__(256)
+ring_put_kernel(const float* __restrict__ src, float* __restrict__ ring, int64_t items, int n_pad,
+                int ld_src, int col0, int c4, int ld_ring, int R, int t0) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t per_row = (int64_t)n_pad * c4;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += stride) {
+    const int64_t row = i / per_row, rem = i - row * per_row;
+    const int n = (int)(rem / c4), c = (int)(rem - (int64_t)n * c4) * 4;
+    const int64_t dst_row = (t0 + row) % R;
+    const float4 v =
+        *reinterpret_cast<const float4*>(src + (row * n_pad + n) * ld_src + col0 + c);
+    *reinterpret_cast<float4*>(ring + (dst_row * n_pad + n) * ld_ring + c) = v;
+  }
+}
 }  // namespace
+
+extern "C" int asr_ring_put(const float* src, float* ring, int Tq, int n_pad, int ld_src, int col0,
+                            int cols, int ld_ring, int ring_rows, int t0, asr_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ASR_CHECK_ARG(src && ring && src != ring, "ring_put: src and ring are required (not the same)");
+  ASR_CHECK_ARG(Tq >= 1 && n_pad >= 1 && ring_rows >= Tq && t0 >= 0 &&
+                    (long long)t0 + Tq <= 0x7fffffffLL,
+                "ring_put: bad geometry (Tq %d n_pad %d ring rows %d t0 %d; 1 <= Tq <= ring rows, "
+                "t0 >= 0)", Tq, n_pad, ring_rows, t0);
+  ASR_CHECK_ARG(cols >= 4 && !(cols & 3) && col0 >= 0 && !(col0 & 3) && !(ld_src & 3) &&
+                    !(ld_ring & 3) && (long long)col0 + cols <= ld_src && cols <= ld_ring,
+                "ring_put: bad columns (col0 %d cols %d ld_src %d ld_ring %d; multiples of 4, "
+                "col0 + cols <= ld_src, cols <= ld_ring)", col0, cols, ld_src, ld_ring);
+  ASR_CHECK_ARG(((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(ring)) & 15) == 0,
+                "ring_put: 16-byte alignment");
+  const int64_t items = (int64_t)Tq * n_pad * (cols / 4);
+  int64_t blocks = (items + 255) / 256;
+  if (blocks > 4096) blocks = 4096;       // (the cap of the flat kernels: a grid-stride loop)
+  hipLaunchKernelGGL(ring_put_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src, ring,
+                     items, n_pad, ld_src, col0, cols / 4, ld_ring, ring_rows, t0);
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
+}
 
 extern "C" int asr_axpby(int64_t n, float a, const float* x, float b, const float* y, float* out,
                          asr_stream_t stream_) {

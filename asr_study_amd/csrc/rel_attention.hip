@@ -188,7 +188,6 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_fwd_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = 4 * ty + i;
-      float mx = asr_neg_inf();
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int col = tx + 16 * j;
@@ -196,25 +195,9 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_fwd_kernel(
         bool vis = k0 + col < len;
         if constexpr (WIN) vis = k0 + col >= wlo[i] && k0 + col < whi[i];
         s[i][j] = vis ? (s[i][j] + sp) * g.c2 : asr_neg_inf();
-        mx = fmaxf(mx, s[i][j]);
       }
-      // without a window finite: key k0 of every tile is a valid one.  Under a window a row may
-      // have seen no key yet (m, mx both -inf, attention.hip): subtract 0 then, l stays 0
-      mx = fmaxf(m[i], at_max16(mx));
-      float mref = mx;
-      if constexpr (WIN) mref = mx == asr_neg_inf() ? 0.f : mx;
-      const float alpha = exp2f(m[i] - mref);
-      float sum = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s[i][j] = exp2f(s[i][j] - mref);
-        sum += s[i][j];
-      }
-      l[i] = fmaf(l[i], alpha, at_sum16(sum));
-      m[i] = mx;
-#pragma unroll
-      for (int jj = 0; jj < NJ; ++jj) o[i][jj] *= alpha;
     }
+    at_softmax_tile<NJ, WIN>(s, m, l, o);
     __syncthreads();                        // (every G read before P overwrites it)
     at_put_tile(Ps, s, ty, tx);
     __syncthreads();
@@ -237,6 +220,106 @@ __global__ __launch_bounds__(AT_THREADS) void relattn_fwd_kernel(
       if constexpr (WIN) v = l[i] == 0.f ? 0.f : v;
       lse[((size_t)t * g.n_pad + n) * g.heads + h] = v;
     }
+  }
+}
+
+// K26, the streaming forward: attn_stream_kernel of attention.hip (Q from the chunk's slab, K and
+// V from THE RING of attn_tile.h, the absolute 64-aligned key tiles of the whole-utterance call,
+// kv_len for lens) with the relative term.  pos is a table of 2P - 1 rows, row r + P - 1 the
+// relative index r, P >= left + chunk: it covers every visible pair (0 <= t - u <= left + chunk
+// - 1) and does not depend on how long the stream runs.  Band rows outside the table are staged
+// as zeros, here as in the whole-utterance call, and meet masked pairs only; a band element is one
+// at_dot chain over a query row and a table row, wherever the rows sit in their tiles, so the
+// rows come out bit for bit as from asr_relattn_win_fwd on the same projected table values.
+struct RasGeo {
+  int Tq, N, n_pad, heads, ld, ld_kv, ld_out, R, t0, P, ld_pos;
+  float c2;         // scale * log2(e)
+};
+
+template <int DH>
+__global__ __launch_bounds__(AT_THREADS) void relattn_stream_kernel(
+    const float* __restrict__ q, const float* __restrict__ ring, const int* __restrict__ kv_len,
+    const float* __restrict__ pos, const float* __restrict__ bias_u,
+    const float* __restrict__ bias_v, float* __restrict__ out, RasGeo g, asr_attn_window w) {
+  constexpr int DP = DH + 4, NJ = DH / 16;
+  extern __shared__ float4 ra_lds4[];
+  float* Qs = reinterpret_cast<float*>(ra_lds4);
+  float* Ks = Qs + AT_TILE * DP;
+  float* Vs = Ks + AT_TILE * DP;
+  float* Bs = Vs + AT_TILE * DP;            // 128 band rows
+  float* Ps = Bs + 2 * AT_TILE * DP;
+  float* cP = Ps + AT_TILE * AT_PP;
+  float* vu = cP + 256, *vd = vu + 64;
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int r0 = blockIdx.x * AT_TILE, h = blockIdx.y, n = blockIdx.z;   // r0: row of the chunk
+  const int D = g.heads * DH;
+  const size_t rs = (size_t)g.n_pad * g.ld, rsk = (size_t)g.n_pad * g.ld_kv;
+  const size_t rso = (size_t)g.n_pad * g.ld_out;
+  float* o_base = out + (size_t)n * g.ld_out;
+  if (h == 0) at_zero_cols(o_base, rso, r0, g.Tq, D, g.ld_out - D, tid);
+  if (n >= g.N) {
+    at_zero_cols(o_base, rso, r0, g.Tq, h * DH, DH, tid);
+    return;
+  }
+  const float* kbase = ring + (size_t)n * g.ld_kv + h * DH;
+  const float* pos_h = pos + h * DH;
+  int len = kv_len[n];
+  len = len < 1 ? 1 : (len > g.t0 + g.Tq ? g.t0 + g.Tq : len);      // (as at_len)
+  ra_load_bias<DH>(vu, vd, bias_u + h * DH, bias_v + h * DH, tid);
+  __syncthreads();
+  ra_load_rows<DH>(Qs, q + (size_t)n * g.ld + h * DH, rs, r0, g.Tq, vu, tid);
+  float m[4], l[4], o[4][NJ];
+  int wlo[4], whi[4];                       // the visible keys of row i
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    m[i] = asr_neg_inf();
+    l[i] = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) o[i][jj] = 0.f;
+    wlo[i] = at_win_lo(w, g.t0 + r0 + 4 * ty + i);
+    whi[i] = min(at_win_hi(w, g.t0 + r0 + 4 * ty + i), len);
+  }
+  const int qa = g.t0 + r0, qb = g.t0 + min(r0 + AT_TILE, g.Tq) - 1;
+  const int kb = at_win_lo(w, qa) / AT_TILE * AT_TILE, ke = min(at_win_hi(w, qb), len);
+  for (int k0 = kb; k0 < ke; k0 += AT_TILE) {
+    const int pr0 = qa - k0 - 63 + g.P - 1;           // table row of band row 0
+    // (k0 and R are multiples of 64: the tile is 64 consecutive ring rows; rows >= len: zeros)
+    const float* tile = kbase + (size_t)(k0 % g.R) * rsk;
+    at_load_tile<DH>(Ks, tile, rsk, 0, len - k0, tid);
+    at_load_tile<DH>(Vs, tile + D, rsk, 0, len - k0, tid);
+    ra_load_rows<DH>(Bs, pos_h, g.ld_pos, pr0, 2 * g.P - 1, nullptr, tid);
+    ra_load_rows<DH>(Bs + AT_TILE * DP, pos_h, g.ld_pos, pr0 + 64, 2 * g.P - 1, nullptr, tid);
+    __syncthreads();
+    if (tid < 128) cP[tid] = ra_rowdot<DH>(Bs + tid * DP, vd);
+    float s[4][4];
+    at_dot<DH>(Qs, Ks, ty, tx, s);
+    ra_band_scores<DH>(Qs, Bs, Ps, ty, tx);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = 4 * ty + i;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int col = tx + 16 * j;
+        const float sp = Ps[row * AT_PP + col] + cP[row - col + 63];
+        const bool vis = k0 + col >= wlo[i] && k0 + col < whi[i];
+        s[i][j] = vis ? (s[i][j] + sp) * g.c2 : asr_neg_inf();
+      }
+    }
+    at_softmax_tile<NJ, true>(s, m, l, o);
+    __syncthreads();                        // (every G read before P overwrites it)
+    at_put_tile(Ps, s, ty, tx);
+    __syncthreads();
+    at_acc<DH>(Ps, Vs, ty, tx, o);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int r = r0 + 4 * ty + i;
+    if (r >= g.Tq) continue;
+    float* orow = o_base + (size_t)r * rso + h * DH;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) orow[tx + 16 * jj] = l[i] == 0.f ? 0.f : o[i][jj] / l[i];
   }
 }
 
@@ -747,6 +830,29 @@ extern "C" int asr_relattn_win_fwd(const asr_relattn_args* a, const asr_attn_win
                                    asr_stream_t stream) {
   ASR_CHECK_ARG(at_win_ok(w), "relattn_win_fwd: bad window (" RA_WIN_TEXT ")");
   return ra_fwd(a, w, stream);
+}
+
+extern "C" int asr_relattn_stream_fwd(const asr_attn_stream_args* a, const asr_attn_window* w,
+                                      asr_stream_t stream) {
+  const char* bad = at_stream_bad(a, w, RA_MAX_DH, true);
+  ASR_CHECK_ARG(bad == nullptr, "relattn_stream_fwd: %s", bad);
+  RasGeo g;
+  g.Tq = a->Tq, g.N = a->N, g.n_pad = a->n_pad, g.heads = a->heads, g.ld = a->ld;
+  g.ld_kv = a->ld_kv, g.ld_out = a->ld_out, g.R = a->R, g.t0 = a->t0, g.P = a->P;
+  g.ld_pos = a->ld_pos, g.c2 = a->scale * AT_LOG2E;
+  const dim3 grid((a->Tq + AT_TILE - 1) / AT_TILE, a->heads, a->n_pad);
+  const size_t lds = ra_lds_bytes(a->dh, 0);
+#define RA_STREAM(DH)                                                                           \
+  {                                                                                             \
+    if (at_allow_lds(relattn_stream_kernel<DH>, lds) != ASR_OK) return ASR_ERR_LAUNCH;          \
+    hipLaunchKernelGGL((relattn_stream_kernel<DH>), grid, dim3(AT_THREADS), lds,                \
+                       (hipStream_t)stream, a->q, a->ring, a->kv_len, a->pos, a->bias_u,        \
+                       a->bias_v, a->out, g, *w);                                               \
+  }
+  RA_DISPATCH(RA_STREAM)
+#undef RA_STREAM
+  ASR_CHECK_LAUNCH();
+  return ASR_OK;
 }
 
 static int ra_bwd(const asr_relattn_args* a, const asr_attn_window* wp, void* workspace,

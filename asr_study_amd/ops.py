@@ -1097,6 +1097,105 @@ def ctc_greedy(logits, seq_len, N):
     return dec, dlen
 
 
+def ctc_greedy_stream(logits, seq_len, state, N):
+    """ctc_greedy over one chunk (T, n_pad, C) of a stream's logits (K26, asr_ctc_greedy_stream):
+    seq_len (device int32, N) the valid frames of THIS chunk, state (device int32, N) the arg-max
+    of the stream's last valid frame (-1: none yet), read and updated.  Returns the labels this
+    chunk adds, (N, T) padded with -1, and their counts."""
+    T, n_pad, Cc = logits.shape
+    dec = torch.empty((int(N), T), dtype=torch.int32, device=logits.device)
+    dlen = torch.empty(int(N), dtype=torch.int32, device=logits.device)
+    assert state.dtype == torch.int32 and state.numel() >= int(N) and state.is_contiguous()
+    L.check(L.load().asr_ctc_greedy_stream(_ptr(logits), _ptr(seq_len), _ptr(state), T, int(N),
+                                           n_pad, Cc, _ptr(dec), _ptr(dlen), _stream()),
+            'asr_ctc_greedy_stream')
+    return dec, dlen
+
+
+# --------------------------------------------------------------------------- streaming (K26)
+def attn_stream_plan(window, max_tq):
+    """Rows of the smallest [K | V] ring (a multiple of 64) that is valid for every call of up to
+    max_tq new frames under the window (chunk, left >= 0, 0) (asr_attn_stream_plan; the ring
+    convention is stated once in csrc/attn_tile.h)."""
+    rows = C.c_int(0)
+    w = attn_window(window)
+    L.check(L.load().asr_attn_stream_plan(C.byref(w), int(max_tq), C.byref(rows)),
+            'asr_attn_stream_plan')
+    return rows.value
+
+
+def ring_put(src, ring, t0, col0=0, cols=None):
+    """Rows [0, Tq) of the columns [col0, col0 + cols) of the slab src (Tq, n_pad, ld) into the
+    columns [0, cols) of the ring rows (t0 + i) % R of ring (R, n_pad, ld_ring) (asr_ring_put)."""
+    _check_f32(src, ring)
+    Tq, n_pad, ld = src.shape
+    assert ring.dim() == 3 and ring.shape[1] == n_pad
+    cols = int(ld - col0 if cols is None else cols)
+    L.check(L.load().asr_ring_put(_ptr(src), _ptr(ring), int(Tq), int(n_pad), int(ld), int(col0),
+                                  cols, int(ring.shape[2]), int(ring.shape[0]), int(t0),
+                                  _stream()), 'asr_ring_put')
+    return ring
+
+
+def _attn_stream_args(q, ring, kv_len, out, N, heads, dh, t0, scale):
+    Tq, n_pad, ld = q.shape
+    assert ring.dim() == 3 and ring.shape[1] == n_pad and out.shape[:2] == q.shape[:2]
+    assert kv_len.dtype == torch.int32 and kv_len.numel() >= int(N)
+    a = L.AttnStreamArgs()
+    a.Tq, a.N, a.n_pad, a.heads, a.dh = int(Tq), int(N), int(n_pad), int(heads), int(dh)
+    a.ld, a.ld_kv, a.ld_out = int(ld), int(ring.shape[2]), int(out.shape[2])
+    a.R, a.t0 = int(ring.shape[0]), int(t0)
+    a.scale = float(scale if scale is not None else 1.0 / math.sqrt(dh))
+    a.q, a.ring, a.kv_len, a.out = q.data_ptr(), ring.data_ptr(), kv_len.data_ptr(), out.data_ptr()
+    return a
+
+
+def attn_stream_fwd(q, ring, kv_len, out, N, heads, dh, t0, window, scale=None):
+    """attn_fwd under `window` for the queries [t0, t0 + Tq) of a stream: q (Tq, n_pad, ld >= heads
+    dh) holds Q in its first columns (the chunk's qkv slab serves), ring (R, n_pad, >= 2 heads dh)
+    the [K | V] of the absolute frames u at rows u % R, the new ones already put (ring_put);
+    kv_len (device int32, N): the absolute frames valid so far.  The rows of the whole-utterance
+    call, bit for bit (asr_attn_stream_fwd)."""
+    _check_f32(q, ring, out)
+    a = _attn_stream_args(q, ring, kv_len, out, N, heads, dh, t0, scale)
+    w = attn_window(window)
+    L.check(L.load().asr_attn_stream_fwd(C.byref(a), C.byref(w), _stream()),
+            'asr_attn_stream_fwd')
+    return out
+
+
+def relattn_stream_fwd(q, ring, kv_len, pos, bias_u, bias_v, out, N, heads, dh, t0, window,
+                       scale=None):
+    """relattn_fwd under `window` for the queries [t0, t0 + Tq) of a stream (as attn_stream_fwd);
+    pos (2P - 1, ld_pos) is the projected table of the relative indices -(P - 1) .. P - 1,
+    P >= left + chunk (asr_relattn_stream_fwd)."""
+    _check_f32(q, ring, out, pos, bias_u, bias_v)
+    assert pos.dim() == 2 and pos.shape[0] % 2 == 1
+    a = _attn_stream_args(q, ring, kv_len, out, N, heads, dh, t0, scale)
+    a.P, a.ld_pos = (int(pos.shape[0]) + 1) // 2, int(pos.shape[1])
+    a.pos, a.bias_u, a.bias_v = pos.data_ptr(), bias_u.data_ptr(), bias_v.data_ptr()
+    w = attn_window(window)
+    L.check(L.load().asr_relattn_stream_fwd(C.byref(a), C.byref(w), _stream()),
+            'asr_relattn_stream_fwd')
+    return out
+
+
+def dwconv1d_stream_fwd(ring, w, b, lens, y, N, k, t0, C_=None):
+    """The causal dwconv1d_fwd (pad_left = k - 1) for the output frames [t0, t0 + Tq) of a stream:
+    y (Tq, n_pad, ld); ring (Rc >= k - 1 + Tq, n_pad, ld) holds the input's absolute frame u at
+    row u % Rc; lens (device int32, N): absolute lengths (asr_dwconv1d_stream_fwd)."""
+    _check_f32(ring, w, b, y)
+    Tq, n_pad, ld = y.shape
+    Cc = int(C_ or ld)
+    assert ring.shape[1:] == y.shape[1:] and w.numel() == k * Cc and b.numel() == Cc
+    assert lens.dtype == torch.int32 and lens.numel() >= int(N)
+    L.check(L.load().asr_dwconv1d_stream_fwd(_ptr(ring), _ptr(w), _ptr(b), _ptr(lens), _ptr(y),
+                                             int(Tq), int(N), int(n_pad), Cc, int(ld), int(k),
+                                             int(ring.shape[0]), int(t0), _stream()),
+            'asr_dwconv1d_stream_fwd')
+    return y
+
+
 def _check_align_labels(labels, label_len, N, Cc):
     """Host-side argument checks of ctc_align / ctc_align_host (numpy views of the labels)."""
     if labels.ndim != 2 or labels.shape[0] < N or labels.shape[1] < 1 or len(label_len) < N:

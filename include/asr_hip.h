@@ -58,7 +58,9 @@ const char* asr_last_error(void);
  * (K18: plain scalar arguments again); the asr_dwconv1d_* / asr_glu_* / asr_swish_* entry points
  * (K22: plain scalar arguments, additions only); asr_specaug_apply (K23: likewise);
  * asr_relattn_args and asr_relattn_* (K24), asr_attn_window and the asr_attn_win_* /
- * asr_relattn_win_* / asr_dwconv1d_pad_* entry points (K25): additions only as well. */
+ * asr_relattn_win_* / asr_dwconv1d_pad_* entry points (K25): additions only as well;
+ * asr_attn_stream_args, asr_ring_put, asr_attn_stream_*, asr_relattn_stream_fwd,
+ * asr_dwconv1d_stream_fwd and asr_ctc_greedy_stream (K26): additions only again. */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -907,6 +909,85 @@ int asr_glu_bwd(const float* x, const float* dy, float* dx, int64_t rows, int C,
 /* derivative is not a function of y).  Finite for every finite x.                            */
 int asr_swish_fwd(const float* x, float* y, int64_t n, asr_stream_t stream);
 int asr_swish_bwd(const float* x, const float* dy, float* dx, int64_t n, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K26 cached chunk-by-chunk (streaming) inference: the forward passes of    */
+/* K25's bounded-look-ahead stages on a few NEW frames of a stream, the past */
+/* kept in rings by the caller (csrc/attn_tile.h states the convention once).*/
+/* Forward only.  Every slab is time major, (frames, n_pad, ld).             */
+/*                                                                           */
+/* THE RING is a slab (R, n_pad, ld): absolute frame u of the stream lives   */
+/* in ring row u % R.  A call states the absolute index t0 of its first new  */
+/* frame and the count Tq of new frames, which the caller has put into the   */
+/* ring beforehand (asr_ring_put).  For the attention calls R is a multiple  */
+/* of 64, so that a 64-frame key tile that starts at an absolute multiple of */
+/* 64 is contiguous in the ring, and the ring is valid for a call iff        */
+/*   R >= t0 + Tq - (lo(t0) / 64) * 64            (lo of asr_attn_window)    */
+/* asr_attn_stream_plan returns the smallest R that is valid for every t0    */
+/* and every Tq <= max_tq: at most left + chunk - 1 + max_tq + 63 rounded up */
+/* to 64.  Ring rows that hold frames below a query's lo are stale; they     */
+/* meet probability exactly 0 and must be FINITE (0 * NaN would reach the    */
+/* sum): the owner zero-fills a ring when it creates or resets it.           */
+/* All of them refuse bad geometry with ASR_ERR_INVALID before any device    */
+/* call; no float atomics; no workgroup waits on another.  New entry points  */
+/* and one new struct only: the ABI version stays.                           */
+/* ------------------------------------------------------------------------ */
+/* Rows [0, Tq) of the columns [col0, col0 + cols) of src (Tq, n_pad, ld_src) into the columns */
+/* [0, cols) of the ring rows (t0 + i) % ring_rows of ring (ring_rows, n_pad, ld_ring), all    */
+/* n_pad samples, the wrap included.  Tq <= ring_rows; col0, cols, ld_src, ld_ring multiples   */
+/* of 4; 16-byte aligned pointers.  Used for the [K | V] columns of a qkv chunk (col0 = D,     */
+/* cols = 2 D) and for the input of the depthwise convolution.                                 */
+int asr_ring_put(const float* src, float* ring, int Tq, int n_pad, int ld_src, int col0, int cols,
+                 int ld_ring, int ring_rows, int t0, asr_stream_t stream);
+typedef struct asr_attn_stream_args {
+  int Tq, N, n_pad;      /* new frames, real streams, padded streams per frame             */
+  int heads, dh;         /* D = heads * dh                                                 */
+  int ld, ld_kv, ld_out; /* floats per row of q (>= D), of the ring (>= 2 D), of out (>= D) */
+  int R, t0;             /* ring rows; absolute index of the first new frame               */
+  int P, ld_pos;         /* relative form only: the table's half length and row pitch      */
+  float scale;           /* of the scores, usually 1 / sqrt(dh)                            */
+  const float* q;        /* (Tq, n_pad, ld): Q in columns [0, D) (a qkv chunk serves)      */
+  const float* ring;     /* (R, n_pad, ld_kv): [K | V], the new frames already put         */
+  const int* kv_len;     /* device int32 (N): absolute frames of stream n valid so far,    */
+                         /*   the part lens plays in asr_attn_win_fwd; clamped to          */
+                         /*   1 .. t0 + Tq (a key at or past t0 + Tq does not exist yet)   */
+  float* out;            /* (Tq, n_pad, ld_out)                                            */
+  const float* pos;      /* relative form only: (2P - 1, ld_pos), row r + P - 1 holds the  */
+                         /*   relative index r = t - u; P >= left + chunk                  */
+  const float* bias_u;   /* relative form only: (D)                                        */
+  const float* bias_v;   /* relative form only: (D)                                        */
+} asr_attn_stream_args;
+/* asr_attn_win_fwd for the queries [t0, t0 + Tq) under a window with left >= 0 and right = 0: */
+/* the visibility rule of K25 on absolute frame numbers, out = exactly 0 for a row with no     */
+/* visible key, exact zeros in the rows n >= N and the pad columns of out, no lse.  The kernel */
+/* walks the absolute 64-aligned key tiles the whole-utterance call walks, so the rows are     */
+/* those of asr_attn_win_fwd on the whole qkv slab BIT FOR BIT, provided every key a query     */
+/* sees is in the ring: a call ends at a multiple of chunk or at the end of the stream.  Any   */
+/* Tq >= 1 (64 queries per workgroup).                                                         */
+int asr_attn_stream_plan(const asr_attn_window* w, int max_tq, int* ring_rows);
+int asr_attn_stream_fwd(const asr_attn_stream_args* a, const asr_attn_window* w,
+                        asr_stream_t stream);
+/* The same for K24 (asr_relattn_win_fwd; dh 16 .. 64).  The table does not depend on how long */
+/* the stream runs: its rows are those of the whole-utterance table at the same relative       */
+/* index.  Band rows a tile pair stages from outside the table are zeros and meet masked pairs */
+/* only.  Bit for bit the rows of asr_relattn_win_fwd on the same table values.                */
+int asr_relattn_stream_fwd(const asr_attn_stream_args* a, const asr_attn_window* w,
+                           asr_stream_t stream);
+/* asr_dwconv1d_pad_fwd with pad_left = k - 1 for the output frames [t0, t0 + Tq): y (Tq,      */
+/* n_pad, ld); the input is a ring (ring_rows >= k - 1 + Tq, n_pad, ld) indexed row by row     */
+/* (ring_rows need not be a multiple of anything); frames < 0 and frames >= lens[n] (device    */
+/* int32 (N), ABSOLUTE, required, clamped to 0 .. t0 + Tq) are zeros by a select.  The taps    */
+/* are added in the order of the whole-utterance call: its rows bit for bit.                   */
+int asr_dwconv1d_stream_fwd(const float* ring, const float* w, const float* b, const int* lens,
+                            float* y, int Tq, int N, int n_pad, int C, int ld, int k,
+                            int ring_rows, int t0, asr_stream_t stream);
+/* asr_ctc_greedy over one chunk of a stream's logits (T, n_pad, C); seq_len (N): the valid    */
+/* frames of THIS chunk.  state (device int32, N) holds the arg-max of the stream's last valid */
+/* frame, -1 before the first one; the call reads and updates it, so a repeat across the       */
+/* boundary is merged.  decoded (N, T) receives the labels this chunk adds (padded with -1),   */
+/* decoded_len (N) their count.                                                                */
+int asr_ctc_greedy_stream(const float* logits, const int* seq_len, int* state, int T, int N,
+                          int n_pad, int C, int* decoded, int* decoded_len, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* K23 SpecAugment (arXiv 1904.08779; csrc/specaug.hip) of an input slab     */
