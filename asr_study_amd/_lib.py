@@ -337,6 +337,12 @@ SIGNATURES = {
                                          void_p]),
     'asr_dwconv1d_stream_fwd': (C.c_int, [void_p] * 5 + [C.c_int] * 8 + [void_p]),
     'asr_ctc_greedy_stream': (C.c_int, [void_p] * 3 + [C.c_int] * 4 + [void_p] * 3),
+    'asr_ctc_beam_stream_state_bytes': (C.c_size_t, [C.c_int] * 4),
+    'asr_ctc_beam_stream_workspace_bytes': (C.c_size_t, [C.c_int] * 5),
+    'asr_ctc_beam_stream': (C.c_int, [void_p] * 2 + [C.c_int] * 7 +
+                            [void_p, C.c_size_t, void_p, C.c_size_t] + [void_p] * 5),
+    'asr_ctc_beam_lm_stream': (C.c_int, [void_p] * 2 + [C.c_int] * 6 + [void_p, C.c_int, C.c_int] +
+                               [void_p, C.c_size_t, void_p, C.c_size_t] + [void_p] * 5),
     'asr_glu_fwd': (C.c_int, [void_p] * 2 + [C.c_int64] + [C.c_int] * 3 + [void_p]),
     'asr_glu_bwd': (C.c_int, [void_p] * 3 + [C.c_int64] + [C.c_int] * 3 + [void_p]),
     'asr_swish_fwd': (C.c_int, [void_p] * 2 + [C.c_int64, void_p]),

@@ -65,6 +65,9 @@ PREDICT_FLAGS = [
     # chunk-by-chunk inference (Model.stream): feed every utterance in pieces of this many
     # milliseconds of features; the decoder is then the greedy one
     ('--stream', dict(default=None, type=float)),
+    # ... unless --stream_beam: the session then decodes with the device beam search at
+    # --beam_width, with --lm* where given (Model.stream(beam=True))
+    ('--stream_beam', dict(action='store_true', default=False)),
 ] + _DEVICE_FLAGS + [
     ('--save', dict(default=None, type=str)),
     ('--override', dict(default=False, action='store_true')),
@@ -250,10 +253,15 @@ def predict_main(argv=None):
     features and prints the growing greedy hypothesis per piece and the final one, which is the
     non-streaming greedy result (under a convolution front-end: of the utterance with one zero
     frame appended where its number of frames is odd, StreamSession.finish); a model that cannot
-    stream is refused with the session's message."""
+    stream is refused with the session's message.  With ``--stream_beam`` the session decodes
+    with the device beam search of width ``--beam_width`` (and ``--lm``): per piece it prints the
+    committed text, which no later frame changes, and the tentative tail in brackets; the final
+    hypothesis is the whole-utterance beam decode of the streamed network outputs."""
     import numpy as np
     parser = make_parser('Predicting with an ASR system.', PREDICT_FLAGS)
     args = parser.parse_args(argv)
+    if args.stream_beam and (args.stream is None or args.no_decoder):
+        raise ValueError('--stream_beam decodes a stream: it needs --stream MS and a decoder')
     if args.dataset is None and args.file is None:
         raise ValueError('dataset or file args must be set.')
     if args.dataset and args.file:
@@ -265,8 +273,11 @@ def predict_main(argv=None):
     model, meta = load_model(args.model, return_meta=True, mode='predict',
                              decoder=(not args.no_decoder), beam_width=args.beam_width,
                              lm=None if args.no_decoder else args.lm, lm_alpha=args.lm_alpha,
-                             lm_beta=args.lm_beta, is_greedy=args.stream is not None)
-    session = model.stream(1) if args.stream is not None else None
+                             lm_beta=args.lm_beta,
+                             is_greedy=args.stream is not None and not args.stream_beam)
+    session = None
+    if args.stream is not None:
+        session = model.stream(1, beam=True) if args.stream_beam else model.stream(1)
     # only the feature / label plugins are inherited from the training run (the reference
     # overlays every stored argument, predict.py:60, which would also import its --save)
     stored = {k: v for k, v in meta['training_args'].items()
@@ -327,16 +338,20 @@ def _predict_streamed(session, batch, ms, feature, labels):
     for pos in range(0, T, piece):
         end = min(T, pos + piece)
         parts.append(session.feed(x[:, pos:end], ended=[T] if end == T else None))
-        _print_partial(parts, labels, end)
+        _print_partial(parts, labels, end, session)
     parts.append(session.finish())
     if labels is None:
         return np.concatenate([p[0] for p in parts], 0)
     return [l for p in parts for l in p[0]]
 
 
-def _print_partial(parts, labels, frames):
+def _print_partial(parts, labels, frames, session=None):
     if labels is None:
         print('  %6d frames in: %d frames out' % (frames, sum(p.shape[1] for p in parts)))
+    elif session is not None and session.beam is not None:
+        done = [l for p in parts for l in p[0]]
+        print('  %6d frames in: %s[%s]' % (frames, labels.imap(done),
+                                           labels.imap(session.hypothesis()[0][0][len(done):])))
     else:
         print('  %6d frames in: %s' % (frames, labels.imap([l for p in parts for l in p[0]])))
 

@@ -1523,15 +1523,21 @@ class Model(object):
         dec, dlen = dec.cpu().numpy(), dlen.cpu().numpy()
         return [dec[n, :dlen[n]].tolist() for n in range(N)]
 
-    def stream(self, n_streams=1, step=None):
+    def stream(self, n_streams=1, step=None, beam=None):
         """A StreamSession (core/stream.py, K26): cached chunk-by-chunk inference of n_streams
         streams in lock-step, ``step`` strided frames per internal step (a multiple of the
         attention chunk; default: the smallest one >= 16).  Raises ValueError, naming the stage
         and the reason, before any device call unless every attention stage has a window (chunk,
         left >= 0, 0), every depthwise convolution is causal and every other stage is per-frame at
-        inference or the two-convolution front-end; NotImplementedError for a beam decoder."""
+        inference or the two-convolution front-end; NotImplementedError for a beam decoder
+        unless ``beam`` asks for it.  beam=True: the session decodes with the device beam search
+        (K27) at the width, merge_repeated and LM of self.decoder; a dict (beam_width,
+        merge_repeated, lm, lm_alpha, lm_beta, max_frames) overrides them.  feed() then returns
+        the labels newly committed, hypothesis() the current best, finish() the rest
+        (StreamSession); max_frames (strided frames per stream, default 3000) sizes the prefix
+        tree: about max_frames * beam_width * (num_classes - 1) * 8 bytes per stream."""
         from .stream import StreamSession
-        return StreamSession(self, n_streams, step)
+        return StreamSession(self, n_streams, step, beam)
 
     def align(self, x, labels, inputs_length):
         """Forced alignment (K19): where in its utterance each label of a KNOWN transcript lies.

@@ -100,16 +100,51 @@ def front_end(model):
     return convs[-1] + 1, (model.stages[convs[0]].kt, model.stages[convs[1]].kt)
 
 
-def check(model, step):
+BEAM_MAX_FRAMES = 3000      # strided frames a beam session's tree is sized for by default
+
+
+def beam_config(model, beam):
+    """The beam decoder of Model.stream(beam=...), before any device call: None for beam=None;
+    else a dict beam_width, merge_repeated, max_frames and lm (None or (CharLM, alpha, beta)).
+    ``True`` takes width, merge_repeated and the LM from model.decoder (which must then be a beam
+    decoder), a dict overrides them and may give max_frames."""
+    if beam is None or beam is False:
+        return None
+    from . import ctc_utils
+    over = {} if beam is True else dict(beam)
+    unknown = set(over) - {'beam_width', 'merge_repeated', 'max_frames', 'lm', 'lm_alpha',
+                           'lm_beta'}
+    if unknown:
+        raise ValueError('beam: unknown keys %s' % sorted(unknown))
+    dec = dict(model.decoder or {})
+    if beam is True and dec.get('is_greedy', True):
+        raise ValueError('beam=True takes the beam decoder of the model, which has %s: give a '
+                         'dict (beam_width, ...) instead'
+                         % ('a greedy one' if model.decoder else 'none'))
+    dec.update(over, is_greedy=False)
+    cfg = dict(beam_width=int(dec.get('beam_width', 100)),
+               merge_repeated=bool(dec.get('merge_repeated', True)),
+               max_frames=int(dec.get('max_frames', BEAM_MAX_FRAMES)),
+               lm=ctc_utils.lm_of(dec, model.num_classes))
+    if not 1 <= cfg['beam_width'] <= 1024:
+        raise ValueError('beam: beam_width %d, the device decoder takes 1 .. 1024'
+                         % cfg['beam_width'])
+    if cfg['max_frames'] < 1:
+        raise ValueError('beam: max_frames %d' % cfg['max_frames'])
+    return cfg
+
+
+def check(model, step, beam=None):
     """What Model.stream refuses, before any device call -> (step, first encoder stage, front)."""
     for si, s in enumerate(model.stages):
         why = stream_check(model, s, si)
         if why is not None:
             raise ValueError('stage %d (%s) cannot stream: %s' % (si, s.kind, why))
     enc0, front = front_end(model)
-    if model.decoder is not None and not model.decoder.get('is_greedy', True):
-        raise NotImplementedError('streaming decode is greedy: a beam search over a stream is '
-                                  'not built (load the model with a greedy decoder or none)')
+    if beam is None and model.decoder is not None and not model.decoder.get('is_greedy', True):
+        raise NotImplementedError('streaming decode is greedy unless asked otherwise: pass '
+                                  'beam=True (or a dict) to Model.stream for the beam search of '
+                                  'the model\'s decoder, or load it with a greedy decoder or none')
     chunk = 1
     for s in model.stages:
         if s.kind == 'mha':
@@ -120,6 +155,9 @@ def check(model, step):
     if step < 1 or step % chunk:
         raise ValueError('step %d: a positive multiple of the chunk, %d strided frames'
                          % (step, chunk))
+    if beam is not None and step > beam['max_frames']:
+        raise ValueError('beam: max_frames %d is less than one step, %d strided frames'
+                         % (beam['max_frames'], step))
     return step, enc0, front
 
 
@@ -140,18 +178,34 @@ class StreamSession(object):
     reset()              zero-fills the state: the session serves another set of streams.
     frames_in, frames_out  input frames fed, strided frames emitted.
 
+    With ``beam`` (K27, beam_config): the device beam search resumed chunk by chunk
+    (ops.ctc_beam_stream).  feed() returns per stream the labels NEWLY COMMITTED -- the growth
+    of the stable prefix, the labels on the path to the deepest common ancestor of the whole
+    beam, which no later frame can change; hypothesis() the current best (labels, score) per
+    stream; finish() the rest of the final best hypothesis.  Everything returned, joined, is the
+    whole-utterance beam decode of the stream's logits.  A stream may have max_frames strided
+    frames (default 3000): beyond, feed / finish raise ValueError before they take the input or
+    launch anything, and the session stays as it was.  The tree takes
+    64 + (1 + B (C - 1)) 8 + B 4 (8 with an LM) bytes per stream, B = max_frames * beam_width,
+    rounded up to 256: 64.8 MB + 1.2 MB at 3000 frames, width 100 and 28 classes.
+
     The absolute positional table is taken as long as the stream has grown (ops.posenc_get, in
     powers of two from 1024 rows): a stream has no length to size it by."""
 
-    def __init__(self, model, n_streams=1, step=None):
-        self.step, self.enc0, front = check(model, step)
+    def __init__(self, model, n_streams=1, step=None, beam=None):
+        self.beam = beam_config(model, beam)
+        self.step, self.enc0, front = check(model, step, self.beam)
         self.model, self.N = model, int(n_streams)
+        # the decoder the session was made under: a later change of model.decoder (another
+        # session of the same model with another decoder) does not reach into this one
+        self.decoder = model.decoder
         if self.N < 1:
             raise ValueError('n_streams %d' % self.N)
         self.n_pad = ops.pad16(self.N)
         self.schedule = Schedule(self.step, front)
         self.state = {}             # stage index -> what the stage carries (core/stages.py)
         self._conv = {}             # front-end stage index -> its ops.Conv2d on the window
+        self._beam_state = None     # ops.BeamStreamState, made at the first step
         self.reset()
 
     # ------------------------------------------------------------------ what the handlers use
@@ -180,6 +234,11 @@ class StreamSession(object):
         self._lens_host = np.full(self.N, NO_END, np.int64)      # on the strided axis
         self.lens = None                        # ... on the device, made at the first step
         self._greedy = None
+        if self._beam_state is not None:
+            self._beam_state.zero_()            # (the records only: the tree needs no fill)
+        self._committed = [0] * self.N          # labels of the stable prefix already returned
+        self._hyp = [([], 0.0) for _ in range(self.N)]
+        self._stable = [0] * self.N
 
     def _set_ended(self, ended):
         if ended is None:
@@ -225,14 +284,20 @@ class StreamSession(object):
         if self._finished:
             raise RuntimeError('feed after finish(): reset() starts another stream')
         self._set_ended(ended)
+        shape = x.shape if hasattr(x, 'shape') else np.shape(x)
+        if len(shape) == 3:     # (a shape _append refuses is refused there)
+            self._beam_room(self.schedule.ready(self.frames_in + int(shape[1]), self.frames_out))
         self._append(x)
         return self._run(self.schedule.ready(self.frames_in, self.frames_out))
 
     def finish(self):
         if self._finished:
             raise RuntimeError('finish() twice: reset() starts another stream')
-        self._finished = True
         total = self.frames_in + (self.frames_in % self.schedule.stride)    # (one zero frame)
+        known = [e if e is not None else total for e in self._ended]
+        self._beam_room(self.schedule.total(total),
+                        np.array([self.schedule.total(e) for e in known]))
+        self._finished = True
         self._set_ended([total if e is None else None for e in self._ended])
         return self._run(self.schedule.total(total), end=total)
 
@@ -245,7 +310,10 @@ class StreamSession(object):
                 self.lens = torch.as_tensor(self._lens_host.astype(np.int32)).to(m.device)
             a = self._front(end) if self.schedule.front else self._take()
             logits = self._encoder(a)
-            if m.decoder is None:
+            if self.beam is not None:
+                chunk_len = np.clip(self._lens_host - self.t0, 0, self.Tq).astype(np.int32)
+                outs = [self._beam_step(logits, chunk_len)]     # (only the last one is read)
+            elif self.decoder is None:
                 outs.append(logits[:, :self.N].clone())
             else:
                 chunk_len = np.clip(self._lens_host - self.t0, 0, self.Tq).astype(np.int32)
@@ -254,7 +322,9 @@ class StreamSession(object):
                 outs.append(ops.ctc_greedy_stream(logits, torch.as_tensor(chunk_len).to(m.device),
                                                   self._greedy, self.N))
             self.frames_out += self.Tq
-        if m.decoder is None:
+        if self.beam is not None:
+            return self._beam_result(outs)
+        if self.decoder is None:
             if not outs:
                 return np.zeros((self.N, 0, m.num_classes), np.float32)
             return torch.cat(outs, 0).permute(1, 0, 2).contiguous().cpu().numpy()
@@ -264,6 +334,54 @@ class StreamSession(object):
             for n in range(self.N):
                 labels[n] += dec[n, :dlen[n]].tolist()
         return labels
+
+    # ------------------------------------------------------------------ the beam decoder (K27)
+    def _beam_room(self, upto, lens=None):
+        """Refuses, before the input is taken and before any launch, the steps up to strided frame
+        ``upto`` if they would take a stream past max_frames: the session stays as it was."""
+        if self.beam is None or upto <= self.frames_out:
+            return
+        reach = int(np.minimum(self._lens_host if lens is None else lens, upto).max())
+        if reach > self.beam['max_frames']:
+            raise ValueError('a stream would reach %d strided frames: the beam session was made '
+                             'for max_frames=%d' % (reach, self.beam['max_frames']))
+
+    def _beam_step(self, logits, chunk_len):
+        m, b = self.model, self.beam
+        if self._beam_state is None:
+            lm = None
+            if b['lm'] is not None:
+                table, alpha, beta = b['lm']
+                lm = (table.fused_device(alpha, beta, m.device), table.order)
+            self._beam_state = ops.BeamStreamState(self.N, m.num_classes, b['beam_width'],
+                                                   b['max_frames'], lm, m.device)
+        return ops.ctc_beam_stream(logits, torch.as_tensor(chunk_len).to(m.device),
+                                   self._beam_state, self.N, b['beam_width'],
+                                   b['merge_repeated'], b['max_frames'])
+
+    def _beam_result(self, outs):
+        """The one copy to the host of a feed: the last step's hypothesis.  -> the labels the
+        stable prefix has grown by (feed) or all that is left of the best hypothesis (finish)."""
+        if outs:
+            dec, dlen, stable, score = outs[-1]
+            dlen, stable, score = dlen.cpu().numpy(), stable.cpu().numpy(), score.cpu().numpy()
+            dec = dec[:, :max(1, int(dlen.max()))].cpu().numpy()
+            self._hyp = [(dec[n, :dlen[n]].tolist(), float(score[n])) for n in range(self.N)]
+            self._stable = [int(v) for v in stable]
+        new = []
+        for n in range(self.N):
+            upto = len(self._hyp[n][0]) if self._finished else \
+                (self._stable[n] if outs else self._committed[n])
+            new.append(self._hyp[n][0][self._committed[n]:upto])
+            self._committed[n] = max(self._committed[n], upto)
+        return new
+
+    def hypothesis(self):
+        """Beam sessions: the current best (labels, log score) per stream, the committed labels
+        included; it may still change behind them."""
+        if self.beam is None:
+            raise RuntimeError('hypothesis(): the session has no beam decoder (Model.stream(beam=))')
+        return [(list(l), s) for l, s in self._hyp]
 
     def _take(self):
         """The step's input frames off the pending slab (no front-end: they are the strided ones;

@@ -57,7 +57,24 @@ struct BeamParams {
   int max_blocks;
   const float* w;                       // LM only: fused table (n_ctx, C - 1)
   int n_ctx;                            // LM only: (C - 1 + 1)^(order - 1)
+  // STREAM only (K27): seq_len is the chunk's valid frames, T the chunk's rows
+  char* state;                          // N state records
+  size_t state_per;
+  int max_frames;                       // frames the workspace was sized for = row of decoded
+  int* stable_len;
 };
+
+// K27, the state record of one stream: what ctc_beam_kernel carries from frame to frame beside the
+// prefix tree in its workspace.  8 ints (nb, nblocks, frames_done, stable_node, overflow, 3 spare),
+// then b_ob, b_ol, b_ot (W doubles each), b_node, b_par and -- LM -- b_ctx (W ints each).  All
+// zeros: a fresh stream (a live one has nb >= 1).
+constexpr int kHdrInts = 8;
+enum { H_NB = 0, H_NBLOCKS = 1, H_FRAMES = 2, H_STABLE = 3, H_OVERFLOW = 4 };
+
+size_t state_per_stream(int W, bool lm) {
+  return asr_align_up(kHdrInts * sizeof(int) + (size_t)W * (3 * sizeof(double) +
+                                                           (lm ? 3 : 2) * sizeof(int)), 64);
+}
 
 __device__ __forceinline__ double neg_inf() { return -__builtin_huge_val(); }
 
@@ -95,7 +112,7 @@ size_t lds_bytes(int W, bool lm) {
   return (size_t)W * 100 + 72 * 8 + 64 * 4 + 16 * 4 + (lm ? (size_t)W * 4 : 0);
 }
 
-template <int E, bool DPP, bool LM>
+template <int E, bool DPP, bool LM, bool STREAM>
 __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int W = p.W, C = p.C, K = p.C - 1, blank = p.C - 1;
@@ -121,7 +138,8 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
 
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // head of the utterance's workspace: 100 MHz ticks spent in phases B, C, D, E, then the
-  // numbers of expanding turns, insertions and child blocks (asr_ctc_beam_device_counters)
+  // numbers of expanding turns, insertions and child blocks (asr_ctc_beam_device_counters);
+  // STREAM: summed over the calls of the stream, and an eighth, the ticks of the stable-node walk
   long long* counters = reinterpret_cast<long long*>(p.ws + (size_t)n * p.ws_per_utt);
   long long tk_b = 0, tk_c = 0, tk_d = 0, tk_e = 0, n_turn = 0, n_ins = 0;
   Rec* rec = reinterpret_cast<Rec*>(p.ws + (size_t)n * p.ws_per_utt + 64);
@@ -130,7 +148,42 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   int Tn = p.seq_len[n];
   Tn = Tn < 0 ? 0 : (Tn > p.T ? p.T : Tn);
 
-  if (tid == 0) {
+  // STREAM: the record of this stream; a chunk never takes it past max_frames, the bound the
+  // workspace (max_frames * W child blocks) was sized by
+  int* hdr = nullptr;
+  double* st_d = nullptr;
+  int* st_i = nullptr;
+  int nb0 = 0, stable0 = 0;
+  bool over = false;
+  if (STREAM) {
+    hdr = reinterpret_cast<int*>(p.state + (size_t)n * p.state_per);
+    st_d = reinterpret_cast<double*>(hdr + kHdrInts);
+    st_i = reinterpret_cast<int*>(st_d + 3 * (size_t)W);
+    nb0 = hdr[H_NB];
+    const int done = nb0 > 0 ? hdr[H_FRAMES] : 0;
+    const int room = done < p.max_frames ? p.max_frames - (done > 0 ? done : 0) : 0;
+    over = Tn > room;
+    Tn = over ? room : Tn;
+    // a record of another geometry (or a corrupt one) must not index past LDS or let phase D
+    // allocate past the workspace: a live record has 1 .. W entries and at most W blocks per
+    // frame done.  Such a record is left as it is, flagged, and answered with the empty hypothesis
+    const long long blocks0 = nb0 > 0 ? (long long)hdr[H_NBLOCKS] : 0;
+    if (nb0 < 0 || nb0 > W || done < 0 || blocks0 < 0 ||
+        blocks0 + (long long)W * Tn > (long long)p.max_blocks) {
+      nb0 = 0; Tn = 0; over = true;
+    }
+    stable0 = nb0 > 0 ? hdr[H_STABLE] : 0;
+    for (int q = tid; q < nb0; q += kThreads) {          // as phase E leaves the table
+      const double ot = st_d[2 * (size_t)W + q];
+      b_ob[q] = st_d[q]; b_ol[q] = st_d[(size_t)W + q]; b_ot[q] = ot; b_ot0[q] = ot;
+      b_node[q] = st_i[q]; b_par[q] = st_i[(size_t)W + q];
+      b_evicted[q] = 0; b_kidhead[q] = -1;
+      if (LM) b_ctx[q] = st_i[2 * (size_t)W + q];
+    }
+    if (tid == 0 && nb0 > 0) { s_misc[0] = nb0; s_misc[1] = hdr[H_NBLOCKS]; s_misc[2] = nb0; }
+  }
+
+  if (tid == 0 && (!STREAM || nb0 <= 0)) {
     // the root: total 0, blank path 0, no label path (decode_host.cpp: beam_one)
     b_node[0] = 0; b_par[0] = -1;
     b_ob[0] = 0.0; b_ol[0] = neg_inf(); b_ot[0] = 0.0; b_ot0[0] = 0.0;
@@ -402,15 +455,49 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   }
 
   // ---- the best leaf's label sequence (merge_repeated collapses consecutive repeats)
-  int* out = p.decoded + (size_t)n * p.T;
+  const int out_row = STREAM ? p.max_frames : p.T;
+  int* out = p.decoded + (size_t)n * out_row;
   __shared__ int s_len;
+  __shared__ int s_stable;
+  long long tk_walk = 0;                                   // STREAM: ticks of the stable-node walk
+  if (STREAM) {
+    // ---- the stable node: the deepest common ancestor of the beam's entries.  An id is larger
+    //      than its parent's, so two nodes meet by replacing the larger id by its parent; every
+    //      entry descends from the stable node of the call before, where the walk stops.  The
+    //      meeting points with the best entry lie on ITS path: the one nearest the root has the
+    //      smallest id.
+    if (tid == 0) s_stable = b_node[0];
+    const long long tk0 = wall_clock64();
+    __syncthreads();
+    const int nbe = s_misc[0], best = b_node[0];
+    int lo = best;
+    for (int q = tid; q < nbe; q += kThreads) {
+      int a = b_node[q], b = best;
+      while (a != b && a != stable0 && b != stable0) {
+        if (a > b) a = block_parent[(a - 1) / K];
+        else b = block_parent[(b - 1) / K];
+      }
+      a = a < b ? a : b;
+      lo = a < lo ? a : lo;
+    }
+    if (lo < best) atomicMin(&s_stable, lo);
+    __syncthreads();
+    tk_walk = wall_clock64() - tk0;
+  }
   if (tid == 0) {
     const int best = b_node[0];
     int L = 0, prev = -1;
+    int SL = 0, sprev = -1;                                // STREAM: the same over root -> stable
+    bool in_stable = false;
     for (int c = best; c != 0; c = block_parent[(c - 1) / K]) {
       const int label = (c - 1) % K;
       if (!p.merge || label != prev) ++L;
       prev = label;
+      if (STREAM) {
+        in_stable = in_stable || c == s_stable;
+        if (in_stable && (!p.merge || label != sprev)) ++SL;
+        if (in_stable) sprev = label;
+      }
     }
     int w = L;
     prev = -1;
@@ -422,20 +509,46 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
     p.decoded_len[n] = L;
     if (p.score) p.score[n] = (float)b_ot[0];
     s_len = L;
+    if (STREAM) {
+      p.stable_len[n] = SL;
+      if (nb0 > 0) {                                       // (the workspace is not zero-filled)
+        tk_b += counters[0]; tk_c += counters[1]; tk_d += counters[2]; tk_e += counters[3];
+        n_turn += counters[4]; n_ins += counters[5]; tk_walk += counters[7];
+      }
+      counters[7] = tk_walk;
+    }
     counters[0] = tk_b; counters[1] = tk_c; counters[2] = tk_d; counters[3] = tk_e;
     counters[4] = n_turn; counters[5] = n_ins; counters[6] = s_misc[1];
   }
   __syncthreads();
-  for (int i = s_len + tid; i < p.T; i += kThreads) out[i] = -1;
+  for (int i = s_len + tid; i < out_row; i += kThreads) out[i] = -1;
+  if (STREAM) {
+    // ---- the record, in the precision the table is held in; a chunk without frames leaves it
+    //      as it is (a fresh one fresh)
+    if (Tn > 0) {
+      const int nbe = s_misc[0];
+      for (int q = tid; q < nbe; q += kThreads) {
+        st_d[q] = b_ob[q]; st_d[(size_t)W + q] = b_ol[q]; st_d[2 * (size_t)W + q] = b_ot[q];
+        st_i[q] = b_node[q]; st_i[(size_t)W + q] = b_par[q];
+        if (LM) st_i[2 * (size_t)W + q] = b_ctx[q];
+      }
+      if (tid == 0) {
+        const int done = nb0 > 0 ? hdr[H_FRAMES] : 0;
+        hdr[H_NB] = nbe; hdr[H_NBLOCKS] = s_misc[1]; hdr[H_FRAMES] = done + Tn;
+        hdr[H_STABLE] = s_stable;
+      }
+    }
+    if (tid == 0 && over) hdr[H_OVERFLOW] = 1;
+  }
 }
 
 typedef void (*beam_kern_t)(BeamParams);
 
-template <bool LM>
+template <bool LM, bool STREAM>
 beam_kern_t pick(int W) {           // (the lane shift of the sorted beam: DPP wave_shr:1)
-  if (W <= 128) return ctc_beam_kernel<2, true, LM>;
-  if (W <= 448) return ctc_beam_kernel<7, true, LM>;
-  return ctc_beam_kernel<16, true, LM>;
+  if (W <= 128) return ctc_beam_kernel<2, true, LM, STREAM>;
+  if (W <= 448) return ctc_beam_kernel<7, true, LM, STREAM>;
+  return ctc_beam_kernel<16, true, LM, STREAM>;
 }
 
 size_t ws_per_utt(int T, int C, int W, int* max_blocks, bool lm = false) {
@@ -446,10 +559,12 @@ size_t ws_per_utt(int T, int C, int W, int* max_blocks, bool lm = false) {
                           blocks * sizeof(int) * (lm ? 2 : 1), 256);
 }
 
-int launch(BeamParams p, int N, bool lm, size_t ws_bytes, asr_stream_t stream) {
-  p.ws_per_utt = ws_per_utt(p.T, p.C, p.W, &p.max_blocks, lm);
+int launch(BeamParams p, int N, bool lm, size_t ws_bytes, asr_stream_t stream,
+           bool streaming = false) {
+  p.ws_per_utt = ws_per_utt(streaming ? p.max_frames : p.T, p.C, p.W, &p.max_blocks, lm);
   ASR_CHECK_ARG(ws_bytes >= p.ws_per_utt * (size_t)N, "beam: workspace too small");
-  beam_kern_t k = lm ? pick<true>(p.W) : pick<false>(p.W);
+  beam_kern_t k = streaming ? (lm ? pick<true, true>(p.W) : pick<false, true>(p.W))
+                            : (lm ? pick<true, false>(p.W) : pick<false, false>(p.W));
   const size_t shm = lds_bytes(p.W, lm);
   if (shm > 64 * 1024)
     ASR_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -549,4 +664,81 @@ extern "C" int asr_ctc_beam_lm_device(const float* logits, const int* seq_len, i
   p.ws = reinterpret_cast<char*>(workspace);
   p.w = w; p.n_ctx = (int)n_ctx;
   return launch(p, N, true, ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------- K27: streams
+namespace {
+bool stream_geometry_ok(int max_frames, int N, int C, int beam_width) {
+  return max_frames >= 1 && N > 0 && C >= 2 && C <= kMaxC && beam_width >= 1 &&
+         beam_width <= 1024 &&
+         (size_t)max_frames * (size_t)beam_width * (size_t)(C - 1) < (size_t)INT_MAX;
+}
+
+int stream_call(const float* logits, const int* chunk_len, int Tq, int N, int n_pad, int C,
+                int beam_width, int merge_repeated, const float* w, int n_ctx, bool lm,
+                int max_frames, void* state, size_t state_bytes, void* workspace, size_t ws_bytes,
+                int* decoded, int* decoded_len, int* stable_len, float* log_score,
+                asr_stream_t stream) {
+  ASR_CHECK_ARG(logits && chunk_len && state && workspace && decoded && decoded_len &&
+                stable_len && log_score, "beam stream: null pointer");
+  ASR_CHECK_ARG(N > 0 && n_pad >= N && C >= 2, "beam stream: bad shape");
+  ASR_CHECK_ARG(C <= kMaxC, "beam stream: at most %d classes", kMaxC);
+  ASR_CHECK_ARG(beam_width >= 1 && beam_width <= 1024, "beam stream: width must be 1 .. 1024");
+  ASR_CHECK_ARG(Tq >= 1 && Tq <= max_frames, "beam stream: a chunk has 1 .. max_frames frames");
+  ASR_CHECK_ARG(stream_geometry_ok(max_frames, N, C, beam_width),
+                "beam stream: max_frames * width * labels overflows the node ids");
+  BeamParams p;
+  p.logits = logits; p.seq_len = chunk_len; p.T = Tq; p.n_pad = n_pad; p.C = C; p.W = beam_width;
+  p.merge = merge_repeated ? 1 : 0;
+  p.decoded = decoded; p.decoded_len = decoded_len; p.score = log_score;
+  p.ws = reinterpret_cast<char*>(workspace);
+  p.w = w; p.n_ctx = n_ctx;
+  p.state = reinterpret_cast<char*>(state);
+  p.state_per = state_per_stream(beam_width, lm);
+  p.max_frames = max_frames; p.stable_len = stable_len;
+  ASR_CHECK_ARG(state_bytes >= p.state_per * (size_t)N, "beam stream: state too small");
+  return launch(p, N, lm, ws_bytes, stream, true);
+}
+}  // namespace
+
+extern "C" size_t asr_ctc_beam_stream_state_bytes(int N, int C, int beam_width, int lm) {
+  if (!stream_geometry_ok(1, N, C, beam_width)) return 0;
+  return state_per_stream(beam_width, lm != 0) * (size_t)N;
+}
+
+extern "C" size_t asr_ctc_beam_stream_workspace_bytes(int max_frames, int N, int C,
+                                                      int beam_width, int lm) {
+  if (!stream_geometry_ok(max_frames, N, C, beam_width)) return 0;
+  int mb;
+  return ws_per_utt(max_frames, C, beam_width, &mb, lm != 0) * (size_t)N;
+}
+
+extern "C" int asr_ctc_beam_stream(const float* logits, const int* chunk_len, int Tq, int N,
+                                   int n_pad, int C, int beam_width, int merge_repeated,
+                                   int max_frames, void* state, size_t state_bytes,
+                                   void* workspace, size_t ws_bytes, int* decoded,
+                                   int* decoded_len, int* stable_len, float* log_score,
+                                   asr_stream_t stream) {
+  return stream_call(logits, chunk_len, Tq, N, n_pad, C, beam_width, merge_repeated, nullptr, 1,
+                     false, max_frames, state, state_bytes, workspace, ws_bytes, decoded,
+                     decoded_len, stable_len, log_score, stream);
+}
+
+extern "C" int asr_ctc_beam_lm_stream(const float* logits, const int* chunk_len, int Tq, int N,
+                                      int n_pad, int C, int beam_width, int merge_repeated,
+                                      const float* w, int order, int max_frames, void* state,
+                                      size_t state_bytes, void* workspace, size_t ws_bytes,
+                                      int* decoded, int* decoded_len, int* stable_len,
+                                      float* log_score, asr_stream_t stream) {
+  ASR_CHECK_ARG(w, "beam lm: null table");
+  ASR_CHECK_ARG(order >= 1 && order <= 5, "beam lm: order must be 1 .. 5");
+  ASR_CHECK_ARG(C >= 2 && C <= kMaxC, "beam stream: 2 .. %d classes", kMaxC);
+  long long n_ctx = 1;                                   // (K + 1)^(order - 1), K = C - 1
+  for (int i = 1; i < order; ++i) {
+    n_ctx *= C;
+    ASR_CHECK_ARG(n_ctx * (C - 1) <= (long long)INT_MAX, "beam lm: table does not fit an int32");
+  }
+  return stream_call(logits, chunk_len, Tq, N, n_pad, C, beam_width, merge_repeated, w,
+                     (int)n_ctx, true, max_frames, state, state_bytes, workspace, ws_bytes,
+                     decoded, decoded_len, stable_len, log_score, stream);
 }

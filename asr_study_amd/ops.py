@@ -1352,6 +1352,101 @@ def ctc_beam_search_lm(logits, seq_len, N, beam_width, merge_repeated, w, order)
     return dec, dlen, score
 
 
+class BeamStreamState(object):
+    """What ctc_beam_stream carries between the chunks of N streams (K27): ``rec``, the state
+    records (a zero-filled uint8 tensor: fresh streams), and the prefix-tree workspace, which
+    belongs to THIS object -- two sessions never share a tree -- and is allocated at the first
+    call: asr_ctc_beam_stream_workspace_bytes, about max_frames * width * (C - 1) * 8 bytes per
+    stream, never filled.  ``lm``: None or (fused table as a float32 device tensor, order)."""
+    HEADER = ('nb', 'nblocks', 'frames_done', 'stable_node', 'overflow')
+
+    def __init__(self, N, num_classes, width, max_frames, lm=None, device='cuda:0'):
+        self.N, self.C, self.width = int(N), int(num_classes), int(width)
+        self.max_frames, self.lm = int(max_frames), lm
+        lib = L.load()
+        flag = int(lm is not None)
+        self.rec_bytes = int(lib.asr_ctc_beam_stream_state_bytes(self.N, self.C, self.width, flag))
+        self.ws_bytes = int(lib.asr_ctc_beam_stream_workspace_bytes(self.max_frames, self.N,
+                                                                    self.C, self.width, flag))
+        if self.rec_bytes == 0 or self.ws_bytes == 0:
+            raise ValueError('beam stream: %d streams, %d classes (2 .. 64), width %d (1 .. 1024), '
+                             'max_frames %d (>= 1, max_frames * width * (classes - 1) < 2^31)'
+                             % (self.N, self.C, self.width, self.max_frames))
+        if lm is not None:
+            _lm_table_shape(lm[0], self.C, lm[1])
+        self.rec = torch.zeros(self.rec_bytes, dtype=torch.uint8, device=device)
+        self.ws = None
+
+    def zero_(self):
+        """Fresh streams; the tree is left as it is (blocks are initialised when allocated)."""
+        self.rec.zero_()
+
+    def counters(self, stream=0):
+        """The work counters at the head of a stream's tree, summed over its calls since the
+        record was fresh (synchronises): seconds in the frame phases and in the stable-prefix
+        walk, and the event counts (asr_ctc_beam_device_counters)."""
+        per = self.ws_bytes // self.N
+        v = self.ws[stream * per:stream * per + 64].cpu().numpy().view(np.int64)
+        out = {k: float(v[i]) * 1e-8 for i, k in enumerate(('branch_s', 'rank_s', 'turns_s',
+                                                              'handover_s'))}
+        out.update(turns=int(v[4]), inserts=int(v[5]), blocks=int(v[6]), walk_s=float(v[7]) * 1e-8)
+        return out
+
+    def header(self):
+        """The records' header fields as host integers (synchronises): {name: (N,) array}."""
+        h = self.rec.view(self.N, -1)[:, :32].contiguous().cpu().numpy().view(np.int32)
+        return {k: h[:, i].copy() for i, k in enumerate(self.HEADER)}
+
+
+def ctc_beam_stream(logits, chunk_len, state, N, width, merge, max_frames, lm=None):
+    """K27: the device beam search over one chunk (Tq, n_pad, C) of the logits of N streams
+    (asr_ctc_beam_stream / asr_ctc_beam_lm_stream).  chunk_len (device int32, N): the valid frames
+    of this chunk; state: a BeamStreamState of the same N, width, max_frames and lm, read and
+    updated.  -> (decoded (N, max_frames) padded with -1, decoded_len, stable_len, log_score):
+    the current best hypothesis of every stream and how many of its labels are final."""
+    lib = L.load()
+    Tq, n_pad, Cc = logits.shape
+    _check_f32(logits)
+    if (state.N, state.C, state.width, state.max_frames) != (int(N), Cc, int(width),
+                                                             int(max_frames)):
+        raise ValueError('ctc_beam_stream: the state was made for %r'
+                         % ((state.N, state.C, state.width, state.max_frames),))
+    # the table is the state's: a stream cannot change its LM between two chunks
+    if lm is not None and (state.lm is None or lm[0] is not state.lm[0]
+                           or int(lm[1]) != int(state.lm[1])):
+        raise ValueError('ctc_beam_stream: lm is not the table the state was made with')
+    lm = state.lm
+    dev = logits.device
+    if not (torch.is_tensor(chunk_len) and chunk_len.dtype == torch.int32
+            and chunk_len.device == dev and chunk_len.is_contiguous()
+            and chunk_len.numel() >= int(N)):
+        raise ValueError('ctc_beam_stream: chunk_len must be a contiguous int32 tensor of %d '
+                         'entries on %s' % (int(N), dev))
+    if state.rec.device != dev or n_pad < int(N):
+        raise ValueError('ctc_beam_stream: the state lives on %s, the logits (%d rows for %d '
+                         'streams) on %s' % (state.rec.device, n_pad, int(N), dev))
+    if state.ws is None:
+        state.ws = torch.empty(state.ws_bytes, dtype=torch.uint8, device=dev)
+    dec = torch.empty((int(N), int(max_frames)), dtype=torch.int32, device=dev)
+    dlen = torch.empty(int(N), dtype=torch.int32, device=dev)
+    stable = torch.empty(int(N), dtype=torch.int32, device=dev)
+    score = torch.empty(int(N), dtype=torch.float32, device=dev)
+    head = (_ptr(logits), _ptr(chunk_len), Tq, int(N), n_pad, Cc, int(width), int(bool(merge)))
+    tail = (int(max_frames), _ptr(state.rec), state.rec_bytes, _ptr(state.ws), state.ws_bytes,
+            _ptr(dec), _ptr(dlen), _ptr(stable), _ptr(score), _stream())
+    if lm is None:
+        L.check(lib.asr_ctc_beam_stream(*(head + tail)), 'asr_ctc_beam_stream')
+    else:
+        w, order = lm
+        _check_f32(w)
+        order = _lm_table_shape(w, Cc, order)
+        if w.device != dev or not w.is_contiguous():
+            raise ValueError('ctc_beam_stream: the fused table must be contiguous on %s' % dev)
+        L.check(lib.asr_ctc_beam_lm_stream(*(head + (_ptr(w), order) + tail)),
+                'asr_ctc_beam_lm_stream')
+    return dec, dlen, stable, score
+
+
 def ctc_beam_lm_counters(logits_shape, N, beam_width, utterance=0, device='cuda:0'):
     """ctc_beam_counters for the last ctc_beam_search_lm call of that shape."""
     lib = L.load()

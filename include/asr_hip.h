@@ -60,7 +60,8 @@ const char* asr_last_error(void);
  * asr_relattn_args and asr_relattn_* (K24), asr_attn_window and the asr_attn_win_* /
  * asr_relattn_win_* / asr_dwconv1d_pad_* entry points (K25): additions only as well;
  * asr_attn_stream_args, asr_ring_put, asr_attn_stream_*, asr_relattn_stream_fwd,
- * asr_dwconv1d_stream_fwd and asr_ctc_greedy_stream (K26): additions only again. */
+ * asr_dwconv1d_stream_fwd and asr_ctc_greedy_stream (K26): additions only again;
+ * asr_ctc_beam_stream, asr_ctc_beam_lm_stream and their two size functions (K27): likewise. */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -988,6 +989,47 @@ int asr_dwconv1d_stream_fwd(const float* ring, const float* w, const float* b, c
 /* decoded_len (N) their count.                                                                */
 int asr_ctc_greedy_stream(const float* logits, const int* seq_len, int* state, int T, int N,
                           int n_pad, int C, int* decoded, int* decoded_len, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K27 The device beam search (K9: asr_ctc_beam_device, asr_ctc_beam_lm_device) over a stream, */
+/* one chunk (Tq, n_pad, C) of logits per call; chunk_len (device int32, N): the valid frames  */
+/* of THIS chunk, 0 .. Tq.  The same kernel, resumable: any split of a stream into chunks ends */
+/* with the branch table, the tree, the string and the score of one whole-utterance call over  */
+/* the concatenated frames, bit for bit.                                                        */
+/*   state      N records of asr_ctc_beam_stream_state_bytes / N bytes each: 8 int32 (nb,       */
+/*              nblocks, frames_done, stable_node, overflow, 3 spare), then b_ob, b_ol, b_ot    */
+/*              (beam_width float64 each), b_node, b_par and -- LM -- b_ctx (beam_width int32   */
+/*              each).  ALL ZEROS = a fresh stream.  A record belongs to one (C, beam_width,    */
+/*              max_frames, lm) and to one record of the workspace; one that cannot be that     */
+/*              geometry's (nb outside 0 .. beam_width, more blocks than the frames left have   */
+/*              room for) is left as it is, its overflow field set, and answered with the empty */
+/*              hypothesis.                                                                     */
+/*   workspace  the prefix tree, sized as asr_ctc_beam_device's for T = max_frames (about       */
+/*              max_frames * beam_width * (C - 1) * 8 bytes per stream); never needs a fill,    */
+/*              but must keep its contents between the calls of a stream.  Its head holds the   */
+/*              work counters of asr_ctc_beam_device_counters, summed over the stream's calls,  */
+/*              and an eighth int64: the 100 MHz ticks of the stable-prefix walk.               */
+/*   A stream takes at most max_frames frames in all: what a chunk holds beyond is not          */
+/*   processed and sets the record's overflow field.  chunk_len 0 leaves the record as it is.   */
+/*   decoded (N, max_frames) padded with -1, decoded_len, log_score (N): the CURRENT best       */
+/*   hypothesis; stable_len (N): how many of its labels are final -- the labels on the path     */
+/*   from the root to the deepest common ancestor of all beam entries (merged as decoded is),   */
+/*   a prefix of every later hypothesis of the stream that never shrinks.                       */
+/* The size functions return 0 for bad arguments and where max_frames * beam_width * (C - 1)    */
+/* does not fit the int32 node ids.  ASR_ERR_INVALID, before any device call: a null pointer,   */
+/* Tq < 1 or > max_frames, C > 64, beam_width outside 1 .. 1024, a buffer that is too small.    */
+size_t asr_ctc_beam_stream_state_bytes(int N, int C, int beam_width, int lm);
+size_t asr_ctc_beam_stream_workspace_bytes(int max_frames, int N, int C, int beam_width, int lm);
+int asr_ctc_beam_stream(const float* logits, const int* chunk_len, int Tq, int N, int n_pad,
+                        int C, int beam_width, int merge_repeated, int max_frames, void* state,
+                        size_t state_bytes, void* workspace, size_t ws_bytes, int* decoded,
+                        int* decoded_len, int* stable_len, float* log_score,
+                        asr_stream_t stream);
+int asr_ctc_beam_lm_stream(const float* logits, const int* chunk_len, int Tq, int N, int n_pad,
+                           int C, int beam_width, int merge_repeated, const float* w, int order,
+                           int max_frames, void* state, size_t state_bytes, void* workspace,
+                           size_t ws_bytes, int* decoded, int* decoded_len, int* stable_len,
+                           float* log_score, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* K23 SpecAugment (arXiv 1904.08779; csrc/specaug.hip) of an input slab     */
