@@ -26,6 +26,7 @@ def _deps():
         os.path.join(CSRC, 'rec_tile.h'),
         os.path.join(CSRC, 'vec4.h'),
         os.path.join(CSRC, 'attn_tile.h'),
+        os.path.join(CSRC, 'attn_core.h'),
         os.path.join(CSRC, 'philox.h'),
         os.path.join(os.path.dirname(HERE), 'include', 'asr_hip.h')]
 

@@ -1,9 +1,10 @@
-// attn_tile.h -- the 64 x 64 tile pieces the attention kernels share (attention.hip,
-// rel_attention.hip): a workgroup of 256 threads (16 x 16), tiles of 64 rows at a pitch of dh + 4
-// floats in LDS ((dh + 4) / 4 is odd: the 16 lanes of a row group read 16-byte pieces of 16
-// different rows without a bank conflict), a 64 x 64 score tile in registers, 4 x 4 per thread
-// (rows 4 ty + i, columns tx + 16 j), which goes through LDS once (pitch 68) for the second
-// product (64 x dh, 4 x dh / 16 per thread).
+// attn_tile.h -- the 64 x 64 tile pieces of the attention kernels (attn_core.h: the passes that
+// attention.hip and rel_attention.hip instantiate; rel_attention.hip: its dpos pass), the window,
+// the ring and the checks of a streaming call: a workgroup of 256 threads (16 x 16), tiles of 64
+// rows at a pitch of dh + 4 floats in LDS ((dh + 4) / 4 is odd: the 16 lanes of a row group read
+// 16-byte pieces of 16 different rows without a bank conflict), a 64 x 64 score tile in registers,
+// 4 x 4 per thread (rows 4 ty + i, columns tx + 16 j), which goes through LDS once (pitch 68) for
+// the second product (64 x dh, 4 x dh / 16 per thread).
 #pragma once
 #include "vec4.h"
 
@@ -147,7 +148,8 @@ __device__ __forceinline__ int at_len(const int* lens, int n, int T) {
   return len < 1 ? 1 : (len > T ? T : len);
 }
 
-// THE WINDOW (K25), defined here once for attention.hip, rel_attention.hip and their plans.
+// THE WINDOW (K25), defined here once for the kernels of attn_core.h and rel_attention.hip and
+// for the plans.
 // Three integers: chunk >= 1; left >= -1 frames (-1: unlimited); right >= 0 frames.  For query
 // frame t let c0 = (t / chunk) * chunk.  Key u is visible to t iff lo(t) <= u < hi(t) and
 // u < lens[n], with
@@ -195,15 +197,15 @@ inline long long at_win_tile_pairs(const asr_attn_window& w, int T) {
   return pairs;
 }
 
-// THE RING (K26), defined here once for the streaming forms of attention.hip and
-// rel_attention.hip and their plan.  A ring is a slab (R, n_pad, ld): absolute frame u of the
-// stream lives in ring row u % R.  R is a multiple of 64, so a 64-frame tile that starts at an
-// absolute multiple of 64 is contiguous in the ring and at_load_tile reads it through a shifted
-// base pointer.  A call states the absolute index t0 of its first new frame and their count Tq;
-// the caller has put the new frames into the ring beforehand.  The first key tile the call walks
-// starts at lo(t0) / 64 * 64, the last frame it holds is t0 + Tq - 1: the ring is valid for the
-// call iff R >= at_ring_need.  Rows that hold frames below a query's lo are stale (older frames,
-// or the zeros the owner filled the ring with): finite, and they meet p = exactly 0 only.
+// THE RING (K26), defined here once for the streaming forward of attn_core.h and its plan.  A ring
+// is a slab (R, n_pad, ld): absolute frame u of the stream lives in ring row u % R.  R is a
+// multiple of 64, so a 64-frame tile that starts at an absolute multiple of 64 is contiguous in
+// the ring and at_load_tile reads it through a shifted base pointer.  A call states the absolute
+// index t0 of its first new frame and their count Tq; the caller has put the new frames into the
+// ring beforehand.  The first key tile the call walks starts at lo(t0) / 64 * 64, the last frame
+// it holds is t0 + Tq - 1: the ring is valid for the call iff R >= at_ring_need.  Rows that hold
+// frames below a query's lo are stale (older frames, or the zeros the owner filled the ring with):
+// finite, and they meet p = exactly 0 only.
 __host__ __device__ __forceinline__ long long at_ring_need(const asr_attn_window& w, int t0,
                                                            int Tq) {
   return (long long)t0 + Tq - at_win_lo(w, t0) / AT_TILE * AT_TILE;

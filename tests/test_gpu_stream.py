@@ -80,8 +80,12 @@ def _attn_case(window, heads, dh, seed=0):
     return TW._make(rs, T, N, N_PAD, heads, dh, lens), N, T, lens
 
 
-@pytest.mark.parametrize('kind', ['attn', 'rel'])
-@pytest.mark.parametrize('heads,dh', [(2, 16), (1, 64)])
+# (the relative family refuses dh > 64)
+STREAM_HEADS = [(heads, dh, kind) for heads, dh in [(2, 16), (1, 64), (1, 48), (1, 128)]
+                for kind in ('attn', 'rel') if kind == 'attn' or dh <= 64]
+
+
+@pytest.mark.parametrize('heads,dh,kind', STREAM_HEADS, ids=['%d-%d-%s' % c for c in STREAM_HEADS])
 @pytest.mark.parametrize('window', WINDOWS, ids=['%d_%d_%d' % w for w in WINDOWS])
 def test_streamed_attention_is_the_whole_utterance_kernel(kind, window, heads, dh):
     """Bit for bit the rows of asr_*_win_fwd on the whole qkv slab, for every step; lengths that

@@ -109,9 +109,12 @@ def _parts(kind, r, N, D):
 def _check(kind, tag, d, N, heads, dh, lens, window, zero_scale=None):
     """zero_scale: the size against which the gradients through dS are measured where the
     oracle's are exactly zero (every row sees a single key: p = 1, dS = 0); the sums over all
-    (sample, frame) pairs (dpos, the biases) against T N times that."""
+    (sample, frame) pairs (dpos, the biases) against T N times that.  window None: the unwindowed
+    entry points, against the oracle under a window that hides nothing."""
     T, D = d['qkv'].shape[0], heads * dh
     got_all = _run(kind, d, N, heads, dh, lens, window)
+    if window is None:
+        window = (1, -1, T)
     want_all = _oracle(kind, d, N, heads, dh, lens, window)
     got, want = _parts(kind, got_all, N, D), _parts(kind, want_all, N, D)
     errs = [_rel(g, w) for g, w in zip(got, want)]
@@ -187,6 +190,22 @@ def test_kernel_parity_other_head_sizes(kind, heads, dh):
     d = _make(rs, 130, 5, 16, heads, dh, lens)
     _check(kind, 'dh=%d' % dh, d, 5, heads, dh, lens, (16, 16, 0))
     _check(kind, 'dh=%d null lens' % dh, d, 5, heads, dh, None, (48, 100, 5))
+
+
+# every head size the dispatch knows (the relative family refuses dh > 64), so that each reaches
+# its own instantiation: a kernel of another DH reads another pitch and misses by orders of magnitude
+HEAD_SIZES = [('attn', dh) for dh in range(16, 129, 16)] + [('rel', dh) for dh in range(16, 65, 16)]
+
+
+@pytest.mark.parametrize('window', [None, (16, 16, 0)], ids=['plain', '16_16_0'])
+@pytest.mark.parametrize('kind,dh', HEAD_SIZES, ids=['%s-%d' % c for c in HEAD_SIZES])
+def test_every_head_size_reaches_its_own_kernel(kind, dh, window):
+    """T = 70: two tiles; one length inside the second tile, one inside the first.  Data differ
+    per dh."""
+    rs = np.random.RandomState(1000 + dh)
+    lens = np.array([70, 41])
+    d = _make(rs, 70, 2, 16, 1, dh, lens)
+    _check(kind, 'dh=%d' % dh, d, 2, 1, dh, lens, window)
 
 
 @pytest.mark.parametrize('kind', ['attn', 'rel'])

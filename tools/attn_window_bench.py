@@ -23,7 +23,9 @@ the unwindowed ones for the window (1, T, T) (bit-equal) before anything is time
 
 --window C L R times that one window beside the unwindowed call: the program to put behind
 ``rocprofv3 --kernel-trace --stats --output-format csv --`` (a run of its own), where the
-windowed kernels are the instantiations ``<dh, true>`` and the unwindowed ones ``<dh, false>``.
+kernels are the instantiations ``attn_fwd_kernel<dh, WIN, REL, false>``, ``attn_bwd_dq_kernel<dh,
+WIN, REL>`` and ``attn_bwd_dkv_kernel<dh, WIN, REL>`` of csrc/attn_core.h (WIN true: windowed;
+REL true: the relative family) and ``relattn_bwd_dpos_kernel<dh, WIN>``.
 
 A measurement path without a GPU fails; it does not fall back."""
 import argparse
