@@ -5,7 +5,9 @@ Runs only in the build container (needs /root/reference).  The reference's
 Python never ships to the GPU box -- only the vectors written here do.  While
 generating, every oracle function in oracle/frontend.py is checked bit-for-bit
 (float64) against the reference's own code; the script aborts on any mismatch,
-so a committed fixture set implies a pinned oracle.
+so a committed fixture set implies a pinned oracle.  ``--edge`` writes the
+frontend_edge_*.npz set alone (an .npz is not byte-reproducible: regenerating a
+file that has not changed only churns history).
 
 Shims: librosa stub (file-path branch only, audio.py:57-58),
 builtins.xrange/unicode (py2 names, audio.py:55,272-275), scipy.signal.hamming
@@ -60,6 +62,10 @@ CONFIGS = {
                                      'dd': True}),
     'mfcc39_s2c2': ('mfcc', {'stride': 2, 'num_context': 2}),
 }
+# name -> the row of tests/frontend_cases.py CONFIGS it is (the kwargs live there, once)
+EDGE_CONFIGS = ('lfb64', 'lfb21_d_dd', 'lfb65', 'lfb128_full', 'lfb41_d_dd_s3c1', 'mfcc26x26',
+                'mfcc_w512', 'mfcc_w320_s80', 'mfcc_8k', 'mfcc_pe0', 'mfcc_nomean', 'mfcc_novar',
+                'mfcc39_raw', 'lfb41_d_dd_s3c1_raw', 'mfcc39_s2c2_raw')
 SMALL_N = (300, 400, 401, 16000)
 SEEDS = (0, 1)
 
@@ -68,16 +74,43 @@ def audio_for(seed, n):
     return np.random.RandomState(seed).randn(n)
 
 
+def same(a, b, what):
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype or not np.array_equal(a, b):
+        raise SystemExit('ORACLE MISMATCH vs reference: %s' % what)
+
+
+def edge(ref_audio):
+    """tests/golden/frontend_edge_<name>.npz: the parameter sets of tests/frontend_cases.py that
+    CONFIGS above does not have (other framings, filter counts, DCT widths, strides, one norm at
+    a time, no norm), at lengths of 1, 3, 4 and 18 frames and with a run of silence, inputs
+    rounded to float32.  Outputs only: tests.frontend_cases.edge_input(name, key) rebuilds the
+    input of a key."""
+    from oracle import frontend as F
+    from tests import frontend_cases as FC
+    cls = {'mfcc': ref_audio.MFCC, 'logfbank': ref_audio.LogFbank}
+    for name in EDGE_CONFIGS:
+        kind, kw = FC.oracle_kind(name), FC.CONFIGS[name].kw
+        out = {}
+        for key in FC.edge_keys(name):
+            x = FC.edge_input(name, key)
+            with np.errstate(all='ignore'):
+                y = cls[kind](**kw)(x.copy())
+                yo = F.extract(kind, x, **kw)
+            same(yo, y, '%s %s' % (name, key))
+            out[key] = y
+        np.savez_compressed(os.path.join(OUT, 'frontend_edge_%s.npz' % name), **out)
+        print('%-22s ok  %d vectors, widest %s' % (name, len(out), max(v.shape for v in out.values())))
+    print('oracle/frontend.py == reference (bit-exact) at the edge parameter sets; fixtures in', OUT)
+
+
 def main():
     from oracle import frontend as F
     ref_audio, ref_utils = import_reference_audio()
     os.makedirs(OUT, exist_ok=True)
+    if '--edge' in sys.argv:            # the edge fixtures alone: the others stay as committed
+        return edge(ref_audio)
     cls = {'mfcc': ref_audio.MFCC, 'logfbank': ref_audio.LogFbank}
-
-    def same(a, b, what):
-        a, b = np.asarray(a), np.asarray(b)
-        if a.shape != b.shape or a.dtype != b.dtype or not np.array_equal(a, b):
-            raise SystemExit('ORACLE MISMATCH vs reference: %s' % what)
 
     # --- intermediates (one case) -------------------------------------
     x = audio_for(0, 16000)
@@ -130,6 +163,7 @@ def main():
         print('%-18s ok  (T,F)@10s=%s' % (name, y.shape))
     print('oracle/frontend.py == reference (bit-exact float64); fixtures in',
           OUT)
+    edge(ref_audio)
 
 
 if __name__ == '__main__':

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import frontend as F
+from tests import frontend_cases as FC
 
 CONFIGS = {
     'mfcc39': ('mfcc', {}),
@@ -28,6 +29,20 @@ def test_extractors_bit_exact(name, golden_dir):
         n, seed = int(key.split('_')[0][1:]), int(key.split('_')[1][1:])
         x = np.random.RandomState(seed).randn(n)
         y = F.extract(kind, x, **kw)
+        assert y.dtype == g[key].dtype and y.shape == g[key].shape
+        assert np.array_equal(y, g[key]), (name, key)
+
+
+@pytest.mark.parametrize('name', FC.EDGE_CONFIGS)
+def test_edge_extractors_bit_exact(name, golden_dir):
+    """The parameter sets of tests/frontend_cases.py that the table above does not have, at
+    1, 3, 4 and 18 frames and over a run of silence (oracle/gen_golden.py --edge)."""
+    g = np.load(os.path.join(golden_dir, 'frontend_edge_%s.npz' % name))
+    assert sorted(g.files) == sorted(FC.edge_keys(name))
+    kind, kw = FC.oracle_kind(name), FC.CONFIGS[name].kw
+    for key in g.files:
+        with np.errstate(all='ignore'):
+            y = F.extract(kind, FC.edge_input(name, key), **kw)
         assert y.dtype == g[key].dtype and y.shape == g[key].shape
         assert np.array_equal(y, g[key]), (name, key)
 
@@ -71,3 +86,14 @@ def test_frame_counts():
     assert F.num_frames(160000) == 999 and F.num_frames(16000) == 99
     assert F.num_frames(400) == 1 and F.num_frames(401) == 2 and F.num_frames(2) == 1
     assert F.round_half_up(0.5) == 1 and F.round_half_up(2.5) == 3
+    # the other framings of tests/frontend_cases.py: win_len 0.032, 0.02 / 0.005, and 8 kHz
+    assert FC.framing('mfcc_w512') == (512, 160)
+    assert FC.framing('mfcc_w320_s80') == (320, 80)
+    assert FC.framing('mfcc_8k') == (200, 80)
+    for L, S in ((512, 160), (320, 80), (200, 80)):
+        assert F.num_frames(2, L, S) == 1 and F.num_frames(L, L, S) == 1
+        assert F.num_frames(L + 1, L, S) == 2 and F.num_frames(L + S, L, S) == 2
+        assert F.num_frames(L + S + 1, L, S) == 3
+        assert F.num_frames(L + 16 * S + 1, L, S) == 18
+    assert F.num_frames(3000, 512, 160) == 17 and F.num_frames(3000, 320, 80) == 35
+    assert F.num_frames(3000, 200, 80) == 36 and F.num_frames(16000, 200, 80) == 199
