@@ -125,6 +125,16 @@ class GruArgs(C.Structure):
                 ('dz_absmax', void_p)]
 
 
+class GruUniArgs(C.Structure):
+    # asr_gru_uni_args (K28): one direction, no direction axis; h0 / h_last carry the state
+    _fields_ = [('T', C.c_int), ('n_pad', C.c_int), ('H', C.c_int), ('mode', C.c_int),
+                ('activation', C.c_int), ('clip', C.c_float),
+                ('U', void_p), ('mask_u', void_p), ('zx', void_p), ('h', void_p),
+                ('gates', void_p), ('rm', void_p), ('h0', void_p), ('h_last', void_p),
+                ('dy', void_p), ('dy_ld', C.c_int), ('da', void_p), ('db_part', void_p),
+                ('dz_absmax', void_p)]
+
+
 class RhnArgs(C.Structure):
     _fields_ = [('T', C.c_int), ('n_pad', C.c_int), ('H', C.c_int), ('depth', C.c_int),
                 ('coupling', C.c_int), ('mode', C.c_int),
@@ -278,6 +288,11 @@ SIGNATURES = {
     'asr_gru_seq_fwd': (C.c_int, [C.POINTER(GruArgs), void_p, C.c_size_t, void_p]),
     'asr_gru_seq_bwd': (C.c_int, [C.POINTER(GruArgs), void_p, C.c_size_t, void_p]),
     'asr_gru_plan': (C.c_int, [C.POINTER(GruArgs), C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
+    'asr_gru_uni_workspace_bytes': (C.c_size_t, [C.POINTER(GruUniArgs), C.c_int]),
+    'asr_gru_uni_seq_fwd': (C.c_int, [C.POINTER(GruUniArgs), void_p, C.c_size_t, void_p]),
+    'asr_gru_uni_seq_bwd': (C.c_int, [C.POINTER(GruUniArgs), void_p, C.c_size_t, void_p]),
+    'asr_gru_uni_plan': (C.c_int, [C.POINTER(GruUniArgs), C.c_int, c_int_p, c_int_p, c_int_p,
+                                   c_int_p]),
     'asr_rhn_workspace_bytes': (C.c_size_t, [C.POINTER(RhnArgs), C.c_int]),
     'asr_rhn_seq_fwd': (C.c_int, [C.POINTER(RhnArgs), void_p, C.c_size_t, void_p]),
     'asr_rhn_seq_bwd': (C.c_int, [C.POINTER(RhnArgs), void_p, C.c_size_t, void_p]),

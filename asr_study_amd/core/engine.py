@@ -269,7 +269,8 @@ class Model(object):
             if hasattr(st, 'oW'):
                 prev = st
         if (prev is not None and hasattr(prev, 'Hp') and prev.Hp != prev.H
-                and getattr(prev, 'merge', 'concat') == 'concat'):
+                and getattr(prev, 'merge', 'concat') == 'concat'
+                and getattr(prev, 'directions', 2) == 2):
             idx = np.concatenate([np.arange(prev.H), prev.Hp + np.arange(prev.H)])
         else:
             idx = np.arange(s.f_in)

@@ -230,7 +230,12 @@ class GRU(object):
     p = (x (.) B_W) W and mu, var the per-column moments of the batch's VALID frames (t < length);
     padded frames are normalised with them and count for nothing.  beta replaces b: the weights per
     direction are W, U, gamma, beta and the running mean / variance (momentum bn_momentum), which
-    inference uses.  Runs on the K18 kernels of csrc/batchnorm.hip."""
+    inference uses.  Runs on the K18 kernels of csrc/batchnorm.hip.
+
+    Used bare, ``GRU(H, ...)(x)``, it is a UNIDIRECTIONAL layer (frames in order, output width H)
+    on the one-direction form of the same kernels (K28): it trains like the wrapped layer and,
+    its state being one (N, H) vector, streams chunk by chunk (core/stream.py).  Keras names of
+    the unwrapped layer: gru_k_W / _U / _b.  batch_norm=True is refused there."""
 
     IMPLEMENTED = ("output_dim, init='glorot_uniform', inner_init='orthogonal', activation in "
                    "(tanh, relu, linear, clipped_relu(v)), inner_activation='hard_sigmoid', "
@@ -279,6 +284,15 @@ class GRU(object):
         self.dropout_U = float(dropout_U or 0.0)
         self.l2_W = W_regularizer.l2 if W_regularizer is not None else 0.0
         self.l2_U = U_regularizer.l2 if U_regularizer is not None else 0.0
+
+    def __call__(self, x):
+        """Used bare (not inside Bidirectional): a unidirectional layer of width output_dim."""
+        if self.batch_norm:
+            raise NotImplementedError(
+                'GRU(batch_norm=True) outside Bidirectional: the sequence-wise batch '
+                'normalisation kernels take the projections of both directions of a layer; '
+                'a one-direction form is not built')
+        return Sym(self.output_dim, producer=self, parent=x, fc=None)
 
 
 def highway_bias_initializer(shape, name=None):

@@ -100,6 +100,12 @@ def ctc_model(inputs, output, **kwargs):
             if r.batch_norm:        # (only then: the spec of every other model is unchanged)
                 spec[-1].update(batch_norm=True, bn_epsilon=r.bn_epsilon,
                                 bn_momentum=r.bn_momentum)
+        elif isinstance(layer, GRU):
+            # a bare GRU: the one-direction variant of the kind (the key only then, and no
+            # merge_mode: there is nothing to merge)
+            spec.append({'type': 'bigru', 'H': layer.output_dim, 'activation': layer.activation,
+                         'dropout_W': layer.dropout_W, 'dropout_U': layer.dropout_U,
+                         'l2_W': layer.l2_W, 'l2_U': layer.l2_U, 'directions': 1})
         elif isinstance(layer, Bidirectional) and isinstance(layer.lstm, RHN):
             r = layer.lstm
             spec.append({'type': 'birhn', 'H': r.output_dim, 'depth': r.depth,
@@ -295,7 +301,8 @@ def brsmv1(num_features=39, num_classes=28, num_hiddens=256, num_layers=5,
 def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
                  conv_filters=32, conv_kernels=((11, 41), (11, 21)), conv_strides=((2, 2), (1, 2)),
                  max_value=20, dropout=0.2, weight_decay=1e-4, input_std_noise=.0,
-                 batch_norm=False, rnn_type='lstm', spec_augment=False, **kw):
+                 batch_norm=False, rnn_type='lstm', spec_augment=False, bidirectional=True,
+                 **kw):
     """BASELINE.json configs[2]: "DeepSpeech2-style 5xBiLSTM(512) + 2 conv front-end, 80-dim
     log-mel".  NO REFERENCE COUNTERPART: the reference lists Deep Speech 2 as TODO
     (README.md:118) and its ``deep_speech`` factory (core/models.py:148-214) is dead code
@@ -327,9 +334,17 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
     published Deep Speech 2; Keras-1.2.2 GRU on csrc/gru.hip) with the same regularisers and
     dropouts; it composes with batch_norm.
 
-    spec_augment=True (or a dict of its arguments): a SpecAugment layer directly behind Input."""
+    spec_augment=True (or a dict of its arguments): a SpecAugment layer directly behind Input.
+
+    bidirectional=False (with rnn_type='gru' only): every recurrent layer is a bare, unidirectional
+    GRU of width num_hiddens (the deployment form of Deep Speech 2) and the Dense reads num_hiddens
+    features; batch_norm False, True and 'layer' compose as above.  Such a model has no look-ahead
+    behind its convolutions: with batch_norm=False, Model.stream runs it chunk by chunk."""
     if rnn_type not in ('lstm', 'gru'):
         raise ValueError("deep_speech2: rnn_type %r ('lstm' or 'gru')" % (rnn_type,))
+    if not bidirectional and rnn_type != 'gru':
+        raise ValueError("deep_speech2: bidirectional=False needs rnn_type='gru': there is no "
+                         "unidirectional LSTM layer")
     if batch_norm not in (False, True, 'recurrent', 'layer'):
         raise ValueError("deep_speech2: batch_norm %r (False, True, 'recurrent' or 'layer')"
                          % (batch_norm,))
@@ -338,6 +353,9 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
     if recurrent_bn and rnn_type != 'gru':
         raise ValueError("deep_speech2: batch_norm='recurrent' needs rnn_type='gru': only the GRU "
                          "layer normalises its input projection (LSTM has no batch_norm argument)")
+    if not bidirectional and recurrent_bn:
+        raise NotImplementedError("deep_speech2: bidirectional=False with batch_norm='recurrent': "
+                                  "a bare GRU has no sequence-wise batch normalisation")
     cell = GRU if rnn_type == 'gru' else LSTM
     cell_kw = dict(batch_norm=True) if recurrent_bn else {}
     x = Input(name='inputs', shape=(None, num_features))
@@ -356,9 +374,10 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
     for _ in range(num_layers):
         if batch_norm and not recurrent_bn:
             o = norm()(o)
-        o = Bidirectional(cell(num_hiddens, return_sequences=True,
-                               W_regularizer=l2(weight_decay), U_regularizer=l2(weight_decay),
-                               dropout_W=dropout, dropout_U=dropout, **cell_kw))(o)
+        rec = cell(num_hiddens, return_sequences=True,
+                   W_regularizer=l2(weight_decay), U_regularizer=l2(weight_decay),
+                   dropout_W=dropout, dropout_U=dropout, **cell_kw)
+        o = Bidirectional(rec)(o) if bidirectional else rec(o)
     o = TimeDistributed(Dense(num_classes, W_regularizer=l2(weight_decay)))(o)
     model = ctc_model(x, o, **kw)
     model.config = {'name': 'deep_speech2', 'kwargs': dict(
@@ -371,6 +390,8 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
         model.config['kwargs']['batch_norm'] = batch_norm if isinstance(batch_norm, str) else True
     if rnn_type != 'lstm':  # (likewise)
         model.config['kwargs']['rnn_type'] = rnn_type
+    if not bidirectional:   # (likewise)
+        model.config['kwargs']['bidirectional'] = False
     _record_spec_augment(model, spec_augment)
     return model
 

@@ -137,7 +137,8 @@ def segments(stages):
 
 def keras_names(stages):
     """[(layer name, [weight name, ...])] in Keras-1.2.2 naming, one entry per weight-bearing
-    stage: 'bidirectional_k' holds 'forward_gru_k_W:0', ...  Weights are numbered like their
+    stage: 'bidirectional_k' holds 'forward_gru_k_W:0', ... and an unwrapped GRU's 'gru_k' holds
+    'gru_k_W:0', ..., k counting the unwrapped GRU layers.  Weights are numbered like their
     layer, except a Dense's: its group is named after the TimeDistributed around it, and Keras
     counts the TimeDistributed(Dropout / Activation) layers with those."""
     groups = {'convolution2d': 'convolution2d', 'batchnormalization': 'batchnormalization',
@@ -151,7 +152,8 @@ def keras_names(stages):
             n['timedistributed'] += bool(getattr(s, 'wrapped', False))
             continue
         cls = s.tensors[0].layer.split('_')[-1]
-        group = groups.get(cls, 'bidirectional')
+        # ('forward_gru' ends in 'gru' too: an unwrapped GRU is told by its whole layer name)
+        group = 'gru' if s.tensors[0].layer == 'gru' else groups.get(cls, 'bidirectional')
         n[group] += 1
         n['dense'] += cls == 'dense'
         out.append(('%s_%d' % (group, n[group]),
@@ -269,6 +271,19 @@ def bigru(s, alloc, rows):
         else:
             out.append(Tensor(layer, 'b', (3 * H,), s.ob, (2, G), (d,), pad))
     return out
+
+
+def gru_uni(s, alloc, rows):
+    """A bare, unidirectional GRU (csrc/gru.hip, K28): W (in, 3Hp), U (Hp, 3Hp), b (3Hp), column
+    blocks z, r, h; the initialisers and l2 of one direction of ``bigru``."""
+    H, Hp, F = s.H, s.Hp, len(rows)
+    G, pad = 3 * Hp, ('blocks', H, Hp, 3)
+    s.oW, s.oU, s.ob = alloc.take(s.f_in_pad * G), alloc.take(Hp * G), alloc.take(G)
+    return [Tensor('gru', 'W', (F, 3 * H), s.oW, (s.f_in_pad, G), (rows,), pad, s.l2_W,
+                   _glorot(F, 3 * H)),
+            Tensor('gru', 'U', (H, 3 * H), s.oU, (Hp, G), (slice(0, H),), pad, s.l2_U,
+                   ('orthogonal', 1.1)),
+            Tensor('gru', 'b', (3 * H,), s.ob, (G,), (), pad)]
 
 
 def birhn(s, alloc, rows):

@@ -23,6 +23,13 @@ variational-dropout masks), ``needs_lens`` (forward needs seq_len), ``attention`
 workspaces carry timeout words of their own).  Whether a stage is the first trainable one is
 ``s.first``: no stage before it has ``tensors``.
 
+A VARIANT of a kind is a stage of that kind told by an attribute only it carries (``relative`` and
+``window`` on 'mha'; ``directions`` = 1 on 'bigru': a bare, unidirectional GRU, whose three
+handlers the kind's own hand over to).  A variant may stream where its kind does not:
+``STREAM_VARIANTS`` (at the end of this module) maps a kind to (is this stage the variant?, its
+step handler ``(m, s, si, a, ss)``), and ``stream_variant(s)`` is what ``stream_check`` and
+``StreamSession._encoder`` consult FIRST, before ``Kind.stream`` -- which stays None for 'bigru'.
+
 A new stage kind is one builder in params.py and one entry here.  The two BiLSTM bodies are the
 scheduled hot path (pipe and side streams, compact BPTT, packed planes, per-layer all-reduce) and
 stay in engine.py as ``Model._bilstm_forward`` / ``_bilstm_backward``; their entry calls them.
@@ -53,6 +60,11 @@ Kind = collections.namedtuple(
 # says why a stage cannot stream.  The kinds of STREAM_AS_FORWARD are per-frame or the identity
 # at inference (bn: the running moments): the session calls their ``forward`` on the chunk slab.
 # A 'conv' stage belongs to the front-end, which the session runs itself.
+# A VARIANT of a kind may stream where the kind as such does not: the unidirectional GRU is a
+# 'bigru' stage with one direction.  ``stream_variant(s)`` (below, from STREAM_VARIANTS at the end
+# of this module) gives such a stage's step handler, or None; ``StreamSession._encoder`` and
+# ``stream_check`` ask it first, before ``Kind.stream``.  The 'bigru' kind itself has no handler:
+# the bidirectional layer reads the whole utterance.
 STREAM_AS_FORWARD = ('dense', 'ln', 'act', 'glu', 'merge', 'reshape', 'dropout', 'noise',
                      'specaug', 'bn')
 
@@ -661,6 +673,8 @@ def _mha_stream(m, s, si, a, ss):
 def stream_check(m, s, si):
     """Why stage si cannot run chunk by chunk (K26), or None: no device is touched."""
     kind = KINDS[s.kind]
+    if stream_variant(s) is not None:
+        return None
     if s.kind == 'mha':
         w = getattr(s, 'window', None)
         if w is None or w[1] < 0 or w[2] != 0:
@@ -726,6 +740,8 @@ def _birnn_build(m, s, st, width):
 
 
 def _bigru_build(m, s, st, width):
+    if st.get('directions', 2) == 1:
+        return _gru_uni_build(m, s, st, width)
     _rec_fields(s, st)
     # batch_norm (K18, csrc/batchnorm.hip): sequence-wise BN of the input projection
     s.bn = bool(st.get('batch_norm', False))
@@ -734,6 +750,24 @@ def _bigru_build(m, s, st, width):
         s.bn_momentum = float(st.get('bn_momentum', 0.99))
     s.tensors = P.bigru(s, m._alloc, m._real_rows(s))
     return _rec_width(s)
+
+
+def _gru_uni_build(m, s, st, width):
+    """A bare GRU, the one-direction variant of the kind (K28): ``s.directions`` is set on such
+    a stage only (read it with getattr(s, 'directions', 2)); there is no merge and no batch
+    normalisation of the projection."""
+    if st.get('batch_norm'):
+        raise NotImplementedError('a unidirectional GRU stage has no batch_norm: the sequence-wise '
+                                  'normalisation kernels take both directions of a layer')
+    s.directions = 1
+    s.H = st['H']
+    s.Hp = _pad4(s.H)
+    s.act = st.get('activation') or 'tanh'
+    s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
+    s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
+    s.bn = False
+    s.tensors = P.gru_uni(s, m._alloc, m._real_rows(s))
+    return s.H, s.Hp
 
 
 def _birhn_build(m, s, st, width):
@@ -851,6 +885,8 @@ def _bigru_forward(m, s, si, a, rec, fp):
     batch_norm: the GEMMs write the bias-free projection p into a buffer of the layer (the
     backward pass reads it again), and zx = BN(p) goes to a scratch all layers share (BPTT
     never reads zx)."""
+    if getattr(s, 'directions', 2) == 1:
+        return _gru_uni_forward(m, s, si, a, rec, fp)
     a = a.contiguous()
     n_pad = fp.n_pad
     T, Hp = a.shape[0], s.Hp
@@ -902,6 +938,8 @@ def _bigru_backward(m, s, si, rec, da, bp):
     dU_z, dU_r [d] = (h_prev (.) B_U)^T [da_z | da_r], dU_h[d] = (r (.) m)^T da_h (r (.) m
     kept by the forward pass), dW[d] = (x (.) B_W)^T da_d, db from the per-batch-tile sums,
     dx = sum_d B_W[d] (.) (da_d @ W_d^T).  Returns dx (or None)."""
+    if getattr(s, 'directions', 2) == 1:
+        return _gru_uni_backward(m, s, si, rec, da, bp)
     split = bp.split
     T, n_pad = da.shape[0], da.shape[1]
     rows, Hp = T * n_pad, s.Hp
@@ -932,6 +970,91 @@ def _bigru_backward(m, s, si, rec, da, bp):
         dg = dp
     _rec_dw(m, a_in.contiguous(), dg, s, 3 * Hp, BW, rows, n_pad, split, zmx)
     return _rec_dx(m, dg, s, si, 3 * Hp, BW, T, n_pad, zmx, bp.first)
+
+
+# The unidirectional GRU (K28): the one-direction versions of the two handlers above.  The masks
+# are direction 0's of the pair a 'bigru' stage is drawn (same shapes, streams and step).
+def _gru_uni_zx(m, s, si, a, BW, n_pad):
+    """zx (T, n_pad, 3Hp) = (a (.) B_W) @ W + b: one GEMM."""
+    T, G = a.shape[0], 3 * s.Hp
+    zx = m._buf('gzx%d' % si, (T, n_pad, G))
+    scale = {} if BW is None else dict(a_scale=BW, a_scale_period=n_pad)
+    ops.gemm(a, m.params, zx, T * n_pad, G, s.f_in_pad, b_off=s.oW, bias=m._view(s.ob, G),
+             **scale)
+    return zx
+
+
+def _gru_uni_forward(m, s, si, a, rec, fp):
+    a = a.contiguous()
+    n_pad = fp.n_pad
+    T, Hp = a.shape[0], s.Hp
+    BW, BU = fp.stage_masks(si)[:2]
+    rec['BW'], rec['BU'] = BW, BU
+    BW, BU = (None if BW is None else BW[0]), (None if BU is None else BU[0])
+    zx = _gru_uni_zx(m, s, si, a, BW, n_pad)
+    h = m._buf('gh%d' % si, (T, n_pad, Hp))
+    gates = m._buf('ggates%d' % si, (T, n_pad, 3 * Hp))
+    rm = m._buf('grm%d' % si, (T, n_pad, Hp))
+    ops.gru_uni_seq_fwd(zx, m._view(s.oU, Hp * 3 * Hp), h, gates, rm, T, n_pad, Hp, act=s.act,
+                        mask_u=BU)
+    rec.update(h=h, gates=gates, rm=rm)
+    return h
+
+
+def _gru_uni_backward(m, s, si, rec, da, bp):
+    """BPTT from the zero state, then dU_z, dU_r = (h_prev (.) B_U)^T [da_z | da_r], dU_h =
+    (r (.) m)^T da_h, dW = (x (.) B_W)^T da, db from the per-batch-tile sums, dx = B_W (.)
+    (da @ W^T).  Returns dx (or None)."""
+    split = bp.split
+    T, n_pad = da.shape[0], da.shape[1]
+    rows, Hp = T * n_pad, s.Hp
+    G = 3 * Hp
+    BW, BU, h, a_in = rec['BW'], rec['BU'], rec['h'], rec['in'].contiguous()
+    BW, BU = (None if BW is None else BW[0]), (None if BU is None else BU[0])
+    dg = m._buf('gda%d' % si, (T, n_pad, G))
+    dbp = m._buf('gdbp%d' % si, (n_pad // 16, G))
+    zmx = m._buf('gdamax%d' % si, (1,))
+    ops.gru_uni_seq_bwd(da.contiguous(), m._view(s.oU, Hp * G), h, rec['gates'], dg, T, n_pad,
+                        Hp, act=s.act, mask_u=BU, db_part=dbp, dz_absmax=zmx)
+    ops.colsum(dbp, n_pad // 16, G, G, m._gview(s.ob, G))
+    kk = (T - 1) * n_pad
+    if kk > 0:      # h_prev of frame t is h[t - 1]: 0 before frame 0
+        ops.gemm(h, dg, m.grads, Hp, 2 * Hp, kk, trans_a=True, lda=Hp, ldb=G, ldc=G,
+                 b_off=n_pad * G, c_off=s.oU, split_k=split, a_scale=BU, a_scale_period=n_pad,
+                 b_absmax=zmx)
+    else:
+        m._gview(s.oU, Hp * G).view(Hp, G)[:, :2 * Hp].zero_()
+    ops.gemm(rec['rm'], dg, m.grads, Hp, Hp, rows, trans_a=True, lda=Hp, ldb=G, ldc=G,
+             b_off=2 * Hp, c_off=s.oU + 2 * Hp, split_k=split, b_absmax=zmx)
+    scale = {} if BW is None else dict(a_scale=BW, a_scale_period=n_pad)
+    ops.gemm(a_in, dg, m.grads, s.f_in_pad, G, rows, trans_a=True, c_off=s.oW, split_k=split,
+             b_absmax=zmx, **scale)
+    if bp.first:
+        return None
+    dx = m._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
+    scale = {} if BW is None else dict(c_scale=BW, c_scale_period=n_pad)
+    ops.gemm(dg, m.params, dx, rows, s.f_in_pad, G, trans_b=True, b_off=s.oW, a_absmax=zmx,
+             **scale)
+    return dx
+
+
+def _gru_uni_stream(m, s, si, a, ss):
+    """The new frames of a unidirectional GRU: the zx GEMM of the chunk, then the recurrence from
+    the stage's state into the other buffer of its pair, then the swap.  State: two (n_pad, Hp)
+    buffers, zero-filled when created or reset; no ring."""
+    a = a.contiguous()
+    Tq, n_pad, Hp = a.shape[0], a.shape[1], s.Hp
+    st = ss.state.setdefault(si, {})
+    if 'h' not in st:
+        st['h'] = [ss.zeros((n_pad, Hp)), ss.zeros((n_pad, Hp))]
+    zx = _gru_uni_zx(m, s, si, a, None, n_pad)
+    h = m._buf('gh%d' % si, (Tq, n_pad, Hp))
+    gates = m._buf('ggates%d' % si, (Tq, n_pad, 3 * Hp))
+    rm = m._buf('grm%d' % si, (Tq, n_pad, Hp))
+    ops.gru_uni_seq_fwd(zx, m._view(s.oU, Hp * 3 * Hp), h, gates, rm, Tq, n_pad, Hp, act=s.act,
+                        h0=st['h'][0], h_last=st['h'][1])
+    st['h'].reverse()
+    return h
 
 
 def _birhn_forward(m, s, si, a, rec, fp):
@@ -1014,3 +1137,15 @@ KINDS = {
     'birhn': Kind(_birhn_build, _birhn_forward, _birhn_backward,
                   mask_shape=_birhn_mask_shape),
 }
+
+# Variants of a kind with a step handler of their own (see the K26 note at the top):
+# kind -> (says whether a stage is the variant, its stream(m, s, si, a, ss))
+STREAM_VARIANTS = {
+    'bigru': (lambda s: getattr(s, 'directions', 2) == 1, _gru_uni_stream),
+}
+
+
+def stream_variant(s):
+    """The step handler of a stage that streams as a variant of its kind, or None."""
+    is_variant, handler = STREAM_VARIANTS.get(s.kind, (None, None))
+    return handler if handler is not None and is_variant(s) else None

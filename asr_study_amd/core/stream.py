@@ -3,7 +3,8 @@ every attention layer under a window (chunk, left >= 0, 0), every depthwise conv
 
 ``Model.stream()`` returns a ``StreamSession``.  It keeps, per stage, what the stage carries from
 step to step -- the ring of keys and values of an attention layer, the ring of input frames of a
-depthwise convolution (core/stages.py: the ``stream`` handlers), the greedy decoder's last label
+depthwise convolution, the (N, H) state of a unidirectional GRU (core/stages.py: the ``stream``
+handlers; a bare GRU has no look-ahead at all), the greedy decoder's last label
 -- and runs the stage list on ``step`` new strided frames at a time, one launch per stage and no
 host synchronisation inside a step.  The result is the full forward of the whole utterance:
 bit for bit in the attention cores and the convolutions (their kernels add the same terms in the
@@ -22,7 +23,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .stages import KINDS, STREAM_AS_FORWARD, Pass, stream_check
+from .stages import KINDS, STREAM_AS_FORWARD, Pass, stream_check, stream_variant
 
 NO_END = 1 << 30            # the length of a stream whose end is not known yet
 
@@ -222,9 +223,11 @@ class StreamSession(object):
     # ------------------------------------------------------------------ state
     def reset(self):
         for st in self.state.values():
-            for k in [k for k in st if k != 'ring']:
+            for k in [k for k in st if k not in ('ring', 'h')]:
                 del st[k]           # (projected tables: the weights may have changed)
-            st['ring'].zero_()
+            # a ring, or the pair of state buffers of a unidirectional GRU (which has no ring)
+            for t in ([st['ring']] if 'ring' in st else []) + list(st.get('h', ())):
+                t.zero_()
         self.frames_in = self.frames_out = 0
         self.t0 = self.Tq = 0
         self._ended = [None] * self.N           # input lengths, where known
@@ -441,8 +444,9 @@ class StreamSession(object):
             s = m.stages[si]
             kind = KINDS[s.kind]
             rec = {'in': a}
-            if kind.stream is not None:
-                a = kind.stream(m, s, si, a, self)
+            step = stream_variant(s) or kind.stream
+            if step is not None:
+                a = step(m, s, si, a, self)
             else:
                 assert s.kind in STREAM_AS_FORWARD
                 a = kind.forward(m, s, si, a, rec, fp)

@@ -172,9 +172,11 @@ __global__ void rec_sum_kernel(const float4* __restrict__ h, float4* __restrict_
   }
 }
 
-// db_part (n_pad / 16, 2, L, W): sums of da (L, T, n_pad, 2, W) over the 16 rows of a batch tile
+// db_part (n_pad / 16, ND, L, W): sums of da (L, T, n_pad, ND, W) over the 16 rows of a batch tile
 // and all frames of a level, in a fixed order (16 columns x 16 interleaved slices per workgroup,
-// the slices added in sequence); max |da| beside it.  blockIdx.z = d * L + l.
+// the slices added in sequence); max |da| beside it.  blockIdx.z = d * L + l.  ND: directions in
+// the slabs, 2 or (the unidirectional GRU) 1; a direction's sums do not depend on it.
+template <int ND>
 __global__ void __launch_bounds__(kThreads)
 rec_dbias_kernel(const float* __restrict__ da, float* __restrict__ db_part, unsigned* dz_absmax,
                  int T, int n_pad, int L, int W) {
@@ -186,7 +188,7 @@ rec_dbias_kernel(const float* __restrict__ da, float* __restrict__ db_part, unsi
   if (c < W) {
     for (int i = sl; i < T * 16; i += 16) {
       const int t = i >> 4, n = tile * 16 + (i & 15);
-      const float v = da[((((size_t)l * T + t) * n_pad + n) * 2 + d) * W + c];
+      const float v = da[((((size_t)l * T + t) * n_pad + n) * ND + d) * W + c];
       sum += v;
       mx = fmaxf(mx, fabsf(v));
     }
@@ -196,7 +198,7 @@ rec_dbias_kernel(const float* __restrict__ da, float* __restrict__ db_part, unsi
   if (sl == 0 && c < W && db_part != nullptr) {
     float tot = 0.f;
     for (int k = 0; k < 16; ++k) tot += part[k][cl];
-    db_part[(((size_t)tile * 2 + d) * L + l) * W + c] = tot;
+    db_part[(((size_t)tile * ND + d) * L + l) * W + c] = tot;
   }
   if (dz_absmax != nullptr) {
     mx = asr_wave_max(mx);
@@ -222,12 +224,13 @@ inline int rec_sum(const float* h, float* y_sum, long long rows, int H, hipStrea
   return ASR_OK;
 }
 
-// db_part and / or dz_absmax (either may be null, not both) of da (L, T, n_pad, 2, W)
+// db_part and / or dz_absmax (either may be null, not both) of da (L, T, n_pad, ND, W)
+template <int ND = 2>
 inline int rec_dbias(const float* da, float* db_part, float* dz_absmax, int T, int n_pad, int L,
                      int W, hipStream_t stream) {
   if (dz_absmax) ASR_CHECK_HIP(hipMemsetAsync(dz_absmax, 0, sizeof(float), stream));
-  hipLaunchKernelGGL(rec_dbias_kernel, dim3((W + 15) / 16, n_pad / 16, 2 * L), dim3(kThreads), 0,
-                     stream, da, db_part, reinterpret_cast<unsigned*>(dz_absmax), T, n_pad, L, W);
+  hipLaunchKernelGGL(rec_dbias_kernel<ND>, dim3((W + 15) / 16, n_pad / 16, ND * L), dim3(kThreads),
+                     0, stream, da, db_part, reinterpret_cast<unsigned*>(dz_absmax), T, n_pad, L, W);
   ASR_CHECK_LAUNCH();
   return ASR_OK;
 }
@@ -243,7 +246,8 @@ auto rec_with_rows(int NR, F&& f) {
 
 inline bool rec_act_ok(int id) { return id == 0 || id == 1 || id == 4 || id == kActClipped; }
 
-// the checks every plan starts with (asr_rnn_args / asr_gru_args / asr_rhn_args: the same fields);
+// the checks every plan starts with (asr_rnn_args / asr_gru_args / asr_gru_uni_args / asr_rhn_args:
+// the same fields);
 // persistent_form: mode 2 exists
 template <class Args>
 int rec_check_args(const char* pfx, const Args* a, bool persistent_form) {

@@ -425,6 +425,40 @@ def gru_plan(T, n_pad, H, backward=False, mode=0):
     return _rec_plan('gru', _rec_args(L.GruArgs(), T, n_pad, H, mode), backward)
 
 
+# --------------------------------------------------------------------------- unidirectional GRU (K28)
+GRU_UNI_WS = ('gru_uni_fwd', 'gru_uni_bwd')     # scratch only, as GRU_WS
+
+
+def gru_uni_seq_fwd(zx, U, h, gates, rm, T, n_pad, H, act='tanh', mask_u=None, h0=None,
+                    h_last=None, mode=0):
+    """One direction, frames 0 .. T-1: h (T, n_pad, H), gates (T, n_pad, 3H) = z | r | hh and
+    rm (T, n_pad, H) from zx (T, n_pad, 3H), U (H, 3H), optional B_U (n_pad, H).  h0 (n_pad, H):
+    the state before frame 0 (None: zeros); h_last (n_pad, H) <- h[T-1] when given, never the
+    same buffer as h0.  With h0 = None the outputs are direction 0 of gru_seq_fwd bit for bit."""
+    _check_f32(zx, U, h, gates, rm, mask_u, h0, h_last)
+    a = _rec_args(L.GruUniArgs(), T, n_pad, H, mode, U, act, mask_u, h=h, gates=gates, zx=zx,
+                  rm=rm, h0=h0, h_last=h_last)
+    return _rec_run('gru_uni', a, False, GRU_UNI_WS[0], zx.device)
+
+
+def gru_uni_seq_bwd(dy, U, h, gates, da, T, n_pad, H, act='tanh', mask_u=None, dy_ld=None,
+                    mode=0, db_part=None, dz_absmax=None):
+    """BPTT from the zero state: da (T, n_pad, 3H) = da_z | da_r | da_h.  dy: the gradient of the
+    layer output, rows dy_ld floats apart (default H).  db_part (n_pad/16, 3H): per-batch-tile
+    sums of da; dz_absmax (1,): max |da|."""
+    _check_f32(dy, U, h, gates, da, mask_u, db_part, dz_absmax)
+    a = _rec_args(L.GruUniArgs(), T, n_pad, H, mode, U, act, mask_u, h=h, gates=gates, dy=dy,
+                  da=da, db_part=db_part, dz_absmax=dz_absmax)
+    a.dy_ld = int(H if dy_ld is None else dy_ld)
+    return _rec_run('gru_uni', a, True, GRU_UNI_WS[1], dy.device)
+
+
+def gru_uni_plan(T, n_pad, H, backward=False, mode=0):
+    """As gru_plan, for one direction: the same rows and units, half the workgroups
+    (asr_gru_uni_plan)."""
+    return _rec_plan('gru_uni', _rec_args(L.GruUniArgs(), T, n_pad, H, mode), backward)
+
+
 # --------------------------------------------------------------------------- RHN (K17)
 RHN_WS = ('rhn_fwd', 'rhn_bwd')     # scratch only: the stepwise form has no status words
 

@@ -198,6 +198,9 @@ def model_config(model):
                 'name': name, 'trainable': True, 'merge_mode': s.merge,
                 'layer': {'class_name': 'SimpleRNN', 'config': _simplernn_config(
                     'simplernn_%d' % counts['bidirectional'], s)}}, [prev])
+        elif s.kind == 'bigru' and getattr(s, 'directions', 2) == 1:
+            name = nm('gru')            # a bare (unidirectional) GRU: a plain Keras GRU layer
+            add('GRU', name, _gru_config(name, s), [prev])
         elif s.kind == 'bigru':
             name = nm('bidirectional')
             add('Bidirectional', name, {
@@ -429,6 +432,14 @@ def topology_from_config(text):
                 batch_norm=bool(r.get('batch_norm', False)), bn_epsilon=r.get('bn_epsilon', 1e-3),
                 bn_momentum=r.get('bn_momentum', 0.99)),
                 merge_mode=c.get('merge_mode', 'concat'))(o)
+        elif kind == 'GRU':
+            o = L.GRU(
+                c['output_dim'], init=c.get('init', 'glorot_uniform'),
+                inner_init=c.get('inner_init', 'orthogonal'), activation=_act_from(c),
+                inner_activation=c.get('inner_activation', 'hard_sigmoid'),
+                W_regularizer=reg(c.get('W_regularizer')), U_regularizer=reg(c.get('U_regularizer')),
+                dropout_W=c.get('dropout_W', 0.), dropout_U=c.get('dropout_U', 0.),
+                consume_less=c.get('consume_less', 'gpu'))(o)
         elif kind == 'Bidirectional' and c['layer']['class_name'] == 'RHN':
             r = c['layer']['config']
             o = L.Bidirectional(L.RHN(

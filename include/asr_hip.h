@@ -61,7 +61,8 @@ const char* asr_last_error(void);
  * asr_relattn_win_* / asr_dwconv1d_pad_* entry points (K25): additions only as well;
  * asr_attn_stream_args, asr_ring_put, asr_attn_stream_*, asr_relattn_stream_fwd,
  * asr_dwconv1d_stream_fwd and asr_ctc_greedy_stream (K26): additions only again;
- * asr_ctc_beam_stream, asr_ctc_beam_lm_stream and their two size functions (K27): likewise. */
+ * asr_ctc_beam_stream, asr_ctc_beam_lm_stream and their two size functions (K27): likewise;
+ * asr_gru_uni_args and the asr_gru_uni_* entry points (K28): additions only. */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -540,6 +541,56 @@ int asr_gru_seq_bwd(const asr_gru_args* a, void* workspace, size_t ws_bytes,
 /* columns per workgroup, workgroups of the widest launch of a step (both directions).        */
 int asr_gru_plan(const asr_gru_args* a, int backward, int* persistent, int* rows, int* units,
                  int* blocks);
+
+/* ------------------------------------------------------------------------ */
+/* K28 UNIDIRECTIONAL GRU recurrence with a carried state (csrc/gru.hip: the */
+/* K16 step kernel with one direction in every slab).  The cell, BPTT and    */
+/* the saved slopes are K16's; frames run 0 .. T-1 in order and no slab has  */
+/* a direction axis.  The tile plan is the one asr_gru_plan gives for the    */
+/* same (n_pad, H), so with h0 = NULL every output equals direction 0 of the */
+/* K16 call on the same operands bit for bit.                                */
+/* The forward pass may start from a state: h0 is h before frame 0 (NULL:    */
+/* zeros, and frame 0 skips its two products as K16 does), and h_last, when  */
+/* given, receives h[T-1] from the epilogue of the last launch (no extra     */
+/* launch).  Frame 0 reads h0 by the code that reads h[t-1] at t > 0, so one */
+/* call over T frames and two calls over [0, k) and [k, T) with h0 = the     */
+/* first call's h_last give the same bits.  h_last == h0 is refused: a call  */
+/* leaves the state it starts from intact (it can be repeated), and a caller */
+/* keeps two buffers and swaps them.  BPTT starts from the zero state: it    */
+/* takes neither.  Stepwise only: two launches per frame, no float atomics.  */
+/* Every argument error (H % 4, n_pad % 16, T < 1, a missing pointer, the    */
+/* alias, mode 2, an unknown activation, a short workspace) is refused with  */
+/* ASR_ERR_INVALID before any device call.                                   */
+/* ------------------------------------------------------------------------ */
+typedef struct asr_gru_uni_args {
+  int T, n_pad, H;       /* as asr_gru_args                                             */
+  int mode;              /* 0 = the plan's form, 1 = stepwise; 2: ASR_ERR_INVALID        */
+  int activation;        /* 0 tanh, 1 relu, 4 linear, ASR_ACT_CLIPPED_RELU              */
+  float clip;            /* max_value of the clipped relu                               */
+  const float* U;        /* (H, 3H), Keras [in][out], blocks z, r, h                    */
+  const float* mask_u;   /* optional (n_pad, H) B_U, constant over time                  */
+  const float* zx;       /* forward: (T, n_pad, 3H) = x @ W + b                          */
+  float* h;              /* (T, n_pad, H): forward writes it, BPTT reads it              */
+  float* gates;          /* (T, n_pad, 3H) z | r | hh: forward writes, BPTT reads        */
+  float* rm;             /* forward: (T, n_pad, H) r (.) m, written (left operand of     */
+                         /*   dU_h)                                                      */
+  const float* h0;       /* forward, optional: (n_pad, H) state before frame 0           */
+  float* h_last;         /* forward, optional: (n_pad, H) <- h[T-1]; never h0            */
+  const float* dy;       /* BPTT: gradient of the layer output, row (t, n) at dy_ld      */
+  int dy_ld;             /*   floats per (t, n) row, >= H, a multiple of 4               */
+  float* da;             /* BPTT: (T, n_pad, 3H) da_z | da_r | da_h                      */
+  float* db_part;        /* BPTT, optional: (n_pad/16, 3H) per-batch-tile sums of da     */
+  float* dz_absmax;      /* BPTT, optional: max |da| (written, not accumulated)          */
+} asr_gru_uni_args;
+/* Workspace: scratch only (BPTT: U^T and two (n_pad, H) vectors); no status words.          */
+size_t asr_gru_uni_workspace_bytes(const asr_gru_uni_args* a, int backward);
+int asr_gru_uni_seq_fwd(const asr_gru_uni_args* a, void* workspace, size_t ws_bytes,
+                        asr_stream_t stream);
+int asr_gru_uni_seq_bwd(const asr_gru_uni_args* a, void* workspace, size_t ws_bytes,
+                        asr_stream_t stream);
+/* As asr_gru_plan: the same rows and units, half the workgroups.                             */
+int asr_gru_uni_plan(const asr_gru_uni_args* a, int backward, int* persistent, int* rows,
+                     int* units, int* blocks);
 
 /* ------------------------------------------------------------------------ */
 /* K17 Recurrent Highway Network recurrence of a Bidirectional layer (Zilly  */

@@ -6,6 +6,7 @@ Model.forward over a trailing slab of left + chunk strided frames for every chun
     python tools/stream_bench.py [--rounds R] [--reps K] [--json FILE] [--streams 1 64]
                                  [--decoder none greedy beam] [--beam_width 8 100]
     python tools/stream_bench.py --beam_call_cost [--beam_width 8 100] [--streams 1 64]
+    python tools/stream_bench.py --model ds2_uni [--streams 1 16]
 
 Model: conformer(positions='relative', context=(16, 64, 0), causal_conv=True) at the factory's
 default sizes (80 features, the two-convolution front-end, d_model 256, 4 heads, 6 blocks), 10 ms
@@ -15,6 +16,12 @@ of audio per input frame, time stride 2.  A step is 16 strided frames = 320 ms o
            front-end over its window, every stage on 16 new frames, the logits back on the host
   re-run   Model.forward (inference) over 2 (left + chunk) = 160 input frames, which is NOT equal
            to the full forward (the left context of layer 2 would need layer 1's, and so on)
+
+``--model ds2_uni`` (K28) times deep_speech2(rnn_type='gru', bidirectional=False)
+at the factory's sizes instead (80 features, the two-convolution front-end, 5 x 512 unidirectional
+GRU): the same step of 16 strided frames = 320 ms of audio, the same ``stream`` variant and
+decoders.  It has no ``re-run`` variant: a recurrent layer has no bounded left context to re-run
+over.
 
 ``--decoder`` adds sessions that decode (K27), timed in the same rounds as the
 decoder-less one: ``greedy`` (variant 'stream+greedy': asr_ctc_greedy_stream per step) and
@@ -132,6 +139,7 @@ def main(argv=None):
     ap.add_argument('--decoder', nargs='+', default=['none'], choices=['none', 'greedy', 'beam'])
     ap.add_argument('--beam_width', type=int, nargs='+', default=[100])
     ap.add_argument('--beam_call_cost', action='store_true')
+    ap.add_argument('--model', default='conformer', choices=['conformer', 'ds2_uni'])
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit('stream_bench: no GPU')
@@ -141,7 +149,11 @@ def main(argv=None):
             with open(args.json, 'w') as f:
                 json.dump(results, f, indent=1)
         return results
-    model = models.conformer(positions='relative', context=CONTEXT, causal_conv=True, dropout=0)
+    if args.model == 'ds2_uni':
+        model = models.deep_speech2(rnn_type='gru', bidirectional=False, dropout=0)
+    else:
+        model = models.conformer(positions='relative', context=CONTEXT, causal_conv=True,
+                                 dropout=0)
     model.decoder = None
     rs = np.random.RandomState(0)
     results = []
@@ -163,10 +175,11 @@ def main(argv=None):
             frames = (WARMUP + args.rounds * args.reps) * ss.step    # every feed of this run
             variants['stream+beam%d' % width] = decoding(
                 model, n, x, dict(beam_width=width, max_frames=max(3000, frames)))
-        variants.update({
-            're-run': lambda: model.forward(slab, training=False, need_grad=False, n_valid=n,
-                                            seq_len=lens)[:, :n].cpu(),
-        })
+        if args.model == 'conformer':
+            variants.update({
+                're-run': lambda: model.forward(slab, training=False, need_grad=False, n_valid=n,
+                                                seq_len=lens)[:, :n].cpu(),
+            })
         for _ in range(WARMUP):             # (the first feeds emit nothing: the front-end's reach)
             for fn in variants.values():
                 fn()
