@@ -135,6 +135,18 @@ class GruUniArgs(C.Structure):
                 ('dz_absmax', void_p)]
 
 
+class LstmUniArgs(C.Structure):
+    # asr_lstm_uni_args (K29): one direction, no direction axis; (h0, c0) / (h_last, c_last)
+    # carry the state
+    _fields_ = [('T', C.c_int), ('n_pad', C.c_int), ('H', C.c_int), ('mode', C.c_int),
+                ('activation', C.c_int),
+                ('U', void_p), ('mask_u', void_p), ('zx', void_p), ('h', void_p),
+                ('cell', void_p), ('gates', void_p), ('h0', void_p), ('c0', void_p),
+                ('h_last', void_p), ('c_last', void_p),
+                ('dy', void_p), ('dy_ld', C.c_int), ('dz', void_p), ('db_part', void_p),
+                ('dz_absmax', void_p)]
+
+
 class RhnArgs(C.Structure):
     _fields_ = [('T', C.c_int), ('n_pad', C.c_int), ('H', C.c_int), ('depth', C.c_int),
                 ('coupling', C.c_int), ('mode', C.c_int),
@@ -293,6 +305,11 @@ SIGNATURES = {
     'asr_gru_uni_seq_bwd': (C.c_int, [C.POINTER(GruUniArgs), void_p, C.c_size_t, void_p]),
     'asr_gru_uni_plan': (C.c_int, [C.POINTER(GruUniArgs), C.c_int, c_int_p, c_int_p, c_int_p,
                                    c_int_p]),
+    'asr_lstm_uni_workspace_bytes': (C.c_size_t, [C.POINTER(LstmUniArgs), C.c_int]),
+    'asr_lstm_uni_seq_fwd': (C.c_int, [C.POINTER(LstmUniArgs), void_p, C.c_size_t, void_p]),
+    'asr_lstm_uni_seq_bwd': (C.c_int, [C.POINTER(LstmUniArgs), void_p, C.c_size_t, void_p]),
+    'asr_lstm_uni_plan': (C.c_int, [C.POINTER(LstmUniArgs), C.c_int, c_int_p, c_int_p, c_int_p,
+                                    c_int_p]),
     'asr_rhn_workspace_bytes': (C.c_size_t, [C.POINTER(RhnArgs), C.c_int]),
     'asr_rhn_seq_fwd': (C.c_int, [C.POINTER(RhnArgs), void_p, C.c_size_t, void_p]),
     'asr_rhn_seq_bwd': (C.c_int, [C.POINTER(RhnArgs), void_p, C.c_size_t, void_p]),

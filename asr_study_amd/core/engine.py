@@ -202,7 +202,7 @@ class Model(object):
             s.p_hi = alloc.params
             self.stages.append(s)
         del self._alloc
-        widest = max([st.Hp for st in self.stages if st.kind == 'bilstm'] + [0])
+        widest = max([st.Hp for st in self.stages if self._is_bilstm(st)] + [0])
         self.packed = (os.environ.get('ASR_GEMM_PREC', '1') != '0' and
                        (self._packed_mode == '1' or (self._packed_mode == 'auto' and widest >= 512)))
         self.num_classes = f_real
@@ -379,16 +379,24 @@ class Model(object):
         return self._one
 
     @staticmethod
+    def _is_bilstm(s):
+        """A BIDIRECTIONAL LSTM stage: the one every scheduled path of this module is about (packed
+        planes, the sizing by the widest recurrence, the pipe and side streams, compact BPTT).  A
+        'bilstm' stage with ``directions`` = 1 is the unidirectional variant (core/stages.py,
+        csrc/lstm_uni.hip): it takes none of them."""
+        return s.kind == 'bilstm' and getattr(s, 'directions', 2) == 2
+
+    @staticmethod
     def _y_bounded(s):
         """|h| <= 1 for a BiLSTM stage whose output activation is bounded (h = o * act(c), 0 <= o
         <= 1): only then may a packed operand built from its y take 1 as the tensor bound (x the
         inverted-dropout scale, far below the 2^8 head-room of pow2_scale(1)).  relu / linear /
         softplus carry an unbounded c through: those outputs are measured."""
-        return s.kind == 'bilstm' and s.act in ('tanh', 'sigmoid', 'hard_sigmoid', 'softsign')
+        return Model._is_bilstm(s) and s.act in ('tanh', 'sigmoid', 'hard_sigmoid', 'softsign')
 
     def _stage_packed(self, s):
         """Whether a BiLSTM stage's GEMMs run on packed operands (plain cell only)."""
-        return (self.packed and s.kind == 'bilstm' and s.mi is None and s.ln is None
+        return (self.packed and self._is_bilstm(s) and s.mi is None and s.ln is None
                 and s.f_in_pad % 8 == 0 and s.Hp % 8 == 0)      # 16-byte rows of the planes
 
     def _pack_weights(self):
@@ -601,7 +609,7 @@ class Model(object):
                                 n_pad, Hp, has_mi=s.mi is not None, mask_u=BU,
                                 zone_c=var.get('zone_c'), zone_h=var.get('zone_h'),
                                 act=s.act)
-        elif pipe and nxt is not None and nxt.kind == 'bilstm' and not var \
+        elif pipe and nxt is not None and self._is_bilstm(nxt) and not var \
                 and nxt.mi is None and nxt.ln is None:
             # after S = 13T/16 steps the frames [T-S, S) of y are final in BOTH
             # directions: the next layer's input projection of those frames runs
@@ -692,7 +700,7 @@ class Model(object):
             return False
         if not hasattr(self, '_num_cu'):
             self._num_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
-        widest = max([(st.Hp + 15) // 16 for st in self.stages if st.kind == 'bilstm'] + [0])
+        widest = max([(st.Hp + 15) // 16 for st in self.stages if self._is_bilstm(st)] + [0])
         return 2 * (n_pad // 16) * widest >= self._num_cu
 
     def _bptt_compact(self, s, n_pad):
@@ -700,7 +708,7 @@ class Model(object):
         leaves free (plain cell, persistent kernels, H = 256 / 512, at most half of the CUs)."""
         if self._compact_mode == '0' or self.device.type != 'cuda' or self.lstm_mode != 0:
             return False
-        if s.kind != 'bilstm' or s.mi is not None or s.ln is not None or s.Hp not in (256, 512):
+        if not self._is_bilstm(s) or s.mi is not None or s.ln is not None or s.Hp not in (256, 512):
             return False
         if s.zoneout_c > 0 or s.zoneout_h > 0 or s.act != 'tanh':
             return False
@@ -720,7 +728,7 @@ class Model(object):
             return True
         if not hasattr(self, '_num_cu'):
             self._num_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
-        widest = max([(st.Hp + 15) // 16 for st in self.stages if st.kind == 'bilstm'] + [0])
+        widest = max([(st.Hp + 15) // 16 for st in self.stages if self._is_bilstm(st)] + [0])
         return 0 < 2 * (n_pad // 16) * widest <= self._num_cu // 2
 
     def _variant_args(self, s, si, T, n_pad, training, masks):
@@ -1168,7 +1176,7 @@ class Model(object):
         # (compact schedule: is there a BiLSTM stage below whose BPTT this layer's
         # weight gradients could run beside?  A convolution / Dense / nothing below:
         # chip-filling GEMMs either way -- one stream, as in the serial schedule)
-        below = any(st.kind == 'bilstm' for st in self.stages[:si])
+        below = any(self._is_bilstm(st) for st in self.stages[:si])
         if not overlap:
             weight_grads('gemm')
             if reduce_now and not first:

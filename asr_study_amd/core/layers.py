@@ -149,6 +149,12 @@ class LSTM(object):
     variational dropout_W / dropout_U, W/U l2 regularisers,
     multiplicative integration (mi=[alpha, beta1, beta2] inits), zoneout_c / zoneout_h and
     layer_norm=[gain_init, bias_init] (LN of h@U, x@W and the output cell state).
+
+    Used bare, ``LSTM(H, ...)(x)``, it is a UNIDIRECTIONAL layer (frames in order, output width H)
+    on the stepwise kernels of csrc/lstm_uni.hip (K29): the plain cell with any ``activation``,
+    dropout_W / dropout_U and the l2 regularisers.  It trains like the wrapped layer and, its
+    state being two (N, H) vectors, streams chunk by chunk (core/stream.py).  Keras names of the
+    unwrapped layer: lstm_k_W / _U / _b.  mi, zoneout_* and layer_norm are refused there.
     """
 
     def __init__(self, output_dim, zoneout_h=0., zoneout_c=0., layer_norm=None, mi=None,
@@ -178,6 +184,17 @@ class LSTM(object):
         self.dropout_U = float(dropout_U or 0.0)
         self.l2_W = W_regularizer.l2 if W_regularizer is not None else 0.0
         self.l2_U = U_regularizer.l2 if U_regularizer is not None else 0.0
+
+    def __call__(self, x):
+        """Used bare (not inside Bidirectional): a unidirectional layer of width output_dim."""
+        for name, on in (('mi', self.mi is not None),
+                         ('zoneout_c / zoneout_h', self.zoneout_c > 0 or self.zoneout_h > 0),
+                         ('layer_norm', self.layer_norm is not None)):
+            if on:
+                raise NotImplementedError(
+                    'LSTM(%s) outside Bidirectional: the unidirectional kernels are the plain '
+                    'cell only' % name)
+        return Sym(self.output_dim, producer=self, parent=x, fc=None)
 
 
 class SimpleRNN(object):

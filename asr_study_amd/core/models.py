@@ -106,6 +106,12 @@ def ctc_model(inputs, output, **kwargs):
             spec.append({'type': 'bigru', 'H': layer.output_dim, 'activation': layer.activation,
                          'dropout_W': layer.dropout_W, 'dropout_U': layer.dropout_U,
                          'l2_W': layer.l2_W, 'l2_U': layer.l2_U, 'directions': 1})
+        elif isinstance(layer, LSTM):
+            # a bare LSTM (K29): the one-direction variant of the kind (the key only then; the
+            # variant keys mi / zoneout / layer_norm are left out: LSTM.__call__ refused them)
+            spec.append({'type': 'bilstm', 'H': layer.output_dim, 'dropout_W': layer.dropout_W,
+                         'dropout_U': layer.dropout_U, 'l2_W': layer.l2_W, 'l2_U': layer.l2_U,
+                         'activation': layer.activation, 'directions': 1})
         elif isinstance(layer, Bidirectional) and isinstance(layer.lstm, RHN):
             r = layer.lstm
             spec.append({'type': 'birhn', 'H': r.output_dim, 'depth': r.depth,
@@ -262,28 +268,41 @@ def deep_speech(num_features=81, num_classes=29, num_hiddens=2048, dropout=0.1, 
 def brsmv1(num_features=39, num_classes=28, num_hiddens=256, num_layers=5,
            dropout=0.2, zoneout=0., input_dropout=False, input_std_noise=.0,
            weight_decay=1e-4, residual=None, layer_norm=None, mi=None,
-           activation='tanh', **kw):
-    """BRSM v1.0 (core/models.py:217-281), same defaults."""
+           activation='tanh', bidirectional=True, **kw):
+    """BRSM v1.0 (core/models.py:217-281), same defaults.
+
+    bidirectional=False (no reference counterpart, K29): every layer is a bare, unidirectional
+    LSTM(num_hiddens) on csrc/lstm_uni.hip and the ``residual`` Dense is num_hiddens wide; zoneout,
+    mi and layer_norm are refused.  Such a model has no look-ahead: Model.stream runs it chunk by
+    chunk."""
+    if not bidirectional:
+        for name, on in (('zoneout', zoneout and zoneout > 0), ('mi', mi is not None),
+                         ('layer_norm', layer_norm is not None)):
+            if on:
+                raise NotImplementedError('brsmv1: bidirectional=False with %s: the unidirectional '
+                                          'LSTM is the plain cell only' % name)
+    width = num_hiddens * 2 if bidirectional else num_hiddens
     x = Input(name='inputs', shape=(None, num_features))
     o = x
     if input_std_noise is not None:
         o = GaussianNoise(input_std_noise)(o)
     if residual is not None:
-        o = TimeDistributed(Dense(num_hiddens * 2, W_regularizer=l2(weight_decay)))(o)
+        o = TimeDistributed(Dense(width, W_regularizer=l2(weight_decay)))(o)
     if input_dropout:
         o = Dropout(dropout)(o)
     for i, _ in enumerate(range(num_layers)):
-        new_o = Bidirectional(LSTM(num_hiddens,
-                                   return_sequences=True,
-                                   W_regularizer=l2(weight_decay),
-                                   U_regularizer=l2(weight_decay),
-                                   dropout_W=dropout,
-                                   dropout_U=dropout,
-                                   zoneout_c=zoneout,
-                                   zoneout_h=zoneout,
-                                   mi=mi,
-                                   layer_norm=layer_norm,
-                                   activation=activation))(o)
+        cell = LSTM(num_hiddens,
+                    return_sequences=True,
+                    W_regularizer=l2(weight_decay),
+                    U_regularizer=l2(weight_decay),
+                    dropout_W=dropout,
+                    dropout_U=dropout,
+                    zoneout_c=zoneout,
+                    zoneout_h=zoneout,
+                    mi=mi,
+                    layer_norm=layer_norm,
+                    activation=activation)
+        new_o = Bidirectional(cell)(o) if bidirectional else cell(o)
         if residual is not None:
             o = merge([new_o, o], mode=residual)
         else:
@@ -295,6 +314,8 @@ def brsmv1(num_features=39, num_classes=28, num_hiddens=256, num_layers=5,
         num_layers=num_layers, dropout=dropout, zoneout=zoneout, input_dropout=input_dropout,
         input_std_noise=input_std_noise, weight_decay=weight_decay, residual=residual,
         layer_norm=layer_norm, mi=mi, activation=activation)}
+    if not bidirectional:   # (only then: default checkpoints keep their bytes)
+        model.config['kwargs']['bidirectional'] = False
     return model
 
 
@@ -343,8 +364,9 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
     if rnn_type not in ('lstm', 'gru'):
         raise ValueError("deep_speech2: rnn_type %r ('lstm' or 'gru')" % (rnn_type,))
     if not bidirectional and rnn_type != 'gru':
-        raise ValueError("deep_speech2: bidirectional=False needs rnn_type='gru': there is no "
-                         "unidirectional LSTM layer")
+        raise ValueError("deep_speech2: bidirectional=False needs rnn_type='gru': this factory "
+                         "wires only the GRU one-directionally (the unidirectional LSTM is a "
+                         "bare LSTM layer, brsmv1(bidirectional=False))")
     if batch_norm not in (False, True, 'recurrent', 'layer'):
         raise ValueError("deep_speech2: batch_norm %r (False, True, 'recurrent' or 'layer')"
                          % (batch_norm,))

@@ -138,7 +138,8 @@ def segments(stages):
 def keras_names(stages):
     """[(layer name, [weight name, ...])] in Keras-1.2.2 naming, one entry per weight-bearing
     stage: 'bidirectional_k' holds 'forward_gru_k_W:0', ... and an unwrapped GRU's 'gru_k' holds
-    'gru_k_W:0', ..., k counting the unwrapped GRU layers.  Weights are numbered like their
+    'gru_k_W:0', ..., k counting the unwrapped GRU layers (an unwrapped LSTM's 'lstm_k' likewise,
+    counting the unwrapped LSTM layers).  Weights are numbered like their
     layer, except a Dense's: its group is named after the TimeDistributed around it, and Keras
     counts the TimeDistributed(Dropout / Activation) layers with those."""
     groups = {'convolution2d': 'convolution2d', 'batchnormalization': 'batchnormalization',
@@ -152,8 +153,8 @@ def keras_names(stages):
             n['timedistributed'] += bool(getattr(s, 'wrapped', False))
             continue
         cls = s.tensors[0].layer.split('_')[-1]
-        # ('forward_gru' ends in 'gru' too: an unwrapped GRU is told by its whole layer name)
-        group = 'gru' if s.tensors[0].layer == 'gru' else groups.get(cls, 'bidirectional')
+        # ('forward_gru' ends in 'gru' too: an unwrapped GRU / LSTM is told by its whole layer name)
+        group = cls if s.tensors[0].layer in ('gru', 'lstm') else groups.get(cls, 'bidirectional')
         n[group] += 1
         n['dense'] += cls == 'dense'
         out.append(('%s_%d' % (group, n[group]),
@@ -222,6 +223,21 @@ def bilstm(s, alloc, rows):
                 out.append(Tensor(layer, name, (n,), voff, vblock, (d, slice(lo, lo + n)),
                                   um if k < 4 else None, init=('blocks', (float(s.ln[k % 2]),))))
     return out
+
+
+def lstm_uni(s, alloc, rows):
+    """A bare, unidirectional LSTM (csrc/lstm_uni.hip, K29): W (in, 4Hp), U (Hp, 4Hp), b (4Hp) in
+    the unit-major / gate-minor layout; the initialisers and l2 of one direction of ``bilstm``
+    (the forget block of b is 1)."""
+    H, Hp, F = s.H, s.Hp, len(rows)
+    G, um = 4 * Hp, ('um', H, Hp)
+    s.oW, s.oU, s.ob = alloc.take(s.f_in_pad * G), alloc.take(Hp * G), alloc.take(G)
+    return [Tensor('lstm', 'W', (F, 4 * H), s.oW, (s.f_in_pad, G), (rows,), um, s.l2_W,
+                   _glorot(F, 4 * H)),
+            Tensor('lstm', 'U', (H, 4 * H), s.oU, (Hp, G), (slice(0, H),), um, s.l2_U,
+                   ('orthogonal', 1.1)),
+            Tensor('lstm', 'b', (4 * H,), s.ob, (G,), (), um,
+                   init=('blocks', (0.0, 1.0, 0.0, 0.0)))]
 
 
 def birnn(s, alloc, rows):

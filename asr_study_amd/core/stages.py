@@ -24,8 +24,8 @@ workspaces carry timeout words of their own).  Whether a stage is the first trai
 ``s.first``: no stage before it has ``tensors``.
 
 A VARIANT of a kind is a stage of that kind told by an attribute only it carries (``relative`` and
-``window`` on 'mha'; ``directions`` = 1 on 'bigru': a bare, unidirectional GRU, whose three
-handlers the kind's own hand over to).  A variant may stream where its kind does not:
+``window`` on 'mha'; ``directions`` = 1 on 'bigru' and on 'bilstm': a bare, unidirectional GRU
+or LSTM, whose three handlers the kind's own hand over to).  A variant may stream where its kind does not:
 ``STREAM_VARIANTS`` (at the end of this module) maps a kind to (is this stage the variant?, its
 step handler ``(m, s, si, a, ss)``), and ``stream_variant(s)`` is what ``stream_check`` and
 ``StreamSession._encoder`` consult FIRST, before ``Kind.stream`` -- which stays None for 'bigru'.
@@ -692,6 +692,8 @@ def stream_check(m, s, si):
 
 # --------------------------------------------------------------------------- bilstm
 def _bilstm_build(m, s, st, width):
+    if st.get('directions', 2) == 1:
+        return _lstm_uni_build(m, s, st, width)
     s.H = st['H']
     s.Hp = _pad4(s.H)
     s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
@@ -706,11 +708,122 @@ def _bilstm_build(m, s, st, width):
 
 
 def _bilstm_forward(m, s, si, a, rec, fp):
+    if getattr(s, 'directions', 2) == 1:
+        return _lstm_uni_forward(m, s, si, a, rec, fp)
     return m._bilstm_forward(s, si, a, rec, fp)
 
 
 def _bilstm_backward(m, s, si, rec, da, bp):
+    if getattr(s, 'directions', 2) == 1:
+        return _lstm_uni_backward(m, s, si, rec, da, bp)
     return m._bilstm_backward(s, si, rec, da, bp)
+
+
+# The unidirectional LSTM (K29, csrc/lstm_uni.hip): the one-direction variant of the kind, as the
+# unidirectional GRU is of 'bigru' (below).  None of the scheduled paths of the bidirectional
+# body (packed planes, pipe and side streams, compact BPTT) applies to it: engine.py asks
+# ``Model._is_bilstm`` (kind 'bilstm' AND two directions) wherever it decides one of them.  The
+# masks are direction 0's of the pair a 'bilstm' stage is drawn (same shapes, streams and step).
+def _lstm_uni_build(m, s, st, width):
+    """``s.directions`` is set on such a stage only (read it with getattr(s, 'directions', 2));
+    mi / ln are None and the zoneouts 0, for whoever reads them off a 'bilstm' stage."""
+    for k in ('mi', 'layer_norm', 'zoneout_c', 'zoneout_h'):
+        if st.get(k):
+            raise NotImplementedError('a unidirectional LSTM stage has no %s: the kernels of '
+                                      'csrc/lstm_uni.hip are the plain cell only' % k)
+    s.directions = 1
+    s.H = st['H']
+    s.Hp = _pad4(s.H)
+    s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
+    s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
+    s.mi = s.ln = None
+    s.zoneout_c = s.zoneout_h = 0.0
+    s.act = st.get('activation') or 'tanh'
+    s.tensors = P.lstm_uni(s, m._alloc, m._real_rows(s))
+    return s.H, s.Hp
+
+
+def _lstm_uni_zx(m, s, si, a, BW, n_pad):
+    """zx (T, n_pad, 4Hp) = (a (.) B_W) @ W + b: one GEMM."""
+    T, G = a.shape[0], 4 * s.Hp
+    zx = m._buf('uzx%d' % si, (T, n_pad, G))
+    scale = {} if BW is None else dict(a_scale=BW, a_scale_period=n_pad)
+    ops.gemm(a, m.params, zx, T * n_pad, G, s.f_in_pad, b_off=s.oW, bias=m._view(s.ob, G),
+             **scale)
+    return zx
+
+
+def _lstm_uni_forward(m, s, si, a, rec, fp):
+    a = a.contiguous()
+    n_pad = fp.n_pad
+    T, Hp = a.shape[0], s.Hp
+    BW, BU = fp.stage_masks(si)[:2]
+    rec['BW'], rec['BU'] = BW, BU
+    BW, BU = (None if BW is None else BW[0]), (None if BU is None else BU[0])
+    zx = _lstm_uni_zx(m, s, si, a, BW, n_pad)
+    h = m._buf('uh%d' % si, (T, n_pad, Hp))
+    cell = m._buf('ucell%d' % si, (T, n_pad, Hp))
+    gates = m._buf('ugates%d' % si, (T, n_pad, 4 * Hp))
+    ops.lstm_uni_seq_fwd(zx, m._view(s.oU, Hp * 4 * Hp), h, cell, gates, T, n_pad, Hp, act=s.act,
+                         mask_u=BU)
+    rec.update(h=h, cell=cell, gates=gates)
+    return h
+
+
+def _lstm_uni_backward(m, s, si, rec, da, bp):
+    """BPTT from the zero state, then dU = (h_prev (.) B_U)^T dz over the (T - 1) n_pad rows that
+    have an h_prev, dW = (x (.) B_W)^T dz, db from the per-batch-tile sums, dx = B_W (.)
+    (dz @ W^T).  Returns dx (or None)."""
+    split = bp.split
+    T, n_pad = da.shape[0], da.shape[1]
+    rows, Hp = T * n_pad, s.Hp
+    G = 4 * Hp
+    BW, BU, h, a_in = rec['BW'], rec['BU'], rec['h'], rec['in'].contiguous()
+    BW, BU = (None if BW is None else BW[0]), (None if BU is None else BU[0])
+    dz = m._buf('udz%d' % si, (T, n_pad, G))
+    dbp = m._buf('udbp%d' % si, (n_pad // 16, G))
+    zmx = m._buf('udzmax%d' % si, (1,))
+    ops.lstm_uni_seq_bwd(da.contiguous(), m._view(s.oU, Hp * G), h, rec['cell'], rec['gates'], dz,
+                         T, n_pad, Hp, act=s.act, mask_u=BU, db_part=dbp, dz_absmax=zmx)
+    ops.colsum(dbp, n_pad // 16, G, G, m._gview(s.ob, G))
+    kk = (T - 1) * n_pad
+    if kk > 0:      # h_prev of frame t is h[t - 1]: 0 before frame 0
+        scale = {} if BU is None else dict(a_scale=BU, a_scale_period=n_pad)
+        ops.gemm(h, dz, m.grads, Hp, G, kk, trans_a=True, b_off=n_pad * G, c_off=s.oU,
+                 split_k=split, b_absmax=zmx, **scale)
+    else:
+        m._gview(s.oU, Hp * G).zero_()
+    scale = {} if BW is None else dict(a_scale=BW, a_scale_period=n_pad)
+    ops.gemm(a_in, dz, m.grads, s.f_in_pad, G, rows, trans_a=True, c_off=s.oW, split_k=split,
+             b_absmax=zmx, **scale)
+    if bp.first:
+        return None
+    dx = m._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
+    scale = {} if BW is None else dict(c_scale=BW, c_scale_period=n_pad)
+    ops.gemm(dz, m.params, dx, rows, s.f_in_pad, G, trans_b=True, b_off=s.oW, a_absmax=zmx,
+             **scale)
+    return dx
+
+
+def _lstm_uni_stream(m, s, si, a, ss):
+    """The new frames of a unidirectional LSTM: the zx GEMM of the chunk, then the recurrence from
+    the stage's state into the other buffer of each pair, then the two swaps.  State: 'h' and 'c',
+    two (n_pad, Hp) buffers each, zero-filled when created or reset; no ring."""
+    a = a.contiguous()
+    Tq, n_pad, Hp = a.shape[0], a.shape[1], s.Hp
+    st = ss.state.setdefault(si, {})
+    if 'h' not in st:
+        st['h'] = [ss.zeros((n_pad, Hp)), ss.zeros((n_pad, Hp))]
+        st['c'] = [ss.zeros((n_pad, Hp)), ss.zeros((n_pad, Hp))]
+    zx = _lstm_uni_zx(m, s, si, a, None, n_pad)
+    h = m._buf('uh%d' % si, (Tq, n_pad, Hp))
+    cell = m._buf('ucell%d' % si, (Tq, n_pad, Hp))
+    gates = m._buf('ugates%d' % si, (Tq, n_pad, 4 * Hp))
+    ops.lstm_uni_seq_fwd(zx, m._view(s.oU, Hp * 4 * Hp), h, cell, gates, Tq, n_pad, Hp, act=s.act,
+                         h0=st['h'][0], c0=st['c'][0], h_last=st['h'][1], c_last=st['c'][1])
+    st['h'].reverse()
+    st['c'].reverse()
+    return h
 
 
 def _mask_shape(s, n_pad):
@@ -1142,6 +1255,7 @@ KINDS = {
 # kind -> (says whether a stage is the variant, its stream(m, s, si, a, ss))
 STREAM_VARIANTS = {
     'bigru': (lambda s: getattr(s, 'directions', 2) == 1, _gru_uni_stream),
+    'bilstm': (lambda s: getattr(s, 'directions', 2) == 1, _lstm_uni_stream),
 }
 
 

@@ -3,8 +3,9 @@ every attention layer under a window (chunk, left >= 0, 0), every depthwise conv
 
 ``Model.stream()`` returns a ``StreamSession``.  It keeps, per stage, what the stage carries from
 step to step -- the ring of keys and values of an attention layer, the ring of input frames of a
-depthwise convolution, the (N, H) state of a unidirectional GRU (core/stages.py: the ``stream``
-handlers; a bare GRU has no look-ahead at all), the greedy decoder's last label
+depthwise convolution, the (N, H) state of a unidirectional GRU, the (N, H) hidden and cell
+states of a unidirectional LSTM (core/stages.py: the ``stream`` handlers; a bare GRU or LSTM has
+no look-ahead at all), the greedy decoder's last label
 -- and runs the stage list on ``step`` new strided frames at a time, one launch per stage and no
 host synchronisation inside a step.  The result is the full forward of the whole utterance:
 bit for bit in the attention cores and the convolutions (their kernels add the same terms in the
@@ -223,10 +224,12 @@ class StreamSession(object):
     # ------------------------------------------------------------------ state
     def reset(self):
         for st in self.state.values():
-            for k in [k for k in st if k not in ('ring', 'h')]:
+            for k in [k for k in st if k not in ('ring', 'h', 'c')]:
                 del st[k]           # (projected tables: the weights may have changed)
-            # a ring, or the pair of state buffers of a unidirectional GRU (which has no ring)
-            for t in ([st['ring']] if 'ring' in st else []) + list(st.get('h', ())):
+            # a ring, or the pair(s) of state buffers of a unidirectional GRU ('h') or LSTM ('h'
+            # and 'c'), which have no ring
+            for t in (([st['ring']] if 'ring' in st else []) + list(st.get('h', ()))
+                      + list(st.get('c', ()))):
                 t.zero_()
         self.frames_in = self.frames_out = 0
         self.t0 = self.Tq = 0

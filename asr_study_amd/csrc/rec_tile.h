@@ -1,6 +1,7 @@
-// rec_tile.h -- what the stepwise recurrences of gru.hip and rhn.hip share (and, of the small
-// pieces, rnn.hip): the reduction of one workgroup tile, the helper kernels around a sequence and
-// the argument checks of their plans.
+// rec_tile.h -- what the stepwise recurrences of gru.hip, rhn.hip and lstm_uni.hip share (and, of
+// the small pieces, rnn.hip): the reduction of one workgroup tile, the helper kernels around a
+// sequence and the argument checks of their plans (lstm_uni.hip, whose activation ids are the
+// LSTM's 0..6, checks its own).
 //
 // Geometry of a tile (RecTile<NR>): a workgroup (256 threads) owns NR batch rows x J tile columns
 // of one direction, NR * J = 1024, NR = 64 / 32 / 16 (the largest that divides n_pad).  The

@@ -459,6 +459,50 @@ def gru_uni_plan(T, n_pad, H, backward=False, mode=0):
     return _rec_plan('gru_uni', _rec_args(L.GruUniArgs(), T, n_pad, H, mode), backward)
 
 
+# --------------------------------------------------------------------------- unidirectional LSTM (K29)
+LSTM_UNI_WS = ('lstm_uni_fwd', 'lstm_uni_bwd')     # scratch only: no status words
+
+
+def _lstm_uni_args(T, n_pad, H, mode, act=None, **fields):
+    a = L.LstmUniArgs()
+    a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
+    a.activation = activation_id(act)
+    for name, t in fields.items():
+        setattr(a, name, t.data_ptr() if t is not None else None)
+    return a
+
+
+def lstm_uni_seq_fwd(zx, U, h, cell, gates, T, n_pad, H, act='tanh', mask_u=None, h0=None,
+                     c0=None, h_last=None, c_last=None, mode=0):
+    """One direction, frames 0 .. T-1: h, cell (T, n_pad, H) and gates (T, n_pad, 4H) = the
+    post-activation i, f, g, o of every unit, from zx (T, n_pad, 4H), U (H, 4H) (both
+    [unit * 4 + gate]), optional B_U (n_pad, H).  (h0, c0) (n_pad, H): the state before frame 0
+    (None: zeros); (h_last, c_last) <- (h[T-1], cell[T-1]) when given, never the buffers of
+    (h0, c0).  act: a name of ACTIVATION_IDS."""
+    _check_f32(zx, U, h, cell, gates, mask_u, h0, c0, h_last, c_last)
+    a = _lstm_uni_args(T, n_pad, H, mode, act, U=U, mask_u=mask_u, zx=zx, h=h, cell=cell,
+                       gates=gates, h0=h0, c0=c0, h_last=h_last, c_last=c_last)
+    return _rec_run('lstm_uni', a, False, LSTM_UNI_WS[0], zx.device)
+
+
+def lstm_uni_seq_bwd(dy, U, h, cell, gates, dz, T, n_pad, H, act='tanh', mask_u=None, dy_ld=None,
+                     mode=0, db_part=None, dz_absmax=None):
+    """BPTT from the zero state: dz (T, n_pad, 4H), the gradient of the gate pre-activations.
+    dy: the gradient of the layer output, rows dy_ld floats apart (default H).  db_part
+    (n_pad/16, 4H): per-batch-tile sums of dz; dz_absmax (1,): max |dz|."""
+    _check_f32(dy, U, h, cell, gates, dz, mask_u, db_part, dz_absmax)
+    a = _lstm_uni_args(T, n_pad, H, mode, act, U=U, mask_u=mask_u, h=h, cell=cell, gates=gates,
+                       dy=dy, dz=dz, db_part=db_part, dz_absmax=dz_absmax)
+    a.dy_ld = int(H if dy_ld is None else dy_ld)
+    return _rec_run('lstm_uni', a, True, LSTM_UNI_WS[1], dy.device)
+
+
+def lstm_uni_plan(T, n_pad, H, backward=False, mode=0):
+    """{'persistent': False, 'rows', 'units', 'blocks'}: the launch geometry of a frame
+    (asr_lstm_uni_plan)."""
+    return _rec_plan('lstm_uni', _lstm_uni_args(T, n_pad, H, mode), backward)
+
+
 # --------------------------------------------------------------------------- RHN (K17)
 RHN_WS = ('rhn_fwd', 'rhn_bwd')     # scratch only: the stepwise form has no status words
 

@@ -173,6 +173,9 @@ def model_config(model):
                     'W_regularizer': _regularizer(s.l2), 'b_regularizer': None,
                     'activity_regularizer': None, 'W_constraint': None, 'b_constraint': None,
                     'bias': True}}}, [prev])
+        elif s.kind == 'bilstm' and getattr(s, 'directions', 2) == 1:
+            name = nm('lstm')           # a bare (unidirectional) LSTM: a plain LSTM layer
+            add('LSTM', name, _lstm_config(name, s), [prev])
         elif s.kind == 'bilstm':
             name = nm('bidirectional')
             add('Bidirectional', name, {
@@ -440,6 +443,14 @@ def topology_from_config(text):
                 W_regularizer=reg(c.get('W_regularizer')), U_regularizer=reg(c.get('U_regularizer')),
                 dropout_W=c.get('dropout_W', 0.), dropout_U=c.get('dropout_U', 0.),
                 consume_less=c.get('consume_less', 'gpu'))(o)
+        elif kind == 'LSTM':
+            o = L.LSTM(
+                c['output_dim'], zoneout_h=c.get('zoneout_h', 0.), zoneout_c=c.get('zoneout_c', 0.),
+                layer_norm=c.get('layer_norm'), mi=c.get('mi'),
+                W_regularizer=reg(c.get('W_regularizer')), U_regularizer=reg(c.get('U_regularizer')),
+                dropout_W=c.get('dropout_W', 0.), dropout_U=c.get('dropout_U', 0.),
+                activation=c.get('activation', 'tanh'),
+                inner_activation=c.get('inner_activation', 'hard_sigmoid'))(o)
         elif kind == 'Bidirectional' and c['layer']['class_name'] == 'RHN':
             r = c['layer']['config']
             o = L.Bidirectional(L.RHN(

@@ -62,7 +62,8 @@ const char* asr_last_error(void);
  * asr_attn_stream_args, asr_ring_put, asr_attn_stream_*, asr_relattn_stream_fwd,
  * asr_dwconv1d_stream_fwd and asr_ctc_greedy_stream (K26): additions only again;
  * asr_ctc_beam_stream, asr_ctc_beam_lm_stream and their two size functions (K27): likewise;
- * asr_gru_uni_args and the asr_gru_uni_* entry points (K28): additions only. */
+ * asr_gru_uni_args and the asr_gru_uni_* entry points (K28): additions only;
+ * asr_lstm_uni_args and the asr_lstm_uni_* entry points (K29): additions only. */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -591,6 +592,68 @@ int asr_gru_uni_seq_bwd(const asr_gru_uni_args* a, void* workspace, size_t ws_by
 /* As asr_gru_plan: the same rows and units, half the workgroups.                             */
 int asr_gru_uni_plan(const asr_gru_uni_args* a, int backward, int* persistent, int* rows,
                      int* units, int* blocks);
+
+/* ------------------------------------------------------------------------ */
+/* K29 UNIDIRECTIONAL LSTM recurrence with a carried state                   */
+/* (csrc/lstm_uni.hip; a bare LSTM(H)(x), brsmv1(bidirectional=False)).      */
+/* The plain cell of the reference (core/layers.py:432-469 without mi,       */
+/* zoneout or layer normalisation), one direction, frames 0 .. T-1 in order, */
+/* with m = h_prev (.) B_U:                                                  */
+/*     z = zx + m @ U;  i, f, o = hard_sigmoid;  g = act(z_c);               */
+/*     c = f c_prev + i g;  h = o act(c).                                    */
+/* NOT the persistent kernels of asr_lstm_seq_*: a stepwise kernel on the    */
+/* reduction core of csrc/rec_tile.h, ONE launch per frame in either pass,   */
+/* exact fp32 FMAs in a fixed order, no float atomics, no workgroup waiting  */
+/* on another, no status words.  Layouts are the LSTM gate layout, unit-     */
+/* major / gate-minor ([unit * 4 + gate], gates i, f, c, o), and no slab has */
+/* a direction axis.                                                         */
+/* The forward pass may start from a state: (h0, c0) are h and c before      */
+/* frame 0 (both or neither; NULL: zeros), and (h_last, c_last), both or     */
+/* neither, receive h[T-1] and cell[T-1] from the epilogue of the last       */
+/* launch (no extra launch).  Frame 0 reads the state by the code that reads */
+/* h[t-1], cell[t-1] at t > 0, so one call over T frames and two calls over  */
+/* [0, k) and [k, T) that hand the state on give the same bits.  Any alias   */
+/* between {h_last, c_last} and {h0, c0} is refused: a call leaves the state */
+/* it starts from intact (it can be repeated); a caller keeps two buffers of */
+/* each and swaps them.  BPTT starts from the zero state: it takes none.     */
+/* Every argument error (H % 4, n_pad % 16, T < 1, mode 2, an activation id  */
+/* outside 0..6, a missing U / h / cell / gates / zx / dy / dz, a dy_ld      */
+/* below H or no multiple of 4, half a state pair, an aliased state, a state */
+/* given to BPTT, a short workspace) is refused with ASR_ERR_INVALID and a   */
+/* message before any device call.                                           */
+/* ------------------------------------------------------------------------ */
+typedef struct asr_lstm_uni_args {
+  int T, n_pad, H;       /* frames, padded batch (multiple of 16), units (multiple of 4) */
+  int mode;              /* 0 = the plan's form, 1 = stepwise; 2: ASR_ERR_INVALID        */
+  int activation;        /* as asr_lstm_args.activation: 0 tanh .. 6 softplus            */
+  const float* U;        /* (H, 4H), [k][unit * 4 + gate]                                */
+  const float* mask_u;   /* optional (n_pad, H) B_U, constant over time                  */
+  const float* zx;       /* forward: (T, n_pad, 4H) = x @ W + b                          */
+  float* h;              /* (T, n_pad, H): forward writes it                             */
+  float* cell;           /* (T, n_pad, H): forward writes it, BPTT reads it              */
+  float* gates;          /* (T, n_pad, 4H) post-activation i, f, g, o: forward writes,   */
+                         /*   BPTT reads                                                 */
+  const float* h0;       /* forward, optional: (n_pad, H) h before frame 0 ...           */
+  const float* c0;       /*   ... and c before frame 0 (both or neither)                 */
+  float* h_last;         /* forward, optional: (n_pad, H) <- h[T-1] ...                  */
+  float* c_last;         /*   ... and <- cell[T-1] (both or neither; never h0 / c0)      */
+  const float* dy;       /* BPTT: gradient of the layer output, row (t, n) at dy_ld      */
+  int dy_ld;             /*   floats per (t, n) row, >= H, a multiple of 4               */
+  float* dz;             /* BPTT: (T, n_pad, 4H) gradient of the gate pre-activations    */
+  float* db_part;        /* BPTT, optional: (n_pad/16, 4H) per-batch-tile sums of dz     */
+  float* dz_absmax;      /* BPTT, optional: max |dz| (written, not accumulated)          */
+} asr_lstm_uni_args;
+/* Workspace: scratch only (BPTT: U^T and one (n_pad, H) vector); no status words.           */
+size_t asr_lstm_uni_workspace_bytes(const asr_lstm_uni_args* a, int backward);
+int asr_lstm_uni_seq_fwd(const asr_lstm_uni_args* a, void* workspace, size_t ws_bytes,
+                         asr_stream_t stream);
+int asr_lstm_uni_seq_bwd(const asr_lstm_uni_args* a, void* workspace, size_t ws_bytes,
+                         asr_stream_t stream);
+/* The launch geometry: *persistent = 0, *rows = batch rows and *units = tile columns of a    */
+/* workgroup (rows x units = 1024), *blocks = workgroups per launch (forward: 4H gate         */
+/* columns; BPTT: H units).                                                                   */
+int asr_lstm_uni_plan(const asr_lstm_uni_args* a, int backward, int* persistent, int* rows,
+                      int* units, int* blocks);
 
 /* ------------------------------------------------------------------------ */
 /* K17 Recurrent Highway Network recurrence of a Bidirectional layer (Zilly  */

@@ -7,6 +7,7 @@ Model.forward over a trailing slab of left + chunk strided frames for every chun
                                  [--decoder none greedy beam] [--beam_width 8 100]
     python tools/stream_bench.py --beam_call_cost [--beam_width 8 100] [--streams 1 64]
     python tools/stream_bench.py --model ds2_uni [--streams 1 16]
+    python tools/stream_bench.py --model brsmv1_uni [--streams 1 16]
 
 Model: conformer(positions='relative', context=(16, 64, 0), causal_conv=True) at the factory's
 default sizes (80 features, the two-convolution front-end, d_model 256, 4 heads, 6 blocks), 10 ms
@@ -22,6 +23,10 @@ at the factory's sizes instead (80 features, the two-convolution front-end, 5 x 
 GRU): the same step of 16 strided frames = 320 ms of audio, the same ``stream`` variant and
 decoders.  It has no ``re-run`` variant: a recurrent layer has no bounded left context to re-run
 over.
+
+``--model brsmv1_uni`` (K29) times brsmv1(bidirectional=False) at the factory's
+sizes (39 features, no front-end, 5 x 256 unidirectional LSTM): a step is 16 input frames = 160 ms
+of audio (no time stride), one launch per frame and layer.  No ``re-run`` variant either.
 
 ``--decoder`` adds sessions that decode (K27), timed in the same rounds as the
 decoder-less one: ``greedy`` (variant 'stream+greedy': asr_ctc_greedy_stream per step) and
@@ -139,7 +144,7 @@ def main(argv=None):
     ap.add_argument('--decoder', nargs='+', default=['none'], choices=['none', 'greedy', 'beam'])
     ap.add_argument('--beam_width', type=int, nargs='+', default=[100])
     ap.add_argument('--beam_call_cost', action='store_true')
-    ap.add_argument('--model', default='conformer', choices=['conformer', 'ds2_uni'])
+    ap.add_argument('--model', default='conformer', choices=['conformer', 'ds2_uni', 'brsmv1_uni'])
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit('stream_bench: no GPU')
@@ -151,6 +156,8 @@ def main(argv=None):
         return results
     if args.model == 'ds2_uni':
         model = models.deep_speech2(rnn_type='gru', bidirectional=False, dropout=0)
+    elif args.model == 'brsmv1_uni':
+        model = models.brsmv1(bidirectional=False, dropout=0)
     else:
         model = models.conformer(positions='relative', context=CONTEXT, causal_conv=True,
                                  dropout=0)
