@@ -20,7 +20,7 @@ class FrontendCfg(C.Structure):
                 ('nfft', C.c_int), ('num_filt', C.c_int), ('num_cep', C.c_int),
                 ('append_energy', C.c_int), ('d', C.c_int), ('dd', C.c_int),
                 ('stride', C.c_int), ('num_context', C.c_int),
-                ('mean_norm', C.c_int), ('var_norm', C.c_int), ('reserved', C.c_int),
+                ('mean_norm', C.c_int), ('var_norm', C.c_int), ('norm_mode', C.c_int),
                 ('pre_emph', C.c_double), ('eps', C.c_double)]
 
 
@@ -208,6 +208,16 @@ SIGNATURES = {
                                         c_int_p, C.c_int, C.c_int, void_p, void_p, void_p,
                                         void_p, void_p, C.c_int, void_p, void_p, C.c_size_t,
                                         void_p]),
+    'asr_frontend_stream_state_bytes': (C.c_size_t, [C.POINTER(FrontendCfg), C.c_int]),
+    'asr_frontend_stream_host_ints': (C.c_int, [C.c_int]),
+    'asr_frontend_stream_workspace_bytes': (C.c_size_t, [C.POINTER(FrontendCfg), C.c_int,
+                                                         C.c_int]),
+    'asr_frontend_stream_reset': (C.c_int, [C.POINTER(FrontendCfg), void_p, void_p, C.c_int,
+                                            void_p, void_p, void_p]),
+    'asr_frontend_stream': (C.c_int, [C.POINTER(FrontendCfg), void_p, void_p, void_p, C.c_int,
+                                      void_p, c_int_p, C.c_int, C.c_int, void_p, void_p, void_p,
+                                      void_p, void_p, C.c_int, c_int_p, c_int_p, void_p,
+                                      C.c_size_t, void_p]),
     'asr_gemm_workspace_bytes': (C.c_size_t, [C.POINTER(GemmArgs)]),
     'asr_gemm': (C.c_int, [C.POINTER(GemmArgs), void_p, C.c_size_t, void_p]),
     'asr_pack_hl': (C.c_int, [C.POINTER(PackArgs), void_p]),

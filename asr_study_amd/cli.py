@@ -68,6 +68,9 @@ PREDICT_FLAGS = [
     # ... unless --stream_beam: the session then decodes with the device beam search at
     # --beam_width, with --lm* where given (Model.stream(beam=True))
     ('--stream_beam', dict(action='store_true', default=False)),
+    # the pieces of --stream are raw samples, not features: the front-end runs inside the
+    # session (Model.stream(feature=...)); the model's input parser must be norm='running'
+    ('--stream_audio', dict(action='store_true', default=False)),
 ] + _DEVICE_FLAGS + [
     ('--save', dict(default=None, type=str)),
     ('--override', dict(default=False, action='store_true')),
@@ -256,12 +259,17 @@ def predict_main(argv=None):
     stream is refused with the session's message.  With ``--stream_beam`` the session decodes
     with the device beam search of width ``--beam_width`` (and ``--lm``): per piece it prints the
     committed text, which no later frame changes, and the tentative tail in brackets; the final
-    hypothesis is the whole-utterance beam decode of the streamed network outputs."""
+    hypothesis is the whole-utterance beam decode of the streamed network outputs.
+    With ``--stream_audio`` the pieces are MS milliseconds of raw samples (``--file``, or a dataset
+    whose input parser runs on the fly): the front-end runs inside the session, resumed piece by
+    piece (FeatureStream); the model's stored input parser must be ``norm='running'``."""
     import numpy as np
     parser = make_parser('Predicting with an ASR system.', PREDICT_FLAGS)
     args = parser.parse_args(argv)
     if args.stream_beam and (args.stream is None or args.no_decoder):
         raise ValueError('--stream_beam decodes a stream: it needs --stream MS and a decoder')
+    if args.stream_audio and args.stream is None:
+        raise ValueError('--stream_audio feeds raw samples to a stream: it needs --stream MS')
     if args.dataset is None and args.file is None:
         raise ValueError('dataset or file args must be set.')
     if args.dataset and args.file:
@@ -276,7 +284,7 @@ def predict_main(argv=None):
                              lm_beta=args.lm_beta,
                              is_greedy=args.stream is not None and not args.stream_beam)
     session = None
-    if args.stream is not None:
+    if args.stream is not None and not args.stream_audio:
         session = model.stream(1, beam=True) if args.stream_beam else model.stream(1)
     # only the feature / label plugins are inherited from the training run (the reference
     # overlays every stored argument, predict.py:60, which would also import its --save)
@@ -286,6 +294,14 @@ def predict_main(argv=None):
     args = merged_args(args, stored, explicit)
     feature, labels = resolve_plugins(args)
     _check_lm(model, labels)
+    if args.stream_audio:
+        if getattr(feature, 'norm', None) != 'running':
+            raise ValueError(
+                "--stream_audio: the model's input parser (%s) standardises with the statistics "
+                "of the whole utterance, which a live signal does not have: build the dataset "
+                "(extras/make_dataset.py) or train (train.py) with --input_parser_params norm "
+                "running" % (feature,))
+        session = model.stream(1, beam=True if args.stream_beam else None, feature=feature)
     if args.dataset is not None:
         flow = DatasetGenerator(feature, labels, batch_size=1, seed=0, mode='predict',
                                 shuffle=False).flow_from_fname(args.dataset, datasets=args.subset)
@@ -296,7 +312,11 @@ def predict_main(argv=None):
     truth = list(flow.labels) if flow.labels is not None else [u''] * flow.len
     results = []
     for index in range(flow.len):
-        if session is not None:
+        if args.stream_audio:
+            out = [_predict_streamed_audio(session, _raw_samples(flow, index, feature),
+                                           args.stream, feature,
+                                           None if args.no_decoder else labels)]
+        elif session is not None:
             out = [_predict_streamed(session, flow.next(), args.stream, feature,
                                      None if args.no_decoder else labels)]
         else:
@@ -340,6 +360,41 @@ def _predict_streamed(session, batch, ms, feature, labels):
         parts.append(session.feed(x[:, pos:end], ended=[T] if end == T else None))
         _print_partial(parts, labels, end, session)
     parts.append(session.finish())
+    if labels is None:
+        return np.concatenate([p[0] for p in parts], 0)
+    return [l for p in parts for l in p[0]]
+
+
+def _raw_samples(flow, index, feature):
+    """Utterance ``index`` of the flow as samples: a dataset whose input parser runs on the fly
+    holds file names or sample arrays; stored features cannot be streamed as audio."""
+    if getattr(flow, 'num_feats', None) is not None:
+        raise ValueError('--stream_audio: the dataset stores features (%d columns), not audio; '
+                         'give --file, or a dataset whose input parser runs on the fly'
+                         % flow.num_feats)
+    item = flow.inputs[[index]][0]
+    if isinstance(item, bytes):
+        item = item.decode('utf-8')
+    if isinstance(item, str):
+        return feature._load_file(item)
+    return item
+
+
+def _predict_streamed_audio(session, samples, ms, feature, labels):
+    """One utterance through a session made with ``feature=``, in pieces of ``ms`` milliseconds
+    of RAW SAMPLES: the front-end runs inside the session (feed_audio).  Prints and returns as
+    _predict_streamed."""
+    import numpy as np
+    x = np.asarray(samples, np.float32).reshape(1, -1)
+    n = x.shape[1]
+    piece = max(1, int(round(ms / 1000.0 * float(feature.fs))))
+    session.reset()
+    parts = []
+    for pos in range(0, n, piece):
+        end = min(n, pos + piece)
+        parts.append(session.feed_audio(x[:, pos:end], ended=[n] if end == n else None))
+        _print_partial(parts, labels, session.frames_in, session)
+    parts.append(session.finish_audio())
     if labels is None:
         return np.concatenate([p[0] for p in parts], 0)
     return [l for p in parts for l in p[0]]

@@ -1254,7 +1254,6 @@ class Model(object):
         x, labels, lens = inputs[0], inputs[1], inputs[2]
         if hasattr(labels, 'tocsr'):            # scipy.sparse (the reference's batches)
             csr = labels.tocsr()
-            N = x.shape[0] if not torch.is_tensor(x) or x.dim() == 3 else len(lens)
             labels = [csr.data[csr.indptr[i]:csr.indptr[i + 1]] if i < csr.shape[0] else []
                       for i in range(len(np.asarray(lens).reshape(-1)))]
         lens = np.asarray(lens).reshape(-1)
@@ -1532,7 +1531,7 @@ class Model(object):
         dec, dlen = dec.cpu().numpy(), dlen.cpu().numpy()
         return [dec[n, :dlen[n]].tolist() for n in range(N)]
 
-    def stream(self, n_streams=1, step=None, beam=None):
+    def stream(self, n_streams=1, step=None, beam=None, feature=None):
         """A StreamSession (core/stream.py, K26): cached chunk-by-chunk inference of n_streams
         streams in lock-step, ``step`` strided frames per internal step (a multiple of the
         attention chunk; default: the smallest one >= 16).  Raises ValueError, naming the stage
@@ -1544,9 +1543,11 @@ class Model(object):
         merge_repeated, lm, lm_alpha, lm_beta, max_frames) overrides them.  feed() then returns
         the labels newly committed, hypothesis() the current best, finish() the rest
         (StreamSession); max_frames (strided frames per stream, default 3000) sizes the prefix
-        tree: about max_frames * beam_width * (num_classes - 1) * 8 bytes per stream."""
+        tree: about max_frames * beam_width * (num_classes - 1) * 8 bytes per stream.
+        feature: a norm='running' extractor of preprocessing.audio; the session then owns its
+        FeatureStream and takes raw samples through feed_audio / finish_audio (K30)."""
         from .stream import StreamSession
-        return StreamSession(self, n_streams, step, beam)
+        return StreamSession(self, n_streams, step, beam, feature)
 
     def align(self, x, labels, inputs_length):
         """Forced alignment (K19): where in its utterance each label of a KNOWN transcript lies.

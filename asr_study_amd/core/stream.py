@@ -179,6 +179,10 @@ class StreamSession(object):
                          forward of THAT slab.
     reset()              zero-fills the state: the session serves another set of streams.
     frames_in, frames_out  input frames fed, strided frames emitted.
+    feed_audio(samples, ended=None), finish_audio()   with Model.stream(feature=...): raw samples
+                         (N, s) through the session's FeatureStream (preprocessing/audio.py,
+                         norm='running') and its new rows through feed / finish; ``ended`` in
+                         samples.
 
     With ``beam`` (K27, beam_config): the device beam search resumed chunk by chunk
     (ops.ctc_beam_stream).  feed() returns per stream the labels NEWLY COMMITTED -- the growth
@@ -194,8 +198,14 @@ class StreamSession(object):
     The absolute positional table is taken as long as the stream has grown (ops.posenc_get, in
     powers of two from 1024 rows): a stream has no length to size it by."""
 
-    def __init__(self, model, n_streams=1, step=None, beam=None):
+    def __init__(self, model, n_streams=1, step=None, beam=None, feature=None):
         self.beam = beam_config(model, beam)
+        self.audio = None           # the FeatureStream of feed_audio (Model.stream(feature=))
+        if feature is not None:
+            if feature.num_feats != model.num_features:
+                raise ValueError('feature: %s gives %s columns, the model takes %d'
+                                 % (feature, feature.num_feats, model.num_features))
+            self.audio = feature.stream(n_streams)
         self.step, self.enc0, front = check(model, step, self.beam)
         self.model, self.N = model, int(n_streams)
         # the decoder the session was made under: a later change of model.decoder (another
@@ -245,6 +255,35 @@ class StreamSession(object):
         self._committed = [0] * self.N          # labels of the stable prefix already returned
         self._hyp = [([], 0.0) for _ in range(self.N)]
         self._stable = [0] * self.N
+        if self.audio is not None:
+            self.audio.reset()
+
+    # ------------------------------------------------------------------ raw audio (K30)
+    def _audio(self):
+        if self.audio is None:
+            raise RuntimeError('this session takes features: make it with '
+                               'Model.stream(..., feature=<a norm=\'running\' extractor>) to '
+                               'feed raw audio')
+        return self.audio
+
+    def feed_audio(self, samples, ended=None):
+        """samples (N, s): s new samples of every stream; ended: None, or per stream None / its
+        total length in SAMPLES.  The front-end's new rows (FeatureStream.feed) go through
+        feed(): the same kind of result."""
+        fs = self._audio()
+        fs._set_ended(ended)
+        known = [None if e is None else fs.frames_of(e) for e in fs._ends]
+        return self.feed(fs.feed(samples), ended=known)
+
+    def finish_audio(self):
+        """Ends every stream at the samples fed, then finish()."""
+        fs = self._audio()
+        rows = fs.finish()
+        out = self.feed(rows, ended=[fs.frames_of(e) for e in fs._ends])
+        rest = self.finish()
+        if self.beam is not None or self.decoder is not None:
+            return [a + b for a, b in zip(out, rest)]
+        return np.concatenate([out, rest], 1)
 
     def _set_ended(self, ended):
         if ended is None:

@@ -1780,6 +1780,52 @@ def frontend_features(cfg, audio, offsets, lengths, host_lengths, n_pad, tables,
     return out, frames
 
 
+class FrontendStreamState(object):
+    """What asr_frontend_stream carries from call to call for ``n_streams`` streams: the device
+    state (carry, base-row ring, running statistics, tables) and the host's counts."""
+
+    def __init__(self, cfg, n_streams, tables, device):
+        lib = L.load()
+        self.cfg, self.n_streams, self.tables = cfg, int(n_streams), tables
+        nbytes = lib.asr_frontend_stream_state_bytes(C.byref(cfg), self.n_streams)
+        if nbytes == 0:
+            raise ValueError('frontend stream: n_streams %d' % self.n_streams)
+        self.state = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.host = (C.c_longlong * lib.asr_frontend_stream_host_ints(self.n_streams))()
+        self.reset()
+
+    def reset(self):
+        L.check(L.load().asr_frontend_stream_reset(
+            C.byref(self.cfg), _ptr(self.state), C.cast(self.host, C.c_void_p), self.n_streams,
+            _ptr(self.tables['mel']), _ptr(self.tables['mel_range']), _stream()),
+            'asr_frontend_stream_reset')
+
+
+def frontend_stream(st, audio, ended, ended_host, n_pad, rows):
+    """One call of asr_frontend_stream.  st: FrontendStreamState; audio (n_streams, s) float32
+    CUDA, s >= 0; ended: int32 CUDA (n_streams,) of -1 / total lengths with its host mirror
+    ended_host (a list), or both None; rows: the kept rows the call emits (FrameSchedule).
+    Returns (out (rows, n_pad, F) float32, first kept row, one past the last)."""
+    lib = L.load()
+    cfg, N = st.cfg, st.n_streams
+    _check_f32(audio)
+    assert audio.dim() == 2 and audio.shape[0] == N
+    s = int(audio.shape[1])
+    f_out = lib.asr_frontend_num_feats(C.byref(cfg))
+    nbytes = lib.asr_frontend_stream_workspace_bytes(C.byref(cfg), N, s)
+    ws = WS.get('frontend', nbytes, audio.device)
+    out = torch.empty((int(rows), int(n_pad), f_out), dtype=torch.float32, device=audio.device)
+    eh = None if ended_host is None else (C.c_int * N)(*[int(e) for e in ended_host])
+    lo, hi = C.c_int(0), C.c_int(0)
+    t = st.tables
+    L.check(lib.asr_frontend_stream(
+        C.byref(cfg), _ptr(st.state), C.cast(st.host, C.c_void_p),
+        _ptr(audio) if s else None, s, _ptr(ended), eh, N, int(n_pad), _ptr(t['window']),
+        _ptr(t['mel']), _ptr(t['mel_range']), _ptr(t.get('dct')), _ptr(out) if rows else None,
+        int(rows), C.byref(lo), C.byref(hi), _ptr(ws), nbytes, _stream()), 'asr_frontend_stream')
+    return out, lo.value, hi.value
+
+
 def axpby(a, x, b, y, out=None):
     """out = a * x + b * y over contiguous float32 CUDA tensors of equal size (the residual
     merge of brsmv1 and its gradient); out defaults to a new tensor."""

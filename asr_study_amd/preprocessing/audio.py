@@ -34,10 +34,22 @@ class Feature(object):
     # Arguments
         fs: sampling frequency; files are resampled to it
         eps, stride, num_context, mean_norm, var_norm: as in the reference
+        norm: 'utterance' (the reference: mean and standard deviation of the whole
+            utterance) or 'running' (causal: those of the kept frames up to and including
+            the current one, Welford's recursion) -- what a model that is to
+            run on a live signal (``stream``) is trained on.  Not with num_context > 0.
     """
 
+    NORMS = ('utterance', 'running')
+
     def __init__(self, fs=16e3, eps=1e-8, stride=1, num_context=0,
-                 mean_norm=True, var_norm=True, device=None):
+                 mean_norm=True, var_norm=True, norm='utterance', device=None):
+        if norm not in self.NORMS:
+            raise ValueError("norm must be 'utterance' or 'running', got %r" % (norm,))
+        if norm == 'running' and int(num_context) > 0:
+            raise ValueError("norm='running' does not take num_context > 0: stacking the "
+                             "right context is a look-ahead of its own")
+        self.norm = norm
         self.fs = fs
         self.eps = eps
         self.mean_norm = mean_norm
@@ -92,12 +104,172 @@ class Feature(object):
             data = resample_poly(data, fr.numerator, fr.denominator)
         return data
 
+    def stream(self, n_streams=1):
+        """A FeatureStream: this extractor resumed across chunks of raw audio."""
+        raise NotImplementedError("%s has no streaming form" % type(self).__name__)
+
     def __str__(self):
         raise NotImplementedError("__str__ must be overrided")
 
     @property
     def num_feats(self):
         return self._num_feats
+
+
+class FrameSchedule(object):
+    """Which frames of a stream exist and are final after how many samples: plain integers, no
+    device (asr_frontend_stream does the same arithmetic on the host).
+
+    After S samples a stream that has not ended has ``complete(S)`` whole frames; its frame f is
+    final once f + la < complete(S), la the frames the deltas look ahead.  A stream whose length
+    n has been reached has all ``total(n)`` frames (the last one zero-padded), all final.  Of the
+    final frames every stride-th is kept."""
+
+    def __init__(self, frame_len, frame_step, la=0, stride=1):
+        self.frame_len, self.frame_step = int(frame_len), int(frame_step)
+        self.la, self.stride = int(la), max(1, int(stride))
+
+    def complete(self, samples):
+        if samples < self.frame_len:
+            return 0
+        return 1 + (samples - self.frame_len) // self.frame_step
+
+    def total(self, samples):
+        """Frames of a finished stream of ``samples`` samples (asr_frontend_num_frames)."""
+        if samples <= self.frame_len:
+            return 1
+        return 1 + -(-(samples - self.frame_len) // self.frame_step)
+
+    def final(self, samples, ended=None):
+        """Final frames after ``samples`` samples; ended: None or the stream's length."""
+        if ended is not None and ended <= samples:
+            return self.total(ended)
+        return max(0, self.complete(samples) - self.la)
+
+    def kept(self, frames):
+        return -(-int(frames) // self.stride)
+
+    def rows(self, samples, ended=None):
+        """Kept rows a stream has emitted after ``samples`` samples."""
+        return self.kept(self.final(samples, ended))
+
+    def window(self, samples, ends):
+        """Streams in lock-step (ends: per stream None or its length): the frames [0, window)
+        have been emitted for every stream -- up to what is final for the streams still running,
+        up to the longest stream's last frame once all have ended."""
+        if any(e is None or e > samples for e in ends):
+            return max(0, self.complete(samples) - self.la)
+        return max(self.total(e) for e in ends)
+
+
+class FeatureStream(object):
+    """A feature extractor resumed across chunks of raw audio (Feature.stream): n_streams
+    streams that advance in lock-step, every feed the same number of new samples for each.
+
+    feed(samples, ended=None)  samples (N, s) float, host or device, s >= 0.  ended: None, or N
+                               entries, each None or the stream's total length in samples (may be
+                               given ahead; samples past it are ignored).  Returns the new rows,
+                               a device tensor (N, t, F): the kept frames that became final,
+                               zero rows where a stream has ended before -- what
+                               StreamSession.feed takes.
+    finish()                   ends every stream that has not ended at samples_in; the rest.
+                               Refused (ValueError) while a length given ahead is not reached.
+    reset()                    another set of streams.
+    samples_in, frames_out, lookahead_frames (la = 2 d + 2 dd).
+
+    The rows of a stream, concatenated up to ``frames_of(its length)``, are bit for bit the rows
+    of the batch call on the whole signal (csrc/frontend.hip, asr_frontend_stream)."""
+
+    def __init__(self, feature, n_streams=1):
+        if getattr(feature, 'norm', 'utterance') != 'running':
+            raise ValueError("a feature stream needs norm='running': whole-utterance statistics "
+                             "(norm='utterance') need the end of the utterance before the first "
+                             "frame can be normalised")
+        if feature.KIND is None:
+            raise NotImplementedError("FBank is a base class; use MFCC or LogFbank")
+        self.N = int(n_streams)
+        if self.N < 1:
+            raise ValueError('n_streams %d' % self.N)
+        if feature._tables is None:
+            feature._build_tables()
+        self.feature = feature
+        self.cfg, self.tables = feature._tables
+        d = bool(self.cfg.d)
+        self.lookahead_frames = 2 * d + 2 * bool(d and self.cfg.dd)
+        self.schedule = FrameSchedule(self.cfg.frame_len, self.cfg.frame_step,
+                                      self.lookahead_frames, self.cfg.stride)
+        self.n_pad = ops.pad16(self.N)
+        self._state = ops.FrontendStreamState(self.cfg, self.N, self.tables, feature.device)
+        self._reset_host()
+
+    def _reset_host(self):
+        self.samples_in = self.frames_out = 0
+        self._ends = [None] * self.N
+        self._passed = [-1] * self.N        # what the library has been told
+        self._ended_dev = None
+        self._finished = False
+
+    def reset(self):
+        self._state.reset()
+        self._reset_host()
+
+    def frames_of(self, samples):
+        """Rows of a finished stream of ``samples`` samples."""
+        return self.schedule.kept(self.schedule.total(int(samples)))
+
+    def _set_ended(self, ended):
+        if ended is None:
+            return
+        if len(ended) != self.N:
+            raise ValueError('ended: %d entries for %d streams' % (len(ended), self.N))
+        for n, e in enumerate(ended):
+            if e is None or e == self._ends[n]:
+                continue
+            if self._ends[n] is not None:
+                raise ValueError('stream %d: its length was given as %d before'
+                                 % (n, self._ends[n]))
+            if int(e) < max(2, self.samples_in):
+                raise ValueError('stream %d: the length %d lies before the %d samples already '
+                                 'fed as samples of the stream (or is < 2)'
+                                 % (n, int(e), self.samples_in))
+            self._ends[n] = int(e)
+
+    def feed(self, samples, ended=None):
+        if self._finished:
+            raise RuntimeError('feed after finish(): reset() starts another stream')
+        dev = self.feature.device
+        if not torch.is_tensor(samples):
+            samples = torch.as_tensor(np.asarray(samples, np.float32))
+        if samples.dim() != 2 or samples.shape[0] != self.N:
+            raise ValueError('feed: samples is (%d streams, samples), got %s'
+                             % (self.N, tuple(samples.shape)))
+        self._set_ended(ended)
+        x = samples.to(dev, dtype=torch.float32).contiguous()
+        after = self.samples_in + int(x.shape[1])
+        passed = [e if e is not None and e <= after else -1 for e in self._ends]
+        if passed != self._passed:
+            self._ended_dev = torch.tensor(passed, dtype=torch.int32, device=dev)
+        has = self._ended_dev is not None
+        rows = self.schedule.kept(self.schedule.window(after, self._ends)) - self.frames_out
+        rows = max(rows, 0)
+        out, lo, hi = ops.frontend_stream(self._state, x, self._ended_dev if has else None,
+                                          passed if has else None, self.n_pad, rows)
+        assert (lo, hi) == (self.frames_out, self.frames_out + rows), (lo, hi, rows)
+        self._passed = passed
+        self.samples_in, self.frames_out = after, hi
+        return out[:, :self.N].permute(1, 0, 2).contiguous()
+
+    def finish(self):
+        if self._finished:
+            raise RuntimeError('finish() twice: reset() starts another stream')
+        for n, e in enumerate(self._ends):
+            if e is not None and e > self.samples_in:
+                raise ValueError('finish(): stream %d was given the length %d, and only %d '
+                                 'samples have been fed' % (n, e, self.samples_in))
+        ended = [self.samples_in if e is None else None for e in self._ends]
+        out = self.feed(torch.zeros((self.N, 0)), ended=ended)
+        self._finished = True
+        return out
 
 
 class FBank(Feature):
@@ -164,6 +336,7 @@ class FBank(Feature):
         cfg.num_context = int(self.num_context)
         cfg.mean_norm = int(bool(self.mean_norm))
         cfg.var_norm = int(bool(self.var_norm))
+        cfg.norm_mode = self.NORMS.index(self.norm)
         cfg.pre_emph = float(self.pre_emph)
         cfg.eps = float(self.eps)
         return cfg
@@ -222,6 +395,9 @@ class FBank(Feature):
             n_pad = ops.pad16(len(host_lengths))
         return ops.frontend_features(cfg, audio, offsets, lengths, host_lengths, n_pad,
                                      tables, t_out)
+
+    def stream(self, n_streams=1):
+        return FeatureStream(self, n_streams)
 
     def __str__(self):
         return "fbank"

@@ -63,7 +63,11 @@ const char* asr_last_error(void);
  * asr_dwconv1d_stream_fwd and asr_ctc_greedy_stream (K26): additions only again;
  * asr_ctc_beam_stream, asr_ctc_beam_lm_stream and their two size functions (K27): likewise;
  * asr_gru_uni_args and the asr_gru_uni_* entry points (K28): additions only;
- * asr_lstm_uni_args and the asr_lstm_uni_* entry points (K29): additions only. */
+ * asr_lstm_uni_args and the asr_lstm_uni_* entry points (K29): additions only;
+ * asr_frontend_cfg.norm_mode (the former `reserved`, same layout) and the
+ * asr_frontend_stream* entry points (K30): additions only -- but the field is
+ * now READ: a caller that left `reserved` uninitialised must set it to 0,
+ * any value other than 0 or 1 is ASR_ERR_INVALID. */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -89,7 +93,8 @@ typedef struct asr_frontend_cfg {
   int stride;        /* keep every stride-th frame                           */
   int num_context;   /* +-context frame stacking (zero rows off the edges)   */
   int mean_norm, var_norm;
-  int reserved;      /* (keeps the doubles 8-byte aligned)                   */
+  int norm_mode;     /* 0 = whole-utterance statistics, 1 = running (causal):  */
+                     /* Welford's recursion over the kept frames, see below    */
   double pre_emph;   /* 0.97 -- float64: the per-frame chain runs in float64 */
   double eps;        /* 1e-8                                                 */
 } asr_frontend_cfg;
@@ -119,6 +124,65 @@ int asr_frontend_features(const asr_frontend_cfg* cfg, const float* audio,
                           int t_out,
                           int* out_frames, void* workspace, size_t ws_bytes,
                           asr_stream_t stream);
+
+/* K30  Running normalisation and the resumed front-end.
+ *
+ * cfg->norm_mode = 1 (num_context must be 0): per utterance and output column,
+ * over the rows kept after feats[::stride], kept frame t = 0, 1, ... with value
+ * x_t (float64):  n = t + 1;  d = x_t - mean;  mean += d / n;
+ * M2 += d * (x_t - mean);  sd = sqrt(M2 / n);
+ * out_t = (x_t - (mean_norm ? mean : 0)) / (var_norm ? sd + eps : 1).
+ * asr_frontend_features takes it as it takes norm_mode = 0.
+ *
+ * asr_frontend_stream is the same computation resumed across calls that each
+ * bring n_samples new samples of every one of n_streams streams (lock-step):
+ * the rows it emits, concatenated, are bit for bit the rows of
+ * asr_frontend_features with norm_mode = 1 on the whole signals.  norm_mode = 0
+ * is refused (ASR_ERR_INVALID): whole-utterance statistics need the end of the
+ * utterance.  frame_step <= frame_len.
+ *   state       device memory of asr_frontend_stream_state_bytes: per stream the
+ *               sample in front of the carry, the carried samples that do not
+ *               complete a frame yet (< frame_len), the counts of samples seen,
+ *               frames computed and rows emitted, the ring of the last
+ *               2 la + 1 base-feature rows (la = 2 d + 2 dd, what the deltas
+ *               look ahead), mean and M2 of every output column; and the FFT
+ *               twiddles and the transposed mel table, built by the reset.
+ *   host_state  asr_frontend_stream_host_ints(n_streams) int64 of the caller's:
+ *               the same counts on the host.  Which frames a call emits is
+ *               integer arithmetic on them; no call reads the device.
+ *   audio       (n_streams, n_samples) float32, device.  n_samples may be 0.
+ *   ended_total / host_ended_total   device and host int32 per stream (both or
+ *               neither): -1, or the stream's total length in samples from the
+ *               call on whose samples reach it (samples_fed <= total <=
+ *               samples_fed + n_samples at that call; >= 2), in every later
+ *               call too.  Samples past it are ignored.
+ * After S samples a stream that has not ended has F(S) = 0 if S < frame_len else
+ * 1 + (S - frame_len) / frame_step complete frames, and its frame f is final once
+ * f + la < F(S); all asr_frontend_num_frames(total) frames of an ended stream are
+ * final (tail zero-padded, deltas edge-replicated, as the batch call).  A call
+ * emits, for every stream, the kept frames of the window [lo, hi) that became
+ * final for the streams still running (hi = the largest frame count once all
+ * have ended): out[(t, stream, col)], t < *frames_hi - *frames_lo <= t_cap, the
+ * kept rows *frames_lo .. *frames_hi - 1 of every stream (host ints; zero rows
+ * past a stream's end; batch-padding rows zero).  Launches: gather, frames,
+ * finalize, commit (+ the padding rows); a call that completes no frame and
+ * emits none runs gather and commit only. */
+size_t asr_frontend_stream_state_bytes(const asr_frontend_cfg* cfg, int n_streams);
+int asr_frontend_stream_host_ints(int n_streams);
+size_t asr_frontend_stream_workspace_bytes(const asr_frontend_cfg* cfg, int n_streams,
+                                           int n_samples);
+/* Zero-fills the state, builds its tables (mel, mel_range as above). */
+int asr_frontend_stream_reset(const asr_frontend_cfg* cfg, void* state,
+                              long long* host_state, int n_streams,
+                              const double* mel, const int* mel_range,
+                              asr_stream_t stream);
+int asr_frontend_stream(const asr_frontend_cfg* cfg, void* state, long long* host_state,
+                        const float* audio, int n_samples, const int* ended_total,
+                        const int* host_ended_total, int n_streams, int n_pad,
+                        const double* window, const double* mel, const int* mel_range,
+                        const double* dct, float* out, int t_cap, int* frames_lo,
+                        int* frames_hi, void* workspace, size_t ws_bytes,
+                        asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* K4/K6  fp32 MFMA GEMM.  Replaces K.dot(x*B_W, W) (core/layers.py:439,     */

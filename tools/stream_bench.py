@@ -8,6 +8,8 @@ Model.forward over a trailing slab of left + chunk strided frames for every chun
     python tools/stream_bench.py --beam_call_cost [--beam_width 8 100] [--streams 1 64]
     python tools/stream_bench.py --model ds2_uni [--streams 1 16]
     python tools/stream_bench.py --model brsmv1_uni [--streams 1 16]
+    python tools/stream_bench.py --audio [--model ...] [--streams 1 64]
+    python tools/stream_bench.py --frontend_batch
 
 Model: conformer(positions='relative', context=(16, 64, 0), causal_conv=True) at the factory's
 default sizes (80 features, the two-convolution front-end, d_model 256, 4 heads, 6 blocks), 10 ms
@@ -43,6 +45,13 @@ frame, no save); device events around EACH call, so a figure includes the enqueu
 is an upper bound of the kernel's time; medians over the calls of frames 512 .. 1023.  The
 stable-prefix walk is taken from the kernel's own counter (BeamStreamState.counters: walk_s) over
 the same calls.
+
+``--audio`` (K30) adds the front-end to the step: variant 'stream+audio' is
+session.feed_audio() of the step's raw samples (device resident, 160 per input frame) on a session
+made with Model.stream(feature=...) -- LogFbank(num_filt=80, norm='running'), or
+MFCC(norm='running') for brsmv1_uni -- and 'front-end' the FeatureStream.feed of the same samples
+alone.  ``--frontend_batch`` times the batch front-end call (64 utterances of 10 s, log-mel 80:
+cfg3's shape) with norm='utterance' and with norm='running', alternating.
 
 Both are warmed up, then timed with device events over K back-to-back calls (one event pair
 around the K calls, ending in a synchronise); the two ALTERNATE within a round, R rounds in one
@@ -135,6 +144,34 @@ def beam_call_cost(widths, streams, T=1024, C=28, max_frames=3000):
     return results
 
 
+def frontend_batch(rounds, reps, n_utt=64, seconds=10.0):
+    """The batch front-end call at cfg3's shape under both normalisations."""
+    from asr_study_amd.preprocessing import audio
+    rs = np.random.RandomState(0)
+    n = int(seconds * 16000)
+    lens = [n] * n_utt
+    flat = torch.from_numpy(rs.randn(n_utt * n).astype(np.float32)).cuda()
+    offs = torch.arange(n_utt, dtype=torch.int32, device='cuda:0') * n
+    dlen = torch.full((n_utt,), n, dtype=torch.int32, device='cuda:0')
+    feats = {k: audio.LogFbank(num_filt=80, norm=k) for k in ('utterance', 'running')}
+    calls = {k: (lambda f=f: f.batch_device(flat, offs, dlen, lens)) for k, f in feats.items()}
+    for fn in calls.values():
+        for _ in range(3):
+            fn()
+    ms = {k: [] for k in calls}
+    for _ in range(rounds):
+        for k, fn in calls.items():
+            ms[k].append(timed(fn, reps))
+    results = []
+    for k, v in ms.items():
+        med = float(np.median(v))
+        results.append(dict(norm=k, n_utt=n_utt, seconds=seconds, ms=med,
+                            spread=float((max(v) - min(v)) / med)))
+        print('front-end batch call, %d x %.0f s, log-mel 80, norm=%-9s %8.3f ms  (spread %.3f)'
+              % (n_utt, seconds, k, med, results[-1]['spread']))
+    return results
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--rounds', type=int, default=7)
@@ -145,9 +182,17 @@ def main(argv=None):
     ap.add_argument('--beam_width', type=int, nargs='+', default=[100])
     ap.add_argument('--beam_call_cost', action='store_true')
     ap.add_argument('--model', default='conformer', choices=['conformer', 'ds2_uni', 'brsmv1_uni'])
+    ap.add_argument('--audio', action='store_true')
+    ap.add_argument('--frontend_batch', action='store_true')
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit('stream_bench: no GPU')
+    if args.frontend_batch:
+        results = frontend_batch(args.rounds, args.reps)
+        if args.json:
+            with open(args.json, 'w') as f:
+                json.dump(results, f, indent=1)
+        return results
     if args.beam_call_cost:
         results = beam_call_cost(args.beam_width, args.streams)
         if args.json:
@@ -182,6 +227,16 @@ def main(argv=None):
             frames = (WARMUP + args.rounds * args.reps) * ss.step    # every feed of this run
             variants['stream+beam%d' % width] = decoding(
                 model, n, x, dict(beam_width=width, max_frames=max(3000, frames)))
+        if args.audio:
+            from asr_study_amd.preprocessing import audio
+            feat = (audio.MFCC(norm='running') if args.model == 'brsmv1_uni'
+                    else audio.LogFbank(num_filt=80, norm='running'))
+            sa = model.stream(n_streams=n, feature=feat)
+            wave = torch.tensor(rs.randn(n, per_step * 160).astype(np.float32),
+                                device=model.device)
+            fs = feat.stream(n)
+            variants['stream+audio'] = lambda: sa.feed_audio(wave)
+            variants['front-end'] = lambda: fs.feed(wave)
         if args.model == 'conformer':
             variants.update({
                 're-run': lambda: model.forward(slab, training=False, need_grad=False, n_valid=n,
