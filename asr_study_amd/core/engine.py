@@ -33,7 +33,7 @@ from .. import ops
 from . import optimizers as _opt
 from . import params as P
 from .params import _pad4
-from .stages import KINDS, Pass
+from .stages import KINDS, Pass, _nd
 
 
 # where a Model lives when the factory is given no ``device`` (host-only tests build on 'cpu':
@@ -270,7 +270,7 @@ class Model(object):
                 prev = st
         if (prev is not None and hasattr(prev, 'Hp') and prev.Hp != prev.H
                 and getattr(prev, 'merge', 'concat') == 'concat'
-                and getattr(prev, 'directions', 2) == 2):
+                and _nd(prev) == 2):
             idx = np.concatenate([np.arange(prev.H), prev.Hp + np.arange(prev.H)])
         else:
             idx = np.arange(s.f_in)
@@ -384,7 +384,7 @@ class Model(object):
         planes, the sizing by the widest recurrence, the pipe and side streams, compact BPTT).  A
         'bilstm' stage with ``directions`` = 1 is the unidirectional variant (core/stages.py,
         csrc/lstm_uni.hip): it takes none of them."""
-        return s.kind == 'bilstm' and getattr(s, 'directions', 2) == 2
+        return s.kind == 'bilstm' and _nd(s) == 2
 
     @staticmethod
     def _y_bounded(s):

@@ -257,26 +257,29 @@ def birnn(s, alloc, rows):
     return out
 
 
-def bigru(s, alloc, rows):
+def bigru(s, alloc, rows, layers=('forward_gru', 'backward_gru')):
     """Bidirectional(GRU) (csrc/gru.hip): W (in, 2, 3Hp), U (2, Hp, 3Hp), b (2, 3Hp), column
-    blocks z, r, h.  batch_norm (K18): no b -- gamma, beta (2, 3Hp) each instead (beta is what
-    the kernels read as the bias), the running moments (mean | variance) x (2, 3Hp) and the
+    blocks z, r, h.  layers = ('gru',): a bare, unidirectional GRU (K28), the same blocks without
+    the direction axis.  batch_norm (K18): no b -- gamma, beta (2, 3Hp) each instead (beta is
+    what the kernels read as the bias), the running moments (mean | variance) x (2, 3Hp) and the
     moments block kept where the bn stage keeps its own."""
-    H, Hp, F = s.H, s.Hp, len(rows)
+    H, Hp, F, nd = s.H, s.Hp, len(rows), len(layers)
     G, pad = 3 * Hp, ('blocks', H, Hp, 3)
-    s.oW, s.oU = alloc.take(s.f_in_pad * 2 * G), alloc.take(2 * Hp * G)
+    ax = (2,) if nd == 2 else ()            # the direction axis of a block ...
+    s.oW, s.oU = alloc.take(s.f_in_pad * nd * G), alloc.take(nd * Hp * G)
     if s.bn:
         s.ob, s.og, s.obeta = None, alloc.take(2 * G), alloc.take(2 * G)
         s.orun, ovar = alloc.take(2 * G, 'running'), alloc.take(2 * G, 'running')
         s.omom = alloc.take(ops.bn_moments_len(2 * G), 'moments')
     else:
-        s.ob = alloc.take(2 * G)
+        s.ob = alloc.take(nd * G)
     out = []
-    for d, layer in enumerate(('forward_gru', 'backward_gru')):
-        out += [Tensor(layer, 'W', (F, 3 * H), s.oW, (s.f_in_pad, 2, G), (rows, d), pad, s.l2_W,
-                       _glorot(F, 3 * H)),
-                Tensor(layer, 'U', (H, 3 * H), s.oU, (2, Hp, G), (d, slice(0, H)), pad, s.l2_U,
-                       ('orthogonal', 1.1))]
+    for d, layer in enumerate(layers):
+        at = (d,) if nd == 2 else ()        # ... and a direction's place on it
+        out += [Tensor(layer, 'W', (F, 3 * H), s.oW, (s.f_in_pad,) + ax + (G,), (rows,) + at, pad,
+                       s.l2_W, _glorot(F, 3 * H)),
+                Tensor(layer, 'U', (H, 3 * H), s.oU, ax + (Hp, G), at + (slice(0, H),), pad,
+                       s.l2_U, ('orthogonal', 1.1))]
         if s.bn:        # (running_std holds the variance, as in keras.layers.BatchNormalization)
             out += [Tensor(layer, 'gamma', (3 * H,), s.og, (2, G), (d,), pad, init=ONES),
                     Tensor(layer, 'beta', (3 * H,), s.obeta, (2, G), (d,), pad),
@@ -285,21 +288,8 @@ def bigru(s, alloc, rows):
                     Tensor(layer, 'running_std', (3 * H,), ovar, (2, G), (d,), pad, init=ONES,
                            buf='running', fill=1.0)]
         else:
-            out.append(Tensor(layer, 'b', (3 * H,), s.ob, (2, G), (d,), pad))
+            out.append(Tensor(layer, 'b', (3 * H,), s.ob, ax + (G,), at, pad))
     return out
-
-
-def gru_uni(s, alloc, rows):
-    """A bare, unidirectional GRU (csrc/gru.hip, K28): W (in, 3Hp), U (Hp, 3Hp), b (3Hp), column
-    blocks z, r, h; the initialisers and l2 of one direction of ``bigru``."""
-    H, Hp, F = s.H, s.Hp, len(rows)
-    G, pad = 3 * Hp, ('blocks', H, Hp, 3)
-    s.oW, s.oU, s.ob = alloc.take(s.f_in_pad * G), alloc.take(Hp * G), alloc.take(G)
-    return [Tensor('gru', 'W', (F, 3 * H), s.oW, (s.f_in_pad, G), (rows,), pad, s.l2_W,
-                   _glorot(F, 3 * H)),
-            Tensor('gru', 'U', (H, 3 * H), s.oU, (Hp, G), (slice(0, H),), pad, s.l2_U,
-                   ('orthogonal', 1.1)),
-            Tensor('gru', 'b', (3 * H,), s.ob, (G,), (), pad)]
 
 
 def birhn(s, alloc, rows):

@@ -25,7 +25,10 @@ workspaces carry timeout words of their own).  Whether a stage is the first trai
 
 A VARIANT of a kind is a stage of that kind told by an attribute only it carries (``relative`` and
 ``window`` on 'mha'; ``directions`` = 1 on 'bigru' and on 'bilstm': a bare, unidirectional GRU
-or LSTM, whose three handlers the kind's own hand over to).  A variant may stream where its kind does not:
+or LSTM).  The direction count of a recurrent stage is ``_nd(s)``, the one reader of that
+attribute: the 'bigru' handlers and the GEMM helpers of the recurrent kinds take it as a number
+and serve both forms, the 'bilstm' handlers hand a one-direction stage to ``_lstm_uni_*``, which
+use the same helpers.  A variant may stream where its kind does not:
 ``STREAM_VARIANTS`` (at the end of this module) maps a kind to (is this stage the variant?, its
 step handler ``(m, s, si, a, ss)``), and ``stream_variant(s)`` is what ``stream_check`` and
 ``StreamSession._encoder`` consult FIRST, before ``Kind.stream`` -- which stays None for 'bigru'.
@@ -690,31 +693,66 @@ def stream_check(m, s, si):
     return None
 
 
-# --------------------------------------------------------------------------- bilstm
-def _bilstm_build(m, s, st, width):
-    if st.get('directions', 2) == 1:
-        return _lstm_uni_build(m, s, st, width)
+# --------------------------------------------------------------------------- one or two directions
+def _nd(s):
+    """The directions of a recurrent stage ``s`` (or of the spec entry one is being built from):
+    2, or 1 for a bare GRU / LSTM, the one-direction variant of 'bigru' / 'bilstm'.  The attribute
+    ``directions`` is set on a variant stage only, and read here only."""
+    return s.get('directions', 2) if isinstance(s, dict) else getattr(s, 'directions', 2)
+
+
+def _rec_fields(s, st, merge=True):
+    """What the recurrent kinds share; merge: Bidirectional(SimpleRNN | GRU | RHN) (csrc/rnn.hip,
+    gru.hip, rhn.hip), whose two outputs are concatenated or summed."""
     s.H = st['H']
     s.Hp = _pad4(s.H)
+    if merge:
+        s.merge = st.get('merge_mode', 'concat')
+    s.act = st.get('activation') or 'tanh'      # (LSTM: core/layers.py:452, :463)
     s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
     s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
+
+
+def _uni_stream(keys):
+    """The step handler of a one-direction stage whose state is one (n_pad, Hp) vector per key
+    ('h', and 'c' for the LSTM): the stage's own forward handler on the new frames, from the
+    state into the other buffer of each pair, then the swaps.  The pairs are zero-filled when
+    created or reset (StreamSession.reset); there is no ring."""
+    def step(m, s, si, a, ss):
+        st = ss.state.setdefault(si, {})
+        for k in keys:
+            if k not in st:
+                st[k] = [ss.zeros((a.shape[1], s.Hp)), ss.zeros((a.shape[1], s.Hp))]
+        # h0 / h_last (and c0 / c_last) of the recurrence: the first buffer of a pair, the second
+        carry = {k + sfx: t for k in keys for sfx, t in zip(('0', '_last'), st[k])}
+        out = KINDS[s.kind].forward(m, s, si, a, {}, ss._pass(), carry)
+        for k in keys:
+            st[k].reverse()
+        return out
+    return step
+
+
+# --------------------------------------------------------------------------- bilstm
+def _bilstm_build(m, s, st, width):
+    if _nd(st) == 1:
+        return _lstm_uni_build(m, s, st, width)
+    _rec_fields(s, st, merge=False)
     s.mi = st.get('mi')                     # [alpha, beta1, beta2] inits or None
     s.ln = st.get('layer_norm')             # [gain_init, bias_init] or None
     s.zoneout_c = float(st.get('zoneout_c') or 0.0)
     s.zoneout_h = float(st.get('zoneout_h') or 0.0)
-    s.act = st.get('activation') or 'tanh'      # core/layers.py:452, :463
     s.tensors = P.bilstm(s, m._alloc, m._real_rows(s))
     return 2 * s.H, 2 * s.Hp
 
 
-def _bilstm_forward(m, s, si, a, rec, fp):
-    if getattr(s, 'directions', 2) == 1:
-        return _lstm_uni_forward(m, s, si, a, rec, fp)
+def _bilstm_forward(m, s, si, a, rec, fp, carry=None):
+    if _nd(s) == 1:
+        return _lstm_uni_forward(m, s, si, a, rec, fp, carry)
     return m._bilstm_forward(s, si, a, rec, fp)
 
 
 def _bilstm_backward(m, s, si, rec, da, bp):
-    if getattr(s, 'directions', 2) == 1:
+    if _nd(s) == 1:
         return _lstm_uni_backward(m, s, si, rec, da, bp)
     return m._bilstm_backward(s, si, rec, da, bp)
 
@@ -722,50 +760,38 @@ def _bilstm_backward(m, s, si, rec, da, bp):
 # The unidirectional LSTM (K29, csrc/lstm_uni.hip): the one-direction variant of the kind, as the
 # unidirectional GRU is of 'bigru' (below).  None of the scheduled paths of the bidirectional
 # body (packed planes, pipe and side streams, compact BPTT) applies to it: engine.py asks
-# ``Model._is_bilstm`` (kind 'bilstm' AND two directions) wherever it decides one of them.  The
-# masks are direction 0's of the pair a 'bilstm' stage is drawn (same shapes, streams and step).
+# ``Model._is_bilstm`` (kind 'bilstm' AND two directions) wherever it decides one of them.  What
+# is here is the LSTM's own (the buffers, the recurrence, db); the GEMMs are the shared helpers'
+# (below) with one direction and G = 4 Hp.
 def _lstm_uni_build(m, s, st, width):
-    """``s.directions`` is set on such a stage only (read it with getattr(s, 'directions', 2));
-    mi / ln are None and the zoneouts 0, for whoever reads them off a 'bilstm' stage."""
+    """mi / ln are None and the zoneouts 0, for whoever reads them off a 'bilstm' stage."""
     for k in ('mi', 'layer_norm', 'zoneout_c', 'zoneout_h'):
         if st.get(k):
             raise NotImplementedError('a unidirectional LSTM stage has no %s: the kernels of '
                                       'csrc/lstm_uni.hip are the plain cell only' % k)
     s.directions = 1
-    s.H = st['H']
-    s.Hp = _pad4(s.H)
-    s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
-    s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
+    _rec_fields(s, st, merge=False)
     s.mi = s.ln = None
     s.zoneout_c = s.zoneout_h = 0.0
-    s.act = st.get('activation') or 'tanh'
     s.tensors = P.lstm_uni(s, m._alloc, m._real_rows(s))
     return s.H, s.Hp
 
 
-def _lstm_uni_zx(m, s, si, a, BW, n_pad):
-    """zx (T, n_pad, 4Hp) = (a (.) B_W) @ W + b: one GEMM."""
-    T, G = a.shape[0], 4 * s.Hp
-    zx = m._buf('uzx%d' % si, (T, n_pad, G))
-    scale = {} if BW is None else dict(a_scale=BW, a_scale_period=n_pad)
-    ops.gemm(a, m.params, zx, T * n_pad, G, s.f_in_pad, b_off=s.oW, bias=m._view(s.ob, G),
-             **scale)
-    return zx
-
-
-def _lstm_uni_forward(m, s, si, a, rec, fp):
+def _lstm_uni_forward(m, s, si, a, rec, fp, carry=None):
+    """zx (T, n_pad, 4Hp) = (a (.) B_W) @ W + b, then the recurrence: from the zero state, or
+    (streaming, _uni_stream) with the state arguments ``carry``."""
     a = a.contiguous()
     n_pad = fp.n_pad
     T, Hp = a.shape[0], s.Hp
     BW, BU = fp.stage_masks(si)[:2]
     rec['BW'], rec['BU'] = BW, BU
-    BW, BU = (None if BW is None else BW[0]), (None if BU is None else BU[0])
-    zx = _lstm_uni_zx(m, s, si, a, BW, n_pad)
+    zx = m._buf('uzx%d' % si, (T, n_pad, 4 * Hp))
+    _rec_proj(m, a, s, zx, 4 * Hp, BW, T * n_pad, n_pad, bias=m._view(s.ob, 4 * Hp), nd=1)
     h = m._buf('uh%d' % si, (T, n_pad, Hp))
     cell = m._buf('ucell%d' % si, (T, n_pad, Hp))
     gates = m._buf('ugates%d' % si, (T, n_pad, 4 * Hp))
     ops.lstm_uni_seq_fwd(zx, m._view(s.oU, Hp * 4 * Hp), h, cell, gates, T, n_pad, Hp, act=s.act,
-                         mask_u=BU)
+                         mask_u=None if BU is None else BU[0], **(carry or {}))
     rec.update(h=h, cell=cell, gates=gates)
     return h
 
@@ -774,56 +800,19 @@ def _lstm_uni_backward(m, s, si, rec, da, bp):
     """BPTT from the zero state, then dU = (h_prev (.) B_U)^T dz over the (T - 1) n_pad rows that
     have an h_prev, dW = (x (.) B_W)^T dz, db from the per-batch-tile sums, dx = B_W (.)
     (dz @ W^T).  Returns dx (or None)."""
-    split = bp.split
     T, n_pad = da.shape[0], da.shape[1]
-    rows, Hp = T * n_pad, s.Hp
-    G = 4 * Hp
-    BW, BU, h, a_in = rec['BW'], rec['BU'], rec['h'], rec['in'].contiguous()
-    BW, BU = (None if BW is None else BW[0]), (None if BU is None else BU[0])
+    Hp, G = s.Hp, 4 * s.Hp
+    BW, BU, h = rec['BW'], rec['BU'], rec['h']
+    BU = None if BU is None else BU[0]
     dz = m._buf('udz%d' % si, (T, n_pad, G))
     dbp = m._buf('udbp%d' % si, (n_pad // 16, G))
     zmx = m._buf('udzmax%d' % si, (1,))
     ops.lstm_uni_seq_bwd(da.contiguous(), m._view(s.oU, Hp * G), h, rec['cell'], rec['gates'], dz,
                          T, n_pad, Hp, act=s.act, mask_u=BU, db_part=dbp, dz_absmax=zmx)
     ops.colsum(dbp, n_pad // 16, G, G, m._gview(s.ob, G))
-    kk = (T - 1) * n_pad
-    if kk > 0:      # h_prev of frame t is h[t - 1]: 0 before frame 0
-        scale = {} if BU is None else dict(a_scale=BU, a_scale_period=n_pad)
-        ops.gemm(h, dz, m.grads, Hp, G, kk, trans_a=True, b_off=n_pad * G, c_off=s.oU,
-                 split_k=split, b_absmax=zmx, **scale)
-    else:
-        m._gview(s.oU, Hp * G).zero_()
-    scale = {} if BW is None else dict(a_scale=BW, a_scale_period=n_pad)
-    ops.gemm(a_in, dz, m.grads, s.f_in_pad, G, rows, trans_a=True, c_off=s.oW, split_k=split,
-             b_absmax=zmx, **scale)
-    if bp.first:
-        return None
-    dx = m._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-    scale = {} if BW is None else dict(c_scale=BW, c_scale_period=n_pad)
-    ops.gemm(dz, m.params, dx, rows, s.f_in_pad, G, trans_b=True, b_off=s.oW, a_absmax=zmx,
-             **scale)
-    return dx
-
-
-def _lstm_uni_stream(m, s, si, a, ss):
-    """The new frames of a unidirectional LSTM: the zx GEMM of the chunk, then the recurrence from
-    the stage's state into the other buffer of each pair, then the two swaps.  State: 'h' and 'c',
-    two (n_pad, Hp) buffers each, zero-filled when created or reset; no ring."""
-    a = a.contiguous()
-    Tq, n_pad, Hp = a.shape[0], a.shape[1], s.Hp
-    st = ss.state.setdefault(si, {})
-    if 'h' not in st:
-        st['h'] = [ss.zeros((n_pad, Hp)), ss.zeros((n_pad, Hp))]
-        st['c'] = [ss.zeros((n_pad, Hp)), ss.zeros((n_pad, Hp))]
-    zx = _lstm_uni_zx(m, s, si, a, None, n_pad)
-    h = m._buf('uh%d' % si, (Tq, n_pad, Hp))
-    cell = m._buf('ucell%d' % si, (Tq, n_pad, Hp))
-    gates = m._buf('ugates%d' % si, (Tq, n_pad, 4 * Hp))
-    ops.lstm_uni_seq_fwd(zx, m._view(s.oU, Hp * 4 * Hp), h, cell, gates, Tq, n_pad, Hp, act=s.act,
-                         h0=st['h'][0], c0=st['c'][0], h_last=st['h'][1], c_last=st['c'][1])
-    st['h'].reverse()
-    st['c'].reverse()
-    return h
+    _rec_du_prev(m, h, dz, s.oU, 0, G, G, T, n_pad, Hp, BU, bp.split, zmx, nd=1)
+    _rec_dw(m, rec['in'].contiguous(), dz, s, G, BW, T * n_pad, n_pad, bp.split, zmx, nd=1)
+    return _rec_dx(m, dz, s, si, G, BW, T, n_pad, zmx, bp.first, nd=1)
 
 
 def _mask_shape(s, n_pad):
@@ -831,18 +820,8 @@ def _mask_shape(s, n_pad):
 
 
 # --------------------------------------------------------------------------- SimpleRNN, GRU, RHN
-def _rec_fields(s, st):
-    """What Bidirectional(SimpleRNN | GRU | RHN) share (csrc/rnn.hip, gru.hip, rhn.hip)."""
-    s.H = st['H']
-    s.Hp = _pad4(s.H)
-    s.merge = st.get('merge_mode', 'concat')
-    s.act = st.get('activation') or 'tanh'
-    s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
-    s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
-
-
 def _rec_width(s):
-    return (2 * s.H, 2 * s.Hp) if s.merge == 'concat' else (s.H, s.Hp)
+    return (2 * s.H, 2 * s.Hp) if _nd(s) == 2 and s.merge == 'concat' else (s.H, s.Hp)
 
 
 def _birnn_build(m, s, st, width):
@@ -853,34 +832,24 @@ def _birnn_build(m, s, st, width):
 
 
 def _bigru_build(m, s, st, width):
-    if st.get('directions', 2) == 1:
-        return _gru_uni_build(m, s, st, width)
-    _rec_fields(s, st)
+    """Bidirectional(GRU), or a bare GRU (K28): the one-direction variant of the kind, which has
+    no merge and no batch normalisation of the projection."""
+    nd = _nd(st)
+    if nd == 1:
+        if st.get('batch_norm'):
+            raise NotImplementedError('a unidirectional GRU stage has no batch_norm: the '
+                                      'sequence-wise normalisation kernels take both directions '
+                                      'of a layer')
+        s.directions = 1
+    _rec_fields(s, st, merge=nd == 2)
     # batch_norm (K18, csrc/batchnorm.hip): sequence-wise BN of the input projection
     s.bn = bool(st.get('batch_norm', False))
     if s.bn:
         s.bn_eps = float(st.get('bn_epsilon', 1e-3))
         s.bn_momentum = float(st.get('bn_momentum', 0.99))
-    s.tensors = P.bigru(s, m._alloc, m._real_rows(s))
+    s.tensors = P.bigru(s, m._alloc, m._real_rows(s),
+                        ('forward_gru', 'backward_gru') if nd == 2 else ('gru',))
     return _rec_width(s)
-
-
-def _gru_uni_build(m, s, st, width):
-    """A bare GRU, the one-direction variant of the kind (K28): ``s.directions`` is set on such
-    a stage only (read it with getattr(s, 'directions', 2)); there is no merge and no batch
-    normalisation of the projection."""
-    if st.get('batch_norm'):
-        raise NotImplementedError('a unidirectional GRU stage has no batch_norm: the sequence-wise '
-                                  'normalisation kernels take both directions of a layer')
-    s.directions = 1
-    s.H = st['H']
-    s.Hp = _pad4(s.H)
-    s.act = st.get('activation') or 'tanh'
-    s.dropout_W, s.dropout_U = st.get('dropout_W', 0.0), st.get('dropout_U', 0.0)
-    s.l2_W, s.l2_U = st.get('l2_W', 0.0), st.get('l2_U', 0.0)
-    s.bn = False
-    s.tensors = P.gru_uni(s, m._alloc, m._real_rows(s))
-    return s.H, s.Hp
 
 
 def _birhn_build(m, s, st, width):
@@ -897,58 +866,60 @@ def _birhn_mask_shape(s, n_pad):
     return (2, s.depth, n_pad, s.Hp)
 
 
-# The GEMMs around a recurrence (SimpleRNN, GRU, RHN).  G is the gate width of one direction:
-# the rows of zx and of the gate gradient dg hold both directions, 2 G wide, and so do W's.
-def _rec_proj(m, a, s, zx, G, BW, rows, n_pad, bias=None):
-    """zx = (a (.) B_W[d]) @ W_d (+ b_d), both directions; bias (2 G) or None."""
+# The GEMMs around a recurrence (SimpleRNN, GRU, RHN, the one-direction GRU and LSTM).  G is the
+# gate width of one direction: the rows of zx and of the gate gradient dg hold the nd directions
+# of the stage, nd G wide, and so do W's.  A one-direction stage is handed the (2, n_pad, .) mask
+# pair of its kind like any other (same shapes, streams and step) and reads direction 0 of it.
+def _rec_proj(m, a, s, zx, G, BW, rows, n_pad, bias=None, nd=2):
+    """zx = (a (.) B_W[d]) @ W_d (+ b_d), every direction; bias (nd G) or None."""
     if BW is None:
-        ops.gemm(a, m.params, zx, rows, 2 * G, s.f_in_pad, b_off=s.oW, bias=bias)
+        ops.gemm(a, m.params, zx, rows, nd * G, s.f_in_pad, b_off=s.oW, bias=bias)
         return
-    for d in range(2):
-        ops.gemm(a, m.params, zx, rows, G, s.f_in_pad, ldb=2 * G, ldc=2 * G,
+    for d in range(nd):
+        ops.gemm(a, m.params, zx, rows, G, s.f_in_pad, ldb=nd * G, ldc=nd * G,
                  b_off=s.oW + d * G, c_off=d * G,
                  bias=None if bias is None else bias[d * G:(d + 1) * G],
                  a_scale=BW[d], a_scale_period=n_pad)
 
 
-def _rec_dw(m, a_in, dg, s, G, BW, rows, n_pad, split, zmx):
+def _rec_dw(m, a_in, dg, s, G, BW, rows, n_pad, split, zmx, nd=2):
     """dW[d] = (x (.) B_W[d])^T dg_d."""
     if BW is None:
-        ops.gemm(a_in, dg, m.grads, s.f_in_pad, 2 * G, rows, trans_a=True, c_off=s.oW,
+        ops.gemm(a_in, dg, m.grads, s.f_in_pad, nd * G, rows, trans_a=True, c_off=s.oW,
                  split_k=split, b_absmax=zmx)
         return
-    for d in range(2):
-        ops.gemm(a_in, dg, m.grads, s.f_in_pad, G, rows, trans_a=True, ldb=2 * G,
-                 ldc=2 * G, b_off=d * G, c_off=s.oW + d * G, split_k=split,
+    for d in range(nd):
+        ops.gemm(a_in, dg, m.grads, s.f_in_pad, G, rows, trans_a=True, ldb=nd * G,
+                 ldc=nd * G, b_off=d * G, c_off=s.oW + d * G, split_k=split,
                  a_scale=BW[d], a_scale_period=n_pad, b_absmax=zmx)
 
 
-def _rec_dx(m, dg, s, si, G, BW, T, n_pad, zmx, first):
+def _rec_dx(m, dg, s, si, G, BW, T, n_pad, zmx, first, nd=2):
     """dx = sum_d B_W[d] (.) (dg_d @ W_d^T); None for the first stage."""
     if first:
         return None
     rows = T * n_pad
     dx = m._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
     if BW is None:
-        ops.gemm(dg, m.params, dx, rows, s.f_in_pad, 2 * G, trans_b=True, b_off=s.oW,
+        ops.gemm(dg, m.params, dx, rows, s.f_in_pad, nd * G, trans_b=True, b_off=s.oW,
                  a_absmax=zmx)
         return dx
-    for d in range(2):
-        ops.gemm(dg, m.params, dx, rows, s.f_in_pad, G, trans_b=True, lda=2 * G,
-                 ldb=2 * G, a_off=d * G, b_off=s.oW + d * G, c_scale=BW[d],
+    for d in range(nd):
+        ops.gemm(dg, m.params, dx, rows, s.f_in_pad, G, trans_b=True, lda=nd * G,
+                 ldb=nd * G, a_off=d * G, b_off=s.oW + d * G, c_scale=BW[d],
                  c_scale_period=n_pad, beta=0.0 if d == 0 else 1.0, a_absmax=zmx)
     return dx
 
 
-def _rec_du_prev(m, h, dg, c_off, d, G, N, T, n_pad, Hp, scale, split, zmx, h_off=0):
+def _rec_du_prev(m, h, dg, c_off, d, G, N, T, n_pad, Hp, scale, split, zmx, h_off=0, nd=2):
     """grads[c_off:] (Hp, G), columns [0, N) = (h_prev (.) scale)^T dg_d[:, :N], where h_prev is
-    the slab h (T, n_pad, 2, Hp) at h_off one frame earlier in direction d's processing
+    the slab h (T, n_pad, nd, Hp) at h_off one frame earlier in direction d's processing
     order: 0 before the first frame, so T == 1 leaves zeros."""
     kk = (T - 1) * n_pad
     if kk > 0:
-        ops.gemm(h, dg, m.grads, Hp, N, kk, trans_a=True, lda=2 * Hp, ldb=2 * G, ldc=G,
-                 a_off=h_off + d * Hp + (0 if d == 0 else n_pad * 2 * Hp),
-                 b_off=d * G + (n_pad * 2 * G if d == 0 else 0), c_off=c_off,
+        ops.gemm(h, dg, m.grads, Hp, N, kk, trans_a=True, lda=nd * Hp, ldb=nd * G, ldc=G,
+                 a_off=h_off + d * Hp + (0 if d == 0 else n_pad * nd * Hp),
+                 b_off=d * G + (n_pad * nd * G if d == 0 else 0), c_off=c_off,
                  split_k=split, a_scale=scale, a_scale_period=n_pad, b_absmax=zmx)
     else:
         m._gview(c_off, Hp * G).view(Hp, G)[:, :N].zero_()
@@ -992,32 +963,34 @@ def _birnn_backward(m, s, si, rec, da, bp):
     return _rec_dx(m, dz, s, si, Hp, BW, T, n_pad, zmx, bp.first)
 
 
-def _bigru_forward(m, s, si, a, rec, fp):
-    """Bidirectional(GRU) stage (csrc/gru.hip): zx = (a (.) B_W[d]) @ W_d + b_d from the
+def _bigru_forward(m, s, si, a, rec, fp, carry=None):
+    """GRU stage, one or two directions (csrc/gru.hip): zx = (a (.) B_W[d]) @ W_d + b_d from the
     GEMMs, then the recurrence; h, the gates z | r | hh and r (.) m are kept for BPTT.
     batch_norm: the GEMMs write the bias-free projection p into a buffer of the layer (the
     backward pass reads it again), and zx = BN(p) goes to a scratch all layers share (BPTT
-    never reads zx)."""
-    if getattr(s, 'directions', 2) == 1:
-        return _gru_uni_forward(m, s, si, a, rec, fp)
+    never reads zx).  carry: the state arguments of a one-direction stage that streams."""
     a = a.contiguous()
-    n_pad = fp.n_pad
+    n_pad, nd = fp.n_pad, _nd(s)
     T, Hp = a.shape[0], s.Hp
-    rows = T * n_pad
+    dirs = (2,) if nd == 2 else ()          # (one direction: the slabs have no direction axis)
     BW, BU = fp.stage_masks(si)[:2]
     rec['BW'], rec['BU'] = BW, BU
-    zx = m._buf('gzx%d' % si, (T, n_pad, 2, 3 * Hp))
-    _rec_proj(m, a, s, zx, 3 * Hp, BW, rows, n_pad,
-              bias=None if s.bn else m._view(s.ob, 6 * Hp))
+    zx = m._buf('gzx%d' % si, (T, n_pad) + dirs + (3 * Hp,))
+    _rec_proj(m, a, s, zx, 3 * Hp, BW, T * n_pad, n_pad,
+              bias=None if s.bn else m._view(s.ob, nd * 3 * Hp), nd=nd)
     if s.bn:
         zx = _seqbn_forward(m, s, si, zx, rec, fp)
-    h = m._buf('gh%d' % si, (T, n_pad, 2, Hp))
-    gates = m._buf('ggates%d' % si, (T, n_pad, 2, 3 * Hp))
-    rm = m._buf('grm%d' % si, (T, n_pad, 2, Hp))
-    ysum = m._buf('gsum%d' % si, (T, n_pad, Hp)) if s.merge == 'sum' else None
-    ops.gru_seq_fwd(zx, m._view(s.oU, 2 * Hp * 3 * Hp), h, gates, rm, T, n_pad, Hp,
-                    act=s.act, mask_u=BU, y_sum=ysum)
+    h = m._buf('gh%d' % si, (T, n_pad) + dirs + (Hp,))
+    gates = m._buf('ggates%d' % si, (T, n_pad) + dirs + (3 * Hp,))
+    rm = m._buf('grm%d' % si, (T, n_pad) + dirs + (Hp,))
     rec.update(h=h, gates=gates, rm=rm)
+    U = m._view(s.oU, nd * Hp * 3 * Hp)
+    if nd == 1:
+        ops.gru_uni_seq_fwd(zx, U, h, gates, rm, T, n_pad, Hp, act=s.act,
+                            mask_u=None if BU is None else BU[0], **(carry or {}))
+        return h
+    ysum = m._buf('gsum%d' % si, (T, n_pad, Hp)) if s.merge == 'sum' else None
+    ops.gru_seq_fwd(zx, U, h, gates, rm, T, n_pad, Hp, act=s.act, mask_u=BU, y_sum=ysum)
     return ysum if ysum is not None else h.view(T, n_pad, 2 * Hp)
 
 
@@ -1047,30 +1020,34 @@ def _seqbn_forward(m, s, si, p, rec, fp):
 
 
 def _bigru_backward(m, s, si, rec, da, bp):
-    """BPTT of a GRU stage (csrc/gru.hip), then its weight gradients and dx from the GEMMs:
+    """BPTT of a GRU stage (csrc/gru.hip; one direction: from the zero state), then its weight
+    gradients and dx from the GEMMs:
     dU_z, dU_r [d] = (h_prev (.) B_U)^T [da_z | da_r], dU_h[d] = (r (.) m)^T da_h (r (.) m
     kept by the forward pass), dW[d] = (x (.) B_W)^T da_d, db from the per-batch-tile sums,
     dx = sum_d B_W[d] (.) (da_d @ W_d^T).  Returns dx (or None)."""
-    if getattr(s, 'directions', 2) == 1:
-        return _gru_uni_backward(m, s, si, rec, da, bp)
-    split = bp.split
+    split, nd = bp.split, _nd(s)
     T, n_pad = da.shape[0], da.shape[1]
-    rows, Hp = T * n_pad, s.Hp
+    rows, Hp, G = T * n_pad, s.Hp, 3 * s.Hp
+    dirs = (2,) if nd == 2 else ()
     BW, BU, h, a_in = rec['BW'], rec['BU'], rec['h'], rec['in']
-    dg = m._buf('gda%d' % si, (T, n_pad, 2, 3 * Hp))
-    dbp = m._buf('gdbp%d' % si, (n_pad // 16, 2, 3 * Hp))
+    dg = m._buf('gda%d' % si, (T, n_pad) + dirs + (G,))
+    dbp = m._buf('gdbp%d' % si, (n_pad // 16,) + dirs + (G,))
     zmx = m._buf('gdamax%d' % si, (1,))
-    ops.gru_seq_bwd(da.contiguous(), m._view(s.oU, 2 * Hp * 3 * Hp), h, rec['gates'],
-                    dg, T, n_pad, Hp, act=s.act, mask_u=BU,
-                    shared_dy=s.merge == 'sum', db_part=dbp, dz_absmax=zmx)
+    U = m._view(s.oU, nd * Hp * G)
+    if nd == 1:
+        ops.gru_uni_seq_bwd(da.contiguous(), U, h, rec['gates'], dg, T, n_pad, Hp, act=s.act,
+                            mask_u=None if BU is None else BU[0], db_part=dbp, dz_absmax=zmx)
+    else:
+        ops.gru_seq_bwd(da.contiguous(), U, h, rec['gates'], dg, T, n_pad, Hp, act=s.act,
+                        mask_u=BU, shared_dy=s.merge == 'sum', db_part=dbp, dz_absmax=zmx)
     if not s.bn:
-        ops.colsum(dbp, n_pad // 16, 6 * Hp, 6 * Hp, m._gview(s.ob, 6 * Hp))
-    for d in range(2):
-        oU = s.oU + d * Hp * 3 * Hp
-        _rec_du_prev(m, h, dg, oU, d, 3 * Hp, 2 * Hp, T, n_pad, Hp,
-                     None if BU is None else BU[d], split, zmx)
-        ops.gemm(rec['rm'], dg, m.grads, Hp, Hp, rows, trans_a=True, lda=2 * Hp,
-                 ldb=6 * Hp, ldc=3 * Hp, a_off=d * Hp, b_off=d * 3 * Hp + 2 * Hp,
+        ops.colsum(dbp, n_pad // 16, nd * G, nd * G, m._gview(s.ob, nd * G))
+    for d in range(nd):
+        oU = s.oU + d * Hp * G
+        _rec_du_prev(m, h, dg, oU, d, G, 2 * Hp, T, n_pad, Hp,
+                     None if BU is None else BU[d], split, zmx, nd=nd)
+        ops.gemm(rec['rm'], dg, m.grads, Hp, Hp, rows, trans_a=True, lda=nd * Hp,
+                 ldb=nd * G, ldc=G, a_off=d * Hp, b_off=d * G + 2 * Hp,
                  c_off=oU + 2 * Hp, split_k=split, b_absmax=zmx)
     if s.bn:
         # dU above came from da; dW and dx come from dp = BN'(da), which has its own absmax
@@ -1081,93 +1058,8 @@ def _bigru_backward(m, s, si, rec, da, bp):
                       rec['stats'], dp, m._gview(s.og, 6 * Hp), rec['N'], 6 * Hp,
                       lens=rec['lens'], dbeta=m._gview(s.obeta, 6 * Hp), dp_absmax=zmx)
         dg = dp
-    _rec_dw(m, a_in.contiguous(), dg, s, 3 * Hp, BW, rows, n_pad, split, zmx)
-    return _rec_dx(m, dg, s, si, 3 * Hp, BW, T, n_pad, zmx, bp.first)
-
-
-# The unidirectional GRU (K28): the one-direction versions of the two handlers above.  The masks
-# are direction 0's of the pair a 'bigru' stage is drawn (same shapes, streams and step).
-def _gru_uni_zx(m, s, si, a, BW, n_pad):
-    """zx (T, n_pad, 3Hp) = (a (.) B_W) @ W + b: one GEMM."""
-    T, G = a.shape[0], 3 * s.Hp
-    zx = m._buf('gzx%d' % si, (T, n_pad, G))
-    scale = {} if BW is None else dict(a_scale=BW, a_scale_period=n_pad)
-    ops.gemm(a, m.params, zx, T * n_pad, G, s.f_in_pad, b_off=s.oW, bias=m._view(s.ob, G),
-             **scale)
-    return zx
-
-
-def _gru_uni_forward(m, s, si, a, rec, fp):
-    a = a.contiguous()
-    n_pad = fp.n_pad
-    T, Hp = a.shape[0], s.Hp
-    BW, BU = fp.stage_masks(si)[:2]
-    rec['BW'], rec['BU'] = BW, BU
-    BW, BU = (None if BW is None else BW[0]), (None if BU is None else BU[0])
-    zx = _gru_uni_zx(m, s, si, a, BW, n_pad)
-    h = m._buf('gh%d' % si, (T, n_pad, Hp))
-    gates = m._buf('ggates%d' % si, (T, n_pad, 3 * Hp))
-    rm = m._buf('grm%d' % si, (T, n_pad, Hp))
-    ops.gru_uni_seq_fwd(zx, m._view(s.oU, Hp * 3 * Hp), h, gates, rm, T, n_pad, Hp, act=s.act,
-                        mask_u=BU)
-    rec.update(h=h, gates=gates, rm=rm)
-    return h
-
-
-def _gru_uni_backward(m, s, si, rec, da, bp):
-    """BPTT from the zero state, then dU_z, dU_r = (h_prev (.) B_U)^T [da_z | da_r], dU_h =
-    (r (.) m)^T da_h, dW = (x (.) B_W)^T da, db from the per-batch-tile sums, dx = B_W (.)
-    (da @ W^T).  Returns dx (or None)."""
-    split = bp.split
-    T, n_pad = da.shape[0], da.shape[1]
-    rows, Hp = T * n_pad, s.Hp
-    G = 3 * Hp
-    BW, BU, h, a_in = rec['BW'], rec['BU'], rec['h'], rec['in'].contiguous()
-    BW, BU = (None if BW is None else BW[0]), (None if BU is None else BU[0])
-    dg = m._buf('gda%d' % si, (T, n_pad, G))
-    dbp = m._buf('gdbp%d' % si, (n_pad // 16, G))
-    zmx = m._buf('gdamax%d' % si, (1,))
-    ops.gru_uni_seq_bwd(da.contiguous(), m._view(s.oU, Hp * G), h, rec['gates'], dg, T, n_pad,
-                        Hp, act=s.act, mask_u=BU, db_part=dbp, dz_absmax=zmx)
-    ops.colsum(dbp, n_pad // 16, G, G, m._gview(s.ob, G))
-    kk = (T - 1) * n_pad
-    if kk > 0:      # h_prev of frame t is h[t - 1]: 0 before frame 0
-        ops.gemm(h, dg, m.grads, Hp, 2 * Hp, kk, trans_a=True, lda=Hp, ldb=G, ldc=G,
-                 b_off=n_pad * G, c_off=s.oU, split_k=split, a_scale=BU, a_scale_period=n_pad,
-                 b_absmax=zmx)
-    else:
-        m._gview(s.oU, Hp * G).view(Hp, G)[:, :2 * Hp].zero_()
-    ops.gemm(rec['rm'], dg, m.grads, Hp, Hp, rows, trans_a=True, lda=Hp, ldb=G, ldc=G,
-             b_off=2 * Hp, c_off=s.oU + 2 * Hp, split_k=split, b_absmax=zmx)
-    scale = {} if BW is None else dict(a_scale=BW, a_scale_period=n_pad)
-    ops.gemm(a_in, dg, m.grads, s.f_in_pad, G, rows, trans_a=True, c_off=s.oW, split_k=split,
-             b_absmax=zmx, **scale)
-    if bp.first:
-        return None
-    dx = m._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-    scale = {} if BW is None else dict(c_scale=BW, c_scale_period=n_pad)
-    ops.gemm(dg, m.params, dx, rows, s.f_in_pad, G, trans_b=True, b_off=s.oW, a_absmax=zmx,
-             **scale)
-    return dx
-
-
-def _gru_uni_stream(m, s, si, a, ss):
-    """The new frames of a unidirectional GRU: the zx GEMM of the chunk, then the recurrence from
-    the stage's state into the other buffer of its pair, then the swap.  State: two (n_pad, Hp)
-    buffers, zero-filled when created or reset; no ring."""
-    a = a.contiguous()
-    Tq, n_pad, Hp = a.shape[0], a.shape[1], s.Hp
-    st = ss.state.setdefault(si, {})
-    if 'h' not in st:
-        st['h'] = [ss.zeros((n_pad, Hp)), ss.zeros((n_pad, Hp))]
-    zx = _gru_uni_zx(m, s, si, a, None, n_pad)
-    h = m._buf('gh%d' % si, (Tq, n_pad, Hp))
-    gates = m._buf('ggates%d' % si, (Tq, n_pad, 3 * Hp))
-    rm = m._buf('grm%d' % si, (Tq, n_pad, Hp))
-    ops.gru_uni_seq_fwd(zx, m._view(s.oU, Hp * 3 * Hp), h, gates, rm, Tq, n_pad, Hp, act=s.act,
-                        h0=st['h'][0], h_last=st['h'][1])
-    st['h'].reverse()
-    return h
+    _rec_dw(m, a_in.contiguous(), dg, s, G, BW, rows, n_pad, split, zmx, nd=nd)
+    return _rec_dx(m, dg, s, si, G, BW, T, n_pad, zmx, bp.first, nd=nd)
 
 
 def _birhn_forward(m, s, si, a, rec, fp):
@@ -1252,10 +1144,11 @@ KINDS = {
 }
 
 # Variants of a kind with a step handler of their own (see the K26 note at the top):
-# kind -> (says whether a stage is the variant, its stream(m, s, si, a, ss))
+# kind -> (says whether a stage is the variant, its stream(m, s, si, a, ss)).  The bare GRU and
+# LSTM share one (_uni_stream): the forward handler of training, given the state they carry.
 STREAM_VARIANTS = {
-    'bigru': (lambda s: getattr(s, 'directions', 2) == 1, _gru_uni_stream),
-    'bilstm': (lambda s: getattr(s, 'directions', 2) == 1, _lstm_uni_stream),
+    'bigru': (lambda s: _nd(s) == 1, _uni_stream(('h',))),
+    'bilstm': (lambda s: _nd(s) == 1, _uni_stream(('h', 'c'))),
 }
 
 

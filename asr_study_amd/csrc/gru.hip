@@ -206,11 +206,6 @@ struct GruCall {
   int dy_dstride;
 };
 
-struct GruPlan {
-  int NR, J, NBT, blocks;
-  size_t ut_bytes, vec_bytes;
-};
-
 // the checks of rec_check_args, then the fields both args blocks share
 template <class Args>
 int gru_call_common(const char* pfx, int nd, const Args* a, GruCall* c) {
@@ -241,17 +236,17 @@ int gru_call(const asr_gru_uni_args* a, GruCall* c) {
 
 // the tile plan depends on (n_pad, H) alone: one direction's is the bidirectional one's, with
 // half the workgroups
-void make_gru_plan(const GruCall& c, bool bwd, GruPlan* pl) {
-  pl->NR = rec_rows(c.n_pad);
-  pl->J = 1024 / pl->NR;
-  pl->NBT = c.n_pad / pl->NR;
+RecPlan make_gru_plan(const GruCall& c, bool bwd) {
   // the widest launch: forward phase A has 2H output columns, every other phase H
-  pl->blocks = ((bwd ? c.H : 2 * c.H) + pl->J - 1) / pl->J * pl->NBT * c.nd;
-  pl->ut_bytes = bwd ? asr_align_up((size_t)c.nd * 3 * c.H * c.H * sizeof(float), 256) : 0;
-  pl->vec_bytes = bwd ? asr_align_up((size_t)c.n_pad * c.nd * c.H * sizeof(float), 256) : 0;
+  RecPlan pl = rec_plan(c.n_pad, bwd ? c.H : 2 * c.H, c.nd);
+  if (bwd) {
+    pl.ut_bytes = asr_align_up((size_t)c.nd * 3 * c.H * c.H * sizeof(float), 256);
+    pl.vec_bytes = asr_align_up((size_t)c.n_pad * c.nd * c.H * sizeof(float), 256);
+  }
+  return pl;
 }
 
-size_t gru_ws_bytes(const GruPlan& pl) { return 256 + pl.ut_bytes + 2 * pl.vec_bytes; }
+size_t gru_ws_bytes(const RecPlan& pl) { return 256 + pl.ut_bytes + 2 * pl.vec_bytes; }
 
 template <int NR, int ND>
 int gru_launch(int ph, const GruParams& p, int ncols, int nbt, hipStream_t stream) {
@@ -267,7 +262,7 @@ int gru_launch(int ph, const GruParams& p, int ncols, int nbt, hipStream_t strea
   return ASR_OK;
 }
 
-int gru_phase(const GruPlan& pl, int nd, int ph, const GruParams& p, int ncols, hipStream_t stream) {
+int gru_phase(const RecPlan& pl, int nd, int ph, const GruParams& p, int ncols, hipStream_t stream) {
   return rec_with_rows(pl.NR, [&](auto nr) {
     constexpr int NR = decltype(nr)::value;
     return nd == 1 ? gru_launch<NR, 1>(ph, p, ncols, pl.NBT, stream)
@@ -277,12 +272,10 @@ int gru_phase(const GruPlan& pl, int nd, int ph, const GruParams& p, int ncols, 
 
 // every argument error is refused here, before the first device call
 int gru_run(const GruCall& c, bool bwd, void* workspace, size_t ws_bytes, hipStream_t stream) {
-  GruPlan pl;
-  make_gru_plan(c, bwd, &pl);
+  const RecPlan pl = make_gru_plan(c, bwd);
   const int nd = c.nd;
-  const size_t need = gru_ws_bytes(pl);
-  ASR_CHECK_ARG(workspace != nullptr && ws_bytes >= need, "%s: workspace %zu bytes < %zu", c.pfx,
-                ws_bytes, need);
+  int rc = rec_check_ws(c.pfx, workspace, ws_bytes, gru_ws_bytes(pl));
+  if (rc != ASR_OK) return rc;
   ASR_CHECK_ARG(c.U && c.h && c.gates, "%s: U, h and gates are required", c.pfx);
   if (bwd) ASR_CHECK_ARG(c.dy && c.da && c.dy_ld >= c.H && c.dy_ld % 4 == 0 &&
                          c.dy_dstride % 4 == 0,
@@ -294,7 +287,6 @@ int gru_run(const GruCall& c, bool bwd, void* workspace, size_t ws_bytes, hipStr
                 "(training starts from the zero state)", c.pfx);
   char* ws = static_cast<char*>(workspace);
   const int H = c.H, T = c.T;
-  int rc;
   GruParams p;
   p.T = T; p.n_pad = c.n_pad; p.Hp = H;
   p.act = c.act; p.clip = c.clip;
@@ -335,9 +327,7 @@ template <class Args>
 size_t gru_ws_of(const Args* a, int backward) {
   GruCall c;
   if (gru_call(a, &c) != ASR_OK) return 0;
-  GruPlan pl;
-  make_gru_plan(c, backward != 0, &pl);
-  return gru_ws_bytes(pl);
+  return gru_ws_bytes(make_gru_plan(c, backward != 0));
 }
 
 template <class Args>
@@ -353,13 +343,8 @@ int gru_plan_of(const Args* a, int backward, int* persistent, int* rows, int* un
   GruCall c;
   const int rc = gru_call(a, &c);
   if (rc != ASR_OK) return rc;
-  GruPlan pl;
-  make_gru_plan(c, backward != 0, &pl);
-  if (persistent) *persistent = 0;
-  if (rows) *rows = pl.NR;
-  if (units) *units = pl.J;
-  if (blocks) *blocks = pl.blocks;
-  return ASR_OK;
+  const RecPlan pl = make_gru_plan(c, backward != 0);
+  return rec_plan_out(pl, pl.J, persistent, rows, units, blocks);
 }
 
 }  // namespace

@@ -157,24 +157,17 @@ lstm_uni_bwd_kernel(LstmUniParams p) {
 }
 
 // ---- host side -------------------------------------------------------------------------------
-struct LstmUniPlan {
-  int NR, J, NBT, blocks;
-  size_t ut_bytes, vec_bytes;
-};
-
-// the checks every entry point starts with (the plan and the workspace size too): the geometry,
-// the mode, the activation and the state pairs
+// the checks every entry point starts with (the plan and the workspace size too): those of
+// rec_check_args under the LSTM's activation ids, then the state pairs
 int lstm_uni_check(const asr_lstm_uni_args* a) {
-  const char* pfx = "lstm_uni";
-  ASR_CHECK_ARG(a != nullptr, "%s: null arguments", pfx);
-  ASR_CHECK_ARG(a->T >= 1 && a->n_pad >= 16 && a->n_pad % 16 == 0 && a->H >= 4 && a->H % 4 == 0,
-                "%s: T >= 1, n_pad a multiple of 16, H a positive multiple of 4 (T=%d n_pad=%d H=%d)",
-                pfx, a->T, a->n_pad, a->H);
-  ASR_CHECK_ARG(a->mode == 0 || a->mode == 1, "%s: mode %d: only the stepwise form exists "
-                "(0 = the plan's form, 1 = stepwise)", pfx, a->mode);
-  ASR_CHECK_ARG(a->activation >= 0 && a->activation < kLstmUniActs, "%s: activation id %d (0 tanh, "
-                "1 relu, 2 sigmoid, 3 hard_sigmoid, 4 linear, 5 softsign, 6 softplus)", pfx,
-                a->activation);
+  const int rc = rec_check_args("lstm_uni", a, false,
+                                [](const char* pfx, const asr_lstm_uni_args* a) -> int {
+    ASR_CHECK_ARG(a->activation >= 0 && a->activation < kLstmUniActs, "%s: activation id %d (0 "
+                  "tanh, 1 relu, 2 sigmoid, 3 hard_sigmoid, 4 linear, 5 softsign, 6 softplus)", pfx,
+                  a->activation);
+    return ASR_OK;
+  });
+  if (rc != ASR_OK) return rc;
   ASR_CHECK_ARG((a->h0 == nullptr) == (a->c0 == nullptr), "lstm_uni: h0 and c0 come together "
                 "(both, or neither for the zero state)");
   ASR_CHECK_ARG((a->h_last == nullptr) == (a->c_last == nullptr), "lstm_uni: h_last and c_last "
@@ -187,17 +180,17 @@ int lstm_uni_check(const asr_lstm_uni_args* a) {
   return ASR_OK;
 }
 
-void make_lstm_uni_plan(const asr_lstm_uni_args* a, bool bwd, LstmUniPlan* pl) {
-  pl->NR = rec_rows(a->n_pad);
-  pl->J = 1024 / pl->NR;
-  pl->NBT = a->n_pad / pl->NR;
+RecPlan make_lstm_uni_plan(const asr_lstm_uni_args* a, bool bwd) {
   // forward: 4H gate columns; BPTT: H units
-  pl->blocks = ((bwd ? a->H : 4 * a->H) + pl->J - 1) / pl->J * pl->NBT;
-  pl->ut_bytes = bwd ? asr_align_up((size_t)4 * a->H * a->H * sizeof(float), 256) : 0;
-  pl->vec_bytes = bwd ? asr_align_up((size_t)a->n_pad * a->H * sizeof(float), 256) : 0;
+  RecPlan pl = rec_plan(a->n_pad, bwd ? a->H : 4 * a->H, 1);
+  if (bwd) {
+    pl.ut_bytes = asr_align_up((size_t)4 * a->H * a->H * sizeof(float), 256);
+    pl.vec_bytes = asr_align_up((size_t)a->n_pad * a->H * sizeof(float), 256);
+  }
+  return pl;
 }
 
-size_t lstm_uni_ws_bytes(const LstmUniPlan& pl) { return 256 + pl.ut_bytes + pl.vec_bytes; }
+size_t lstm_uni_ws_bytes(const RecPlan& pl) { return 256 + pl.ut_bytes + pl.vec_bytes; }
 
 template <int NR>
 int lstm_uni_launch(bool bwd, const LstmUniParams& p, int nbt, hipStream_t stream) {
@@ -214,11 +207,9 @@ int lstm_uni_run(const asr_lstm_uni_args* a, bool bwd, void* workspace, size_t w
                  hipStream_t stream) {
   int rc = lstm_uni_check(a);
   if (rc != ASR_OK) return rc;
-  LstmUniPlan pl;
-  make_lstm_uni_plan(a, bwd, &pl);
-  const size_t need = lstm_uni_ws_bytes(pl);
-  ASR_CHECK_ARG(workspace != nullptr && ws_bytes >= need, "lstm_uni: workspace %zu bytes < %zu",
-                ws_bytes, need);
+  const RecPlan pl = make_lstm_uni_plan(a, bwd);
+  if ((rc = rec_check_ws("lstm_uni", workspace, ws_bytes, lstm_uni_ws_bytes(pl))) != ASR_OK)
+    return rc;
   ASR_CHECK_ARG(a->U && a->h && a->cell && a->gates, "lstm_uni: U, h, cell and gates are required");
   if (bwd) ASR_CHECK_ARG(a->dy && a->dz && a->dy_ld >= a->H && a->dy_ld % 4 == 0,
                          "lstm_uni: BPTT needs dy (dy_ld >= H, a multiple of 4) and dz");
@@ -259,9 +250,7 @@ int lstm_uni_run(const asr_lstm_uni_args* a, bool bwd, void* workspace, size_t w
 
 extern "C" size_t asr_lstm_uni_workspace_bytes(const asr_lstm_uni_args* a, int backward) {
   if (lstm_uni_check(a) != ASR_OK) return 0;
-  LstmUniPlan pl;
-  make_lstm_uni_plan(a, backward != 0, &pl);
-  return lstm_uni_ws_bytes(pl);
+  return lstm_uni_ws_bytes(make_lstm_uni_plan(a, backward != 0));
 }
 
 extern "C" int asr_lstm_uni_seq_fwd(const asr_lstm_uni_args* a, void* workspace, size_t ws_bytes,
@@ -278,11 +267,6 @@ extern "C" int asr_lstm_uni_plan(const asr_lstm_uni_args* a, int backward, int* 
                                  int* rows, int* units, int* blocks) {
   const int rc = lstm_uni_check(a);
   if (rc != ASR_OK) return rc;
-  LstmUniPlan pl;
-  make_lstm_uni_plan(a, backward != 0, &pl);
-  if (persistent) *persistent = 0;
-  if (rows) *rows = pl.NR;
-  if (units) *units = pl.J;
-  if (blocks) *blocks = pl.blocks;
-  return ASR_OK;
+  const RecPlan pl = make_lstm_uni_plan(a, backward != 0);
+  return rec_plan_out(pl, pl.J, persistent, rows, units, blocks);
 }

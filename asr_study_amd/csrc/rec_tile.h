@@ -1,7 +1,8 @@
 // rec_tile.h -- what the stepwise recurrences of gru.hip, rhn.hip and lstm_uni.hip share (and, of
 // the small pieces, rnn.hip): the reduction of one workgroup tile, the helper kernels around a
-// sequence and the argument checks of their plans (lstm_uni.hip, whose activation ids are the
-// LSTM's 0..6, checks its own).
+// sequence and the host side of their plans: the tile set-up (RecPlan), the answer of
+// asr_*_plan, the workspace-size check and the argument checks (lstm_uni.hip, whose activation ids
+// are the LSTM's 0..6, passes its own activation rule).
 //
 // Geometry of a tile (RecTile<NR>): a workgroup (256 threads) owns NR batch rows x J tile columns
 // of one direction, NR * J = 1024, NR = 64 / 32 / 16 (the largest that divides n_pad).  The
@@ -245,13 +246,54 @@ auto rec_with_rows(int NR, F&& f) {
        ? f(std::integral_constant<int, 32>()) : f(std::integral_constant<int, 16>());
 }
 
+// The tile set-up of a stepwise recurrence (gru.hip, rhn.hip, lstm_uni.hip): it depends on n_pad,
+// the column count of the widest launch and the directions nd alone.  ut_bytes (BPTT: U^T) and
+// vec_bytes (BPTT: a vector the steps hand on) are the caller's to fill; they stay 0 otherwise.
+struct RecPlan {
+  int NR, J, NBT, blocks;
+  size_t ut_bytes, vec_bytes;
+};
+
+inline RecPlan rec_plan(int n_pad, int cols, int nd) {
+  const int NR = rec_rows(n_pad), J = 1024 / NR, NBT = n_pad / NR;
+  return RecPlan{NR, J, NBT, (cols + J - 1) / J * NBT * nd, 0, 0};
+}
+
+// the out-parameters of asr_*_plan for a stepwise form; units: the tile columns of a workgroup
+inline int rec_plan_out(const RecPlan& pl, int units_of, int* persistent, int* rows, int* units,
+                        int* blocks) {
+  if (persistent) *persistent = 0;
+  if (rows) *rows = pl.NR;
+  if (units) *units = units_of;
+  if (blocks) *blocks = pl.blocks;
+  return ASR_OK;
+}
+
+inline int rec_check_ws(const char* pfx, const void* workspace, size_t ws_bytes, size_t need) {
+  ASR_CHECK_ARG(workspace != nullptr && ws_bytes >= need, "%s: workspace %zu bytes < %zu", pfx,
+                ws_bytes, need);
+  return ASR_OK;
+}
+
 inline bool rec_act_ok(int id) { return id == 0 || id == 1 || id == 4 || id == kActClipped; }
 
-// the checks every plan starts with (asr_rnn_args / asr_gru_args / asr_gru_uni_args / asr_rhn_args:
-// the same fields);
-// persistent_form: mode 2 exists
-template <class Args>
-int rec_check_args(const char* pfx, const Args* a, bool persistent_form) {
+// the activation rule of asr_rnn_args / asr_gru_args / asr_gru_uni_args / asr_rhn_args
+struct RecActRule {
+  template <class Args>
+  int operator()(const char* pfx, const Args* a) const {
+    ASR_CHECK_ARG(rec_act_ok(a->activation), "%s: activation id %d (tanh 0, relu 1, linear 4, "
+                  "clipped relu 7)", pfx, a->activation);
+    ASR_CHECK_ARG(a->activation != kActClipped || a->clip > 0.f, "%s: clipped relu needs clip > 0",
+                  pfx);
+    return ASR_OK;
+  }
+};
+
+// the checks every plan starts with (the args blocks share these fields): the geometry, the mode
+// (persistent_form: mode 2 exists), then the activation by the rule act_ok(pfx, a)
+template <class Args, class ActRule = RecActRule>
+int rec_check_args(const char* pfx, const Args* a, bool persistent_form,
+                   ActRule act_ok = ActRule()) {
   ASR_CHECK_ARG(a != nullptr, "%s: null arguments", pfx);
   ASR_CHECK_ARG(a->T >= 1 && a->n_pad >= 16 && a->n_pad % 16 == 0 && a->H >= 4 && a->H % 4 == 0,
                 "%s: T >= 1, n_pad a multiple of 16, H a positive multiple of 4 (T=%d n_pad=%d H=%d)",
@@ -261,11 +303,7 @@ int rec_check_args(const char* pfx, const Args* a, bool persistent_form) {
   else
     ASR_CHECK_ARG(a->mode == 0 || a->mode == 1, "%s: mode %d: only the stepwise form exists "
                   "(0 = the plan's form, 1 = stepwise)", pfx, a->mode);
-  ASR_CHECK_ARG(rec_act_ok(a->activation), "%s: activation id %d (tanh 0, relu 1, linear 4, "
-                "clipped relu 7)", pfx, a->activation);
-  ASR_CHECK_ARG(a->activation != kActClipped || a->clip > 0.f, "%s: clipped relu needs clip > 0",
-                pfx);
-  return ASR_OK;
+  return act_ok(pfx, a);
 }
 
 }  // namespace

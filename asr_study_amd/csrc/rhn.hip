@@ -221,9 +221,9 @@ __global__ void rhn_interleave_kernel(const float* __restrict__ U, float* __rest
 }
 
 // ---- host side -------------------------------------------------------------------------------
-struct RhnPlan {
-  int NR, J, JB, NBT, C, blocks;
-  size_t ut_bytes, vec_bytes;             // the copy of U (forward: interleaved, BPTT: U^T); gbuf
+// ut_bytes: the copy of U (forward: interleaved, BPTT: U^T); vec_bytes: gbuf
+struct RhnPlan : RecPlan {
+  int JB, C;                              // a workgroup's units; column blocks per unit
   size_t ui_floats;
 };
 
@@ -232,12 +232,11 @@ int make_rhn_plan(const asr_rhn_args* a, bool bwd, RhnPlan* pl) {
   if (rc != ASR_OK) return rc;
   ASR_CHECK_ARG(a->depth >= 1, "rhn: depth %d < 1", a->depth);
   ASR_CHECK_ARG(a->coupling == 0 || a->coupling == 1, "rhn: coupling %d (0 or 1)", a->coupling);
+  // a forward workgroup owns JB = J / k units (their C <= k column blocks fill its J tile columns)
+  const int k = bwd ? 1 : (a->coupling ? 2 : 4);
+  static_cast<RecPlan&>(*pl) = rec_plan(a->n_pad, k * a->H, 2);
   pl->C = a->coupling ? 2 : 3;
-  pl->NR = rec_rows(a->n_pad);
-  pl->J = 1024 / pl->NR;
-  pl->JB = bwd ? pl->J : pl->J / (a->coupling ? 2 : 4);
-  pl->NBT = a->n_pad / pl->NR;
-  pl->blocks = (a->H + pl->JB - 1) / pl->JB * pl->NBT * 2;
+  pl->JB = pl->J / k;
   pl->ut_bytes = bwd ? asr_align_up((size_t)2 * a->depth * pl->C * a->H * a->H * sizeof(float), 256) : 0;
   pl->ui_floats = (size_t)2 * a->depth * a->H * ((a->H + pl->JB - 1) / pl->JB * pl->C * pl->JB);
   if (!bwd) pl->ut_bytes = asr_align_up(pl->ui_floats * sizeof(float), 256);
@@ -271,9 +270,7 @@ int rhn_run(const asr_rhn_args* a, bool bwd, void* workspace, size_t ws_bytes, h
   RhnPlan pl;
   int rc = make_rhn_plan(a, bwd, &pl);
   if (rc != ASR_OK) return rc;
-  const size_t need = rhn_ws_bytes(pl);
-  ASR_CHECK_ARG(workspace != nullptr && ws_bytes >= need, "rhn: workspace %zu bytes < %zu",
-                ws_bytes, need);
+  if ((rc = rec_check_ws("rhn", workspace, ws_bytes, rhn_ws_bytes(pl))) != ASR_OK) return rc;
   ASR_CHECK_ARG(a->U && a->h && a->gates, "rhn: U, h and gates are required");
   if (bwd) ASR_CHECK_ARG(a->dy && a->da && a->dy_ld >= a->H && a->dy_ld % 4 == 0 &&
                          a->dy_dir_stride % 4 == 0,
@@ -346,9 +343,5 @@ extern "C" int asr_rhn_plan(const asr_rhn_args* a, int backward, int* persistent
   RhnPlan pl;
   const int rc = make_rhn_plan(a, backward != 0, &pl);
   if (rc != ASR_OK) return rc;
-  if (persistent) *persistent = 0;
-  if (rows) *rows = pl.NR;
-  if (units) *units = pl.JB;
-  if (blocks) *blocks = pl.blocks;
-  return ASR_OK;
+  return rec_plan_out(pl, pl.JB, persistent, rows, units, blocks);
 }

@@ -355,9 +355,8 @@ int rnn_run(const asr_rnn_args* a, bool bwd, void* workspace, size_t ws_bytes, h
   RnnPlan pl;
   int rc = make_rnn_plan(a, bwd, &pl);
   if (rc != ASR_OK) return rc;
-  const size_t need = kHeadBytes + pl.ut_bytes + pl.x_bytes;
-  ASR_CHECK_ARG(workspace != nullptr && ws_bytes >= need, "rnn: workspace %zu bytes < %zu",
-                ws_bytes, need);
+  rc = rec_check_ws("rnn", workspace, ws_bytes, kHeadBytes + pl.ut_bytes + pl.x_bytes);
+  if (rc != ASR_OK) return rc;
   ASR_CHECK_ARG(a->U && a->h, "rnn: U and h are required");
   if (bwd) ASR_CHECK_ARG(a->dy && a->dz && a->dy_ld >= a->H, "rnn: BPTT needs dy (dy_ld >= H) and dz");
   else ASR_CHECK_ARG(a->zx != nullptr, "rnn: the forward pass needs zx");
