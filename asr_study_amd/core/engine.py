@@ -19,8 +19,9 @@ lies in the flat buffer, and how it is padded, is the parameter table of core/pa
 
 What a stage kind reads from its spec, computes and differentiates is its entry of the stage-kind
 table of core/stages.py; ``_layout`` / ``forward`` / ``backward`` here are the prologues, one loop
-over the stages and the epilogues.  Only the two BiLSTM bodies, whose launches are scheduled over
-three streams, live here (``_bilstm_forward`` / ``_bilstm_backward``).
+over the stages and the epilogues.  The two-direction LSTM stage, whose launches are scheduled
+over three streams, is core/bilstm.py: its handlers, its switches (``bilstm.switches``) and what
+it decides per pass (``bilstm.begin_forward`` / ``begin_backward`` / ``end_backward``).
 """
 import math
 import os
@@ -30,6 +31,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from . import bilstm
 from . import optimizers as _opt
 from . import params as P
 from .params import _pad4
@@ -117,49 +119,9 @@ class Model(object):
         self._enqueued = self._checked = 0   # train_on_batch steps enqueued / whose flags were read
         self._ar_ref_pad = 0            # rank-invariant reference shard (set per batch)
         self._ar_covered = []
-        # weight-gradient GEMMs run on a side stream, concurrently with the next
-        # layer's persistent BPTT kernel (which occupies only H/16 x chains CUs)
-        # ASR_OVERLAP: 1 = always, 0 = never, auto (default) = unless a layer's recurrence
-        # fills every CU (cfg3: 2 directions x 4 batch tiles x 32 workgroups = 256): its waves
-        # hold 480 of a SIMD's 512 registers, no GEMM wave fits beside them, and a GEMM launched
-        # on the side stream only waits (measured: 51.9 vs 52.5 ms per cfg3 step, but every
-        # GEMM duration in a profile doubled by the wait) -- decided per batch in forward()
-        self._overlap_mode = os.environ.get('ASR_OVERLAP', 'auto')
-        self.overlap = self._overlap_mode != '0'
-        self._side = torch.cuda.Stream(device=self.device) if self.device.type == 'cuda' else None
-        # the GEMMs either side of a recurrence are pipelined against its last steps
-        # (frames whose both directions are already final), on a third stream
-        # 'auto': only when a layer's recurrence leaves at least half of the CUs to the GEMMs
-        # it is pipelined against (cfg2: 64 of 256 workgroups; not cfg3's 256 of 256)
-        self._pipeline_mode = os.environ.get('ASR_PIPELINE', 'auto')
-        # the recurrence is cut after split/16 of its steps (frames [T-S, S) are final then)
-        self._pipe_split16 = min(15, max(9, int(os.environ.get('ASR_PIPE_SPLIT', '13'))))
-        # (ASR_PIPE_HALVES=0: the pipelined GEMMs wait for whole frames -- comparison switch)
-        self._pipe_halves = os.environ.get('ASR_PIPE_HALVES', '1') != '0'
-        self.pipeline = self.overlap and self._pipeline_mode == '1'
-        # ASR_BPTT_COMPACT: auto (default) = where a layer's BPTT would fill every CU (cfg3) it is
-        # launched in the COMPACT geometry (asr_lstm_args.compact: H/32 workgroups per chain,
-        # half the CUs, bit-identical gradients, a longer step) whenever the weight-gradient
-        # GEMMs of the layer above are waiting, and those run beside it on the side stream
-        # instead of behind it; 0 = never (the serial schedule of rounds 1-4), 1 = wherever the
-        # compact kernel exists
-        self._compact_mode = os.environ.get('ASR_BPTT_COMPACT', 'auto')
-        # ASR_BPTT_PLANES=0: BPTT always writes the fp32 dz slab and a pack pass follows (the
-        # round 1-5 path; A/B switch).  Default: BPTT writes the packed planes itself where its
-        # kernel can (backward()); per-stage bounds of max|dz| live in _buf('dzbound<si>')
-        self._dz_planes_mode = os.environ.get('ASR_BPTT_PLANES', '1') != '0'
-        self._dz_bound_key = {}         # stage -> (fault generation, weights epoch) of its bound
-        self._weights_epoch = 0         # bumped when weights are replaced from outside
-        self._dz_measure_passes = 0     # measuring BPTT passes run so far (first step of a layer)
-        self._pipe = torch.cuda.Stream(device=self.device) if self.device.type == 'cuda' else None
-        # big GEMMs on operands packed once into split-fp16 planes (ops.pack_hl / gemm_hl);
-        # ASR_GEMM_PACKED=0 keeps the convert-per-tile kernels, ASR_GEMM_PREC=0 (exact fp32) too
-        # 'auto': from 512 hidden units on (measured: +4 % at 5 x BiLSTM(512) with the 256 x 256
-        # tile, -6 % at 5 x BiLSTM(256), where the frame-range pipelining of the per-tile path
-        # and the absent pack passes win)
-        self._packed_mode = os.environ.get('ASR_GEMM_PACKED', 'auto')
-        self.packed = False                       # decided in _layout (needs the stage list)
-        self._hl = {}
+        # the side and pipe streams, the packed-operand planes and the switches of the BiLSTM
+        # schedule (overlap, pipeline, compact BPTT, planes written by BPTT)
+        bilstm.switches(self)
         # training-time noise comes from the library's counter-based streams (ops.dropout_masks
         # ...: Philox-4x32-10 keyed by this seed; stream id = 4 * stage index + kind, step =
         # the optimisation step), so a step's masks are a pure function of (seed, stage, step)
@@ -202,9 +164,7 @@ class Model(object):
             s.p_hi = alloc.params
             self.stages.append(s)
         del self._alloc
-        widest = max([st.Hp for st in self.stages if self._is_bilstm(st)] + [0])
-        self.packed = (os.environ.get('ASR_GEMM_PREC', '1') != '0' and
-                       (self._packed_mode == '1' or (self._packed_mode == 'auto' and widest >= 512)))
+        self.packed = bilstm.packed_on(self)
         self.num_classes = f_real
         kinds = [KINDS[st.kind] for st in self.stages]
         # (slots 2, 3 of the timeout flags: the SimpleRNN workspaces', ops.collect_timeout_flags)
@@ -373,100 +333,10 @@ class Model(object):
             self._hl[key] = b
         return b
 
-    def _const_one(self):
-        if not hasattr(self, '_one'):
-            self._one = torch.ones(1, dtype=torch.float32, device=self.device)
-        return self._one
-
-    @staticmethod
-    def _is_bilstm(s):
-        """A BIDIRECTIONAL LSTM stage: the one every scheduled path of this module is about (packed
-        planes, the sizing by the widest recurrence, the pipe and side streams, compact BPTT).  A
-        'bilstm' stage with ``directions`` = 1 is the unidirectional variant (core/stages.py,
-        csrc/lstm_uni.hip): it takes none of them."""
-        return s.kind == 'bilstm' and _nd(s) == 2
-
-    @staticmethod
-    def _y_bounded(s):
-        """|h| <= 1 for a BiLSTM stage whose output activation is bounded (h = o * act(c), 0 <= o
-        <= 1): only then may a packed operand built from its y take 1 as the tensor bound (x the
-        inverted-dropout scale, far below the 2^8 head-room of pow2_scale(1)).  relu / linear /
-        softplus carry an unbounded c through: those outputs are measured."""
-        return Model._is_bilstm(s) and s.act in ('tanh', 'sigmoid', 'hard_sigmoid', 'softsign')
-
-    def _stage_packed(self, s):
-        """Whether a BiLSTM stage's GEMMs run on packed operands (plain cell only)."""
-        return (self.packed and self._is_bilstm(s) and s.mi is None and s.ln is None
-                and s.f_in_pad % 8 == 0 and s.Hp % 8 == 0)      # 16-byte rows of the planes
-
-    def _pack_weights(self):
-        """W of every packed stage -> planes for x@W (reduction over the input features:
-        (8H, in)) and for dz@W^T (reduction over the gate columns: (in, 8H)); one pass per W,
-        ~0.3 GB per step at cfg3.  Only the FIRST packed stage's planes are needed at once: its
-        pack runs on the calling stream, the others' (two small kernels each, launch-bound: 0.15 ms
-        of a cfg3 step when they sat in front of the first GEMM) on the side stream beside the
-        first layer's work; self._w_ready[si] is the event the stage's first GEMM waits for."""
-        self._w_ready = {}
-        main = torch.cuda.current_stream(self.device) if self.device.type == 'cuda' else None
-        packed = [(si, s) for si, s in enumerate(self.stages) if self._stage_packed(s)]
-
-        def pack(si, s):
-            n = s.f_in_pad * 8 * s.Hp
-            w = self.params[s.oW:s.oW + n]
-            amax = ops.absmax(w, self._buf('wamax%d' % si, (1,)))
-            ops.pack_hl(self.params, s.f_in_pad, 8 * s.Hp, src_off=s.oW, absmax=amax,
-                        r=self._planes('Wn%d' % si, s.f_in_pad, 8 * s.Hp),
-                        c=self._planes('Wt%d' % si, 8 * s.Hp, s.f_in_pad))
-        aside = (self._side is not None and main is not None and len(packed) > 1
-                 and os.environ.get('ASR_PACK_W_ASIDE', '1') != '0')
-        for k, (si, s) in enumerate(packed):
-            if k == 0 or not aside:
-                pack(si, s)
-        if aside:
-            start = torch.cuda.Event()
-            start.record(main)              # (the weights are final on the calling stream here)
-            with torch.cuda.stream(self._side):
-                self._side.wait_event(start)
-                for si, s in packed[1:]:
-                    pack(si, s)
-                    ev = torch.cuda.Event()
-                    ev.record(self._side)
-                    self._w_ready[si] = ev
-
-    def _await_weights(self, si):
-        """The calling stream waits for stage si's weight planes (packed on the side stream)."""
-        ev = getattr(self, '_w_ready', {}).pop(si, None)
-        if ev is not None:
-            torch.cuda.current_stream(self.device).wait_event(ev)
-
-    def _pack_input(self, si, s, a, BW, rows, n_pad, amax):
-        """The stage's input slab (rows, f_in_pad) [x B_W of each direction] -> (rows, f_in_pad)
-        planes: x@W reduces over their columns, dW = x^T dz over their rows (asr_gemm_hl's
-        k_major form reads them transposed out of LDS -- no second orientation is packed).
-        One entry per direction when masks are on, else one shared entry."""
-        r0 = self._planes('ar%d_0' % si, rows, s.f_in_pad)
-        if BW is None:
-            ops.pack_hl(a, rows, s.f_in_pad, absmax=amax, r=r0)
-            return [r0]
-        # both directions' planes in ONE pass over the slab (the source is read once)
-        r1 = self._planes('ar%d_1' % si, rows, s.f_in_pad)
-        ops.pack_hl(a, rows, s.f_in_pad, mask=BW[0], mask_period=n_pad, absmax=amax, r=r0,
-                    mask2=BW[1], r2=r1)
-        return [r0, r1]
-
-    def _gate_gemm_hl(self, s, si, pa, zx, rows):
-        """zx = (a (.) B_W) @ W + b from packed planes (both directions in one GEMM without
-        masks, one GEMM per direction with them)."""
-        Hp = s.Hp
-        self._await_weights(si)
-        Wt = self._planes('Wt%d' % si, 8 * Hp, s.f_in_pad)
-        bias = self._view(s.ob, 8 * Hp)
-        if len(pa) == 1:
-            ops.gemm_hl(pa[0], Wt, zx, rows, 8 * Hp, s.f_in_pad, bias=bias)
-            return
-        for d in range(2):
-            ops.gemm_hl(pa[d], Wt, zx, rows, 4 * Hp, s.f_in_pad, b_row=d * 4 * Hp,
-                        c_off=d * 4 * Hp, ldc=8 * Hp, bias=bias[d * 4 * Hp:(d + 1) * 4 * Hp])
+    # (the BiLSTM predicates of core/bilstm.py that tests and stages ask the model for)
+    _is_bilstm = staticmethod(bilstm.is_bilstm)
+    _stage_packed = bilstm.stage_packed
+    _recurrence_fills_chip = bilstm.recurrence_fills_chip
 
     # ------------------------------------------------------------------ forward
     def forward(self, x, training=False, masks=None, need_grad=True, n_valid=0, n_real=None,
@@ -502,18 +372,7 @@ class Model(object):
         a = x
         self._acts = []
         drawn = [None]
-        if self._overlap_mode == 'auto':
-            self.overlap = not self._recurrence_fills_chip(n_pad)
-        self._pipe_now = self._pipeline_on(n_pad)
-        # (the packed-operand GEMMs take whole slabs: no frame-range pipelining with them)
-        t_rec = self.out_frames(T)              # frames the recurrent stack sees
-        pipe = (self._pipe_now and self._pipe is not None and self.lstm_mode == 0 and t_rec >= 16
-                and not self.packed)
-        self._pipe_now = self._pipe_now and not self.packed
-        if n_valid == 1 and not need_grad:      # one utterance: the tile-free kernel, whole layers
-            pipe = False
-        if any(self._stage_packed(st) for st in self.stages):
-            self._pack_weights()
+        pipe = bilstm.begin_forward(self, T, n_pad, n_valid, need_grad)
         n_real = int(n_real or n_valid or n_pad)
         bn_weight = n_real if bn_weight is None else int(bn_weight)
 
@@ -533,120 +392,6 @@ class Model(object):
             rec = {'in': a}
             a = rec['out'] = KINDS[s.kind].forward(self, s, si, a, rec, fp)
             self._acts.append(rec)
-        return a
-
-    def _bilstm_forward(self, s, si, a, rec, fp):
-        """The BiLSTM entry of the stage table (core/stages.py): the input projection (whole, or
-        what the layer below has not projected already on the pipe stream), the recurrence, and
-        the next BiLSTM layer's projection of the frames that are final before its last steps."""
-        training, masks, need_grad, n_valid = fp.training, fp.masks, fp.need_grad, fp.n_valid
-        n_pad, pipe, pre, stage_masks = fp.n_pad, fp.pipe, fp.pre, fp.stage_masks
-        T = a.shape[0]                      # (a time-strided convolution shortens the slab)
-        rows = T * n_pad
-        S = (self._pipe_split16 * T) // 16
-        Hp = s.Hp
-        BW, BU = stage_masks(si)[:2]
-        rec['BW'], rec['BU'] = BW, BU
-        var = self._variant_args(s, si, T, n_pad, training, masks)
-        rec['var'] = var
-        if s.mi is None and s.ln is None:
-            zx = self._buf('zx%d_%d' % (fp.nb % 2, Hp), (T, n_pad, 2, 4 * Hp))
-        else:       # x@W is needed again by BPTT: one buffer per layer
-            zx = self._buf('zxmi%d' % si, (T, n_pad, 2, 4 * Hp))
-            rec['zx'] = zx
-        fp.nb += 1
-        main = torch.cuda.current_stream(self.device)
-        inner_done, halves = pre.pop(si, (None, False))
-        if self._stage_packed(s):
-            # |y| < 1 behind a BiLSTM stage with a bounded activation; anything else
-            # is measured
-            prev = self.stages[si - 1] if si > 0 else None
-            bound = self._clip_bound(si)
-            amax = self._const_one() if (prev is not None and self._y_bounded(prev)) \
-                else (bound if bound is not None
-                      else ops.absmax(a, self._buf('aamax%d' % si, (1,))))
-            rec['pa'] = self._pack_input(si, s, a, BW, rows, n_pad, amax)
-            self._gate_gemm_hl(s, si, rec['pa'], zx, rows)
-        elif inner_done is None:
-            self._gate_gemm(a, s, zx, BW, 0, rows, n_pad)
-        elif halves:
-            # frames [T-S, S) were projected while the previous layer ran, and of the
-            # others the half of the reduction that was final by then (below): what is
-            # left on the critical path is the other half of those frames
-            main.wait_event(inner_done)
-            # (r6) the two row ranges are independent and each is two launch-bound GEMMs
-            # of ~25 us: one range on the pipe stream (idle by now), the other here
-            fork = (self._pipe is not None
-                    and os.environ.get('ASR_PIPE_TAIL_FORK', '1') != '0')
-            if fork:
-                ev0 = torch.cuda.Event()
-                ev0.record(main)
-                with torch.cuda.stream(self._pipe):
-                    self._pipe.wait_event(ev0)
-                    self._gate_gemm_half(a, s, zx, BW, S * n_pad, rows, n_pad, 0, False)
-                    ev1 = torch.cuda.Event()
-                    ev1.record(self._pipe)
-                self._gate_gemm_half(a, s, zx, BW, 0, (T - S) * n_pad, n_pad, 1, False)
-                main.wait_event(ev1)
-            else:
-                self._gate_gemm_half(a, s, zx, BW, 0, (T - S) * n_pad, n_pad, 1, False)
-                self._gate_gemm_half(a, s, zx, BW, S * n_pad, rows, n_pad, 0, False)
-        else:       # frames [T-S, S) were projected while the previous layer ran
-            self._gate_gemm(a, s, zx, BW, 0, (T - S) * n_pad, n_pad)
-            self._gate_gemm(a, s, zx, BW, S * n_pad, rows, n_pad)
-            main.wait_event(inner_done)
-        # (the single-utterance kernel writes row 0 only: no junk in the padding rows)
-        one = n_valid == 1 and not need_grad
-        y = self._buf('y%d' % si, (T, n_pad, 2 * Hp), zero=one)
-        cell = self._buf('cell%d' % si, (T, n_pad, 2, Hp), zero=one)
-        gates = self._buf('gates%d' % si, (T, n_pad, 2, 4 * Hp), zero=one)
-        U = self._view(s.oU, 2 * Hp * 4 * Hp)
-        nxt = self.stages[si + 1] if si + 1 < len(self.stages) else None
-        if s.ln is not None:        # generic row-per-workgroup cell (csrc/lstm_ln.hip)
-            uh = self._buf('uh%d' % si, (T, n_pad, 2, 4 * Hp))
-            rec['uh'] = uh
-            ops.lstm_ln_seq_fwd(zx, U, self._view(s.ocell, 68 * Hp), uh, y, cell, gates, T,
-                                n_pad, Hp, has_mi=s.mi is not None, mask_u=BU,
-                                zone_c=var.get('zone_c'), zone_h=var.get('zone_h'),
-                                act=s.act)
-        elif pipe and nxt is not None and self._is_bilstm(nxt) and not var \
-                and nxt.mi is None and nxt.ln is None:
-            # after S = 13T/16 steps the frames [T-S, S) of y are final in BOTH
-            # directions: the next layer's input projection of those frames runs
-            # on the pipe stream while this recurrence finishes its last steps
-            # (nothing runs beside the first S steps: the library's choice of geometry;
-            # the GEMMs of the next layer run beside the last T - S: sixteen units per
-            # workgroup there, i.e. the fewest CUs)
-            ops.lstm_seq_fwd(zx, U, y, cell, gates, T, n_pad, Hp, mask_u=BU,
-                             mode=self.lstm_mode, steps=(0, S))
-            ev = torch.cuda.Event()
-            ev.record(main)
-            zx_n = self._buf('zx%d_%d' % (fp.nb % 2, nxt.Hp), (T, n_pad, 2, 4 * nxt.Hp))
-            with torch.cuda.stream(self._pipe):
-                self._pipe.wait_event(ev)
-                BWn = stage_masks(si + 1)[0]
-                self._gate_gemm(y, nxt, zx_n, BWn, (T - S) * n_pad, S * n_pad, n_pad)
-                # (the next stage's input must be exactly [y_f, y_b] of this one)
-                halves = self._pipe_halves and nxt.f_in_pad == 2 * Hp
-                if halves:
-                    # x = [y_f, y_b]: after S steps y_f is final on the frames [0, T-S)
-                    # too and y_b on [S, T) -- their halves of the reduction
-                    # (+ bias) go ahead as well
-                    self._gate_gemm_half(y, nxt, zx_n, BWn, 0, (T - S) * n_pad, n_pad,
-                                         0, True)
-                    self._gate_gemm_half(y, nxt, zx_n, BWn, S * n_pad, rows, n_pad,
-                                         1, True)
-                done = torch.cuda.Event()
-                done.record(self._pipe)
-            pre[si + 1] = (done, halves)
-            rec['ws'] = ops.lstm_seq_fwd(zx, U, y, cell, gates, T, n_pad, Hp, mask_u=BU,
-                                         mode=self.lstm_mode, steps=(S, T - S), units=16)
-        else:
-            rec['ws'] = ops.lstm_seq_fwd(
-                zx, U, y, cell, gates, T, n_pad, Hp, mask_u=BU, mode=self.lstm_mode,
-                n_valid=n_valid if not need_grad else 0, **var)
-        rec.update(y=y, cell=cell, gates=gates)
-        a = y
         return a
 
     def _bn_update(self):
@@ -695,134 +440,6 @@ class Model(object):
                 lens = -(-np.asarray(lens) // st)
         return lens
 
-    def _recurrence_fills_chip(self, n_pad):
-        if self.device.type != 'cuda':
-            return False
-        if not hasattr(self, '_num_cu'):
-            self._num_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
-        widest = max([(st.Hp + 15) // 16 for st in self.stages if self._is_bilstm(st)] + [0])
-        return 2 * (n_pad // 16) * widest >= self._num_cu
-
-    def _bptt_compact(self, s, n_pad):
-        """True if stage s's BPTT may run in the compact geometry with GEMMs on the CUs it
-        leaves free (plain cell, persistent kernels, H = 256 / 512, at most half of the CUs)."""
-        if self._compact_mode == '0' or self.device.type != 'cuda' or self.lstm_mode != 0:
-            return False
-        if not self._is_bilstm(s) or s.mi is not None or s.ln is not None or s.Hp not in (256, 512):
-            return False
-        if s.zoneout_c > 0 or s.zoneout_h > 0 or s.act != 'tanh':
-            return False
-        if os.environ.get('ASR_LSTM_PREC', '1') == '0':
-            return False
-        if not hasattr(self, '_num_cu'):
-            self._num_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
-        if self._compact_mode == '1':
-            return True
-        return (self._recurrence_fills_chip(n_pad)
-                and 2 * (n_pad // 16) * (s.Hp // 32) <= self._num_cu // 2)
-
-    def _pipeline_on(self, n_pad):
-        if not self.overlap or self._pipeline_mode == '0':
-            return False
-        if self._pipeline_mode == '1':
-            return True
-        if not hasattr(self, '_num_cu'):
-            self._num_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
-        widest = max([(st.Hp + 15) // 16 for st in self.stages if self._is_bilstm(st)] + [0])
-        return 0 < 2 * (n_pad // 16) * widest <= self._num_cu // 2
-
-    def _variant_args(self, s, si, T, n_pad, training, masks):
-        """Keyword arguments of the optional cell variants for ops.lstm_seq_fwd (and, with
-        the backward extras added later, lstm_seq_bwd): {} for the plain cell."""
-        var = {}
-        if s.act != 'tanh' and s.ln is None:        # any other activation: the variant kernels
-            var['act'] = s.act
-        if s.mi is not None and s.ln is None:
-            var['mi'] = self._view(s.omi, 32 * s.Hp)
-            var['uh'] = self._buf('uh%d' % si, (T, n_pad, 2, 4 * s.Hp))
-        if s.zoneout_c > 0 or s.zoneout_h > 0:
-            if masks is not None and si in masks and len(masks[si]) == 4:
-                kc, kh = masks[si][2], masks[si][3]          # explicit (T, 2, Hp) coefficients
-            else:
-                def coef(level, name):
-                    if not (0 < level < 1):
-                        return None
-                    buf = self._buf('%s%d' % (name, si), (T, 2, s.Hp))
-                    if training:    # keep mask, shared over the batch, fresh every frame
-                        ops.dropout_masks(buf, level, 1.0, self.rng_seed,
-                                          4 * si + (2 if name == 'zonec' else 3), self._step)
-                    else:           # test phase: (h - h_prev) * (1 - level) + h_prev
-                        buf.fill_(1.0 - level)
-                    return buf
-                kc, kh = coef(s.zoneout_c, 'zonec'), coef(s.zoneout_h, 'zoneh')
-            if kc is not None:
-                var['zone_c'] = kc
-            if kh is not None:
-                var['zone_h'] = kh
-        return var
-
-    def _gate_gemm(self, a, s, zx, BW, r0, r1, n_pad):
-        """zx[r0:r1] = (a[r0:r1] (.) B_W) @ W + b over slab rows [r0, r1) (whole frames)."""
-        m, Hp = r1 - r0, s.Hp
-        if m <= 0:
-            return
-        # with multiplicative integration the bias enters inside the cell (z = alpha Wx Uh
-        # + beta1 Uh + beta2 Wx + b), so the projection is the bare product
-        bias = self._view(s.ob, 8 * Hp) if (s.mi is None and s.ln is None) else None
-        if BW is None:
-            ops.gate_gemm('fwd', m, n_pad, s.f_in_pad, 8 * Hp, self.params, s.oW, 8 * Hp, 8 * Hp,
-                          x=a, x_off=r0 * s.f_in_pad, bias=bias, zx=zx, z_off=r0 * 8 * Hp)
-            return
-        for d in range(2):      # each direction has its own input mask (two Keras layers)
-            ops.gate_gemm('fwd', m, n_pad, s.f_in_pad, 4 * Hp, self.params, s.oW + d * 4 * Hp,
-                          8 * Hp, 8 * Hp, x=a, x_off=r0 * s.f_in_pad,
-                          bias=None if bias is None else bias[d * 4 * Hp:(d + 1) * 4 * Hp],
-                          mask_w=BW[d], zx=zx, z_off=r0 * 8 * Hp + d * 4 * Hp)
-
-    def _gate_gemm_half(self, a, s, zx, BW, r0, r1, n_pad, half, first):
-        """One half of the reduction of the projection over slab rows [r0, r1): the input is
-        [y_f, y_b] of the BiLSTM stage below, half 0 = its forward direction's columns, 1 = the
-        backward direction's.  first: zx = partial + b, else zx += partial."""
-        m, Hp, kh = r1 - r0, s.Hp, s.f_in_pad // 2
-        if m <= 0:
-            return
-        bias = self._view(s.ob, 8 * Hp) if first else None
-        for d in (range(2) if BW is not None else (None,)):
-            n, c0 = (8 * Hp, 0) if d is None else (4 * Hp, d * 4 * Hp)
-            ops.gemm(a, self.params, zx, m, n, kh, lda=s.f_in_pad, ldb=8 * Hp, ldc=8 * Hp,
-                     a_off=r0 * s.f_in_pad + half * kh, b_off=s.oW + half * kh * 8 * Hp + c0,
-                     c_off=r0 * 8 * Hp + c0, beta=0.0 if first else 1.0,
-                     bias=None if bias is None else bias[c0:c0 + n],
-                     a_scale=None if d is None else BW[d], a_scale_period=n_pad,
-                     a_scale_off=half * kh, a_scale_ld=s.f_in_pad)
-
-    def _dx_gemm_dir(self, dz, s, dx, BW, r0, r1, n_pad, zmx, d, beta):
-        """Direction d's term of _dx_gemm over slab rows [r0, r1): dx = beta dx + B_W[d] (.)
-        (dz_d @ W_d^T)."""
-        m, Hp = r1 - r0, s.Hp
-        if m <= 0:
-            return
-        ops.gate_gemm('dgrad', m, n_pad, s.f_in_pad, 4 * Hp, self.params, s.oW + d * 4 * Hp,
-                      8 * Hp, 8 * Hp, mask_w=None if BW is None else BW[d], dz=dz,
-                      z_off=r0 * 8 * Hp + d * 4 * Hp, dz_absmax=zmx, dx=dx,
-                      dx_off=r0 * s.f_in_pad, dx_beta=beta)
-
-    def _dx_gemm(self, dz, s, dx, BW, r0, r1, n_pad, zmx):
-        """dx[r0:r1] = sum_d B_W[d] (.) (dz_d[r0:r1] @ W_d^T) over slab rows [r0, r1)."""
-        m, Hp = r1 - r0, s.Hp
-        if m <= 0:
-            return
-        if BW is None:
-            ops.gate_gemm('dgrad', m, n_pad, s.f_in_pad, 8 * Hp, self.params, s.oW, 8 * Hp,
-                          8 * Hp, dz=dz, z_off=r0 * 8 * Hp, dz_absmax=zmx, dx=dx,
-                          dx_off=r0 * s.f_in_pad)
-            return
-        for d in range(2):
-            ops.gate_gemm('dgrad', m, n_pad, s.f_in_pad, 4 * Hp, self.params, s.oW + d * 4 * Hp,
-                          8 * Hp, 8 * Hp, mask_w=BW[d], dz=dz, z_off=r0 * 8 * Hp + d * 4 * Hp,
-                          dz_absmax=zmx, dx=dx, dx_off=r0 * s.f_in_pad,
-                          dx_beta=0.0 if d == 0 else 1.0)
-
     def _draw_all_masks(self, n_pad):
         """Variational-dropout masks of every BiLSTM stage for one batch (core/models.py:265-266:
         one mask per batch and direction, constant over time, inverted scaling), from the
@@ -848,74 +465,9 @@ class Model(object):
     def backward(self, dlogits):
         """dlogits (T, n_pad, C) -> fills self.grads (raw, no l2, no clip)."""
         T, n_pad, _ = dlogits.shape
-        rows = T * n_pad
         da = dlogits
-        split = 'auto'
-        pending = []
-        if not hasattr(self, '_dz_free'):
-            self._dz_free = [None, None]
-
-        # ASR_AR_OVERLAP: auto (default) = per-layer asynchronous all-reduces beside the BPTT of
-        # the layers below ONLY while a recurrence leaves CUs free (cfg2: 64 of 256).  Where a
-        # recurrence fills the chip with no compact schedule (ASR_BPTT_COMPACT=0) its
-        # spin-waiting workgroups must all be resident, and an RCCL kernel that takes CUs first
-        # stalls the whole chain: there the gradients are reduced by ONE collective over the flat
-        # buffer after BPTT (110.6 MB: 0.6-2.5 ms of a ~40 ms step).  1 = always overlap, 0 = never.  The decision must be the SAME on every
-        # rank (mismatched collective sequences hang RCCL): it is taken on the rank-invariant
-        # reference shard pad16(ceil(n_global / world)), never on this rank's own n_pad -- the
-        # shards of a ragged last batch differ by one utterance and can straddle a multiple of 16.
-        # Round 6: the COMPACT backward schedule leaves half of the CUs to the side stream during
-        # every BPTT below the top layer, so the same per-layer collectives run there too: layer
-        # l + 1's bucket goes out on the communicator's stream once its weight-gradient GEMMs have
-        # finished on the side stream, i.e. beside the compact BPTT of layer l - 1 (the top
-        # layer's chip-filling BPTT comes first and has no collective beside it); what is left
-        # for the end of the step is the bottom layer + Dense + the flag slots.  compact_any is
-        # a function of the reference shard as well.
-        ar_mode = os.environ.get('ASR_AR_OVERLAP', 'auto')
-        n_ref = self._ar_ref_pad if self._ar_ref_pad else n_pad
-        compact_any = any(self._bptt_compact(st, n_ref) for st in self.stages)
-        reduce_now = (self._dist_active() and ar_mode != '0'
-                      and (ar_mode == '1' or not self._recurrence_fills_chip(n_ref)
-                           or compact_any))
-        self._ar_covered = []
-        self._ar_decision = reduce_now
-
-        def reduce_async(lo, hi, after):
-            # this slice of the gradients is final once the work on stream `after` is done: its
-            # all-reduce (on the communicator's own stream) runs beside the BPTT of the layers below
-            from ..parallel import grad_comm
-            grad_comm(self.device).allreduce_after(self.grads[lo:hi], after)
-            self._ar_covered.append((lo, hi))
-
-        def flush_side():
-            # enqueue deferred weight-gradient work on the side stream (called right
-            # AFTER the next layer's BPTT kernel has been launched on the main stream)
-            while pending:
-                fn, ready, par, rng = pending.pop(0)
-                with torch.cuda.stream(self._side):
-                    self._side.wait_event(ready)
-                    fn('gemm_side')
-                    ev = torch.cuda.Event()
-                    ev.record(self._side)
-                    self._dz_free[par] = ev
-                if reduce_now and rng is not None:
-                    reduce_async(rng[0], rng[1], self._side)
-
-        # the side stream is in use if the recurrences leave CUs free by themselves (cfg2) or
-        # are made to (compact BPTT geometry, cfg3)
-        # (decided, like the collective schedule, on the RANK-INVARIANT reference shard: every
-        # rank then walks the same branches below, whatever its own shard of a ragged batch)
-        overlap = self.overlap or compact_any
-        self._compact_launches = 0
-        # split-K of the weight-gradient GEMMs that run beside a compact BPTT: sized to the CUs
-        # that are free there (ASR_SIDE_SLOTS, measurement switch; 0 = as on the whole chip)
-        side_slots = int(os.environ.get('ASR_SIDE_SLOTS', '0'))
-        split_side = ('auto:%d' % side_slots) if (compact_any and not self.overlap and side_slots) \
-            else split
-        bp = Pass(T=T, n_pad=n_pad, rows=rows, n_ref=n_ref, split=split, split_side=split_side,
-                  overlap=overlap, reduce_now=reduce_now, pending=pending,
-                  skip_grads={},        # stage index -> gradient to add to that stage's OUTPUT
-                  flush_side=flush_side, reduce_async=reduce_async, first=False)
+        # (the all-reduce decision and the side-stream queue of the weight gradients)
+        bp = bilstm.begin_backward(self, T, n_pad)
         for si in range(len(self.stages) - 1, -1, -1):
             s = self.stages[si]
             if si in bp.skip_grads:         # the residual branch rejoins here
@@ -924,287 +476,7 @@ class Model(object):
             bp.first = s.first
             dx = KINDS[s.kind].backward(self, s, si, self._acts[si], da, bp)
             da = dx if dx is not None else da
-        flush_side()
-        if overlap and self._side is not None:
-            torch.cuda.current_stream(self.device).wait_stream(self._side)
-        return da
-
-    def _bilstm_backward(self, s, si, rec, da, bp):
-        """The BiLSTM entry of the stage table (core/stages.py): BPTT, the dX GEMMs on the
-        critical path, and the weight-gradient GEMMs -- run here, or deferred in bp.pending to
-        run on the side stream beside the BPTT of the layer below (bp.flush_side())."""
-        T, n_pad, rows, n_ref, first = bp.T, bp.n_pad, bp.rows, bp.n_ref, bp.first
-        split, split_side, overlap, reduce_now = bp.split, bp.split_side, bp.overlap, bp.reduce_now
-        pending, flush_side, reduce_async = bp.pending, bp.flush_side, bp.reduce_async
-        a_in = rec['in']
-        Hp = s.Hp
-        BW, BU = rec['BW'], rec['BU']
-        # two dz buffers alternate so that the side stream may still read layer
-        # l's dz while layer l-1's BPTT writes the other one
-        par = self._dz_parity = 1 - getattr(self, '_dz_parity', 0)
-        dz = self._buf('dz%d' % par, (T, n_pad, 2, 4 * Hp))
-        main = torch.cuda.current_stream(self.device)
-        if overlap and self._dz_free[par] is not None:
-            main.wait_event(self._dz_free[par])
-        U = self._view(s.oU, 2 * Hp * 4 * Hp)
-        zmx = self._buf('dzmax%d' % par, (1,))
-        var = dict(rec.get('var') or {})
-        gsrc = dz                  # slab the dW / dX GEMMs read
-        pgrad = None               # (per-row parameter-gradient sums, rows, cols, offset)
-        if s.ln is not None:
-            gsrc = self._buf('dwx%d' % par, (T, n_pad, 2, 4 * Hp))
-            dpar = self._buf('dcellp%d' % si, (n_pad, 2, 34 * Hp))
-            pgrad = (dpar, n_pad, 68 * Hp, s.ocell)
-        elif s.mi is not None:
-            gsrc = self._buf('dwx%d' % par, (T, n_pad, 2, 4 * Hp))
-            dmi = self._buf('dmi%d' % si, (n_pad // 16, 2, 4, 4 * Hp))
-            var.update(wx=rec['zx'], dwx=gsrc, dmi=dmi)
-            pgrad = (dmi, n_pad // 16, 32 * Hp, s.omi)
-        else:
-            # plain cell: BPTT leaves the bias gradient as per-batch-tile sums of dz
-            # (accumulated in registers over the steps), so nothing re-reads the dz
-            # slab for it; the tiles are added up on the side stream
-            dbp = self._buf('dbpart%d' % si, (n_pad // 16, 2, 4 * Hp))
-            pgrad = (dbp, n_pad // 16, 8 * Hp, s.ob)
-        planes_now, pdz_r = False, None
-        pipe_b = (getattr(self, '_pipe_now', False) and self._pipe is not None
-                  and not first and self.lstm_mode == 0 and T >= 16 and not var
-                  and s.ln is None)
-        S = (self._pipe_split16 * T) // 16
-        dx = None
-        if pipe_b:
-            # after S BPTT steps the gate gradients of frames [T-S, S) are final
-            # in both directions: their dX GEMMs overlap the last steps
-            dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-            ops.lstm_seq_bwd(da, U, rec['cell'], rec['gates'], dz, T, n_pad, Hp,
-                             mask_u=BU, mode=self.lstm_mode, dz_absmax=zmx, steps=(0, S),
-                             db_part=pgrad[0])
-            ev = torch.cuda.Event()
-            ev.record(main)
-            flush_side()    # previous layer's dW/dU/db now overlap this BPTT
-            with torch.cuda.stream(self._pipe):
-                self._pipe.wait_event(ev)
-                self._dx_gemm(dz, s, dx, BW, (T - S) * n_pad, S * n_pad, n_pad, zmx)
-                if self._pipe_halves:
-                    # the forward direction's BPTT (frames T-1 .. 0) has also finished
-                    # [S, T), the backward direction's [0, T-S): their terms of dx
-                    self._dx_gemm_dir(dz, s, dx, BW, S * n_pad, rows, n_pad, zmx, 0, 0.0)
-                    self._dx_gemm_dir(dz, s, dx, BW, 0, (T - S) * n_pad, n_pad, zmx, 1,
-                                      0.0)
-                dx_inner = torch.cuda.Event()
-                dx_inner.record(self._pipe)
-            rec['ws_b'] = ops.lstm_seq_bwd(da, U, rec['cell'], rec['gates'], dz, T, n_pad,
-                                           Hp, mask_u=BU, mode=self.lstm_mode,
-                                           dz_absmax=zmx, steps=(S, T - S),
-                                           db_part=pgrad[0])
-        elif s.ln is not None:
-            ops.lstm_ln_seq_bwd(da, rec['zx'], U, self._view(s.ocell, 68 * Hp), rec['uh'],
-                                rec['y'], rec['cell'], rec['gates'], dz, gsrc, pgrad[0], T,
-                                n_pad, Hp, has_mi=s.mi is not None, mask_u=BU,
-                                zone_c=var.get('zone_c'), zone_h=var.get('zone_h'),
-                                act=s.act)
-            # one pre-scale for the gradient GEMMs: max over both gradient slabs
-            ops.absmax(dz, zmx)
-            tmp = ops.absmax(gsrc, self._buf('dzmax_t', (1,)))
-            torch.maximum(zmx, tmp, out=zmx)
-            flush_side()
-        else:
-            if s.mi is None:
-                var['db_part'] = pgrad[0]
-            # compact geometry only while there is work to run beside it (the top
-            # layer's BPTT has none: it keeps the whole chip and the shorter step)
-            cmp_now = bool(pending) and not self.overlap and self._bptt_compact(s, n_ref)
-            self._compact_launches += int(cmp_now)
-            # BPTT writes dz as packed planes itself where its kernel can (the plain cell
-            # at H = 256 / 512 on the two-dimensional-split kernels): the pack pass over
-            # the fp32 slab (2.1 GB per layer at cfg3) disappears.  The planes' scale has
-            # to be known before the pass: a per-layer bound kept at ~64 x the measured
-            # max|dz| by asr_lstm_dz_guard (hysteresis: identical inputs see identical
-            # scales); a layer without a bound yet -- first step, after a fault or new
-            # weights -- runs one MEASURING pass first (fp32 slab, discarded).
-            plain = not any(var.get(k) is not None
-                            for k in ('act', 'zone_c', 'zone_h', 'mi', 'uh'))
-            planes_now = (self._dz_planes_mode and self._stage_packed(s) and plain
-                          and self.lstm_mode == 0
-                          and ops.lstm_dz_hl_supported(T, n_pad, Hp, compact=cmp_now))
-            if planes_now:
-                pdz_r = self._planes('dzr%d' % par, rows, 8 * Hp)
-                bound = self._buf('dzbound%d' % si, (1,))
-                key = (self._fault_gen, self._weights_epoch)
-                if self._dz_bound_key.get(si) != key:
-                    bound.zero_()
-                    ops.lstm_seq_bwd(da, U, rec['cell'], rec['gates'], dz, T, n_pad, Hp,
-                                     mask_u=BU, mode=self.lstm_mode, dz_absmax=zmx,
-                                     compact=cmp_now, **var)
-                    ops.lstm_dz_guard(zmx, bound, False)
-                    self._dz_bound_key[si] = key
-                    self._dz_measure_passes += 1
-                rec['ws_b'] = ops.lstm_seq_bwd(
-                    da, U, rec['cell'], rec['gates'], None, T, n_pad, Hp, mask_u=BU,
-                    mode=self.lstm_mode, dz_absmax=zmx, compact=cmp_now,
-                    dz_planes=pdz_r, dz_bound=bound, **var)
-                ops.lstm_dz_guard(zmx, bound, True)
-            else:
-                rec['ws_b'] = ops.lstm_seq_bwd(
-                    da, U, rec['cell'], rec['gates'], dz, T, n_pad, Hp, mask_u=BU,
-                    mode=self.lstm_mode, dz_absmax=zmx, compact=cmp_now, **var)
-            flush_side()    # previous layer's dW/dU/db now overlap this BPTT
-        y = rec['y']
-        hl = self._stage_packed(s)
-        if hl and not planes_now:
-            # dz -> (rows, 8H) planes, once: dX reduces over their gate columns, the
-            # weight gradients over their rows (k_major); the scale is the BPTT kernel's
-            # own max|dz|
-            pdz_r = self._planes('dzr%d' % par, rows, 8 * Hp)
-            ops.pack_hl(dz, rows, 8 * Hp, absmax=zmx, r=pdz_r)
-        # bound of |y| for its planes (dU): 1 behind a bounded activation, else measured
-        # (here, on the main stream, before the side stream's packs read it)
-        ymx = self._const_one() if (not hl or self._y_bounded(s)) \
-            else ops.absmax(y, self._buf('yamax%d' % si, (1,)))
-
-        def grads_U_hl(wsn, s=s, y=y, BU=BU, Hp=Hp, pdz_r=pdz_r, ymx=ymx):
-            # dU[d] = (h_prev (.) B_U)^T dz[d], reduced over the plane rows; h_prev = y
-            # one frame earlier in the direction's processing order = a row offset
-            kk = (T - 1) * n_pad
-            for d in range(2):
-                if kk <= 0:
-                    self._gview(s.oU + d * Hp * 4 * Hp, Hp * 4 * Hp).zero_()
-                    continue
-                # (one pair of buffers per stream: the bottom layer's gradients run on
-                # the main stream while the side stream may still read its own pair)
-                yu = self._planes('yu%d%s' % (d, '' if wsn == 'gemm_side' else '_m'),
-                                  rows, Hp)
-                ops.pack_hl(y, rows, Hp, ld=2 * Hp, src_off=d * Hp,
-                            mask=None if BU is None else BU[d], mask_period=n_pad,
-                            absmax=ymx, r=yu)
-                ops.gemm_hl(yu, pdz_r, self.grads, Hp, 4 * Hp, kk,
-                            a_row=0 if d == 0 else n_pad, b_k=d * 4 * Hp,
-                            b_row=n_pad if d == 0 else 0, c_off=s.oU + d * Hp * 4 * Hp,
-                            split_k=split_side if wsn == 'gemm_side' else split,
-                            ws_name=wsn, k_major=True)
-
-        def grads_W_hl(wsn, s=s, pa=rec.get('pa'), Hp=Hp, pdz_r=pdz_r, pgrad=pgrad):
-            sp = split_side if wsn == 'gemm_side' else split
-            if len(pa) == 1:
-                ops.gemm_hl(pa[0], pdz_r, self.grads, s.f_in_pad, 8 * Hp, rows,
-                            c_off=s.oW, split_k=sp, ws_name=wsn, k_major=True)
-            else:
-                for d in range(2):
-                    ops.gemm_hl(pa[d], pdz_r, self.grads, s.f_in_pad, 4 * Hp, rows,
-                                b_k=d * 4 * Hp, c_off=s.oW + d * 4 * Hp, ldc=8 * Hp,
-                                split_k=sp, ws_name=wsn, k_major=True)
-            buf, nrow, ncol, goff = pgrad
-            ops.colsum(buf, nrow, ncol, ncol, self._gview(goff, ncol), ws_name=wsn + '_cs')
-
-        def grads_U(wsn, s=s, dz=dz, y=y, BU=BU, Hp=Hp, zmx=zmx):
-            # dU[d] = (h_prev (.) B_U)^T dz[d]: h_prev is y shifted by one step in
-            # the direction's processing order (zero at its first step)
-            kk = (T - 1) * n_pad
-            for d in range(2):
-                a_off = d * Hp + (0 if d == 0 else n_pad * 2 * Hp)
-                b_off = d * 4 * Hp + (n_pad * 8 * Hp if d == 0 else 0)
-                if kk > 0:
-                    ops.gemm(y, dz, self.grads, Hp, 4 * Hp, kk, trans_a=True, lda=2 * Hp,
-                             ldb=8 * Hp, ldc=4 * Hp, a_off=a_off, b_off=b_off,
-                             c_off=s.oU + d * Hp * 4 * Hp, split_k=split,
-                             a_scale=None if BU is None else BU[d],
-                             a_scale_period=n_pad, ws_name=wsn, b_absmax=zmx)
-                else:
-                    self._gview(s.oU + d * Hp * 4 * Hp, Hp * 4 * Hp).zero_()
-
-        def grads_W(wsn, s=s, dz=gsrc, a_in=a_in, BW=BW, Hp=Hp, zmx=zmx, pgrad=pgrad):
-            # dW = (x (.) B_W)^T d(x@W); the bias (or MI / LN parameter) gradients come
-            # from BPTT's per-tile partial sums, never from a pass over the dz slab
-            if BW is None:
-                ops.gate_gemm('wgrad', rows, n_pad, s.f_in_pad, 8 * Hp, self.params, s.oW,
-                              8 * Hp, 8 * Hp, x=a_in, dz=dz, dz_absmax=zmx,
-                              dW=self.grads, dw_off=s.oW, split_k=split, ws_name=wsn)
-            else:
-                for d in range(2):
-                    ops.gate_gemm('wgrad', rows, n_pad, s.f_in_pad, 4 * Hp, self.params,
-                                  s.oW + d * 4 * Hp, 8 * Hp, 8 * Hp, x=a_in,
-                                  mask_w=BW[d], dz=dz, z_off=d * 4 * Hp, dz_absmax=zmx,
-                                  dW=self.grads, dw_off=s.oW + d * 4 * Hp, split_k=split,
-                                  ws_name=wsn)
-            buf, nrow, ncol, goff = pgrad
-            ops.colsum(buf, nrow, ncol, ncol, self._gview(goff, ncol), ws_name=wsn + '_cs')
-
-        if hl:
-            grads_U, grads_W = grads_U_hl, grads_W_hl
-
-        def weight_grads(wsn, gu=grads_U, gw=grads_W):
-            gu(wsn)
-            gw(wsn)
-
-        if pipe_b and self._pipe_halves:
-            main.wait_event(dx_inner)
-            # (r6: two independent row ranges, one launch-bound GEMM each: two streams)
-            if os.environ.get('ASR_PIPE_TAIL_FORK', '1') != '0':
-                ev0 = torch.cuda.Event()
-                ev0.record(main)
-                with torch.cuda.stream(self._pipe):
-                    self._pipe.wait_event(ev0)
-                    self._dx_gemm_dir(dz, s, dx, BW, 0, (T - S) * n_pad, n_pad, zmx, 0, 1.0)
-                    ev1 = torch.cuda.Event()
-                    ev1.record(self._pipe)
-                self._dx_gemm_dir(dz, s, dx, BW, S * n_pad, rows, n_pad, zmx, 1, 1.0)
-                main.wait_event(ev1)
-            else:
-                self._dx_gemm_dir(dz, s, dx, BW, S * n_pad, rows, n_pad, zmx, 1, 1.0)
-                self._dx_gemm_dir(dz, s, dx, BW, 0, (T - S) * n_pad, n_pad, zmx, 0, 1.0)
-            da = dx
-        elif pipe_b:
-            self._dx_gemm(dz, s, dx, BW, 0, (T - S) * n_pad, n_pad, zmx)
-            self._dx_gemm(dz, s, dx, BW, S * n_pad, rows, n_pad, zmx)
-            main.wait_event(dx_inner)
-            da = dx
-        elif not first and hl:
-            dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-            Wn = self._planes('Wn%d' % si, s.f_in_pad, 8 * Hp)
-            if BW is None:
-                ops.gemm_hl(pdz_r, Wn, dx, rows, s.f_in_pad, 8 * Hp)
-            else:       # dx = sum_d B_W[d] (.) (dz_d @ W_d^T)
-                for d in range(2):
-                    ops.gemm_hl(pdz_r, Wn, dx, rows, s.f_in_pad, 4 * Hp, a_k=d * 4 * Hp,
-                                b_k=d * 4 * Hp, c_scale=BW[d], c_scale_period=n_pad,
-                                beta=0.0 if d == 0 else 1.0)
-            da = dx
-        elif not first:
-            dx = self._buf('da_s%d' % si, (T, n_pad, s.f_in_pad))
-            self._dx_gemm(gsrc, s, dx, BW, 0, rows, n_pad, zmx)
-            da = dx
-        # (compact schedule: is there a BiLSTM stage below whose BPTT this layer's
-        # weight gradients could run beside?  A convolution / Dense / nothing below:
-        # chip-filling GEMMs either way -- one stream, as in the serial schedule)
-        below = any(self._is_bilstm(st) for st in self.stages[:si])
-        if not overlap:
-            weight_grads('gemm')
-            if reduce_now and not first:
-                # no side stream (a recurrence fills the chip): this layer's gradients
-                # are final on the main stream; their all-reduce runs beside the layers
-                # below instead of after them all
-                reduce_async(s.p_lo, s.p_hi, main)
-        elif (first or not below) and not self.overlap:
-            # (compact schedule: the tail's GEMMs each fill the chip -- one stream)
-            weight_grads('gemm')
-            if reduce_now and not first:
-                reduce_async(s.p_lo, s.p_hi, main)
-            if not first:
-                da = dx
-        elif first:
-            # nothing left to hide behind: share the tail between both streams
-            ready = torch.cuda.Event()
-            ready.record(main)
-            pending.append((grads_U, ready, par, None))
-            flush_side()
-            grads_W('gemm')
-        else:
-            # the side stream starts once the dX GEMMs (critical path) are done,
-            # i.e. together with the next layer's BPTT kernel
-            ready = torch.cuda.Event()
-            ready.record(main)
-            pending.append((weight_grads, ready, par, (s.p_lo, s.p_hi)))
-            da = dx
+        bilstm.end_backward(self, bp)
         return da
 
     # ------------------------------------------------------------------ batches

@@ -33,9 +33,10 @@ use the same helpers.  A variant may stream where its kind does not:
 step handler ``(m, s, si, a, ss)``), and ``stream_variant(s)`` is what ``stream_check`` and
 ``StreamSession._encoder`` consult FIRST, before ``Kind.stream`` -- which stays None for 'bigru'.
 
-A new stage kind is one builder in params.py and one entry here.  The two BiLSTM bodies are the
-scheduled hot path (pipe and side streams, compact BPTT, packed planes, per-layer all-reduce) and
-stay in engine.py as ``Model._bilstm_forward`` / ``_bilstm_backward``; their entry calls them.
+A new stage kind is one builder in params.py and one entry here.  The two-direction LSTM stage is
+the scheduled hot path (pipe and side streams, compact BPTT, packed planes, per-layer all-reduce):
+its ``forward`` / ``backward`` are written like the handlers here but fill a module of their own,
+core/bilstm.py, with their helpers, predicates and switches; the 'bilstm' entry calls them.
 """
 import collections
 
@@ -748,19 +749,21 @@ def _bilstm_build(m, s, st, width):
 def _bilstm_forward(m, s, si, a, rec, fp, carry=None):
     if _nd(s) == 1:
         return _lstm_uni_forward(m, s, si, a, rec, fp, carry)
-    return m._bilstm_forward(s, si, a, rec, fp)
+    from . import bilstm        # (imports Pass and _nd from here)
+    return bilstm.forward(m, s, si, a, rec, fp)
 
 
 def _bilstm_backward(m, s, si, rec, da, bp):
     if _nd(s) == 1:
         return _lstm_uni_backward(m, s, si, rec, da, bp)
-    return m._bilstm_backward(s, si, rec, da, bp)
+    from . import bilstm
+    return bilstm.backward(m, s, si, rec, da, bp)
 
 
 # The unidirectional LSTM (K29, csrc/lstm_uni.hip): the one-direction variant of the kind, as the
 # unidirectional GRU is of 'bigru' (below).  None of the scheduled paths of the bidirectional
-# body (packed planes, pipe and side streams, compact BPTT) applies to it: engine.py asks
-# ``Model._is_bilstm`` (kind 'bilstm' AND two directions) wherever it decides one of them.  What
+# body (packed planes, pipe and side streams, compact BPTT) applies to it: bilstm.py asks its
+# ``is_bilstm`` (kind 'bilstm' AND two directions) wherever it decides one of them.  What
 # is here is the LSTM's own (the buffers, the recurrence, db); the GEMMs are the shared helpers'
 # (below) with one direction and G = 4 Hp.
 def _lstm_uni_build(m, s, st, width):

@@ -8,10 +8,10 @@ Floating-point digests are no safe pin across commits here (the CTC kernels and 
 accumulate with float atomics); what a pure engine refactor must keep exactly is this sequence.
 
 LIMIT: the recorder sees calls into ``asr_study_amd.ops`` only.  It does not see torch event
-records and stream waits (nor torch's own copies and fills).  For those the schedules rely on the
-BiLSTM bodies having been moved verbatim and on the bit-identity tests of the schedules, which
-pass unchanged: test_gpu_model.py, test_gpu_parallel.py and the pipelining tests of
-test_gpu_lstm.py."""
+records and stream waits (nor torch's own copies and fills).  Those of the BiLSTM schedule
+(core/bilstm.py) are pinned by test_gpu_bilstm_sched.py, whose recorder extends this one with the
+event and stream-wait lines and which also compares the bits; the schedules under a process group
+stay with the bit-identity tests of test_gpu_parallel.py."""
 import importlib.util
 import json
 import os

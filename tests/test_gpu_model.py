@@ -404,7 +404,7 @@ def test_brsmv1_packed_operand_gemm_path(use_masks, N, monkeypatch):
 
 
 def test_side_stream_is_used_only_where_a_gemm_can_run_beside_the_recurrence():
-    """ASR_OVERLAP=auto (engine.Model._recurrence_fills_chip): 5xBiLSTM(512) at batch 64 puts
+    """ASR_OVERLAP=auto (core/bilstm.py, recurrence_fills_chip): 5xBiLSTM(512) at batch 64 puts
     2 directions x 4 batch tiles x 32 workgroups = 256 recurrent workgroups on the 256 CUs and
     leaves no registers for a GEMM wave -> no side stream; BiLSTM(256) at batch 32 uses 64 CUs ->
     side stream on.  Same gradients either way (the switch only moves launches between streams)."""
@@ -429,7 +429,7 @@ def test_side_stream_is_used_only_where_a_gemm_can_run_beside_the_recurrence():
 
 
 def test_compact_bptt_schedule_runs_weight_gradients_beside_the_layer_below():
-    """ASR_BPTT_COMPACT=auto (engine.Model._bptt_compact): where a layer's BPTT would fill the chip
+    """ASR_BPTT_COMPACT=auto (core/bilstm.py, bptt_compact): where a layer's BPTT would fill the chip
     (5xBiLSTM(512) at batch 64: 256 workgroups) every layer BELOW the top one is launched in the
     compact geometry (asr_lstm_args.compact: 128 workgroups) with the weight-gradient GEMMs of
     the layer above on the side stream; the top layer has nothing to run beside it and keeps the
