@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libasr_hip.so')
-SOURCES = ['capi.cpp', 'ctc.hip', 'beam.hip', 'frontend.hip', 'conv.hip', 'gemm.hip', 'lstm.hip', 'lstm_fwd.hip', 'lstm_bwd.hip', 'lstm_ln.hip', 'lstm_uni.hip', 'rnn.hip',
+SOURCES = ['capi.cpp', 'ctc.hip', 'beam.hip', 'frontend.hip', 'conv.hip', 'gemm.hip', 'gemm_hl.hip', 'pack.hip', 'lstm.hip', 'lstm_fwd.hip', 'lstm_bwd.hip', 'lstm_ln.hip', 'lstm_uni.hip', 'rnn.hip',
            'batchnorm.hip', 'gru.hip', 'rhn.hip', 'layernorm.hip', 'attention.hip', 'rel_attention.hip', 'dwconv.hip',
            'specaug.hip', 'optim.hip', 'random.hip', 'decode_host.cpp', 'comm.cpp', 'roles.cpp']
 ARCH = 'gfx950'
@@ -22,6 +22,7 @@ STAMP = LIB + '.srchash'
 def _deps():
     return [os.path.join(CSRC, s) for s in SOURCES] + [
         os.path.join(CSRC, 'common.h'),
+        os.path.join(CSRC, 'gemm_common.h'),
         os.path.join(CSRC, 'lstm_common.h'),
         os.path.join(CSRC, 'rec_tile.h'),
         os.path.join(CSRC, 'vec4.h'),

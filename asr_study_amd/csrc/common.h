@@ -64,7 +64,7 @@ __device__ __forceinline__ float asr_wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
-// The power-of-two pre-scale of the packed split-fp16 planes (asr_pack_hl; gemm.hip's
+// The power-of-two pre-scale of the packed split-fp16 planes (asr_pack_hl; gemm_common.h's
 // pow2_scale): 2^(9 - e) with max = f * 2^e, f in [0.5, 1), i.e. max * scale in [2^8, 2^9);
 // 1 for a null pointer or a zero maximum.
 __device__ __forceinline__ float asr_pow2_scale(const float* absmax) {

@@ -215,7 +215,7 @@ Ws make_ws(const Geo& g) {
   return w;
 }
 
-// the power-of-two pre-scale of asr_pack_hl (gemm.hip, pow2_scale): max |x| -> [2^8, 2^9)
+// the power-of-two pre-scale of asr_pack_hl (gemm_common.h, pow2_scale): max |x| -> [2^8, 2^9)
 __device__ __forceinline__ float pow2_scale_of(const float* absmax) {
   if (absmax == nullptr) return 1.f;
   const unsigned b = __float_as_uint(*absmax);

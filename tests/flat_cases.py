@@ -1,6 +1,6 @@
 """The case table of the flat element-wise and reduction kernels: the optimiser (csrc/optim.hip),
 asr_axpby, asr_mul and the Philox kernels (csrc/random.hip), asr_activation_fwd/_bwd
-(csrc/rnn.hip), swish / GLU (csrc/dwconv.hip), asr_absmax and asr_colsum (csrc/gemm.hip).
+(csrc/rnn.hip), swish / GLU (csrc/dwconv.hip), asr_absmax and asr_colsum (csrc/pack.hip).
 
 They all have one shape: a launch capped at a fixed number of workgroups, a grid-stride loop, a
 16-byte fast path and a scalar tail.  GEOMETRY restates each launch (the comment names the line it
@@ -31,12 +31,12 @@ GEOMETRY = {
     # optim.hip asr_grad_norm(): grid_for(n) capped at kNormBlocks = 1024; a workgroup owns one
     # chunk (a multiple of 2048), a trip of its 256 threads is two float4 groups 1024 apart
     'norm': dict(blocks=1024, per_thread=8),
-    # gemm.hip asr_absmax(): (n / 4 + 255) / 256 in [1, 256]
+    # pack.hip asr_absmax(): (n / 4 + 255) / 256 in [1, 256]
     'absmax': dict(blocks=256, per_thread=4),
 }
 
 NORM_TRIP, NORM_HALF = 2048, 1024
-COLSUM_ROWS, COLSUM_MAX_SLICES, COLSUM_UNROLL = 128, 256, 16     # gemm.hip colsum_slices()
+COLSUM_ROWS, COLSUM_MAX_SLICES, COLSUM_UNROLL = 128, 256, 16     # pack.hip colsum_slices()
 
 
 def cap(kernel):
