@@ -148,17 +148,21 @@ static inline int splitk_workspace(const char* who, int splits, size_t rows, int
   return ASR_OK;
 }
 
-// More than 64 KB of dynamic LDS has to be asked for, once per kernel.
+// More than 64 KB of dynamic LDS has to be asked for, once per kernel AND device (the attribute
+// belongs to the device's copy of the function).
 static inline hipError_t set_dynamic_lds_once(const void* kernel, size_t bytes) {
   static std::mutex mu;
-  static const void* done[16];
-  static int n = 0;
+  static const void* done[16][16];
+  static int n[16] = {0};
+  int dev = 0;
+  const bool keyed = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16;
   std::lock_guard<std::mutex> lock(mu);
-  for (int i = 0; i < n; ++i)
-    if (done[i] == kernel) return hipSuccess;
+  if (keyed)
+    for (int i = 0; i < n[dev]; ++i)
+      if (done[dev][i] == kernel) return hipSuccess;
   const hipError_t e =
       hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e == hipSuccess && n < 16) done[n++] = kernel;
+  if (e == hipSuccess && keyed && n[dev] < 16) done[dev][n[dev]++] = kernel;
   return e;
 }
 

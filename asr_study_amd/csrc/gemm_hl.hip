@@ -586,6 +586,247 @@ gemm_hlx_kernel(HlSrc A, HlSrc B, int M, int N, int K, int k_per_split, int spli
 }
 
 
+// The DMA-staged tile walk of gemm_hlp_kernel<.., DMA = true>: the operands go from global memory
+// straight into LDS (buffer_load_dwordx4 ... lds), no staging registers, no ds_write pass.
+//
+// LDS image (tests/test_gemm_dma_layout_model.py is the model these expressions are copied from):
+// per buffer and operand [256 rows][128 bytes] -- a row's slab line, hi and lo planes together --
+// with the 16-byte chunk index XORed by (row >> 1) & 7.  One wave instruction writes 64 x 16 bytes
+// contiguously at M0, so the image is filled in 1 KB pieces of 8 rows and the swizzle sits on the
+// SOURCE side: lane p of piece P fetches row 8 P + (p >> 3), chunk (p & 7) ^ swizzle -- eight lanes
+// still read one whole 128-byte line.  A fragment lane reads (row, plane, reduction chunk fk) at
+// 128 row + 16 ((4 (fk >> 1) + 2 plane + (fk & 1)) ^ (row >> 1) & 7): conflict-free in the lane
+// groups ds_read_b128 is serviced in.  A wave stages four pieces of B (8 i + wave) and four of A
+// out of ITS OWN wave row's rows: two of the 64 rows read in half-step 0 (region A0), two of those
+// read in half-step 1 (A1) -- so an A region has one wave row as writer and reader, and only B is
+// shared across the stagger.
+//
+// Phase table of a step kt (local phases of a wave; the second wave row runs one barrier late, so
+// its phase p is global phase p + 1).  Buffer kt & 1 is the one this step reads AND restages:
+//   0  ds_read B[kt], A0[kt]; lgkmcnt(0)                                     barrier
+//   1  MFMAs of half 0;  issue A0[kt+2] (2 pieces: last read in phase 0 of this row, retired)   barrier
+//   2  ds_read A1[kt]; lgkmcnt(0); vmcnt(2): everything up to A1[kt+1] has landed -- B[kt+1],
+//      A0[kt+1], A1[kt+1] -- only this step's A0[kt+2] stays in flight                barrier
+//   3  MFMAs of half 1;  issue B[kt+2] (4), A1[kt+2] (2)                             barrier
+// Writes after reads: B[kt] is last read in global phase 4 kt + 1 (second row, retired before its
+// barrier) and restaged from global phase 4 kt + 3 on; A1[kt] is read in phase 2 and restaged in
+// phase 3 of the same row.  Reads after writes: slab kt + 1 is first read in global phase 4 kt + 4
+// (A regions: local phase 4 kt + 4 of the row that staged them); every wave has waited for its
+// pieces before its local barrier 4 kt + 3, i.e. global barrier 4 kt + 3 or 4 kt + 4, which every
+// reader has passed by then.  Loads fly for three phases (B, A1) and five (A0); the wait is never
+// vmcnt(0) inside the loop.  Raw s_barrier throughout: __syncthreads() would drain the DMAs.
+// The cursor is two slabs ahead, so the next tile's id must be known at step nk - 2: K >= 4 slabs.
+template <int WN, int MI, int NJ>
+__device__ __forceinline__ void hlp_dma_tiles(const HlSrc& A, const HlSrc& B, int M, int N, int K,
+                                              const Epilogue ep, float unscale,
+                                              unsigned* __restrict__ ctl, char* lds, int* mbox,
+                                              int vt) {
+  static_assert(WN == 4 && MI == 4 && NJ == 2, "the piece map is that of the 256 x 256 tile");
+  typedef __attribute__((address_space(3))) void* lds_ptr;
+  constexpr int TM2 = 64 * MI, TN2 = 32 * NJ * WN, RB = 2 * MI, CB = 2 * NJ;
+  constexpr int kImg = TM2 * 128;                               // one operand's slab image: 32 KB
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave / WN, wn = wave % WN;
+  const int TMc = (M + TM2 - 1) / TM2, TNc = (N + TN2 - 1) / TN2, total = TMc * TNc;
+  const int xcd = (int)(blockIdx.x % 8u);
+  const int nk = (K + HBK - 1) / HBK;
+
+  // ---- load cursor: tile, slab lkt of it; uniform except one offset per operand
+  const int l8 = lane >> 3;
+  const int cs = (lane & 7) ^ ((l8 >> 1) | ((wn & 1) << 2));    // the line chunk this lane fetches
+  const int kq = 16 * (cs >> 2) + 8 * (cs & 1);
+  const unsigned pitchA = (unsigned)A.ld * 4u, pitchB = (unsigned)B.ld * 4u;
+  const unsigned offA = (unsigned)l8 * pitchA + 16u * cs;
+  const unsigned offB = (unsigned)l8 * pitchB + 16u * cs;
+  auto pieceA = [&](int h, int q) { return wm * 16 + 8 * h + 4 * q + wn; };
+  auto pieceB = [&](int i) { return 8 * i + wave; };
+  __amdgpu_buffer_rsrc_t rsA, rsB;
+  int ra_left = 0, rb_left = 0, lkt = 0;
+  int v_nxt = total;
+  auto setup = [&](int v) {
+    if (v < total) {
+      const TileId t = tile_of_id(v, TMc, TNc, 1);
+      const unsigned ba = (unsigned)(t.tm * TM2) * pitchA;
+      const unsigned bb = (unsigned)(t.tn * TN2) * pitchB;
+      rsA = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<char*>(reinterpret_cast<const char*>(A.p)) + ba, 0, A.extent - ba, 0x00020000);
+      rsB = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<char*>(reinterpret_cast<const char*>(B.p)) + bb, 0, B.extent - bb, 0x00020000);
+      ra_left = M - t.tm * TM2;
+      rb_left = N - t.tn * TN2;
+    } else {                                     // past the last tile: every offset out of range
+      ra_left = 0;
+      rb_left = 0;
+    }
+  };
+  auto advance = [&]() {
+    if (++lkt == nk) {
+      lkt = 0;
+      setup(v_nxt);
+    }
+  };
+  // (rows past the operand and the reduction tail send the lane's offset out of range: zeros)
+  auto offs_a = [&](int h, unsigned (&o)[2]) {
+    const unsigned a0 = lkt * HBK + kq < K ? offA : kOob;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) o[q] = 8 * pieceA(h, q) + l8 < ra_left ? a0 : kOob;
+  };
+  auto offs_b = [&](unsigned (&o)[4]) {
+    const unsigned b0 = lkt * HBK + kq < K ? offB : kOob;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = 8 * pieceB(i) + l8 < rb_left ? b0 : kOob;
+  };
+  auto issue_a = [&](int h, const unsigned (&o)[2], char* img) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(
+          rsA, (lds_ptr)(img + 1024 * pieceA(h, q)), 16, o[q],
+          (unsigned)(8 * pieceA(h, q)) * pitchA + (unsigned)(lkt * HBK * 4), 0, 0);
+  };
+  auto issue_b = [&](const unsigned (&o)[4], char* img) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(
+          rsB, (lds_ptr)(img + kImg + 1024 * pieceB(i)), 16, o[i],
+          (unsigned)(8 * pieceB(i)) * pitchB + (unsigned)(lkt * HBK * 4), 0, 0);
+  };
+  rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(A.p), 0, A.extent, 0x00020000);
+  rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(B.p), 0, B.extent, 0x00020000);
+  setup(vt);
+
+  f32x4 am[RB][CB];
+#pragma unroll
+  for (int i = 0; i < RB; ++i)
+#pragma unroll
+    for (int j = 0; j < CB; ++j) am[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // ---- prologue: slabs 0 and 1 whole (K >= 4 slabs: the cursor stays in this tile)
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    unsigned o0[2], o1[2], ob[4];
+    offs_a(0, o0);
+    offs_a(1, o1);
+    offs_b(ob);
+    char* img = lds + s * 2 * kImg;
+    issue_a(0, o0, img);
+    issue_b(ob, img);
+    issue_a(1, o1, img);
+    if (s == 0) ++lkt;
+  }
+  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");              // slab 0 has landed
+  __builtin_amdgcn_s_barrier();
+  const int frow = lane & 15, fk = lane >> 4;
+  // fragment byte within the image, hi plane; the lo plane is 32 bytes (two chunks) away
+  const int fro = 128 * frow + 16 * (((4 * (fk >> 1) + (fk & 1)) ^ (frow >> 1)) & 7);
+  const int frl = fro ^ 32;
+  TileId tc = tile_of_id(vt, TMc, TNc, 1);
+  int m0 = tc.tm * TM2, n0 = tc.tn * TN2;
+  unsigned pending = 0u;
+  int ti = 0, kt = 0, cur = 0;
+  if (wm == 1) __builtin_amdgcn_s_barrier();      // the second wave row runs one barrier late
+  for (;;) {
+    if (kt == 0) {
+      if (tid == 0) pending = atomicAdd(&ctl[xcd], 1u);
+    } else if (kt == 1) {
+      if (tid == 0) mbox[(ti + 1) & 1] = (int)(pending * 8u) + xcd;
+    } else if (kt == 2) {
+      v_nxt = __builtin_amdgcn_readfirstlane(mbox[(ti + 1) & 1]);
+    }
+    advance();                                    // the cursor: slab kt + 2 (of the next tile)
+    char* img = lds + cur * 2 * kImg;
+    const char* fa = img + 128 * (wm * (32 * MI));
+    const char* fb = img + kImg + 128 * (wn * (32 * NJ));
+    hx8 fah[MI], fal[MI], fbh[CB], fbl[CB];
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      // ---- read phase
+      if (hf == 0) {
+#pragma unroll
+        for (int j = 0; j < CB; ++j) {
+          fbh[j] = *reinterpret_cast<const hx8*>(fb + 2048 * j + fro);
+          fbl[j] = *reinterpret_cast<const hx8*>(fb + 2048 * j + frl);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        fah[i] = *reinterpret_cast<const hx8*>(fa + 2048 * (hf * MI + i) + fro);
+        fal[i] = *reinterpret_cast<const hx8*>(fa + 2048 * (hf * MI + i) + frl);
+      }
+      unsigned oa[2], ob[4];
+      offs_a(hf, oa);
+      asm volatile("" : "+v"(oa[0]), "+v"(oa[1]));
+      if (hf == 1) {
+        offs_b(ob);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(ob[i]));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (hf == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      // ---- MFMA phase, this step's DMA pieces in its issue gaps
+      __builtin_amdgcn_s_setprio(1);
+      if (hf == 1) issue_b(ob, img);
+      issue_a(hf, oa, img);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < CB; ++j)
+          am[hf * MI + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbh[j], fal[i], am[hf * MI + i][j], 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < CB; ++j)
+          am[hf * MI + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbl[j], fah[i], am[hf * MI + i][j], 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < CB; ++j)
+          am[hf * MI + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbh[j], fah[i], am[hf * MI + i][j], 0, 0, 0);
+      if (hf == 0) {
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);               // MFMA
+          __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);                // VMEM: one piece
+        }
+      } else {
+#pragma unroll
+        for (int g = 0; g < 6; ++g) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+          __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    cur ^= 1;
+    if (++kt == nk) {
+      // ---- a finished tile: epilogue behind the closing barrier, accumulators back to zero
+      int fr = lane & 15, fq = lane >> 4;
+      asm volatile("" : "+v"(fr), "+v"(fq));
+      hlx_epilogue<MI, NJ, false>(am, ep, M, N, m0, n0, 0, unscale, wm, wn, fr, fq, TM2, TN2);
+#pragma unroll
+      for (int i = 0; i < RB; ++i)
+#pragma unroll
+        for (int j = 0; j < CB; ++j) am[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      kt = 0;
+      ++ti;
+      vt = v_nxt;
+      if (vt >= total) break;
+      tc = tile_of_id(vt, TMc, TNc, 1);
+      m0 = tc.tm * TM2;
+      n0 = tc.tn * TN2;
+    }
+  }
+  // the pieces issued past the last tile (out of range, zeros) must land before the LDS is given up
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (wm == 0) __builtin_amdgcn_s_barrier();
+}
+
 // PERSISTENT row-major form (gemm_hlp_kernel; round 6).  The 256 x 256 tile of the plain kernel
 // pays ~17 us per output tile around its K loop -- the dispatch of a new workgroup onto a CU whose
 // LDS and registers the previous one filled, a cold prologue (two dependent L2 / HBM round
@@ -605,7 +846,10 @@ gemm_hlx_kernel(HlSrc A, HlSrc B, int M, int N, int K, int k_per_split, int spli
 // second and read by all at the third (needs K >= 4 slabs).  ctl[8] counts finished workgroups
 // (atomicInc wraps it to 0); the last one clears ctl[0..7]: a control block is reusable by the
 // next launch without a memset.
-template <int WN, int MI, int NJ>
+// DMA = true: the same walk with the operands staged by LDS-DMA (hlp_dma_tiles above; its own LDS
+// image, cursor and K loop; tile hand-out, epilogue and every product as here).  The host picks the
+// instantiation per launch (ASR_GEMM_DMA); the register-staged one is the code below, unchanged.
+template <int WN, int MI, int NJ, bool DMA = false>
 __global__ void __launch_bounds__(128 * WN)
 gemm_hlp_kernel(HlSrc A, HlSrc B, int M, int N, int K, Epilogue ep,
                 const float* __restrict__ a_scale, const float* __restrict__ b_scale,
@@ -631,7 +875,10 @@ gemm_hlp_kernel(HlSrc A, HlSrc B, int M, int N, int K, Epilogue ep,
   __syncthreads();
   int vt = __builtin_amdgcn_readfirstlane(mbox[0]);          // the tile being multiplied
   int v_nxt = total;                                           // the one after it (known from kt = 2)
-  if (vt < total) {
+  if constexpr (DMA) {
+    if (vt < total)
+      hlp_dma_tiles<WN, MI, NJ>(A, B, M, N, K, ep, unscale, ctl, reinterpret_cast<char*>(hsm), mbox, vt);
+  } else if (vt < total) {
     // ---- load cursor: tile lv, slab lkt of it; everything uniform except the two offsets
     const int c8 = tid & 7, r8 = tid >> 3;
     const int kq = 16 * (c8 >> 2) + 8 * (c8 & 1);
@@ -803,21 +1050,39 @@ static int hlp_num_cu() {
 // still owns no device memory it had to ask for)
 constexpr int kHlpRing = 256, kHlpWords = 16;
 __device__ unsigned g_hlp_ctl[kHlpRing * kHlpWords];
-static unsigned* hlp_control_block() {
+// A slot belongs to the STREAM that first asked for one: launches of one stream run one after the
+// other and the kernel re-arms its block, so they can share it; launches of different streams
+// never do, however many are in flight.  (A round-robin over the ring handed a block out again
+// after kHlpRing launches whether or not its first user had finished.)  nullptr -- the plain
+// kernel runs -- once kHlpRing different streams of a device have asked.
+static unsigned* hlp_control_block(hipStream_t stream) {
   static unsigned* ring[16] = {nullptr};
-  static std::atomic<unsigned> next[16];
+  static hipStream_t owner[16][kHlpRing];
+  static int used[16] = {0};
   static std::mutex mu;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
+  std::lock_guard<std::mutex> lock(mu);
   if (!ring[dev]) {
-    std::lock_guard<std::mutex> lock(mu);
-    if (!ring[dev]) {
-      void* p = nullptr;
-      if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_hlp_ctl)) != hipSuccess || !p) return nullptr;
-      ring[dev] = reinterpret_cast<unsigned*>(p);
-    }
+    void* p = nullptr;
+    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_hlp_ctl)) != hipSuccess || !p) return nullptr;
+    ring[dev] = reinterpret_cast<unsigned*>(p);
   }
-  return ring[dev] + (size_t)(next[dev].fetch_add(1u) % kHlpRing) * kHlpWords;
+  int slot = 0;
+  while (slot < used[dev] && owner[dev][slot] != stream) ++slot;
+  if (slot == used[dev]) {
+    if (slot == kHlpRing) return nullptr;
+    owner[dev][used[dev]++] = stream;
+  }
+  return ring[dev] + (size_t)slot * kHlpWords;
+}
+// ASR_GEMM_DMA: 1 (the default: DESIGN.md 6) = the DMA-staged persistent form wherever the
+// persistent form runs, 0 = the register-staged one, 2 = the DMA-staged one for EVERY plain
+// row-major launch of the big tile with K >= 4 slabs, however few tiles (tests: small shapes)
+static int hlp_dma_mode() {
+  const char* v = getenv("ASR_GEMM_DMA");
+  if (!v || !*v) return 1;
+  return *v == '0' ? 0 : (*v == '2' ? 2 : 1);
 }
 
 extern "C" size_t asr_gemm_hl_workspace_bytes(const asr_gemm_hl_args* a) {
@@ -935,16 +1200,20 @@ extern "C" int asr_gemm_hl(const asr_gemm_hl_args* a, void* workspace, size_t ws
   // (bit-identical results: the switch changes time only)
   unsigned* ctl = nullptr;
   int grid_p = 0;
-  if (!km && !segd && splits == 1 && nbatch == 1 && big && a->K >= 5 * HBK && hlp_enabled()) {
+  // ASR_GEMM_DMA picks the staging of the persistent form (hlp_dma_mode; bit-identical as well)
+  const int dma = hlp_dma_mode();
+  if (!km && !segd && splits == 1 && nbatch == 1 && big && hlp_enabled() &&
+      a->K >= (dma ? 3 * HBK + 1 : 5 * HBK)) {
     const int ncu = hlp_num_cu();
     grid_p = ncu / 8 * 8;
-    if (grid_p >= 8 && total >= 2 * grid_p) ctl = hlp_control_block();
+    if (grid_p >= 8 && (total >= 2 * grid_p || dma == 2)) ctl = hlp_control_block(stream);
   }
   if (ctl) {
     const size_t shm_p = shm + 16;
-    ASR_CHECK_HIP(set_dynamic_lds_once((const void*)gemm_hlp_kernel<4, 4, 2>, shm_p));
-    hipLaunchKernelGGL((gemm_hlp_kernel<4, 4, 2>), dim3(grid_p), dim3(512), shm_p, stream, A, B,
-                       a->M, a->N, a->K, ep, a->a_scale, a->b_scale, ctl);
+    auto kern_p = dma ? gemm_hlp_kernel<4, 4, 2, true> : gemm_hlp_kernel<4, 4, 2, false>;
+    ASR_CHECK_HIP(set_dynamic_lds_once((const void*)kern_p, shm_p));
+    hipLaunchKernelGGL(kern_p, dim3(grid_p), dim3(512), shm_p, stream, A, B, a->M, a->N, a->K, ep,
+                       a->a_scale, a->b_scale, ctl);
   } else {
     ASR_CHECK_HIP(set_dynamic_lds_once((const void*)kern[vi][vj], shm));
     hipLaunchKernelGGL(kern[vi][vj], dim3(total), dim3(big ? 512 : 256), shm, stream, A, B, a->M,
