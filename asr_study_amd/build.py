@@ -14,6 +14,7 @@ SOURCES = ['capi.cpp', 'ctc.hip', 'beam.hip', 'frontend.hip', 'conv.hip', 'gemm.
            'batchnorm.hip', 'gru.hip', 'rhn.hip', 'layernorm.hip', 'attention.hip', 'rel_attention.hip', 'dwconv.hip',
            'specaug.hip', 'optim.hip', 'random.hip', 'decode_host.cpp', 'comm.cpp', 'roles.cpp']
 ARCH = 'gfx950'
+HEADER = os.path.join(os.path.dirname(HERE), 'include', 'asr_hip.h')   # _lib.py reads it too
 
 
 STAMP = LIB + '.srchash'
@@ -29,7 +30,7 @@ def _deps():
         os.path.join(CSRC, 'attn_tile.h'),
         os.path.join(CSRC, 'attn_core.h'),
         os.path.join(CSRC, 'philox.h'),
-        os.path.join(os.path.dirname(HERE), 'include', 'asr_hip.h')]
+        HEADER]
 
 
 def _source_hash():

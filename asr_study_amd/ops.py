@@ -281,7 +281,8 @@ def lstm_seq_bwd(dy, U, cell, gates, dz, T, n_pad, H, mask_u=None, mode=0, check
 
 # --------------------------------------------------------------------------- SimpleRNN (K14)
 # asr_rnn_args.activation: the SimpleRNN / Activation names this build runs
-RNN_ACTIVATIONS = {'tanh': 0, 'relu': 1, 'linear': 4, 'clipped_relu': 7}
+RNN_ACTIVATIONS = {'tanh': 0, 'relu': 1, 'linear': 4,
+                   'clipped_relu': L.CONSTANTS['ASR_ACT_CLIPPED_RELU']}
 RNN_WS = ('rnn_fwd', 'rnn_bwd')     # workspaces: sticky timeout word in their first bytes
 
 

@@ -184,7 +184,7 @@ def _decide_gpu_comm(device):
     try:
         import ctypes as C
         from . import _lib
-        buf = (C.c_char * 128)()
+        buf = (C.c_char * _lib.CONSTANTS['ASR_COMM_ID_BYTES'])()
         ok = 1 if _lib.load().asr_comm_unique_id(buf) == 0 else 0
     except Exception:
         ok = 0
@@ -299,7 +299,7 @@ class CapiComm(object):
         world = dist.get_world_size() if dist.is_initialized() else 1
         box = [None]
         if rank == 0:
-            buf = (C.c_char * 128)()
+            buf = (C.c_char * _lib.CONSTANTS['ASR_COMM_ID_BYTES'])()
             _lib.check(self._lib.asr_comm_unique_id(buf), 'asr_comm_unique_id')
             box[0] = bytes(buf)
         if world > 1:

@@ -26,9 +26,10 @@ def test_exports_every_declared_symbol(lib):
     header = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
     declared = set(re.findall(r'\b(asr_[a-z0-9_]+)\s*\(', header))
     assert len(declared) >= 20
+    # this scan is independent of the reader that SIGNATURES comes from: the two must agree
+    assert declared == set(L.SIGNATURES), sorted(declared ^ set(L.SIGNATURES))
     for name in sorted(declared):
         assert hasattr(lib, name), 'libasr_hip.so does not export %s' % name
-        assert name in L.SIGNATURES, 'no ctypes signature for %s' % name
     assert lib.asr_version() >= 100
 
 
@@ -109,66 +110,41 @@ def test_beam_search_host_tie_breaking_follows_creation_order():
 
 
 def test_ctypes_structs_match_the_header_layout(tmp_path):
-    """The argument structs of include/asr_hip.h are mirrored by hand in _lib.py: compile a
-    C program that prints sizeof / a few offsetof of every struct with gcc and compare with
-    ctypes (catches ABI drift when a field is added on one side only)."""
+    """The argument structs of _lib.py are computed from include/asr_hip.h by a reader of our own:
+    the C compiler is the independent judge of it.  A C program generated from the ctypes classes
+    prints sizeof of every struct and offsetof / sizeof of EVERY member; all must equal ctypes'
+    (a field the reader dropped, mistyped or misplaced moves an offset or the size)."""
     import ctypes as C
     import shutil
     import subprocess
-    from asr_study_amd import _lib
     gcc = shutil.which('gcc')
     if gcc is None:
         pytest.skip('no gcc')
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    classes = sorted((c for c in vars(L).values() if isinstance(c, type)
+                      and issubclass(c, C.Structure) and c is not C.Structure),
+                     key=lambda c: c.__name__)               # a class carries its header name
+    want, lines = {}, []
+    for c in classes:
+        s = c.__name__
+        want[s] = [C.sizeof(c)]
+        lines.append('  printf("%s %%zu", sizeof(%s));' % (s, s))
+        for f, _ in c._fields_:
+            want[s] += [getattr(c, f).offset, getattr(c, f).size]
+            lines.append('  printf(" %%zu %%zu", offsetof(%s, %s), sizeof(((%s*)0)->%s));'
+                         % (s, f, s, f))
+        lines.append('  printf("\\n");')
     src = tmp_path / 'layout.c'
-    src.write_text('''
-#include <stdio.h>
-#include <stddef.h>
-#include "asr_hip.h"
-int main(void) {
-  printf("frontend %zu %zu\\n", sizeof(asr_frontend_cfg), offsetof(asr_frontend_cfg, eps));
-  printf("gemm %zu %zu %zu\\n", sizeof(asr_gemm_args), offsetof(asr_gemm_args, bias),
-         offsetof(asr_gemm_args, b_absmax));
-  printf("lstm %zu %zu %zu %zu %zu\\n", sizeof(asr_lstm_args), offsetof(asr_lstm_args, dz_absmax),
-         offsetof(asr_lstm_args, step_begin), offsetof(asr_lstm_args, dmi),
-         offsetof(asr_lstm_args, db_part) + 1000 * offsetof(asr_lstm_args, n_valid));
-  printf("pack %zu %zu %zu\\n", sizeof(asr_pack_args), offsetof(asr_pack_args, scale_out),
-         offsetof(asr_pack_args, ldk_c));
-  printf("gemmhl %zu %zu %zu %zu\\n", sizeof(asr_gemm_hl_args), offsetof(asr_gemm_hl_args, b_scale),
-         offsetof(asr_gemm_hl_args, bias), offsetof(asr_gemm_hl_args, split_k) + 1000 * offsetof(asr_gemm_hl_args, tile));
-  printf("gemmhl2 %zu %zu %zu\\n", offsetof(asr_gemm_hl_args, a_seg_row), offsetof(asr_gemm_hl_args, a_batch_row),
-         offsetof(asr_gemm_hl_args, clamp_hi));
-  printf("conv %zu %zu %zu %zu %zu\\n", sizeof(asr_conv2d_args), offsetof(asr_conv2d_args, clip),
-         offsetof(asr_conv2d_args, y), offsetof(asr_conv2d_args, reuse_dz), offsetof(asr_conv2d_args, x_absmax));
-  printf("segment %zu %zu\\n", sizeof(asr_segment), offsetof(asr_segment, l2));
-  printf("lstmln %zu %zu %zu\\n", sizeof(asr_lstm_ln_args), offsetof(asr_lstm_ln_args, cellp),
-         offsetof(asr_lstm_ln_args, dparams));
-  printf("gate %zu %zu %zu %zu\\n", sizeof(asr_gate_gemm_args), offsetof(asr_gate_gemm_args, zx),
-         offsetof(asr_gate_gemm_args, dx_beta), offsetof(asr_gate_gemm_args, precision));
-  return 0;
-}
-''')
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "asr_hip.h"\n'
+                   'int main(void) {\n%s\n  return 0;\n}\n' % '\n'.join(lines))
     exe = tmp_path / 'layout'
-    subprocess.check_call([gcc, '-I', os.path.join(root, 'include'), str(src), '-o', str(exe)])
-    out = dict((ln.split()[0], [int(v) for v in ln.split()[1:]])
+    subprocess.check_call([gcc, '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)])
+    got = dict((ln.split()[0], [int(v) for v in ln.split()[1:]])
                for ln in subprocess.check_output([str(exe)]).decode().splitlines())
-    F, G, Ls, S = _lib.FrontendCfg, _lib.GemmArgs, _lib.LstmArgs, _lib.Segment
-    assert out['frontend'] == [C.sizeof(F), F.eps.offset]
-    assert out['gemm'] == [C.sizeof(G), G.bias.offset, G.b_absmax.offset]
-    assert out['lstm'] == [C.sizeof(Ls), Ls.dz_absmax.offset, Ls.step_begin.offset, Ls.dmi.offset,
-                           Ls.db_part.offset + 1000 * Ls.n_valid.offset]
-    P, GH = _lib.PackArgs, _lib.GemmHlArgs
-    assert out['pack'] == [C.sizeof(P), P.scale_out.offset, P.ldk_c.offset]
-    assert out['gemmhl'] == [C.sizeof(GH), GH.b_scale.offset, GH.bias.offset, GH.split_k.offset + 1000 * GH.tile.offset]
-    assert out['gemmhl2'] == [GH.a_seg_row.offset, GH.a_batch_row.offset, GH.clamp_hi.offset]
-    CV = _lib.Conv2dArgs
-    assert out['conv'] == [C.sizeof(CV), CV.clip.offset, CV.y.offset, CV.reuse_dz.offset,
-                           CV.x_absmax.offset]
-    assert out['segment'] == [C.sizeof(S), S.l2.offset]
-    LN = _lib.LstmLnArgs
-    assert out['lstmln'] == [C.sizeof(LN), LN.cellp.offset, LN.dparams.offset]
-    GG = _lib.GateGemmArgs
-    assert out['gate'] == [C.sizeof(GG), GG.zx.offset, GG.dx_beta.offset, GG.precision.offset]
+    for s in want:
+        assert got[s] == want[s], (s, got[s], want[s])
+    header = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'asr_hip.h')).read(),
+                    flags=re.S)
+    assert len(got) == len(want) == len(re.findall(r'\btypedef\s+struct\b', header)) >= 18
 
 
 def test_gemm_hl_argument_checks_need_no_gpu(lib):
