@@ -82,7 +82,9 @@ def save_model(model, filepath, meta=None, model_config=None):
     with h5lite.File(filepath, 'w') as f:
         f.attrs['keras_version'] = '1.2.2'
         g = f.create_group('model_weights')
-        layers = keras_layers(model, weights)
+        # (a TransducerModel names the layers of its two towers itself, under distinct prefixes)
+        layers = (model.keras_layers(weights) if hasattr(model, 'keras_layers')
+                  else keras_layers(model, weights))
         g.attrs.set_strings('layer_names', [name for name, _ in layers])
         for name, ws in layers:
             lg = g.create_group(name)

@@ -603,3 +603,55 @@ def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_lay
     _record_positions(model, positions)
     _record_context(model, context, causal_conv)
     return model
+
+
+def transducer(num_features=80, num_classes=28, encoder='lstm', num_hiddens=512, num_layers=5,
+               joint_dim=512, pred_hiddens=512, pred_layers=1, dropout=0.2, weight_decay=1e-4,
+               **encoder_kw):
+    """An RNN-Transducer (arXiv 1211.3711; core/transducer.py, csrc/rnnt.hip).  NO REFERENCE
+    COUNTERPART.  ``encoder``: 'lstm' (brsmv1's unidirectional stack), 'gru' (the unidirectional
+    deep_speech2 form) or 'conformer' (which takes ``context=`` and ``causal_conv=``), each with
+    its final Dense ``joint_dim`` wide instead of the classes; further keyword arguments go to
+    that factory (``bidirectional=True`` is allowed for training: only streaming needs a bounded
+    context).  The predictor is ``pred_layers`` bare LSTM(pred_hiddens), Dense(joint_dim), on the
+    one-hot rows of the label history; the joint is tanh(f_t + g_u) W_out + b_out over the
+    ``num_classes`` classes (blank last), like the CTC models' output."""
+    from .transducer import TransducerModel
+    kw = dict(encoder_kw)
+    device, seed = kw.pop('device', None), kw.pop('seed', 0)
+    decoder_kw = {k: kw.pop(k) for k in ('is_greedy', 'beam_width', 'merge_repeated', 'top_paths',
+                                         'lm', 'lm_alpha', 'lm_beta') if k in kw}
+    if joint_dim % 4:
+        raise ValueError('transducer: joint_dim %d must be a multiple of 4' % joint_dim)
+    common = dict(num_features=num_features, num_classes=joint_dim, device=device, seed=seed)
+    if encoder == 'lstm':
+        enc = brsmv1(num_hiddens=num_hiddens, num_layers=num_layers, dropout=dropout,
+                     weight_decay=weight_decay,
+                     **dict(dict(common, bidirectional=False), **kw))
+    elif encoder == 'gru':
+        enc = deep_speech2(num_hiddens=num_hiddens, num_layers=num_layers, dropout=dropout,
+                           weight_decay=weight_decay,
+                           **dict(dict(common, rnn_type='gru', bidirectional=False), **kw))
+    elif encoder == 'conformer':
+        enc = conformer(num_layers=num_layers, dropout=dropout, weight_decay=weight_decay,
+                        **dict(common, **kw))
+    else:
+        raise ValueError("transducer(encoder=%r): 'lstm', 'gru' or 'conformer'" % (encoder,))
+    classes = num_classes               # blank included (the last class), as in every factory
+    x = Input(name='labels_onehot', shape=(None, classes - 1))
+    o = x
+    for _ in range(pred_layers):
+        o = LSTM(pred_hiddens, return_sequences=True, consume_less='gpu', dropout_W=dropout,
+                 dropout_U=dropout, W_regularizer=l2(weight_decay),
+                 U_regularizer=l2(weight_decay))(o)
+    o = TimeDistributed(Dense(joint_dim, W_regularizer=l2(weight_decay)))(o)
+    o = TimeDistributed(Dense(classes, W_regularizer=l2(weight_decay)))(o)
+    pred = ctc_model(x, o, device=device, seed=seed + 1)
+    model = TransducerModel(enc, pred)
+    model.decoder = ctc_utils.decoder_config(**decoder_kw)
+    model.config = {'name': 'transducer', 'kwargs': dict(
+        num_features=num_features, num_classes=num_classes, encoder=encoder,
+        num_hiddens=num_hiddens, num_layers=num_layers, joint_dim=joint_dim,
+        pred_hiddens=pred_hiddens, pred_layers=pred_layers, dropout=dropout,
+        weight_decay=weight_decay, **kw)}
+    return model

@@ -1191,6 +1191,102 @@ def ctc_greedy_stream(logits, seq_len, state, N):
     return dec, dlen
 
 
+# --------------------------------------------------------------------------- transducer (K31)
+RNNT_MAX_J, RNNT_MAX_C, RNNT_MAX_LABELS = 512, 64, 255    # the limits of asr_rnnt_loss_grad
+
+
+def _check_i32(t, n):
+    assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= n, \
+        'expected a contiguous int32 CUDA tensor of at least %d words' % n
+
+
+def rnnt_loss_grad(enc, pred, W_out, b_out, labels, label_len, seq_len, N, J, grads=None,
+                   grad_scale=1.0, loss=None):
+    """The transducer loss (include/asr_hip.h K31) of enc (T, n_pad, Jp) and pred (U1, n_pad, Jp)
+    through the joint's output layer W_out (J, C), b_out (C); labels (N, U1 - 1) int32, label_len
+    and seq_len (N) int32, all on the device.  grads: None (loss only) or the four tensors
+    (d_enc, d_pred, dW_out, db_out), which are WRITTEN, scaled by grad_scale.  Returns loss (N)."""
+    lib = L.load()
+    T, n_pad, Jp = enc.shape
+    U1 = int(pred.shape[0])
+    J, Cc, N = int(J), int(b_out.numel()), int(N)
+    assert pred.shape[1:] == (n_pad, Jp) and Jp == (J + 3) // 4 * 4 and W_out.numel() == J * Cc
+    d = tuple(grads) if grads is not None else (None,) * 4
+    assert len(d) == 4
+    _check_f32(enc, pred, W_out, b_out, *d)
+    if d[0] is not None:
+        assert d[0].shape == enc.shape and d[1].shape == pred.shape
+        assert d[2].numel() == J * Cc and d[3].numel() == Cc
+    l_max = U1 - 1
+    if l_max:
+        _check_i32(labels, N * l_max)
+    _check_i32(label_len, N)
+    _check_i32(seq_len, N)
+    if loss is None:
+        loss = torch.empty(N, dtype=torch.float32, device=enc.device)
+    nbytes = lib.asr_rnnt_workspace_bytes(int(T), U1, N, int(n_pad), J, Cc)
+    ws = WS.get('rnnt', nbytes, enc.device)
+    L.check(lib.asr_rnnt_loss_grad(
+        _ptr(enc), _ptr(pred), _ptr(W_out), _ptr(b_out), _ptr(labels) if l_max else None,
+        _ptr(label_len), _ptr(seq_len), int(T), U1, N, int(n_pad), J, Cc, l_max,
+        float(grad_scale), _ptr(loss), _ptr(d[0]), _ptr(d[1]), _ptr(d[2]), _ptr(d[3]), _ptr(ws),
+        nbytes, _stream()), 'asr_rnnt_loss_grad')
+    return loss
+
+
+def rnnt_greedy_step(enc, g_cur, W_out, b_out, seq_len, N, J, t_ptr, n_sym, decoded, decoded_len,
+                     advance, x_next, active, max_symbols=10):
+    """One iteration of frame-synchronous greedy transducer decoding (asr_rnnt_greedy_step): enc
+    (T, n_pad, Jp), g_cur (n_pad, Jp) the predictor's current output; t_ptr, n_sym, decoded_len,
+    advance (N) and active (1) int32, decoded (N, cap) int32, x_next (n_pad, ld) float32 the next
+    predictor input, all on the device and updated in place."""
+    T, n_pad, Jp = enc.shape
+    J, Cc, N = int(J), int(b_out.numel()), int(N)
+    _check_f32(enc, g_cur, W_out, b_out, x_next)
+    assert g_cur.numel() >= n_pad * Jp and W_out.numel() == J * Cc
+    assert x_next.shape[0] >= N and decoded.shape[0] >= N
+    for t in (seq_len, t_ptr, n_sym, decoded_len, advance):
+        _check_i32(t, N)
+    _check_i32(decoded, N)
+    _check_i32(active, 1)
+    L.check(L.load().asr_rnnt_greedy_step(
+        _ptr(enc), _ptr(g_cur), _ptr(W_out), _ptr(b_out), _ptr(seq_len), int(T), N, int(n_pad),
+        J, Cc, int(max_symbols), int(decoded.shape[1]), int(x_next.shape[1]), _ptr(t_ptr),
+        _ptr(n_sym), _ptr(decoded), _ptr(decoded_len), _ptr(advance), _ptr(x_next), _ptr(active),
+        _stream()), 'asr_rnnt_greedy_step')
+
+
+def onehot_rows(labels, label_len, N, n_pad, width, out=None, ld=None):
+    """The predictor's input slab (U1, n_pad, ld) of labels (N, U1 - 1): position 0 (start of the
+    sequence) and the padding are zero rows, label y_u is the unit vector at position u
+    (asr_onehot_rows)."""
+    l_max = int(labels.shape[1])
+    ld = int(ld if ld is not None else width)
+    if out is None:
+        out = torch.empty((l_max + 1, int(n_pad), ld), dtype=torch.float32, device=labels.device)
+    _check_f32(out)
+    assert out.shape == (l_max + 1, int(n_pad), ld)
+    if l_max:
+        _check_i32(labels, int(N) * l_max)
+    _check_i32(label_len, int(N))
+    L.check(L.load().asr_onehot_rows(_ptr(labels) if l_max else None, _ptr(label_len), l_max + 1,
+                                     int(N), int(n_pad), l_max, int(width), ld, _ptr(out),
+                                     _stream()), 'asr_onehot_rows')
+    return out
+
+
+def rows_select(mask, a, b, out, N):
+    """out[n, :] = a[n, :] where mask[n] != 0 (n < N), b[n, :] elsewhere; out may be a or b
+    (asr_rows_select)."""
+    _check_f32(a, b, out)
+    assert a.shape == b.shape == out.shape and a.dim() == 2
+    _check_i32(mask, int(N))
+    L.check(L.load().asr_rows_select(_ptr(mask), _ptr(a), _ptr(b), _ptr(out), int(N),
+                                     int(a.shape[0]), int(a.shape[1]), _stream()),
+            'asr_rows_select')
+    return out
+
+
 # --------------------------------------------------------------------------- streaming (K26)
 def attn_stream_plan(window, max_tq):
     """Rows of the smallest [K | V] ring (a multiple of 64) that is valid for every call of up to

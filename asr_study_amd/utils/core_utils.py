@@ -104,6 +104,8 @@ def load_model(model_fname, return_meta=False, mode='train', **kwargs):
                     lm_beta=kwargs.get('lm_beta', 0.0), **model.decoder)
         else:                       # predict.py --no_decoder: the network output itself
             model.decoder = None
+        if getattr(model, 'greedy_only', False) and model.decoder is not None:
+            model.decoder = dict(is_greedy=True)    # (a TransducerModel has no beam search yet)
         model.metrics_names = ['loss', 'ctc_loss', 'beam_search_loss', 'beam_search_ler']
     if return_meta:
         return model, load_meta(model_fname)

@@ -67,7 +67,9 @@ const char* asr_last_error(void);
  * asr_frontend_cfg.norm_mode (the former `reserved`, same layout) and the
  * asr_frontend_stream* entry points (K30): additions only -- but the field is
  * now READ: a caller that left `reserved` uninitialised must set it to 0,
- * any value other than 0 or 1 is ASR_ERR_INVALID. */
+ * any value other than 0 or 1 is ASR_ERR_INVALID;
+ * asr_rnnt_workspace_bytes, asr_rnnt_loss_grad, asr_rnnt_greedy_step, asr_onehot_rows and
+ * asr_rows_select (K31: plain scalar arguments, additions only). */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -1246,6 +1248,64 @@ int asr_specaug_apply(const float* in, float* out, const int* lens, int T, int N
                       int F, int ld, int W, int mF, int Fw, int mT, int Tw, float p,
                       float mask_value, uint64_t seed, uint32_t stream_id, uint32_t step,
                       int* params_out, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K31 RNN-Transducer (Graves, arXiv 1211.3711; csrc/rnnt.hip; no reference  */
+/* counterpart).  U1 = l_max + 1 label positions, position 0 = start of the  */
+/* sequence; blank = C - 1.  enc (T, n_pad, Jp), pred (U1, n_pad, Jp), Jp =  */
+/* J rounded up to 4, time-major float32; W_out (J, C) row-major, b_out (C). */
+/*   z(n,t,u,:) = tanh(enc(t,n,:) + pred(u,n,:)) W_out + b_out               */
+/*   lp = log_softmax(z);  alpha(0,0) = 0;  alpha(t,u) = logsumexp(          */
+/*     alpha(t-1,u) + lp_blank(t-1,u), alpha(t,u-1) + lp_{y_u}(t,u-1))       */
+/*   loss[n] = -(alpha(T_n-1,U_n) + lp_blank(T_n-1,U_n)), natural log, T_n = */
+/*   seq_len[n] clamped to 1 .. T, U_n = label_len[n] clamped to 0 .. l_max. */
+/* d_enc / d_pred (the shapes of enc / pred), dW_out, db_out = grad_scale *  */
+/* d sum_n loss_n / d(.), WRITTEN (not accumulated); d_enc is 0 at frames    */
+/* t >= T_n, d_pred at positions u > U_n, both in rows n >= N and in columns */
+/* >= J.  The four gradient pointers are all NULL (loss only) or all set.    */
+/* Rows n >= N of enc / pred are never read.  No float atomics: the same     */
+/* bits on every run.  The workspace needs no initialisation; it holds four  */
+/* floats per lattice cell and 256 partial (J + 1, 16 / 32 / 64) slabs of    */
+/* dW_out / db_out, never a (t, u, j) or (t, u, c) tensor.  alpha / beta are */
+/* re-centred on their anti-diagonal's maximum every 4 diagonals, the        */
+/* removed amount summed in float64.  ASR_ERR_INVALID before any device      */
+/* call: a NULL pointer, T outside 1 .. 1000000, J outside 1 .. 512, C       */
+/* outside 2 .. 64, l_max                                                    */
+/* outside 0 .. 255, U1 != l_max + 1, n_pad % 16 != 0 or < N (the size       */
+/* function returns 0 for those).                                            */
+/* ------------------------------------------------------------------------ */
+size_t asr_rnnt_workspace_bytes(int T, int U1, int N, int n_pad, int J, int C);
+int asr_rnnt_loss_grad(const float* enc, const float* pred, const float* W_out,
+                       const float* b_out, const int* labels, const int* label_len,
+                       const int* seq_len, int T, int U1, int N, int n_pad, int J, int C,
+                       int l_max, float grad_scale, float* loss, float* d_enc, float* d_pred,
+                       float* dW_out, float* db_out, void* workspace, size_t ws_bytes,
+                       asr_stream_t stream);
+/* One iteration of frame-synchronous greedy decoding for all utterances.    */
+/* Row n is active while t_ptr[n] < seq_len[n] (clamped to 0 .. T).  An      */
+/* active row evaluates the joint cell (enc(t_ptr[n], n, :), g_cur(n, :))    */
+/* and takes the first-max arg-max k.  k a label and n_sym[n] < max_symbols: */
+/* decoded[n, decoded_len[n]++] = k (dropped past cap), n_sym[n]++,          */
+/* advance[n] = 1, x_next(n, :) = e_k.  Otherwise (blank, or max_symbols     */
+/* labels already emitted in this frame): t_ptr[n]++, n_sym[n] = 0,          */
+/* advance[n] = 0.  x_next (n < N, ld_next >= C - 1 columns) is 0 elsewhere; */
+/* an ended row gets advance 0 and nothing else.  *active = the rows still   */
+/* active AFTER this call.  t_ptr, n_sym, decoded_len: device int32 (N),     */
+/* zeroed by the caller before the first call.                               */
+int asr_rnnt_greedy_step(const float* enc, const float* g_cur, const float* W_out,
+                         const float* b_out, const int* seq_len, int T, int N, int n_pad,
+                         int J, int C, int max_symbols, int cap, int ld_next, int* t_ptr,
+                         int* n_sym, int* decoded, int* decoded_len, int* advance,
+                         float* x_next, int* active, asr_stream_t stream);
+/* The predictor's input slab out (U1, n_pad, ld): row (u, n) = the unit     */
+/* vector of label y_u = labels[n, u - 1] for 1 <= u <= label_len[n], n < N, */
+/* within `width` columns; all other rows (u = 0, padding) and columns 0.    */
+int asr_onehot_rows(const int* labels, const int* label_len, int U1, int N, int n_pad,
+                    int l_max, int width, int ld, float* out, asr_stream_t stream);
+/* out[n, :] = mask[n] != 0 (n < N) ? a[n, :] : b[n, :] over (n_pad, width); */
+/* out may be a or b.                                                        */
+int asr_rows_select(const int* mask, const float* a, const float* b, float* out, int N,
+                    int n_pad, int width, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* K7  CTC loss + gradient.  Replaces core/ctc_utils.py:60-70 ->             */
