@@ -1,5 +1,6 @@
 // asr_gemm_hl: the split-fp16 GEMM on PACKED planes -- gemm_hlx_kernel (row-major, k-major and
-// segmented forms, two tiles) and the persistent row-major form gemm_hlp_kernel.  asr_pack_hl
+// segmented forms, two tiles), the DMA-staged k-major big tile gemm_hlt_dma_kernel and the
+// persistent row-major form gemm_hlp_kernel.  asr_pack_hl
 // (pack.hip) makes the planes; the split-K partials are reduced by gemm.hip's kernels.
 //
 // ===========================================================================
@@ -585,6 +586,245 @@ gemm_hlx_kernel(HlSrc A, HlSrc B, int M, int N, int K, int k_per_split, int spli
   hlx_epilogue<MI, NJ, SEG>(am, ep, M, N, m0, n0, tb.z, 1.f / (sa * sb), wm, wn, frow, fk, TM2, TN2);
 }
 
+// The DMA-staged K-MAJOR kernel: gemm_hlx_kernel<4, 4, 2, true> with its operands staged from
+// global memory straight into LDS (buffer_load_dwordx4 ... lds): the same eight 16-byte loads per
+// thread and slab, no staging registers, no ds_write_b128 pass.  Tiles, splits, batches, products,
+// their order per accumulator, the k permutation both operands share and the epilogue are those of
+// the register-staged kernel: results are BIT-IDENTICAL (tests/test_gpu_gemm_km_dma.py).
+//
+// LDS image (tests/test_gemm_km_dma_layout_model.py is the model these expressions are copied
+// from).  A slab row of an operand is 1 KB: 16 column groups of (16 hi, 16 lo) = 64 chunks of 16
+// bytes.  Per buffer and operand four REGIONS of [32 k][256 bytes]: region R holds column groups
+// 4 R .. 4 R + 3 -- for A the 64 columns wave row R >> 1 reads in half-step R & 1, for B the 64
+// columns of wave column R.  One wave instruction writes 64 x 16 bytes contiguously at M0, so a
+// region is filled in 1 KB pieces of four rows and the swizzle sits on the SOURCE side: lane p of
+// piece q fetches row 4 q + (p >> 4), chunk (p & 15) ^ ((row & 7) << 1) of the region's 16 --
+// sixteen lanes still read 256 contiguous bytes, an instruction eight whole lines.  A lane of
+// ds_read_b64_tr_b16 supplies row lane >> 2 (+ 16), four columns of group (gq, plane), at
+// 256 row + ((16 ((lane >> 1 & 1) ^ (row & 7) << 1) + 8 (lane & 1)) ^ (64 gq + 32 plane)): the
+// eight rows of a 32-lane half fall into the eight 32-byte windows of the bank row, no conflicts;
+// each lane receives the halfs HlLoaderT::fragment gives it.  A wave stages piece `wave` of B's
+// four regions and, out of ITS OWN wave row's columns, pieces wn and wn + 4 of region A0 (half-step
+// 0) and of A1 -- so an A region has one wave row as writer and reader, only B is shared across
+// the stagger, and all of a wave's pieces have q & 1 = wn & 1: one offset register per operand.
+// The scalar offset (the piece's rows, the region's columns, the slab) is outside the descriptor's
+// range check: rows past the reduction range and column groups past the operand are compares
+// that send the lane's offset out of range, and the DMA then stores zeros.
+//
+// Phase table of a step kt (local phases of a wave; the second wave row runs one barrier late, so
+// its phase p is global phase p + 1).  Buffer kt & 1 is the one this step reads AND restages:
+//   0  tr-read B[kt], A0[kt]; lgkmcnt(0)                                              barrier
+//   1  MFMAs of half 0;  issue A0[kt+2] (2 pieces: last read in phase 0 of this row, retired)   barrier
+//   2  tr-read A1[kt]; lgkmcnt(0); vmcnt(2): everything up to A1[kt+1] has landed -- B[kt+1],
+//      A0[kt+1], A1[kt+1] -- only this step's A0[kt+2] stays in flight                barrier
+//   3  MFMAs of half 1;  issue B[kt+2] (4), A1[kt+2] (2)                             barrier
+// Writes after reads: B[kt] is last read in global phase 4 kt + 1 (second row, retired before its
+// barrier) and restaged from global phase 4 kt + 3 on; A1[kt] is read in phase 2 and restaged in
+// phase 3 of the same row, A0[kt] read in phase 0 and restaged in phase 1.  Reads after writes:
+// slab kt + 1 is first read in global phase 4 kt + 4 (A regions: local phase 4 kt + 4 of the row
+// that staged them); every wave has waited for its pieces before the barrier that ends its local
+// phase 4 kt + 2, i.e. global phase 4 kt + 2 or 4 kt + 3, which every reader has passed by then.
+// Loads fly for three phases (B, A1) and five (A0); the wait is never vmcnt(0) inside the loop.
+// Raw s_barrier throughout: __syncthreads() would drain the DMAs.  Past the last slab of the range every lane is
+// out of range, so any number of slabs is computed correctly; the host sends ranges shorter than
+// kKmDmaMinSlabs -- the two slabs the prologue stages whole -- to the register-staged kernel.
+constexpr int kKmDmaMinSlabs = 2;
+template <int WN, int MI, int NJ>
+__global__ void __launch_bounds__(128 * WN)
+gemm_hlt_dma_kernel(HlSrc A, HlSrc B, int M, int N, int K, int k_per_split, int splits,
+                    Epilogue ep, const float* __restrict__ a_scale,
+                    const float* __restrict__ b_scale, HlSeg seg) {
+  static_assert(WN == 4 && MI == 4 && NJ == 2, "the piece map is that of the 256 x 256 tile");
+  typedef __attribute__((address_space(3))) void* lds_ptr;
+  typedef short s4 __attribute__((__vector_size__(4 * sizeof(short))));
+  constexpr int TM2 = 64 * MI, TN2 = 32 * NJ * WN, RB = 2 * MI, CB = 2 * NJ;
+  constexpr int kRegion = 32 * 256, kImg = 4 * kRegion;          // one operand's slab image: 32 KB
+  extern __shared__ __attribute__((aligned(16))) _Float16 hsm[];
+  char* lds = reinterpret_cast<char*>(hsm);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave / WN, wn = wave % WN;
+  const int nbatch = seg.batch > 1u ? (int)seg.batch : 1;
+  const TileId tb = tile_of_block((M + TM2 - 1) / TM2, (N + TN2 - 1) / TN2, splits * nbatch);
+  const int m0 = tb.tm * TM2, n0 = tb.tn * TN2;
+  const int zb = tb.z % nbatch;
+  const int k_begin = (tb.z / nbatch) * k_per_split;
+  int k_end = k_begin + k_per_split;
+  if (k_end > K) k_end = K;
+  const int depth = k_end - k_begin;
+  const int nk = (depth + HBK - 1) / HBK;
+  const float sa = a_scale ? *a_scale : 1.f, sb = b_scale ? *b_scale : 1.f;
+  if (nbatch > 1) {         // member zb: A shifted by its byte offset, C by zb x M rows
+    const unsigned o = seg.adj[zb];
+    A.p = reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(A.p) + o);
+    A.extent -= o;
+    ep.C += (size_t)zb * M * ep.ldc;
+  }
+
+  // ---- load cursor: slab lkt; uniform except one offset per operand
+  const int r4 = lane >> 4;
+  const int cs = (lane & 15) ^ ((((wn & 1) << 2) | r4) << 1);    // the region chunk this lane fetches
+  const unsigned pitchA = (unsigned)A.ld * 4u, pitchB = (unsigned)B.ld * 4u;
+  const unsigned offA = (unsigned)r4 * pitchA + 16u * cs;
+  const unsigned offB = (unsigned)r4 * pitchB + 16u * cs;
+  // (the tile's first slab and column: scalar, with the piece's rows and the region's columns)
+  const unsigned baseA = (unsigned)k_begin * pitchA + (unsigned)m0 * 4u;
+  const unsigned baseB = (unsigned)k_begin * pitchB + (unsigned)n0 * 4u;
+  const int ca_end = ((A.rows + 15) & ~15) - m0 - 16 * (cs >> 2);   // region column 64 R < this: in
+  const int cb_end = ((B.rows + 15) & ~15) - n0 - 16 * (cs >> 2);
+  const __amdgpu_buffer_rsrc_t rsA =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(A.p), 0, A.extent, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsB =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(B.p), 0, B.extent, 0x00020000);
+  int lkt = 0;
+  auto pieceA = [&](int q) { return wn + 4 * q; };               // of region 2 wm + h
+  // (rows past the reduction range and column groups past the operand: out of range -> zeros)
+  auto offs_a = [&](int h, unsigned (&o)[2]) {
+    const unsigned a0 = 64 * (2 * wm + h) < ca_end ? offA : kOob;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) o[q] = lkt * HBK + 4 * pieceA(q) + r4 < depth ? a0 : kOob;
+  };
+  auto offs_b = [&](unsigned (&o)[4]) {
+    const unsigned b0 = lkt * HBK + 4 * wave + r4 < depth ? offB : kOob;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = 64 * i < cb_end ? b0 : kOob;
+  };
+  auto issue_a = [&](int h, const unsigned (&o)[2], char* img) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(
+          rsA, (lds_ptr)(img + kRegion * (2 * wm + h) + 1024 * pieceA(q)), 16, o[q],
+          baseA + (unsigned)(lkt * HBK + 4 * pieceA(q)) * pitchA + 256u * (unsigned)(2 * wm + h), 0, 0);
+  };
+  auto issue_b = [&](const unsigned (&o)[4], char* img) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(
+          rsB, (lds_ptr)(img + kImg + kRegion * i + 1024 * wave), 16, o[i],
+          baseB + (unsigned)(lkt * HBK + 4 * wave) * pitchB + 256u * (unsigned)i, 0, 0);
+  };
+
+  f32x4 am[RB][CB];
+#pragma unroll
+  for (int i = 0; i < RB; ++i)
+#pragma unroll
+    for (int j = 0; j < CB; ++j) am[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // ---- prologue: slabs 0 and 1 whole
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    unsigned o0[2], o1[2], ob[4];
+    offs_a(0, o0);
+    offs_a(1, o1);
+    offs_b(ob);
+    char* img = lds + s * 2 * kImg;
+    issue_a(0, o0, img);
+    issue_b(ob, img);
+    issue_a(1, o1, img);
+    ++lkt;
+  }
+  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");              // slab 0 has landed
+  __builtin_amdgcn_s_barrier();
+  // fragment byte within a region: frx[2 gq + plane] for the lane's 8 bytes of group gq of a plane
+  // (an XOR of 64 gq + 32 plane on the group-0 hi-plane byte).  The transposing reads are written
+  // as assembly: behind the builtin the compiler cannot tell the image from the pieces still in
+  // flight and puts vmcnt(0) in front of every read phase.  Their results are waited for by the
+  // lgkmcnt(0) that closes the read phase, which the MFMAs cannot be moved across.
+  const int frow = lane >> 2;
+  const unsigned lds0 = (unsigned)(size_t)(lds_ptr)lds;
+  unsigned frx[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c)
+    frx[c] = lds0 + (unsigned)((256 * frow + 16 * (((lane >> 1) & 1) ^ ((frow & 7) << 1)) + 8 * (lane & 1)) ^
+                               (32 * c));
+  auto fragment = [&](unsigned region, int gq, int plane) {
+    const unsigned q = frx[2 * gq + plane] + region;
+    s4 t1, t2;
+    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(t1) : "v"(q) : "memory");
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:4096" : "=v"(t2) : "v"(q) : "memory");
+    const hx4 a = __builtin_bit_cast(hx4, t1), b = __builtin_bit_cast(hx4, t2);
+    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+  };
+  if (wm == 1) __builtin_amdgcn_s_barrier();      // the second wave row runs one barrier late
+  for (int kt = 0; kt < nk; ++kt) {
+    const unsigned bufo = (unsigned)(kt & 1) * 2u * kImg;
+    char* img = lds + bufo;                       // lkt = kt + 2: the slab this step restages
+    hx8 fah[MI], fal[MI], fbh[CB], fbl[CB];
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      // ---- read phase
+      if (hf == 0) {
+#pragma unroll
+        for (int j = 0; j < CB; ++j) {
+          fbh[j] = fragment(bufo + kImg + kRegion * wn, j, 0);
+          fbl[j] = fragment(bufo + kImg + kRegion * wn, j, 1);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        fah[i] = fragment(bufo + kRegion * (2 * wm + hf), i, 0);
+        fal[i] = fragment(bufo + kRegion * (2 * wm + hf), i, 1);
+      }
+      unsigned oa[2], ob[4];
+      offs_a(hf, oa);
+      asm volatile("" : "+v"(oa[0]), "+v"(oa[1]));
+      if (hf == 1) {
+        offs_b(ob);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(ob[i]));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (hf == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      // ---- MFMA phase, this step's DMA pieces in its issue gaps
+      __builtin_amdgcn_s_setprio(1);
+      if (hf == 1) issue_b(ob, img);
+      issue_a(hf, oa, img);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < CB; ++j)
+          am[hf * MI + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbh[j], fal[i], am[hf * MI + i][j], 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < CB; ++j)
+          am[hf * MI + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbl[j], fah[i], am[hf * MI + i][j], 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < CB; ++j)
+          am[hf * MI + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbh[j], fah[i], am[hf * MI + i][j], 0, 0, 0);
+      if (hf == 0) {
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);               // MFMA
+          __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);                // VMEM: one piece
+        }
+      } else {
+#pragma unroll
+        for (int g = 0; g < 6; ++g) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+          __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    ++lkt;
+  }
+  // the pieces issued past the last slab (out of range, zeros) must land before the LDS is given up
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (wm == 0) __builtin_amdgcn_s_barrier();
+  // ---- epilogue
+  hlx_epilogue<MI, NJ, false>(am, ep, M, N, m0, n0, tb.z, 1.f / (sa * sb), wm, wn, lane & 15,
+                              lane >> 4, TM2, TN2);
+}
+
 
 // The DMA-staged tile walk of gemm_hlp_kernel<.., DMA = true>: the operands go from global memory
 // straight into LDS (buffer_load_dwordx4 ... lds), no staging registers, no ds_write pass.
@@ -1084,6 +1324,13 @@ static int hlp_dma_mode() {
   if (!v || !*v) return 1;
   return *v == '0' ? 0 : (*v == '2' ? 2 : 1);
 }
+// ASR_GEMM_KM_DMA: 1 (the default: DESIGN.md 6) = gemm_hlt_dma_kernel wherever the big-tile k_major
+// kernel runs with at least kKmDmaMinSlabs slabs per split, 0 = the register-staged kernel
+// everywhere.  Read per call, like ASR_GEMM_DMA (bit-identical results: the switch changes time only)
+static bool km_dma_enabled() {
+  const char* v = getenv("ASR_GEMM_KM_DMA");
+  return !(v && *v == '0');
+}
 
 extern "C" size_t asr_gemm_hl_workspace_bytes(const asr_gemm_hl_args* a) {
   if (!a) return 0;
@@ -1215,8 +1462,14 @@ extern "C" int asr_gemm_hl(const asr_gemm_hl_args* a, void* workspace, size_t ws
     hipLaunchKernelGGL(kern_p, dim3(grid_p), dim3(512), shm_p, stream, A, B, a->M, a->N, a->K, ep,
                        a->a_scale, a->b_scale, ctl);
   } else {
-    ASR_CHECK_HIP(set_dynamic_lds_once((const void*)kern[vi][vj], shm));
-    hipLaunchKernelGGL(kern[vi][vj], dim3(total), dim3(big ? 512 : 256), shm, stream, A, B, a->M,
+    // the k_major big tile: DMA-staged (its own LDS image, 128 KB) unless switched off or the
+    // reduction range of a split is shorter than its prologue
+    const bool km_dma = km && big && kps >= kKmDmaMinSlabs * HBK && a->K >= kKmDmaMinSlabs * HBK &&
+                        km_dma_enabled();
+    const hlx_t kern_x = km_dma ? gemm_hlt_dma_kernel<4, 4, 2> : kern[vi][vj];
+    const size_t shm_x = km_dma ? (size_t)2 * 2 * 4 * 32 * 256 : shm;
+    ASR_CHECK_HIP(set_dynamic_lds_once((const void*)kern_x, shm_x));
+    hipLaunchKernelGGL(kern_x, dim3(total), dim3(big ? 512 : 256), shm_x, stream, A, B, a->M,
                        a->N, a->K, kps, splits, ep, a->a_scale, a->b_scale, seg);
   }
   ASR_CHECK_LAUNCH();
