@@ -718,6 +718,7 @@ lstm_bwd_kernel_x(LstmParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int unit_local, cw;
   if (!map_block(p, unit_local, cw)) return;
+  flush_f32_denormals();                           // zero partial sums stay zero under a tag bit
   const int unit = p.chain_begin + unit_local;
   const bool fast = chain_on_one_xcd(p, unit, cw, reinterpret_cast<int*>(lds));
   if (fast) bwd_body_x<TPW, true>(p, unit, cw, lds);
@@ -1305,6 +1306,7 @@ lstm_bwd_kernel_c(LstmParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int unit_local, cw;
   if (!map_block(p, unit_local, cw)) return;
+  flush_f32_denormals();                           // zero partial sums stay zero under a tag bit
   const int unit = p.chain_begin + unit_local;
   const bool fast = chain_on_one_xcd(p, unit, cw, reinterpret_cast<int*>(lds));
   if (fast) bwd_body_c<OT, true, EXACT, NBLK, PL>(p, unit, cw, lds);

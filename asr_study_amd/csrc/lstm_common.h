@@ -111,6 +111,23 @@ struct StepProf {
 __device__ __forceinline__ float hard_sigmoid(float x) {
   return fminf(fmaxf(0.2f * x + 0.5f, 0.f), 1.f);
 }
+// v_min_f32 / v_max_f32 / v_med3_f32 return an operand that is NOT a NaN, so the clamps of
+// hard_sigmoid and of the tanh forms turn a NaN pre-activation into the gates (0, 0, -1, 0),
+// c = 0, h = 0, where the reference's clip hands the NaN on -- a diverged layer would look healthy
+// from above.  The forward kernels therefore test a lane's pre-activations and its new cell state
+// (nan_lanes: one unordered compare per pair) and replace its outputs by NaN (poison: one select
+// each) BEHIND the unchanged arithmetic.  Both are inline asm on purpose: written in C++ the
+// selects are vectorised in pairs together with the gate arithmetic that feeds them, a
+// multiply-add loses its fusion and the bits of finite results move.
+__device__ __forceinline__ unsigned long long nan_lanes(float a, float b) {
+  unsigned long long m;
+  asm("v_cmp_u_f32_e64 %0, %1, %2" : "=s"(m) : "v"(a), "v"(b));
+  return m;
+}
+__device__ __forceinline__ void poison(unsigned long long lanes, float& x) {
+  const float qnan = __builtin_nanf("");
+  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(x) : "v"(x), "v"(qnan), "s"(lanes));
+}
 __device__ __forceinline__ float fast_tanh(float x) {
   // tanh(x) = (e^{2x}-1)/(e^{2x}+1); |abs err| ~ 1e-7, saturates cleanly.
   const float xc = fminf(fmaxf(x, -15.f), 15.f);
@@ -134,6 +151,16 @@ __device__ __forceinline__ unsigned tag_word(float v, unsigned tag) {
 __device__ __forceinline__ bool tags_ok(const u32x4& v, unsigned tag) {
   return ((v[0] & 1u) == tag) & ((v[1] & 1u) == tag) & ((v[2] & 1u) == tag) &
          ((v[3] & 1u) == tag);
+}
+// The specialised BPTT kernels add the gathered partial sums WITH their tag bit.  On a normal
+// number that is <= 1 ulp; on an exact zero (the partial sums of a sample without upstream
+// gradient: a padding row) a set tag bit is the denormal 2^-149, and the row's gate gradients
+// came out as a few 1e-45 instead of 0 from the first step with tag 1 on.  With fp32 denormals
+// flushed (MODE.FP_DENORM[1:0] = 0, for the rest of the wave's life; fp16 / fp64 stay as they
+// are) such a word adds as the zero it stands for: one scalar instruction per kernel, none per
+// step, and no bit of a result changes that was not itself a denormal.
+__device__ __forceinline__ void flush_f32_denormals() {
+  __builtin_amdgcn_s_setreg(1 | (4 << 6) | (1 << 11), 0u);      // hwreg(HW_REG_MODE, 4, 2)
 }
 template <bool FAST>
 __device__ __forceinline__ u32x4 xload(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off) {

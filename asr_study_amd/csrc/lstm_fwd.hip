@@ -162,15 +162,21 @@ __device__ __forceinline__ void fwd_body_h(const LstmParams& p, int chain, int w
       } else {
         z0 = a[0] + zx4.x; z1 = a[1] + zx4.y; z2 = a[2] + zx4.z; z3 = a[3] + zx4.w;
       }
-      const float gi = hard_sigmoid(z0);
-      const float gf = hard_sigmoid(z1);
-      const float gg = VAR ? act_apply(p.act, z2) : fast_tanh(z2);
-      const float go = hard_sigmoid(z3);
+      float gi = hard_sigmoid(z0);
+      float gf = hard_sigmoid(z1);
+      float gg = VAR ? act_apply(p.act, z2) : fast_tanh(z2);
+      float go = hard_sigmoid(z3);
       float cn = gf * c + gi * gg;
       if (VAR) cn = c + kc * (cn - c);              // zoneout of the cell state (:457-459)
       c = cn;
       float h = go * (VAR ? act_apply(p.act, c) : fast_tanh(c));
-      if (VAR) { h = hprev + kh * (h - hprev); hprev = h; }   // ... of the hidden state
+      if (VAR) h = hprev + kh * (h - hprev);        // ... of the hidden state
+      {   // a NaN the clamps above swallowed leaves as NaN (lstm_common.h)
+        const unsigned long long bad = nan_lanes(z0, z1) | nan_lanes(z2, z3) | nan_lanes(c, c);
+        poison(bad, gi); poison(bad, gf); poison(bad, gg); poison(bad, go);
+        poison(bad, c); poison(bad, h);
+      }
+      if (VAR) hprev = h;
       if (s + 1 < p.T) {
         const unsigned wtag = (unsigned)(s >> 1) & 1u;
         _Float16 ph, pl;
@@ -270,6 +276,12 @@ __device__ __forceinline__ CellFwd cell_forward(const f32x4& a, const float4& zx
   o.go = hard_sigmoid_nc(a[3] + zx4.w);
   o.c = __builtin_fmaf(o.gf, c_prev, o.gi * o.gg);
   o.h = o.go * tanh_nc(o.c);
+  {   // a NaN the clamps above swallowed leaves as NaN (lstm_common.h)
+    const unsigned long long bad = nan_lanes(a[0] + zx4.x, a[1] + zx4.y) |
+                                   nan_lanes(a[2] + zx4.z, a[3] + zx4.w) | nan_lanes(o.c, o.c);
+    poison(bad, o.gi); poison(bad, o.gf); poison(bad, o.gg); poison(bad, o.go);
+    poison(bad, o.c); poison(bad, o.h);
+  }
   o.hm = o.h * mask;
   return o;
 }

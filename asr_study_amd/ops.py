@@ -1136,10 +1136,15 @@ def lstm_profile(ws):
     return [[out[6 * w + i] for i in range(6)] for w in range(4)]
 
 
-def lstm_plan(T, n_pad, H, backward):
+def lstm_plan(T, n_pad, H, backward, mode=0, compact=False, units=0, activation=0):
+    """asr_lstm_plan for the form a call with these arguments would take (mode, compact,
+    fwd_units and activation of asr_lstm_args; the ASR_LSTM_* switches act as in a call)."""
     lib = L.load()
     a = L.LstmArgs()
-    a.T, a.n_pad, a.H = int(T), int(n_pad), int(H)
+    a.T, a.n_pad, a.H, a.mode = int(T), int(n_pad), int(H), int(mode)
+    a.compact = 1 if compact else 0
+    a.fwd_units = int(units)
+    a.activation = activation_id(activation)
     ks, r, blocks, cpl = C.c_int(), C.c_int(), C.c_int(), C.c_int()
     L.check(lib.asr_lstm_plan(C.byref(a), int(backward), C.byref(ks), C.byref(r),
                               C.byref(blocks), C.byref(cpl)), 'asr_lstm_plan')

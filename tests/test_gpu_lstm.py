@@ -8,47 +8,9 @@ import torch
 
 from oracle import lstm as OL
 from tests.gpu_util import (to_dev, pad_batch, report, gate_major_to_unit_major)
+from tests.lstm_cases import make_case as _case, oracle as _oracle, pack_inputs as _pack_inputs
 
 pytestmark = pytest.mark.gpu
-
-
-def _case(T, N, F, H, seed, use_mask):
-    rs = np.random.RandomState(seed)
-    x = rs.randn(T, N, F)
-    p = {d: OL.init_lstm(rs, F, H, np.float64) for d in ('fwd', 'bwd')}
-    for d in p:
-        p[d]['b'] = p[d]['b'] + rs.randn(4 * H) * 0.3
-        p[d]['U'] = p[d]['U'] * 0.8
-    masks = {d: None for d in p}
-    if use_mask:
-        masks = {d: ((rs.rand(N, H) > 0.2) / 0.8) for d in p}
-    return rs, x, p, masks
-
-
-def _oracle(x, p, masks, dhs=None):
-    out = {}
-    for d, rev in (('fwd', False), ('bwd', True)):
-        hs, cache = OL.lstm_forward(x, p[d]['W'], p[d]['U'], p[d]['b'], rev, None, masks[d])
-        out[d] = dict(hs=hs, cache=cache)
-        if dhs is not None:
-            OL.lstm_backward(dhs[d], cache)
-    return out
-
-
-def _pack_inputs(x, p, masks, H, n_pad):
-    T, N, F = x.shape
-    zx = np.zeros((T, n_pad, 2, 4 * H), np.float32)
-    U = np.zeros((2, H, 4 * H), np.float32)
-    mk = np.ones((2, n_pad, H), np.float32)
-    for di, d in enumerate(('fwd', 'bwd')):
-        z = x @ p[d]['W'] + p[d]['b']                     # (T,N,4H) gate-major
-        zx[:, :N, di] = gate_major_to_unit_major(z, H)
-        # padding rows get the bias only (x = 0), like the real pipeline
-        zx[:, N:, di] = gate_major_to_unit_major(p[d]['b'][None, None], H)
-        U[di] = gate_major_to_unit_major(p[d]['U'], H)
-        if masks[d] is not None:
-            mk[di, :N] = masks[d]
-    return zx, U, mk
 
 
 @pytest.mark.parametrize('T,N,F,H,mode,use_mask', [
