@@ -68,6 +68,7 @@ AttnArgs = _struct('asr_attn_args')
 RelAttnArgs = _struct('asr_relattn_args')
 AttnWindow = _struct('asr_attn_window')
 AttnStreamArgs = _struct('asr_attn_stream_args')
+AttnCrossArgs = _struct('asr_attn_cross_args')
 Segment = _struct('asr_segment')
 if _unnamed:
     raise AsrHipError('%s declares %s: give it a name above' % (HEADER, ', '.join(_unnamed)))

@@ -11,8 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libasr_hip.so')
 SOURCES = ['capi.cpp', 'ctc.hip', 'beam.hip', 'frontend.hip', 'conv.hip', 'gemm.hip', 'gemm_hl.hip', 'pack.hip', 'lstm.hip', 'lstm_fwd.hip', 'lstm_bwd.hip', 'lstm_ln.hip', 'lstm_uni.hip', 'rnn.hip',
-           'batchnorm.hip', 'gru.hip', 'rhn.hip', 'layernorm.hip', 'attention.hip', 'rel_attention.hip', 'dwconv.hip',
-           'specaug.hip', 'rnnt.hip', 'optim.hip', 'random.hip', 'decode_host.cpp', 'comm.cpp', 'roles.cpp']
+           'batchnorm.hip', 'gru.hip', 'rhn.hip', 'layernorm.hip', 'attention.hip', 'rel_attention.hip', 'cross_attention.hip', 'dwconv.hip',
+           'specaug.hip', 'rnnt.hip', 'aed.hip', 'optim.hip', 'random.hip', 'decode_host.cpp', 'comm.cpp', 'roles.cpp']
 ARCH = 'gfx950'
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'asr_hip.h')   # _lib.py reads it too
 
@@ -29,6 +29,7 @@ def _deps():
         os.path.join(CSRC, 'vec4.h'),
         os.path.join(CSRC, 'attn_tile.h'),
         os.path.join(CSRC, 'attn_core.h'),
+        os.path.join(CSRC, 'joint_common.h'),
         os.path.join(CSRC, 'philox.h'),
         HEADER]
 

@@ -655,3 +655,61 @@ def transducer(num_features=80, num_classes=28, encoder='lstm', num_hiddens=512,
         pred_hiddens=pred_hiddens, pred_layers=pred_layers, dropout=dropout,
         weight_decay=weight_decay, **kw)}
     return model
+
+
+def aed(num_features=80, num_classes=28, encoder='blstm', num_hiddens=512, num_layers=5,
+        d_att=256, num_heads=4, pred_hiddens=512, pred_layers=1, label_smoothing=0.0,
+        dropout=0.2, weight_decay=1e-4, **encoder_kw):
+    """An attention encoder-decoder (arXiv 1508.01211 with the multi-head attention of arXiv
+    1706.03762; core/aed.py, csrc/cross_attention.hip, csrc/aed.hip).  NO REFERENCE COUNTERPART:
+    the reference lists "Encoder-decoder models with attention mechanism" as TODO.  ``encoder``:
+    'blstm' (brsmv1, bidirectional: the persistent BiLSTM stack), 'lstm' (brsmv1's unidirectional
+    stack), 'gru' (deep_speech2 with rnn_type='gru'), 'conformer' or 'transformer', each with its
+    final Dense ``2 d_att`` wide: the [K | V] of the decoder's cross-attention; further keyword
+    arguments go to that factory.  The predictor is ``pred_layers`` bare LSTM(pred_hiddens),
+    Dense(d_att) = the queries, on the one-hot rows of the label history; the output layer is
+    tanh(ctx_u + q_u) W_out + b_out over the ``num_classes`` classes, EOS last (where the CTC
+    models have blank).  ``label_smoothing`` is the eps of the cross-entropy; ``max_labels``
+    (default 255) caps the greedy decode."""
+    from .aed import AttentionDecoderModel, MAX_LABELS
+    kw = dict(encoder_kw)
+    device, seed = kw.pop('device', None), kw.pop('seed', 0)
+    max_labels = kw.pop('max_labels', MAX_LABELS)
+    decoder_kw = {k: kw.pop(k) for k in ('is_greedy', 'beam_width', 'merge_repeated', 'top_paths',
+                                         'lm', 'lm_alpha', 'lm_beta') if k in kw}
+    common = dict(num_features=num_features, num_classes=2 * d_att, device=device, seed=seed)
+    if encoder in ('blstm', 'lstm'):
+        enc = brsmv1(num_hiddens=num_hiddens, num_layers=num_layers, dropout=dropout,
+                     weight_decay=weight_decay,
+                     **dict(dict(common, bidirectional=encoder == 'blstm'), **kw))
+    elif encoder == 'gru':
+        enc = deep_speech2(num_hiddens=num_hiddens, num_layers=num_layers, dropout=dropout,
+                           weight_decay=weight_decay, **dict(dict(common, rnn_type='gru'), **kw))
+    elif encoder in ('conformer', 'transformer'):
+        factory = conformer if encoder == 'conformer' else transformer
+        enc = factory(num_layers=num_layers, dropout=dropout, weight_decay=weight_decay,
+                      **dict(common, **kw))
+    else:
+        raise ValueError("aed(encoder=%r): 'blstm', 'lstm', 'gru', 'conformer' or 'transformer'"
+                         % (encoder,))
+    classes = num_classes               # EOS included (the last class), as blank in every factory
+    x = Input(name='labels_onehot', shape=(None, classes - 1))
+    o = x
+    for _ in range(pred_layers):
+        o = LSTM(pred_hiddens, return_sequences=True, consume_less='gpu', dropout_W=dropout,
+                 dropout_U=dropout, W_regularizer=l2(weight_decay),
+                 U_regularizer=l2(weight_decay))(o)
+    o = TimeDistributed(Dense(d_att, W_regularizer=l2(weight_decay)))(o)
+    o = TimeDistributed(Dense(classes, W_regularizer=l2(weight_decay)))(o)
+    pred = ctc_model(x, o, device=device, seed=seed + 1)
+    model = AttentionDecoderModel(enc, pred, num_heads=num_heads,
+                                  label_smoothing=label_smoothing, max_labels=max_labels)
+    model.decoder = ctc_utils.decoder_config(**decoder_kw)
+    model.config = {'name': 'aed', 'kwargs': dict(
+        num_features=num_features, num_classes=num_classes, encoder=encoder,
+        num_hiddens=num_hiddens, num_layers=num_layers, d_att=d_att, num_heads=num_heads,
+        pred_hiddens=pred_hiddens, pred_layers=pred_layers, label_smoothing=label_smoothing,
+        dropout=dropout, weight_decay=weight_decay, **kw)}
+    if max_labels != MAX_LABELS:        # (only then: a default model's config names no cap)
+        model.config['kwargs']['max_labels'] = max_labels
+    return model

@@ -113,7 +113,8 @@ static int at_fwd(const asr_attn_args* a, const asr_attn_window* w, asr_stream_t
   ASR_CHECK_ARG(a->qkv && a->out && a->out != a->qkv, "attn_fwd: qkv and out are required");
   ASR_CHECK_ARG(at_aligned(a->qkv) && at_aligned(a->out), "attn_fwd: qkv, out 16-byte aligned");
   return at_launch_fwd<false, false>(a->qkv, a->qkv + a->heads * a->dh, a->lens, nullptr, nullptr,
-                                     nullptr, a->out, a->lse, at_geo(a, 0), a->dh, w, stream);
+                                     nullptr, nullptr, a->out, a->lse, at_geo(a, 0), a->dh, w,
+                                     stream);
 }
 
 extern "C" int asr_attn_fwd(const asr_attn_args* a, asr_stream_t stream) {
@@ -140,9 +141,10 @@ static int at_bwd(const asr_attn_args* a, const asr_attn_window* w, void* worksp
     asr_set_error("attn_bwd: workspace too small (%zu bytes needed)", need);
     return ASR_ERR_WORKSPACE;
   }
-  return at_launch_bwd<false>(a->qkv, a->lens, nullptr, nullptr, nullptr, a->out, a->lse, a->dout,
-                              a->dqkv, (float*)workspace, nullptr, nullptr, at_geo(a, 0), a->dh, w,
-                              stream);
+  const int D = a->heads * a->dh;
+  return at_launch_bwd<false>(a->qkv, a->qkv + D, a->lens, nullptr, nullptr, nullptr, nullptr,
+                              a->out, a->lse, a->dout, a->dqkv, a->dqkv + D, (float*)workspace,
+                              nullptr, nullptr, at_geo(a, 0), a->dh, w, stream);
 }
 
 extern "C" int asr_attn_bwd(const asr_attn_args* a, void* workspace, size_t ws_bytes,
@@ -168,8 +170,8 @@ extern "C" int asr_attn_stream_fwd(const asr_attn_stream_args* a, const asr_attn
                                    asr_stream_t stream) {
   const char* bad = at_stream_bad(a, w, AT_MAX_DH, false);
   ASR_CHECK_ARG(bad == nullptr, "attn_stream_fwd: %s", bad);
-  return at_launch_fwd<false, true>(a->q, a->ring, a->kv_len, nullptr, nullptr, nullptr, a->out,
-                                    nullptr, at_geo(a), a->dh, w, stream);
+  return at_launch_fwd<false, true>(a->q, a->ring, a->kv_len, nullptr, nullptr, nullptr, nullptr,
+                                    a->out, nullptr, at_geo(a), a->dh, w, stream);
 }
 
 extern "C" int asr_posenc_add(const float* x, const float* pe, float* y, int T, int N, int n_pad,

@@ -5,6 +5,8 @@
 //   WIN     under the window of attn_tile.h (K25); without it w is not read;
 //   REL     with the relative term: the staged band of the position table, the two biases;
 //   STREAM  (forward only, implies WIN) the queries of one chunk against THE RING of attn_tile.h;
+//   CROSS   (plain form only) queries and keys of two sequences: Tq query rows against Tk keys, the
+//           keys and their gradients in slabs of their own, and a query-row mask (qlens);
 // and the host path they share: the geometry, the dispatch over dh, the launchers, the plan.
 // Every difference between the forms is an `if constexpr`: an instantiation holds the code of its
 // own form only (no ring modulo in a whole-utterance kernel; no band, no cP, not the barrier that
@@ -30,12 +32,23 @@ constexpr int RA_SMALL = 384;             // floats: cP / cK [128] | Ls [64] | D
 // which the absolute frame u lives in row u (whole utterance: the K block of qkv, ld_kv = ld, t0 =
 // 0) or in row u % R (the ring).  The position table has 2 P - 1 rows, row r + P - 1 the relative
 // index r (whole utterance: P = T).
+// CROSS: T counts the queries, Tk the keys (every other form has T of both and never reads Tk);
+// the key source is a slab (Tk, n_pad, ld_kv) of its own, and so is its gradient.
 struct AtGeo {
   int T, N, n_pad, heads, ld, ld_out, ld_pos;
   float c2;         // scale * log2(e)
   float scale;
   int ld_kv, R, t0, P;
+  int Tk;
 };
+
+// CROSS: the valid query rows of sample n, qlens[n] clamped to 0 .. T (T without qlens).  A row at
+// or past it is a padding query: out = lse = exactly 0, and it adds exactly 0 to every gradient
+// (K25's rule for a row with no visible key), by selects on the row index.
+__device__ __forceinline__ int at_qlen(const int* qlens, int n, int T) {
+  const int len = qlens ? qlens[n] : T;
+  return len < 0 ? 0 : (len > T ? T : len);
+}
 
 // rows [r0, r0 + 64) of a column block -> LDS tile (64, DH + 4), plus the vector `add` (LDS, DH
 // floats, or nullptr); rows outside [0, r_end) are zeros (r0 may be negative)
@@ -105,14 +118,17 @@ __device__ __forceinline__ void ra_band_scores(const float* Qs, const float* Bs,
 // are split into tiles and on each key's column inside its tile, and a tile without a visible key
 // for the row is an exact no-op (alpha = 1, or 0 on sums that are 0); stale ring rows and band rows
 // outside the table (staged as zeros) meet masked pairs only; lens is kv_len (a key at or past
-// t0 + T does not exist yet and is never visible); no lse.
-template <int DH, bool WIN, bool REL, bool STREAM>
+// t0 + T does not exist yet and is never visible); no lse.  CROSS: the keys are rows 0 .. Tk - 1
+// of their own slab; rows n >= N of lse are written (zeros) too.
+template <int DH, bool WIN, bool REL, bool STREAM, bool CROSS = false>
 __global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(
     const float* __restrict__ q, const float* __restrict__ kv, const int* __restrict__ lens,
-    const float* __restrict__ pos, const float* __restrict__ bias_u,
+    const int* __restrict__ qlens, const float* __restrict__ pos,
+    const float* __restrict__ bias_u,
     const float* __restrict__ bias_v, float* __restrict__ out, float* __restrict__ lse, AtGeo g,
     asr_attn_window w) {
   static_assert(WIN || !STREAM, "a streaming call has a window");
+  static_assert(!CROSS || !(WIN || REL || STREAM), "the cross form is the plain one");
   constexpr int DP = DH + 4, NJ = DH / 16;
   extern __shared__ float4 at_lds4[];
   float* Qs = reinterpret_cast<float*>(at_lds4);
@@ -131,20 +147,25 @@ __global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(
   if (h == 0) at_zero_cols(o_base, rso, r0, g.T, D, g.ld_out - D, tid);
   if (n >= g.N) {
     at_zero_cols(o_base, rso, r0, g.T, h * DH, DH, tid);
+    if constexpr (CROSS)
+      if (lse != nullptr && tid < AT_TILE && r0 + tid < g.T)
+        lse[((size_t)(r0 + tid) * g.n_pad + n) * g.heads + h] = 0.f;
     return;
   }
+  int qend = g.T;                           // one past the last valid query row
+  if constexpr (CROSS) qend = at_qlen(qlens, n, g.T);
   const float* qbase = q + (size_t)n * g.ld + h * DH;
   const float* kbase = kv + (size_t)n * g.ld_kv + h * DH;
   const float* pos_h = pos + h * DH;
   int q0 = r0, t_end = g.T;                 // the absolute frame of row r0; one past the last query
   if constexpr (STREAM) q0 += g.t0, t_end += g.t0;
-  const int len = at_len(lens, n, t_end);
+  const int len = at_len(lens, n, CROSS ? g.Tk : t_end);
   if constexpr (REL) {
     ra_load_bias<DH>(vu, vd, bias_u + h * DH, bias_v + h * DH, tid);
     __syncthreads();
     ra_load_rows<DH>(Qs, qbase, rs, r0, g.T, vu, tid);
   } else {
-    at_load_tile<DH>(Qs, qbase, rs, r0, g.T, tid);
+    at_load_tile<DH>(Qs, qbase, rs, r0, qend, tid);
   }
   float m[4], l[4], o[4][NJ];
 #pragma unroll
@@ -219,12 +240,14 @@ __global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(
     for (int jj = 0; jj < NJ; ++jj) {
       float v = o[i][jj] / l[i];
       if constexpr (WIN) v = l[i] == 0.f ? 0.f : v;      // a row with no visible key: out = lse = 0
+      if constexpr (CROSS) v = r < qend ? v : 0.f;       // a padding query: likewise
       orow[tx + 16 * jj] = v;
     }
     if constexpr (!STREAM) {
       if (lse != nullptr && tx == 0) {
         float v = (m[i] + log2f(l[i])) * AT_LN2;
         if constexpr (WIN) v = l[i] == 0.f ? 0.f : v;
+        if constexpr (CROSS) v = r < qend ? v : 0.f;
         lse[((size_t)r * g.n_pad + n) * g.heads + h] = v;
       }
     }
@@ -233,13 +256,18 @@ __global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(
 
 // BACKWARD PASS 1: D = dout . out (to dvec, laid out like lse) and dQ, per query tile.  REL:
 // dQ = dQ_c + dQ_p, the content and position parts; dQ_c -> slab_c, dQ_p -> slab_p (T, n_pad, D).
-template <int DH, bool WIN, bool REL>
+// q / dq are the query source and its gradient (rows ld floats apart), kv the [K | V] columns of
+// the key source: q + D of the one qkv slab, or (CROSS) a slab of its own with rows ld_kv apart,
+// in which case the pad columns of dq (>= D) are written as zeros here.
+template <int DH, bool WIN, bool REL, bool CROSS = false>
 __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(
-    const float* __restrict__ qkv, const int* __restrict__ lens, const float* __restrict__ pos,
+    const float* __restrict__ q, const float* __restrict__ kv, const int* __restrict__ lens,
+    const int* __restrict__ qlens, const float* __restrict__ pos,
     const float* __restrict__ bias_u, const float* __restrict__ bias_v,
     const float* __restrict__ out, const float* __restrict__ lse, const float* __restrict__ dout,
-    float* __restrict__ dqkv, float* __restrict__ dvec, float* __restrict__ slab_c,
+    float* __restrict__ dq_out, float* __restrict__ dvec, float* __restrict__ slab_c,
     float* __restrict__ slab_p, AtGeo g, asr_attn_window w) {
+  static_assert(!CROSS || !(WIN || REL), "the cross form is the plain one");
   constexpr int DP = DH + 4, NJ = DH / 16;
   extern __shared__ float4 at_lds4[];
   float* Qs = reinterpret_cast<float*>(at_lds4);
@@ -256,9 +284,13 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(
   const int D = g.heads * DH;
   const size_t rs = (size_t)g.n_pad * g.ld, rso = (size_t)g.n_pad * g.ld_out;
   const size_t rsd = (size_t)g.n_pad * D;
-  float* dq_base = dqkv + (size_t)n * g.ld;
+  const int ldk = CROSS ? g.ld_kv : g.ld;
+  const size_t rsk = CROSS ? (size_t)g.n_pad * g.ld_kv : rs;
+  float* dq_base = dq_out + (size_t)n * g.ld;
   float* sc_base = slab_c + (size_t)n * D + h * DH;
   float* sp_base = slab_p + (size_t)n * D + h * DH;
+  if constexpr (CROSS)
+    if (h == 0) at_zero_cols(dq_base, rs, q0, g.T, D, g.ld - D, tid);
   if (n >= g.N) {
     at_zero_cols(dq_base, rs, q0, g.T, h * DH, DH, tid);
     if constexpr (REL) {
@@ -267,26 +299,29 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(
     }
     return;
   }
-  const float* base = qkv + (size_t)n * g.ld + h * DH;
+  const float* base = q + (size_t)n * g.ld + h * DH;
+  const float* kbase = kv + (size_t)n * ldk + h * DH;
   const float* do_base = dout + (size_t)n * g.ld_out + h * DH;
   const float* o_base = out + (size_t)n * g.ld_out + h * DH;
   const float* pos_h = pos + h * DH;
-  const int len = at_len(lens, n, g.T);
+  const int len = at_len(lens, n, CROSS ? g.Tk : g.T);
+  int qend = g.T;                           // one past the last valid query row
+  if constexpr (CROSS) qend = at_qlen(qlens, n, g.T);
   if constexpr (REL) {
     ra_load_bias<DH>(vu, vd, bias_u + h * DH, bias_v + h * DH, tid);
     __syncthreads();
     ra_load_rows<DH>(Qs, base, rs, q0, g.T, vu, tid);
   } else {
-    at_load_tile<DH>(Qs, base, rs, q0, g.T, tid);
+    at_load_tile<DH>(Qs, base, rs, q0, qend, tid);
   }
-  at_load_tile<DH>(Gs, do_base, rso, q0, g.T, tid);
+  at_load_tile<DH>(Gs, do_base, rso, q0, qend, tid);
   __syncthreads();
   float lse2[4], dsum[4], dq[4][NJ], dqp[4][NJ];         // dqp: REL
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int t = q0 + 4 * ty + i;
     float acc = 0.f;
-    if (t < g.T) {
+    if (t < qend) {
 #pragma unroll
       for (int jj = 0; jj < NJ; ++jj)
         acc = fmaf(Gs[(4 * ty + i) * DP + tx + 16 * jj], o_base[(size_t)t * rso + tx + 16 * jj], acc);
@@ -308,8 +343,8 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(
     }
   }
   for (int k0 = kb; k0 < ke; k0 += AT_TILE) {
-    at_load_tile<DH>(Ks, base + D, rs, k0, len, tid);
-    at_load_tile<DH>(Vs, base + 2 * D, rs, k0, len, tid);
+    at_load_tile<DH>(Ks, kbase, rsk, k0, len, tid);
+    at_load_tile<DH>(Vs, kbase + D, rsk, k0, len, tid);
     if constexpr (REL) {
       const int pr0 = q0 - k0 - 63 + g.T - 1;
       ra_load_rows<DH>(Bs, pos_h, g.ld_pos, pr0, 2 * g.T - 1, nullptr, tid);
@@ -333,6 +368,7 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(
         const float sp = REL ? Ps[row * AT_PP + col] + cP[row - col + 63] : 0.f;
         bool vis = k0 + col < len;
         if constexpr (WIN) vis = k0 + col >= wlo[i] && k0 + col < whi[i];
+        if constexpr (CROSS) vis = vis && q0 + row < qend;
         const float p = vis ? exp2f(fmaf(REL ? s[i][j] + sp : s[i][j], g.c2, -lse2[i])) : 0.f;
         s[i][j] = p * (dp[i][j] - dsum[i]) * g.scale;
       }
@@ -377,13 +413,17 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(
 }
 
 // BACKWARD PASS 2: dK and dV of one key tile over all query tiles (query tiles ascending).  REL:
-// Qs holds q + b_u, so dK sees it.
-template <int DH, bool WIN, bool REL>
+// Qs holds q + b_u, so dK sees it.  kv / dkv are the [K | V] columns of the key source and of its
+// gradient: q + D and dq + D of the qkv / dqkv slabs, or (CROSS) slabs (Tk, n_pad, ld_kv) of
+// their own; the columns behind dV are written as zeros here.
+template <int DH, bool WIN, bool REL, bool CROSS = false>
 __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dkv_kernel(
-    const float* __restrict__ qkv, const int* __restrict__ lens, const float* __restrict__ pos,
+    const float* __restrict__ q, const float* __restrict__ kv, const int* __restrict__ lens,
+    const int* __restrict__ qlens, const float* __restrict__ pos,
     const float* __restrict__ bias_u, const float* __restrict__ bias_v,
-    const float* __restrict__ lse, const float* __restrict__ dout, float* __restrict__ dqkv,
+    const float* __restrict__ lse, const float* __restrict__ dout, float* __restrict__ dkv,
     const float* __restrict__ dvec, AtGeo g, asr_attn_window w) {
+  static_assert(!CROSS || !(WIN || REL), "the cross form is the plain one");
   constexpr int DP = DH + 4, NJ = DH / 16;
   extern __shared__ float4 at_lds4[];
   float* Ks = reinterpret_cast<float*>(at_lds4);
@@ -400,27 +440,32 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dkv_kernel(
   const int k0 = blockIdx.x * AT_TILE, h = blockIdx.y, n = blockIdx.z;
   const int D = g.heads * DH;
   const size_t rs = (size_t)g.n_pad * g.ld, rso = (size_t)g.n_pad * g.ld_out;
-  float* d_base = dqkv + (size_t)n * g.ld;
-  if (h == 0) at_zero_cols(d_base, rs, k0, g.T, 3 * D, g.ld - 3 * D, tid);
-  const int len = n < g.N ? at_len(lens, n, g.T) : 0;
+  const int Tk = CROSS ? g.Tk : g.T, ldk = CROSS ? g.ld_kv : g.ld;
+  const size_t rsk = CROSS ? (size_t)g.n_pad * g.ld_kv : rs;
+  float* d_base = dkv + (size_t)n * ldk;
+  if (h == 0) at_zero_cols(d_base, rsk, k0, Tk, 2 * D, ldk - (CROSS ? 2 : 3) * D, tid);
+  const int len = n < g.N ? at_len(lens, n, Tk) : 0;
   if (k0 >= len) {          // a padding sample, or a tile of masked keys only
-    at_zero_cols(d_base, rs, k0, g.T, D + h * DH, DH, tid);
-    at_zero_cols(d_base, rs, k0, g.T, 2 * D + h * DH, DH, tid);
+    at_zero_cols(d_base, rsk, k0, Tk, h * DH, DH, tid);
+    at_zero_cols(d_base, rsk, k0, Tk, D + h * DH, DH, tid);
     return;
   }
-  const float* base = qkv + (size_t)n * g.ld + h * DH;
+  const float* base = q + (size_t)n * g.ld + h * DH;
+  const float* kbase = kv + (size_t)n * ldk + h * DH;
   const float* do_base = dout + (size_t)n * g.ld_out + h * DH;
   const float* pos_h = pos + h * DH;
+  int qend = g.T;                           // one past the last valid query row
+  if constexpr (CROSS) qend = at_qlen(qlens, n, g.T);
   if constexpr (REL) ra_load_bias<DH>(vu, vd, bias_u + h * DH, bias_v + h * DH, tid);
-  at_load_tile<DH>(Ks, base + D, rs, k0, len, tid);
-  at_load_tile<DH>(Vs, base + 2 * D, rs, k0, len, tid);
+  at_load_tile<DH>(Ks, kbase, rsk, k0, len, tid);
+  at_load_tile<DH>(Vs, kbase + D, rsk, k0, len, tid);
   if constexpr (REL) __syncthreads();       // (vu before the first query tile adds it)
   float dk[4][NJ], dv[4][NJ];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int jj = 0; jj < NJ; ++jj) dk[i][jj] = dv[i][jj] = 0.f;
-  for (int q0 = 0; q0 < g.T; q0 += AT_TILE) {
+  for (int q0 = 0; q0 < qend; q0 += AT_TILE) {
     int qlo[4], qhi[4];                     // the visible keys of query tx + 16 j
     if constexpr (WIN) {
       // only the query tiles that see a key of this tile: one contiguous range, lo and hi being
@@ -435,9 +480,9 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dkv_kernel(
     if constexpr (REL) {
       ra_load_rows<DH>(Qs, base, rs, q0, g.T, vu, tid);
     } else {
-      at_load_tile<DH>(Qs, base, rs, q0, g.T, tid);
+      at_load_tile<DH>(Qs, base, rs, q0, qend, tid);
     }
-    at_load_tile<DH>(Gs, do_base, rso, q0, g.T, tid);
+    at_load_tile<DH>(Gs, do_base, rso, q0, qend, tid);
     if constexpr (REL) {
       const int pr0 = q0 - k0 - 63 + g.T - 1;
       ra_load_rows<DH>(Bs, pos_h, g.ld_pos, pr0, 2 * g.T - 1, nullptr, tid);
@@ -475,7 +520,7 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dkv_kernel(
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int q = tx + 16 * j, kk = 4 * ty + i;
-        bool live = (k0 + kk < len) && (q0 + q < g.T);
+        bool live = (k0 + kk < len) && (q0 + q < qend);
         if constexpr (WIN) live = live && k0 + kk >= qlo[j] && k0 + kk < qhi[j];
         const float sp = REL ? Ps[kk * AT_PP + q] + cP[q - kk + 63] : 0.f;
         s[i][j] = live ? exp2f(fmaf(REL ? s[i][j] + sp : s[i][j], g.c2, -Ls[q])) : 0.f;
@@ -494,12 +539,12 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dkv_kernel(
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int u = k0 + 4 * ty + i;
-    if (u >= g.T) continue;
-    float* row = d_base + (size_t)u * rs + h * DH;
+    if (u >= Tk) continue;
+    float* row = d_base + (size_t)u * rsk + h * DH;
 #pragma unroll
     for (int jj = 0; jj < NJ; ++jj) {       // (rows u >= len accumulated p = 0 only: exact zeros)
-      row[D + tx + 16 * jj] = dk[i][jj];
-      row[2 * D + tx + 16 * jj] = dv[i][jj];
+      row[tx + 16 * jj] = dk[i][jj];
+      row[D + tx + 16 * jj] = dv[i][jj];
     }
   }
 }
@@ -523,7 +568,7 @@ template <typename Args>
 AtGeo at_geo(const Args* a, int ld_pos) {
   AtGeo g;
   g.T = a->T, g.N = a->N, g.n_pad = a->n_pad, g.heads = a->heads, g.ld = a->ld, g.ld_kv = a->ld;
-  g.ld_out = a->ld_out, g.ld_pos = ld_pos, g.R = 0, g.t0 = 0, g.P = a->T;
+  g.ld_out = a->ld_out, g.ld_pos = ld_pos, g.R = 0, g.t0 = 0, g.P = a->T, g.Tk = a->T;
   g.scale = a->scale, g.c2 = a->scale * AT_LOG2E;
   return g;
 }
@@ -532,12 +577,21 @@ inline AtGeo at_geo(const asr_attn_stream_args* a) {
   AtGeo g;
   g.T = a->Tq, g.N = a->N, g.n_pad = a->n_pad, g.heads = a->heads, g.ld = a->ld;
   g.ld_kv = a->ld_kv, g.ld_out = a->ld_out, g.ld_pos = a->ld_pos, g.R = a->R, g.t0 = a->t0;
-  g.P = a->P, g.scale = a->scale, g.c2 = a->scale * AT_LOG2E;
+  g.P = a->P, g.Tk = 0, g.scale = a->scale, g.c2 = a->scale * AT_LOG2E;
+  return g;
+}
+// ... and of a cross call
+inline AtGeo at_geo(const asr_attn_cross_args* a) {
+  AtGeo g;
+  g.T = a->Tq, g.Tk = a->Tk, g.N = a->N, g.n_pad = a->n_pad, g.heads = a->heads, g.ld = a->ld_q;
+  g.ld_kv = a->ld_kv, g.ld_out = a->ld_out, g.ld_pos = 0, g.R = 0, g.t0 = 0, g.P = 0;
+  g.scale = a->scale, g.c2 = a->scale * AT_LOG2E;
   return g;
 }
 
-inline dim3 at_grid(const AtGeo& g) {
-  return dim3((g.T + AT_TILE - 1) / AT_TILE, g.heads, g.n_pad);
+// one workgroup per 64 rows of a side: the queries (forward, pass 1) or the keys (pass 2)
+inline dim3 at_grid(const AtGeo& g, int rows) {
+  return dim3((rows + AT_TILE - 1) / AT_TILE, g.heads, g.n_pad);
 }
 
 // bq, bk, blocks of a plan (any pointer may be NULL)
@@ -560,23 +614,27 @@ int at_dispatch(int dh, F&& launch) {
   }
 }
 
-// The forward launch of every form: w == nullptr: the unwindowed kernels (not for STREAM).
-template <bool REL, bool STREAM>
-int at_launch_fwd(const float* q, const float* kv, const int* lens, const float* pos,
-                  const float* bias_u, const float* bias_v, float* out, float* lse, const AtGeo& g,
-                  int dh, const asr_attn_window* w, asr_stream_t stream) {
+// The forward launch of every form: w == nullptr: the unwindowed kernels (not for STREAM; CROSS
+// has no other).  qlens: CROSS only.
+template <bool REL, bool STREAM, bool CROSS = false>
+int at_launch_fwd(const float* q, const float* kv, const int* lens, const int* qlens,
+                  const float* pos, const float* bias_u, const float* bias_v, float* out,
+                  float* lse, const AtGeo& g, int dh, const asr_attn_window* w,
+                  asr_stream_t stream) {
   const size_t lds = at_lds_bytes<REL>(dh, 0);
   const asr_attn_window win = w ? *w : asr_attn_window{1, -1, 0};
   auto go = [&](auto kernel) -> int {
     if (at_allow_lds(kernel, lds) != ASR_OK) return ASR_ERR_LAUNCH;
-    hipLaunchKernelGGL(kernel, at_grid(g), dim3(AT_THREADS), lds, (hipStream_t)stream, q, kv, lens,
-                       pos, bias_u, bias_v, out, lse, g, win);
+    hipLaunchKernelGGL(kernel, at_grid(g, g.T), dim3(AT_THREADS), lds, (hipStream_t)stream, q, kv,
+                       lens, qlens, pos, bias_u, bias_v, out, lse, g, win);
     ASR_CHECK_LAUNCH();
     return ASR_OK;
   };
   return at_dispatch<REL ? RA_MAX_DH : AT_MAX_DH>(dh, [&](auto c) -> int {
     constexpr int DH = decltype(c)::value;
-    if constexpr (STREAM) {
+    if constexpr (CROSS) {
+      return go(attn_fwd_kernel<DH, false, false, false, true>);
+    } else if constexpr (STREAM) {
       return go(attn_fwd_kernel<DH, true, REL, true>);
     } else {
       return w ? go(attn_fwd_kernel<DH, true, REL, false>)
@@ -586,28 +644,35 @@ int at_launch_fwd(const float* q, const float* kv, const int* lens, const float*
 }
 
 // The launches of backward passes 1 and 2 (plain: pos .. bias_v, slab_c, slab_p are nullptr).
-template <bool REL>
-int at_launch_bwd(const float* qkv, const int* lens, const float* pos, const float* bias_u,
-                  const float* bias_v, const float* out, const float* lse, const float* dout,
-                  float* dqkv, float* dvec, float* slab_c, float* slab_p, const AtGeo& g, int dh,
-                  const asr_attn_window* w, asr_stream_t stream) {
+// One qkv slab: kv = q + D, dkv = dq + D.  qlens: CROSS only.
+template <bool REL, bool CROSS = false>
+int at_launch_bwd(const float* q, const float* kv, const int* lens, const int* qlens,
+                  const float* pos, const float* bias_u, const float* bias_v, const float* out,
+                  const float* lse, const float* dout, float* dq, float* dkv, float* dvec,
+                  float* slab_c, float* slab_p, const AtGeo& g, int dh, const asr_attn_window* w,
+                  asr_stream_t stream) {
   const size_t lds1 = at_lds_bytes<REL>(dh, 1), lds2 = at_lds_bytes<REL>(dh, 2);
   const asr_attn_window win = w ? *w : asr_attn_window{1, -1, 0};
   hipStream_t s = (hipStream_t)stream;
   auto go = [&](auto dq_kernel, auto dkv_kernel) -> int {
     if (at_allow_lds(dq_kernel, lds1) != ASR_OK) return ASR_ERR_LAUNCH;
     if (at_allow_lds(dkv_kernel, lds2) != ASR_OK) return ASR_ERR_LAUNCH;
-    hipLaunchKernelGGL(dq_kernel, at_grid(g), dim3(AT_THREADS), lds1, s, qkv, lens, pos, bias_u,
-                       bias_v, out, lse, dout, dqkv, dvec, slab_c, slab_p, g, win);
-    hipLaunchKernelGGL(dkv_kernel, at_grid(g), dim3(AT_THREADS), lds2, s, qkv, lens, pos, bias_u,
-                       bias_v, lse, dout, dqkv, (const float*)dvec, g, win);
+    hipLaunchKernelGGL(dq_kernel, at_grid(g, g.T), dim3(AT_THREADS), lds1, s, q, kv, lens, qlens,
+                       pos, bias_u, bias_v, out, lse, dout, dq, dvec, slab_c, slab_p, g, win);
+    hipLaunchKernelGGL(dkv_kernel, at_grid(g, CROSS ? g.Tk : g.T), dim3(AT_THREADS), lds2, s, q, kv,
+                       lens, qlens, pos, bias_u, bias_v, lse, dout, dkv, (const float*)dvec, g, win);
     ASR_CHECK_LAUNCH();
     return ASR_OK;
   };
   return at_dispatch<REL ? RA_MAX_DH : AT_MAX_DH>(dh, [&](auto c) -> int {
     constexpr int DH = decltype(c)::value;
-    return w ? go(attn_bwd_dq_kernel<DH, true, REL>, attn_bwd_dkv_kernel<DH, true, REL>)
-             : go(attn_bwd_dq_kernel<DH, false, REL>, attn_bwd_dkv_kernel<DH, false, REL>);
+    if constexpr (CROSS) {
+      return go(attn_bwd_dq_kernel<DH, false, false, true>,
+                attn_bwd_dkv_kernel<DH, false, false, true>);
+    } else {
+      return w ? go(attn_bwd_dq_kernel<DH, true, REL>, attn_bwd_dkv_kernel<DH, true, REL>)
+               : go(attn_bwd_dq_kernel<DH, false, REL>, attn_bwd_dkv_kernel<DH, false, REL>);
+    }
   });
 }
 

@@ -278,9 +278,9 @@ static int ra_fwd(const asr_relattn_args* a, const asr_attn_window* w, asr_strea
                 "relattn_fwd: qkv, out, pos, bias_u and bias_v are required");
   ASR_CHECK_ARG(at_aligned(a->qkv) && at_aligned(a->out) && at_aligned(a->pos),
                 "relattn_fwd: qkv, out, pos 16-byte aligned");
-  return at_launch_fwd<true, false>(a->qkv, a->qkv + a->heads * a->dh, a->lens, a->pos, a->bias_u,
-                                    a->bias_v, a->out, a->lse, at_geo(a, a->ld_pos), a->dh, w,
-                                    stream);
+  return at_launch_fwd<true, false>(a->qkv, a->qkv + a->heads * a->dh, a->lens, nullptr, a->pos,
+                                    a->bias_u, a->bias_v, a->out, a->lse, at_geo(a, a->ld_pos),
+                                    a->dh, w, stream);
 }
 
 extern "C" int asr_relattn_fwd(const asr_relattn_args* a, asr_stream_t stream) {
@@ -297,8 +297,8 @@ extern "C" int asr_relattn_stream_fwd(const asr_attn_stream_args* a, const asr_a
                                       asr_stream_t stream) {
   const char* bad = at_stream_bad(a, w, RA_MAX_DH, true);
   ASR_CHECK_ARG(bad == nullptr, "relattn_stream_fwd: %s", bad);
-  return at_launch_fwd<true, true>(a->q, a->ring, a->kv_len, a->pos, a->bias_u, a->bias_v, a->out,
-                                   nullptr, at_geo(a), a->dh, w, stream);
+  return at_launch_fwd<true, true>(a->q, a->ring, a->kv_len, nullptr, a->pos, a->bias_u,
+                                   a->bias_v, a->out, nullptr, at_geo(a), a->dh, w, stream);
 }
 
 static int ra_bwd(const asr_relattn_args* a, const asr_attn_window* wp, void* workspace,
@@ -325,8 +325,10 @@ static int ra_bwd(const asr_relattn_args* a, const asr_attn_window* wp, void* wo
   float* slab_p = (float*)(ws + w.slab_p);
   float* part = (float*)(ws + w.part);
   const int rows = 2 * a->T - 1;
-  int rc = at_launch_bwd<true>(a->qkv, a->lens, a->pos, a->bias_u, a->bias_v, a->out, a->lse,
-                               a->dout, a->dqkv, dvec, slab_c, slab_p, g, a->dh, wp, stream);
+  const int D = a->heads * a->dh, M = a->T * a->n_pad;
+  int rc = at_launch_bwd<true>(a->qkv, a->qkv + D, a->lens, nullptr, a->pos, a->bias_u, a->bias_v,
+                               a->out, a->lse, a->dout, a->dqkv, a->dqkv + D, dvec, slab_c, slab_p,
+                               g, a->dh, wp, stream);
   if (rc != ASR_OK) return rc;
   const dim3 grid_pos((rows + AT_TILE - 1) / AT_TILE, a->heads, a->N);
   const size_t lds3 = ra_dpos_lds_bytes(a->dh);
@@ -344,7 +346,6 @@ static int ra_bwd(const asr_relattn_args* a, const asr_attn_window* wp, void* wo
     return wp ? go(relattn_bwd_dpos_kernel<DH, true>) : go(relattn_bwd_dpos_kernel<DH, false>);
   });
   if (rc != ASR_OK) return rc;
-  const int D = a->heads * a->dh, M = a->T * a->n_pad;
   rc = asr_colsum(slab_c, M, D, D, a->dbias_u, 0.f, ws + w.colsum, w.colsum_bytes, stream);
   if (rc != ASR_OK) return rc;
   rc = asr_colsum(slab_p, M, D, D, a->dbias_v, 0.f, ws + w.colsum, w.colsum_bytes, stream);

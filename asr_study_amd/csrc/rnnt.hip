@@ -28,11 +28,11 @@
 //
 // Layout of the per-cell arrays: SKEWED, index (n, d, u) with d = t + u, so the chains read and
 // write one contiguous row per step.
-#include "common.h"
+// (the pieces this joint shares with the attention decoder's, aed.hip: joint_common.h)
+#include "joint_common.h"
 
 namespace {
 
-constexpr float kNegInf = -__builtin_huge_valf();
 constexpr int TS = 16;        // cells per tile side
 constexpr int KJ = 64;        // rows of W_out (and columns of the enc / pred tiles) staged at once
 constexpr int SJ = 16;        // of those, rows per pass of the dW_out accumulation
@@ -65,14 +65,7 @@ __device__ __forceinline__ float row16_sum(float v) {
   return v;
 }
 
-// tanh to a few ulp of 1 (absolute): what the joint needs of it, h and 1 - h^2 are O(1) factors
-__device__ __forceinline__ float joint_tanh(float x) {
-  x = fminf(fmaxf(x, -15.f), 15.f);
-  return 1.f - __fdividef(2.f, __expf(2.f * x) + 1.f);
-}
-
 __host__ __device__ inline int pad4(int x) { return (x + 3) / 4 * 4; }
-inline int class_pad(int C) { return C <= 16 ? 16 : (C <= 32 ? 32 : 64); }
 
 __device__ __forceinline__ void clamp_lens(const int* seq_len, const int* label_len, int n, int T,
                                            int U1, int& Tn, int& Un) {
@@ -155,11 +148,6 @@ __device__ __forceinline__ float pick(const float (&z)[CP], int k) {
 #pragma unroll
   for (int c = 0; c < CP; ++c) v = fmaxf(v, c == k ? z[c] : kNegInf);
   return v;
-}
-__device__ __forceinline__ int label_at(const int* __restrict__ labels, int n, int l_max, int u,
-                                        int C) {
-  const int y = labels[(size_t)n * l_max + u];
-  return (y < 0 || y >= C) ? C - 1 : y;
 }
 
 // ---------------------------------------------------------------------------
@@ -459,19 +447,6 @@ rnnt_bwd_kernel(const float* __restrict__ enc, const float* __restrict__ pred,
   }
 }
 
-// dW_out (J, C) and db_out (C): the slabs added in index order
-__global__ void __launch_bounds__(256)
-rnnt_slab_sum_kernel(const float* __restrict__ slabs, int nslabs, int J, int C, int CP,
-                     float* __restrict__ dW, float* __restrict__ db) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= (J + 1) * C) return;
-  const int j = i / C, c = i % C;
-  float s = 0.f;
-  for (int g = 0; g < nslabs; ++g) s += slabs[((size_t)g * (J + 1) + j) * CP + c];
-  if (j < J) dW[(size_t)j * C + c] = s;
-  else db[c] = s;
-}
-
 // ---------------------------------------------------------------------------
 // one iteration of greedy decoding: one wave per utterance
 __global__ void __launch_bounds__(64)
@@ -621,7 +596,7 @@ int launch_joint(const float* enc, const float* pred, const float* W, const floa
                      l_max, scale, lpb, lpy, alpha, beta, Aoff, Boff, logz, d_pred,
                      (float*)nullptr);
   ASR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(rnnt_slab_sum_kernel, dim3(((J + 1) * C + 255) / 256), dim3(256), 0, stream,
+  hipLaunchKernelGGL(joint_slab_sum_kernel, dim3(((J + 1) * C + 255) / 256), dim3(256), 0, stream,
                      slabs, kSlabs, J, C, CP, dW, db);
   ASR_CHECK_LAUNCH();
   return ASR_OK;

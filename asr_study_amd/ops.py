@@ -1292,6 +1292,114 @@ def rows_select(mask, a, b, out, N):
     return out
 
 
+# --------------------------------------------------------------------------- attention decoder (K32)
+AED_MAX_J, AED_MAX_C, AED_MAX_LABELS = 512, 64, 255      # the limits of asr_aed_loss_grad
+
+
+def _attn_cross_args(q, kv, out, N, heads, dh, scale, **tensors):
+    assert q.dim() == 3 and kv.dim() == 3 and out.dim() == 3
+    assert kv.shape[1] == q.shape[1] and out.shape[:2] == q.shape[:2]
+    a = L.AttnCrossArgs()
+    a.Tq, a.Tk, a.N, a.n_pad = int(q.shape[0]), int(kv.shape[0]), int(N), int(q.shape[1])
+    a.heads, a.dh = int(heads), int(dh)
+    a.ld_q, a.ld_kv, a.ld_out = int(q.shape[2]), int(kv.shape[2]), int(out.shape[2])
+    a.scale = float(scale if scale is not None else 1.0 / math.sqrt(dh))
+    for k, t in dict(tensors, q=q, kv=kv, out=out).items():
+        setattr(a, k, None if t is None else t.data_ptr())
+    return a
+
+
+def attn_cross_fwd(q, kv, out, N, heads, dh, q_lens=None, k_lens=None, lse=None, scale=None):
+    """out (Tq, n_pad, ld_out >= heads dh) = softmax(scale Q K^T) V per real sample and head: Q the
+    first heads dh columns of q (Tq, n_pad, ld_q), [K | V] the first 2 heads dh columns of kv (Tk,
+    n_pad, ld_kv).  Keys u >= k_lens[n] carry probability 0; a query row t >= q_lens[n] has out =
+    lse = 0 (device int32 (N), both optional).  lse (attn_lse_len(Tq, ..)) is kept for
+    attn_cross_bwd when given (asr_attn_cross_fwd: the kernels of attn_fwd)."""
+    _check_f32(q, kv, out, lse)
+    _check_lens(q_lens, N)
+    _check_lens(k_lens, N)
+    a = _attn_cross_args(q, kv, out, N, heads, dh, scale, q_lens=q_lens, k_lens=k_lens, lse=lse)
+    L.check(L.load().asr_attn_cross_fwd(C.byref(a), _stream()), 'asr_attn_cross_fwd')
+    return out
+
+
+def attn_cross_bwd(q, kv, out, lse, dout, dq, dkv, N, heads, dh, q_lens=None, k_lens=None,
+                   scale=None):
+    """dq (like q) and dkv (like kv) = dK | dV from dout (like out), recomputing p from lse; both
+    are WRITTEN, pad columns and padding rows as zeros (asr_attn_cross_bwd)."""
+    _check_f32(q, kv, out, lse, dout, dq, dkv)
+    _check_lens(q_lens, N)
+    _check_lens(k_lens, N)
+    assert dq.shape == q.shape and dkv.shape == kv.shape and dout.shape == out.shape
+    a = _attn_cross_args(q, kv, out, N, heads, dh, scale, q_lens=q_lens, k_lens=k_lens, lse=lse,
+                         dout=dout, dq=dq, dkv=dkv)
+    nbytes = L.load().asr_attn_cross_workspace_bytes(C.byref(a))
+    if nbytes == 0:
+        L.check(-1, 'asr_attn_cross_workspace_bytes (Tq %d Tk %d N %d n_pad %d heads %d dh %d '
+                'ld_q %d ld_kv %d ld_out %d)' % (a.Tq, a.Tk, a.N, a.n_pad, a.heads, a.dh, a.ld_q,
+                                                 a.ld_kv, a.ld_out))
+    ws = WS.get('attn', nbytes, q.device)
+    L.check(L.load().asr_attn_cross_bwd(C.byref(a), _ptr(ws), nbytes, _stream()),
+            'asr_attn_cross_bwd')
+    return dq, dkv
+
+
+def aed_loss_grad(ctx, q, W_out, b_out, labels, label_len, N, grads=None, grad_scale=1.0,
+                  eps=0.0, loss=None):
+    """The attention decoder's loss (include/asr_hip.h K32): the label-smoothed cross-entropy of
+    tanh(ctx + q) W_out + b_out, ctx and q (U1, n_pad, J), W_out (J, C), b_out (C); labels (N,
+    U1 - 1) int32 and label_len (N) int32 on the device; row u of utterance n is scored against
+    label u, row label_len[n] against EOS = C - 1.  grads: None (loss only) or the four tensors
+    (d_ctx, d_q, dW_out, db_out), which are WRITTEN, scaled by grad_scale (d_ctx and d_q get the
+    same values).  Returns loss (N)."""
+    lib = L.load()
+    U1, n_pad, J = (int(v) for v in ctx.shape)
+    Cc, N = int(b_out.numel()), int(N)
+    assert q.shape == ctx.shape and W_out.numel() == J * Cc
+    d = tuple(grads) if grads is not None else (None,) * 4
+    assert len(d) == 4
+    _check_f32(ctx, q, W_out, b_out, *d)
+    if d[0] is not None:
+        assert d[0].shape == ctx.shape and d[1].shape == ctx.shape
+        assert d[2].numel() == J * Cc and d[3].numel() == Cc
+    l_max = U1 - 1
+    if l_max:
+        _check_i32(labels, N * l_max)
+    _check_i32(label_len, N)
+    if loss is None:
+        loss = torch.empty(N, dtype=torch.float32, device=ctx.device)
+    nbytes = lib.asr_aed_workspace_bytes(U1, N, n_pad, J, Cc)
+    ws = WS.get('aed', nbytes, ctx.device)
+    L.check(lib.asr_aed_loss_grad(
+        _ptr(ctx), _ptr(q), _ptr(W_out), _ptr(b_out), _ptr(labels) if l_max else None,
+        _ptr(label_len), U1, N, n_pad, J, Cc, l_max, float(eps), float(grad_scale), _ptr(loss),
+        _ptr(d[0]), _ptr(d[1]), _ptr(d[2]), _ptr(d[3]), _ptr(ws), nbytes, _stream()),
+        'asr_aed_loss_grad')
+    return loss
+
+
+def aed_greedy_step(ctx, q, W_out, b_out, N, finished, decoded, decoded_len, advance, x_next,
+                    active, max_labels=AED_MAX_LABELS):
+    """One iteration of label-synchronous greedy decoding (asr_aed_greedy_step): ctx, q (n_pad, J)
+    the current context and query rows; finished, decoded_len, advance (N) and active (1) int32,
+    decoded (N, cap) int32, x_next (n_pad, ld) float32 the next predictor input, all on the device
+    and updated in place."""
+    n_pad, J = int(ctx.shape[-2]), int(ctx.shape[-1])
+    Cc, N = int(b_out.numel()), int(N)
+    _check_f32(ctx, q, W_out, b_out, x_next)
+    assert ctx.numel() == n_pad * J and q.numel() == n_pad * J and W_out.numel() == J * Cc
+    assert x_next.shape[0] >= N and decoded.shape[0] >= N
+    for t in (finished, decoded_len, advance):
+        _check_i32(t, N)
+    _check_i32(decoded, N)
+    _check_i32(active, 1)
+    L.check(L.load().asr_aed_greedy_step(
+        _ptr(ctx), _ptr(q), _ptr(W_out), _ptr(b_out), N, n_pad, J, Cc, int(max_labels),
+        int(decoded.shape[1]), int(x_next.shape[1]), _ptr(finished), _ptr(decoded),
+        _ptr(decoded_len), _ptr(advance), _ptr(x_next), _ptr(active), _stream()),
+        'asr_aed_greedy_step')
+
+
 # --------------------------------------------------------------------------- streaming (K26)
 def attn_stream_plan(window, max_tq):
     """Rows of the smallest [K | V] ring (a multiple of 64) that is valid for every call of up to

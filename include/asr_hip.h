@@ -69,7 +69,9 @@ const char* asr_last_error(void);
  * now READ: a caller that left `reserved` uninitialised must set it to 0,
  * any value other than 0 or 1 is ASR_ERR_INVALID;
  * asr_rnnt_workspace_bytes, asr_rnnt_loss_grad, asr_rnnt_greedy_step, asr_onehot_rows and
- * asr_rows_select (K31: plain scalar arguments, additions only). */
+ * asr_rows_select (K31: plain scalar arguments, additions only);
+ * asr_attn_cross_args, asr_attn_cross_* and the asr_aed_* entry points (K32: a new struct and
+ * plain scalar arguments, additions only). */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -1306,6 +1308,94 @@ int asr_onehot_rows(const int* labels, const int* label_len, int U1, int N, int 
 /* out may be a or b.                                                        */
 int asr_rows_select(const int* mask, const float* a, const float* b, float* out, int N,
                     int n_pad, int width, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K32 attention encoder-decoder (no reference counterpart): the cross-      */
+/* attention core (csrc/cross_attention.hip) and the decoder's fused joint + */
+/* softmax cross-entropy (csrc/aed.hip).                                     */
+/*                                                                           */
+/* CROSS-ATTENTION: K21 with the queries and the keys in two slabs of two    */
+/* lengths.  q (Tq, n_pad, ld_q >= D) holds Q in its first D = heads * dh    */
+/* columns, kv (Tk, n_pad, ld_kv >= 2D) holds [K | V]; head h in columns     */
+/* h dh .. of each block.  For n < N, head h, query row t < q_lens[n]:       */
+/*   s[t,u] = scale q_t . k_u  for u < k_lens[n],  p = softmax_u(s),         */
+/*   out_t = sum_u p[t,u] v_u,  lse_t = log sum_u exp s[t,u];                */
+/* masked keys carry probability exactly 0 and get dK = dV = exactly 0.  A   */
+/* query row t >= q_lens[n] has out = lse = exactly 0 and adds exactly 0 to  */
+/* every gradient (K25's rule for a row with no visible key); its dQ is 0.   */
+/* Rows n >= N of out, lse, dq, dkv and the pad columns (>= D of out and dq, */
+/* >= 2D of dkv) are written as exact zeros.  The kernels are the passes of  */
+/* K21 (csrc/attn_core.h, CROSS = true): the same arithmetic in the same     */
+/* order, so with Tq = Tk, q_lens = NULL and q, kv the column blocks of one  */
+/* qkv slab the results equal asr_attn_fwd / asr_attn_bwd bit for bit.       */
+/* Exact fp32 FMAs, base-2 exponentials, no float atomics, no workgroup      */
+/* waits on another.  dh a multiple of 16 in 16 .. 128, any Tq, Tk >= 1 (Tq  */
+/* = 1: the decode step), 1 <= N <= n_pad <= 65535, ld_* multiples of 4,     */
+/* 16-byte aligned slabs; anything else is ASR_ERR_INVALID before any device */
+/* call (the size function returns 0).                                       */
+/* ------------------------------------------------------------------------ */
+typedef struct asr_attn_cross_args {
+  int Tq, Tk, N, n_pad, heads, dh;
+  int ld_q, ld_kv, ld_out;   /* floats per row of q / dq, of kv / dkv, of out / dout          */
+  float scale;               /* of the scores, usually 1 / sqrt(dh)                          */
+  const float* q;            /* (Tq, n_pad, ld_q)                                            */
+  const float* kv;           /* (Tk, n_pad, ld_kv)                                           */
+  const int* q_lens;         /* optional device int32 (N): valid query rows, clamped to      */
+                             /*   0 .. Tq                                                    */
+  const int* k_lens;         /* optional device int32 (N): valid keys, clamped to 1 .. Tk    */
+  float* out;                /* (Tq, n_pad, ld_out): forward writes it, backward reads it    */
+  float* lse;                /* (Tq, n_pad, heads): forward writes it when not NULL,         */
+                             /*   backward reads it                                          */
+  const float* dout;         /* backward: (Tq, n_pad, ld_out)                                */
+  float* dq;                 /* backward: (Tq, n_pad, ld_q)                                  */
+  float* dkv;                /* backward: (Tk, n_pad, ld_kv), dK | dV                        */
+} asr_attn_cross_args;
+/* Workspace of asr_attn_cross_bwd (D of every query row); 0 for a refused geometry.         */
+size_t asr_attn_cross_workspace_bytes(const asr_attn_cross_args* a);
+int asr_attn_cross_fwd(const asr_attn_cross_args* a, asr_stream_t stream);
+int asr_attn_cross_bwd(const asr_attn_cross_args* a, void* workspace, size_t ws_bytes,
+                       asr_stream_t stream);
+/* THE DECODER'S JOINT + CROSS-ENTROPY.  ctx, q (U1, n_pad, J) time-major    */
+/* float32 (the attention context and the predictor's query projection), J a */
+/* multiple of 4; W_out (J, C) row-major, b_out (C); U1 = l_max + 1 label    */
+/* positions, U_n = label_len[n] clamped to 0 .. l_max.  Per row (u, n),     */
+/* n < N, 0 <= u <= U_n:                                                     */
+/*   h = tanh(ctx + q),  z = h W_out + b_out,  lp = log_softmax(z),          */
+/*   target = labels[n, u] for u < U_n (a value outside 0 .. C - 2 counts as */
+/*   C - 1), EOS = C - 1 for u = U_n (the class the CTC models give blank),  */
+/*   loss[n] = sum_u -((1 - eps) lp[target] + eps mean_c lp[c]),  eps in     */
+/*   [0, 1) the label smoothing; natural log; rows added in ascending u.     */
+/* d_ctx, d_q (both WRITTEN with the same values: d loss / d(ctx + q)),      */
+/* dW_out, db_out = grad_scale * d sum_n loss_n / d(.); rows u > U_n and     */
+/* rows n >= N of d_ctx / d_q are exact zeros.  The four gradient pointers   */
+/* are all NULL (loss only) or all set.  dW_out / db_out: every workgroup    */
+/* sums its rows in a fixed order into a partial (J + 1, 16 / 32 / 64) slab, */
+/* the slabs are added in index order; no float atomics, the same bits on    */
+/* every run.  The workspace needs no initialisation.  ASR_ERR_INVALID       */
+/* before any device call: a NULL pointer, J outside 4 .. 512 or no multiple */
+/* of 4, C outside 2 .. 64, l_max outside 0 .. 255, U1 != l_max + 1, n_pad   */
+/* % 16 != 0 or < N, eps outside [0, 1) (the size function returns 0).       */
+size_t asr_aed_workspace_bytes(int U1, int N, int n_pad, int J, int C);
+int asr_aed_loss_grad(const float* ctx, const float* q, const float* W_out, const float* b_out,
+                      const int* labels, const int* label_len, int U1, int N, int n_pad, int J,
+                      int C, int l_max, float eps, float grad_scale, float* loss, float* d_ctx,
+                      float* d_q, float* dW_out, float* db_out, void* workspace, size_t ws_bytes,
+                      asr_stream_t stream);
+/* One iteration of label-synchronous greedy decoding for all utterances,    */
+/* one wave per utterance.  A row with finished[n] != 0 gets advance[n] = 0  */
+/* and nothing else.  Any other row evaluates the joint of ctx(n, :) and     */
+/* q(n, :) (both (n_pad, J)) and takes the first-max arg-max k.  k = EOS     */
+/* (C - 1), or decoded_len[n] >= max_labels: finished[n] = 1, advance[n] =   */
+/* 0.  Otherwise decoded[n, decoded_len[n]++] = k (dropped past cap),        */
+/* advance[n] = 1, x_next(n, :) = e_k, and the row counts as active unless   */
+/* it has just reached max_labels (then finished[n] = 1).  x_next (n < N,    */
+/* ld_next >= C - 1 columns) is 0 elsewhere.  *active = the rows still       */
+/* active AFTER this call.  finished, decoded_len: device int32 (N), zeroed  */
+/* by the caller before the first call.                                      */
+int asr_aed_greedy_step(const float* ctx, const float* q, const float* W_out,
+                        const float* b_out, int N, int n_pad, int J, int C, int max_labels,
+                        int cap, int ld_next, int* finished, int* decoded, int* decoded_len,
+                        int* advance, float* x_next, int* active, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* K7  CTC loss + gradient.  Replaces core/ctc_utils.py:60-70 ->             */
