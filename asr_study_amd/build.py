@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libasr_hip.so')
 SOURCES = ['capi.cpp', 'ctc.hip', 'beam.hip', 'frontend.hip', 'conv.hip', 'gemm.hip', 'gemm_hl.hip', 'pack.hip', 'lstm.hip', 'lstm_fwd.hip', 'lstm_bwd.hip', 'lstm_ln.hip', 'lstm_uni.hip', 'rnn.hip',
            'batchnorm.hip', 'gru.hip', 'rhn.hip', 'layernorm.hip', 'attention.hip', 'rel_attention.hip', 'cross_attention.hip', 'dwconv.hip',
-           'specaug.hip', 'rnnt.hip', 'aed.hip', 'optim.hip', 'random.hip', 'decode_host.cpp', 'comm.cpp', 'roles.cpp']
+           'specaug.hip', 'rnnt.hip', 'aed.hip', 'timestack.hip', 'optim.hip', 'random.hip', 'decode_host.cpp', 'comm.cpp', 'roles.cpp']
 ARCH = 'gfx950'
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'asr_hip.h')   # _lib.py reads it too
 

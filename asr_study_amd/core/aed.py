@@ -4,7 +4,10 @@ csrc/cross_attention.hip and csrc/aed.hip.  The two towers of cor
 
   encoder    any stage list the engine builds, ending in ``Dense(2 d_att)``: its output IS the
              [K | V] slab of the cross-attention, the bidirectional persistent BiLSTM stack
-             included (the decoder reads the whole utterance)
+             included (the decoder reads the whole utterance: at the encoder OUTPUT's frame rate,
+             the input's unless the encoder has a convolution front-end or TimeReduction stages
+             -- ``time_reduction=[[1, 2], [2, 2]]`` is the pyramid of arXiv 1508.01211; the key
+             lengths are on that axis, enc.out_lengths)
   predictor  the transducer's: bare ``LSTM(pred_hiddens)`` x ``pred_layers`` on the one-hot label
              history (a zero row is the start of the sequence), ``Dense(d_att)`` which gives Q, and
              the parameter-only ``Dense(num_classes)`` that owns ``W_out`` / ``b_out``.

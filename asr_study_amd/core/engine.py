@@ -35,7 +35,7 @@ from . import bilstm
 from . import optimizers as _opt
 from . import params as P
 from .params import _pad4
-from .stages import KINDS, Pass, _nd
+from .stages import KINDS, Pass, _nd, time_factor
 
 
 # where a Model lives when the factory is given no ``device`` (host-only tests build on 'cpu':
@@ -198,7 +198,15 @@ class Model(object):
                 nxt = self.stages[i + 1] if i + 1 < len(self.stages) else None
                 st.bias_dead = (nxt is not None and nxt.kind == 'bn' and not nxt.grouped
                                 and i not in skips)
-        self.time_strides = [st.st for st in self.stages if st.kind == 'conv' and st.st > 1]
+        # the time strides in stage order: the strided convolutions and the TimeReduction stages
+        # (K33).  _axis_of[i]: how many of them lie in front of stage i, i.e. which time axis its
+        # INPUT is on (0: the model input's); read only when the model has a TimeReduction
+        strided = [(i, st.st if st.kind == 'conv' else time_factor(st))
+                   for i, st in enumerate(self.stages)
+                   if (st.kind == 'conv' and st.st > 1) or time_factor(st)]
+        self.time_strides = [k for _, k in strided]
+        self._treduce = any(time_factor(st) for st in self.stages)
+        self._axis_of = [sum(1 for j, _ in strided if j < i) for i in range(len(self.stages))]
         self._convs = {}
         self.n_params = off = alloc.params
         self.params = torch.zeros(off, dtype=torch.float32, device=self.device)
@@ -228,6 +236,8 @@ class Model(object):
                 break
             if hasattr(st, 'oW'):
                 prev = st
+            elif time_factor(st):       # (a stacked frame has no pad columns inside)
+                prev = None
         if (prev is not None and hasattr(prev, 'Hp') and prev.Hp != prev.H
                 and getattr(prev, 'merge', 'concat') == 'concat'
                 and _nd(prev) == 2):
@@ -353,6 +363,10 @@ class Model(object):
         reads, in training and inference (None: every frame).
         in_len: device int32 lengths of the real samples on the INPUT time axis (x's frames): the
         utterances a SpecAugment stage warps and masks within, in training (None: every frame).
+        A model with a TimeReduction stage has more than one time axis behind its front-end, and
+        ceil(len / k) cannot be inverted: it takes in_len in every phase, derives the lengths of
+        every axis from it on the device (_axis_lens) and hands each stage those of its own axis
+        as fp.seq_len; without in_len (and seq_len) every frame is valid.
 
         masks: optional explicit variational-dropout masks (parity tests):
         {stage_index: (BW (2, n_pad, f_in_pad), BU (2, n_pad, Hp))}.
@@ -388,11 +402,40 @@ class Model(object):
         fp = Pass(training=training, masks=masks, need_grad=need_grad, n_valid=n_valid,
                   n_real=n_real, bn_weight=bn_weight, seq_len=seq_len, in_len=in_len,
                   n_pad=n_pad, pipe=pipe, pre={}, nb=0, stage_masks=stage_masks)
+        axes = self._axis_lens(in_len, seq_len) if self._treduce else None
         for si, s in enumerate(self.stages):
             rec = {'in': a}
+            if axes is not None:        # (a model without the stage: one seq_len, as ever)
+                fp.seq_len = axes[self._axis_of[si]]
             a = rec['out'] = KINDS[s.kind].forward(self, s, si, a, rec, fp)
             self._acts.append(rec)
         return a
+
+    def _axis_lens(self, in_len, seq_len):
+        """The device lengths on every time axis of a model with a TimeReduction stage: [input
+        axis, behind the first stride, ...], each ceil(previous / stride), computed on the device
+        from the input lengths (no host copy).  All None when no lengths are given."""
+        n = len(self.time_strides) + 1
+        if in_len is None:
+            if seq_len is not None:
+                raise ValueError(
+                    'a model with a TimeReduction stage needs in_len, the lengths on the INPUT '
+                    'time axis: the stages in front of the reduction run on a longer axis than '
+                    'seq_len, and ceil(len / k) cannot be inverted')
+            return [None] * n
+        axes = [in_len.to(torch.int32)]
+        for st in self.time_strides:
+            axes.append(torch.div(axes[-1] + (st - 1), st, rounding_mode='floor').to(torch.int32))
+        return axes
+
+    def _input_lens(self, lens):
+        """in_len of forward() for a model with a TimeReduction stage (None for any other): the
+        host or device input lengths as a device int32 tensor."""
+        if not self._treduce:
+            return None
+        if torch.is_tensor(lens):
+            return lens.to(self.device, dtype=torch.int32)
+        return torch.as_tensor(np.asarray(lens, np.int32).reshape(-1)).to(self.device)
 
     def _bn_update(self):
         """Running-moment update of every BatchNormalization stage, once per optimisation step,
@@ -543,7 +586,7 @@ class Model(object):
         """One forward + CTC + backward.  Returns per-sample CTC loss (device) and
         logits; self.grads holds d(mean ctc)/d params."""
         lab, lab_len, sl = self._prep_labels(labels, seq_len, slab.shape[0])
-        in_len = None
+        in_len = self._input_lens(seq_len)
         if self._has_specaug and training:
             # the batch's input lengths, for the SpecAugment stage (a copy like the three above)
             in_len = torch.as_tensor(np.asarray(seq_len, np.int32).reshape(-1)).to(self.device)
@@ -575,7 +618,7 @@ class Model(object):
         synchronisation: forward, CTC, BPTT, (RCCL all-reduce), clip + update, greedy
         decode for the LER metric.  Returns device tensors (ctc, decoded, lengths)."""
         self._maybe_retry_persistent()
-        in_len = sl.to(torch.int32) if self._has_specaug else None      # (input frames)
+        in_len = sl.to(torch.int32) if (self._has_specaug or self._treduce) else None   # (input frames)
         sl = self.out_lengths(sl)
         ctc, logits, sl = self.loss_and_grads_device(slab, lab, lab_len, sl, N, training=True,
                                                      n_global=N * world, in_len=in_len)
@@ -753,7 +796,8 @@ class Model(object):
         N = len(labels)
         lab, lab_len, sl = self._prep_labels(labels, lens, slab.shape[0])
         logits = self.forward(slab, training=False, need_grad=False, n_valid=N,
-                              seq_len=sl if self._needs_lens else None)
+                              seq_len=sl if self._needs_lens else None,
+                              in_len=self._input_lens(lens))
         ctc = ops.ctc_loss_grad(logits, lab, lab_len, sl, N, grad=None)
         hyps = None
         dec = dlen = None
@@ -792,7 +836,8 @@ class Model(object):
             sl = self._key_lens(self.out_lengths(lens), slab.shape[0]).astype(np.int32)
             sl = torch.as_tensor(sl).to(self.device)
         logits = self.forward(slab, training=False, need_grad=False, n_valid=N,
-                              seq_len=sl if self._needs_lens else None)
+                              seq_len=sl if self._needs_lens else None,
+                              in_len=self._input_lens(lens))
         if self.decoder is None:
             return logits[:, :N].permute(1, 0, 2).contiguous().cpu().numpy()
         if self.decoder.get('is_greedy', True):
@@ -836,7 +881,8 @@ class Model(object):
         lens = np.asarray(inputs_length).reshape(-1)
         lab, lab_len, sl = self._prep_labels(labels, lens, slab.shape[0])
         logits = self.forward(slab, training=False, need_grad=False, n_valid=N,
-                              seq_len=sl if self._needs_lens else None)
+                              seq_len=sl if self._needs_lens else None,
+                              in_len=self._input_lens(lens))
         from .ctc_utils import align_paths
         path, score = align_paths(logits, lab, lab_len, sl, N)
         sl_h = sl.cpu().numpy()

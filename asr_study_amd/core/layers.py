@@ -25,6 +25,8 @@ csrc/rel_attention.hip; ``positions='relative'`` of transformer / conformer uses
 reference counterpart either) run on csrc/dwconv.hip and make the ``conformer`` factory.
 ``SpecAugment`` (no reference counterpart) augments the input slab on csrc/specaug.hip; the
 ``spec_augment`` argument of deep_speech2 / transformer / conformer puts it behind ``Input``.
+``TimeReduction`` (no reference counterpart) stacks consecutive frames on csrc/timestack.hip; the
+``time_reduction`` argument of brsmv1 / deep_speech2 / transformer / conformer places it.
 """
 
 
@@ -755,6 +757,39 @@ class GLU(Layer):
 
     def out_features(self, f):
         return f // 2
+
+
+class TimeReduction(Layer):
+    """Time reduction by frame stacking (no reference counterpart) on csrc/timestack.hip: ``factor``
+    consecutive frames of an (N, T, F) tensor are concatenated into one frame,
+
+        y[n, to, j F + f] = x[n, to * factor + j, f]        j < factor, To = ceil(T / factor)
+
+    the pyramid step of "Listen, Attend and Spell" (arXiv 1508.01211), the time-reduction layer
+    of RNN-T encoders, and -- directly behind Input -- the stacked input frames of LSTM-CTC.  The
+    frames at or past an utterance's length (the lengths the model is called with) count as zeros,
+    so the last, partial group of an utterance is zero-filled and its valid output frames do not
+    depend on how far its batch is padded; the lengths behind the layer are ceil(len / factor).
+    No parameters; the output width is factor * F; factor is an integer in 2 .. 8.  Not built:
+    pooling (mean, max) in place of the concatenation, streaming through the layer."""
+
+    MIN_FACTOR, MAX_FACTOR = 2, 8
+
+    def __init__(self, factor, **kwargs):
+        if kwargs:
+            raise NotImplementedError('TimeReduction: unknown arguments %s' % sorted(kwargs))
+        if (isinstance(factor, bool) or int(factor) != factor
+                or not self.MIN_FACTOR <= factor <= self.MAX_FACTOR):
+            raise NotImplementedError('TimeReduction: factor %r (an integer in %d .. %d: the '
+                                      'limits of asr_time_stack_*)'
+                                      % (factor, self.MIN_FACTOR, self.MAX_FACTOR))
+        self.factor = int(factor)
+
+    def out_features(self, f):
+        return self.factor * f
+
+    def out_fc(self, x):
+        return None
 
 
 class Reshape(Layer):

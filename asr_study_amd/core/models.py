@@ -19,7 +19,7 @@ from .layers import (Input, GaussianNoise, TimeDistributed, Dense, LSTM, Bidirec
                      Dropout, Merge, merge, l2, Reshape, Convolution2D, clipped_relu, SimpleRNN,
                      Activation, BatchNormalization, GRU, RHN, LayerNormalization,
                      MultiHeadAttention, RelativeMultiHeadAttention, PositionalEncoding,
-                     DepthwiseConvolution1D, GLU, SpecAugment)
+                     DepthwiseConvolution1D, GLU, SpecAugment, TimeReduction)
 
 
 def ctc_model(inputs, output, **kwargs):
@@ -51,6 +51,11 @@ def ctc_model(inputs, output, **kwargs):
             spec.append({'type': 'merge', 'mode': layer.mode, 'skip': src[0]})
             if layer.scale != 1.0:  # (only then: the spec of every other model is unchanged)
                 spec[-1]['scale'] = layer.scale
+        elif isinstance(layer, TimeReduction):
+            # batch major, stacking k frames is Reshape((-1, k F)) of an utterance's (T, F) block:
+            # the 'treduce' variant of the kind (the key only then, as for merge)
+            spec.append({'type': 'reshape', 'target': [-1, outputs[len(spec)].features],
+                         'time_factor': layer.factor})
         elif isinstance(layer, Reshape):
             spec.append({'type': 'reshape', 'target': list(layer.target)})   # a view: no data moves
         elif isinstance(layer, Convolution2D):
@@ -184,6 +189,46 @@ def _record_context(model, context, causal_conv=False):
         model.config['kwargs']['causal_conv'] = True
 
 
+def _time_reduction(factory, time_reduction, num_layers):
+    """The ``time_reduction`` argument of a recurrent factory, [[after_layer, factor], ...], as
+    {after_layer: factor}: after_layer = 0 puts the TimeReduction in front of the first
+    recurrent layer, i behind recurrent layer i; 0 <= i < num_layers, strictly increasing."""
+    if time_reduction is None:
+        return {}
+    try:
+        pairs = [(a, f) for a, f in time_reduction]
+        ok = bool(pairs) and all(not isinstance(v, bool) and int(v) == v for p in pairs for v in p)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('%s(time_reduction=%r): None or a list of [after_layer, factor] pairs '
+                         'of integers' % (factory, time_reduction))
+    last = -1
+    for a, f in pairs:
+        if not last < a < num_layers:
+            raise ValueError('%s(time_reduction=%r): after_layer %d (0: in front of the first '
+                             'recurrent layer, i: behind layer i; 0 <= i < num_layers = %d, '
+                             'strictly increasing)' % (factory, time_reduction, a, num_layers))
+        last = a
+    return {int(a): int(f) for a, f in pairs}
+
+
+def _single_factor(factory, time_reduction):
+    """The ``time_reduction`` argument of transformer / conformer: one integer factor."""
+    if isinstance(time_reduction, bool) or not isinstance(time_reduction, int):
+        raise ValueError('%s(time_reduction=%r): None or one integer factor (the stage goes in '
+                         'front of the input projection)' % (factory, time_reduction))
+    return time_reduction
+
+
+def _record_time_reduction(model, time_reduction):
+    """... recorded in the factory record only when set (a default checkpoint keeps its bytes)."""
+    if time_reduction is not None:
+        model.config['kwargs']['time_reduction'] = (
+            int(time_reduction) if isinstance(time_reduction, int)
+            else [[int(a), int(f)] for a, f in time_reduction])
+
+
 def graves2006(num_features=26, num_hiddens=100, num_classes=28, std=.6, **kw):
     """Graves et al. 2006 (core/models.py:55-73)."""
     x = Input(name='inputs', shape=(None, num_features))
@@ -268,8 +313,17 @@ def deep_speech(num_features=81, num_classes=29, num_hiddens=2048, dropout=0.1, 
 def brsmv1(num_features=39, num_classes=28, num_hiddens=256, num_layers=5,
            dropout=0.2, zoneout=0., input_dropout=False, input_std_noise=.0,
            weight_decay=1e-4, residual=None, layer_norm=None, mi=None,
-           activation='tanh', bidirectional=True, **kw):
+           activation='tanh', bidirectional=True, time_reduction=None, **kw):
     """BRSM v1.0 (core/models.py:217-281), same defaults.
+
+    time_reduction=[[after_layer, factor], ...] (no reference counterpart, K33): a
+    TimeReduction(factor) in front of the first recurrent layer (after_layer = 0) or behind
+    recurrent layer ``after_layer`` (0 <= after_layer < num_layers, strictly increasing): the
+    layers behind it, the logits and CTC run on ceil(T / factor) frames of factor times the
+    width -- the pyramid of arXiv 1508.01211 with [[1, 2], [2, 2]], the time-reduction layer of
+    RNN-T encoders with [[2, 2]], stacked input frames with [[0, 3]].  ``inputs_length`` is mapped
+    inside the model.  With ``residual`` the stage is followed by a TimeDistributed(Dense) of the
+    recurrent width, so that the skip widths agree (no skip spans the stage).
 
     bidirectional=False (no reference counterpart, K29): every layer is a bare, unidirectional
     LSTM(num_hiddens) on csrc/lstm_uni.hip and the ``residual`` Dense is num_hiddens wide; zoneout,
@@ -282,6 +336,7 @@ def brsmv1(num_features=39, num_classes=28, num_hiddens=256, num_layers=5,
                 raise NotImplementedError('brsmv1: bidirectional=False with %s: the unidirectional '
                                           'LSTM is the plain cell only' % name)
     width = num_hiddens * 2 if bidirectional else num_hiddens
+    reduce_at = _time_reduction('brsmv1', time_reduction, num_layers)
     x = Input(name='inputs', shape=(None, num_features))
     o = x
     if input_std_noise is not None:
@@ -291,6 +346,10 @@ def brsmv1(num_features=39, num_classes=28, num_hiddens=256, num_layers=5,
     if input_dropout:
         o = Dropout(dropout)(o)
     for i, _ in enumerate(range(num_layers)):
+        if i in reduce_at:
+            o = TimeReduction(reduce_at[i])(o)
+            if residual is not None:
+                o = TimeDistributed(Dense(width, W_regularizer=l2(weight_decay)))(o)
         cell = LSTM(num_hiddens,
                     return_sequences=True,
                     W_regularizer=l2(weight_decay),
@@ -316,6 +375,7 @@ def brsmv1(num_features=39, num_classes=28, num_hiddens=256, num_layers=5,
         layer_norm=layer_norm, mi=mi, activation=activation)}
     if not bidirectional:   # (only then: default checkpoints keep their bytes)
         model.config['kwargs']['bidirectional'] = False
+    _record_time_reduction(model, time_reduction)
     return model
 
 
@@ -323,7 +383,7 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
                  conv_filters=32, conv_kernels=((11, 41), (11, 21)), conv_strides=((2, 2), (1, 2)),
                  max_value=20, dropout=0.2, weight_decay=1e-4, input_std_noise=.0,
                  batch_norm=False, rnn_type='lstm', spec_augment=False, bidirectional=True,
-                 **kw):
+                 time_reduction=None, **kw):
     """BASELINE.json configs[2]: "DeepSpeech2-style 5xBiLSTM(512) + 2 conv front-end, 80-dim
     log-mel".  NO REFERENCE COUNTERPART: the reference lists Deep Speech 2 as TODO
     (README.md:118) and its ``deep_speech`` factory (core/models.py:148-214) is dead code
@@ -360,7 +420,12 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
     bidirectional=False (with rnn_type='gru' only): every recurrent layer is a bare, unidirectional
     GRU of width num_hiddens (the deployment form of Deep Speech 2) and the Dense reads num_hiddens
     features; batch_norm False, True and 'layer' compose as above.  Such a model has no look-ahead
-    behind its convolutions: with batch_norm=False, Model.stream runs it chunk by chunk."""
+    behind its convolutions: with batch_norm=False, Model.stream runs it chunk by chunk.
+
+    time_reduction=[[after_layer, factor], ...]: brsmv1's argument -- a TimeReduction(factor) in
+    front of the first recurrent layer (0; in front of its normalisation, if any) or behind
+    recurrent layer ``after_layer``, on top of the front-end's time stride; the statistics of a
+    GRU(batch_norm=True) behind it run over the valid frames of its own, reduced axis."""
     if rnn_type not in ('lstm', 'gru'):
         raise ValueError("deep_speech2: rnn_type %r ('lstm' or 'gru')" % (rnn_type,))
     if not bidirectional and rnn_type != 'gru':
@@ -380,6 +445,7 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
                                   "a bare GRU has no sequence-wise batch normalisation")
     cell = GRU if rnn_type == 'gru' else LSTM
     cell_kw = dict(batch_norm=True) if recurrent_bn else {}
+    reduce_at = _time_reduction('deep_speech2', time_reduction, num_layers)
     x = Input(name='inputs', shape=(None, num_features))
     o = _spec_augment(x, spec_augment)
     if input_std_noise is not None:
@@ -393,7 +459,9 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
             o = norm()(o)
             o = Activation(clipped_relu(max_value))(o)
     o = Reshape((-1, o.features))(o)
-    for _ in range(num_layers):
+    for i in range(num_layers):
+        if i in reduce_at:
+            o = TimeReduction(reduce_at[i])(o)
         if batch_norm and not recurrent_bn:
             o = norm()(o)
         rec = cell(num_hiddens, return_sequences=True,
@@ -415,6 +483,7 @@ def deep_speech2(num_features=80, num_classes=28, num_hiddens=512, num_layers=5,
     if not bidirectional:   # (likewise)
         model.config['kwargs']['bidirectional'] = False
     _record_spec_augment(model, spec_augment)
+    _record_time_reduction(model, time_reduction)
     return model
 
 
@@ -454,7 +523,7 @@ def rhn(num_features=39, num_classes=28, num_hiddens=256, num_layers=5, depth=2,
 def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_layers=6,
                 d_ff=1024, dropout=0.1, conv=True, conv_filters=32,
                 conv_kernels=((11, 41), (11, 21)), weight_decay=0., spec_augment=False,
-                positions='absolute', context=None, **kw):
+                positions='absolute', context=None, time_reduction=None, **kw):
     """A CTC-trained pre-LN transformer encoder (arXiv 1706.03762, 2002.04745).  NO REFERENCE
     COUNTERPART.  conv=True: deep_speech2's front-end first -- Reshape, two Convolution2D with
     clipped ReLU (strides (2, 2) and (1, 2): time stride 2), Reshape.  Then
@@ -478,7 +547,11 @@ def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_l
     (TensorFlow's 'same' rule at stride 2), the second (kt2 - 1) // 2 strided frames; a strided
     frame t with an encoder look-ahead of A strided frames reads the input frames up to
     2 (t + A + (kt2 - 1) // 2) + kt1 - 1 - p1, which is 2 (t + A) + 16 with the default kernels
-    and an even number of input frames."""
+    and an even number of input frames.
+    time_reduction=k (2 .. 8): one TimeReduction(k) directly in front of the input projection
+    Dense(d_model): 2k x with the convolution front-end (4 x with k = 2, the papers' rate).  The
+    encoder, its positions and a ``context`` window are then in frames of the REDUCED axis (one
+    is 2k input frames), and the look-ahead stated above in strided frames multiplies by k."""
     attention = _attention_layer('transformer', positions)
     reg = l2(weight_decay)
     x = Input(name='inputs', shape=(None, num_features))
@@ -489,6 +562,8 @@ def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_l
             o = Convolution2D(conv_filters, kt, kf, subsample=(st, sf), border_mode='same',
                               activation=clipped_relu(20), W_regularizer=reg)(o)
         o = Reshape((-1, o.features))(o)
+    if time_reduction is not None:
+        o = TimeReduction(_single_factor('transformer', time_reduction))(o)
     o = TimeDistributed(Dense(d_model, W_regularizer=reg))(o)
     if positions == 'absolute':
         o = PositionalEncoding()(o)
@@ -513,13 +588,15 @@ def transformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_l
     _record_spec_augment(model, spec_augment)
     _record_positions(model, positions)
     _record_context(model, context)
+    _record_time_reduction(model, time_reduction)
     return model
 
 
 def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_layers=6,
               d_ff=1024, kernel_size=31, conv_norm='batch', dropout=0.1, conv=True,
               conv_filters=32, conv_kernels=((11, 41), (11, 21)), weight_decay=0.,
-              spec_augment=False, positions='absolute', context=None, causal_conv=False, **kw):
+              spec_augment=False, positions='absolute', context=None, causal_conv=False,
+              time_reduction=None, **kw):
     """A CTC-trained Conformer encoder (arXiv 2005.08100).  NO REFERENCE COUNTERPART.  The
     front-end and input projection of ``transformer`` (conv=True: deep_speech2's two strided
     Convolution2D; then TimeDistributed(Dense(d_model)), PositionalEncoding, Dropout), then
@@ -552,7 +629,10 @@ def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_lay
     'same'-padded Convolution2D of the front-end as ``transformer`` states it: with an encoder
     look-ahead of A strided frames the strided frame t reads the input frames up to
     2 (t + A + (kt2 - 1) // 2) + kt1 - 1 - p1.  With conv_norm='batch' the bound holds at inference only: the training statistics
-    run over all frames."""
+    run over all frames.
+    time_reduction=k (2 .. 8): one TimeReduction(k) directly in front of the input projection
+    Dense(d_model), as in ``transformer``: 2k x with the convolution front-end.  ``context``
+    windows, kernel_size and the look-ahead are then in frames of the REDUCED axis."""
     if conv_norm not in ('batch', 'layer'):
         raise ValueError("conformer(conv_norm=%r): 'batch' or 'layer'" % (conv_norm,))
     attention = _attention_layer('conformer', positions)
@@ -565,6 +645,8 @@ def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_lay
             o = Convolution2D(conv_filters, kt, kf, subsample=(st, sf), border_mode='same',
                               activation=clipped_relu(20), W_regularizer=reg)(o)
         o = Reshape((-1, o.features))(o)
+    if time_reduction is not None:
+        o = TimeReduction(_single_factor('conformer', time_reduction))(o)
     o = TimeDistributed(Dense(d_model, W_regularizer=reg))(o)
     if positions == 'absolute':
         o = PositionalEncoding()(o)
@@ -602,6 +684,7 @@ def conformer(num_features=80, num_classes=28, d_model=256, num_heads=4, num_lay
     _record_spec_augment(model, spec_augment)
     _record_positions(model, positions)
     _record_context(model, context, causal_conv)
+    _record_time_reduction(model, time_reduction)
     return model
 
 
@@ -613,7 +696,10 @@ def transducer(num_features=80, num_classes=28, encoder='lstm', num_hiddens=512,
     deep_speech2 form) or 'conformer' (which takes ``context=`` and ``causal_conv=``), each with
     its final Dense ``joint_dim`` wide instead of the classes; further keyword arguments go to
     that factory (``bidirectional=True`` is allowed for training: only streaming needs a bounded
-    context).  The predictor is ``pred_layers`` bare LSTM(pred_hiddens), Dense(joint_dim), on the
+    context; ``time_reduction=[[2, 2]]`` -- for 'conformer' an integer -- shortens the encoder
+    output and with it the T x U lattice of the loss and the frames the greedy decode walks:
+    ``inputs_length`` is mapped to the reduced axis inside the encoder).  The predictor is
+    ``pred_layers`` bare LSTM(pred_hiddens), Dense(joint_dim), on the
     one-hot rows of the label history; the joint is tanh(f_t + g_u) W_out + b_out over the
     ``num_classes`` classes (blank last), like the CTC models' output."""
     from .transducer import TransducerModel
@@ -666,8 +752,10 @@ def aed(num_features=80, num_classes=28, encoder='blstm', num_hiddens=512, num_l
     'blstm' (brsmv1, bidirectional: the persistent BiLSTM stack), 'lstm' (brsmv1's unidirectional
     stack), 'gru' (deep_speech2 with rnn_type='gru'), 'conformer' or 'transformer', each with its
     final Dense ``2 d_att`` wide: the [K | V] of the decoder's cross-attention; further keyword
-    arguments go to that factory.  The predictor is ``pred_layers`` bare LSTM(pred_hiddens),
-    Dense(d_att) = the queries, on the one-hot rows of the label history; the output layer is
+    arguments go to that factory: ``time_reduction=[[1, 2], [2, 2]]`` makes the 'blstm' encoder the
+    pyramid of arXiv 1508.01211 (an integer for 'conformer' / 'transformer'), and the decoder
+    then attends over the reduced frames, with key lengths on that axis.  The predictor is
+    ``pred_layers`` bare LSTM(pred_hiddens), Dense(d_att) = the queries, on the one-hot rows of the label history; the output layer is
     tanh(ctx_u + q_u) W_out + b_out over the ``num_classes`` classes, EOS last (where the CTC
     models have blank).  ``label_smoothing`` is the eps of the cross-entropy; ``max_labels``
     (default 255) caps the greedy decode."""

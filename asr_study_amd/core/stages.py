@@ -15,6 +15,10 @@ a spec ``type`` to a ``Kind`` of three plain functions, and ``Model._layout`` / 
 fp: training, masks, need_grad, n_valid, n_real, bn_weight, seq_len, in_len, n_pad, pipe, pre,
 nb (BiLSTM stages seen so far) and stage_masks(i); bp: T, n_pad, rows, n_ref, split, split_side,
 overlap, reduce_now, pending, skip_grads, flush_side(), reduce_async() and, per stage, first.
+In a model with a TimeReduction stage (the 'treduce' variant of 'reshape', below) the time axis
+changes in mid-stack: fp.seq_len is then, for every stage, the lengths on the axis that stage
+runs on (``Model.forward`` derives them from in_len by the chain of strides), and the stage's
+backward handler sets bp.T / bp.rows to its input's frames for the stages below.
 
 The further fields of a ``Kind`` are the facts the engine reduces over the stage list instead of
 keeping lists of kinds: ``mask_shape(s, n_pad)`` (the shape of B_U, for a kind that takes
@@ -25,7 +29,7 @@ workspaces carry timeout words of their own).  Whether a stage is the first trai
 
 A VARIANT of a kind is a stage of that kind told by an attribute only it carries (``relative`` and
 ``window`` on 'mha'; ``directions`` = 1 on 'bigru' and on 'bilstm': a bare, unidirectional GRU
-or LSTM).  The direction count of a recurrent stage is ``_nd(s)``, the one reader of that
+or LSTM; ``time_factor`` on 'reshape': TimeReduction, the one reshape that moves data).  The direction count of a recurrent stage is ``_nd(s)``, the one reader of that
 attribute: the 'bigru' handlers and the GEMM helpers of the recurrent kinds take it as a number
 and serve both forms, the 'bilstm' handlers hand a one-direction stage to ``_lstm_uni_*``, which
 use the same helpers.  A variant may stream where its kind does not:
@@ -122,7 +126,74 @@ def _dropout_backward(m, s, si, rec, da, bp):
 # --------------------------------------------------------------------------- reshape, specaug
 def _reshape_build(m, s, st, width):
     s.target = [int(v) for v in st['target']]
+    if st.get('time_factor'):       # (only then: the stages of every other model are unchanged)
+        return _treduce_build(m, s, st, width)
     return width
+
+
+# TimeReduction (K33, csrc/timestack.hip) is the 'treduce' VARIANT of the reshape kind: batch
+# major, stacking k frames IS keras' Reshape((-1, k F)) of the (T, F) block of an utterance; in
+# the time-major slab it moves data, and it changes the time axis.  ``time_factor(s)`` is the one
+# reader of the attribute ``time_factor``, which only a variant stage carries.
+def time_factor(s):
+    """k of a TimeReduction stage, 0 for every other stage."""
+    return getattr(s, 'time_factor', 0) if s.kind == 'reshape' else 0
+
+
+def _refuse_behind_treduce(m, what, why):
+    if any(time_factor(p) for p in m.stages):
+        raise ValueError('%s behind a TimeReduction stage: %s' % (what, why))
+
+
+def _treduce_build(m, s, st, width):
+    # the stage changes the TIME axis, so what cannot cross it is refused when the model is built
+    # (here, in _merge_build, _conv_build and _specaug_build)
+    f_real, f_pad = width
+    k = int(st['time_factor'])
+    lo, hi = ops.TIME_STACK_FACTORS
+    if not lo <= k <= hi:
+        raise NotImplementedError('TimeReduction: factor %d (in %d .. %d: the limits of '
+                                  'asr_time_stack_*)' % (k, lo, hi))
+    if s.target != [-1, k * f_real]:
+        raise ValueError('TimeReduction(%d) of %d features: target %r' % (k, f_real, s.target))
+    if not np.array_equal(m._real_rows(s), np.arange(f_real)):
+        raise NotImplementedError(
+            'TimeReduction behind a layer whose two directions are padded apart (%d features in '
+            '%d columns): the stacked frame takes the leading columns only; use a hidden width '
+            'that is a multiple of 4' % (f_real, f_pad))
+    s.time_factor = k
+    return k * f_real, _pad4(k * f_real)
+
+
+def _reshape_forward(m, s, si, a, rec, fp):
+    """A view -- or, TimeReduction: y[to] = [x[to k], .., x[to k + k - 1]] behind the length mask
+    of the stage's OWN time axis (fp.seq_len: Model.forward hands every stage of such a model
+    the lengths of the axis it runs on).  Nothing but the input shape is kept for the backward
+    pass, which is the transpose of a copy."""
+    k = time_factor(s)
+    if not k:
+        return a
+    a = a.contiguous()
+    T, n_pad, _ = a.shape
+    N = min(fp.n_real, n_pad)
+    rec.update(shape=tuple(a.shape), N=N, lens=fp.seq_len)
+    out = m._buf('treduce%d' % si, (ops.time_stack_frames(T, k), n_pad, s.f_out_pad))
+    return ops.time_stack_fwd(a, out, N, s.f_in, k, lens=fp.seq_len)
+
+
+def _reshape_backward(m, s, si, rec, da, bp):
+    """TimeReduction: the stages below run on the longer axis, so bp.T / bp.rows become the
+    input's.  (Work that is already queued for the side stream keeps the values it was queued
+    with: the record ``g`` of a BiLSTM stage copies them when its BPTT is launched.)"""
+    k = time_factor(s)
+    if not k:
+        return None
+    T, n_pad, _ = rec['shape']
+    bp.T, bp.rows = T, T * n_pad
+    if bp.first:
+        return None
+    dx = m._buf('dtreduce%d' % si, rec['shape'])
+    return ops.time_stack_bwd(da.contiguous(), dx, rec['N'], s.f_in, k, lens=rec['lens'])
 
 
 def _specaug_build(m, s, st, width):
@@ -133,6 +204,8 @@ def _specaug_build(m, s, st, width):
                                    'time_masks', 'time_width', 'time_ratio')}
     ops.specaug_check(**s.policy)
     s.policy['mask_value'] = float(st.get('mask_value', 0.0))
+    _refuse_behind_treduce(m, 'SpecAugment', 'it augments the input data, within the lengths of '
+                           'the input time axis')
     if any(p.tensors or getattr(p, 'st', 1) > 1 for p in m.stages):
         raise ValueError(
             'SpecAugment behind a trainable or time-strided layer: it augments the '
@@ -220,6 +293,9 @@ def _merge_build(m, s, st, width):
     if s.scale != 1.0 and s.mode != 'sum':
         raise NotImplementedError("merge(scale=%r): with mode='sum' only" % s.scale)
     src = m.stages[s.skip]
+    if any(time_factor(p) for p in m.stages[s.skip + 1:]):
+        raise ValueError('merge: the skip connection spans a TimeReduction stage: its two inputs '
+                         'would be on different time axes; put the merge on one side of the stage')
     if (src.f_out, src.f_out_pad) != (f_real, f_pad):
         raise ValueError('merge: widths differ (%d vs %d)' % (src.f_out, f_real))
     s.coef = 1.0 if s.mode == 'sum' else 0.5
@@ -293,6 +369,9 @@ def _conv_build(m, s, st, width):
                          '(asr_conv2d_* keeps one plane shift per time tap)' % s.kt)
     if s.st < 1 or s.sf < 1:
         raise ValueError('conv stage: strides must be >= 1')
+    _refuse_behind_treduce(m, 'a conv stage', 'the convolution front-end reads the (time, '
+                           'frequency) image of the input, and a stacked frame is k frames of it '
+                           'side by side')
     if s.st > 1 and any(p.tensors for p in m.stages):
         raise ValueError(
             'conv stage with time stride %d behind a trainable stage: asr_conv2d_dgrad '
@@ -679,6 +758,10 @@ def stream_check(m, s, si):
     kind = KINDS[s.kind]
     if stream_variant(s) is not None:
         return None
+    if time_factor(s):
+        return ('it is a TimeReduction stage: a session counts frames on one time axis (its '
+                'chunks, rings and committed prefix are in the frames of the encoder), and the '
+                'stage changes the axis in mid-stack')
     if s.kind == 'mha':
         w = getattr(s, 'window', None)
         if w is None or w[1] < 0 or w[2] != 0:
@@ -1123,7 +1206,7 @@ def _birhn_backward(m, s, si, rec, da, bp):
 KINDS = {
     'noise': Kind(_noise_build, _noise_forward, _pass_through),
     'dropout': Kind(_noise_build, _dropout_forward, _dropout_backward),
-    'reshape': Kind(_reshape_build, _same_slab, _pass_through),
+    'reshape': Kind(_reshape_build, _reshape_forward, _reshape_backward),
     'specaug': Kind(_specaug_build, _specaug_forward, _pass_through, needs_in_len=True),
     'act': Kind(_act_build, _act_forward, _act_backward),
     'glu': Kind(_glu_build, _glu_forward, _glu_backward),

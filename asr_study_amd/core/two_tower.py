@@ -165,7 +165,8 @@ class TwoTowerModel(object):
         f = enc.forward(slab, training=training, need_grad=training, n_real=N,
                         n_valid=0 if training else N,
                         seq_len=sl if (training or enc._needs_lens) else None,
-                        in_len=in_len if (training and enc._has_specaug) else None)
+                        in_len=in_len if ((training and enc._has_specaug) or enc._treduce)
+                        else None)
         x = ops.onehot_rows(lab, lab_len, N, slab.shape[1], self.num_classes - 1,
                             out=pred._buf('onehot', (lab.shape[1] + 1, slab.shape[1],
                                                      pred.f_in_pad0)), ld=pred.f_in_pad0)
@@ -265,7 +266,8 @@ class TwoTowerModel(object):
         sl = enc._key_lens(enc.out_lengths(lens), slab.shape[0]).astype(np.int32)
         sl = torch.as_tensor(sl).to(self.device)
         f = enc.forward(slab, training=False, need_grad=False, n_valid=N,
-                        seq_len=sl if enc._needs_lens else None).contiguous()
+                        seq_len=sl if enc._needs_lens else None,
+                        in_len=enc._input_lens(lens)).contiguous()
         dec, dlen = self._greedy(f, sl, N)
         dec, dlen = dec.cpu().numpy(), dlen.cpu().numpy()
         return [dec[n, :dlen[n]].tolist() for n in range(N)]

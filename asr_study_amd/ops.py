@@ -1027,6 +1027,45 @@ def swish_bwd(x, dy, dx):
     return dx
 
 
+# --------------------------------------------------------------------------- time reduction (K33)
+TIME_STACK_FACTORS = (2, 8)     # k of asr_time_stack_* (inclusive)
+
+
+def time_stack_frames(T, k):
+    """Frames of the stacked slab: ceil(T / k)."""
+    return -(-int(T) // int(k))
+
+
+def time_stack_fwd(x, y, N, F, k, lens=None):
+    """y (ceil(T / k), n_pad, ld_out)[to, n, j F + f] = x (T, n_pad, ld_in)[to k + j, n, f] for
+    j < k, f < F where to k + j < lens[n] (device int32; None and rows n >= N: every frame), zeros
+    elsewhere, the columns k F .. ld_out included (csrc/timestack.hip)."""
+    _check_f32(x, y)
+    _check_lens(lens, N)
+    T, n_pad, ld_in = x.shape
+    To, n_pad_y, ld_out = y.shape
+    assert To == time_stack_frames(T, k) and n_pad_y == n_pad
+    L.check(L.load().asr_time_stack_fwd(_ptr(x), _ptr(lens), _ptr(y), int(T), int(N), int(n_pad),
+                                        int(F), int(ld_in), int(ld_out), int(k), _stream()),
+            'asr_time_stack_fwd')
+    return y
+
+
+def time_stack_bwd(dy, dx, N, F, k, lens=None):
+    """The transpose of time_stack_fwd: dx (T, n_pad, ld_in)[t, n, f] = dy (ceil(T / k), n_pad,
+    ld_out)[t // k, n, (t % k) F + f] for f < F where t < lens[n], zeros elsewhere.  Every
+    element of dx is written."""
+    _check_f32(dy, dx)
+    _check_lens(lens, N)
+    T, n_pad, ld_in = dx.shape
+    To, n_pad_y, ld_out = dy.shape
+    assert To == time_stack_frames(T, k) and n_pad_y == n_pad
+    L.check(L.load().asr_time_stack_bwd(_ptr(dy), _ptr(lens), _ptr(dx), int(T), int(N), int(n_pad),
+                                        int(F), int(ld_in), int(ld_out), int(k), _stream()),
+            'asr_time_stack_bwd')
+    return dx
+
+
 # --------------------------------------------------------------------------- sequence-wise BN (K18)
 def seqbn_stats_len(W):
     """Floats of a stats block: [mean_hi | mean_lo | invstd | var] (W each) + [|V|, 0, 0, 0]."""

@@ -246,6 +246,10 @@ def model_config(model):
         elif s.kind == 'posenc':
             name = nm('positionalencoding')
             add('PositionalEncoding', name, {'name': name, 'trainable': True}, [prev])
+        elif s.kind == 'reshape' and getattr(s, 'time_factor', 0):
+            name = nm('timereduction')      # (the 'treduce' variant of the kind)
+            add('TimeReduction', name, {'name': name, 'trainable': True,
+                                        'factor': int(s.time_factor)}, [prev])
         elif s.kind == 'reshape':
             name = nm('reshape')
             add('Reshape', name, {'name': name, 'trainable': True,
@@ -411,6 +415,8 @@ def topology_from_config(text):
                                          causal=c.get('causal', False))(o)
         elif kind == 'GLU':
             o = L.GLU()(o)
+        elif kind == 'TimeReduction':
+            o = L.TimeReduction(c['factor'])(o)
         elif kind == 'TimeDistributed' and c['layer']['class_name'] == 'Activation':
             o = L.TimeDistributed(L.Activation(_act_from(c['layer']['config'])))(o)
         elif kind == 'TimeDistributed' and c['layer']['class_name'] == 'Dropout':

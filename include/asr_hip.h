@@ -71,7 +71,8 @@ const char* asr_last_error(void);
  * asr_rnnt_workspace_bytes, asr_rnnt_loss_grad, asr_rnnt_greedy_step, asr_onehot_rows and
  * asr_rows_select (K31: plain scalar arguments, additions only);
  * asr_attn_cross_args, asr_attn_cross_* and the asr_aed_* entry points (K32: a new struct and
- * plain scalar arguments, additions only). */
+ * plain scalar arguments, additions only);
+ * asr_time_stack_fwd / _bwd (K33: plain scalar arguments, additions only). */
 #define ASR_HIP_ABI_VERSION 107
 int asr_version(void);
 /* Device facts the host needs for sizing persistent grids (CU count etc). */
@@ -1396,6 +1397,31 @@ int asr_aed_greedy_step(const float* ctx, const float* q, const float* W_out,
                         const float* b_out, int N, int n_pad, int J, int C, int max_labels,
                         int cap, int ld_next, int* finished, int* decoded, int* decoded_len,
                         int* advance, float* x_next, int* active, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K33 time reduction by frame stacking (csrc/timestack.hip; no reference    */
+/* counterpart): k consecutive frames of a time-major slab become one frame  */
+/* of k times the width (the pyramid of arXiv 1508.01211, the time-reduction */
+/* layer of RNN-T encoders, the stacked input frames of LSTM-CTC), and the   */
+/* exact adjoint.  x (T, n_pad, ld_in), y (To, n_pad, ld_out), To = ceil(T / */
+/* k); len_n = lens[n] (device int32, N) clamped to 0 .. T for n < N, T for  */
+/* n >= N or lens NULL:                                                      */
+/*   y[to, n, j F + f] = x[to k + j, n, f]  for j < k, f < F where           */
+/*                       to k + j < len_n, else 0; 0 in k F <= c < ld_out    */
+/*   dx[t, n, f] = dy[t / k, n, (t % k) F + f]  for f < F where t < len_n,   */
+/*                 else 0; 0 in F <= c < ld_in                               */
+/* The mask is a select: no frame >= len_n and no column >= F of x (>= k F   */
+/* of dy) is read.  Every element of y / dx is written exactly once: no      */
+/* atomics, no workspace, bit-identical repeats.  k in 2 .. 8, F >= 1 (F a   */
+/* multiple of 4: 16-byte loads; else scalar loads), ld_in >= F, ld_out >=   */
+/* k F, both multiples of 4, n_pad a multiple of 16, 1 <= N <= n_pad,        */
+/* 16-byte aligned pointers that do not alias; anything else is              */
+/* ASR_ERR_INVALID before any device call.                                   */
+/* ------------------------------------------------------------------------ */
+int asr_time_stack_fwd(const float* x, const int* lens, float* y, int T, int N, int n_pad,
+                       int F, int ld_in, int ld_out, int k, asr_stream_t stream);
+int asr_time_stack_bwd(const float* dy, const int* lens, float* dx, int T, int N, int n_pad,
+                       int F, int ld_in, int ld_out, int k, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* K7  CTC loss + gradient.  Replaces core/ctc_utils.py:60-70 ->             */
